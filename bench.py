@@ -8,7 +8,8 @@ in, pinned host buffer out, uploads / kernels / downloads overlapped) is measure
 never `value`.
 
 Workloads (BASELINE.json configs). Sizes are per GPU; frames beyond the distinct ones are repeats of them (host
-generation and compression stay in seconds), every frame's output is compared with its plaintext before anything is timed:
+generation and compression stay in seconds), every frame must decode without error to its plaintext's size before anything is
+timed (--full: its output is compared with its plaintext byte for byte):
   enwik9like  configs[1]  enwik9.zst as ONE frame per GPU. $ZGPU_DATA/enwik9 (1e9 bytes) is compressed with libzstd -3 when
               present; else the stand-in text_like(1e9 B, seed 0xE9 + gpu, V=14000) | libzstd -3 (ratio 3.19, 7630 blocks).
               N > 1: every GPU decodes its own frame (a single frame does not shard: replicas, weak scaling).
@@ -28,7 +29,11 @@ generation and compression stay in seconds), every frame's output is compared wi
 --gpus N: under torch.distributed.run (WORLD_SIZE set) there is one process per GPU and each rank's pool holds its own GPU
 (frames -> ranks by the LPT rule of the library's queue, zgpu_dist.shard_frames); without it ONE process drives N engines
 through the library's work queue (zgpu_pool_create(N): one worker thread + engine per GPU). Prints ONE JSON line (rank 0).
-The timed region lasts at least --min-seconds whatever --steps says: a step then consists of `passes_per_step` passes.
+The timed region is exactly --steps steps (one pass each) after --warmup untimed ones; `ms_per_step` is the time of one.
+
+A plain run measures the headline alone. --full adds the byte-for-byte parity gate, the host-to-host rates (e2e_GBps, the
+io::Read figures), the CPU baselines and the other configurations (each timed for at least --min-seconds); --no-e2e, --no-cpu
+and --no-other leave parts of that out. --dump-outputs DIR writes what the last timed step decoded (dump_outputs) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -269,6 +274,57 @@ def roofline(kern, A, workload, pass_ms=None, njobs=1, plaintext_bytes=None, pla
             "frac_dominant": round(ach_dom / HBM_PEAK_GBS, 6), "algorithmic_bytes": int(A), "traffic": traffic, "traffic_source": traffic_src}
 
 
+def timed_steps(pool, steps, barrier=None):
+    """the headline's timed region: exactly `steps` steps of one pass each"""
+    if barrier:
+        barrier()
+    t0 = time.perf_counter()
+    busy = [0.0] * pool.n_gpus
+    for _ in range(steps):
+        gms, _wall = pool.run()                        # blocks until every GPU of the pool has finished the pass
+        for g, v in enumerate(gms):
+            busy[g] += v
+    if barrier:
+        barrier()
+    return time.perf_counter() - t0, [b / steps for b in busy]
+
+
+DUMP_CHUNK = 1 << 20
+DUMP_SAMPLES = 1 << 21
+DUMP_SEED = 0x5A17
+
+
+def dump_outputs(pool, n_frames, out_dir, prefix=""):
+    """what the last pass left for the caller (zgpu_pool_frame / zgpu_pool_read of every staged frame) as float arrays, ~25 MB:
+    frame_status, frame_size; chunk_sum / chunk_wsum: per frame and 1 MiB piece of its plaintext the sum of the bytes and the sum of
+    byte * (i % 251 + 1), i = offset inside the piece (every byte counted, exact in float64); sample: the bytes at 2^21 positions of
+    the frames' plaintexts laid end to end, drawn with a fixed seed (sample_index: the positions)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frames = [pool.frame(k) for k in range(n_frames)]
+    sizes = np.array([f[1] for f in frames], dtype=np.int64)
+    total = int(sizes.sum())
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(total, size=DUMP_SAMPLES, replace=False)) if total > DUMP_SAMPLES else np.arange(total, dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    w = (np.arange(DUMP_CHUNK) % 251 + 1).astype(np.float64)
+    sums, wsums, sample = [], [], np.zeros(len(idx), dtype=np.float32)
+    for k, (_gpu, size, _st) in enumerate(frames):
+        a = np.frombuffer(pool.read(k, size), dtype=np.uint8) if size else np.zeros(0, dtype=np.uint8)
+        lo, hi = np.searchsorted(idx, [starts[k], starts[k + 1]])
+        sample[lo:hi] = a[idx[lo:hi] - starts[k]]
+        for p in range(0, len(a), DUMP_CHUNK):
+            piece = a[p:p + DUMP_CHUNK].astype(np.float64)
+            sums.append(piece.sum())
+            wsums.append(piece @ w[:len(piece)])
+    arrays = {"frame_status": np.array([f[2] for f in frames], dtype=np.float64), "frame_size": sizes.astype(np.float64),
+              "chunk_sum": np.array(sums, dtype=np.float64), "chunk_wsum": np.array(wsums, dtype=np.float64),
+              "sample": sample, "sample_index": idx.astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+    return sorted(prefix + name for name in arrays)
+
+
 def timed_passes(pool, steps, min_seconds, barrier=None):
     """the timed region: `steps` steps of `pps` passes each, pps chosen so that the region lasts >= min_seconds"""
     t0 = time.perf_counter()
@@ -415,11 +471,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="enwik9like", choices=["enwik9like", "realtext", "realtext1g", "silesia12", "blocks", "blocks4b", "iso"])
     ap.add_argument("--size", type=int, default=int(os.environ.get("ZGPU_BENCH_SIZE", 1000000000)), help="plaintext bytes per GPU (enwik9like)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="lower bound of the timed region (passes per step are raised to reach it)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-other", action="store_true", help="skip the runs of the other BASELINE.json configurations")
+    ap.add_argument("--min-seconds", type=float, default=2.0,
+                    help="--full: lower bound of the timed region of each other configuration (its passes are raised to reach it)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the byte-for-byte parity gate, e2e / io::Read rates, the CPU baselines and the other BASELINE.json configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step decoded as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the e2e / io::Read rates")
+    ap.add_argument("--no-other", action="store_true", help="--full without the runs of the other BASELINE.json configurations")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -472,20 +534,24 @@ def main():
 
     for _ in range(max(args.warmup, 1)):
         pool.run()
-    # parity gate on a warm run: the full plaintext of every frame must match the generator's bytes
+    # every frame decoded without error to its plaintext's size; --full: parity gate on a warm run, the full plaintext of every frame
+    # must match the generator's bytes
     import numpy as np
     used_gpus = set()
     for k, p in enumerate(staged_p):
         gpu, size, st = pool.frame(k)
         used_gpus.add(gpu)
         assert st == 0 and size == len(p), (k, st, size)
-        assert np.array_equal(np.frombuffer(pool.read(k, size), dtype=np.uint8), np.frombuffer(p, dtype=np.uint8)), "GPU output differs (frame %d)" % k
+        if args.full:
+            assert np.array_equal(np.frombuffer(pool.read(k, size), dtype=np.uint8), np.frombuffer(p, dtype=np.uint8)), "GPU output differs (frame %d)" % k
 
     # every GPU this process drives must have taken part (one frame per GPU, or at least as many sharded frames as GPUs)
     if world == 1 and len(staged_p) >= ngpu_here:
         assert len(used_gpus) == ngpu_here, ("GPUs used", sorted(used_gpus), "GPUs driven", ngpu_here)
 
-    dt, pps, busy = timed_passes(pool, args.steps, args.min_seconds, barrier)
+    dt, busy = timed_steps(pool, args.steps, barrier)
+    pps = 1
+    dumped = dump_outputs(pool, len(staged_z), args.dump_outputs, "rank%d_" % rank if world > 1 else "") if args.dump_outputs else None
     if world > 1:
         tmax = torch.tensor([dt], device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -510,8 +576,8 @@ def main():
             "config": {"workload": desc, "name": args.workload, "plaintext_bytes_job": int(D_job), "compressed_bytes_job": int(C_job),
                        "passes_per_step": pps, "plaintext_bytes_per_step": int(D_job) * pps, "ms_per_pass": round(dt / (args.steps * pps) * 1e3, 3),
                        "frames_job": len(staged_z) if world == 1 else None, "frames_gpu0_blocks": nblocks,
-                       "timed_region": "kernels only, inputs + block tables resident in HBM, output left in HBM; steps x passes_per_step "
-                                       "passes (one zgpu_pool_run each), >= %.1f s" % args.min_seconds,
+                       "timed_region": "kernels only, inputs + block tables resident in HBM, output left in HBM; one pass (one zgpu_pool_run) "
+                                       "per step",
                        "queue": ("one process, zgpu_pool_create(%d): LPT order, one worker thread + engine per GPU; GPUs used: %s" % (args.gpus, sorted(used_gpus)))
                                 if world == 1 else "one process per GPU (torch.distributed.run); frames -> ranks by zgpu_dist.shard_frames (the queue's LPT rule)",
                        "gpus_requested": args.gpus, "host_prepare_s": round(prep_s, 3), "host_affinity": affinity_note},
@@ -526,7 +592,9 @@ def main():
         if sharded:
             out["lpt"] = {"loads_compressed_bytes": loads, "bound_speedup": round(sum(job_lens) / max(loads), 3) if max(loads) else float(n_gpus)}
         pool.close(); pool = None
-        if not args.no_e2e:
+        if args.dump_outputs:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if args.full and not args.no_e2e:
             # the path a caller of the ABI sees: 1 GiB of 64 MiB frames (or the workload's own frames when they are many), host to host
             if len(staged_z) >= 8:
                 ez, ep = staged_z[:16], staged_p[:16]
@@ -538,16 +606,16 @@ def main():
             out["e2e_GBps"] = round(rate, 3)
             out["e2e_note"] = ("C ABI zgpu_pool_decode_all on %d frames (%d B of plaintext): pinned host buffer in, pinned host buffer out; host walk + H2D "
                                "+ kernels + D2H with the jobs of two engines overlapped, best of 3; per GPU" % (len(ez), sum(len(p) for p in ep)))
-        if not args.no_e2e and n_gpus == 1 and args.workload == "enwik9like" and len(staged_z) == 1:
+        if args.full and not args.no_e2e and n_gpus == 1 and args.workload == "enwik9like" and len(staged_z) == 1:
             out.update(stream_rates(local_rank, staged_z[0], staged_p[0]))
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             if affinity_before:
                 os.sched_setaffinity(0, affinity_before)         # the CPU legs use every core of the box
             # bounded CPU sample of the same workload: one frame of at most 64 MiB of plaintext
             n = min(len(staged_p[0]), 64 << 20)
             zc = staged_z[0] if n == len(staged_p[0]) else zgdata.zstd_compress(staged_p[0][:n], level=3)
             out["cpu_baseline"] = cpu_baseline(zc, n, max(1, min(os.cpu_count() or 1, 64)))
-        if not args.no_other and n_gpus == 1 and args.workload == "enwik9like":
+        if args.full and not args.no_other and n_gpus == 1 and args.workload == "enwik9like":
             # the other BASELINE.json configurations on this GPU, at one GPU's share of their size (parity gate on every frame first):
             # context for the headline, not part of `value`
             del staged_p, staged_z, per_gpu, zs_gpu

@@ -3,7 +3,8 @@
 
 Inputs (read-only): /root/reference/ruzstd/{decodecorpus_files,dict_tests,test_fixtures,fuzz/artifacts}
 Outputs: *.pack (the compressed inputs, verbatim) and *.json manifests holding, for every
-input with a known plaintext, its size and sha256 (the plaintexts themselves are not copied).
+input with a known plaintext, its size and sha256 (the plaintexts themselves are not copied);
+decodecorpus_tree.json lists every file of decodecorpus_files with its size and sha256.
 These are the vectors the reference's own tests pin.
 """
 import hashlib
@@ -44,8 +45,19 @@ def pack_pairs(src_dir, pack_name, manifest_name, extra=()):
     return len(manifest)
 
 
+def list_tree(src_dir, manifest_name):
+    """size and sha256 of every file of a reference directory: what the packs are checked against where the reference is absent"""
+    tree = {}
+    for fn in sorted(os.listdir(src_dir)):
+        data = rd(os.path.join(src_dir, fn))
+        tree[fn] = {"size": len(data), "sha256": sha(data)}
+    with open(os.path.join(HERE, manifest_name), "w") as f:
+        json.dump(tree, f, indent=0, sort_keys=True)
+
+
 def main():
     n1 = pack_pairs(os.path.join(REF, "decodecorpus_files"), "decodecorpus.pack", "decodecorpus.json")
+    list_tree(os.path.join(REF, "decodecorpus_files"), "decodecorpus_tree.json")
     dict_raw = rd(os.path.join(REF, "dict_tests", "dictionary"))
     n2 = pack_pairs(os.path.join(REF, "dict_tests", "files"), "dict_tests.pack", "dict_tests.json",
                     extra=[("dictionary", dict_raw)])

@@ -19,5 +19,6 @@ timeout 600 python tools/dev/soak_big.py 6 $S 200,640 | tail -1
 python -m pytest tests -m gpu -q -x 2>&1 | grep -v "^  File" | tail -3
 if [ "${1:-}" = profile ]; then
   SQ_ALL=0 bash tools/dev/profile.sh > gpurun_out/profile_sh.log 2>&1; tail -1 gpurun_out/profile_sh.log | cut -c1-200
-  python3 bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err; tail -c 300 gpurun_out/bench_final.json
+  LOG_DIR=${LOG_DIR:-bench_logs}; mkdir -p "$LOG_DIR"
+  python3 bench.py --full > "$LOG_DIR/bench_final.json" 2> "$LOG_DIR/bench_final.err"; tail -c 300 "$LOG_DIR/bench_final.json"
 fi
