@@ -110,6 +110,35 @@ int zgpu_decode_all(zgpu_ctx*, const uint8_t* src, size_t len, uint8_t* dst, siz
 int zgpu_decode_all_alloc(zgpu_ctx*, const uint8_t* src, size_t len, uint8_t** out, size_t* written);
 void zgpu_free(void*);
 
+/* ---- decode_all over many independent buffers in few submits --------------------------------------------------------------
+ * One zgpu_decode_all call lasts as long as one block's sequence chain plus its launches and copies (~1.6 ms host to host for a 128 KiB frame)
+ * whatever it holds; a caller with many small buffers hands them over together. Entry i is srcs[i] (lens[i] bytes: frames back to back, skippable
+ * frames allowed — what decode_all takes), its plaintext goes to dsts[i] (caps[i] bytes). Entries are walked one by one and their frames decoded
+ * together in submits of at most 512 MiB of plaintext (an entry is never split); results[i] is what zgpu_decode_all of entry i ALONE would give
+ * — it does not depend on the other entries or on their order. The return value reports engine failures only (BAD_ARG, NOMEM, HIP). */
+typedef struct {
+  uint64_t written;              /* bytes written to dsts[i]; 0 unless status == 0 */
+  int32_t status;                /* what zgpu_decode_all(ctx, srcs[i], lens[i], dsts[i], caps[i], &w) returns */
+  uint32_t nframes;              /* frames decoded in the entry (skippable frames not counted); 0 unless status == 0 */
+  /* the content checksums, reported, never enforced (the reference checks them neither in decode_all nor in its CLI): 0 unless status == 0 */
+  uint32_t checksums;            /* of those frames, the ones that carry a Content_Checksum */
+  uint32_t checksum_mismatches;  /* of those, the ones whose XXH64 (seed 0, low 32 bits) of the decoded bytes differs from it */
+  uint32_t checksum_from_data;   /* the entry's first frame: FrameDecoder::get_checksum_from_data (frame_decoder.rs:254), 0 if absent */
+  uint32_t calculated_checksum;  /* the entry's first frame: get_calculated_checksum (frame_decoder.rs:263-270); 0 if the entry has no frame */
+} zgpu_entry_result;
+/* Submits hold at most 512 MiB of plaintext (bounded from the headers) and 512 MiB of input. A submit's frames are hashed on the device (one lane
+ * per frame) when an estimate says that beats the host's copy threads (up to 16) — many short frames —, else on the host, from the bytes that come
+ * back anyway. (An Unsupported / Internal verdict of the one-submit path is decoded again alone; should the checksums of such an entry not be
+ * computable, it reports its frames with checksums = checksum_mismatches = checksum_from_data = calculated_checksum = 0.) */
+int zgpu_decode_frames(zgpu_ctx*, const uint8_t* const* srcs, const size_t* lens, uint32_t n, uint8_t* const* dsts, const size_t* caps,
+                       zgpu_entry_result* results);
+/* An upper bound of the plaintext of src (concatenated frames) from frame and block headers only — a frame's declared content size when smaller,
+ * 128 KiB per compressed block; the walk stops where a header cannot be read. What zgpu_decode_frames cuts its submits by; a caller may size
+ * caps[i] with it. Host only. */
+uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len);
+/* diagnostics: the submits the context's last zgpu_decode_frames call ran */
+uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
+
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of
  * FrameDecoder::decode_all (frame_decoder.rs:541-577), which decodes the frames of a buffer one after the other. */
@@ -143,11 +172,11 @@ int zgpu_pool_frame(zgpu_pool*, uint32_t i, int* gpu, uint64_t* out_size, uint32
 int zgpu_pool_read(zgpu_pool*, uint32_t i, uint8_t* dst, size_t cap, size_t* written);
 
 /* ---- staged form of the same path, for device-resident runs (bench / roofline) ----------------------------
- * (No content checksum on this surface: the reference feeds XXH64 as bytes are DRAINED (decode_buffer.rs:223-227,290,301) and output that
- *  stays in HBM is never drained. XXH64 is serial in 32-byte stripes — one 1 GB frame is 31 M dependent steps, ~0.5 s on a GPU lane against
- *  ~50 ms on a host core — so the checksum is computed where the bytes reach the host: zgpu_decoder_* / zgpu_frame_* / zgpu_streaming_*. A caller
- *  of zgpu_batch_* / zgpu_pool_stage that wants it reads the frame back (zgpu_batch_read) and hashes, or compares zgpu_frame_info.checksum,
- *  the value stored in the frame, with its own.) */
+ * (Content checksums: the reference feeds XXH64 as bytes are DRAINED (decode_buffer.rs:223-227,290,301), and output that stays in HBM is never
+ *  drained. XXH64 is serial in 32-byte stripes — one 1 GB frame is 31 M dependent steps, ~0.5 s on a GPU lane against ~50 ms on a host core — so
+ *  a long frame is hashed where its bytes reach the host (zgpu_decoder_* / zgpu_frame_* / zgpu_streaming_*). Many short frames are the case one
+ *  lane per frame fills the chip with: zgpu_batch_checksums hashes every frame of a synced batch on the device, and zgpu_decode_frames below reports
+ *  the checksums of the frames it decodes. zgpu_frame_info.checksum is the value stored in the frame; neither surface fails on a mismatch.) */
 typedef struct {
   uint64_t src_begin, src_end;   /* byte range of the frame in the input */
   uint64_t window_size;          /* FrameHeader::window_size  frame.rs:116-139 */
@@ -174,6 +203,9 @@ uint32_t zgpu_batch_num_blocks(const zgpu_batch*);
 uint64_t zgpu_batch_compressed_size(const zgpu_batch*);
 int zgpu_batch_frame_info(const zgpu_batch*, uint32_t frame, zgpu_frame_info* out);
 int zgpu_batch_read(zgpu_batch*, uint64_t offset, uint8_t* dst, uint64_t n);   /* D2H of plaintext bytes (waits for the run like zgpu_batch_sync) */
+/* after zgpu_batch_sync: out[f] = XXH64 (seed 0, all 64 bits) of frame f's output bytes as zgpu_batch_frame_info describes them — a frame that failed:
+ * the bytes of its good blocks — computed on the device, one lane per frame (zg_k_xxh64). n = zgpu_batch_num_frames, else ZGPU_E_BAD_ARG. */
+int zgpu_batch_checksums(zgpu_batch*, uint64_t* out, uint32_t n);
 const void* zgpu_batch_output_device(const zgpu_batch*);            /* device pointer of the plaintext (no copy); valid after zgpu_batch_sync */
 /* kernel times of the last run in ms, measured with HIP events on the ctx stream:
  * [0] tables [1] huffman [2] sequence chains [3] sequence post-processing [4] scan [5] literals/raw/rle [6] flatten

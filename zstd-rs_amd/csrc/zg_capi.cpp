@@ -138,6 +138,17 @@ int zgpu_batch_frame_info(const zgpu_batch* zb, uint32_t f, zgpu_frame_info* o) 
   return ZGPU_OK;
 }
 int zgpu_batch_read(zgpu_batch* zb, uint64_t off, uint8_t* dst, uint64_t n) { return zb->b->read_output(off, dst, n); }
+int zgpu_batch_checksums(zgpu_batch* zb, uint64_t* out, uint32_t n) {
+  // XXH64 of every frame's bytes as zgpu_batch_frame_info describes them (a failed frame: its good blocks), one lane per frame (zg_k_xxh64)
+  if (!zb || (!out && n) || n != (uint32_t)zb->b->bb.frames.size()) return ZGPU_E_BAD_ARG;
+  Batch* b = zb->b;
+  if (n && b->frame_out.size() != n) return ZGPU_E_BAD_ARG;   // (not run and synced yet)
+  std::vector<uint32_t> frames(n);
+  for (uint32_t f = 0; f < n; f++) frames[f] = f;
+  int st = b->hash_launch(frames.data(), n);
+  if (st) return st;
+  return b->hash_wait(out);
+}
 const void* zgpu_batch_output_device(const zgpu_batch* zb) { return zb->b->device_output(); }
 int zgpu_batch_timings(const zgpu_batch* zb, float* ms, int n) {
   int k = n < ZG_T_COUNT ? n : ZG_T_COUNT;
@@ -241,7 +252,9 @@ int zgpu_batch_huf_slot(zgpu_batch* zb, uint32_t slot, uint16_t* entries, int* m
 }
 
 // ---- decode_all --------------------------------------------------------------------------------------------
-static int decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written);
+static int decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written) {
+  return zg_decode_all_per_frame(c, src, len, dst, cap, written, nullptr);
+}
 int zgpu_decode_all(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written) {
   if (!c || !written || (!src && len) || (!dst && cap)) return ZGPU_E_BAD_ARG;
   *written = 0;
@@ -823,11 +836,21 @@ int zgpu_decoder_collect_to_writer(zgpu_decoder* d, zgpu_write_fn write, void* u
 
 }  // extern "C"
 
-static int decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written) {
+int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums) {
   // FrameDecoder::decode_all (frame_decoder.rs:541-577) frame by frame
   zgpu_decoder* d = nullptr;
   int st = zgpu_decoder_create(c, &d);
   if (st) return st;
+  // (sums: the content checksums of the frames decoded, as zgpu_decode_frames reports them — the decoder hashes what is drained)
+  auto note = [&]() {
+    if (!sums) return;
+    uint32_t v = 0;
+    const bool has = zgpu_decoder_checksum_from_data(d, &v) != 0;
+    const uint32_t calc = zgpu_decoder_calculated_checksum(d);
+    if (sums->nframes == 0) { sums->first_data = has ? v : 0u; sums->first_calc = calc; }
+    sums->nframes++;
+    if (has) { sums->checksums++; if (v != calc) sums->mismatches++; }
+  };
   d->drain_rule = ZG_DRAIN_DECODE_ALL;   // one decode_blocks(All) per frame stands for the reference's rounds of UptoBytes(1 MiB) + read(): same verdicts
   size_t p = 0, total = 0;
   while (p < len) {
@@ -865,12 +888,14 @@ static int decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uin
       }
       d->drain_rule = ZG_DRAIN_DECODE_ALL;
       if (st) break;
+      note();
       continue;
     }
     p += used;
     if (st) break;
     total += zgpu_decoder_read(d, dst + total, cap - total);
     if (zgpu_decoder_can_collect(d) != 0) { st = ZGPU_E_TARGET_TOO_SMALL; break; }
+    note();
   }
   zgpu_decoder_destroy(d);
   if (!st) *written = total;

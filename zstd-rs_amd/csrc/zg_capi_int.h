@@ -20,6 +20,7 @@ struct ZgDict {   // Dictionary (decoding/dictionary.rs:12-37), tables in the en
 struct zgpu_ctx {
   zg::Engine* eng = nullptr;
   std::map<uint32_t, ZgDict> dicts;   // FrameDecoder::dicts (frame_decoder.rs:82)
+  uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
   std::string err;
 };
 
@@ -61,3 +62,11 @@ bool zg_stream_checksum_from_data(const zg::StreamCore* c, uint32_t* out);
 uint32_t zg_stream_calculated_checksum(zg::StreamCore* c);
 uint64_t zg_stream_host_bytes(const zg::StreamCore* c);
 size_t zg_stream_take(zg::StreamCore* c, uint8_t* dst, size_t n);   // n <= can_collect: bytes that are buffered already
+
+// (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); sums, if given, collects the
+// content checksums of the frames it decoded (zgpu_decode_frames)
+struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0; };
+int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums);
+// (zg_stream.cpp) the process-wide cache of pinned host blocks the streams use; nullptr if none can be had
+void* zg_pinned_get(size_t n);
+void zg_pinned_put(void* p);

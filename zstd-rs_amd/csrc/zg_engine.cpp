@@ -1,6 +1,7 @@
 // zg_engine.cpp — see zg_engine.h. Compiled by hipcc as host code.
 #include "zg_engine.h"
 #include <stdlib.h>
+#include <algorithm>
 #include <string.h>
 
 namespace zg {
@@ -110,6 +111,8 @@ Tuning Tuning::from_env() {
   num("ZGPU_SWEEP_GROUP", &t.sweep.group, true);
   num("ZGPU_SWEEP_HEAD_LDS", &t.sweep.head_lds, false);
   num("ZGPU_SWEEP_HEAD_NB", &t.sweep.head_nbatch, true);
+  { const char* e = getenv("ZGPU_FRAMES_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.frames_submit_bytes = (uint64_t)atoll(e); }
+  { const char* e = getenv("ZGPU_HASH_DEVICE_MAX"); if (e && atoll(e) >= 0) { t.hash_device_max_set = true; t.hash_device_max = (uint64_t)atoll(e); } }
 #endif
   return t;
 }
@@ -157,7 +160,7 @@ void Engine::recycle(Scratch* s) {
   else { s->release(); delete s; }
 }
 
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info) {
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
   // FrameDecoder::decode_all (frame_decoder.rs:541-577): concatenated frames, skippable frames skipped;
   // the first error ends the walk (the reference returns it).
   size_t p = 0;
@@ -181,7 +184,7 @@ int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuild
     FrameInfo fi;
     fi.header = h;
     fi.window_size = w;
-    fi.src_begin = p;
+    fi.src_begin = base + p;
     p += c;
     bb->begin_frame(w, kHist, 0);
     for (;;) {
@@ -190,7 +193,7 @@ int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuild
       if ((st = read_block_header(src + p, &bh))) break;
       p += 3;
       if (len - p < bh.content_size) { st = ZG_FAILED_READ_BLOCK_BODY; break; }
-      st = bb->add_block(bh, src + p, p);
+      st = bb->add_block(bh, src + p, base + p);
       p += bh.content_size;
       fi.nblocks++;
       if (st) break;
@@ -204,7 +207,7 @@ int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuild
         break;
       }
     }
-    fi.src_end = p;
+    fi.src_end = base + p;
     fi.host_status = st;
     info->push_back(fi);
     if (st) return st;
@@ -254,6 +257,34 @@ int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out) {
   return ZG_OK;
 }
 
+uint64_t plaintext_bound(const uint8_t* src, size_t len) {
+  uint64_t total = 0;
+  size_t p = 0;
+  while (p < len) {
+    FrameHeader h;
+    size_t c;
+    uint32_t sm = 0, sl = 0;
+    int st = read_frame_header(src + p, len - p, &h, &c, &sm, &sl);
+    if (st == ZG_SKIP_FRAME) { p += c; if ((size_t)sl > len - p) break; p += sl; continue; }
+    if (st) break;
+    p += c;
+    uint64_t fb = 0;
+    bool ok = false;
+    while (len - p >= 3) {
+      BlockHeader bh;
+      if (read_block_header(src + p, &bh)) break;
+      p += 3;
+      fb += bh.type == ZG_BT_COMPRESSED ? (uint64_t)kMaxBlockSize : (uint64_t)bh.decompressed_size;
+      if (len - p < bh.content_size) break;
+      p += bh.content_size;
+      if (bh.last) { ok = true; if (h.content_checksum()) p += len - p < 4 ? len - p : 4; break; }
+    }
+    total += h.has_fcs() && h.frame_content_size < fb ? h.frame_content_size : fb;
+    if (!ok) break;
+  }
+  return total;
+}
+
 Batch::~Batch() {
   // a run uses all three of the engine's streams (Huffman chain and sweep heads on the second, the ramped chain on the third) and
   // joins them by events only when it reaches its end: nothing may be in flight on any of them when the buffers go back
@@ -264,6 +295,7 @@ Batch::~Batch() {
     (void)hipStreamSynchronize(eng->stream5_);                      // (the second half of a download)
     eng->recycle(sc);
   }
+  if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
 }
 
 void FrameState::reset() {
@@ -395,6 +427,28 @@ int Engine::prepare(const uint8_t* src, size_t len, Batch** out) {
   b->eng = this;
   b->src_len = len;
   b->parse_status = parse_frames(src, len, max_window, &b->bb, &b->info);
+  b->all_declared = !b->info.empty();
+  for (const FrameInfo& fi : b->info) {
+    if (!fi.header.has_fcs()) { b->all_declared = false; break; }
+    b->declared_total += fi.header.frame_content_size;
+  }
+  if (!b->all_declared || b->declared_total > (1ull << 40)) { b->all_declared = false; b->declared_total = 0; }
+  return upload(b, src, len, out);
+}
+
+int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
+                            std::vector<int>* walk, std::vector<uint32_t>* first_frame) {
+  Batch* b = new Batch();
+  b->eng = this;
+  b->src_len = len;
+  walk->assign(n, 0);
+  first_frame->assign(n + 1, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    (*first_frame)[i] = (uint32_t)b->info.size();
+    (*walk)[i] = parse_frames(src + off[i], elen[i], max_window, &b->bb, &b->info, off[i]);
+    if (!b->parse_status) b->parse_status = (*walk)[i];
+  }
+  (*first_frame)[n] = (uint32_t)b->info.size();
   b->all_declared = !b->info.empty();
   for (const FrameInfo& fi : b->info) {
     if (!fi.header.has_fcs()) { b->all_declared = false; break; }
@@ -953,6 +1007,39 @@ int Batch::read_output(uint64_t off, uint8_t* dst, uint64_t n) {
     ZG_HIP(hipStreamSynchronize(eng->stream2_));
     if (n > h) ZG_HIP(hipStreamSynchronize(eng->stream5_));
   }
+  return ZG_OK;
+}
+int Batch::hash_launch(const uint32_t* frames, uint32_t n) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  hash_n_ = 0;
+  if (!n) return ZG_OK;
+  if (!synced) return ZG_BAD_ARG;
+  // longest first: the 64 lanes of a wave get ranges of similar length (a wave lasts as long as its longest lane), and the longest waves start first
+  std::vector<ZgHashRange> r(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t f = frames[i];
+    if (f >= frame_out.size()) return ZG_BAD_ARG;
+    r[i].off = frame_out[f].out_base; r[i].len = frame_out[f].out_size; r[i].slot = i; r[i].pad = 0;
+    if (r[i].len && (r[i].off > dev.dst_cap || r[i].len > dev.dst_cap - r[i].off)) return ZG_INTERNAL;   // (never: sync() trims, it does not grow)
+  }
+  std::stable_sort(r.begin(), r.end(), [](const ZgHashRange& a, const ZgHashRange& b) { return a.len > b.len; });
+  const size_t rb = (size_t)n * sizeof(ZgHashRange);
+  int st = d_hash_.reserve(rb + (size_t)n * 8);
+  if (st) return st;
+  hipStream_t s = eng->stream_;
+  ZG_HIP(hipMemcpyAsync(d_hash_.p, r.data(), rb, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (r is pageable and goes out of scope)
+  zg_launch_xxh64(dev.dst, d_hash_.as<ZgHashRange>(), (uint64_t*)((uint8_t*)d_hash_.p + rb), n, s);
+  ZG_HIP(hipGetLastError());
+  hash_n_ = n;
+  return ZG_OK;
+}
+int Batch::hash_wait(uint64_t* out) {
+  if (!hash_n_) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  ZG_HIP(hipStreamSynchronize(eng->stream_));
+  ZG_HIP(hipMemcpy(out, (uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange), (size_t)hash_n_ * 8, hipMemcpyDeviceToHost));
+  hash_n_ = 0;
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

@@ -117,6 +117,9 @@ struct Tuning {
   int seq_packed = -1;             // ZGPU_SEQ_PACKED: zg_k_seq's table entries — -1 (default): packed (16 bits, three workgroups per CU) when the submit has more
                                    // blocks with sequences than one round holds, else unpacked; 0 / 1: never / always
   ZgSweepTuning sweep;             // ZGPU_SWEEP_MODE / _NB / _GROUP / _HEAD_LDS
+  uint64_t frames_submit_bytes = 0;  // ZGPU_FRAMES_SUBMIT_BYTES: plaintext (and input) per submit of zgpu_decode_frames (0: the library's constant; tests force several submits)
+  bool hash_device_max_set = false;  // ZGPU_HASH_DEVICE_MAX: longest frame zgpu_decode_frames hashes on the device (measurement of the threshold)
+  uint64_t hash_device_max = 0;
   static Tuning from_env();
 };
 
@@ -161,6 +164,10 @@ class Batch {
   int read_output(uint64_t off, uint8_t* dst, uint64_t n);   // D2H
   int read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s);
   const uint8_t* device_output() const { return dev.dst; }
+  // after sync(): XXH64 (seed 0) of the output bytes of frames[0 .. n) as sync() left them ([out_base, out_base + out_size): a failed frame's
+  // good blocks), one lane per frame (zg_k_xxh64), enqueued on the engine's first stream; hash_wait() waits and writes digest i of frames[i]
+  int hash_launch(const uint32_t* frames, uint32_t n);
+  int hash_wait(uint64_t* out);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -183,6 +190,8 @@ class Batch {
   bool ran = false;
   uint32_t epoch_ = 0;                   // runs of this batch so far (the flatten's per-unit flags carry it)
   FrameState* fs = nullptr;              // streaming submit: the frame state this run reads from / writes into
+  DevBuf d_hash_;                        // hash_launch: the ranges, then the digests
+  uint32_t hash_n_ = 0;
 };
 
 class Engine {
@@ -192,6 +201,10 @@ class Engine {
   uint64_t max_window = kDefaultMaxWindow;
   // Walk `len` bytes of concatenated frames (decode_all semantics, frame_decoder.rs:541-577), upload everything.
   int prepare(const uint8_t* src, size_t len, Batch** out);
+  // n independent entries that lie back to back in src (entry i at off[i], len[i] bytes): each is walked on its own with decode_all's rule
+  // (parse_frames), its frames appended to ONE submit. walk[i] = the entry's walk status, its frames are [first_frame[i], first_frame[i + 1]).
+  int prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
+                      std::vector<int>* walk, std::vector<uint32_t>* first_frame);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes
@@ -231,7 +244,8 @@ class Engine {
 };
 
 // Host-only walk of concatenated frames into a BatchBuilder (no GPU involved; unit-tested on CPU).
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info);
+// base: offset of src in the buffer that will be uploaded (block bodies and FrameInfo::src_begin / src_end are counted from there)
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base = 0);
 int parse_block_run(const uint8_t* src, size_t len, uint64_t window, bool has_checksum, const uint32_t hist[3], uint32_t carry_mask,
                     uint32_t max_blocks, BatchBuilder* bb, std::vector<FrameInfo>* info, size_t* consumed, bool* saw_last);
 // Byte ranges of the frames (and skippable frames) of a buffer, by walking frame and block headers only: what a work queue
@@ -239,5 +253,8 @@ int parse_block_run(const uint8_t* src, size_t len, uint64_t window, bool has_ch
 // far stay valid).
 struct FrameSpan { uint64_t begin, end; uint64_t content_size; bool has_content_size; bool skippable; };
 int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out);
+// Upper bound of the plaintext of a buffer of concatenated frames from frame and block headers only (a frame's declared content size when it
+// is smaller; a compressed block counts 128 KiB). Tolerant: the walk stops where a header cannot be read and returns what it found so far.
+uint64_t plaintext_bound(const uint8_t* src, size_t len);
 
 }  // namespace zg

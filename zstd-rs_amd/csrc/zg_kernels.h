@@ -37,3 +37,6 @@ void zg_launch_lz(const ZgBatchDev& d, hipStream_t s);
 void zg_launch_partial(const ZgBatchDev& d, hipStream_t s, uint32_t frame, uint32_t block, uint32_t nexec, bool lits_of_next, uint32_t limit);   // what the reference's buffer holds of a block whose sequence execution failed (Batch::sync, runs of one frame)
 void zg_launch_exact(const ZgBatchDev& d, hipStream_t s, uint32_t drain_rule);   // zg_exact.h: the reference's DecodeBuffer bookkeeping, exactly (rare path, Batch::sync)
 void zg_launch_calib(const void* src, void* dst, uint64_t bytes, hipStream_t s);
+// zg_k_xxh64: XXH64 (seed 0) of byte ranges of a batch's output, one lane per range; out[slot] = digest. ranges are sorted by length, longest first
+struct ZgHashRange { uint64_t off, len; uint32_t slot, pad; };
+void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s);

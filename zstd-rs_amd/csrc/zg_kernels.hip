@@ -32,6 +32,7 @@
 #include <stdlib.h>
 #include "zg_kernels.h"
 #include "zg_dev.h"
+#include "zg_xxh64_dev.h"
 
 #define ZG_SEQ_G 16       // blocks per workgroup (four lanes per block in either wave) in zg_k_seq: 16 x (2.5 KiB + 1.25 KiB tables + ring + records) in LDS -> 2 workgroups per CU
 #define ZG_LZ_T 256       // threads per frame in zg_k_lz
@@ -1768,6 +1769,20 @@ void zg_launch_calib(const void* src, void* dst, uint64_t bytes, hipStream_t s) 
   hipLaunchKernelGGL(zg_k_calib_copy4, dim3(2048), dim3(256), 0, s, (const uint32_t*)src, (uint32_t*)dst, bytes / 4);
   hipLaunchKernelGGL(zg_k_calib_gather<uint32_t>, dim3(2048), dim3(256), 0, s, (const uint32_t*)src, (uint32_t*)dst, bytes / 4, bytes / 64);
   hipLaunchKernelGGL(zg_k_calib_gather<uint64_t>, dim3(2048), dim3(256), 0, s, (const uint64_t*)src, (uint32_t*)dst, bytes / 8, bytes / 64);
+}
+
+// XXH64 (seed 0) of n byte ranges of a batch's output, one lane per range (zg_xxh64_dev.h: the four accumulators in registers, 16-byte loads of
+// the next stripe in flight while one stripe is mixed; no LDS). A wave lasts as long as its longest lane, so the host hands the ranges over sorted by length, longest first
+// (Batch::hash_launch): the 64 lanes of a wave hold ranges of similar length, and the long waves start first. Launched only by the
+// many-frame checksum calls (zgpu_decode_frames, zgpu_batch_checksums).
+__global__ void __launch_bounds__(256) zg_k_xxh64(const uint8_t* base, const ZgHashRange* r, uint64_t* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const ZgHashRange x = r[i];
+  out[x.slot] = zgx::xxh64(base + x.off, x.len, 0);
+}
+void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(zg_k_xxh64, dim3((n + 255) / 256), dim3(256), 0, s, base, ranges, out, n);
 }
 
 // ------------------------------------------------------------------------------------------------------------

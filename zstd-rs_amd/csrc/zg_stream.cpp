@@ -248,6 +248,9 @@ class GpuStreamBackend : public StreamBackend {
 
 }  // namespace
 
+void* zg_pinned_get(size_t n) { return g_pinned.get(n); }
+void zg_pinned_put(void* p) { g_pinned.put(p); }
+
 struct zgpu_streaming {
   zgpu_decoder* dec = nullptr;
   GpuStreamBackend* be = nullptr;

@@ -26,6 +26,29 @@ E_UNSUPPORTED = 80
 E_HIP = 92
 
 
+class EntryResultC(C.Structure):
+    _fields_ = [("written", C.c_uint64), ("status", C.c_int32), ("nframes", C.c_uint32), ("checksums", C.c_uint32),
+                ("checksum_mismatches", C.c_uint32), ("checksum_from_data", C.c_uint32), ("calculated_checksum", C.c_uint32)]
+
+
+class EntryResult:
+    """One entry of Context.decode_frames (zgpu_entry_result): status is what decode_all of the entry alone returns; data its plaintext
+    (None unless status == 0); the checksum fields are reported, never enforced."""
+    __slots__ = ("status", "data", "written", "nframes", "checksums", "checksum_mismatches", "checksum_from_data", "calculated_checksum")
+
+    def __repr__(self):
+        return "EntryResult(status=%d, written=%d, nframes=%d, checksums=%d, mismatches=%d)" % (
+            self.status, self.written, self.nframes, self.checksums, self.checksum_mismatches)
+
+
+def plaintext_bound(buf):
+    """zgpu_plaintext_bound: an upper bound of the plaintext of concatenated frames from frame and block headers only (a frame's declared
+    content size when smaller; a compressed block counts 128 KiB); the walk stops where a header cannot be read. Decode_frames' default
+    capacity and what it cuts its submits by. Host only (no GPU touched)."""
+    b = bytes(buf)
+    return load_library().zgpu_plaintext_bound(b, len(b))
+
+
 class FrameInfo(C.Structure):
     _fields_ = [("src_begin", C.c_uint64), ("src_end", C.c_uint64), ("window_size", C.c_uint64), ("frame_content_size", C.c_uint64),
                 ("out_base", C.c_uint64), ("out_size", C.c_uint64), ("nblocks", C.c_uint32), ("status", C.c_uint32),
@@ -59,6 +82,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
     "zgpu_decode_all", "zgpu_batch_prepare", "zgpu_batch_run", "zgpu_batch_sync", "zgpu_batch_num_frames", "zgpu_batch_num_blocks",
     "zgpu_batch_compressed_size", "zgpu_batch_frame_info", "zgpu_batch_read", "zgpu_batch_output_device", "zgpu_batch_timings",
@@ -120,6 +144,12 @@ def _declare(L):
     L.zgpu_batch_compressed_size.restype = C.c_uint64
     L.zgpu_batch_frame_info.argtypes = [vp, C.c_uint32, P(FrameInfo)]
     L.zgpu_batch_read.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
+    L.zgpu_batch_checksums.argtypes = [vp, P(C.c_uint64), C.c_uint32]
+    L.zgpu_decode_frames.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(EntryResultC)]
+    L.zgpu_plaintext_bound.argtypes = [u8p, sz]
+    L.zgpu_plaintext_bound.restype = C.c_uint64
+    L.zgpu_debug_frames_submits.argtypes = [vp]
+    L.zgpu_debug_frames_submits.restype = C.c_uint32
     L.zgpu_batch_output_device.argtypes = [vp]
     L.zgpu_batch_output_device.restype = vp
     L.zgpu_batch_timings.argtypes = [vp, P(C.c_float), C.c_int]
@@ -286,6 +316,49 @@ class Context:
     def prepare(self, src):
         return Batch(self, src)
 
+    def decode_frames(self, entries, caps=None):
+        """zgpu_decode_frames: many independent buffers (bytes, or (address, length) of memory the caller keeps alive), each what decode_all
+        takes, in few submits. caps: bytes of room per entry (default: plaintext_bound of the entry). Returns one EntryResult per entry, which is
+        what decode_all of that entry alone would give, plus the content checksums of its frames."""
+        import numpy as np
+        n = len(entries)
+        srcs, lens, keep = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), []
+        for i, e in enumerate(entries):
+            if isinstance(e, tuple):
+                srcs[i], lens[i] = e[0], e[1]
+            else:
+                b = C.c_char_p(bytes(e))                   # (no copy of a bytes object)
+                keep.append(b)
+                srcs[i], lens[i] = C.cast(b, C.c_void_p).value, len(e)
+        if caps is None:
+            caps = [self.L.zgpu_plaintext_bound(C.cast(C.c_void_p(srcs[i]), C.c_char_p), lens[i]) for i in range(n)]
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            offs[1:] = np.cumsum(np.asarray(caps, dtype=np.uint64))
+        out = np.empty(max(int(offs[-1]), 1), dtype=np.uint8)
+        base = out.ctypes.data
+        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            dsts[i], capa[i] = base + int(offs[i]), int(caps[i])
+        res = (EntryResultC * max(n, 1))()
+        st = self.L.zgpu_decode_frames(self.h, srcs, lens, n, dsts, capa, res)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        outl = []
+        for i in range(n):
+            r, e = res[i], EntryResult()
+            e.status, e.written, e.nframes = r.status, r.written, r.nframes
+            e.checksums, e.checksum_mismatches = r.checksums, r.checksum_mismatches
+            e.checksum_from_data, e.calculated_checksum = r.checksum_from_data, r.calculated_checksum
+            o = int(offs[i])
+            e.data = out[o:o + r.written].tobytes() if r.status == 0 else None
+            outl.append(e)
+        return outl
+
+    def frames_submits(self):
+        """submits the last decode_frames call ran (zgpu_debug_frames_submits)"""
+        return self.L.zgpu_debug_frames_submits(self.h)
+
 
 class Batch:
     """A run of whole frames resident on the device (zgpu_batch)."""
@@ -367,6 +440,14 @@ class Batch:
         if st:
             raise ZgpuError(st)
         return buf.raw[:n]
+
+    def checksums(self):
+        """zgpu_batch_checksums (after sync): XXH64 (seed 0, 64 bits) of every frame's output bytes, computed on the device"""
+        a = (C.c_uint64 * max(self.nframes, 1))()
+        st = self.L.zgpu_batch_checksums(self.h, a, self.nframes)
+        if st:
+            raise ZgpuError(st)
+        return [int(x) for x in a][:self.nframes]
 
     def frame_bytes(self, f):
         fi = self.frame_info(f)
