@@ -79,70 +79,19 @@ def test_corpus_frame_decoder_surface(ctx):
     d.close()
 
 
-def _oracle_blocks(z):
-    d = oracle.FrameDecoder()
-    st, c, _, _ = d.init(z)
-    assert st == 0
-    pos, blocks = c, []
-    while not d.is_finished():
-        st, used, fin = d.decode_blocks(z[pos:], oracle.STRAT_UPTO_BLOCKS, 1)
-        assert st == 0
-        pos += used
-        rec = {"type": d.last_block_type(), "hist_after": d.offset_hist()}
-        if rec["type"] == 2:
-            rec["literals"] = d.last_literals()
-            rec["sequences"] = d.last_sequences()
-            rec["huf"] = d.huf_table()
-            rec["fse"] = [d.fse_table(k) for k in range(3)]
-        blocks.append(rec)
-        if fin:
-            break
-    return blocks
-
-
 @pytest.mark.parametrize("name", ["z000000.zst", "z000033.zst", "z000059.zst", "z000088.zst"])
 def test_kernel_intermediates_match_oracle(ctx, name):
     """per kernel: Huffman tables + literals (zg_k_tables, zg_k_huf), FSE tables + sequences (zg_k_tables, zg_k_seq),
-    offset history at every block start (zg_k_scan) — against the oracle's intermediates"""
+    offset history at every block start (zg_k_scan) — against the oracle's intermediates (tests/blockcheck.py)"""
+    import blockcheck
     z = read_pack("decodecorpus.pack")[name]
-    ob = _oracle_blocks(z)
+    ob = blockcheck.oracle_blocks(z)
     b = ctx.prepare(z)
     b.run()
     b.sync()
     assert b.bad_status == 0
     assert b.nblocks == len(ob)
-    hist = [1, 4, 8]
-    for i, rec in enumerate(ob):
-        info = b.block_info(i)
-        assert info.btype == rec["type"] and info.status == 0
-        assert list(info.hist_init) == hist, (name, i)
-        hist = rec["hist_after"]
-        if rec["type"] != 2:
-            continue
-        if info.lit_type >= 2:
-            assert b.block_literals(i, info.regen_size) == rec["literals"], (name, i)
-            tab, mb = b.huf_slot(info.huf_slot)
-            oents, omb = rec["huf"]
-            assert mb == omb and [(tab[k] & 255, tab[k] >> 8) for k in range(1 << mb)] == oents
-        seqs = b.block_sequences(i, info.nseq)
-        lit_pos = out_pos = 0
-        h = list(info.hist_init)
-        for (of, ml, mdst, lit_start), (oll, oml, _o, oactual) in zip(seqs, rec["sequences"]):
-            tag, k = of >> 30, of & 0x3FFFFFFF
-            actual = of if tag == 0 else max(h[tag - 1] - k, 0)
-            assert (actual, ml, mdst, lit_start) == (oactual, oml, out_pos + oll, lit_pos), (name, i)
-            lit_pos += oll
-            out_pos += oll + oml
-        if info.nseq:
-            for k, slot in enumerate((info.ll_slot, info.of_slot, info.ml_slot)):
-                oents, olog, orle = rec["fse"][k]
-                p, logs = b.fse_slot(slot)
-                off = (0, 1024, 512)[k]
-                if orle >= 0:
-                    assert logs[k] == 0 and ((p[off] >> 20) & 63) == orle
-                else:
-                    got = [(p[off + j] & 0xFFFF, (p[off + j] >> 16) & 15, (p[off + j] >> 20) & 63) for j in range(1 << olog)]
-                    assert logs[k] == olog and got == oents, (name, i, k)
+    blockcheck.check_frame(b, 0, ob, name)
     b.close()
 
 

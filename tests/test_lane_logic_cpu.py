@@ -4,6 +4,7 @@ import hashlib
 
 import pytest
 
+import blockcheck
 import emu
 import oracle
 from golden_io import read_manifest, read_pack
@@ -39,70 +40,13 @@ def test_window_fixtures():
     assert st == 0 and hashlib.sha256(out).hexdigest() == man["window_256mib.zst"]["sha256"]
 
 
-def _oracle_blocks(z):
-    """decode block by block with the oracle, collecting its intermediates"""
-    d = oracle.FrameDecoder()
-    st, c, _, _ = d.init(z)
-    assert st == 0
-    pos, blocks = c, []
-    while not d.is_finished():
-        st, used, fin = d.decode_blocks(z[pos:], oracle.STRAT_UPTO_BLOCKS, 1)
-        assert st == 0
-        pos += used
-        rec = {"type": d.last_block_type(), "hist_after": d.offset_hist()}
-        if rec["type"] == 2:
-            rec["literals"] = d.last_literals()
-            rec["sequences"] = d.last_sequences()
-            rec["huf"] = d.huf_table()
-            rec["fse"] = [d.fse_table(k) for k in range(3)]
-        blocks.append(rec)
-        if fin:
-            break
-    return blocks
-
-
 @pytest.mark.parametrize("name", ["z000000.zst", "z000013.zst", "z000033.zst", "z000059.zst", "z000088.zst", "z000099.zst"])
 def test_intermediates_match_oracle(name):
     z = read_pack("decodecorpus.pack")[name]
-    ob = _oracle_blocks(z)
+    ob = blockcheck.oracle_blocks(z)
     e = emu.EmuBatch(z)
     assert e.nblocks == len(ob)
-    hist = [1, 4, 8]
-    for b, rec in enumerate(ob):
-        info = e.block(b)
-        assert info["btype"] == rec["type"] and info["status"] == 0
-        assert e.block_hist(b) == hist, (name, b)
-        hist = rec["hist_after"]
-        if rec["type"] != 2:
-            continue
-        if info["lit_type"] >= 2:   # Huffman literals: bytes and the table they were decoded with
-            assert e.block_literals(b, info["regen_size"]) == rec["literals"], (name, b)
-            tab, mb = e.huf_slot(info["huf_slot"])
-            oents, omb = rec["huf"]
-            assert mb == omb
-            assert [(tab[i] & 255, tab[i] >> 8) for i in range(1 << mb)] == oents
-        seqs = e.block_sequences(b, info["nseq"])
-        oseq = rec["sequences"]
-        assert len(oseq) == info["nseq"]
-        lit_pos = out_pos = 0
-        h = e.block_hist(b)
-        for (of, ml, mdst, lit_start), (oll, oml, _oof, oactual) in zip(seqs, oseq):
-            tag, k = of >> 30, of & 0x3FFFFFFF
-            actual = of if tag == 0 else max(h[tag - 1] - k, 0)
-            assert (actual, ml, mdst, lit_start) == (oactual, oml, out_pos + oll, lit_pos), (name, b)
-            lit_pos += oll
-            out_pos += oll + oml
-        if info["nseq"]:            # the three FSE tables this block decoded with
-            for k, slot in enumerate((info["ll_slot"], info["of_slot"], info["ml_slot"])):
-                oents, olog, orle = rec["fse"][k]
-                p, logs = e.fse_slot(slot)
-                off = (0, 1024, 512)[k]
-                if orle >= 0:
-                    assert logs[k] == 0 and ((p[off] >> 20) & 63) == orle
-                else:
-                    assert logs[k] == olog
-                    got = [(p[off + i] & 0xFFFF, (p[off + i] >> 16) & 15, (p[off + i] >> 20) & 63) for i in range(1 << olog)]
-                    assert got == oents, (name, b, k)
+    blockcheck.check_frame(e, 0, ob, name)
 
 
 def test_fuzz_artifacts_do_not_crash_and_agree_on_failure():
