@@ -136,8 +136,48 @@ int zgpu_decode_frames(zgpu_ctx*, const uint8_t* const* srcs, const size_t* lens
  * 128 KiB per compressed block; the walk stops where a header cannot be read. What zgpu_decode_frames cuts its submits by; a caller may size
  * caps[i] with it. Host only. */
 uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len);
-/* diagnostics: the submits the context's last zgpu_decode_frames call ran */
+/* diagnostics: the submits the context's last zgpu_decode_frames / zgpu_decode_frames_device call ran */
 uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
+
+/* ---- the same, with the plaintext left in device memory the caller owns ------------------------------------------------------
+ * For callers that want the plaintext ON the GPU (compressed shards headed for tensors, columnar pages headed for a GPU query): no download,
+ * no host copy, no upload of the caller's own. srcs are HOST pointers — the host keeps the header walk, as everywhere in this library;
+ * compressed input that is already device-resident is out of scope. device_dsts[i] is device memory on the context's device (a hipMalloc'ed
+ * block or any part of one, e.g. a torch tensor's data_ptr()), caps[i] bytes, at any alignment.
+ *  - results[i].r.status / .written / .nframes are what zgpu_decode_frames reports for the same entries: what zgpu_decode_all of entry i ALONE
+ *    returns, independent of the other entries and of their order. On status 0 the first `written` bytes of device_dsts[i] are the plaintext.
+ *    No byte of a FAILED entry's destination is written, and no byte at or behind device_dsts[i] + written ever is.
+ *  - Before any kernel is launched every destination is checked with the HIP runtime (hipPointerGetAttributes, hipMemGetAddressRange): device
+ *    memory (not host, not managed), on the context's device, [dst, dst + caps[i]) inside ONE allocation. An entry that fails the check gets
+ *    ZGPU_E_BAD_ARG and takes no part in any launch; the other entries are unaffected. (caps[i] == 0: nothing is written, nothing is checked.)
+ *    A wrong pointer becomes a status, never a GPU fault.
+ *  - The call returns after the engine's streams are synchronised: every later operation on any stream sees the bytes. The caller guarantees
+ *    that nothing in flight touches the destinations during the call (memory of a stream-ordered allocator: synchronise that stream first).
+ *    Overlapping destinations are undefined.
+ *  - Submits are cut as zgpu_decode_frames cuts them (512 MiB of plaintext bound and of input; zgpu_debug_frames_submits counts them). A submit's
+ *    plaintext lies back to back in the engine's output; ONE kernel launch per submit (zg_k_scatter) copies the frames of every successful entry
+ *    to their destinations.
+ *  - Entries the one-submit path does not serve — dictionary frames while dictionaries are registered, Unsupported / Internal verdicts — are
+ *    decoded again alone, as by zgpu_decode_frames, into a host buffer and then copied to the destination with one H2D (rare; correct first).
+ *  - Checksums: the bytes never reach the host, so frames are hashed on the device only (zg_k_xxh64, one lane per frame, ~226 MB/s per lane).
+ *    r.checksums counts the frames that carry a Content_Checksum, r.checksum_mismatches only those among the HASHED frames; the rest are
+ *    counted in checksums_unverified. Nothing fails on a mismatch. (Entries decoded alone are hashed on the host, whatever their length.) */
+typedef struct {
+  uint64_t hash_max_bytes;   /* frames whose plaintext is at most this long are hashed on the device (one lane per frame: a 4 MiB frame costs
+                                ~18 ms); longer ones are not hashed. 0: default 4 MiB */
+  uint32_t flags;            /* bit 0: hash no frame at all */
+  uint32_t pad;
+} zgpu_device_opts;
+typedef struct {
+  zgpu_entry_result r;            /* exactly the fields and meanings of zgpu_decode_frames, except as said above */
+  uint32_t checksums_unverified;  /* frames that carry a Content_Checksum and were not hashed (too long / hashing off) */
+  uint32_t first_hashed;          /* 1 if r.calculated_checksum is the first frame's real XXH64, 0 if it was not hashed (then 0) */
+} zgpu_device_entry_result;
+int zgpu_decode_frames_device(zgpu_ctx*, const uint8_t* const* srcs, const size_t* lens, uint32_t n, void* const* device_dsts, const size_t* caps,
+                              const zgpu_device_opts* opts_or_null, zgpu_device_entry_result* results);
+/* diagnostics: the context's last zgpu_decode_frames_device call — out[0] submits, [1] scatter launches, [2] bytes scattered, [3] scatter kernel
+ * microseconds (HIP events), [4] frames hashed, [5] frames not hashed, [6] entries that were decoded alone. Returns how many were written. */
+int zgpu_debug_frames_device_stats(const zgpu_ctx*, uint64_t* out, int n);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

@@ -11,7 +11,15 @@
 4. where frames are hashed: one zgpu_decode_frames call on 4096 x 128 KiB, 1024 x 512 KiB, 256 x 2 MiB and 1 x 4 MiB entries with the
    library's own choice ("auto", twice) and, in the development build (ZGPU_HASH_DEVICE_MAX), every frame on the host ("host", twice) or
    every frame on the device ("device"), in that interleaved order; and the rate of one lane alone (zgpu_batch_checksums, one 4 MiB frame).
-Prints one JSON object."""
+Prints one JSON object.
+
+  python tools/dev/small_frames.py --device [workload ...]     (default: corpus101 4096x128K 1024x512K 256x2M 128x64M)
+
+the host call (zgpu_decode_frames) against the device call (zgpu_decode_frames_device, destinations in one torch tensor) on the same entries,
+in one process and in its SECOND context (the first context of a process downloads more slowly, LABNOTES round 6): best of 5 after a warm-up
+each, interleaved; the device call with its default hashing and with hashing off (the difference is the device hash's share); and the scatter
+kernel's own time and bytes (zgpu_debug_frames_device_stats). ZGPU_SCATTER_CHUNK (read by the development build) sets the chunk size:
+`--device --dev` loads libzgpu_dev.so. Prints one JSON object."""
 import json
 import os
 import sys
@@ -39,7 +47,66 @@ def loop(ctx, entries, caps):
         ctx.decode_all(z, c)
 
 
+def device_workload(name):
+    if name == "corpus101":
+        pack, man = read_pack("decodecorpus.pack"), read_manifest("decodecorpus.json")
+        names = sorted(man)
+        return [pack[n] for n in names], [man[n]["size"] for n in names]
+    count, size = name.split("x")
+    count, size = int(count), int(size[:-1]) << (10 if size[-1] == "K" else 20)
+    d = [zgdata.text_like(size, seed=0x700 + k) for k in range(min(count, 8 if size > (8 << 20) else 16))]
+    c = [zgdata.zstd_compress(t) for t in d]
+    return [c[k % len(c)] for k in range(count)], [size] * count
+
+
+def device_main(args):
+    import torch
+    dev = "--dev" in args
+    names = [a for a in args if not a.startswith("--")] or ["corpus101", "4096x128K", "1024x512K", "256x2M", "128x64M"]
+    first = zgpu.Context(0, dev=dev)            # (the process's first context: not the one that is measured)
+    first.decode_all(zgdata.zstd_compress(b"warm" * 1000), 4000)
+    ctx = zgpu.Context(0, dev=dev)
+    out = {"scatter_chunk_env": os.environ.get("ZGPU_SCATTER_CHUNK") if dev else None}
+    for name in names:
+        ent, caps = device_workload(name)
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (c + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        ptrs = [buf.data_ptr() + o for o in offs]
+        # (address, length) entries of memory that stays alive: neither call copies the input in Python
+        keep = [zgpu.C.c_char_p(z) for z in ent]
+        raw = [(zgpu.C.cast(k, zgpu.C.c_void_p).value, len(z)) for k, z in zip(keep, ent)]
+        host = lambda: ctx.decode_frames(raw, caps)                                        # noqa: E731
+        devc = lambda: ctx.decode_frames_device(raw, ptrs, caps)                           # noqa: E731
+        devn = lambda: ctx.decode_frames_device(raw, ptrs, caps, no_hash=True)             # noqa: E731
+        rh, rd = host(), devc()
+        assert [(x.status, x.written) for x in rh] == [(x.status, x.written) for x in rd] and all(x.status == 0 for x in rd)
+        k = max(range(len(ent)), key=lambda i: caps[i])
+        assert buf[offs[k]:offs[k] + rd[k].written].cpu().numpy().tobytes() == rh[k].data
+        del rh
+        t_host = t_dev = t_nohash = None
+        for _ in range(5):                                                                 # interleaved: best of 5 each
+            t_host = min(x for x in (t_host, best(host, 1)) if x is not None)
+            t_dev = min(x for x in (t_dev, best(devc, 1)) if x is not None)
+            t_nohash = min(x for x in (t_nohash, best(devn, 1)) if x is not None)
+        devc()
+        st = ctx.frames_device_stats()
+        out[name] = {"entries": len(ent), "plain_MiB": sum(caps) / 2 ** 20, "host_call_ms": 1e3 * t_host, "device_call_ms": 1e3 * t_dev,
+                     "device_call_no_hash_ms": 1e3 * t_nohash, "hash_share_of_device_call": max(0.0, (t_dev - t_nohash) / t_dev),
+                     "speedup": t_host / t_dev, "stats": st,
+                     "scatter_GBps": st["bytes_scattered"] / max(st["scatter_us"], 1) / 1e3}
+        del buf
+    ctx.close()
+    first.close()
+    print(json.dumps(out))
+
+
 def main():
+    if "--device" in sys.argv[1:]:
+        return device_main([a for a in sys.argv[1:] if a != "--device"])
     nf = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = zgpu.Context(0)
     out = {}

@@ -112,6 +112,7 @@ Tuning Tuning::from_env() {
   num("ZGPU_SWEEP_HEAD_LDS", &t.sweep.head_lds, false);
   num("ZGPU_SWEEP_HEAD_NB", &t.sweep.head_nbatch, true);
   { const char* e = getenv("ZGPU_FRAMES_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.frames_submit_bytes = (uint64_t)atoll(e); }
+  num("ZGPU_SCATTER_CHUNK", &t.scatter_chunk, true);
   { const char* e = getenv("ZGPU_HASH_DEVICE_MAX"); if (e && atoll(e) >= 0) { t.hash_device_max_set = true; t.hash_device_max = (uint64_t)atoll(e); } }
 #endif
   return t;
@@ -296,6 +297,8 @@ Batch::~Batch() {
     eng->recycle(sc);
   }
   if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
+  if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
+  for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
 }
 
 void FrameState::reset() {
@@ -1040,6 +1043,44 @@ int Batch::hash_wait(uint64_t* out) {
   ZG_HIP(hipStreamSynchronize(eng->stream_));
   ZG_HIP(hipMemcpy(out, (uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange), (size_t)hash_n_ * 8, hipMemcpyDeviceToHost));
   hash_n_ = 0;
+  return ZG_OK;
+}
+int Batch::scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  scatter_on_ = false;
+  if (!n) return ZG_OK;
+  if (!synced) return ZG_BAD_ARG;
+  for (uint32_t i = 0; i < n; i++)   // reads stay inside the output: the lanes read [src_off, src_off + len) and nothing else (zg_scatter.h)
+    if (segs[i].len && (segs[i].src_off > dev.dst_cap || segs[i].len > dev.dst_cap - segs[i].src_off)) return ZG_INTERNAL;
+  std::vector<zgs::Chunk> ch;
+  zgs::plan_chunks(segs, n, chunk, &ch);
+  if (ch.empty()) return ZG_OK;
+  if (ch.size() > 0xFFFFFFFFull) return ZG_INTERNAL;
+  const size_t sb = (size_t)n * sizeof(zgs::Seg), cb = ch.size() * sizeof(zgs::Chunk);
+  int st = d_scatter_.reserve(sb + cb);
+  if (st) return st;
+  for (hipEvent_t& e : ev_scatter_) if (!e) ZG_HIP(hipEventCreate(&e));
+  hipStream_t s = eng->stream2_;
+  ZG_HIP(hipMemcpyAsync(d_scatter_.p, segs, sb, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipMemcpyAsync((uint8_t*)d_scatter_.p + sb, ch.data(), cb, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (the tables are pageable, and ch goes out of scope)
+  ZG_HIP(hipEventRecord(ev_scatter_[0], s));
+  zg_launch_scatter(dev.dst, d_scatter_.as<zgs::Seg>(), (const zgs::Chunk*)((uint8_t*)d_scatter_.p + sb), (uint32_t)ch.size(), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev_scatter_[1], s));
+  scatter_on_ = true;
+  return ZG_OK;
+}
+int Batch::scatter_wait(uint64_t* kernel_us, bool* launched) {
+  *kernel_us = 0;
+  *launched = scatter_on_;
+  if (!scatter_on_) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  scatter_on_ = false;
+  ZG_HIP(hipStreamSynchronize(eng->stream2_));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, ev_scatter_[0], ev_scatter_[1]));
+  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

@@ -1,5 +1,7 @@
 // zg_engine.h — one engine per (GPU, pair of HIP streams): device memory, upload of a parsed submit, the kernel
-// pipeline, and result download. Host buffers never enter the kernels; torch is not involved.
+// pipeline, and result download. Host buffers never enter the kernels. The engine allocates its own device memory with the HIP runtime and
+// knows nothing of torch; the one place where memory it does not own enters a kernel is Batch::scatter_launch, whose destinations are device
+// pointers of the caller (a torch tensor's data_ptr(), say) that zgpu_decode_frames_device has checked against the runtime's allocations.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -118,6 +120,7 @@ struct Tuning {
                                    // blocks with sequences than one round holds, else unpacked; 0 / 1: never / always
   ZgSweepTuning sweep;             // ZGPU_SWEEP_MODE / _NB / _GROUP / _HEAD_LDS
   uint64_t frames_submit_bytes = 0;  // ZGPU_FRAMES_SUBMIT_BYTES: plaintext (and input) per submit of zgpu_decode_frames (0: the library's constant; tests force several submits)
+  uint32_t scatter_chunk = 0;        // ZGPU_SCATTER_CHUNK: bytes per chunk of zg_k_scatter's plan (0: zgs::kChunkDefault; measurement of the chunk size)
   bool hash_device_max_set = false;  // ZGPU_HASH_DEVICE_MAX: longest frame zgpu_decode_frames hashes on the device (measurement of the threshold)
   uint64_t hash_device_max = 0;
   static Tuning from_env();
@@ -168,6 +171,12 @@ class Batch {
   // good blocks), one lane per frame (zg_k_xxh64), enqueued on the engine's first stream; hash_wait() waits and writes digest i of frames[i]
   int hash_launch(const uint32_t* frames, uint32_t n);
   int hash_wait(uint64_t* out);
+  // after sync(): zg_k_scatter (zg_scatter.h) copies segs[0 .. n) of the output to their destinations — device memory of the CALLER, which it
+  // has checked (zgpu_decode_frames_device) — in one launch on the engine's second stream, beside hash_launch's kernel on the first. Segments
+  // that leave the output are refused (ZGPU_E_INTERNAL) before anything is launched. chunk: bytes per chunk of the plan (0: zgs::kChunkDefault).
+  // scatter_wait() waits for the kernel; *kernel_us = its time between two HIP events, *launched = whether there was one (no bytes: none)
+  int scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk);
+  int scatter_wait(uint64_t* kernel_us, bool* launched);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -192,6 +201,9 @@ class Batch {
   FrameState* fs = nullptr;              // streaming submit: the frame state this run reads from / writes into
   DevBuf d_hash_;                        // hash_launch: the ranges, then the digests
   uint32_t hash_n_ = 0;
+  DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
+  hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
+  bool scatter_on_ = false;
 };
 
 class Engine {

@@ -6,6 +6,12 @@
 // zgpu_decode_all's logic applied to its own frames: a device error in them, else its walk error, else TargetTooSmall, else success.
 // Entries the one-submit path does not serve as zgpu_decode_all would (dictionary frames; Unsupported / Internal) are decoded again on their
 // own after the submit. Submits hold at most kFramesSubmitBytes of plaintext (bounded from the block headers); an entry is never split.
+//
+// zgpu_decode_frames_device is the same call with destinations in device memory of the caller: the walk, the verdicts, the again-list and the
+// submit cutting are shared (decode_submit, decode_entries); what differs is the sink of a submit's plaintext — the host sink downloads it and
+// copies it to the callers' buffers, the device sink leaves it where it is and lets zg_k_scatter (zg_scatter.h) copy the frames of every
+// successful entry to their destinations in one launch, and hashes on the device only. Every destination is checked against the HIP runtime's
+// allocations before anything is launched (check_device_dst): a wrong pointer becomes a status, never a GPU fault.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -15,6 +21,7 @@
 #include <utility>
 #include <vector>
 #include "zg_capi_int.h"
+#include "zg_scatter.h"
 #include "zg_xxh64_dev.h"
 
 using namespace zg;
@@ -81,38 +88,51 @@ struct Call {
   zgpu_ctx* c;
   const uint8_t* const* srcs;
   const size_t* lens;
-  uint8_t* const* dsts;
+  uint8_t* const* dsts;                            // host sink: host memory; device sink: device memory of the caller (checked)
   const size_t* caps;
-  zgpu_entry_result* res;
+  zgpu_entry_result* res;                          // host sink
   bool hash_forced;                                // (development build, ZGPU_HASH_DEVICE_MAX) frames up to hash_max on the device, no estimate
   uint64_t hash_max;
   std::vector<std::pair<uint32_t, bool>> again;   // entries decoded again on their own after the submits (true: the walk met a dictionary frame)
+  zgpu_device_entry_result* dres = nullptr;        // device sink (zgpu_decode_frames_device): its results; hash_max is the caller's, no estimate
+  bool no_hash = false;                            //   flags bit 0: hash no frame
+  uint64_t* stats = nullptr;                       //   zgpu_ctx::frames_device_stats
+  zgpu_entry_result& result(uint32_t i) const { return dres ? dres[i].r : res[i]; }
 };
 
-// one submit: the entries idx[0 .. n)
-int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
+// what a submit leaves behind for its sink
+struct Submit {
+  Staging in;
+  Batch* b = nullptr;
+  std::vector<int> walk;
+  std::vector<uint32_t> ff;       // entry j's frames are [ff[j], ff[j + 1])
+  std::vector<uint32_t> cand;     // frames of successful entries short enough to be hashed on the device
+  uint64_t down = 0;              // output bytes the successful entries reach up to
+  ~Submit() { delete b; }
+};
+
+// one submit, up to its verdicts: the entries idx[0 .. n) staged, walked, decoded; status / written / nframes of every entry it serves
+int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   std::vector<uint64_t> off(n), len(n);
   uint64_t total_in = 0;
   for (uint32_t j = 0; j < n; j++) { off[j] = total_in; len[j] = k.lens[idx[j]]; total_in += len[j]; }
-  Staging in;
+  Staging& in = u.in;
   int st = in.get(total_in);
   if (st) return st;
   parallel_for(n, total_in, 8u << 20, [&](uint32_t j) { if (len[j]) memcpy(in.p + off[j], k.srcs[idx[j]], len[j]); });
-  Batch* b = nullptr;
-  std::vector<int> walk;
-  std::vector<uint32_t> ff;
-  if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &b, &walk, &ff))) return st;
+  std::vector<int>& walk = u.walk;
+  std::vector<uint32_t>& ff = u.ff;
+  if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff))) return st;
+  Batch* b = u.b;
   b->drain_rule = ZG_DRAIN_DECODE_ALL;   // (as zgpu_decode_all: decode_all drains its DecodeBuffer every MiB, zg_exact.h)
-  if ((st = b->run()) || (st = b->sync())) { delete b; return st; }
+  if ((st = b->run()) || (st = b->sync())) return st;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
-  if (fo.size() != b->info.size()) { delete b; return ZGPU_E_INTERNAL; }
+  if (fo.size() != b->info.size()) return ZGPU_E_INTERNAL;
 
   // verdicts (zgpu_decode_all, zg_capi.cpp, on the entry's own frames)
-  std::vector<uint32_t> dev_hash;   // frames hashed on the device
-  uint64_t down = 0;                // output bytes the host needs (of entries that succeed)
   for (uint32_t j = 0; j < n; j++) {
     const uint32_t i = idx[j];
-    zgpu_entry_result& r = k.res[i];
+    zgpu_entry_result& r = k.result(i);
     if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); continue; }   // zgpu_decode_all's frame-by-frame path
     int dev = 0;
     uint64_t bytes = 0;
@@ -126,22 +146,34 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
     r.written = bytes;
     r.nframes = ff[j + 1] - ff[j];
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (fo[f].out_size <= k.hash_max) dev_hash.push_back(f);   // (candidates)
+      if (fo[f].out_size <= k.hash_max) u.cand.push_back(f);   // (candidates)
       const uint64_t e = fo[f].out_base + fo[f].out_size;
-      if (e > down) down = e;
+      if (e > u.down) u.down = e;
     }
   }
+  return ZGPU_OK;
+}
+
+// the host sink: the plaintext comes back, goes to the callers' buffers on the host threads, and the frames the device did not hash are hashed there
+int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
+  Batch* b = u.b;
+  const std::vector<ZgFrameOut>& fo = b->frame_out;
+  const std::vector<int>& walk = u.walk;
+  const std::vector<uint32_t>& ff = u.ff;
+  std::vector<uint32_t>& dev_hash = u.cand;   // frames hashed on the device
+  const uint64_t down = u.down;                // output bytes the host needs (of entries that succeed)
+  int st;
   if (!k.hash_forced && !hash_on_device(dev_hash, fo)) dev_hash.clear();
   std::vector<uint8_t> on_dev(fo.size(), 0);
   for (uint32_t f : dev_hash) on_dev[f] = 1;
   // the device hashes its frames while the output comes back
-  if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) { delete b; return st; }
+  if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) return st;
   Staging out;
-  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down))) { delete b; return st; }
+  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down))) return st;
   std::vector<uint64_t> digest(fo.size(), 0);
   {
     std::vector<uint64_t> dh(dev_hash.size());
-    if ((st = b->hash_wait(dh.data()))) { delete b; return st; }
+    if ((st = b->hash_wait(dh.data()))) return st;
     for (size_t q = 0; q < dev_hash.size(); q++) digest[dev_hash[q]] = dh[q];
   }
   // bytes to the callers' buffers; the long frames hashed here, from those bytes
@@ -167,14 +199,76 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
       if (fi.has_checksum) { r.checksums++; if (fi.checksum != calc) r.checksum_mismatches++; }
     }
   }
-  delete b;
   return ZGPU_OK;
+}
+
+// the device sink: the plaintext stays on the device; one zg_k_scatter launch copies the frames of every successful entry to its destination
+// (an entry's frames back to back) while zg_k_xxh64 hashes the candidates beside it; frames that are not hashed are counted, not verified
+int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
+  Batch* b = u.b;
+  const std::vector<ZgFrameOut>& fo = b->frame_out;
+  const std::vector<uint32_t>& ff = u.ff;
+  std::vector<uint32_t>& dev_hash = u.cand;
+  if (k.no_hash) dev_hash.clear();
+  std::vector<uint8_t> on_dev(fo.size(), 0);
+  for (uint32_t f : dev_hash) on_dev[f] = 1;
+  int st;
+  if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) return st;
+  std::vector<zgs::Seg> segs;
+  uint64_t bytes = 0;
+  for (uint32_t j = 0; j < n; j++) {
+    const zgpu_entry_result& r = k.dres[idx[j]].r;
+    if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
+    uint64_t at = 0;
+    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+      if (fo[f].out_size) segs.push_back(zgs::Seg{fo[f].out_base, (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, fo[f].out_size});
+      at += fo[f].out_size;
+    }
+    if (at != r.written || at > k.caps[idx[j]]) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
+    bytes += at;
+  }
+  if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
+  if ((st = b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk))) return st;
+  std::vector<uint64_t> digest(fo.size(), 0);
+  {
+    std::vector<uint64_t> dh(dev_hash.size());
+    if ((st = b->hash_wait(dh.data()))) return st;
+    for (size_t q = 0; q < dev_hash.size(); q++) digest[dev_hash[q]] = dh[q];
+  }
+  uint64_t us = 0;
+  bool launched = false;
+  if ((st = b->scatter_wait(&us, &launched))) return st;
+  k.stats[1] += launched ? 1u : 0u; k.stats[2] += bytes; k.stats[3] += us;
+  for (uint32_t j = 0; j < n; j++) {
+    zgpu_device_entry_result& d = k.dres[idx[j]];
+    zgpu_entry_result& r = d.r;
+    if (r.status || r.nframes == 0) continue;
+    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+      const FrameInfo& fi = b->info[f];
+      const uint32_t calc = (uint32_t)digest[f];
+      k.stats[on_dev[f] ? 4 : 5]++;
+      if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = on_dev[f] ? calc : 0u; d.first_hashed = on_dev[f]; }
+      if (!fi.has_checksum) continue;
+      r.checksums++;
+      if (!on_dev[f]) d.checksums_unverified++;
+      else if (fi.checksum != calc) r.checksum_mismatches++;
+    }
+  }
+  return ZGPU_OK;
+}
+
+// one submit: the entries idx[0 .. n)
+int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
+  Submit u;
+  int st = decode_submit(k, idx, n, u);
+  if (st) return st;
+  return k.dres ? sink_device(k, idx, n, u) : sink_host(k, idx, n, u);
 }
 
 // an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
 // which also hashes what it hands out)
-int decode_alone(Call& k, uint32_t i, bool dict_walk) {
-  zgpu_entry_result& r = k.res[i];
+int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr) {
+  zgpu_entry_result& r = k.result(i);
   memset(&r, 0, sizeof r);
   ZgFrameSums sums;
   size_t w = 0;
@@ -182,9 +276,9 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk) {
   bool sums_ok = true;
   if (dict_walk) {
     // (what zgpu_decode_all does with this entry: its walk meets a dictionary frame, and dictionaries are registered)
-    st = zg_decode_all_per_frame(k.c, k.srcs[i], k.lens[i], k.dsts[i], k.caps[i], &w, &sums);
+    st = zg_decode_all_per_frame(k.c, k.srcs[i], k.lens[i], dst, cap, &w, &sums);
   } else {
-    st = zgpu_decode_all(k.c, k.srcs[i], k.lens[i], k.dsts[i], k.caps[i], &w);
+    st = zgpu_decode_all(k.c, k.srcs[i], k.lens[i], dst, cap, &w);
     if (!st) {
       // (Unsupported / Internal in a larger submit, but not alone — never seen; the status stays zgpu_decode_all's.) The checksums come from a
       // second, frame-by-frame pass into a buffer of its own; should that pass fail or disagree, the entry reports none rather than a wrong one.
@@ -192,7 +286,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk) {
       uint8_t* tmp = (uint8_t*)malloc(w ? w : 1);
       if (!tmp) return ZGPU_E_NOMEM;
       const int s2 = zg_decode_all_per_frame(k.c, k.srcs[i], k.lens[i], tmp, w, &w2, &sums);
-      sums_ok = s2 == ZGPU_OK && w2 == w && (w == 0 || memcmp(tmp, k.dsts[i], w) == 0);
+      sums_ok = s2 == ZGPU_OK && w2 == w && (w == 0 || memcmp(tmp, dst, w) == 0);
       free(tmp);
       if (s2 == ZGPU_E_NOMEM || s2 == ZGPU_E_HIP) return s2;
     }
@@ -200,6 +294,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk) {
   if (st == ZGPU_E_NOMEM || st == ZGPU_E_HIP) return st;
   r.status = st;
   if (st) return ZGPU_OK;
+  if (summed) *summed = sums_ok;
   if (!sums_ok) {   // the frames are counted from their headers; no checksum is reported
     std::vector<FrameSpan> sp;
     (void)split_frames(k.srcs[i], k.lens[i], &sp);
@@ -213,6 +308,88 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk) {
   return ZGPU_OK;
 }
 
+// the device sink's form of decode_alone: into a host buffer (no larger than the entry can need), then one H2D to the caller's memory. The host
+// hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
+int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
+  const uint64_t bound = plaintext_bound(k.srcs[i], k.lens[i]);
+  const size_t cap = k.caps[i] < bound ? k.caps[i] : (size_t)bound;   // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i])
+  uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
+  if (!tmp) return ZGPU_E_NOMEM;
+  bool summed = false;
+  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed);
+  zgpu_device_entry_result& d = k.dres[i];
+  d.checksums_unverified = 0;
+  d.first_hashed = 0;
+  if (!st && !d.r.status) {
+    if (d.r.written && hipMemcpy(k.dsts[i], tmp, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    const bool hashed = summed && !k.no_hash && d.r.nframes;
+    if (k.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
+    d.first_hashed = hashed ? 1u : 0u;
+    k.stats[hashed ? 4 : 5] += d.r.nframes;
+  }
+  free(tmp);
+  k.stats[6]++;
+  return st;
+}
+
+// Is [p, p + cap) device memory of one allocation on the context's device? Asked of the HIP runtime, before any launch. `known` remembers the
+// allocations already seen in this call: entries usually share a few (a torch tensor cut into slots).
+struct DevRange { uintptr_t lo, hi; };
+bool check_device_dst(int device, const void* p, size_t cap, std::vector<DevRange>& known) {
+  if (!p) return false;
+  const uintptr_t a = (uintptr_t)p;
+  if (cap > UINTPTR_MAX - a) return false;
+  for (const DevRange& r : known) if (a >= r.lo && a + cap <= r.hi) return true;
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (an address the runtime does not know)
+  if (at.type != hipMemoryTypeDevice || at.device != device) return false;                        // (host, managed, unregistered, another GPU)
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const uintptr_t lo = (uintptr_t)base;
+  if (a < lo || size > UINTPTR_MAX - lo || a + cap > lo + size) return false;
+  known.push_back(DevRange{lo, lo + size});
+  return true;
+}
+
+// the entries cut into submits (an entry is never split), then the again-list
+int decode_entries(Call& k, uint32_t n) {
+  zgpu_ctx* c = k.c;
+  const Tuning& tn = c->eng->tuning();
+  const uint64_t S = tn.frames_submit_bytes ? tn.frames_submit_bytes : kFramesSubmitBytes;
+  c->frames_submits = 0;
+  std::vector<DevRange> known;
+  std::vector<uint32_t> group;
+  uint64_t in_group = 0, in_bytes = 0;   // plaintext bound and input bytes of the submit being gathered (both bounded by S)
+  int st = ZGPU_OK;
+  for (uint32_t i = 0; i <= n && !st; i++) {
+    uint64_t bound = 0;
+    if (i < n) {
+      if (k.dres) memset(&k.dres[i], 0, sizeof k.dres[i]);
+      else memset(&k.res[i], 0, sizeof k.res[i]);
+      bool bad = (!k.srcs[i] && k.lens[i]) || (!k.dsts[i] && k.caps[i]);   // (what zgpu_decode_all returns)
+      if (!bad && k.dres && k.caps[i]) bad = !check_device_dst(c->eng->device(), k.dsts[i], k.caps[i], known);
+      if (bad) { k.result(i).status = ZGPU_E_BAD_ARG; continue; }
+      bound = plaintext_bound(k.srcs[i], k.lens[i]);
+    }
+    // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
+    // yield nothing — skippable frames, garbage — still travel to the device, through the pinned staging.)
+    if (!group.empty() && (i == n || in_group + bound > S || in_bytes + k.lens[i] > S)) {
+      st = run_submit(k, group.data(), (uint32_t)group.size());
+      c->frames_submits++;
+      group.clear();
+      in_group = 0; in_bytes = 0;
+    }
+    if (i < n) { group.push_back(i); in_group += bound; in_bytes += k.lens[i]; }
+  }
+  for (size_t q = 0; q < k.again.size() && !st; q++) {
+    const uint32_t i = k.again[q].first;
+    st = k.dres ? decode_alone_device(k, i, k.again[q].second) : decode_alone(k, i, k.again[q].second, k.dsts[i], k.caps[i]);
+  }
+  return st;
+}
+
 }  // namespace
 
 extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, uint8_t* const* dsts, const size_t* caps,
@@ -220,30 +397,29 @@ extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const
   if (!c || (n && (!srcs || !lens || !dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
   const Tuning& tn = c->eng->tuning();
   Call k{c, srcs, lens, dsts, caps, results, tn.hash_device_max_set, tn.hash_device_max_set ? tn.hash_device_max : kHashDeviceMax, {}};
-  const uint64_t S = tn.frames_submit_bytes ? tn.frames_submit_bytes : kFramesSubmitBytes;
-  c->frames_submits = 0;
-  std::vector<uint32_t> group;
-  uint64_t in_group = 0, in_bytes = 0;   // plaintext bound and input bytes of the submit being gathered (both bounded by S)
-  int st = ZGPU_OK;
-  for (uint32_t i = 0; i <= n && !st; i++) {
-    uint64_t bound = 0;
-    if (i < n) {
-      memset(&results[i], 0, sizeof results[i]);
-      if ((!srcs[i] && lens[i]) || (!dsts[i] && caps[i])) { results[i].status = ZGPU_E_BAD_ARG; continue; }   // (what zgpu_decode_all returns)
-      bound = plaintext_bound(srcs[i], lens[i]);
-    }
-    // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
-    // yield nothing — skippable frames, garbage — still travel to the device, through the pinned staging.)
-    if (!group.empty() && (i == n || in_group + bound > S || in_bytes + lens[i] > S)) {
-      st = run_submit(k, group.data(), (uint32_t)group.size());
-      c->frames_submits++;
-      group.clear();
-      in_group = 0; in_bytes = 0;
-    }
-    if (i < n) { group.push_back(i); in_group += bound; in_bytes += lens[i]; }
-  }
-  for (size_t q = 0; q < k.again.size() && !st; q++) st = decode_alone(k, k.again[q].first, k.again[q].second);
+  return decode_entries(k, n);
+}
+
+extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
+                                         const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
+  if (!c || (n && (!srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  for (uint64_t& x : c->frames_device_stats) x = 0;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  Call k{c, srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
+  k.dres = results;
+  k.no_hash = opts && (opts->flags & 1u);
+  k.stats = c->frames_device_stats;
+  int st = decode_entries(k, n);
+  // every later operation on any stream sees the bytes: nothing of this call is in flight on the engine's streams (the scatter ran on the second)
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  k.stats[0] = c->frames_submits;
   return st;
+}
+extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c || !out) return 0;
+  int k = 0;
+  for (; k < n && k < 7; k++) out[k] = c->frames_device_stats[k];
+  return k;
 }
 
 extern "C" uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len) { return src || !len ? plaintext_bound(src, len) : 0; }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zg_types.h"
+#include "zg_scatter.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -40,3 +41,5 @@ void zg_launch_calib(const void* src, void* dst, uint64_t bytes, hipStream_t s);
 // zg_k_xxh64: XXH64 (seed 0) of byte ranges of a batch's output, one lane per range; out[slot] = digest. ranges are sorted by length, longest first
 struct ZgHashRange { uint64_t off, len; uint32_t slot, pad; };
 void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s);
+// zg_k_scatter (zg_scatter.h): the chunks of the segments of a batch's output (base) to the segments' destinations, one workgroup per chunk
+void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);

@@ -33,6 +33,7 @@
 #include "zg_kernels.h"
 #include "zg_dev.h"
 #include "zg_xxh64_dev.h"
+#include "zg_scatter.h"
 
 #define ZG_SEQ_G 16       // blocks per workgroup (four lanes per block in either wave) in zg_k_seq: 16 x (2.5 KiB + 1.25 KiB tables + ring + records) in LDS -> 2 workgroups per CU
 #define ZG_LZ_T 256       // threads per frame in zg_k_lz
@@ -1783,6 +1784,33 @@ __global__ void __launch_bounds__(256) zg_k_xxh64(const uint8_t* base, const ZgH
 }
 void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s) {
   if (n) hipLaunchKernelGGL(zg_k_xxh64, dim3((n + 255) / 256), dim3(256), 0, s, base, ranges, out, n);
+}
+
+// A submit's plaintext to the caller's device memory (zgpu_decode_frames_device): one workgroup per chunk of the host's plan, grid-stride
+// over the chunk table; zg_scatter.h has the plan, the lane routine, its bounds and the ISA notes. The host checked every segment against
+// the batch output and every destination against the runtime's allocation table before the launch (Batch::scatter_launch, zg_frames.cpp).
+struct ZgScatterRead {
+  const uint8_t* base;
+  __device__ __forceinline__ uint8_t ld1(uint64_t off) const { return base[off]; }
+  __device__ __forceinline__ zgs::V16 ld16(uint64_t off) const { zgs::V16 v; memcpy(&v, base + off, 16); return v; }
+};
+struct ZgScatterWrite {   // (the destinations are global memory — the host checked that —: global_store_*, not flat_store_*)
+  __device__ __forceinline__ void st1(uint64_t addr, uint8_t v) const { *(__attribute__((address_space(1))) uint8_t*)addr = v; }
+  __device__ __forceinline__ void st16(uint64_t addr, const zgs::V16& v) const {
+    __builtin_memcpy((__attribute__((address_space(1))) void*)__builtin_assume_aligned((void*)addr, 16), &v, 16);
+  }
+};
+__global__ void __launch_bounds__(256) zg_k_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks) {
+  const ZgScatterRead r{base};
+  const ZgScatterWrite w{};
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const zgs::Chunk ch = chunks[c];
+    const zgs::Seg sg = segs[ch.seg];
+    zgs::copy_chunk(r, w, sg.src_off + ch.at, sg.dst + ch.at, ch.len, threadIdx.x, zgs::kThreads);
+  }
+}
+void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(zg_k_scatter, dim3(nchunks < zgs::kMaxGroups ? nchunks : zgs::kMaxGroups), dim3(zgs::kThreads), 0, s, base, segs, chunks, nchunks);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -41,6 +41,27 @@ class EntryResult:
             self.status, self.written, self.nframes, self.checksums, self.checksum_mismatches)
 
 
+class DeviceOptsC(C.Structure):
+    """zgpu_device_opts (include/zgpu.h)"""
+    _fields_ = [("hash_max_bytes", C.c_uint64), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class DeviceEntryResultC(C.Structure):
+    _fields_ = [("r", EntryResultC), ("checksums_unverified", C.c_uint32), ("first_hashed", C.c_uint32)]
+
+
+class DeviceEntryResult:
+    """One entry of Context.decode_frames_device (zgpu_device_entry_result): the fields of EntryResult without data — on status 0 the first
+    `written` bytes of the entry's destination are the plaintext — plus checksums_unverified (frames with a Content_Checksum that were not
+    hashed) and first_hashed (whether calculated_checksum is the first frame's real XXH64)."""
+    __slots__ = ("status", "written", "nframes", "checksums", "checksum_mismatches", "checksum_from_data", "calculated_checksum",
+                 "checksums_unverified", "first_hashed")
+
+    def __repr__(self):
+        return "DeviceEntryResult(status=%d, written=%d, nframes=%d, checksums=%d, mismatches=%d, unverified=%d)" % (
+            self.status, self.written, self.nframes, self.checksums, self.checksum_mismatches, self.checksums_unverified)
+
+
 def plaintext_bound(buf):
     """zgpu_plaintext_bound: an upper bound of the plaintext of concatenated frames from frame and block headers only (a frame's declared
     content size when smaller; a compressed block counts 128 KiB); the walk stops where a header cannot be read. Decode_frames' default
@@ -82,6 +103,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
     "zgpu_decode_all", "zgpu_batch_prepare", "zgpu_batch_run", "zgpu_batch_sync", "zgpu_batch_num_frames", "zgpu_batch_num_blocks",
@@ -146,6 +168,8 @@ def _declare(L):
     L.zgpu_batch_read.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
     L.zgpu_batch_checksums.argtypes = [vp, P(C.c_uint64), C.c_uint32]
     L.zgpu_decode_frames.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(EntryResultC)]
+    L.zgpu_decode_frames_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
+    L.zgpu_debug_frames_device_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_plaintext_bound.argtypes = [u8p, sz]
     L.zgpu_plaintext_bound.restype = C.c_uint64
     L.zgpu_debug_frames_submits.argtypes = [vp]
@@ -252,6 +276,7 @@ class Context:
         if st:
             raise ZgpuError(st, "zgpu_ctx_create: no usable MI355X/HIP device — the engine has no CPU path")
         self.h = h
+        self.device = device
 
     def close(self):
         if getattr(self, "h", None):
@@ -322,16 +347,9 @@ class Context:
         what decode_all of that entry alone would give, plus the content checksums of its frames."""
         import numpy as np
         n = len(entries)
-        srcs, lens, keep = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), []
-        for i, e in enumerate(entries):
-            if isinstance(e, tuple):
-                srcs[i], lens[i] = e[0], e[1]
-            else:
-                b = C.c_char_p(bytes(e))                   # (no copy of a bytes object)
-                keep.append(b)
-                srcs[i], lens[i] = C.cast(b, C.c_void_p).value, len(e)
+        srcs, lens, keep = self._entries(entries)
         if caps is None:
-            caps = [self.L.zgpu_plaintext_bound(C.cast(C.c_void_p(srcs[i]), C.c_char_p), lens[i]) for i in range(n)]
+            caps = self._bounds(srcs, lens, n)
         offs = np.zeros(n + 1, dtype=np.uint64)
         if n:
             offs[1:] = np.cumsum(np.asarray(caps, dtype=np.uint64))
@@ -356,8 +374,90 @@ class Context:
         return outl
 
     def frames_submits(self):
-        """submits the last decode_frames call ran (zgpu_debug_frames_submits)"""
+        """submits the last decode_frames / decode_frames_device call ran (zgpu_debug_frames_submits)"""
         return self.L.zgpu_debug_frames_submits(self.h)
+
+    @staticmethod
+    def _entries(entries):
+        """(srcs, lens, what keeps them alive) of entries: bytes, or (address, length) of memory the caller keeps alive"""
+        n = len(entries)
+        srcs, lens, keep = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), []
+        for i, e in enumerate(entries):
+            if isinstance(e, tuple):
+                srcs[i], lens[i] = e[0], e[1]
+            else:
+                b = C.c_char_p(bytes(e))                   # (no copy of a bytes object)
+                keep.append(b)
+                srcs[i], lens[i] = C.cast(b, C.c_void_p).value, len(e)
+        return srcs, lens, keep
+
+    def _bounds(self, srcs, lens, n):
+        return [self.L.zgpu_plaintext_bound(C.cast(C.c_void_p(srcs[i]), C.c_char_p), lens[i]) for i in range(n)]
+
+    def decode_frames_device(self, entries, ptrs, caps, hash_max=0, no_hash=False):
+        """zgpu_decode_frames_device: decode_frames with the plaintext left in DEVICE memory the caller owns. ptrs[i] is the address of caps[i]
+        bytes on this context's device (any alignment; a torch tensor's data_ptr()); the library checks every one with the HIP runtime before it
+        launches anything, and a pointer that is not such memory gives that entry E_BAD_ARG. Nothing in flight may touch the destinations during
+        the call; when it returns, the bytes are there for every stream. hash_max: frames up to this many bytes are hashed on the device
+        (0: 4 MiB), longer ones are counted in checksums_unverified; no_hash: hash nothing. Returns one DeviceEntryResult per entry."""
+        n = len(entries)
+        if len(ptrs) != n or len(caps) != n:
+            raise ValueError("decode_frames_device: one pointer and one capacity per entry")
+        srcs, lens, keep = self._entries(entries)
+        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            dsts[i], capa[i] = int(ptrs[i]) or None, int(caps[i])
+        opts = DeviceOptsC(int(hash_max), 1 if no_hash else 0, 0)
+        res = (DeviceEntryResultC * max(n, 1))()
+        st = self.L.zgpu_decode_frames_device(self.h, srcs, lens, n, dsts, capa, C.byref(opts), res)
+        del keep
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        outl = []
+        for i in range(n):
+            d, e = res[i], DeviceEntryResult()
+            r = d.r
+            e.status, e.written, e.nframes = r.status, r.written, r.nframes
+            e.checksums, e.checksum_mismatches = r.checksums, r.checksum_mismatches
+            e.checksum_from_data, e.calculated_checksum = r.checksum_from_data, r.calculated_checksum
+            e.checksums_unverified, e.first_hashed = d.checksums_unverified, d.first_hashed
+            outl.append(e)
+        return outl
+
+    def frames_device_stats(self):
+        """the last decode_frames_device call (zgpu_debug_frames_device_stats)"""
+        a = (C.c_uint64 * 7)()
+        k = self.L.zgpu_debug_frames_device_stats(self.h, a, 7)
+        keys = ["submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed", "entries_alone"]
+        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False):
+        """decode_frames_device into ONE torch.uint8 tensor on this context's device, every entry's slot 256-byte aligned (caps: bytes of room per
+        entry, default plaintext_bound of the entry). Returns (tensors, results): tensors[i] is a view of entry i's slot cut to `written` bytes
+        (empty unless status == 0), results[i] its DeviceEntryResult. torch is imported here, not by `import zgpu`.
+        torch wheels ship a HIP runtime of their own: the process must run on ONE runtime for torch's memory to be known to this library,
+        which it does when torch is imported before the first Context is created (load_library); otherwise this raises."""
+        import torch
+        hip = set(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln) if os.path.exists("/proc/self/maps") else ()
+        if len(hip) > 1:
+            raise RuntimeError("two HIP runtimes are loaded (%s): import torch before creating the first zgpu.Context" % ", ".join(sorted(hip)))
+        n = len(entries)
+        srcs, lens, keep = self._entries(entries)
+        if caps is None:
+            caps = self._bounds(srcs, lens, n)
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (int(c) + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        # the caching allocator may hand out memory that is still in use on torch's stream
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+        base = buf.data_ptr()
+        ents = [(srcs[i] or 0, lens[i]) for i in range(n)]
+        res = self.decode_frames_device(ents, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
+        del keep
+        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
 
 
 class Batch:
