@@ -136,13 +136,13 @@ int zgpu_decode_frames(zgpu_ctx*, const uint8_t* const* srcs, const size_t* lens
  * 128 KiB per compressed block; the walk stops where a header cannot be read. What zgpu_decode_frames cuts its submits by; a caller may size
  * caps[i] with it. Host only. */
 uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len);
-/* diagnostics: the submits the context's last zgpu_decode_frames / zgpu_decode_frames_device call ran */
+/* diagnostics: the submits the context's last zgpu_decode_frames / zgpu_decode_frames_device / zgpu_decode_frames_device_src call ran */
 uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
 
 /* ---- the same, with the plaintext left in device memory the caller owns ------------------------------------------------------
  * For callers that want the plaintext ON the GPU (compressed shards headed for tensors, columnar pages headed for a GPU query): no download,
- * no host copy, no upload of the caller's own. srcs are HOST pointers — the host keeps the header walk, as everywhere in this library;
- * compressed input that is already device-resident is out of scope. device_dsts[i] is device memory on the context's device (a hipMalloc'ed
+ * no host copy, no upload of the caller's own. srcs are HOST pointers (compressed input that is already device-resident: the call below).
+ * device_dsts[i] is device memory on the context's device (a hipMalloc'ed
  * block or any part of one, e.g. a torch tensor's data_ptr()), caps[i] bytes, at any alignment.
  *  - results[i].r.status / .written / .nframes are what zgpu_decode_frames reports for the same entries: what zgpu_decode_all of entry i ALONE
  *    returns, independent of the other entries and of their order. On status 0 the first `written` bytes of device_dsts[i] are the plaintext.
@@ -178,6 +178,33 @@ int zgpu_decode_frames_device(zgpu_ctx*, const uint8_t* const* srcs, const size_
 /* diagnostics: the context's last zgpu_decode_frames_device call — out[0] submits, [1] scatter launches, [2] bytes scattered, [3] scatter kernel
  * microseconds (HIP events), [4] frames hashed, [5] frames not hashed, [6] entries that were decoded alone. Returns how many were written. */
 int zgpu_debug_frames_device_stats(const zgpu_ctx*, uint64_t* out, int n);
+
+/* ---- the same, with the compressed input in device memory too ------------------------------------------------------------------
+ * For callers whose compressed bytes are in HBM already (a GPUDirect / RDMA read, a torch tensor loaded from a sharded checkpoint, the output of
+ * an earlier GPU stage): no download of the caller's, no staging copy, no upload. device_srcs[i] is device memory on the context's device,
+ * lens[i] bytes at any alignment; everything else is zgpu_decode_frames_device.
+ *  - results[i] equals, field for field, what zgpu_decode_frames_device reports for a host copy of the same bytes with the same destinations
+ *    and options, and so do the destination bytes. Every guarantee of that call holds: entries are isolated and their order does not matter,
+ *    nothing of a failed entry and nothing at or behind dst + written is written, submits are cut the same way (zgpu_debug_frames_submits gives
+ *    the same count), the hash rule is the same, the engine's streams are synchronised on return.
+ *  - The host still owns every verdict, the table lineage and the launch plan. It reads a skeleton instead of the bytes: one lane per entry
+ *    follows the header chain on the device (zg_k_walk, two launches for the whole call) and 32 bytes per frame header, block and checksum
+ *    come back; the host's one parse runs over those records. A submit's entries reach the engine's input buffer by ONE kernel launch
+ *    (zg_k_gather).
+ *  - Every source passes the check the destinations pass, before anything is launched: device memory (not host, not managed), on the
+ *    context's device, [src, src + lens[i]) inside ONE allocation; else that entry gets ZGPU_E_BAD_ARG and the others are unaffected.
+ *    lens[i] == 0: nothing is checked, nothing is read.
+ *  - The library never writes to a source and no lane reads a byte outside [src, src + lens[i]), not even inside the same allocation: an
+ *    entry may end flush with its allocation. A source that overlaps a destination is undefined. The caller guarantees that nothing in
+ *    flight writes the sources during the call.
+ *  - Entries the one-submit path does not serve (dictionary frames while dictionaries are registered, Unsupported / Internal verdicts) are
+ *    downloaded, one D2H each, and decoded alone as by zgpu_decode_frames_device (rare; correct first). */
+int zgpu_decode_frames_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
+                                  const size_t* caps, const zgpu_device_opts* opts_or_null, zgpu_device_entry_result* results);
+/* diagnostics: the context's last zgpu_decode_frames_device_src call — out[0] walk launches, [1] walk kernel microseconds (HIP events), [2] skeleton
+ * bytes downloaded, [3] gather launches, [4] gather kernel microseconds, [5] input bytes that crossed to the host (entries decoded alone only).
+ * zgpu_debug_frames_device_stats is filled by that call as well. Returns how many were written. */
+int zgpu_debug_frames_device_src_stats(const zgpu_ctx*, uint64_t* out, int n);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

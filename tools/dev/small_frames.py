@@ -19,7 +19,15 @@ the host call (zgpu_decode_frames) against the device call (zgpu_decode_frames_d
 in one process and in its SECOND context (the first context of a process downloads more slowly, LABNOTES round 6): best of 5 after a warm-up
 each, interleaved; the device call with its default hashing and with hashing off (the difference is the device hash's share); and the scatter
 kernel's own time and bytes (zgpu_debug_frames_device_stats). ZGPU_SCATTER_CHUNK (read by the development build) sets the chunk size:
-`--device --dev` loads libzgpu_dev.so. Prints one JSON object."""
+`--device --dev` loads libzgpu_dev.so. Prints one JSON object.
+
+  python tools/dev/small_frames.py --device-src [workload ...]  (default: corpus101 4096x128K 1024x512K 256x2M 128x64M 1x1024M)
+
+compressed input that lies in device memory (one torch tensor, entries back to back): zgpu_decode_frames_device_src against the detour a
+caller takes without it — download the inputs to the host (one D2H of the tensor), then zgpu_decode_frames_device — in one process and its
+second context, interleaved, best of 5 after a warm-up each; the walk's and the gather's own times and the skeleton's size
+(zgpu_debug_frames_device_src_stats) beside the scatter's. 1x1024M is ONE frame of 8192 blocks: the walk lane's worst case. Prints one
+JSON object."""
 import json
 import os
 import sys
@@ -104,7 +112,65 @@ def device_main(args):
     print(json.dumps(out))
 
 
+def device_src_main(args):
+    import torch
+    names = [a for a in args if not a.startswith("--")] or ["corpus101", "4096x128K", "1024x512K", "256x2M", "128x64M", "1x1024M"]
+    first = zgpu.Context(0)
+    first.decode_all(zgdata.zstd_compress(b"warm" * 1000), 4000)
+    ctx = zgpu.Context(0)
+    out = {}
+    for name in names:
+        ent, caps = device_workload(name)
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (c + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device="cuda:0")
+        ptrs = [buf.data_ptr() + o for o in offs]
+        lens = [len(z) for z in ent]
+        soffs, at = [], 0
+        for n in lens:
+            soffs.append(at)
+            at += n
+        src = torch.frombuffer(bytearray(b"".join(ent)), dtype=torch.uint8).to("cuda:0")
+        pinned = torch.empty(at, dtype=torch.uint8).pin_memory()
+        torch.cuda.synchronize()
+        sptrs = [src.data_ptr() + o for o in soffs]
+
+        def detour():
+            pinned.copy_(src)                    # the caller's download (pinned: the fastest form of it)
+            torch.cuda.synchronize()
+            base = pinned.data_ptr()
+            return ctx.decode_frames_device([(base + o, n) for o, n in zip(soffs, lens)], ptrs, caps)
+
+        direct = lambda: ctx.decode_frames_device_src(sptrs, lens, ptrs, caps)           # noqa: E731
+        ra = detour()
+        want = buf.clone()
+        buf.zero_()
+        rb = direct()
+        key = lambda r: (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches, r.calculated_checksum, r.checksums_unverified)   # noqa: E731
+        assert [key(x) for x in ra] == [key(x) for x in rb] and all(x.status == 0 for x in rb) and torch.equal(buf, want)
+        del want
+        t_detour = t_direct = None
+        for _ in range(5):
+            t_detour = min(x for x in (t_detour, best(detour, 1)) if x is not None)
+            t_direct = min(x for x in (t_direct, best(direct, 1)) if x is not None)
+        direct()
+        out[name] = {"entries": len(ent), "plain_MiB": sum(caps) / 2 ** 20, "input_MiB": at / 2 ** 20, "download_then_device_call_ms": 1e3 * t_detour,
+                     "device_src_call_ms": 1e3 * t_direct, "speedup": t_detour / t_direct, "src_stats": ctx.frames_device_src_stats(),
+                     "stats": ctx.frames_device_stats()}
+        st, ss = out[name]["stats"], out[name]["src_stats"]
+        out[name]["scatter_GBps"] = st["bytes_scattered"] / max(st["scatter_us"], 1) / 1e3
+        out[name]["gather_GBps"] = at / max(ss["gather_us"], 1) / 1e3
+        del buf, src, pinned
+    ctx.close()
+    first.close()
+    print(json.dumps(out))
+
+
 def main():
+    if "--device-src" in sys.argv[1:]:
+        return device_src_main([a for a in sys.argv[1:] if a != "--device-src"])
     if "--device" in sys.argv[1:]:
         return device_main([a for a in sys.argv[1:] if a != "--device"])
     nf = int(sys.argv[1]) if len(sys.argv) > 1 else 4096

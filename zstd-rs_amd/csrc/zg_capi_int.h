@@ -22,6 +22,7 @@ struct zgpu_ctx {
   std::map<uint32_t, ZgDict> dicts;   // FrameDecoder::dicts (frame_decoder.rs:82)
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
   uint64_t frames_device_stats[7] = {0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
+  uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)
   std::string err;
 };
 

@@ -161,131 +161,6 @@ void Engine::recycle(Scratch* s) {
   else { s->release(); delete s; }
 }
 
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
-  // FrameDecoder::decode_all (frame_decoder.rs:541-577): concatenated frames, skippable frames skipped;
-  // the first error ends the walk (the reference returns it).
-  size_t p = 0;
-  static const uint32_t kHist[3] = {1, 4, 8};  // scratch.rs:44
-  while (p < len) {
-    FrameHeader h;
-    size_t c;
-    uint32_t sm = 0, sl = 0;
-    int st = read_frame_header(src + p, len - p, &h, &c, &sm, &sl);
-    if (st == ZG_SKIP_FRAME) {
-      p += c;
-      if ((size_t)sl > len - p) return ZG_FAILED_SKIP_FRAME;  // :550-556
-      p += sl;
-      continue;
-    }
-    if (st) return st;
-    uint64_t w;
-    if ((st = frame_window_size(h, &w))) return st;
-    if (w > max_window) return ZG_WINDOW_SIZE_TOO_BIG;          // frame_decoder.rs:137-145
-    if (h.has_dict_id) return ZG_DICT_NOT_PROVIDED;             // :212-217 (dictionaries: see DESIGN.md "next")
-    FrameInfo fi;
-    fi.header = h;
-    fi.window_size = w;
-    fi.src_begin = base + p;
-    p += c;
-    bb->begin_frame(w, kHist, 0);
-    for (;;) {
-      if (len - p < 3) { st = ZG_FAILED_READ_BLOCK_HEADER; break; }
-      BlockHeader bh;
-      if ((st = read_block_header(src + p, &bh))) break;
-      p += 3;
-      if (len - p < bh.content_size) { st = ZG_FAILED_READ_BLOCK_BODY; break; }
-      st = bb->add_block(bh, src + p, base + p);
-      p += bh.content_size;
-      fi.nblocks++;
-      if (st) break;
-      if (bh.last) {
-        if (h.content_checksum()) {
-          if (len - p < 4) { st = ZG_FAILED_READ_CHECKSUM; break; }
-          memcpy(&fi.checksum, src + p, 4);
-          fi.has_checksum = true;
-          p += 4;
-        }
-        break;
-      }
-    }
-    fi.src_end = base + p;
-    fi.host_status = st;
-    info->push_back(fi);
-    if (st) return st;
-  }
-  return ZG_OK;
-}
-
-
-int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out) {
-  // the walk of parse_frames without the section headers: frame header, then block headers up to the last block
-  size_t p = 0;
-  while (p < len) {
-    FrameHeader h;
-    size_t c;
-    uint32_t sm = 0, sl = 0;
-    FrameSpan sp;
-    sp.begin = p; sp.content_size = 0; sp.has_content_size = false; sp.skippable = false;
-    int st = read_frame_header(src + p, len - p, &h, &c, &sm, &sl);
-    if (st == ZG_SKIP_FRAME) {
-      p += c;
-      if ((size_t)sl > len - p) return ZG_FAILED_SKIP_FRAME;
-      p += sl;
-      sp.end = p; sp.skippable = true;
-      out->push_back(sp);
-      continue;
-    }
-    if (st) return st;
-    p += c;
-    for (;;) {
-      if (len - p < 3) return ZG_FAILED_READ_BLOCK_HEADER;
-      BlockHeader bh;
-      if ((st = read_block_header(src + p, &bh))) return st;
-      p += 3;
-      if (len - p < bh.content_size) return ZG_FAILED_READ_BLOCK_BODY;
-      p += bh.content_size;
-      if (bh.last) {
-        if (h.content_checksum()) {
-          if (len - p < 4) return ZG_FAILED_READ_CHECKSUM;
-          p += 4;
-        }
-        break;
-      }
-    }
-    sp.end = p; sp.content_size = h.frame_content_size; sp.has_content_size = h.has_fcs();
-    out->push_back(sp);
-  }
-  return ZG_OK;
-}
-
-uint64_t plaintext_bound(const uint8_t* src, size_t len) {
-  uint64_t total = 0;
-  size_t p = 0;
-  while (p < len) {
-    FrameHeader h;
-    size_t c;
-    uint32_t sm = 0, sl = 0;
-    int st = read_frame_header(src + p, len - p, &h, &c, &sm, &sl);
-    if (st == ZG_SKIP_FRAME) { p += c; if ((size_t)sl > len - p) break; p += sl; continue; }
-    if (st) break;
-    p += c;
-    uint64_t fb = 0;
-    bool ok = false;
-    while (len - p >= 3) {
-      BlockHeader bh;
-      if (read_block_header(src + p, &bh)) break;
-      p += 3;
-      fb += bh.type == ZG_BT_COMPRESSED ? (uint64_t)kMaxBlockSize : (uint64_t)bh.decompressed_size;
-      if (len - p < bh.content_size) break;
-      p += bh.content_size;
-      if (bh.last) { ok = true; if (h.content_checksum()) p += len - p < 4 ? len - p : 4; break; }
-    }
-    total += h.has_fcs() && h.frame_content_size < fb ? h.frame_content_size : fb;
-    if (!ok) break;
-  }
-  return total;
-}
-
 Batch::~Batch() {
   // a run uses all three of the engine's streams (Huffman chain and sweep heads on the second, the ramped chain on the third) and
   // joins them by events only when it reaches its end: nothing may be in flight on any of them when the buffers go back
@@ -299,6 +174,8 @@ Batch::~Batch() {
   if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
   if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
   for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
+  if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
+  for (hipEvent_t e : ev_gather_) if (e) (void)hipEventDestroy(e);
 }
 
 void FrameState::reset() {
@@ -461,6 +338,100 @@ int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off,
   return upload(b, src, len, out);
 }
 
+namespace {
+struct WalkTmp {   // device memory and events of one walk_entries call
+  DevBuf lanes, ends, recs;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~WalkTmp() {
+    lanes.release(); ends.release(); recs.release();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+}  // namespace
+
+int Engine::walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats) {
+  Engine* eng = this;
+  sk->recs.clear();
+  sk->first.assign((size_t)n + 1, 0);
+  sk->ends.assign(n, zgw::End{0, 0, 0});
+  if (!n) return ZG_OK;
+  ZG_HIP(hipSetDevice(device_));
+  hipStream_t s = stream_;
+  WalkTmp t;
+  std::vector<zgw::Lane> lanes(n);
+  for (uint32_t i = 0; i < n; i++) lanes[i] = zgw::Lane{e[i].src, e[i].len, 0, 0};
+  int st;
+  if ((st = t.lanes.reserve((size_t)n * sizeof(zgw::Lane))) || (st = t.ends.reserve((size_t)n * sizeof(zgw::End)))) return st;
+  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
+  // count pass: how many records every entry has
+  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
+  ZG_HIP(hipEventRecord(t.ev[0], s));
+  zg_launch_walk(t.lanes.as<zgw::Lane>(), n, t.ends.as<zgw::End>(), nullptr, s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(t.ev[1], s));
+  ZG_HIP(hipMemcpyAsync(sk->ends.data(), t.ends.p, (size_t)n * sizeof(zgw::End), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgw::End);
+  for (uint32_t i = 0; i < n; i++) {
+    lanes[i].first = sk->first[i];
+    lanes[i].limit = sk->ends[i].nrec;
+    sk->first[i + 1] = sk->first[i] + sk->ends[i].nrec;
+  }
+  const uint64_t total = sk->first[n];
+  if (!total) return ZG_OK;
+  // emit pass: every lane writes its own range of records, and no other
+  sk->recs.resize(total);
+  if ((st = t.recs.reserve(total * sizeof(zgw::Rec)))) return st;
+  std::vector<zgw::End> again(n);
+  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  ZG_HIP(hipEventRecord(t.ev[2], s));
+  zg_launch_walk(t.lanes.as<zgw::Lane>(), n, t.ends.as<zgw::End>(), t.recs.as<zgw::Rec>(), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(t.ev[3], s));
+  ZG_HIP(hipMemcpyAsync(again.data(), t.ends.p, (size_t)n * sizeof(zgw::End), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipMemcpyAsync(sk->recs.data(), t.recs.p, total * sizeof(zgw::Rec), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  ZG_HIP(hipEventElapsedTime(&ms, t.ev[2], t.ev[3]));
+  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgw::End) + total * sizeof(zgw::Rec);
+  for (uint32_t i = 0; i < n; i++)   // (a source that changed between the passes: the caller's promise broken, nothing of the skeleton is used)
+    if (again[i].nrec != sk->ends[i].nrec || again[i].stop_off != sk->ends[i].stop_off || again[i].why != sk->ends[i].why) {
+      last_error = "zgpu_decode_frames_device_src: a source changed while it was walked";
+      return ZG_INTERNAL;
+    }
+  return ZG_OK;
+}
+
+int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
+                                   std::vector<int>* walk, std::vector<uint32_t>* first_frame) {
+  Batch* b = new Batch();
+  b->eng = this;
+  b->src_len = total;
+  walk->assign(n, 0);
+  first_frame->assign((size_t)n + 1, 0);
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t i = idx[j];
+    bool consistent = true;
+    (*first_frame)[j] = (uint32_t)b->info.size();
+    (*walk)[j] = parse_frames_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), e[i].len, max_window, &b->bb, &b->info, off[j],
+                                   &consistent);
+    if (!consistent) { delete b; last_error = "zgpu_decode_frames_device_src: skeleton records out of step with the walk"; return ZG_INTERNAL; }
+    if (!b->parse_status) b->parse_status = (*walk)[j];
+  }
+  (*first_frame)[n] = (uint32_t)b->info.size();
+  b->all_declared = !b->info.empty();
+  for (const FrameInfo& fi : b->info) {
+    if (!fi.header.has_fcs()) { b->all_declared = false; break; }
+    b->declared_total += fi.header.frame_content_size;
+  }
+  if (!b->all_declared || b->declared_total > (1ull << 40)) { b->all_declared = false; b->declared_total = 0; }
+  const GatherPlan g{e, idx, off, n};
+  return upload(b, nullptr, total, out, false, &g);
+}
+
 int Engine::prepare_run(const uint8_t* src, size_t len, FrameState* fs, bool has_checksum, uint32_t max_blocks, uint64_t keep, Batch** out, size_t* consumed,
                         bool side, const uint32_t* carry_mask_now) {
   Batch* b = new Batch();
@@ -513,7 +484,7 @@ int Engine::prepare_blocks(const uint8_t* src, size_t len, const HostBlock* hb, 
   return upload(b, src, len, out);
 }
 
-int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool side) {
+int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool side, const GatherPlan* g) {
   Engine* eng = this;
   ZG_HIP(hipSetDevice(device_));
   // side: the submit in front is still running on the main stream — everything this one brings to the device travels on the upload stream
@@ -546,7 +517,31 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
   // ... and 64 bytes in front for the 16-byte windows of the sequence decoder
   if ((st = sc->d_src.reserve(len + 128))) { delete b; return st; }
   (void)hipMemsetAsync(sc->d_src.p, 0, 64, us);
-  if (len && hipMemcpyAsync((uint8_t*)sc->d_src.p + 64, src, len, hipMemcpyHostToDevice, us) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
+  if (g) {
+    // the bytes are on the device already: one launch copies every entry to its place behind the front pad (zg_k_gather: the lanes read
+    // [src, src + len) of an entry and nothing else, and write [d_src + 64 + off, + len), which the reserve above covers)
+    const uint64_t at = (uint64_t)(uintptr_t)sc->d_src.p + 64;
+    for (uint32_t j = 0; j < g->n; j++) {
+      const DevEntry& en = g->e[g->idx[j]];
+      if (en.len > len || g->off[j] > len - en.len) { delete b; return ZG_INTERNAL; }
+      if (en.len) b->gather_segs_.push_back(zgs::Seg{en.src, at + g->off[j], en.len});
+    }
+    zgs::plan_chunks(b->gather_segs_.data(), (uint32_t)b->gather_segs_.size(), tn.scatter_chunk, &b->gather_chunks_);
+    if (b->gather_chunks_.size() > 0xFFFFFFFFull) { delete b; return ZG_INTERNAL; }
+    if (!b->gather_chunks_.empty()) {
+      const size_t sb = b->gather_segs_.size() * sizeof(zgs::Seg), cb = b->gather_chunks_.size() * sizeof(zgs::Chunk);
+      if ((st = b->d_gather_.reserve(sb + cb))) { delete b; return st; }
+      bool ok = true;
+      for (hipEvent_t& e : b->ev_gather_) ok = ok && (e || hipEventCreate(&e) == hipSuccess);
+      ok = ok && hipMemcpyAsync(b->d_gather_.p, b->gather_segs_.data(), sb, hipMemcpyHostToDevice, us) == hipSuccess;
+      ok = ok && hipMemcpyAsync((uint8_t*)b->d_gather_.p + sb, b->gather_chunks_.data(), cb, hipMemcpyHostToDevice, us) == hipSuccess;
+      ok = ok && hipEventRecord(b->ev_gather_[0], us) == hipSuccess;
+      if (ok) zg_launch_gather(b->d_gather_.as<zgs::Seg>(), (const zgs::Chunk*)((uint8_t*)b->d_gather_.p + sb), (uint32_t)b->gather_chunks_.size(), us);
+      ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(b->ev_gather_[1], us) == hipSuccess;
+      if (!ok) { delete b; return ZG_HIP_ERROR; }
+      b->gather_launched = true;
+    }
+  } else if (len && hipMemcpyAsync((uint8_t*)sc->d_src.p + 64, src, len, hipMemcpyHostToDevice, us) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
   (void)hipMemsetAsync((uint8_t*)sc->d_src.p + 64 + len, 0, 64, us);
   const uint32_t nslots = bb.nslots();
   if ((st = up(sc->d_blocks, bb.blocks.data(), nb * sizeof(ZgBlock))) || (st = up(sc->d_frames, bb.frames.data(), nf * sizeof(ZgFrame))) ||
@@ -605,6 +600,11 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
     if (hipEventRecord(sc->ev_up, us) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
     b->wait_upload = true;
   } else if (hipStreamSynchronize(stream_) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
+  if (b->gather_launched && !side) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, b->ev_gather_[0], b->ev_gather_[1]) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
+    b->gather_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  }
   *out = b;
   return ZG_OK;
 }

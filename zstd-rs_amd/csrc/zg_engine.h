@@ -26,17 +26,6 @@ struct DevBuf {
   template <typename T> T* as() const { return (T*)p; }
 };
 
-// What the host knows about each frame of a submit (header fields + where it sits in the input).
-struct FrameInfo {
-  FrameHeader header;
-  uint64_t window_size = 0;
-  uint64_t src_begin = 0, src_end = 0;   // byte range of the frame in the input (header .. checksum)
-  bool has_checksum = false;
-  uint32_t checksum = 0;                 // Content_Checksum read from the data
-  uint32_t nblocks = 0;
-  int host_status = 0;                   // error found while walking the frame (truncated input, bad header, ...)
-};
-
 // What one frame carries from one submit of its blocks to the next (the reference's DecoderScratch, scratch.rs:15-27):
 // the decode window (a dictionary's content sits in front of it), the offset history, and the Huffman / FSE tables a
 // later Treeless / Repeat block may decode with. The device holds [front pad][dictionary content][the last `have` bytes of
@@ -146,6 +135,8 @@ class Batch {
   bool all_declared = false;             //   output can be sized before the run, and the LZ77 stages enqueued without waiting for the scan
   bool presized = false;                 // the last run() did that
   bool exact_ran = false;                // sync(): zg_k_exact replayed the reference's buffer bookkeeping for this submit (tests)
+  bool gather_launched = false;          // prepare_entries_device: zg_k_gather brought the compressed bytes (no entry had any: no launch)
+  uint64_t gather_us = 0;                //   its time between two HIP events
 
   // Enqueue the kernel pipeline on the engine's streams. Two phases with one host round trip in between: the entropy
   // stages and the scan run first; the host reads the exact output size of every frame, sizes the output and the flatten
@@ -204,6 +195,10 @@ class Batch {
   DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
   hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
   bool scatter_on_ = false;
+  std::vector<zgs::Seg> gather_segs_;    // Engine::upload with a gather: the entries' segments and their chunks (the tables travel from here)
+  std::vector<zgs::Chunk> gather_chunks_;
+  DevBuf d_gather_;
+  hipEvent_t ev_gather_[2] = {nullptr, nullptr};
 };
 
 class Engine {
@@ -217,6 +212,18 @@ class Engine {
   // (parse_frames), its frames appended to ONE submit. walk[i] = the entry's walk status, its frames are [first_frame[i], first_frame[i + 1]).
   int prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
                       std::vector<int>* walk, std::vector<uint32_t>* first_frame);
+  // The same for entries whose compressed bytes lie in DEVICE memory of the caller (zgpu_decode_frames_device_src, which has checked every range
+  // against the runtime's allocations). walk_entries: zg_k_walk (zg_walk.h) follows the header chain of all n entries in two launches, count
+  // and emit, and brings back the skeleton: entry i's records are sk->recs[sk->first[i] .. sk->first[i + 1]), sk->ends[i] where its lane
+  // stopped. An entry of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP events), bytes downloaded.
+  // prepare_entries_device: entries idx[0 .. n) of that skeleton parsed with the host's one walk (parse_frames_skel) into ONE submit, as
+  // prepare_entries does with bytes; off[j] = where entry idx[j] lies in the submit's input (back to back, total bytes). The compressed bytes
+  // reach the engine's source buffer by ONE zg_k_gather launch instead of the H2D copy; everything behind that is shared.
+  struct DevEntry { uint64_t src, len; };
+  struct Skeleton { std::vector<zgw::Rec> recs; std::vector<uint64_t> first; std::vector<zgw::End> ends; };
+  int walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats);
+  int prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
+                             std::vector<int>* walk, std::vector<uint32_t>* first_frame);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes
@@ -252,21 +259,13 @@ class Engine {
   Scratch* acquire();
   void recycle(Scratch* s);
   int fail(hipError_t e, const char* what);
-  int upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool side = false);
+  struct GatherPlan { const DevEntry* e; const uint32_t* idx; const uint64_t* off; uint32_t n; };
+  // g: the len bytes come from device memory, entry g->idx[j] to offset g->off[j], by one zg_k_gather launch (src is not looked at)
+  int upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool side = false, const GatherPlan* g = nullptr);
 };
 
-// Host-only walk of concatenated frames into a BatchBuilder (no GPU involved; unit-tested on CPU).
-// base: offset of src in the buffer that will be uploaded (block bodies and FrameInfo::src_begin / src_end are counted from there)
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base = 0);
+// (parse_frames, split_frames and plaintext_bound: zg_host_parse.h)
 int parse_block_run(const uint8_t* src, size_t len, uint64_t window, bool has_checksum, const uint32_t hist[3], uint32_t carry_mask,
                     uint32_t max_blocks, BatchBuilder* bb, std::vector<FrameInfo>* info, size_t* consumed, bool* saw_last);
-// Byte ranges of the frames (and skippable frames) of a buffer, by walking frame and block headers only: what a work queue
-// needs to hand whole frames to different GPUs. Stops at the first malformed frame (its status is returned; ranges found so
-// far stay valid).
-struct FrameSpan { uint64_t begin, end; uint64_t content_size; bool has_content_size; bool skippable; };
-int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out);
-// Upper bound of the plaintext of a buffer of concatenated frames from frame and block headers only (a frame's declared content size when it
-// is smaller; a compressed block counts 128 KiB). Tolerant: the walk stops where a header cannot be read and returns what it found so far.
-uint64_t plaintext_bound(const uint8_t* src, size_t len);
 
 }  // namespace zg

@@ -11,7 +11,14 @@
 // submit cutting are shared (decode_submit, decode_entries); what differs is the sink of a submit's plaintext — the host sink downloads it and
 // copies it to the callers' buffers, the device sink leaves it where it is and lets zg_k_scatter (zg_scatter.h) copy the frames of every
 // successful entry to their destinations in one launch, and hashes on the device only. Every destination is checked against the HIP runtime's
-// allocations before anything is launched (check_device_dst): a wrong pointer becomes a status, never a GPU fault.
+// allocations before anything is launched (check_device_range): a wrong pointer becomes a status, never a GPU fault.
+//
+// zgpu_decode_frames_device_src is that call with the SOURCES in device memory too. The host still owns every verdict, the lineage and the
+// launch plan, but it reads a skeleton instead of the bytes: zg_k_walk (zg_walk.h) follows the header chain of every entry, one lane each, in
+// two launches for the whole call, and brings back a 32-byte record per frame header, block and checksum; parse_frames_skel and
+// plaintext_bound_skel (zg_host_parse.cpp) are the host's one walk run over those records. A submit's entries reach the engine's source buffer
+// by one zg_k_gather launch in place of the staging copy and the H2D (Engine::prepare_entries_device). Submit cutting, verdicts, the sink and
+// the again-list are the code above; an entry of the again-list is downloaded (one D2H) and decoded alone from the host copy.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -97,6 +104,12 @@ struct Call {
   zgpu_device_entry_result* dres = nullptr;        // device sink (zgpu_decode_frames_device): its results; hash_max is the caller's, no estimate
   bool no_hash = false;                            //   flags bit 0: hash no frame
   uint64_t* stats = nullptr;                       //   zgpu_ctx::frames_device_stats
+  // device sources (zgpu_decode_frames_device_src): srcs[i] is device memory; what was found out about every entry before the first submit
+  const Engine::Skeleton* sk = nullptr;            //   the records zg_k_walk brought back
+  const Engine::DevEntry* dev = nullptr;           //   the entries as the engine takes them (a refused entry: length 0)
+  const uint8_t* refused = nullptr;                //   entries whose source or destination failed the pointer check
+  const uint64_t* bound = nullptr;                 //   plaintext_bound of every entry, from its records
+  uint64_t* sstats = nullptr;                      //   zgpu_ctx::frames_device_src_stats
   zgpu_entry_result& result(uint32_t i) const { return dres ? dres[i].r : res[i]; }
 };
 
@@ -117,12 +130,17 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   uint64_t total_in = 0;
   for (uint32_t j = 0; j < n; j++) { off[j] = total_in; len[j] = k.lens[idx[j]]; total_in += len[j]; }
   Staging& in = u.in;
-  int st = in.get(total_in);
-  if (st) return st;
-  parallel_for(n, total_in, 8u << 20, [&](uint32_t j) { if (len[j]) memcpy(in.p + off[j], k.srcs[idx[j]], len[j]); });
   std::vector<int>& walk = u.walk;
   std::vector<uint32_t>& ff = u.ff;
-  if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff))) return st;
+  int st;
+  if (k.sk) {   // the bytes are on the device: no staging, no upload — the skeleton is parsed, one zg_k_gather launch moves the entries
+    if ((st = k.c->eng->prepare_entries_device(k.dev, *k.sk, idx, off.data(), n, total_in, &u.b, &walk, &ff))) return st;
+    k.sstats[3] += u.b->gather_launched ? 1u : 0u; k.sstats[4] += u.b->gather_us;
+  } else {
+    if ((st = in.get(total_in))) return st;
+    parallel_for(n, total_in, 8u << 20, [&](uint32_t j) { if (len[j]) memcpy(in.p + off[j], k.srcs[idx[j]], len[j]); });
+    if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff))) return st;
+  }
   Batch* b = u.b;
   b->drain_rule = ZG_DRAIN_DECODE_ALL;   // (as zgpu_decode_all: decode_all drains its DecodeBuffer every MiB, zg_exact.h)
   if ((st = b->run()) || (st = b->sync())) return st;
@@ -267,7 +285,8 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
 
 // an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
 // which also hashes what it hands out)
-int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr) {
+int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr, const uint8_t* host_src = nullptr) {
+  const uint8_t* src = host_src ? host_src : k.srcs[i];   // (device sources: the entry's bytes downloaded by decode_alone_device)
   zgpu_entry_result& r = k.result(i);
   memset(&r, 0, sizeof r);
   ZgFrameSums sums;
@@ -276,16 +295,16 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
   bool sums_ok = true;
   if (dict_walk) {
     // (what zgpu_decode_all does with this entry: its walk meets a dictionary frame, and dictionaries are registered)
-    st = zg_decode_all_per_frame(k.c, k.srcs[i], k.lens[i], dst, cap, &w, &sums);
+    st = zg_decode_all_per_frame(k.c, src, k.lens[i], dst, cap, &w, &sums);
   } else {
-    st = zgpu_decode_all(k.c, k.srcs[i], k.lens[i], dst, cap, &w);
+    st = zgpu_decode_all(k.c, src, k.lens[i], dst, cap, &w);
     if (!st) {
       // (Unsupported / Internal in a larger submit, but not alone — never seen; the status stays zgpu_decode_all's.) The checksums come from a
       // second, frame-by-frame pass into a buffer of its own; should that pass fail or disagree, the entry reports none rather than a wrong one.
       size_t w2 = 0;
       uint8_t* tmp = (uint8_t*)malloc(w ? w : 1);
       if (!tmp) return ZGPU_E_NOMEM;
-      const int s2 = zg_decode_all_per_frame(k.c, k.srcs[i], k.lens[i], tmp, w, &w2, &sums);
+      const int s2 = zg_decode_all_per_frame(k.c, src, k.lens[i], tmp, w, &w2, &sums);
       sums_ok = s2 == ZGPU_OK && w2 == w && (w == 0 || memcmp(tmp, dst, w) == 0);
       free(tmp);
       if (s2 == ZGPU_E_NOMEM || s2 == ZGPU_E_HIP) return s2;
@@ -297,7 +316,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
   if (summed) *summed = sums_ok;
   if (!sums_ok) {   // the frames are counted from their headers; no checksum is reported
     std::vector<FrameSpan> sp;
-    (void)split_frames(k.srcs[i], k.lens[i], &sp);
+    (void)split_frames(src, k.lens[i], &sp);
     r.written = w;
     for (const FrameSpan& x : sp) r.nframes += x.skippable ? 0u : 1u;
     return ZGPU_OK;
@@ -311,12 +330,19 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
 // the device sink's form of decode_alone: into a host buffer (no larger than the entry can need), then one H2D to the caller's memory. The host
 // hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
 int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
-  const uint64_t bound = plaintext_bound(k.srcs[i], k.lens[i]);
+  std::vector<uint8_t> down;   // device sources: the entry comes to the host with one D2H (rare; correct first)
+  if (k.sk) {
+    try { down.resize(k.lens[i] ? k.lens[i] : 1); } catch (...) { return ZGPU_E_NOMEM; }
+    if (k.lens[i] && hipMemcpy(down.data(), k.srcs[i], k.lens[i], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+    k.sstats[5] += k.lens[i];
+  }
+  const uint8_t* src = k.sk ? down.data() : k.srcs[i];
+  const uint64_t bound = plaintext_bound(src, k.lens[i]);
   const size_t cap = k.caps[i] < bound ? k.caps[i] : (size_t)bound;   // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i])
   uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
   if (!tmp) return ZGPU_E_NOMEM;
   bool summed = false;
-  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed);
+  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src);
   zgpu_device_entry_result& d = k.dres[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
@@ -332,10 +358,11 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   return st;
 }
 
-// Is [p, p + cap) device memory of one allocation on the context's device? Asked of the HIP runtime, before any launch. `known` remembers the
-// allocations already seen in this call: entries usually share a few (a torch tensor cut into slots).
+// Is [p, p + cap) device memory of one allocation on the context's device? Asked of the HIP runtime, before any launch, of every destination
+// and — zgpu_decode_frames_device_src — of every source. `known` remembers the allocations already seen in this call: entries usually share a
+// few (a torch tensor cut into slots).
 struct DevRange { uintptr_t lo, hi; };
-bool check_device_dst(int device, const void* p, size_t cap, std::vector<DevRange>& known) {
+bool check_device_range(int device, const void* p, size_t cap, std::vector<DevRange>& known) {
   if (!p) return false;
   const uintptr_t a = (uintptr_t)p;
   if (cap > UINTPTR_MAX - a) return false;
@@ -369,9 +396,10 @@ int decode_entries(Call& k, uint32_t n) {
       if (k.dres) memset(&k.dres[i], 0, sizeof k.dres[i]);
       else memset(&k.res[i], 0, sizeof k.res[i]);
       bool bad = (!k.srcs[i] && k.lens[i]) || (!k.dsts[i] && k.caps[i]);   // (what zgpu_decode_all returns)
-      if (!bad && k.dres && k.caps[i]) bad = !check_device_dst(c->eng->device(), k.dsts[i], k.caps[i], known);
+      if (k.sk) bad = k.refused[i] != 0;                                   // (device sources: checked before the walk)
+      else if (!bad && k.dres && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
       if (bad) { k.result(i).status = ZGPU_E_BAD_ARG; continue; }
-      bound = plaintext_bound(k.srcs[i], k.lens[i]);
+      bound = k.sk ? k.bound[i] : plaintext_bound(k.srcs[i], k.lens[i]);
     }
     // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
     // yield nothing — skippable frames, garbage — still travel to the device, through the pinned staging.)
@@ -414,6 +442,57 @@ extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs
   if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
   k.stats[0] = c->frames_submits;
   return st;
+}
+
+// Sources in device memory: every pointer is checked, every entry's header chain walked on the device (two launches for the whole call) and
+// its bound taken from the records, before the first submit is cut — then the call above, with the skeleton in place of the bytes.
+extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
+                                             const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
+  if (!c || (n && (!device_srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  for (uint64_t& x : c->frames_device_stats) x = 0;
+  for (uint64_t& x : c->frames_device_src_stats) x = 0;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  Call k{c, (const uint8_t* const*)device_srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
+  k.dres = results;
+  k.no_hash = opts && (opts->flags & 1u);
+  k.stats = c->frames_device_stats;
+  k.sstats = c->frames_device_src_stats;
+  std::vector<uint8_t> refused(n, 0);
+  std::vector<Engine::DevEntry> dev(n);
+  std::vector<uint64_t> bound(n, 0);
+  Engine::Skeleton sk;
+  {
+    std::vector<DevRange> known;
+    for (uint32_t i = 0; i < n; i++) {
+      bool bad = (!device_srcs[i] && lens[i]) || (!device_dsts[i] && caps[i]);
+      if (!bad && lens[i]) bad = !check_device_range(c->eng->device(), device_srcs[i], lens[i], known);
+      if (!bad && caps[i]) bad = !check_device_range(c->eng->device(), device_dsts[i], caps[i], known);
+      refused[i] = bad;
+      dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)device_srcs[i], bad ? 0u : (uint64_t)lens[i]};   // (a refused entry is not read)
+    }
+  }
+  int st = c->eng->walk_entries(dev.data(), n, &sk, k.sstats);
+  for (uint32_t i = 0; i < n && !st; i++) {
+    bool consistent = true;
+    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent);
+    if (!consistent) st = ZGPU_E_INTERNAL;
+  }
+  if (!st) {
+    k.sk = &sk; k.dev = dev.data(); k.refused = refused.data(); k.bound = bound.data();
+    st = decode_entries(k, n);
+  } else {
+    for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
+    c->frames_submits = 0;
+  }
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  k.stats[0] = c->frames_submits;
+  return st;
+}
+extern "C" int zgpu_debug_frames_device_src_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c || !out) return 0;
+  int k = 0;
+  for (; k < n && k < 6; k++) out[k] = c->frames_device_src_stats[k];
+  return k;
 }
 extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) {
   if (!c || !out) return 0;

@@ -111,7 +111,24 @@ void BatchBuilder::fail_frame(int status) {
   frame_failed_ = true;
 }
 
+// the bytes of a block body the host reads: its first min(content_size, 5) and, of a compressed block, the up to 4 at the sequences section header
+static void block_parts_of(const BlockHeader& bh, const uint8_t* body, uint8_t head[5], uint8_t seq[4]) {
+  memset(head, 0, 5);
+  memset(seq, 0, 4);
+  if (bh.type != ZG_BT_COMPRESSED) return;
+  const uint32_t n = bh.content_size;
+  memcpy(head, body, n < 5 ? n : 5);
+  uint32_t pos = 0, avail = 0;
+  if (zgw::seq_header_at(head, n, &pos, &avail)) memcpy(seq, body + pos, avail);
+}
+
 int BatchBuilder::add_block(const BlockHeader& bh, const uint8_t* body, uint64_t src_off) {
+  uint8_t head[5], seq[4];
+  block_parts_of(bh, body, head, seq);
+  return add_block_parts(bh, head, seq, src_off);
+}
+
+int BatchBuilder::add_block_parts(const BlockHeader& bh, const uint8_t head[5], const uint8_t seq[4], uint64_t src_off) {
   ZgBlock b;
   memset(&b, 0, sizeof b);
   b.src_off = src_off;
@@ -125,37 +142,18 @@ int BatchBuilder::add_block(const BlockHeader& bh, const uint8_t* body, uint64_t
     b.regen_size = bh.decompressed_size;
     out_bound += b.regen_size;
   } else {
-    // decompress_block (block_decoder.rs:97-197): header of the literals section
+    // decompress_block (block_decoder.rs:97-197): header of the literals section (zgw::lit_header, which zg_k_walk's lanes run too)
     const uint32_t n = bh.content_size;
     out_bound += kMaxBlockSize;
     do {
-      if (n == 0) { st = ZG_LITERALS_HEADER; break; }               // literals_section.rs:119 (no bits to read)
-      b.lit_type = body[0] & 3;
-      const unsigned sf = (body[0] >> 2) & 3;
-      unsigned need;
-      if (b.lit_type == ZG_LT_RAW || b.lit_type == ZG_LT_RLE) need = (sf == 0 || sf == 2) ? 1 : (sf == 1 ? 2 : 3);
-      else need = sf <= 1 ? 3 : (sf == 2 ? 4 : 5);
-      if (n < need) { st = ZG_LITERALS_HEADER; break; }             // NotEnoughBytes :124-129
-      uint32_t upper;
-      if (b.lit_type == ZG_LT_RAW || b.lit_type == ZG_LT_RLE) {     // :132-159
-        if (sf == 0 || sf == 2) b.regen_size = body[0] >> 3;
-        else if (sf == 1) b.regen_size = (body[0] >> 4) + ((uint32_t)body[1] << 4);
-        else b.regen_size = (body[0] >> 4) + ((uint32_t)body[1] << 4) + ((uint32_t)body[2] << 12);
-        upper = b.lit_type == ZG_LT_RLE ? 1 : b.regen_size;          // block_decoder.rs:120-127
-      } else {                                                      // :161-221
-        b.nstreams = sf == 0 ? 1 : 4;
-        if (sf <= 1) {
-          b.regen_size = (body[0] >> 4) + (((uint32_t)body[1] & 0x3f) << 4);
-          b.lit_comp_size = (body[1] >> 6) + ((uint32_t)body[2] << 2);
-        } else if (sf == 2) {
-          b.regen_size = (body[0] >> 4) + ((uint32_t)body[1] << 4) + (((uint32_t)body[2] & 0x3) << 12);
-          b.lit_comp_size = (body[2] >> 2) + ((uint32_t)body[3] << 6);
-        } else {
-          b.regen_size = (body[0] >> 4) + ((uint32_t)body[1] << 4) + (((uint32_t)body[2] & 0x3F) << 12);
-          b.lit_comp_size = (body[2] >> 6) + ((uint32_t)body[3] << 2) + ((uint32_t)body[4] << 10);
-        }
-        upper = b.lit_comp_size;
-      }
+      zgw::LitHdr lh;
+      const bool lit_ok = zgw::lit_header(head, n, &lh);
+      b.lit_type = lh.type;
+      if (!lit_ok) { st = ZG_LITERALS_HEADER; break; }               // literals_section.rs:119, :124-129
+      const unsigned need = lh.need;
+      const uint32_t upper = lh.upper;
+      b.regen_size = lh.regen;
+      if (b.lit_type >= ZG_LT_COMPRESSED) { b.nstreams = lh.nstreams; b.lit_comp_size = lh.comp; }
       b.lit_off = need;
       if (n - need < upper) { st = ZG_MALFORMED_SECTION_HEADER; break; }  // block_decoder.rs:129-134
       if (b.lit_type == ZG_LT_COMPRESSED) {
@@ -165,7 +163,7 @@ int BatchBuilder::add_block(const BlockHeader& bh, const uint8_t* body, uint64_t
       }
       if (b.lit_type >= ZG_LT_COMPRESSED) b.huf_slot = cur_.huf;
       // sequences section header (sequence_section.rs:108-167)
-      const uint8_t* s = body + need + upper;
+      const uint8_t* s = seq;   // (the bytes at body + need + upper: the first min(rem, 4))
       const uint32_t rem = n - need - upper;
       if (rem == 0) { seq_st = ZG_SEQUENCES_HEADER; break; }
       unsigned shl;
@@ -403,6 +401,229 @@ void BatchBuilder::finish() {
       }
     }
   }
+}
+
+
+// ---- the walk of concatenated frames, over bytes or over the skeleton records of zg_k_walk (zg_walk.h) -------------------------------
+// A source hands the walk the bytes it reads, and nothing else: the header of the frame at p (up to 18 bytes), a block's 3 header bytes, the
+// parts of a block body add_block_parts reads, the 4 checksum bytes.
+namespace {
+struct ByteSource {
+  const uint8_t* src;
+  size_t len;
+  size_t frame_header(size_t p, uint8_t out[zgw::kFrameBytes]) {
+    const size_t n = len - p < zgw::kFrameBytes ? len - p : zgw::kFrameBytes;
+    memcpy(out, src + p, n);
+    return n;
+  }
+  void block_header(size_t p, uint8_t out[3]) { memcpy(out, src + p, 3); }
+  void block_parts(size_t body, const BlockHeader& bh, uint8_t head[5], uint8_t seq[4]) { block_parts_of(bh, src + body, head, seq); }
+  void checksum(size_t p, uint8_t out[4]) { memcpy(out, src + p, 4); }
+  void checksum_short(size_t) {}
+};
+// records in the order the lane emitted them, which is the order the walk asks in; every answer is checked against what the walk expects
+struct SkelSource {
+  const zgw::Rec* recs;
+  uint32_t nrec;
+  size_t len;
+  uint32_t k = 0;
+  bool ok = true;
+  const zgw::Rec* cur = nullptr;   // the block record block_header() took
+  const zgw::Rec* take(uint32_t kind, uint64_t off) {
+    static const zgw::Rec none{};
+    if (k < nrec && recs[k].kind == kind && recs[k].off == off) return &recs[k++];
+    ok = false;
+    return &none;
+  }
+  size_t frame_header(size_t p, uint8_t out[zgw::kFrameBytes]) {
+    const size_t n = len - p < zgw::kFrameBytes ? len - p : zgw::kFrameBytes;
+    const zgw::Rec* r = take(zgw::kFrame, p);
+    if (r->have != n) ok = false;
+    memcpy(out, r->b, zgw::kFrameBytes);
+    return ok ? n : 0;
+  }
+  void block_header(size_t p, uint8_t out[3]) { cur = take(zgw::kBlock, p + 3); memcpy(out, cur->b, 3); }
+  void block_parts(size_t, const BlockHeader& bh, uint8_t head[5], uint8_t seq[4]) {
+    memset(head, 0, 5);
+    memset(seq, 0, 4);
+    if (bh.type != ZG_BT_COMPRESSED || !cur) return;
+    const uint32_t n = bh.content_size;
+    uint32_t pos = 0, avail = 0;
+    memcpy(head, cur->b + 3, 5);
+    if (cur->have != (n < 5 ? n : 5)) ok = false;
+    if (!zgw::seq_header_at(head, n, &pos, &avail)) avail = 0;
+    if (cur->have2 != avail) ok = false;
+    memcpy(seq, cur->b + 8, 4);
+  }
+  void checksum(size_t p, uint8_t out[4]) { const zgw::Rec* r = take(zgw::kCksum, p); if (r->have != 4) ok = false; memcpy(out, r->b, 4); }
+  void checksum_short(size_t p) { const zgw::Rec* r = take(zgw::kCksum, p); if (r->have != len - p) ok = false; }
+};
+
+template <class S> int parse_frames_on(S& s, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
+  // FrameDecoder::decode_all (frame_decoder.rs:541-577): concatenated frames, skippable frames skipped;
+  // the first error ends the walk (the reference returns it).
+  size_t p = 0;
+  static const uint32_t kHist[3] = {1, 4, 8};  // scratch.rs:44
+  while (p < len) {
+    FrameHeader h;
+    size_t c;
+    uint32_t sm = 0, sl = 0;
+    uint8_t fh[zgw::kFrameBytes];
+    const size_t fn = s.frame_header(p, fh);
+    int st = read_frame_header(fh, fn, &h, &c, &sm, &sl);
+    if (st == ZG_SKIP_FRAME) {
+      p += c;
+      if ((size_t)sl > len - p) return ZG_FAILED_SKIP_FRAME;  // :550-556
+      p += sl;
+      continue;
+    }
+    if (st) return st;
+    uint64_t w;
+    if ((st = frame_window_size(h, &w))) return st;
+    if (w > max_window) return ZG_WINDOW_SIZE_TOO_BIG;          // frame_decoder.rs:137-145
+    if (h.has_dict_id) return ZG_DICT_NOT_PROVIDED;             // :212-217 (dictionaries: see DESIGN.md "next")
+    FrameInfo fi;
+    fi.header = h;
+    fi.window_size = w;
+    fi.src_begin = base + p;
+    p += c;
+    bb->begin_frame(w, kHist, 0);
+    for (;;) {
+      if (len - p < 3) { st = ZG_FAILED_READ_BLOCK_HEADER; break; }
+      BlockHeader bh;
+      uint8_t hb[3];
+      s.block_header(p, hb);
+      if ((st = read_block_header(hb, &bh))) break;
+      p += 3;
+      if (len - p < bh.content_size) { st = ZG_FAILED_READ_BLOCK_BODY; break; }
+      uint8_t head[5], seq[4];
+      s.block_parts(p, bh, head, seq);
+      st = bb->add_block_parts(bh, head, seq, base + p);
+      p += bh.content_size;
+      fi.nblocks++;
+      if (st) break;
+      if (bh.last) {
+        if (h.content_checksum()) {
+          if (len - p < 4) { st = ZG_FAILED_READ_CHECKSUM; break; }
+          uint8_t ck[4];
+          s.checksum(p, ck);
+          memcpy(&fi.checksum, ck, 4);
+          fi.has_checksum = true;
+          p += 4;
+        }
+        break;
+      }
+    }
+    fi.src_end = base + p;
+    fi.host_status = st;
+    info->push_back(fi);
+    if (st) return st;
+  }
+  return ZG_OK;
+}
+
+template <class S> uint64_t plaintext_bound_on(S& s, size_t len) {
+  uint64_t total = 0;
+  size_t p = 0;
+  while (p < len) {
+    FrameHeader h;
+    size_t c;
+    uint32_t sm = 0, sl = 0;
+    uint8_t fh[zgw::kFrameBytes];
+    const size_t fn = s.frame_header(p, fh);
+    int st = read_frame_header(fh, fn, &h, &c, &sm, &sl);
+    if (st == ZG_SKIP_FRAME) { p += c; if ((size_t)sl > len - p) break; p += sl; continue; }
+    if (st) break;
+    p += c;
+    uint64_t fb = 0;
+    bool ok = false;
+    while (len - p >= 3) {
+      BlockHeader bh;
+      uint8_t hb[3];
+      s.block_header(p, hb);
+      if (read_block_header(hb, &bh)) break;
+      p += 3;
+      fb += bh.type == ZG_BT_COMPRESSED ? (uint64_t)kMaxBlockSize : (uint64_t)bh.decompressed_size;
+      if (len - p < bh.content_size) break;
+      p += bh.content_size;
+      if (bh.last) {
+        ok = true;
+        if (h.content_checksum()) {
+          if (len - p < 4) s.checksum_short(p);
+          else { uint8_t ck[4]; s.checksum(p, ck); }
+          p += len - p < 4 ? len - p : 4;
+        }
+        break;
+      }
+    }
+    total += h.has_fcs() && h.frame_content_size < fb ? h.frame_content_size : fb;
+    if (!ok) break;
+  }
+  return total;
+}
+}  // namespace
+
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
+  ByteSource s{src, len};
+  return parse_frames_on(s, len, max_window, bb, info, base);
+}
+uint64_t plaintext_bound(const uint8_t* src, size_t len) {
+  ByteSource s{src, len};
+  return plaintext_bound_on(s, len);
+}
+int parse_frames_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info,
+                      uint64_t base, bool* consistent) {
+  SkelSource s{recs, nrec, len};
+  const int st = parse_frames_on(s, len, max_window, bb, info, base);
+  *consistent = s.ok;
+  return st;
+}
+uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent) {
+  SkelSource s{recs, nrec, len};
+  const uint64_t b = plaintext_bound_on(s, len);
+  *consistent = s.ok && s.k == nrec;   // (the bound's walk goes as far as the lane's: every record is asked for)
+  return b;
+}
+
+int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out) {
+  // the walk of parse_frames without the section headers: frame header, then block headers up to the last block
+  size_t p = 0;
+  while (p < len) {
+    FrameHeader h;
+    size_t c;
+    uint32_t sm = 0, sl = 0;
+    FrameSpan sp;
+    sp.begin = p; sp.content_size = 0; sp.has_content_size = false; sp.skippable = false;
+    int st = read_frame_header(src + p, len - p, &h, &c, &sm, &sl);
+    if (st == ZG_SKIP_FRAME) {
+      p += c;
+      if ((size_t)sl > len - p) return ZG_FAILED_SKIP_FRAME;
+      p += sl;
+      sp.end = p; sp.skippable = true;
+      out->push_back(sp);
+      continue;
+    }
+    if (st) return st;
+    p += c;
+    for (;;) {
+      if (len - p < 3) return ZG_FAILED_READ_BLOCK_HEADER;
+      BlockHeader bh;
+      if ((st = read_block_header(src + p, &bh))) return st;
+      p += 3;
+      if (len - p < bh.content_size) return ZG_FAILED_READ_BLOCK_BODY;
+      p += bh.content_size;
+      if (bh.last) {
+        if (h.content_checksum()) {
+          if (len - p < 4) return ZG_FAILED_READ_CHECKSUM;
+          p += 4;
+        }
+        break;
+      }
+    }
+    sp.end = p; sp.content_size = h.frame_content_size; sp.has_content_size = h.has_fcs();
+    out->push_back(sp);
+  }
+  return ZG_OK;
 }
 
 }  // namespace zg

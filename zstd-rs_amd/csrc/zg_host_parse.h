@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <vector>
 #include "zg_types.h"
+#include "zg_walk.h"
 
 namespace zg {
 
@@ -98,6 +99,10 @@ class BatchBuilder {
   // Add one block of the current frame. body points at Block_Content (content_size bytes available).
   // src_off is the body's offset in the buffer that will be uploaded. Returns the block's host status.
   int add_block(const BlockHeader& bh, const uint8_t* body, uint64_t src_off);
+  // The same from the few bytes of the body the host reads (add_block is a wrapper of this): head = the first min(content_size, 5) body
+  // bytes, seq = the up to 4 bytes at the sequences section header (zgw::seq_header_at says where and how many), both zero-padded. What a
+  // skeleton record of zg_k_walk carries (zg_walk.h). Blocks that are not compressed read neither.
+  int add_block_parts(const BlockHeader& bh, const uint8_t head[5], const uint8_t seq[4], uint64_t src_off);
   // Mark the current frame as failed at its next block (host-side errors: truncated input, reserved block...).
   void fail_frame(int status);
   // Resolve slot numbers and build the work lists. Call once after the last block.
@@ -114,5 +119,35 @@ class BatchBuilder {
   static constexpr int32_t kCarry = -3;
   static constexpr int32_t kCarryHuf = -3;
 };
+
+// What the host knows about each frame of a submit (header fields + where it sits in the input).
+struct FrameInfo {
+  FrameHeader header;
+  uint64_t window_size = 0;
+  uint64_t src_begin = 0, src_end = 0;   // byte range of the frame in the input (header .. checksum)
+  bool has_checksum = false;
+  uint32_t checksum = 0;                 // Content_Checksum read from the data
+  uint32_t nblocks = 0;
+  int host_status = 0;                   // error found while walking the frame (truncated input, bad header, ...)
+};
+
+// Host-only walk of concatenated frames into a BatchBuilder (no GPU involved; unit-tested on CPU).
+// base: offset of src in the buffer that will be uploaded (block bodies and FrameInfo::src_begin / src_end are counted from there)
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base = 0);
+// Byte ranges of the frames (and skippable frames) of a buffer, by walking frame and block headers only: what a work queue
+// needs to hand whole frames to different GPUs. Stops at the first malformed frame (its status is returned; ranges found so
+// far stay valid).
+struct FrameSpan { uint64_t begin, end; uint64_t content_size; bool has_content_size; bool skippable; };
+int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out);
+// Upper bound of the plaintext of a buffer of concatenated frames from frame and block headers only (a frame's declared content size when it
+// is smaller; a compressed block counts 128 KiB). Tolerant: the walk stops where a header cannot be read and returns what it found so far.
+uint64_t plaintext_bound(const uint8_t* src, size_t len);
+// parse_frames and plaintext_bound of an entry of len bytes that lies in device memory, from the skeleton records zg_k_walk brought back
+// (zg_walk.h): the same walk — one body, instantiated for bytes and for records — reading every byte it asks for from the records.
+// *consistent = false: the records are not what a walk of len bytes asks for, in kind, position or count of bytes (never, unless the
+// source changed while it was walked); the results mean nothing then.
+int parse_frames_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info,
+                      uint64_t base, bool* consistent);
+uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent);
 
 }  // namespace zg

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "zg_types.h"
 #include "zg_scatter.h"
+#include "zg_walk.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -43,3 +44,9 @@ struct ZgHashRange { uint64_t off, len; uint32_t slot, pad; };
 void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s);
 // zg_k_scatter (zg_scatter.h): the chunks of the segments of a batch's output (base) to the segments' destinations, one workgroup per chunk
 void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);
+// zg_k_gather (zg_walk.h): the same chunks the other way round — segments whose src_off is an ADDRESS in device memory of the caller (the entries
+// of a submit of zgpu_decode_frames_device_src) copied to where the engine's kernels read the compressed bytes; dst: addresses in the engine's buffer
+void zg_launch_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);
+// zg_k_walk (zg_walk.h): one lane per entry follows the entry's header chain; ends[i] = where lane i stopped and how many skeleton records it has.
+// recs == nullptr: the count pass (nothing else is written); else lane i writes records lanes[i].first .. + lanes[i].limit of recs
+void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec* recs, hipStream_t s);

@@ -1813,6 +1813,49 @@ void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chu
   if (nchunks) hipLaunchKernelGGL(zg_k_scatter, dim3(nchunks < zgs::kMaxGroups ? nchunks : zgs::kMaxGroups), dim3(zgs::kThreads), 0, s, base, segs, chunks, nchunks);
 }
 
+// The entries of a submit whose compressed bytes lie in the caller's device memory (zgpu_decode_frames_device_src) copied back to back behind the
+// front pad of the engine's source buffer: zg_k_scatter's plan and lane routine with the roles swapped — the source is an address the host
+// checked against the runtime's allocations, the destination the engine's own buffer. Reads stay inside [src, src + len) of the entry.
+struct ZgGatherRead {   // (global memory, as the host checked: global_load_*, not flat_load_*)
+  __device__ __forceinline__ uint8_t ld1(uint64_t addr) const { return *(const __attribute__((address_space(1))) uint8_t*)addr; }
+  __device__ __forceinline__ zgs::V16 ld16(uint64_t addr) const { zgs::V16 v; __builtin_memcpy(&v, (const __attribute__((address_space(1))) void*)addr, 16); return v; }
+};
+__global__ void __launch_bounds__(256) zg_k_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks) {
+  const ZgGatherRead r{};
+  const ZgScatterWrite w{};
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const zgs::Chunk ch = chunks[c];
+    const zgs::Seg sg = segs[ch.seg];
+    zgs::copy_chunk(r, w, sg.src_off + ch.at, sg.dst + ch.at, ch.len, threadIdx.x, zgs::kThreads);
+  }
+}
+void zg_launch_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(zg_k_gather, dim3(nchunks < zgs::kMaxGroups ? nchunks : zgs::kMaxGroups), dim3(zgs::kThreads), 0, s, segs, chunks, nchunks);
+}
+
+// The header chain of entries that lie in device memory, one lane per entry (zg_walk.h has the routine, the record layout and the ISA notes).
+// The host checked every [src, src + len) against the runtime's allocations; a lane reads nothing outside it and writes its own records only.
+struct ZgWalkRead {
+  uint64_t base;
+  __device__ __forceinline__ uint8_t ld1(uint64_t off) const { return *(const __attribute__((address_space(1))) uint8_t*)(base + off); }
+};
+struct ZgWalkWrite {
+  zgw::Rec* recs;
+  __device__ __forceinline__ void put(uint64_t i, const zgw::Rec& x) const { recs[i] = x; }
+};
+template <bool EMIT> __global__ void __launch_bounds__(zgw::kThreads) zg_k_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec* recs) {
+  const uint32_t i = blockIdx.x * zgw::kThreads + threadIdx.x;
+  if (i >= n) return;
+  const zgw::Lane l = lanes[i];
+  ends[i] = zgw::walk_entry<EMIT>(ZgWalkRead{l.src}, ZgWalkWrite{recs}, l.len, l.first, l.limit);
+}
+void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec* recs, hipStream_t s) {
+  if (!n) return;
+  const dim3 g((n + zgw::kThreads - 1) / zgw::kThreads), t(zgw::kThreads);
+  if (recs) hipLaunchKernelGGL(zg_k_walk<true>, g, t, 0, s, lanes, n, ends, recs);
+  else hipLaunchKernelGGL(zg_k_walk<false>, g, t, 0, s, lanes, n, ends, recs);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

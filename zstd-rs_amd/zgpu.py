@@ -103,6 +103,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
     "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
@@ -170,6 +171,8 @@ def _declare(L):
     L.zgpu_decode_frames.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(EntryResultC)]
     L.zgpu_decode_frames_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
     L.zgpu_debug_frames_device_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_decode_frames_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
+    L.zgpu_debug_frames_device_src_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_plaintext_bound.argtypes = [u8p, sz]
     L.zgpu_plaintext_bound.restype = C.c_uint64
     L.zgpu_debug_frames_submits.argtypes = [vp]
@@ -413,6 +416,10 @@ class Context:
         del keep
         if st:
             raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return self._device_results(res, n)
+
+    @staticmethod
+    def _device_results(res, n):
         outl = []
         for i in range(n):
             d, e = res[i], DeviceEntryResult()
@@ -430,6 +437,68 @@ class Context:
         k = self.L.zgpu_debug_frames_device_stats(self.h, a, 7)
         keys = ["submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed", "entries_alone"]
         return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    def decode_frames_device_src(self, src_ptrs, lens, dst_ptrs, caps, hash_max=0, no_hash=False):
+        """zgpu_decode_frames_device_src: decode_frames_device with the compressed input in DEVICE memory too. src_ptrs[i] is the address of
+        lens[i] bytes on this context's device (any alignment), dst_ptrs[i] of caps[i] bytes; sources pass the same check as destinations
+        (a pointer that is not such memory gives that entry E_BAD_ARG), are never written, and no byte outside [src, src + len) is read.
+        Nothing in flight may write the sources or touch the destinations during the call. Results are those of decode_frames_device on a
+        host copy of the same bytes. Returns one DeviceEntryResult per entry."""
+        n = len(src_ptrs)
+        if len(lens) != n or len(dst_ptrs) != n or len(caps) != n:
+            raise ValueError("decode_frames_device_src: one length, one destination and one capacity per source")
+        srcs, lena = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            srcs[i], lena[i] = int(src_ptrs[i]) or None, int(lens[i])
+            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
+        opts = DeviceOptsC(int(hash_max), 1 if no_hash else 0, 0)
+        res = (DeviceEntryResultC * max(n, 1))()
+        st = self.L.zgpu_decode_frames_device_src(self.h, srcs, lena, n, dsts, capa, C.byref(opts), res)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return self._device_results(res, n)
+
+    def frames_device_src_stats(self):
+        """the last decode_frames_device_src call (zgpu_debug_frames_device_src_stats)"""
+        a = (C.c_uint64 * 6)()
+        k = self.L.zgpu_debug_frames_device_src_stats(self.h, a, 6)
+        keys = ["walk_launches", "walk_us", "skeleton_bytes", "gather_launches", "gather_us", "input_bytes_to_host"]
+        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    @staticmethod
+    def _one_hip_runtime():
+        hip = set(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln) if os.path.exists("/proc/self/maps") else ()
+        if len(hip) > 1:
+            raise RuntimeError("two HIP runtimes are loaded (%s): import torch before creating the first zgpu.Context" % ", ".join(sorted(hip)))
+
+    def decode_tensors(self, tensors, caps=None, hash_max=0, no_hash=False):
+        """decode_frames_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
+        compressed bytes. The plaintext goes to ONE new torch.uint8 tensor, every entry's slot 256-byte aligned with caps[i] bytes of room.
+        caps=None sizes the slots with zgpu_plaintext_bound, which reads the bytes on the HOST: the inputs are downloaded once for that, so a
+        caller that wants no byte of the input to cross passes caps. Returns (tensors, results) like decode_frames_to_tensors, under the same
+        single-runtime rule (import torch before creating the first Context). torch is imported here, not by `import zgpu`."""
+        import torch
+        self._one_hip_runtime()
+        n = len(tensors)
+        dev = torch.device("cuda", self.device)
+        for t in tensors:
+            if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise ValueError("decode_tensors: contiguous torch.uint8 tensors on %s" % dev)
+        if caps is None:
+            caps = [plaintext_bound(t.cpu().numpy().tobytes()) for t in tensors]
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (int(c) + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=dev)
+        # the inputs may still be written, and the caching allocator may hand out memory that is still in use, on torch's stream
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+        base = buf.data_ptr()
+        res = self.decode_frames_device_src([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors],
+                                            [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
+        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
 
     def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False):
         """decode_frames_device into ONE torch.uint8 tensor on this context's device, every entry's slot 256-byte aligned (caps: bytes of room per
