@@ -206,6 +206,67 @@ int zgpu_decode_frames_device_src(zgpu_ctx*, const void* const* device_srcs, con
  * zgpu_debug_frames_device_stats is filled by that call as well. Returns how many were written. */
 int zgpu_debug_frames_device_src_stats(const zgpu_ctx*, uint64_t* out, int n);
 
+/* ---- what device-resident compressed input holds: bounds and frame tables without a download -----------------------------------------------
+ * zgpu_decode_frames_device_src needs caps[i], and zgpu_plaintext_bound reads host memory. These calls answer the sizing question — and how many
+ * frames an entry has, where they start, which declare a content size, name a dictionary or carry a checksum — for entries that lie in device
+ * memory, from frame and block headers alone: one lane per entry follows the header chain on the device (zg_k_index) and reads three bytes per
+ * block, never a block body; a fixed-size summary per entry (and, for the table, a record per frame) comes back, no byte of the input does.
+ *  - Sources pass the check of zgpu_decode_frames_device_src before anything is launched; an entry that fails gets ZGPU_E_BAD_ARG in
+ *    entries[i].status, every other field 0, and the others are unaffected. lens[i] == 0 is neither checked nor read.
+ *  - No lane reads a byte outside [src, src + lens[i]) — an entry may end flush with its allocation — and nothing is written to a source. The
+ *    caller guarantees that nothing in flight writes the sources during the call.
+ *  - The calls return with the engine's streams synchronised; the return value reports engine failures only. Results do not depend on the order
+ *    of the entries.
+ *  - What the index says agrees with what a decode reports: for an entry whose zgpu_decode_frames_device_src status is 0, nframes equals
+ *    r.nframes and r.written <= bound. */
+/* why a header chain ended (zgpu_entry_index.why): no verdict — a decode of the entry decides its status */
+enum {
+  ZGPU_CHAIN_END = 0,                 /* the chain reached the end of the entry */
+  ZGPU_CHAIN_SHORT_HEADER = 1,        /* a frame header that is not all there */
+  ZGPU_CHAIN_BAD_MAGIC = 2,
+  ZGPU_CHAIN_SKIP_PAST_END = 3,       /* a skippable frame's length leads past the entry */
+  ZGPU_CHAIN_SHORT_BLOCK_HEADER = 4,  /* fewer than 3 bytes left where a block header is due */
+  ZGPU_CHAIN_RESERVED_BLOCK = 5,
+  ZGPU_CHAIN_BLOCK_TOO_LARGE = 6,     /* Block_Size above 128 KiB */
+  ZGPU_CHAIN_BODY_PAST_END = 7,
+  ZGPU_CHAIN_SHORT_CHECKSUM = 8
+};
+typedef struct {
+  uint64_t bound;       /* == zgpu_plaintext_bound of a host copy of the entry, always */
+  uint64_t chain_end;   /* offset in the entry at which the header chain ended */
+  uint32_t status;      /* 0, or ZGPU_E_BAD_ARG: the source failed the pointer check (then every other field is 0) */
+  uint32_t nframes;     /* zstd frames whose header the chain read (skippable frames not counted) */
+  uint32_t nskippable;
+  uint32_t nblocks;     /* block headers read, over all frames */
+  uint32_t why;         /* why the chain ended: ZGPU_CHAIN_*; 0 = it reached the end of the entry */
+  uint32_t flags;       /* of the zstd frames counted in nframes (all 0 if there is none) — bit 0: every one declares Frame_Content_Size;
+                           bit 1: some frame names a dictionary id; bit 2: some frame carries a Content_Checksum; bit 3: every frame is
+                           complete (last block seen, checksum all there) */
+} zgpu_entry_index;
+typedef struct {
+  uint64_t src_begin, src_end;   /* the frame's bytes in its entry; src_end = where the chain left it */
+  uint64_t bound;                /* this frame's share of the entry's bound */
+  uint64_t frame_content_size;   /* 0 if absent */
+  uint64_t window_size;          /* as zgpu_frame_info.window_size; 0 for a skippable frame or an unreadable header */
+  uint32_t entry, nblocks;
+  uint32_t dict_id;              /* 0 if absent */
+  uint32_t flags;                /* bit 0 skippable, bit 1 has Frame_Content_Size, bit 2 has Content_Checksum, bit 3 complete, bit 4 single segment */
+  uint32_t header_status;        /* what read_frame_header says about the header bytes: 0, ZGPU_E_SKIP_FRAME, or its error */
+  uint32_t skip_magic;           /* skippable frames: the magic (the low nibble is the caller's), else 0 */
+} zgpu_frame_index;
+/* entries[i] for every entry; one launch, 48 bytes per entry come back, no byte of the input does */
+int zgpu_frames_index_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries);
+/* the same plus a frame table: frames[0 .. *nframes_out), entry by entry in input order, frame_first[i] .. frame_first[i + 1] are entry i's
+ * (frame_first has n + 1 slots): its zstd frames and skippable frames in order, tiling [0, chain_end), and — where the chain ended at a frame
+ * header it could not read — one last record for that header (src_begin == src_end, header_status says what is wrong with it). Two launches:
+ * the summaries, a prefix sum on the host, then every lane writes its own records (64 bytes each come back). frames_cap too small:
+ * ZGPU_E_TARGET_TOO_SMALL, *nframes_out = the count needed, entries[] and frame_first[] are still filled (one launch). */
+int zgpu_frames_table_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries,
+                             uint64_t* frame_first, zgpu_frame_index* frames, size_t frames_cap, size_t* nframes_out);
+/* diagnostics of the context's last index / table call: out[0] launches, [1] kernel microseconds (HIP events), [2] bytes downloaded,
+ * [3] input bytes that crossed to the host (always 0). Returns how many were written. */
+int zgpu_debug_frames_index_stats(const zgpu_ctx*, uint64_t* out, int n);
+
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of
  * FrameDecoder::decode_all (frame_decoder.rs:541-577), which decodes the frames of a buffer one after the other. */

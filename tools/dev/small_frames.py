@@ -27,7 +27,14 @@ compressed input that lies in device memory (one torch tensor, entries back to b
 caller takes without it — download the inputs to the host (one D2H of the tensor), then zgpu_decode_frames_device — in one process and its
 second context, interleaved, best of 5 after a warm-up each; the walk's and the gather's own times and the skeleton's size
 (zgpu_debug_frames_device_src_stats) beside the scatter's. 1x1024M is ONE frame of 8192 blocks: the walk lane's worst case. Prints one
-JSON object."""
+JSON object.
+
+  python tools/dev/small_frames.py --index [workload ...]       (default: corpus101 4096x128K 1x1024M)
+
+what device-resident entries hold, without a download: zgpu_frames_index_device (one zg_k_index launch, the summary pass) and
+zgpu_frames_table_device (summary pass + emit pass) on the entries in one torch tensor, kernel times from zgpu_debug_frames_index_stats (HIP
+events, best of 5 after a warm-up), every bound checked against zgpu_plaintext_bound of the host copy; beside them zg_k_walk's time — count and
+emit pass together — from zgpu_debug_frames_device_src_stats of a decode of the same entries. Prints one JSON object."""
 import json
 import os
 import sys
@@ -168,7 +175,57 @@ def device_src_main(args):
     print(json.dumps(out))
 
 
+def index_main(args):
+    import torch
+    names = [a for a in args if not a.startswith("--")] or ["corpus101", "4096x128K", "1x1024M"]
+    ctx = zgpu.Context(0)
+    out = {}
+    for name in names:
+        ent, caps = device_workload(name)
+        lens = [len(z) for z in ent]
+        soffs, at = [], 0
+        for n in lens:
+            soffs.append(at)
+            at += n
+        src = torch.frombuffer(bytearray(b"".join(ent)), dtype=torch.uint8).to("cuda:0")
+        torch.cuda.synchronize()
+        sptrs = [src.data_ptr() + o for o in soffs]
+        idx = ctx.frames_index_device(sptrs, lens)
+        bounds = {}
+        for z, e in zip(ent, idx):
+            if id(z) not in bounds:
+                bounds[id(z)] = zgpu.plaintext_bound(z)
+            assert e.status == 0 and e.bound == bounds[id(z)]
+        summary, table = [], []
+        for _ in range(5):
+            ctx.frames_index_device(sptrs, lens)
+            summary.append(ctx.frames_index_stats())
+            _, _, frames = ctx.frames_table_device(sptrs, lens, room=sum(e.nframes + e.nskippable for e in idx) + len(ent))
+            table.append(ctx.frames_index_stats())
+        offs, total = [], 0
+        for e in idx:
+            offs.append(total)
+            total += (e.bound + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        walk = []
+        for _ in range(3):
+            r = ctx.decode_frames_device_src(sptrs, lens, [buf.data_ptr() + o for o in offs], [e.bound for e in idx], no_hash=True)
+            assert all(x.status == 0 for x in r)
+            walk.append(ctx.frames_device_src_stats())
+        assert all(x.nframes == e.nframes and x.written <= e.bound for x, e in zip(r, idx))
+        out[name] = {"entries": len(ent), "input_MiB": at / 2 ** 20, "frames": len(frames), "blocks": sum(e.nblocks for e in idx),
+                     "summary_pass_us": min(x["kernel_us"] for x in summary), "summary": summary[-1],
+                     "table_two_passes_us": min(x["kernel_us"] for x in table), "table": table[-1],
+                     "zg_k_walk_two_passes_us": min(x["walk_us"] for x in walk), "walk": walk[-1]}
+        del buf, src
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
+    if "--index" in sys.argv[1:]:
+        return index_main([a for a in sys.argv[1:] if a != "--index"])
     if "--device-src" in sys.argv[1:]:
         return device_src_main([a for a in sys.argv[1:] if a != "--device-src"])
     if "--device" in sys.argv[1:]:

@@ -23,6 +23,7 @@ struct zgpu_ctx {
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
   uint64_t frames_device_stats[7] = {0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
   uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)
+  uint64_t frames_index_stats[4] = {0, 0, 0, 0};              // of the last zgpu_frames_index_device / zgpu_frames_table_device call (zgpu_debug_frames_index_stats)
   std::string err;
 };
 

@@ -405,6 +405,45 @@ int Engine::walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* 
   return ZG_OK;
 }
 
+namespace {
+struct IndexTmp {   // device memory and events of one index_entries / index_frames call
+  DevBuf lanes, ents, recs;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~IndexTmp() {
+    lanes.release(); ents.release(); recs.release();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+}  // namespace
+
+int Engine::index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, const zgi::Entry* sum, zgi::Entry* out, zgi::FrameRec* recs, uint64_t* stats) {
+  Engine* eng = this;
+  if (!n) return ZG_OK;
+  ZG_HIP(hipSetDevice(device_));
+  hipStream_t s = stream_;
+  IndexTmp t;
+  const uint64_t total = first ? first[n] : 0;
+  std::vector<zgw::Lane> lanes(n);
+  for (uint32_t i = 0; i < n; i++) lanes[i] = zgw::Lane{e[i].src, e[i].len, first ? first[i] : 0, first ? (uint64_t)sum[i].nrec : 0};
+  int st;
+  if ((st = t.lanes.reserve((size_t)n * sizeof(zgw::Lane))) || (st = t.ents.reserve((size_t)n * sizeof(zgi::Entry)))) return st;
+  if (first && (st = t.recs.reserve((total ? total : 1) * sizeof(zgi::FrameRec)))) return st;
+  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
+  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
+  ZG_HIP(hipEventRecord(t.ev[0], s));
+  zg_launch_index(t.lanes.as<zgw::Lane>(), n, t.ents.as<zgi::Entry>(), first ? t.recs.as<zgi::FrameRec>() : nullptr, s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(t.ev[1], s));
+  ZG_HIP(hipMemcpyAsync(out, t.ents.p, (size_t)n * sizeof(zgi::Entry), hipMemcpyDeviceToHost, s));
+  if (total) ZG_HIP(hipMemcpyAsync(recs, t.recs.p, total * sizeof(zgi::FrameRec), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgi::Entry) + total * sizeof(zgi::FrameRec);
+  return ZG_OK;
+}
+
 int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
                                    std::vector<int>* walk, std::vector<uint32_t>* first_frame) {
   Batch* b = new Batch();

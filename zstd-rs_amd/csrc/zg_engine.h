@@ -224,6 +224,12 @@ class Engine {
   int walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats);
   int prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
                              std::vector<int>* walk, std::vector<uint32_t>* first_frame);
+  // What such entries hold, from their headers alone (zgpu_frames_index_device / zgpu_frames_table_device): ONE zg_k_index launch (zg_index.h)
+  // over all n entries. first == nullptr: the summary pass, out[i] = entry i's summary. Else the emit pass: sum = the summaries of the summary
+  // pass, first[i] .. first[i + 1] (their prefix sum, n + 1 slots) the frame records lane i may write of recs[0 .. first[n]); out = what this
+  // pass says about every entry (the caller compares). An entry of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
+  // events), bytes downloaded.
+  int index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, const zgi::Entry* sum, zgi::Entry* out, zgi::FrameRec* recs, uint64_t* stats);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes

@@ -488,6 +488,100 @@ extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* dev
   k.stats[0] = c->frames_submits;
   return st;
 }
+// ---- what device-resident entries hold, from their headers alone (zg_index.h) --------------------------------------------------------------
+// The stop reasons of the chain are public under the values the lanes use.
+static_assert(ZGPU_CHAIN_END == zgw::kEnd && ZGPU_CHAIN_SHORT_HEADER == zgw::kShortHeader && ZGPU_CHAIN_BAD_MAGIC == zgw::kBadMagic &&
+              ZGPU_CHAIN_SKIP_PAST_END == zgw::kSkipPastEnd && ZGPU_CHAIN_SHORT_BLOCK_HEADER == zgw::kShortBlockHeader &&
+              ZGPU_CHAIN_RESERVED_BLOCK == zgw::kReservedBlock && ZGPU_CHAIN_BLOCK_TOO_LARGE == zgw::kBlockTooLarge &&
+              ZGPU_CHAIN_BODY_PAST_END == zgw::kBodyPastEnd && ZGPU_CHAIN_SHORT_CHECKSUM == zgw::kShortChecksum, "zgw:: stop reasons");
+static_assert(sizeof(zgpu_entry_index) == 40 && sizeof(zgpu_frame_index) == 64, "include/zgpu.h");
+namespace {
+// Both calls up to the summaries: every source checked, ONE summary launch over the entries that passed, entries[] filled.
+int index_summaries(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries,
+                    std::vector<Engine::DevEntry>* dev, std::vector<zgi::Entry>* sum) {
+  for (uint64_t& x : c->frames_index_stats) x = 0;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  dev->resize(n);
+  sum->assign(n, zgi::Entry{});
+  std::vector<DevRange> known;
+  for (uint32_t i = 0; i < n; i++) {
+    memset(&entries[i], 0, sizeof entries[i]);
+    const bool bad = lens[i] && !check_device_range(c->eng->device(), device_srcs[i], lens[i], known);
+    if (bad) entries[i].status = ZGPU_E_BAD_ARG;
+    (*dev)[i] = Engine::DevEntry{(uint64_t)(uintptr_t)device_srcs[i], bad ? 0u : (uint64_t)lens[i]};   // (a refused entry is not read)
+  }
+  int st = c->eng->index_pass(dev->data(), n, nullptr, nullptr, sum->data(), nullptr, c->frames_index_stats);
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  if (st) return st;
+  for (uint32_t i = 0; i < n; i++) {
+    if (entries[i].status) { (*sum)[i] = zgi::Entry{}; continue; }
+    const zgi::Entry& e = (*sum)[i];
+    if (e.chain_end > lens[i]) { c->eng->last_error = "zgpu_frames_index_device: a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
+    entries[i].bound = e.bound; entries[i].chain_end = e.chain_end;
+    entries[i].nframes = e.nframes; entries[i].nskippable = e.nskippable; entries[i].nblocks = e.nblocks;
+    entries[i].why = e.why; entries[i].flags = e.flags;
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_frames_index_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries) {
+  if (!c || (n && (!device_srcs || !lens || !entries))) return ZGPU_E_BAD_ARG;
+  std::vector<Engine::DevEntry> dev;
+  std::vector<zgi::Entry> sum;
+  return index_summaries(c, device_srcs, lens, n, entries, &dev, &sum);
+}
+
+extern "C" int zgpu_frames_table_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries,
+                                        uint64_t* frame_first, zgpu_frame_index* frames, size_t frames_cap, size_t* nframes_out) {
+  if (!c || !frame_first || !nframes_out || (n && (!device_srcs || !lens || !entries)) || (frames_cap && !frames)) return ZGPU_E_BAD_ARG;
+  std::vector<Engine::DevEntry> dev;
+  std::vector<zgi::Entry> sum;
+  *nframes_out = 0;
+  frame_first[0] = 0;
+  int st = index_summaries(c, device_srcs, lens, n, entries, &dev, &sum);
+  if (st) return st;
+  const uint64_t total = zgi::frame_ranges(sum.data(), n, frame_first);
+  *nframes_out = (size_t)total;
+  if (total > frames_cap) return ZGPU_E_TARGET_TOO_SMALL;
+  if (!total) return ZGPU_OK;
+  std::vector<zgi::Entry> again(n);
+  std::vector<zgi::FrameRec> recs(total);
+  st = c->eng->index_pass(dev.data(), n, frame_first, sum.data(), again.data(), recs.data(), c->frames_index_stats);
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  if (st) return st;
+  for (uint32_t i = 0; i < n; i++) {
+    if (entries[i].status) continue;
+    if (!zgi::same_entry(again[i], sum[i])) {   // (a source that changed between the passes: the caller's promise broken)
+      c->eng->last_error = "zgpu_frames_table_device: a source changed while it was indexed";
+      return ZGPU_E_INTERNAL;
+    }
+    for (uint64_t k = frame_first[i]; k < frame_first[i + 1]; k++) {
+      const zgi::FrameRec& r = recs[k];
+      zgpu_frame_index& f = frames[k];
+      FrameFields hf;
+      frame_fields(r.b, r.have, &hf);
+      memset(&f, 0, sizeof f);
+      f.src_begin = r.begin; f.src_end = r.end; f.bound = r.bound;
+      f.frame_content_size = hf.frame_content_size; f.window_size = hf.window_size;
+      f.entry = i; f.nblocks = r.nblocks;
+      f.dict_id = hf.dict_id;
+      f.flags = hf.flags | r.flags;
+      f.header_status = hf.header_status; f.skip_magic = hf.skip_magic;
+      if (r.begin > r.end || r.end > lens[i] || ((r.flags & zgi::kSkippable) != 0) != (hf.header_status == ZGPU_E_SKIP_FRAME)) {   // (never)
+        c->eng->last_error = "zgpu_frames_table_device: a frame record out of step with its header";
+        return ZGPU_E_INTERNAL;
+      }
+    }
+  }
+  return ZGPU_OK;
+}
+extern "C" int zgpu_debug_frames_index_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c || !out) return 0;
+  int k = 0;
+  for (; k < n && k < 4; k++) out[k] = c->frames_index_stats[k];
+  return k;
+}
 extern "C" int zgpu_debug_frames_device_src_stats(const zgpu_ctx* c, uint64_t* out, int n) {
   if (!c || !out) return 0;
   int k = 0;

@@ -585,6 +585,22 @@ uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, b
   return b;
 }
 
+void frame_fields(const uint8_t* b, uint32_t have, FrameFields* out) {
+  *out = FrameFields{0, 0, 0, 0, 0, 0};
+  FrameHeader h;
+  size_t c = 0;
+  uint32_t sm = 0, sl = 0;
+  const int st = read_frame_header(b, have, &h, &c, &sm, &sl);
+  out->header_status = (uint32_t)st;
+  if (st == ZG_SKIP_FRAME) { out->flags = 1u; out->skip_magic = sm; return; }
+  if (st) return;
+  uint64_t w = 0;
+  if (frame_window_size(h, &w) == ZG_OK) out->window_size = w;
+  out->frame_content_size = h.frame_content_size;
+  out->dict_id = h.has_dict_id ? h.dict_id : 0u;
+  out->flags = (h.has_fcs() ? 2u : 0u) | (h.content_checksum() ? 4u : 0u) | (h.single_segment() ? 16u : 0u);
+}
+
 int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out) {
   // the walk of parse_frames without the section headers: frame header, then block headers up to the last block
   size_t p = 0;

@@ -139,6 +139,12 @@ int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuild
 // far stay valid).
 struct FrameSpan { uint64_t begin, end; uint64_t content_size; bool has_content_size; bool skippable; };
 int split_frames(const uint8_t* src, size_t len, std::vector<FrameSpan>* out);
+// What a frame record of zg_k_index (zg_index.h) says once the host has read its header bytes: b = the (up to 18) bytes where the frame
+// starts, `have` of them real. header_status is read_frame_header's verdict on them (0, ZG_SKIP_FRAME, or its error); window_size is
+// FrameHeader::window_size, 0 where there is none to report (a skippable frame, a header that cannot be read, a window the format refuses);
+// flags are the header's bits of zgpu_frame_index::flags: 0 skippable, 1 Frame_Content_Size declared, 2 Content_Checksum, 4 single segment.
+struct FrameFields { uint64_t window_size, frame_content_size; uint32_t dict_id, flags, header_status, skip_magic; };
+void frame_fields(const uint8_t* b, uint32_t have, FrameFields* out);
 // Upper bound of the plaintext of a buffer of concatenated frames from frame and block headers only (a frame's declared content size when it
 // is smaller; a compressed block counts 128 KiB). Tolerant: the walk stops where a header cannot be read and returns what it found so far.
 uint64_t plaintext_bound(const uint8_t* src, size_t len);

@@ -5,6 +5,7 @@
 #include "zg_types.h"
 #include "zg_scatter.h"
 #include "zg_walk.h"
+#include "zg_index.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -50,3 +51,6 @@ void zg_launch_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t n
 // zg_k_walk (zg_walk.h): one lane per entry follows the entry's header chain; ends[i] = where lane i stopped and how many skeleton records it has.
 // recs == nullptr: the count pass (nothing else is written); else lane i writes records lanes[i].first .. + lanes[i].limit of recs
 void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec* recs, hipStream_t s);
+// zg_k_index (zg_index.h): one lane per entry follows the entry's header chain without touching a block body; entries[i] = the summary of lane i.
+// recs == nullptr: the summary pass (nothing else is written); else lane i also writes frame records lanes[i].first .. + lanes[i].limit of recs
+void zg_launch_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zgi::FrameRec* recs, hipStream_t s);

@@ -1856,6 +1856,26 @@ void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec
   else hipLaunchKernelGGL(zg_k_walk<false>, g, t, 0, s, lanes, n, ends, recs);
 }
 
+// What entries that lie in device memory hold, from frame and block headers alone, one lane per entry (zg_index.h has the routine, the
+// record layouts and the ISA notes). The host checked every [src, src + len) against the runtime's allocations; a lane reads nothing outside
+// it, no byte of a block body, and writes its own Entry and — emit pass — its own frame records only.
+struct ZgIndexWrite {
+  zgi::FrameRec* recs;
+  __device__ __forceinline__ void put(uint64_t i, const zgi::FrameRec& x) const { recs[i] = x; }
+};
+template <bool EMIT> __global__ void __launch_bounds__(zgi::kThreads) zg_k_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zgi::FrameRec* recs) {
+  const uint32_t i = blockIdx.x * zgi::kThreads + threadIdx.x;
+  if (i >= n) return;
+  const zgw::Lane l = lanes[i];
+  entries[i] = zgi::index_entry<EMIT>(ZgWalkRead{l.src}, ZgIndexWrite{recs}, l.len, l.first, l.limit);
+}
+void zg_launch_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zgi::FrameRec* recs, hipStream_t s) {
+  if (!n) return;
+  const dim3 g((n + zgi::kThreads - 1) / zgi::kThreads), t(zgi::kThreads);
+  if (recs) hipLaunchKernelGGL(zg_k_index<true>, g, t, 0, s, lanes, n, entries, recs);
+  else hipLaunchKernelGGL(zg_k_index<false>, g, t, 0, s, lanes, n, entries, recs);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

@@ -112,6 +112,47 @@ ZG_WK_FN uint32_t frame_header_bytes(uint8_t d) {
   return 5u + (single ? 0u : 1u) + (did == 3 ? 4u : did) + (fcs == 0 ? single : (fcs == 1 ? 2u : (fcs == 2 ? 4u : 8u)));
 }
 
+// The stop rules of the chain: ONE definition, which walk_entry below and zgi::index_entry (zg_index.h) both follow.
+// Where a frame is due: `have` = the bytes left in the entry, clipped to kFrameBytes; magic = the first four of them (anything if have < 4).
+// kEnd: a skippable frame (*skip = true, its length field is all there) or the magic and the descriptor of a zstd frame are there.
+ZG_WK_FN uint32_t frame_stop(uint32_t have, uint32_t magic, bool* skip) {
+  *skip = false;
+  if (have < 4) return kShortHeader;
+  if (magic >= kMagicSkipLo && magic <= kMagicSkipHi) {
+    if (have < 8) return kShortHeader;
+    *skip = true;
+    return kEnd;
+  }
+  if (magic != kMagicFrame) return kBadMagic;
+  return have < 5 ? kShortHeader : kEnd;
+}
+// a skippable frame at *p whose length field says sl: *p moves behind its 8 header bytes and, if the entry holds them, behind its sl bytes
+ZG_WK_FN uint32_t skip_stop(uint64_t sl, uint64_t len, uint64_t* p) {
+  *p += 8;
+  if (sl > len - *p) return kSkipPastEnd;
+  *p += sl;
+  return kEnd;
+}
+// a zstd frame whose descriptor is d: *hs = the bytes of its header, all of which must be among the `have`
+ZG_WK_FN uint32_t header_stop(uint32_t have, uint8_t d, uint32_t* hs) {
+  *hs = frame_header_bytes(d);
+  return have < *hs ? kShortHeader : kEnd;
+}
+// a block header (3 bytes, the caller has checked that they are there) with `left` bytes of the entry behind it
+struct BlockHdr { uint32_t type, size, content; bool last; };   // content: the bytes of the body (an RLE block: 1)
+ZG_WK_FN uint32_t block_stop(uint8_t b0, uint8_t b1, uint8_t b2, uint64_t left, BlockHdr* h) {
+  h->last = b0 & 1;
+  h->type = (b0 >> 1) & 3u;
+  h->size = (uint32_t)(b0 >> 3) | ((uint32_t)b1 << 5) | ((uint32_t)b2 << 13);
+  h->content = h->type == 1 ? 1u : h->size;
+  if (h->type == 3) return kReservedBlock;
+  if (h->size > kBlockMax) return kBlockTooLarge;
+  if (left < h->content) return kBodyPastEnd;
+  return kEnd;
+}
+// the Content_Checksum behind a last block at p: how many of its 4 bytes the entry holds (fewer than 4: kShortChecksum, after p has moved over them)
+ZG_WK_FN uint32_t checksum_bytes(uint64_t len, uint64_t p) { const uint64_t cl = len - p; return cl < 4 ? (uint32_t)cl : 4u; }
+
 // What the lane of one entry does. R reads the entry (ld1(off), off counted from the entry's first byte; the routine asks for no off >= len);
 // W writes records (put(index, rec)); EMIT = false is the count pass, which writes nothing.
 template <bool EMIT, class R, class W> ZG_WK_FN End walk_entry(const R& r, const W& w, uint64_t len, uint64_t first, uint64_t limit) {
@@ -131,20 +172,16 @@ template <bool EMIT, class R, class W> ZG_WK_FN End walk_entry(const R& r, const
 ZG_WK_UNROLL
     for (uint32_t i = 0; i < kFrameBytes; i++) fr.b[i] = i < have ? r.ld1(p + i) : (uint8_t)0;
     emit(fr);
-    if (have < 4) { why = kShortHeader; break; }
     const uint32_t magic = (uint32_t)fr.b[0] | ((uint32_t)fr.b[1] << 8) | ((uint32_t)fr.b[2] << 16) | ((uint32_t)fr.b[3] << 24);
-    if (magic >= kMagicSkipLo && magic <= kMagicSkipHi) {
-      if (have < 8) { why = kShortHeader; break; }
+    bool skip;
+    if ((why = frame_stop(have, magic, &skip))) break;
+    if (skip) {
       const uint64_t sl = (uint32_t)fr.b[4] | ((uint32_t)fr.b[5] << 8) | ((uint32_t)fr.b[6] << 16) | ((uint32_t)fr.b[7] << 24);
-      p += 8;
-      if (sl > len - p) { why = kSkipPastEnd; break; }
-      p += sl;
+      if ((why = skip_stop(sl, len, &p))) break;
       continue;
     }
-    if (magic != kMagicFrame) { why = kBadMagic; break; }
-    if (have < 5) { why = kShortHeader; break; }
-    const uint32_t hs = frame_header_bytes(fr.b[4]);
-    if (have < hs) { why = kShortHeader; break; }
+    uint32_t hs;
+    if ((why = header_stop(have, fr.b[4], &hs))) break;
     const bool has_cksum = (fr.b[4] >> 2) & 1;
     p += hs;
     for (;;) {
@@ -155,12 +192,9 @@ ZG_WK_UNROLL
       br.b[0] = r.ld1(p); br.b[1] = r.ld1(p + 1); br.b[2] = r.ld1(p + 2);
       const uint64_t body = p + 3;
       br.off = body;
-      const uint32_t type = (br.b[0] >> 1) & 3u;
-      const uint32_t size = (uint32_t)(br.b[0] >> 3) | ((uint32_t)br.b[1] << 5) | ((uint32_t)br.b[2] << 13);
-      const uint32_t content = type == 1 ? 1u : size;
-      if (type == 3) why = kReservedBlock;
-      else if (size > kBlockMax) why = kBlockTooLarge;
-      else if (len - body < content) why = kBodyPastEnd;
+      BlockHdr bh;
+      why = block_stop(br.b[0], br.b[1], br.b[2], len - body, &bh);
+      const uint32_t type = bh.type, content = bh.content;
       if (!why && type == 2) {
         const uint32_t nh = content < 5 ? content : 5u;
         br.have = (uint8_t)nh;
@@ -176,13 +210,12 @@ ZG_WK_UNROLL
       emit(br);
       if (why) break;
       p = body + content;
-      if (br.b[0] & 1) {   // Last_Block
+      if (bh.last) {   // Last_Block
         if (has_cksum) {
           Rec cr;
           memset(&cr, 0, sizeof cr);
           cr.off = p; cr.kind = (uint8_t)kCksum;
-          const uint64_t cl = len - p;
-          const uint32_t nc = cl < 4 ? (uint32_t)cl : 4u;
+          const uint32_t nc = checksum_bytes(len, p);
           cr.have = (uint8_t)nc;
 ZG_WK_UNROLL
           for (uint32_t i = 0; i < 4; i++) cr.b[i] = i < nc ? r.ld1(p + i) : (uint8_t)0;

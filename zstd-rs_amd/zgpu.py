@@ -62,6 +62,62 @@ class DeviceEntryResult:
             self.status, self.written, self.nframes, self.checksums, self.checksum_mismatches, self.checksums_unverified)
 
 
+# why a header chain ended (zgpu_entry_index.why, ZGPU_CHAIN_*)
+(CHAIN_END, CHAIN_SHORT_HEADER, CHAIN_BAD_MAGIC, CHAIN_SKIP_PAST_END, CHAIN_SHORT_BLOCK_HEADER, CHAIN_RESERVED_BLOCK, CHAIN_BLOCK_TOO_LARGE,
+ CHAIN_BODY_PAST_END, CHAIN_SHORT_CHECKSUM) = range(9)
+
+
+class EntryIndexC(C.Structure):
+    """zgpu_entry_index (include/zgpu.h)"""
+    _fields_ = [("bound", C.c_uint64), ("chain_end", C.c_uint64), ("status", C.c_uint32), ("nframes", C.c_uint32), ("nskippable", C.c_uint32),
+                ("nblocks", C.c_uint32), ("why", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FrameIndexC(C.Structure):
+    """zgpu_frame_index (include/zgpu.h)"""
+    _fields_ = [("src_begin", C.c_uint64), ("src_end", C.c_uint64), ("bound", C.c_uint64), ("frame_content_size", C.c_uint64),
+                ("window_size", C.c_uint64), ("entry", C.c_uint32), ("nblocks", C.c_uint32), ("dict_id", C.c_uint32), ("flags", C.c_uint32),
+                ("header_status", C.c_uint32), ("skip_magic", C.c_uint32)]
+
+
+class EntryIndex:
+    """One entry of Context.frames_index_device (zgpu_entry_index): bound is plaintext_bound of the entry's bytes; status is 0, or E_BAD_ARG for
+    a source that failed the pointer check (every other field is 0 then). flags: all_sized (every frame declares its content size), any_dict,
+    any_checksum, all_complete — of the nframes zstd frames, all False if there is none."""
+    __slots__ = ("bound", "chain_end", "status", "nframes", "nskippable", "nblocks", "why", "flags", "all_sized", "any_dict", "any_checksum",
+                 "all_complete")
+
+    def __init__(self, c):
+        for k in ("bound", "chain_end", "status", "nframes", "nskippable", "nblocks", "why", "flags"):
+            setattr(self, k, int(getattr(c, k)))
+        self.all_sized, self.any_dict = bool(self.flags & 1), bool(self.flags & 2)
+        self.any_checksum, self.all_complete = bool(self.flags & 4), bool(self.flags & 8)
+
+    def __repr__(self):
+        return "EntryIndex(status=%d, bound=%d, nframes=%d, nskippable=%d, nblocks=%d, chain_end=%d, why=%d, flags=%#x)" % (
+            self.status, self.bound, self.nframes, self.nskippable, self.nblocks, self.chain_end, self.why, self.flags)
+
+
+class FrameIndex:
+    """One frame of Context.frames_table_device (zgpu_frame_index): [src_begin, src_end) in entry `entry`, its share of the entry's bound, and
+    what its header says. header_status is 0 for a zstd frame, E_SKIP_FRAME for a skippable one, else the error of a header the chain could
+    not read (the entry's last record then, src_begin == src_end)."""
+    __slots__ = ("src_begin", "src_end", "bound", "frame_content_size", "window_size", "entry", "nblocks", "dict_id", "flags", "header_status",
+                 "skip_magic", "skippable", "has_content_size", "has_checksum", "complete", "single_segment")
+
+    def __init__(self, c):
+        for k in ("src_begin", "src_end", "bound", "frame_content_size", "window_size", "entry", "nblocks", "dict_id", "flags", "header_status",
+                  "skip_magic"):
+            setattr(self, k, int(getattr(c, k)))
+        f = self.flags
+        self.skippable, self.has_content_size, self.has_checksum = bool(f & 1), bool(f & 2), bool(f & 4)
+        self.complete, self.single_segment = bool(f & 8), bool(f & 16)
+
+    def __repr__(self):
+        return "FrameIndex(entry=%d, [%d, %d), bound=%d, nblocks=%d, header_status=%d, flags=%#x)" % (
+            self.entry, self.src_begin, self.src_end, self.bound, self.nblocks, self.header_status, self.flags)
+
+
 def plaintext_bound(buf):
     """zgpu_plaintext_bound: an upper bound of the plaintext of concatenated frames from frame and block headers only (a frame's declared
     content size when smaller; a compressed block counts 128 KiB); the walk stops where a header cannot be read. Decode_frames' default
@@ -103,6 +159,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
     "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
@@ -173,6 +230,9 @@ def _declare(L):
     L.zgpu_debug_frames_device_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_decode_frames_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
     L.zgpu_debug_frames_device_src_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_frames_index_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC)]
+    L.zgpu_frames_table_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC), P(C.c_uint64), P(FrameIndexC), sz, P(sz)]
+    L.zgpu_debug_frames_index_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_plaintext_bound.argtypes = [u8p, sz]
     L.zgpu_plaintext_bound.restype = C.c_uint64
     L.zgpu_debug_frames_submits.argtypes = [vp]
@@ -467,6 +527,74 @@ class Context:
         return dict(zip(keys[:k], [int(x) for x in a][:k]))
 
     @staticmethod
+    def _device_sources(src_ptrs, lens):
+        n = len(src_ptrs)
+        if len(lens) != n:
+            raise ValueError("one length per source")
+        srcs, lena = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            srcs[i], lena[i] = int(src_ptrs[i]) or None, int(lens[i])
+        return n, srcs, lena
+
+    def frames_index_device(self, src_ptrs, lens):
+        """zgpu_frames_index_device: what entries in DEVICE memory hold, from frame and block headers alone. src_ptrs[i] is the address of
+        lens[i] bytes on this context's device (any alignment; checked like the sources of decode_frames_device_src: a pointer that is not
+        such memory gives that entry E_BAD_ARG). One kernel launch, 48 bytes per entry come back, no byte of the input does. Returns one
+        EntryIndex per entry; .bound is plaintext_bound of the entry: room enough for decode_frames_device_src."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        ents = (EntryIndexC * max(n, 1))()
+        st = self.L.zgpu_frames_index_device(self.h, srcs, lena, n, ents)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return [EntryIndex(ents[i]) for i in range(n)]
+
+    def frames_table_device(self, src_ptrs, lens, room=None):
+        """zgpu_frames_table_device: frames_index_device plus one FrameIndex per frame (zstd or skippable) of every entry. Returns
+        (entries, frame_first, frames): frames[frame_first[i]:frame_first[i + 1]] are entry i's, in order. room: records to make room for in the
+        first call (default: two per entry); a table that turns out too small is sized by a second call."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        ents = (EntryIndexC * max(n, 1))()
+        first = (C.c_uint64 * (n + 1))()
+        need = C.c_size_t(0)
+        cap = max(int(room) if room is not None else 2 * n, 1)
+        for _ in range(2):
+            frames = (FrameIndexC * cap)()
+            st = self.L.zgpu_frames_table_device(self.h, srcs, lena, n, ents, first, frames, cap, C.byref(need))
+            if st != E_TARGET_TOO_SMALL:
+                break
+            cap = need.value
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return [EntryIndex(ents[i]) for i in range(n)], [int(x) for x in first], [FrameIndex(frames[k]) for k in range(need.value)]
+
+    def frames_index_stats(self):
+        """the last frames_index_device / frames_table_device call (zgpu_debug_frames_index_stats)"""
+        a = (C.c_uint64 * 4)()
+        k = self.L.zgpu_debug_frames_index_stats(self.h, a, 4)
+        keys = ["launches", "kernel_us", "bytes_downloaded", "input_bytes_to_host"]
+        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    def _tensor_check(self, tensors, what):
+        import torch
+        self._one_hip_runtime()
+        dev = torch.device("cuda", self.device)
+        for t in tensors:
+            if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+                raise ValueError("%s: contiguous torch.uint8 tensors on %s" % (what, dev))
+        # the tensors may still be written on torch's stream
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+
+    def split_tensor_frames(self, tensor):
+        """One view per zstd frame of a contiguous torch.uint8 tensor on this context's device that holds concatenated frames, cut at the frame
+        boundaries frames_table_device finds (skippable frames are left out; no byte of the tensor crosses to the host). The views can go
+        straight into decode_tensors, each as an entry of its own. A tensor whose header chain breaks yields the frames in front of the break
+        and the broken one, up to where the chain left it."""
+        self._tensor_check([tensor], "split_tensor_frames")
+        _, _, frames = self.frames_table_device([tensor.data_ptr() if tensor.numel() else 0], [tensor.numel()])
+        return [tensor[f.src_begin:f.src_end] for f in frames if f.header_status == 0]
+
+    @staticmethod
     def _one_hip_runtime():
         hip = set(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln) if os.path.exists("/proc/self/maps") else ()
         if len(hip) > 1:
@@ -475,18 +603,15 @@ class Context:
     def decode_tensors(self, tensors, caps=None, hash_max=0, no_hash=False):
         """decode_frames_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
         compressed bytes. The plaintext goes to ONE new torch.uint8 tensor, every entry's slot 256-byte aligned with caps[i] bytes of room.
-        caps=None sizes the slots with zgpu_plaintext_bound, which reads the bytes on the HOST: the inputs are downloaded once for that, so a
-        caller that wants no byte of the input to cross passes caps. Returns (tensors, results) like decode_frames_to_tensors, under the same
-        single-runtime rule (import torch before creating the first Context). torch is imported here, not by `import zgpu`."""
+        caps=None sizes the slots with frames_index_device — zgpu_plaintext_bound of every entry, taken on the device from its headers: no
+        byte of the input crosses to the host. Returns (tensors, results) like decode_frames_to_tensors, under the same single-runtime rule
+        (import torch before creating the first Context). torch is imported here, not by `import zgpu`."""
         import torch
-        self._one_hip_runtime()
-        n = len(tensors)
+        self._tensor_check(tensors, "decode_tensors")
         dev = torch.device("cuda", self.device)
-        for t in tensors:
-            if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
-                raise ValueError("decode_tensors: contiguous torch.uint8 tensors on %s" % dev)
+        ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
         if caps is None:
-            caps = [plaintext_bound(t.cpu().numpy().tobytes()) for t in tensors]
+            caps = [e.bound for e in self.frames_index_device(ptrs, lens)]
         offs, total = [], 0
         for c in caps:
             offs.append(total)
@@ -496,8 +621,7 @@ class Context:
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
         base = buf.data_ptr()
-        res = self.decode_frames_device_src([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors],
-                                            [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
+        res = self.decode_frames_device_src(ptrs, lens, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
         return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
 
     def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False):
