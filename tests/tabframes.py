@@ -366,7 +366,9 @@ class Block:
     """one compressed block. lits: all literal bytes (those of the sequences, then the trailing ones); seqs: [(ll, offset_value,
     ml)], offset_value as the format has it (1..3 the repeat offsets, else distance + 3).
     lit: ("raw"|"rle", sf) | ("huf", weights, "direct"|("fse", al[, counts]), nstreams, sf) | ("treeless", nstreams, sf) |
-         ("hufbytes", description, nstreams): a description as it is, the streams a single byte (invalid frames).
+         ("hufbytes", description, nstreams): a description as it is, the streams a single byte (invalid frames) |
+         ("hufstreams", weights or None (treeless), form, [stream bytes, ...], sf): the one or four streams as the caller wrote them;
+         the description, the jump table and the header (its regen is len(lits)) are added here (tests/hufstreams.py).
     ll / of / ml: ("pre",) | ("rle", code) | ("fse", al, counts) | ("rep",) | ("bytes", description) (invalid frames).
     last: {"LL": state, ...} the last sequence's states (see fse_walk). seq_raw: the whole sequences section as it is."""
 
@@ -394,6 +396,16 @@ def _literals(fr, blk):
     if kind == "hufbytes":
         body = blk.lit[1] + (b"\x01" if blk.lit[2] == 1 else b"\x01\x00" * 3 + b"\x01" * 4)
         return lit_header(2, n, len(body), blk.lit[2]) + body, None
+    if kind == "hufstreams":
+        _, weights, form, streams, sf = blk.lit
+        assert len(streams) in (1, 4) and all(len(p) < 65536 for p in streams)
+        desc = b""
+        if weights is not None:
+            desc = weights_direct(weights) if form == "direct" else weights_fse(weights, *form[1:])
+            fr.huf = list(weights)
+        assert fr.huf is not None
+        body = desc + (b"".join(len(p).to_bytes(2, "little") for p in streams[:3]) if len(streams) == 4 else b"") + b"".join(streams)
+        return lit_header(2 if weights is not None else 3, n, len(body), len(streams), sf) + body, huf_table(fr.huf)[:2]
     if kind == "huf":
         _, weights, form, nstreams, sf = blk.lit
         desc = weights_direct(weights) if form == "direct" else weights_fse(weights, *form[1:])
@@ -499,9 +511,10 @@ def _bh(last, btype, size):
     return (last | (btype << 1) | (size << 3)).to_bytes(3, "little")
 
 
-def build(name, blocks, window_log=17, valid=True):
+def build(name, blocks, window_log=17, valid=True, differs=None):
     """blocks: Block | ("raw", bytes) | ("rle", byte, n) | ("bytes", block content as it is: a compressed block, invalid frames).
-    Returns (name, zst, plaintext or None). A valid frame is checked against the oracle (bytes and tables) and libzstd."""
+    Returns (name, zst, plaintext or None). A valid frame is checked against the oracle (bytes and tables) and libzstd (differs: the
+    caller's own list of frames libzstd does not return the plaintext for, in place of LIBZSTD_DIFFERS)."""
     fr = _Frame()
     z = MAGIC + bytes([0x04, (window_log - 10) << 3])    # no single segment, no content size, a checksum
     flat_seqs, flat_lits, pending = [], bytearray(), 0
@@ -542,14 +555,15 @@ def build(name, blocks, window_log=17, valid=True):
         return name, z, None
     plain = seqframes.lz77(flat_seqs, bytes(flat_lits))
     z += (oracle.lib().zor_xxh64(plain, len(plain), 0) & 0xFFFFFFFF).to_bytes(4, "little")
-    _check_valid(name, z, plain, fr)
+    _check_valid(name, z, plain, fr, differs)
     return name, z, plain
 
 
 _LIBZSTD_MISSING = []
 
 
-def _check_valid(name, z, plain, fr):
+def _check_valid(name, z, plain, fr, differs=None):
+    differs = LIBZSTD_DIFFERS if differs is None else differs
     d = oracle.FrameDecoder()
     st, out = d.decode_all(z, len(plain) + 64)
     assert st == 0 and out == plain, (name, st, len(out), len(plain))
@@ -579,7 +593,7 @@ def _check_valid(name, z, plain, fr):
         got = zgdata.zstd_decompress(z, len(plain))
     except RuntimeError:
         got = None
-    if name in LIBZSTD_DIFFERS:
+    if name in differs:
         assert got != plain, (name, "libzstd agrees: take it off LIBZSTD_DIFFERS")
     else:
         assert got == plain, (name, "libzstd does not return the plaintext")
