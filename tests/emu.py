@@ -54,8 +54,38 @@ def lib():
         L.zgemu_seq_block.argtypes = [C.c_void_p, C.c_uint32]
         L.zgemu_seq_block.restype = C.c_uint32
         L.zgemu_exact.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        u32p = C.POINTER(C.c_uint32)
+        L.zgemu_map_apply.argtypes = [C.POINTER(C.c_uint32 * 3), C.c_uint32, u32p]
+        L.zgemu_map_compose.argtypes = [C.POINTER(C.c_uint32 * 3), C.POINTER(C.c_uint32 * 3), C.POINTER(C.c_uint32 * 3)]
+        L.zgemu_sym_resolve.argtypes = [C.c_uint32, C.POINTER(C.c_uint32 * 3)]
+        L.zgemu_sym_resolve.restype = C.c_uint32
+        L.zgemu_map_fold.argtypes = [u32p, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32 * 3), C.c_uint64, C.c_uint32, u32p, u32p]
+        L.zgemu_map_fold.restype = C.c_uint32
         _LIB = L
     return _LIB
+
+
+def map_compose(a, b):
+    """zg_map_compose (zg_dev.h): apply a first, then b; maps are three slot words"""
+    out = (C.c_uint32 * 3)()
+    lib().zgemu_map_compose(C.byref((C.c_uint32 * 3)(*a)), C.byref((C.c_uint32 * 3)(*b)), C.byref(out))
+    return list(out)
+
+
+def sym_resolve(v, hist):
+    return lib().zgemu_sym_resolve(v, C.byref((C.c_uint32 * 3)(*hist)))
+
+
+def map_fold(codes, hist, seed=0, ntrees=4):
+    """codes: [(ll, offset_value)] as zg_hist_step takes them; hist: the three slots in front. Returns (serial, fail, which): serial
+    is [(actual offset, slot 0, slot 1, slot 2)] after every sequence from zg_hist_step on concrete slots; fail is 0 if every
+    bracketing of zg_map_compose over every prefix resolves to the same (tests/emu/zg_emu_map.cpp), else 1 + the prefix length"""
+    n = len(codes)
+    of = (C.c_uint32 * max(n, 1))(*[c[1] for c in codes])
+    ll = (C.c_uint8 * max(n, 1))(*[1 if c[0] else 0 for c in codes])
+    serial, which = (C.c_uint32 * (4 * max(n, 1)))(), C.c_uint32()
+    fail = lib().zgemu_map_fold(of, ll, n, C.byref((C.c_uint32 * 3)(*hist)), seed, ntrees, serial, C.byref(which))
+    return [tuple(serial[4 * i:4 * i + 4]) for i in range(n)], fail, which.value
 
 
 class Plan:

@@ -299,3 +299,27 @@ ZG_HD uint32_t zg_hist_step(uint32_t of, uint32_t ll, uint32_t& h0, uint32_t& h1
   h0 = actual;
   return actual;
 }
+// the effect of a run of sequences (a thread's, a wave's, a block's, a chunk of blocks') on the history: the three slots behind it,
+// relative to the history in front of it (zg_k_seqpost and zg_k_scan scan these; tests/emu/zg_emu_map.cpp folds them on the host)
+struct ZgHistMap { uint32_t s[3]; };
+ZG_HD ZgHistMap zg_map_identity() { return {{1u << 30, 2u << 30, 3u << 30}}; }
+// v (a slot value relative to map A's output) expressed relative to A's input
+ZG_HD uint32_t zg_map_apply(const ZgHistMap& A, uint32_t v) {
+  // (branches on purpose: almost every slot is a constant, and a wave whose lanes all hold constants skips the rest;
+  //  a select-only version was measured slower in zg_k_seqpost and zg_k_scan)
+  const uint32_t t = ZG_SYM_TAG(v);
+  if (!t) return v;
+  const uint32_t a = t == 1 ? A.s[0] : t == 2 ? A.s[1] : A.s[2], k = ZG_SYM_K(v);
+  if (ZG_SYM_TAG(a)) {
+    uint32_t kk = ZG_SYM_K(a) + k;
+    if (kk > 0x3FFFFFFFu) kk = 0x3FFFFFFFu;
+    return (a & 0xC0000000u) | kk;
+  }
+  return a > k ? a - k : 0;
+}
+// apply A first, then B
+ZG_HD ZgHistMap zg_map_compose(const ZgHistMap& A, const ZgHistMap& B) {
+  ZgHistMap r;
+  r.s[0] = zg_map_apply(A, B.s[0]); r.s[1] = zg_map_apply(A, B.s[1]); r.s[2] = zg_map_apply(A, B.s[2]);
+  return r;
+}

@@ -939,29 +939,7 @@ __global__ void __launch_bounds__(128) zg_k_seq(ZgBatchDev d) {
 // ------------------------------------------------------------------------------------------------------------
 #define ZG_SP_T 256
 #define ZG_SP_S 8           // consecutive sequences per thread: the history inside them is stepped directly, only thread totals are scanned
-struct ZgHistMap { uint32_t s[3]; };
-__device__ __forceinline__ ZgHistMap zg_map_identity() { return {{1u << 30, 2u << 30, 3u << 30}}; }
-// v (a slot value relative to map A's output) expressed relative to A's input
-__device__ __forceinline__ uint32_t zg_map_apply(const ZgHistMap& A, uint32_t v) {
-  // (branches on purpose: almost every slot is a constant, and a wave whose lanes all hold constants skips the rest;
-  //  a select-only version was measured slower in zg_k_seqpost and zg_k_scan)
-  const uint32_t t = ZG_SYM_TAG(v);
-  if (!t) return v;
-  const uint32_t a = t == 1 ? A.s[0] : t == 2 ? A.s[1] : A.s[2], k = ZG_SYM_K(v);
-  if (ZG_SYM_TAG(a)) {
-    uint32_t kk = ZG_SYM_K(a) + k;
-    if (kk > 0x3FFFFFFFu) kk = 0x3FFFFFFFu;
-    return (a & 0xC0000000u) | kk;
-  }
-  return a > k ? a - k : 0;
-}
-// apply A first, then B
-__device__ __forceinline__ ZgHistMap zg_map_compose(const ZgHistMap& A, const ZgHistMap& B) {
-  ZgHistMap r;
-  r.s[0] = zg_map_apply(A, B.s[0]); r.s[1] = zg_map_apply(A, B.s[1]); r.s[2] = zg_map_apply(A, B.s[2]);
-  return r;
-}
-
+// (ZgHistMap, zg_map_identity, zg_map_apply, zg_map_compose: zg_dev.h, next to zg_hist_step; the CPU harness folds the same maps)
 __global__ void __launch_bounds__(ZG_SP_T, 4) zg_k_seqpost(ZgBatchDev d) {
   __shared__ ZgHistMap s_wm[ZG_SP_T / 64];
   __shared__ uint32_t s_wl[ZG_SP_T / 64], s_wo[ZG_SP_T / 64], s_wx[ZG_SP_T / 64];
