@@ -206,6 +206,31 @@ int zgpu_decode_frames_device_src(zgpu_ctx*, const void* const* device_srcs, con
  * zgpu_debug_frames_device_stats is filled by that call as well. Returns how many were written. */
 int zgpu_debug_frames_device_src_stats(const zgpu_ctx*, uint64_t* out, int n);
 
+/* ---- dictionary frames inside the shared submits of the three calls above ---------------------------------------------------------------------
+ * Dictionaries are how many small buffers are compressed well (one trained dictionary, thousands of short records), and by default every entry
+ * that holds a dictionary frame is decoded alone: a submit per frame at least, a D2H of the entry for device-resident sources.
+ * zgpu_set_frames_shared_dicts(ctx, 1): dictionary frames whose id is registered (zgpu_add_dict) join the shared submits of zgpu_decode_frames,
+ * zgpu_decode_frames_device and zgpu_decode_frames_device_src. 0 (the default): they are decoded alone, as before — every call then behaves byte
+ * for byte and counter for counter as it did without the switch.
+ *  - The contract of each call is unchanged: results[i] is what zgpu_decode_all of entry i ALONE returns; entries are isolated and their order
+ *    does not matter; nothing of a failed entry and nothing at or behind dst + written is written; the hash rule and the synchronisation on
+ *    return are the same. With device-resident sources no byte of a shared entry's input crosses to the host.
+ *  - In the submit's output a dictionary frame takes [gap of the dictionary's content length][its plaintext]; the dictionary's one device copy
+ *    per context (uploaded at first use, freed with the context, replaced when zgpu_add_dict replaces the dictionary) is replicated into the
+ *    gaps and into the frames' table slots by zg_k_dictfill: two launches per submit that holds dictionary frames — the tables in front of the
+ *    entropy stages, the contents once the frames' sizes have placed the gaps.
+ *  - The submit cut counts a dictionary frame's content length towards the 512 MiB plaintext budget, so zgpu_debug_frames_submits may differ
+ *    from the same call with the switch off. zgpu_plaintext_bound, and with it the room a caller needs, does not change.
+ *  - Still decoded alone, with today's answers: an entry with a frame whose id is not registered (ZGPU_E_DICT_NOT_PROVIDED — or, if the
+ *    window is refused first, ZGPU_E_WINDOW_SIZE_TOO_BIG), a dictionary without content, and an entry whose shared verdict is Unsupported /
+ *    Internal: a match into the dictionary behind a drain that falls inside decode_all (more than 1 MiB of one frame in front of it). */
+void zgpu_set_frames_shared_dicts(zgpu_ctx*, int on);
+int zgpu_frames_shared_dicts(const zgpu_ctx*);
+/* diagnostics: the context's last zgpu_decode_frames / _device / _device_src call — out[0] dictionary frames decoded inside shared submits (of
+ * entries that succeeded), [1] zg_k_dictfill launches, [2] dictionary bytes replicated (contents and tables), [3] fill kernel microseconds
+ * (HIP events), [4] entries with a dictionary frame that still went alone. All 0 with the switch off. Returns how many were written. */
+int zgpu_debug_frames_dict_stats(const zgpu_ctx*, uint64_t* out, int n);
+
 /* ---- what device-resident compressed input holds: bounds and frame tables without a download -----------------------------------------------
  * zgpu_decode_frames_device_src needs caps[i], and zgpu_plaintext_bound reads host memory. These calls answer the sizing question — and how many
  * frames an entry has, where they start, which declare a content size, name a dictionary or carry a checksum — for entries that lie in device

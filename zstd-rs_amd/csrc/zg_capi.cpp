@@ -30,6 +30,7 @@ int zgpu_ctx_create(int device_id, zgpu_ctx** out) {
 }
 void zgpu_ctx_destroy(zgpu_ctx* c) {
   if (!c) return;
+  if (!c->dict_dev.empty()) { (void)hipSetDevice(c->eng->device()); for (auto& d : c->dict_dev) d.second.buf.release(); }
   delete c->eng;
   delete c;
 }
@@ -382,6 +383,14 @@ extern "C" int zgpu_add_dict(zgpu_ctx* c, const uint8_t* raw, size_t len, uint32
   int st = parse_dict(raw, len, &d);
   if (st) return st;
   if (id_out) *id_out = d.id;
+  {   // (a replaced dictionary's device copy is stale: the next shared submit uploads the new one)
+    auto it = c->dict_dev.find(d.id);
+    if (it != c->dict_dev.end()) { (void)hipSetDevice(c->eng->device()); it->second.buf.release(); c->dict_dev.erase(it); }
+    zg::DictFacts f;
+    f.content_len = d.content.size();
+    memcpy(f.hist, d.hist, 12);
+    c->dict_facts[d.id] = f;
+  }
   c->dicts[d.id] = std::move(d);   // BTreeMap::insert: a dictionary with the same id is replaced (frame_decoder.rs:224-227)
   return ZGPU_OK;
 }

@@ -17,9 +17,17 @@ struct ZgDict {   // Dictionary (decoding/dictionary.rs:12-37), tables in the en
   uint32_t hist[3] = {1, 4, 8};
   std::vector<uint8_t> content;
 };
+struct ZgDictDev {   // a dictionary's one device copy per context (zg_dictfill.h: DictImage), uploaded when a shared submit first needs it
+  zg::DevBuf buf;
+  zgd::DictImage im{};
+};
 struct zgpu_ctx {
   zg::Engine* eng = nullptr;
   std::map<uint32_t, ZgDict> dicts;   // FrameDecoder::dicts (frame_decoder.rs:82)
+  std::map<uint32_t, zg::DictFacts> dict_facts;   // what the walk of a shared submit is told of each (zgpu_add_dict keeps it in step with dicts)
+  std::map<uint32_t, ZgDictDev> dict_dev;         // freed with the context; an entry goes when zgpu_add_dict replaces its dictionary
+  bool frames_shared_dicts = false;               // zgpu_set_frames_shared_dicts
+  uint64_t frames_dict_stats[5] = {0, 0, 0, 0, 0};   // of the last zgpu_decode_frames* call (zgpu_debug_frames_dict_stats)
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
   uint64_t frames_device_stats[7] = {0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
   uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)

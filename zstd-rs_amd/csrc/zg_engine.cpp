@@ -174,6 +174,8 @@ Batch::~Batch() {
   if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
   if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
   for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
+  for (DevBuf& x : d_fill_) if (x.p && eng) { (void)hipSetDevice(eng->device_); x.release(); }
+  for (hipEvent_t e : ev_fill_) if (e) (void)hipEventDestroy(e);
   if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
   for (hipEvent_t e : ev_gather_) if (e) (void)hipEventDestroy(e);
 }
@@ -317,7 +319,7 @@ int Engine::prepare(const uint8_t* src, size_t len, Batch** out) {
 }
 
 int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
-                            std::vector<int>* walk, std::vector<uint32_t>* first_frame) {
+                            std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts) {
   Batch* b = new Batch();
   b->eng = this;
   b->src_len = len;
@@ -325,7 +327,7 @@ int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off,
   first_frame->assign(n + 1, 0);
   for (uint32_t i = 0; i < n; i++) {
     (*first_frame)[i] = (uint32_t)b->info.size();
-    (*walk)[i] = parse_frames(src + off[i], elen[i], max_window, &b->bb, &b->info, off[i]);
+    (*walk)[i] = parse_frames(src + off[i], elen[i], max_window, &b->bb, &b->info, off[i], dicts);
     if (!b->parse_status) b->parse_status = (*walk)[i];
   }
   (*first_frame)[n] = (uint32_t)b->info.size();
@@ -445,7 +447,7 @@ int Engine::index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, con
 }
 
 int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
-                                   std::vector<int>* walk, std::vector<uint32_t>* first_frame) {
+                                   std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts) {
   Batch* b = new Batch();
   b->eng = this;
   b->src_len = total;
@@ -456,7 +458,7 @@ int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const 
     bool consistent = true;
     (*first_frame)[j] = (uint32_t)b->info.size();
     (*walk)[j] = parse_frames_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), e[i].len, max_window, &b->bb, &b->info, off[j],
-                                   &consistent);
+                                   &consistent, dicts);
     if (!consistent) { delete b; last_error = "zgpu_decode_frames_device_src: skeleton records out of step with the walk"; return ZG_INTERNAL; }
     if (!b->parse_status) b->parse_status = (*walk)[j];
   }
@@ -674,7 +676,9 @@ int Batch::run() {
   // (not with ramped units, a measurement switch: their sweep chain polls flags that the flatten of a no-op run never raises — ADVICE r4)
   // (not for a declared total of 0: the device's "sized in advance" marker is a capacity > 0, and a submit that declares nothing but produces
   //  one byte kept its promise by that marker while the host's capacity said 0 — zgpu_batch_read refused the byte, tools/dev/soak_batch.py)
-  if (!fs && all_declared && declared_total && !eng->no_presize_ && declared_total <= bb.out_bound && !bb.ramped) {
+  // (nor a shared submit with dictionary frames: the host places their contents once it knows where the scan put the frames)
+  dictfill_launches = 0; dictfill_bytes = 0; dictfill_us = 0; fill_mask_ = 0;
+  if (!fs && all_declared && declared_total && !eng->no_presize_ && declared_total <= bb.out_bound && !bb.ramped && frame_dicts_.empty()) {
     // (the scratch first: it is four times the output. When either reserve fails nothing of the attempt stays allocated — the sizes taken
     //  from the scan may well fit where the declared ones did not: ADVICE r5)
     if (sc->d_og.reserve(declared_total * 4 + 64) == 0 && sc->d_dst.reserve(kOutFront + declared_total + 64) == 0) {
@@ -705,6 +709,7 @@ int Batch::run() {
     ZG_HIP(hipMemcpyAsync(d.huf_arena + (size_t)fr.carry_huf_slot * ZG_HUF_SLOT_U16, fs->d_huf.p, ZG_HUF_SLOT_U16 * 2, hipMemcpyDeviceToDevice, s));
     ZG_HIP(hipMemcpyAsync(d.huf_maxbits + fr.carry_huf_slot, &fs->huf_maxbits, 1, hipMemcpyHostToDevice, s));
   }
+  if (!frame_dicts_.empty()) { const int st = dictfill_launch(0); if (st) return st; }   // (behind the resets above, in front of the first kernel that reads a carry slot)
   // ---- phase 1: entropy stages + scan. Literals (Huffman tree descriptions -> streams) and sequences (FSE descriptions ->
   // state chains -> post-pass) of a block are independent, and all of these kernels are latency-bound chains that leave most
   // of the chip idle: the two chains run side by side on two streams and meet again in zg_k_merge.
@@ -742,10 +747,71 @@ int Batch::run() {
   // behind the scan right away, and the device checks the promise (zg_k_scanf; a frame that produces more than it declared turns
   // them into no-ops and sync() repeats them the slow way: Frame_Content_Size is never checked by the reference, frame_decoder.rs:541-577).
   if (!presized) { const int st = size_output(); if (st) return st; }
+  if (!frame_dicts_.empty()) { const int st = dictfill_launch(1); if (st) return st; }   // (in front of the first kernel that reads or writes the output)
   const int st2 = launch_phase2();
   if (st2) return st2;
   ZG_HIP(hipGetLastError());
   ran = true;
+  return ZG_OK;
+}
+
+int Batch::set_frame_dicts(std::vector<zgd::DictImage> images) {
+  if (fs || images.size() != bb.frames.size()) return ZG_BAD_ARG;
+  bool any = false;
+  for (size_t f = 0; f < images.size(); f++) {
+    if (images[f].content_len != bb.frames[f].dict_len) return ZG_BAD_ARG;   // (what the walk was told of the dictionary is what the image holds)
+    any = any || images[f].content_len;
+  }
+  if (any) frame_dicts_ = std::move(images);
+  else frame_dicts_.clear();
+  return ZG_OK;
+}
+
+// part 0: every dictionary frame's tables into its carry slots of the two arenas; part 1: every dictionary frame's content into the gap in front of
+// its plaintext (frame_out holds the scan's placement: size_output). One launch each; a segment that would leave its buffer is refused.
+int Batch::dictfill_launch(int part) {
+  const ZgBatchDev& d = dev;
+  std::vector<zgd::Seg> segs;
+  auto at = [](const void* p) { return (uint64_t)(uintptr_t)p; };
+  for (uint32_t f = 0; f < d.nframes; f++) {
+    const zgd::DictImage& im = frame_dicts_[f];
+    if (!im.content_len) continue;
+    const ZgFrame& fr = bb.frames[f];
+    if (part == 0) {
+      if (fr.carry_slot >= d.nslots || fr.carry_huf_slot < 0 || (uint32_t)fr.carry_huf_slot >= d.nhuf_slots) return ZG_INTERNAL;   // (never: BatchBuilder::finish)
+      segs.push_back(zgd::Seg{im.fse, at(d.fse_arena + (size_t)fr.carry_slot * ZG_FSE_SLOT_U32), zgd::kFseBytes});
+      segs.push_back(zgd::Seg{im.logs, at(d.slot_log + (size_t)fr.carry_slot * 4), 4});
+      segs.push_back(zgd::Seg{im.huf, at(d.huf_arena + (size_t)fr.carry_huf_slot * ZG_HUF_SLOT_U16), zgd::kHufBytes});
+      segs.push_back(zgd::Seg{im.maxbits, at(d.huf_maxbits + fr.carry_huf_slot), 1});
+    } else {
+      const ZgFrameOut& fo = frame_out[f];
+      if (fo.out_base < fr.dict_len || fo.out_base > d.dst_cap || fo.out_size > d.dst_cap - fo.out_base) {   // (never: zg_k_scanf laid the gap out)
+        eng->last_error = "zg_k_dictfill: a dictionary frame's gap outside the output";
+        return ZG_INTERNAL;
+      }
+      segs.push_back(zgd::Seg{im.content, at(d.dst + (fo.out_base - fr.dict_len)), fr.dict_len});
+    }
+  }
+  if (segs.empty() || segs.size() > 0xFFFFFFFFull) return segs.empty() ? ZG_OK : ZG_INTERNAL;
+  std::vector<zgs::Chunk> ch;
+  zgd::plan_fill(segs.data(), (uint32_t)segs.size(), 0, &ch);
+  if (ch.empty() || ch.size() > 0xFFFFFFFFull) return ch.empty() ? ZG_OK : ZG_INTERNAL;
+  const size_t sb = segs.size() * sizeof(zgd::Seg), cb = ch.size() * sizeof(zgs::Chunk);
+  DevBuf& t = d_fill_[part];
+  int st = t.reserve(sb + cb);
+  if (st) return st;
+  for (int k = 0; k < 2; k++) if (!ev_fill_[2 * part + k]) ZG_HIP(hipEventCreate(&ev_fill_[2 * part + k]));
+  hipStream_t s = eng->stream_;
+  ZG_HIP(hipMemcpyAsync(t.p, segs.data(), sb, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipMemcpyAsync((uint8_t*)t.p + sb, ch.data(), cb, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (the tables are pageable and go out of scope; the stream is idle here: the uploads, or the scan, were waited for)
+  ZG_HIP(hipEventRecord(ev_fill_[2 * part], s));
+  zg_launch_dictfill(t.as<zgd::Seg>(), (const zgs::Chunk*)((uint8_t*)t.p + sb), (uint32_t)ch.size(), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev_fill_[2 * part + 1], s));
+  fill_mask_ |= 1u << part;
+  dictfill_launches++;
+  for (const zgd::Seg& x : segs) dictfill_bytes += x.len;
   return ZG_OK;
 }
 
@@ -987,6 +1053,9 @@ int Batch::sync() {
     if (hipEventElapsedTime(&m, ev[i], ev[i + 1]) == hipSuccess) ms[i] = m;
   }
   float m = 0;
+  dictfill_us = 0;
+  for (int k = 0; k < 2; k++)
+    if (((fill_mask_ >> k) & 1u) && hipEventElapsedTime(&m, ev_fill_[2 * k], ev_fill_[2 * k + 1]) == hipSuccess) dictfill_us += (uint64_t)(m * 1000.0f + 0.5f);
   if (hipEventElapsedTime(&m, sc->ev_huf[0], sc->ev_huf[1]) == hipSuccess) ms[ZG_T_HUF] = m;   // beside seq + seqpost, not in line ...
   if (dev.flags & ZG_FLAG_LIT_DIRECT) ms[ZG_T_LIT] = ms[ZG_T_LIT] > ms[ZG_T_HUF] ? ms[ZG_T_LIT] - ms[ZG_T_HUF] : 0.f;   // ... or, after the scan, in front of zg_k_lit
   if (hipEventElapsedTime(&m, ev[0], ev[ZG_T_TOTAL]) == hipSuccess) ms[ZG_T_TOTAL] = m;

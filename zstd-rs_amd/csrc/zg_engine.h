@@ -135,6 +135,15 @@ class Batch {
   bool all_declared = false;             //   output can be sized before the run, and the LZ77 stages enqueued without waiting for the scan
   bool presized = false;                 // the last run() did that
   bool exact_ran = false;                // sync(): zg_k_exact replayed the reference's buffer bookkeeping for this submit (tests)
+  // dictionary frames of a shared submit (zgpu_set_frames_shared_dicts; the walk marked them: ZgFrame::dict_len, FrameInfo::header.dict_id). The
+  // caller hands over, per frame of the submit, the device image of its dictionary (content_len 0: the frame has none) before run(); run() then
+  // launches zg_k_dictfill (zg_dictfill.h) twice: the tables into the frames' carry slots in front of the entropy stages, the contents into
+  // the gaps in front of the frames' plaintext once the scan has placed them (the gaps' positions depend on the sizes of the frames in front).
+  // Such a submit is never sized before the run. Every segment is checked against the engine's buffers before a launch.
+  int set_frame_dicts(std::vector<zgd::DictImage> images);
+  uint32_t dictfill_launches = 0;        // of the last run()
+  uint64_t dictfill_bytes = 0;           //   bytes it replicated
+  uint64_t dictfill_us = 0;              //   its kernels' time between HIP events (valid after sync())
   bool gather_launched = false;          // prepare_entries_device: zg_k_gather brought the compressed bytes (no entry had any: no launch)
   uint64_t gather_us = 0;                //   its time between two HIP events
 
@@ -195,6 +204,11 @@ class Batch {
   DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
   hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
   bool scatter_on_ = false;
+  std::vector<zgd::DictImage> frame_dicts_;   // set_frame_dicts
+  DevBuf d_fill_[2];                          // dictfill_launch: the segments, then the chunk table (0: tables, 1: contents)
+  hipEvent_t ev_fill_[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint32_t fill_mask_ = 0;                    //   which of the two ran
+  int dictfill_launch(int part);
   std::vector<zgs::Seg> gather_segs_;    // Engine::upload with a gather: the entries' segments and their chunks (the tables travel from here)
   std::vector<zgs::Chunk> gather_chunks_;
   DevBuf d_gather_;
@@ -210,8 +224,9 @@ class Engine {
   int prepare(const uint8_t* src, size_t len, Batch** out);
   // n independent entries that lie back to back in src (entry i at off[i], len[i] bytes): each is walked on its own with decode_all's rule
   // (parse_frames), its frames appended to ONE submit. walk[i] = the entry's walk status, its frames are [first_frame[i], first_frame[i + 1]).
+  // dicts: the lookup the walk resolves Dictionary_IDs with (zg_host_parse.h; nullptr: a dictionary frame ends its entry's walk)
   int prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
-                      std::vector<int>* walk, std::vector<uint32_t>* first_frame);
+                      std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts = nullptr);
   // The same for entries whose compressed bytes lie in DEVICE memory of the caller (zgpu_decode_frames_device_src, which has checked every range
   // against the runtime's allocations). walk_entries: zg_k_walk (zg_walk.h) follows the header chain of all n entries in two launches, count
   // and emit, and brings back the skeleton: entry i's records are sk->recs[sk->first[i] .. sk->first[i + 1]), sk->ends[i] where its lane
@@ -223,7 +238,7 @@ class Engine {
   struct Skeleton { std::vector<zgw::Rec> recs; std::vector<uint64_t> first; std::vector<zgw::End> ends; };
   int walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats);
   int prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
-                             std::vector<int>* walk, std::vector<uint32_t>* first_frame);
+                             std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts = nullptr);
   // What such entries hold, from their headers alone (zgpu_frames_index_device / zgpu_frames_table_device): ONE zg_k_index launch (zg_index.h)
   // over all n entries. first == nullptr: the summary pass, out[i] = entry i's summary. Else the emit pass: sum = the summaries of the summary
   // pass, first[i] .. first[i + 1] (their prefix sum, n + 1 slots) the frame records lane i may write of recs[0 .. first[n]); out = what this

@@ -19,6 +19,13 @@
 // plaintext_bound_skel (zg_host_parse.cpp) are the host's one walk run over those records. A submit's entries reach the engine's source buffer
 // by one zg_k_gather launch in place of the staging copy and the H2D (Engine::prepare_entries_device). Submit cutting, verdicts, the sink and
 // the again-list are the code above; an entry of the again-list is downloaded (one D2H) and decoded alone from the host copy.
+//
+// zgpu_set_frames_shared_dicts(ctx, 1): dictionary frames whose id is registered stay in the submit. The walk is handed a lookup (shared_lookup)
+// and starts such a frame from the dictionary's history and tables; its place in the batch output is [gap of the content's length][plaintext],
+// zg_k_dictfill (zg_dictfill.h) replicates the dictionary's device copy into the gaps and carry slots, and zg_k_exact replays the reference's
+// buffer bookkeeping for every such frame as it does for a one-frame run. The verdict of an entry that holds a dictionary frame is put together
+// in zgpu_decode_all's order for such an entry — frame by frame (zg_decode_all_per_frame) — and what the submit cannot serve exactly (an
+// unregistered id, Unsupported / Internal: the dictionary splice behind a drain inside decode_all, zg_exact.h) goes alone as before.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -110,8 +117,42 @@ struct Call {
   const uint8_t* refused = nullptr;                //   entries whose source or destination failed the pointer check
   const uint64_t* bound = nullptr;                 //   plaintext_bound of every entry, from its records
   uint64_t* sstats = nullptr;                      //   zgpu_ctx::frames_device_src_stats
+  const DictLookup* dicts = nullptr;               // shared dictionaries (zgpu_set_frames_shared_dicts): what the walks resolve ids with; else nullptr
   zgpu_entry_result& result(uint32_t i) const { return dres ? dres[i].r : res[i]; }
 };
+
+// the lookup of a shared submit's walks: the context's registered dictionaries. One without content is not resolved — its frames go alone, as
+// with the switch off (ZgFrame::dict_len != 0 is what marks a dictionary frame for the engine).
+const DictFacts* shared_find(const void* user, uint32_t id) {
+  const zgpu_ctx* c = (const zgpu_ctx*)user;
+  auto it = c->dict_facts.find(id);
+  return it == c->dict_facts.end() || it->second.content_len == 0 ? nullptr : &it->second;
+}
+
+// the device copy of a registered dictionary, uploaded at first use (zg_dictfill.h: DictImage; the formats are zg_apply_dict's)
+int dict_image(zgpu_ctx* c, uint32_t id, zgd::DictImage* out) {
+  auto have = c->dict_dev.find(id);
+  if (have != c->dict_dev.end()) { *out = have->second.im; return ZGPU_OK; }
+  auto it = c->dicts.find(id);
+  if (it == c->dicts.end()) return ZGPU_E_INTERNAL;
+  const ZgDict& d = it->second;
+  if (d.fse.size() != ZG_FSE_SLOT_U32 || d.huf.size() != ZG_HUF_SLOT_U16) return ZGPU_E_INTERNAL;
+  ZgDictDev dd;
+  int st = dd.buf.reserve(zgd::image_bytes(d.content.size()));
+  if (st) return st;
+  dd.im = zgd::image_at((uint64_t)(uintptr_t)dd.buf.p, d.content.size());
+  const uint8_t logs[16] = {d.logs[0], d.logs[1], d.logs[2], d.logs[3]}, mb[16] = {d.huf_maxbits};
+  auto up = [](uint64_t at, const void* h, size_t n) { return !n || hipMemcpy((void*)(uintptr_t)at, h, n, hipMemcpyHostToDevice) == hipSuccess; };
+  if (!up(dd.im.content, d.content.data(), d.content.size()) || !up(dd.im.fse, d.fse.data(), zgd::kFseBytes) || !up(dd.im.logs, logs, 16) ||
+      !up(dd.im.huf, d.huf.data(), zgd::kHufBytes) || !up(dd.im.maxbits, mb, 16)) {
+    (void)hipGetLastError();
+    dd.buf.release();
+    return ZGPU_E_HIP;
+  }
+  *out = dd.im;
+  c->dict_dev[id] = dd;
+  return ZGPU_OK;
+}
 
 // what a submit leaves behind for its sink
 struct Submit {
@@ -134,33 +175,56 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   std::vector<uint32_t>& ff = u.ff;
   int st;
   if (k.sk) {   // the bytes are on the device: no staging, no upload — the skeleton is parsed, one zg_k_gather launch moves the entries
-    if ((st = k.c->eng->prepare_entries_device(k.dev, *k.sk, idx, off.data(), n, total_in, &u.b, &walk, &ff))) return st;
+    if ((st = k.c->eng->prepare_entries_device(k.dev, *k.sk, idx, off.data(), n, total_in, &u.b, &walk, &ff, k.dicts))) return st;
     k.sstats[3] += u.b->gather_launched ? 1u : 0u; k.sstats[4] += u.b->gather_us;
   } else {
     if ((st = in.get(total_in))) return st;
     parallel_for(n, total_in, 8u << 20, [&](uint32_t j) { if (len[j]) memcpy(in.p + off[j], k.srcs[idx[j]], len[j]); });
-    if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff))) return st;
+    if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff, k.dicts))) return st;
   }
   Batch* b = u.b;
+  // the submit's dictionary frames (none unless the walks had a lookup): their dictionaries' device copies, for zg_k_dictfill
+  std::vector<uint8_t> has_dict(n, 0);
+  if (k.dicts) {
+    std::vector<zgd::DictImage> images(b->info.size(), zgd::DictImage{});
+    if (b->info.size() != b->bb.frames.size()) return ZGPU_E_INTERNAL;
+    for (uint32_t j = 0; j < n; j++)
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+        if (!b->bb.frames[f].dict_len) continue;
+        if ((st = dict_image(k.c, b->info[f].header.dict_id, &images[f]))) return st;
+        has_dict[j] = 1;
+      }
+    if ((st = b->set_frame_dicts(std::move(images)))) return st;
+  }
   b->drain_rule = ZG_DRAIN_DECODE_ALL;   // (as zgpu_decode_all: decode_all drains its DecodeBuffer every MiB, zg_exact.h)
   if ((st = b->run()) || (st = b->sync())) return st;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
   if (fo.size() != b->info.size()) return ZGPU_E_INTERNAL;
+  uint64_t* ds = k.c->frames_dict_stats;
+  ds[1] += b->dictfill_launches; ds[2] += b->dictfill_bytes; ds[3] += b->dictfill_us;
 
   // verdicts (zgpu_decode_all, zg_capi.cpp, on the entry's own frames)
   for (uint32_t j = 0; j < n; j++) {
     const uint32_t i = idx[j];
     zgpu_entry_result& r = k.result(i);
-    if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); continue; }   // zgpu_decode_all's frame-by-frame path
+    // zgpu_decode_all's frame-by-frame path (the switch off, or an id the lookup did not resolve)
+    if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); ds[4] += k.dicts ? 1u : 0u; continue; }
     int dev = 0;
     uint64_t bytes = 0;
+    bool small = false;   // (has_dict) the entry's output up to a frame in front of the first failing one does not fit
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (!dev && fo[f].status) dev = (int)fo[f].status;
       bytes += fo[f].out_size;
+      if (has_dict[j] && !dev && !b->info[f].host_status && bytes > k.caps[i]) small = true;
     }
-    if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, false}); continue; }
-    r.status = dev ? dev : walk[j] ? walk[j] : bytes > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
+    if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[4] += has_dict[j]; continue; }
+    // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
+    // next one is looked at), so a frame that does not fit ends it with TargetTooSmall BEFORE a later frame's error or the walk's; without one,
+    // zgpu_decode_all's one submit reports a device error first, then the walk's, then TargetTooSmall.
+    if (has_dict[j]) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j];
+    else r.status = dev ? dev : walk[j] ? walk[j] : bytes > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
     if (r.status) continue;
+    if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[0] += b->bb.frames[f].dict_len ? 1u : 0u;
     r.written = bytes;
     r.nframes = ff[j + 1] - ff[j];
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
@@ -386,6 +450,7 @@ int decode_entries(Call& k, uint32_t n) {
   const Tuning& tn = c->eng->tuning();
   const uint64_t S = tn.frames_submit_bytes ? tn.frames_submit_bytes : kFramesSubmitBytes;
   c->frames_submits = 0;
+  for (uint64_t& x : c->frames_dict_stats) x = 0;
   std::vector<DevRange> known;
   std::vector<uint32_t> group;
   uint64_t in_group = 0, in_bytes = 0;   // plaintext bound and input bytes of the submit being gathered (both bounded by S)
@@ -399,7 +464,7 @@ int decode_entries(Call& k, uint32_t n) {
       if (k.sk) bad = k.refused[i] != 0;                                   // (device sources: checked before the walk)
       else if (!bad && k.dres && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
       if (bad) { k.result(i).status = ZGPU_E_BAD_ARG; continue; }
-      bound = k.sk ? k.bound[i] : plaintext_bound(k.srcs[i], k.lens[i]);
+      bound = k.sk ? k.bound[i] : plaintext_bound(k.srcs[i], k.lens[i], k.dicts);   // (with its dictionary frames' gaps)
     }
     // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
     // yield nothing — skippable frames, garbage — still travel to the device, through the pinned staging.)
@@ -425,6 +490,8 @@ extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const
   if (!c || (n && (!srcs || !lens || !dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
   const Tuning& tn = c->eng->tuning();
   Call k{c, srcs, lens, dsts, caps, results, tn.hash_device_max_set, tn.hash_device_max_set ? tn.hash_device_max : kHashDeviceMax, {}};
+  const DictLookup lookup{shared_find, c};
+  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
   return decode_entries(k, n);
 }
 
@@ -437,6 +504,8 @@ extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs
   k.dres = results;
   k.no_hash = opts && (opts->flags & 1u);
   k.stats = c->frames_device_stats;
+  const DictLookup lookup{shared_find, c};
+  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
   int st = decode_entries(k, n);
   // every later operation on any stream sees the bytes: nothing of this call is in flight on the engine's streams (the scatter ran on the second)
   if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
@@ -457,6 +526,9 @@ extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* dev
   k.no_hash = opts && (opts->flags & 1u);
   k.stats = c->frames_device_stats;
   k.sstats = c->frames_device_src_stats;
+  const DictLookup lookup{shared_find, c};
+  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
+  for (uint64_t& x : c->frames_dict_stats) x = 0;
   std::vector<uint8_t> refused(n, 0);
   std::vector<Engine::DevEntry> dev(n);
   std::vector<uint64_t> bound(n, 0);
@@ -474,7 +546,7 @@ extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* dev
   int st = c->eng->walk_entries(dev.data(), n, &sk, k.sstats);
   for (uint32_t i = 0; i < n && !st; i++) {
     bool consistent = true;
-    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent);
+    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent, k.dicts);
     if (!consistent) st = ZGPU_E_INTERNAL;
   }
   if (!st) {
@@ -586,6 +658,14 @@ extern "C" int zgpu_debug_frames_device_src_stats(const zgpu_ctx* c, uint64_t* o
   if (!c || !out) return 0;
   int k = 0;
   for (; k < n && k < 6; k++) out[k] = c->frames_device_src_stats[k];
+  return k;
+}
+extern "C" void zgpu_set_frames_shared_dicts(zgpu_ctx* c, int on) { if (c) c->frames_shared_dicts = on != 0; }
+extern "C" int zgpu_frames_shared_dicts(const zgpu_ctx* c) { return c && c->frames_shared_dicts ? 1 : 0; }
+extern "C" int zgpu_debug_frames_dict_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c || !out) return 0;
+  int k = 0;
+  for (; k < n && k < 5; k++) out[k] = c->frames_dict_stats[k];
   return k;
 }
 extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) {

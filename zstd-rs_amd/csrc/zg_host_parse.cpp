@@ -295,7 +295,7 @@ void BatchBuilder::finish() {
     // through the scratch and the sweep.
     // (round 5: only where units are large — with units of a few blocks the share rounds to 1.4 - 1.5 and the direct unit becomes the longest
     //  of the submit: twelve Silesia-sized frames in units of 5 blocks, flatten 0.82 ms with the share, 0.65 ms without)
-    const bool direct_frame = unit_blocks == 0 && !ramp && direct_units && !fr.fixed_base && !fr.sparse && nun >= 2 && nun <= direct_max_units && ubf >= 16;
+    const bool direct_frame = unit_blocks == 0 && !ramp && direct_units && !fr.fixed_base && !fr.dict_len && !fr.sparse && nun >= 2 && nun <= direct_max_units && ubf >= 16;
     uint32_t first_take = 0, rest_take = 0;
     if (direct_frame) {
       first_take = (uint32_t)(((uint64_t)fr.nblocks * direct_share10 + (10ull * (nun - 1) + direct_share10) - 1) / (10ull * (nun - 1) + direct_share10));
@@ -329,7 +329,8 @@ void BatchBuilder::finish() {
       // fixed_base before finish()) copies from nothing outside itself: the flatten resolves it to bytes right away (direct unit, zg_flat4.h)
       // ... when that saves a noticeable share of the frame's sweep steps: a direct unit takes ~10 % longer to flatten than a
       // pointer-mode one, and all units of a submit are flattened side by side (a frame of hundreds of units gains nothing)
-      if (i == 0 && !u.noseq && direct_units && !fr.fixed_base && !fr.sparse && (fr.nblocks + ubf - 1) / ubf <= direct_max_units) u.noseq = ZG_UNIT_DIRECT;
+      // (nor a dictionary frame of a shared submit: its first unit copies from the dictionary's content in front of it)
+      if (i == 0 && !u.noseq && direct_units && !fr.fixed_base && !fr.dict_len && !fr.sparse && (fr.nblocks + ubf - 1) / ubf <= direct_max_units) u.noseq = ZG_UNIT_DIRECT;
       units.push_back(u);
       i += u.nblocks; done_blocks += u.nblocks;
     }
@@ -459,7 +460,8 @@ struct SkelSource {
   void checksum_short(size_t p) { const zgw::Rec* r = take(zgw::kCksum, p); if (r->have != len - p) ok = false; }
 };
 
-template <class S> int parse_frames_on(S& s, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
+template <class S> int parse_frames_on(S& s, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base,
+                                       const DictLookup* dicts) {
   // FrameDecoder::decode_all (frame_decoder.rs:541-577): concatenated frames, skippable frames skipped;
   // the first error ends the walk (the reference returns it).
   size_t p = 0;
@@ -481,13 +483,15 @@ template <class S> int parse_frames_on(S& s, size_t len, uint64_t max_window, Ba
     uint64_t w;
     if ((st = frame_window_size(h, &w))) return st;
     if (w > max_window) return ZG_WINDOW_SIZE_TOO_BIG;          // frame_decoder.rs:137-145
-    if (h.has_dict_id) return ZG_DICT_NOT_PROVIDED;             // :212-217 (dictionaries: see DESIGN.md "next")
+    const DictFacts* df = h.has_dict_id && dicts ? dicts->find(dicts->user, h.dict_id) : nullptr;
+    if (h.has_dict_id && !df) return ZG_DICT_NOT_PROVIDED;      // :212-217 (no lookup: dictionary frames are the FrameDecoder mirror's, zg_capi.cpp)
     FrameInfo fi;
     fi.header = h;
     fi.window_size = w;
     fi.src_begin = base + p;
     p += c;
-    bb->begin_frame(w, kHist, 0);
+    if (df) bb->frames[bb->begin_frame(w, df->hist, 0xFu)].dict_len = df->content_len;   // init_from_dict (scratch.rs:70-78)
+    else bb->begin_frame(w, kHist, 0);
     for (;;) {
       if (len - p < 3) { st = ZG_FAILED_READ_BLOCK_HEADER; break; }
       BlockHeader bh;
@@ -522,7 +526,7 @@ template <class S> int parse_frames_on(S& s, size_t len, uint64_t max_window, Ba
   return ZG_OK;
 }
 
-template <class S> uint64_t plaintext_bound_on(S& s, size_t len) {
+template <class S> uint64_t plaintext_bound_on(S& s, size_t len, const DictLookup* dicts) {
   uint64_t total = 0;
   size_t p = 0;
   while (p < len) {
@@ -557,30 +561,32 @@ template <class S> uint64_t plaintext_bound_on(S& s, size_t len) {
       }
     }
     total += h.has_fcs() && h.frame_content_size < fb ? h.frame_content_size : fb;
+    if (h.has_dict_id && dicts) { const DictFacts* df = dicts->find(dicts->user, h.dict_id); if (df) total += df->content_len; }   // (its gap in a shared submit)
     if (!ok) break;
   }
   return total;
 }
 }  // namespace
 
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base) {
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base,
+                 const DictLookup* dicts) {
   ByteSource s{src, len};
-  return parse_frames_on(s, len, max_window, bb, info, base);
+  return parse_frames_on(s, len, max_window, bb, info, base, dicts);
 }
-uint64_t plaintext_bound(const uint8_t* src, size_t len) {
+uint64_t plaintext_bound(const uint8_t* src, size_t len, const DictLookup* dicts) {
   ByteSource s{src, len};
-  return plaintext_bound_on(s, len);
+  return plaintext_bound_on(s, len, dicts);
 }
 int parse_frames_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info,
-                      uint64_t base, bool* consistent) {
+                      uint64_t base, bool* consistent, const DictLookup* dicts) {
   SkelSource s{recs, nrec, len};
-  const int st = parse_frames_on(s, len, max_window, bb, info, base);
+  const int st = parse_frames_on(s, len, max_window, bb, info, base, dicts);
   *consistent = s.ok;
   return st;
 }
-uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent) {
+uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent, const DictLookup* dicts) {
   SkelSource s{recs, nrec, len};
-  const uint64_t b = plaintext_bound_on(s, len);
+  const uint64_t b = plaintext_bound_on(s, len, dicts);
   *consistent = s.ok && s.k == nrec;   // (the bound's walk goes as far as the lane's: every record is asked for)
   return b;
 }

@@ -131,9 +131,22 @@ struct FrameInfo {
   int host_status = 0;                   // error found while walking the frame (truncated input, bad header, ...)
 };
 
+// What the walk needs to know of a registered dictionary to keep a frame that names it in the submit (zgpu_set_frames_shared_dicts): the length
+// of its content and its offset history (dictionary.rs:12-37). find(user, id) returns nullptr for an id that is not registered.
+struct DictFacts { uint64_t content_len; uint32_t hist[3]; };
+struct DictLookup {
+  const DictFacts* (*find)(const void* user, uint32_t id);
+  const void* user;
+};
+
 // Host-only walk of concatenated frames into a BatchBuilder (no GPU involved; unit-tested on CPU).
 // base: offset of src in the buffer that will be uploaded (block bodies and FrameInfo::src_begin / src_end are counted from there)
-int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base = 0);
+// dicts: nullptr — a header with a Dictionary_ID ends the walk with ZG_DICT_NOT_PROVIDED. Else a frame whose id the lookup resolves starts
+// like DecoderScratch::init_from_dict leaves it (scratch.rs:70-78): begin_frame with the dictionary's offset history and all four tables
+// carried in (mask 0xF), ZgFrame::dict_len = the content's length — the engine fills the frame's carry slots and the dict_len bytes in front
+// of its plaintext (zg_dictfill.h) — and FrameInfo::header names the id; an id it does not resolve ends the walk as without a lookup.
+int parse_frames(const uint8_t* src, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info, uint64_t base = 0,
+                 const DictLookup* dicts = nullptr);
 // Byte ranges of the frames (and skippable frames) of a buffer, by walking frame and block headers only: what a work queue
 // needs to hand whole frames to different GPUs. Stops at the first malformed frame (its status is returned; ranges found so
 // far stay valid).
@@ -147,13 +160,14 @@ struct FrameFields { uint64_t window_size, frame_content_size; uint32_t dict_id,
 void frame_fields(const uint8_t* b, uint32_t have, FrameFields* out);
 // Upper bound of the plaintext of a buffer of concatenated frames from frame and block headers only (a frame's declared content size when it
 // is smaller; a compressed block counts 128 KiB). Tolerant: the walk stops where a header cannot be read and returns what it found so far.
-uint64_t plaintext_bound(const uint8_t* src, size_t len);
+// dicts: a frame whose Dictionary_ID the lookup resolves also counts the dictionary's content length — the room it takes in a shared submit.
+uint64_t plaintext_bound(const uint8_t* src, size_t len, const DictLookup* dicts = nullptr);
 // parse_frames and plaintext_bound of an entry of len bytes that lies in device memory, from the skeleton records zg_k_walk brought back
 // (zg_walk.h): the same walk — one body, instantiated for bytes and for records — reading every byte it asks for from the records.
 // *consistent = false: the records are not what a walk of len bytes asks for, in kind, position or count of bytes (never, unless the
 // source changed while it was walked); the results mean nothing then.
 int parse_frames_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, uint64_t max_window, BatchBuilder* bb, std::vector<FrameInfo>* info,
-                      uint64_t base, bool* consistent);
-uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent);
+                      uint64_t base, bool* consistent, const DictLookup* dicts = nullptr);
+uint64_t plaintext_bound_skel(const zgw::Rec* recs, uint32_t nrec, size_t len, bool* consistent, const DictLookup* dicts = nullptr);
 
 }  // namespace zg

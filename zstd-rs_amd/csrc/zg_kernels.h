@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "zg_types.h"
 #include "zg_scatter.h"
+#include "zg_dictfill.h"
 #include "zg_walk.h"
 #include "zg_index.h"
 
@@ -48,6 +49,9 @@ void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chu
 // zg_k_gather (zg_walk.h): the same chunks the other way round — segments whose src_off is an ADDRESS in device memory of the caller (the entries
 // of a submit of zgpu_decode_frames_device_src) copied to where the engine's kernels read the compressed bytes; dst: addresses in the engine's buffer
 void zg_launch_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);
+// zg_k_dictfill (zg_dictfill.h): a dictionary's content and tables from the context's device copy to the gaps and carry slots of the frames that
+// name it; segs hold addresses on both sides, chunks the plan of zgd::plan_fill
+void zg_launch_dictfill(const zgd::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);
 // zg_k_walk (zg_walk.h): one lane per entry follows the entry's header chain; ends[i] = where lane i stopped and how many skeleton records it has.
 // recs == nullptr: the count pass (nothing else is written); else lane i writes records lanes[i].first .. + lanes[i].limit of recs
 void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec* recs, hipStream_t s);

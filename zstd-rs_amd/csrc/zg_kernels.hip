@@ -1290,8 +1290,8 @@ __global__ void __launch_bounds__(ZG_SCAN_T) zg_k_scan(ZgBatchDev d) {
     fo.err_packed = 0xFFFFFFFFu;
     fo.og_base = 0;
     if (d.nframes == 1u) {   // a submit of ONE frame needs no scan over the frames (zg_k_scanf is not launched): its place and the totals, here
-      fo.out_base = fr.fixed_base ? fr.out_base_fixed : 0ull;
-      const uint64_t tot = fr.fixed_base ? 0ull : carry_size;
+      fo.out_base = fr.fixed_base ? fr.out_base_fixed : fr.dict_len;   // (a dictionary frame of a shared submit: its gap first, as zg_k_scanf lays it out)
+      const uint64_t tot = fr.fixed_base ? 0ull : fr.dict_len + carry_size;
       d.totals[0] = (uint32_t)tot; d.totals[1] = (uint32_t)(tot >> 32); d.totals[2] = (d.dst_cap_pre && tot > d.dst_cap_pre) ? 1u : 0u;
     }
     d.frame_out[f] = fo;
@@ -1307,7 +1307,11 @@ __global__ void __launch_bounds__(1024) zg_k_scanf(ZgBatchDev d) {
   uint64_t carry = 0;
   for (uint32_t c0 = 0; c0 < d.nframes; c0 += 1024) {
     uint32_t f = c0 + t;
-    s_v[t] = (f < d.nframes && !d.frames[f].fixed_base) ? d.frame_out[f].out_size : 0;
+    // (a dictionary frame of a shared submit, zg_frames.cpp, takes [gap of dict_len bytes][its plaintext]: zg_k_dictfill puts the dictionary's
+    //  content into the gap, so that a match that reaches in front of the frame finds it where a one-frame run finds it. out_base and out_size
+    //  describe the plaintext alone.)
+    const uint64_t gap = (f < d.nframes && !d.frames[f].fixed_base) ? d.frames[f].dict_len : 0;
+    s_v[t] = (f < d.nframes && !d.frames[f].fixed_base) ? gap + d.frame_out[f].out_size : 0;
     __syncthreads();
     for (uint32_t off = 1; off < 1024; off <<= 1) {
       uint64_t v = t >= off ? s_v[t - off] : 0;
@@ -1316,7 +1320,7 @@ __global__ void __launch_bounds__(1024) zg_k_scanf(ZgBatchDev d) {
       __syncthreads();
     }
     if (f < d.nframes) {
-      const uint64_t rel = carry + (t ? s_v[t - 1] : 0);
+      const uint64_t rel = carry + (t ? s_v[t - 1] : 0) + gap;
       d.frame_out[f].out_base = d.frames[f].fixed_base ? d.frames[f].out_base_fixed : rel;
       d.frame_out[f].og_base = d.frames[f].fixed_base ? 0 : rel;      // (a streaming run holds exactly one frame)
     }
@@ -1809,6 +1813,19 @@ __global__ void __launch_bounds__(256) zg_k_gather(const zgs::Seg* segs, const z
 }
 void zg_launch_gather(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s) {
   if (nchunks) hipLaunchKernelGGL(zg_k_gather, dim3(nchunks < zgs::kMaxGroups ? nchunks : zgs::kMaxGroups), dim3(zgs::kThreads), 0, s, segs, chunks, nchunks);
+}
+
+// A registered dictionary's content and tables replicated to every frame of a submit that names it (zgpu_set_frames_shared_dicts): the content
+// into the gap in front of the frame's plaintext, the tables into the frame's carry slots. zg_k_gather's body over a chunk table ordered by
+// source window (zg_dictfill.h has the plan and why). Sources lie in the context's device copy of the dictionary, destinations in the engine's
+// output and arenas; the host checked every segment against those buffers before the launch (Batch::dictfill_launch).
+__global__ void __launch_bounds__(256) zg_k_dictfill(const zgd::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks) {
+  const ZgGatherRead r{};
+  const ZgScatterWrite w{};
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) zgd::fill_chunk(r, w, segs, chunks[c], threadIdx.x, zgs::kThreads);
+}
+void zg_launch_dictfill(const zgd::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(zg_k_dictfill, dim3(nchunks < zgs::kMaxGroups ? nchunks : zgs::kMaxGroups), dim3(zgs::kThreads), 0, s, segs, chunks, nchunks);
 }
 
 // The header chain of entries that lie in device memory, one lane per entry (zg_walk.h has the routine, the record layout and the ISA notes).

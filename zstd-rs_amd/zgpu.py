@@ -162,6 +162,7 @@ EXPORTS = [
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
     "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats",
+    "zgpu_set_frames_shared_dicts", "zgpu_frames_shared_dicts", "zgpu_debug_frames_dict_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
     "zgpu_decode_all", "zgpu_batch_prepare", "zgpu_batch_run", "zgpu_batch_sync", "zgpu_batch_num_frames", "zgpu_batch_num_blocks",
@@ -233,6 +234,10 @@ def _declare(L):
     L.zgpu_frames_index_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC)]
     L.zgpu_frames_table_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC), P(C.c_uint64), P(FrameIndexC), sz, P(sz)]
     L.zgpu_debug_frames_index_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_set_frames_shared_dicts.argtypes = [vp, C.c_int]
+    L.zgpu_set_frames_shared_dicts.restype = None
+    L.zgpu_frames_shared_dicts.argtypes = [vp]
+    L.zgpu_debug_frames_dict_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_plaintext_bound.argtypes = [u8p, sz]
     L.zgpu_plaintext_bound.restype = C.c_uint64
     L.zgpu_debug_frames_submits.argtypes = [vp]
@@ -439,6 +444,21 @@ class Context:
     def frames_submits(self):
         """submits the last decode_frames / decode_frames_device call ran (zgpu_debug_frames_submits)"""
         return self.L.zgpu_debug_frames_submits(self.h)
+
+    def set_frames_shared_dicts(self, on):
+        """zgpu_set_frames_shared_dicts: True — dictionary frames whose id is registered (add_dict) join the shared submits of decode_frames,
+        decode_frames_device and decode_frames_device_src; False (the default) — their entries are decoded alone, as before."""
+        self.L.zgpu_set_frames_shared_dicts(self.h, 1 if on else 0)
+
+    def frames_shared_dicts(self):
+        return bool(self.L.zgpu_frames_shared_dicts(self.h))
+
+    def frames_dict_stats(self):
+        """the last decode_frames / decode_frames_device / decode_frames_device_src call (zgpu_debug_frames_dict_stats)"""
+        a = (C.c_uint64 * 5)()
+        k = self.L.zgpu_debug_frames_dict_stats(self.h, a, 5)
+        keys = ["frames_shared", "fill_launches", "bytes_replicated", "fill_us", "entries_alone"]
+        return dict(zip(keys[:k], [int(x) for x in a][:k]))
 
     @staticmethod
     def _entries(entries):
