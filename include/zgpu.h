@@ -63,6 +63,10 @@ enum zgpu_status {
   ZGPU_E_EXE_OFFSET_TOO_BIG = 52,     /* DecodeBufferError::OffsetTooBig */
   ZGPU_E_EXE_DICT_TOO_SMALL = 53,
   ZGPU_E_DICT_DECODE = 60,
+  /* No counterpart in the reference, which never enforces a Content_Checksum (libzstd does: its checksum_wrong). Only an entry of
+   * zgpu_decode_frames_device / zgpu_decode_frames_device_src called with ZGPU_DEVICE_VERIFY gets it: the entry decoded, and the XXH64 of a
+   * frame's plaintext differs from the checksum stored in the frame. */
+  ZGPU_E_CHECKSUM_MISMATCH = 70,
   /* Input the reference tolerates but this engine rejects. No conforming encoder produces any of it:
    *  - offsets >= 2^30 (offset codes 30, 31) while >= 1 GiB of the frame is held undrained (FrameDecoder::decode_blocks(All) on a
    *    frame beyond 1 GiB that nobody reads from): ZGPU_E_UNSUPPORTED. With less than 1 GiB held — always the case in decode_all
@@ -159,13 +163,32 @@ uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
  *    to their destinations.
  *  - Entries the one-submit path does not serve — dictionary frames while dictionaries are registered, Unsupported / Internal verdicts — are
  *    decoded again alone, as by zgpu_decode_frames, into a host buffer and then copied to the destination with one H2D (rare; correct first).
- *  - Checksums: the bytes never reach the host, so frames are hashed on the device only (zg_k_xxh64, one lane per frame, ~226 MB/s per lane).
+ *  - Checksums: the bytes never reach the host, so frames are hashed on the device only (zg_k_xxh64, one lane per frame, ~226 MB/s per lane;
+ *    zg_k_xxh64q, four lanes per frame, is built and tested but not yet the library's choice for any launch: LABNOTES.md "xxh64q").
  *    r.checksums counts the frames that carry a Content_Checksum, r.checksum_mismatches only those among the HASHED frames; the rest are
- *    counted in checksums_unverified. Nothing fails on a mismatch. (Entries decoded alone are hashed on the host, whatever their length.) */
+ *    counted in checksums_unverified. By default nothing fails on a mismatch, as in the reference, and the scatter runs beside the hash: a
+ *    corrupted frame's bytes are in the destination when the caller reads the counter. (Entries decoded alone are hashed on the host,
+ *    whatever their length.)
+ *  - ZGPU_DEVICE_VERIFY (flags bit 1) makes a mismatch the entry's verdict, as libzstd does. Every frame that carries a Content_Checksum is
+ *    then hashed, whatever its length (hash_max_bytes == 0 means NO limit under this flag; a nonzero value still bounds what is hashed, and
+ *    longer frames pass, counted in checksums_unverified; frames without a checksum are hashed as without the flag). An entry that would have
+ *    had status 0 and holds a hashed frame whose low 32 digest bits differ from its stored checksum gets ZGPU_E_CHECKSUM_MISMATCH instead:
+ *    written = nframes = 0 like any failed entry, and NO byte of its destination is written — a submit's digests are waited for before its
+ *    scatter list is built. r.checksums and r.checksum_mismatches of such an entry are still filled (all its frames that carry a checksum /
+ *    those that failed), so the caller sees which count failed; every other field is 0. The verdict ranks behind all others: a decode
+ *    error, a walk error, TARGET_TOO_SMALL and BAD_ARG are reported exactly as without the flag. Other entries are unaffected, in any order.
+ *    Entries decoded alone are hashed on the host and compared before their one H2D, with the same verdict. What it costs: the scatter no
+ *    longer overlaps the hash, and a frame is hashed at a lane group's rate — one lane's today: a 64 MiB frame takes ~0.3 s, tens of
+ *    milliseconds even with four lanes —, hidden only when many frames are hashed side by side (LABNOTES.md "xxh64q"); a nonzero
+ *    hash_max_bytes bounds it.
+ *    Bit 1 together with bit 0 is a contradiction: the call returns ZGPU_E_BAD_ARG and launches nothing. */
+#define ZGPU_DEVICE_NO_HASH 1u
+#define ZGPU_DEVICE_VERIFY 2u
 typedef struct {
-  uint64_t hash_max_bytes;   /* frames whose plaintext is at most this long are hashed on the device (one lane per frame: a 4 MiB frame costs
-                                ~18 ms); longer ones are not hashed. 0: default 4 MiB */
-  uint32_t flags;            /* bit 0: hash no frame at all */
+  uint64_t hash_max_bytes;   /* frames whose plaintext is at most this long are hashed on the device; longer ones are not hashed.
+                                0: default 4 MiB — except under ZGPU_DEVICE_VERIFY, where 0 means no limit for frames that carry a checksum */
+  uint32_t flags;            /* bit 0 (ZGPU_DEVICE_NO_HASH): hash no frame at all; bit 1 (ZGPU_DEVICE_VERIFY): a checksum mismatch fails the
+                                entry with ZGPU_E_CHECKSUM_MISMATCH and nothing of it is written */
   uint32_t pad;
 } zgpu_device_opts;
 typedef struct {
@@ -176,8 +199,17 @@ typedef struct {
 int zgpu_decode_frames_device(zgpu_ctx*, const uint8_t* const* srcs, const size_t* lens, uint32_t n, void* const* device_dsts, const size_t* caps,
                               const zgpu_device_opts* opts_or_null, zgpu_device_entry_result* results);
 /* diagnostics: the context's last zgpu_decode_frames_device call — out[0] submits, [1] scatter launches, [2] bytes scattered, [3] scatter kernel
- * microseconds (HIP events), [4] frames hashed, [5] frames not hashed, [6] entries that were decoded alone. Returns how many were written. */
+ * microseconds (HIP events), [4] frames hashed, [5] frames not hashed, [6] entries that were decoded alone, [7] entries failed by
+ * ZGPU_DEVICE_VERIFY, [8] hash kernel microseconds (HIP events, summed over the submits). Returns how many were written. */
 int zgpu_debug_frames_device_stats(const zgpu_ctx*, uint64_t* out, int n);
+/* measurement and tests: XXH64 (seed 0) of n ranges [device_base + offs[i], + lens[i]) of the caller's device memory by the hash kernels of
+ * the calls above. kernel 0: the library's choice for n ranges, 1: zg_k_xxh64 (one lane per range), 4: zg_k_xxh64q (four lanes per range).
+ * [device_base, device_base + max(offs[i] + lens[i])) passes the pointer check that device sources pass, before anything is launched: else
+ * ZGPU_E_BAD_ARG. No lane reads a byte outside its range. The ranges are sorted longest first internally, as the engine sorts a submit's
+ * frames; digests[i] belongs to range i in the caller's order. zgpu_debug_hash_ranges_us: the kernel's time in the last call (HIP events). */
+int zgpu_debug_hash_ranges(zgpu_ctx*, const void* device_base, const uint64_t* offs, const uint64_t* lens, uint32_t n, int kernel,
+                           uint64_t* digests);
+uint64_t zgpu_debug_hash_ranges_us(const zgpu_ctx*);
 
 /* ---- the same, with the compressed input in device memory too ------------------------------------------------------------------
  * For callers whose compressed bytes are in HBM already (a GPUDirect / RDMA read, a torch tensor loaded from a sharded checkpoint, the output of

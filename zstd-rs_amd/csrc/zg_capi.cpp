@@ -79,6 +79,7 @@ const char* zgpu_status_name(int s) {
     case ZGPU_E_EXE_OFFSET_TOO_BIG: return "OffsetTooBig";
     case ZGPU_E_EXE_DICT_TOO_SMALL: return "NotEnoughBytesInDictionary";
     case ZGPU_E_DICT_DECODE: return "DictionaryDecodeError";
+    case ZGPU_E_CHECKSUM_MISMATCH: return "ChecksumMismatch";
     case ZGPU_E_UNSUPPORTED: return "Unsupported";
     case ZGPU_E_INTERNAL: return "Internal";
     case ZGPU_E_NOMEM: return "OutOfMemory";

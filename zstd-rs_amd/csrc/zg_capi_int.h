@@ -29,9 +29,10 @@ struct zgpu_ctx {
   bool frames_shared_dicts = false;               // zgpu_set_frames_shared_dicts
   uint64_t frames_dict_stats[5] = {0, 0, 0, 0, 0};   // of the last zgpu_decode_frames* call (zgpu_debug_frames_dict_stats)
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
-  uint64_t frames_device_stats[7] = {0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
+  uint64_t frames_device_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
   uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)
   uint64_t frames_index_stats[4] = {0, 0, 0, 0};              // of the last zgpu_frames_index_device / zgpu_frames_table_device call (zgpu_debug_frames_index_stats)
+  uint64_t hash_ranges_us = 0;                                // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
 

@@ -174,6 +174,7 @@ Batch::~Batch() {
   if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
   if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
   for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ev_hash_) if (e) (void)hipEventDestroy(e);
   for (DevBuf& x : d_fill_) if (x.p && eng) { (void)hipSetDevice(eng->device_); x.release(); }
   for (hipEvent_t e : ev_fill_) if (e) (void)hipEventDestroy(e);
   if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
@@ -1140,15 +1141,24 @@ int Batch::hash_launch(const uint32_t* frames, uint32_t n) {
   hipStream_t s = eng->stream_;
   ZG_HIP(hipMemcpyAsync(d_hash_.p, r.data(), rb, hipMemcpyHostToDevice, s));
   ZG_HIP(hipStreamSynchronize(s));   // (r is pageable and goes out of scope)
+  for (hipEvent_t& e : ev_hash_) if (!e) ZG_HIP(hipEventCreate(&e));
+  ZG_HIP(hipEventRecord(ev_hash_[0], s));
   zg_launch_xxh64(dev.dst, d_hash_.as<ZgHashRange>(), (uint64_t*)((uint8_t*)d_hash_.p + rb), n, s);
   ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev_hash_[1], s));
   hash_n_ = n;
   return ZG_OK;
 }
-int Batch::hash_wait(uint64_t* out) {
+int Batch::hash_wait(uint64_t* out, uint64_t* kernel_us) {
+  if (kernel_us) *kernel_us = 0;
   if (!hash_n_) return ZG_OK;
   ZG_HIP(hipSetDevice(eng->device_));
   ZG_HIP(hipStreamSynchronize(eng->stream_));
+  if (kernel_us) {
+    float ms = 0;
+    ZG_HIP(hipEventElapsedTime(&ms, ev_hash_[0], ev_hash_[1]));
+    *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  }
   ZG_HIP(hipMemcpy(out, (uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange), (size_t)hash_n_ * 8, hipMemcpyDeviceToHost));
   hash_n_ = 0;
   return ZG_OK;

@@ -168,9 +168,10 @@ class Batch {
   int read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s);
   const uint8_t* device_output() const { return dev.dst; }
   // after sync(): XXH64 (seed 0) of the output bytes of frames[0 .. n) as sync() left them ([out_base, out_base + out_size): a failed frame's
-  // good blocks), one lane per frame (zg_k_xxh64), enqueued on the engine's first stream; hash_wait() waits and writes digest i of frames[i]
+  // good blocks), one lane or one quad of lanes per frame (zg_k_xxh64 / zg_k_xxh64q: zg_launch_xxh64 chooses), enqueued on the engine's first
+  // stream; hash_wait() waits and writes digest i of frames[i]; *kernel_us, if asked for: the kernel's time between two HIP events
   int hash_launch(const uint32_t* frames, uint32_t n);
-  int hash_wait(uint64_t* out);
+  int hash_wait(uint64_t* out, uint64_t* kernel_us = nullptr);
   // after sync(): zg_k_scatter (zg_scatter.h) copies segs[0 .. n) of the output to their destinations — device memory of the CALLER, which it
   // has checked (zgpu_decode_frames_device) — in one launch on the engine's second stream, beside hash_launch's kernel on the first. Segments
   // that leave the output are refused (ZGPU_E_INTERNAL) before anything is launched. chunk: bytes per chunk of the plan (0: zgs::kChunkDefault).
@@ -201,6 +202,7 @@ class Batch {
   FrameState* fs = nullptr;              // streaming submit: the frame state this run reads from / writes into
   DevBuf d_hash_;                        // hash_launch: the ranges, then the digests
   uint32_t hash_n_ = 0;
+  hipEvent_t ev_hash_[2] = {nullptr, nullptr};
   DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
   hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
   bool scatter_on_ = false;

@@ -110,6 +110,8 @@ struct Call {
   std::vector<std::pair<uint32_t, bool>> again;   // entries decoded again on their own after the submits (true: the walk met a dictionary frame)
   zgpu_device_entry_result* dres = nullptr;        // device sink (zgpu_decode_frames_device): its results; hash_max is the caller's, no estimate
   bool no_hash = false;                            //   flags bit 0: hash no frame
+  bool verify = false;                             //   flags bit 1 (ZGPU_DEVICE_VERIFY): a mismatch fails the entry, with nothing of it written
+  bool hash_all = false;                           //   verify with hash_max_bytes == 0: every frame that carries a Content_Checksum is hashed
   uint64_t* stats = nullptr;                       //   zgpu_ctx::frames_device_stats
   // device sources (zgpu_decode_frames_device_src): srcs[i] is device memory; what was found out about every entry before the first submit
   const Engine::Skeleton* sk = nullptr;            //   the records zg_k_walk brought back
@@ -228,7 +230,7 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     r.written = bytes;
     r.nframes = ff[j + 1] - ff[j];
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (fo[f].out_size <= k.hash_max) u.cand.push_back(f);   // (candidates)
+      if (fo[f].out_size <= k.hash_max || (k.hash_all && b->info[f].has_checksum)) u.cand.push_back(f);   // (candidates)
       const uint64_t e = fo[f].out_base + fo[f].out_size;
       if (e > u.down) u.down = e;
     }
@@ -285,7 +287,9 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
 }
 
 // the device sink: the plaintext stays on the device; one zg_k_scatter launch copies the frames of every successful entry to its destination
-// (an entry's frames back to back) while zg_k_xxh64 hashes the candidates beside it; frames that are not hashed are counted, not verified
+// (an entry's frames back to back) while the hash kernel (zg_launch_xxh64) hashes the candidates beside it; frames that are not hashed are
+// counted, not verified. With ZGPU_DEVICE_VERIFY the order is hash launch, hash wait, verdicts, and only then the scatter of the entries that
+// passed: an entry with a hashed frame whose digest differs from its Content_Checksum fails, and nothing of it is ever in the scatter list.
 int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   Batch* b = u.b;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
@@ -296,26 +300,52 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   for (uint32_t f : dev_hash) on_dev[f] = 1;
   int st;
   if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) return st;
-  std::vector<zgs::Seg> segs;
   uint64_t bytes = 0;
-  for (uint32_t j = 0; j < n; j++) {
-    const zgpu_entry_result& r = k.dres[idx[j]].r;
-    if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
-    uint64_t at = 0;
-    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (fo[f].out_size) segs.push_back(zgs::Seg{fo[f].out_base, (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, fo[f].out_size});
-      at += fo[f].out_size;
+  auto scatter = [&]() -> int {   // the frames of every entry that stands at status 0, in one launch
+    std::vector<zgs::Seg> segs;
+    for (uint32_t j = 0; j < n; j++) {
+      const zgpu_entry_result& r = k.dres[idx[j]].r;
+      if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
+      uint64_t at = 0;
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+        if (fo[f].out_size) segs.push_back(zgs::Seg{fo[f].out_base, (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, fo[f].out_size});
+        at += fo[f].out_size;
+      }
+      if (at != r.written || at > k.caps[idx[j]]) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
+      bytes += at;
     }
-    if (at != r.written || at > k.caps[idx[j]]) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
-    bytes += at;
-  }
-  if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
-  if ((st = b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk))) return st;
+    if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
+    return b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk);
+  };
+  if (!k.verify && (st = scatter())) return st;
   std::vector<uint64_t> digest(fo.size(), 0);
   {
     std::vector<uint64_t> dh(dev_hash.size());
-    if ((st = b->hash_wait(dh.data()))) return st;
+    uint64_t hash_us = 0;
+    if ((st = b->hash_wait(dh.data(), &hash_us))) return st;
+    k.stats[8] += hash_us;
     for (size_t q = 0; q < dev_hash.size(); q++) digest[dev_hash[q]] = dh[q];
+  }
+  if (k.verify) {
+    // the verdict of verification ranks behind every other one: only entries that stand at status 0 are looked at
+    for (uint32_t j = 0; j < n; j++) {
+      zgpu_entry_result& r = k.dres[idx[j]].r;
+      if (r.status || r.nframes == 0) continue;
+      uint32_t sums = 0, bad = 0;
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+        const FrameInfo& fi = b->info[f];
+        if (!fi.has_checksum) continue;
+        sums++;
+        if (on_dev[f] && fi.checksum != (uint32_t)digest[f]) bad++;
+      }
+      if (!bad) continue;
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) k.stats[on_dev[f] ? 4 : 5]++;
+      memset(&k.dres[idx[j]], 0, sizeof k.dres[idx[j]]);   // written = nframes = 0, like any failed entry; the two counts say why
+      r.status = ZGPU_E_CHECKSUM_MISMATCH;
+      r.checksums = sums; r.checksum_mismatches = bad;
+      k.stats[7]++;
+    }
+    if ((st = scatter())) return st;
   }
   uint64_t us = 0;
   bool launched = false;
@@ -410,6 +440,15 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   zgpu_device_entry_result& d = k.dres[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
+  // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its one H2D
+  if (!st && !d.r.status && k.verify && summed && !k.no_hash && d.r.checksum_mismatches) {
+    const uint32_t sums = d.r.checksums, bad = d.r.checksum_mismatches;
+    k.stats[4] += d.r.nframes;
+    memset(&d, 0, sizeof d);
+    d.r.status = ZGPU_E_CHECKSUM_MISMATCH;
+    d.r.checksums = sums; d.r.checksum_mismatches = bad;
+    k.stats[7]++;
+  }
   if (!st && !d.r.status) {
     if (d.r.written && hipMemcpy(k.dsts[i], tmp, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
     const bool hashed = summed && !k.no_hash && d.r.nframes;
@@ -498,11 +537,14 @@ extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const
 extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
                                          const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
   if (!c || (n && (!srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
   for (uint64_t& x : c->frames_device_stats) x = 0;
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   Call k{c, srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
   k.dres = results;
   k.no_hash = opts && (opts->flags & 1u);
+  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
+  k.hash_all = k.verify && !opts->hash_max_bytes;
   k.stats = c->frames_device_stats;
   const DictLookup lookup{shared_find, c};
   if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
@@ -518,12 +560,15 @@ extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs
 extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
                                              const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
   if (!c || (n && (!device_srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
   for (uint64_t& x : c->frames_device_stats) x = 0;
   for (uint64_t& x : c->frames_device_src_stats) x = 0;
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   Call k{c, (const uint8_t* const*)device_srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
   k.dres = results;
   k.no_hash = opts && (opts->flags & 1u);
+  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
+  k.hash_all = k.verify && !opts->hash_max_bytes;
   k.stats = c->frames_device_stats;
   k.sstats = c->frames_device_src_stats;
   const DictLookup lookup{shared_find, c};
@@ -560,6 +605,48 @@ extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* dev
   k.stats[0] = c->frames_submits;
   return st;
 }
+// ---- the hash kernels on ranges of the caller's choice (measurement and tests) ---------------------------------------------------------------
+// [base, base + max(off + len)) passes the check the device sources pass before anything is launched; the ranges are sorted longest first as
+// Batch::hash_launch sorts a submit's frames, and digests[i] is range i's in the caller's order (the slot travels with the range).
+extern "C" int zgpu_debug_hash_ranges(zgpu_ctx* c, const void* device_base, const uint64_t* offs, const uint64_t* lens, uint32_t n, int kernel,
+                                      uint64_t* digests) {
+  if (!c || (n && (!offs || !lens || !digests)) || (kernel != 0 && kernel != 1 && kernel != 4)) return ZGPU_E_BAD_ARG;
+  c->hash_ranges_us = 0;
+  if (!n) return ZGPU_OK;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  uint64_t end = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (lens[i] > UINT64_MAX - offs[i]) return ZGPU_E_BAD_ARG;
+    if (offs[i] + lens[i] > end) end = offs[i] + lens[i];
+  }
+  std::vector<DevRange> known;
+  if (end > SIZE_MAX || !check_device_range(c->eng->device(), device_base, (size_t)end, known)) return ZGPU_E_BAD_ARG;
+  std::vector<ZgHashRange> r(n);
+  for (uint32_t i = 0; i < n; i++) r[i] = ZgHashRange{offs[i], lens[i], i, 0};
+  std::stable_sort(r.begin(), r.end(), [](const ZgHashRange& a, const ZgHashRange& b) { return a.len > b.len; });
+  const size_t rb = (size_t)n * sizeof(ZgHashRange);
+  DevBuf buf;
+  int st = buf.reserve(rb + (size_t)n * 8);
+  if (st) return st;
+  hipStream_t s = c->eng->stream();
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  float ms = 0;
+  const bool ok = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess &&
+                  hipMemcpyAsync(buf.p, r.data(), rb, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
+                  hipEventRecord(ev[0], s) == hipSuccess &&
+                  (zg_launch_xxh64_with((const uint8_t*)device_base, buf.as<ZgHashRange>(), (uint64_t*)((uint8_t*)buf.p + rb), n, s, kernel), hipGetLastError() == hipSuccess) &&
+                  hipEventRecord(ev[1], s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
+                  hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess &&
+                  hipMemcpy(digests, (uint8_t*)buf.p + rb, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess;
+  if (!ok) (void)hipGetLastError();
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  buf.release();
+  if (!ok) return ZGPU_E_HIP;
+  c->hash_ranges_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  return ZGPU_OK;
+}
+extern "C" uint64_t zgpu_debug_hash_ranges_us(const zgpu_ctx* c) { return c ? c->hash_ranges_us : 0; }
+
 // ---- what device-resident entries hold, from their headers alone (zg_index.h) --------------------------------------------------------------
 // The stop reasons of the chain are public under the values the lanes use.
 static_assert(ZGPU_CHAIN_END == zgw::kEnd && ZGPU_CHAIN_SHORT_HEADER == zgw::kShortHeader && ZGPU_CHAIN_BAD_MAGIC == zgw::kBadMagic &&
@@ -671,7 +758,7 @@ extern "C" int zgpu_debug_frames_dict_stats(const zgpu_ctx* c, uint64_t* out, in
 extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) {
   if (!c || !out) return 0;
   int k = 0;
-  for (; k < n && k < 7; k++) out[k] = c->frames_device_stats[k];
+  for (; k < n && k < 9; k++) out[k] = c->frames_device_stats[k];
   return k;
 }
 

@@ -44,6 +44,15 @@ void zg_launch_calib(const void* src, void* dst, uint64_t bytes, hipStream_t s);
 // zg_k_xxh64: XXH64 (seed 0) of byte ranges of a batch's output, one lane per range; out[slot] = digest. ranges are sorted by length, longest first
 struct ZgHashRange { uint64_t off, len; uint32_t slot, pad; };
 void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s);
+// zg_k_xxh64q: the same digests, four lanes per range (lane l owns accumulator l), 16 ranges per wave, one wave per workgroup. A range costs more
+// wave-instructions this way (~17/16 of a lane's share per stripe against 54/64), so it is the kernel for launches whose ranges are too few to
+// fill the chip, where the rate PER RANGE decides: zg_launch_xxh64 takes it for up to ZG_XXH64Q_MAX_RANGES ranges. That threshold comes from
+// tools/dev/hash_ranges.py on an MI355X; the measurement has not been taken yet (LABNOTES.md "xxh64q"), so it is 0 and every launch of the
+// library is still zg_k_xxh64 — the quad kernel runs only where it is asked for by name.
+// zg_launch_xxh64_with: kernel 0 the rule above, 1 zg_k_xxh64, 4 zg_k_xxh64q (zgpu_debug_hash_ranges).
+#define ZG_XXH64Q_RANGES 16u
+#define ZG_XXH64Q_MAX_RANGES 0u
+void zg_launch_xxh64_with(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s, int kernel);
 // zg_k_scatter (zg_scatter.h): the chunks of the segments of a batch's output (base) to the segments' destinations, one workgroup per chunk
 void zg_launch_scatter(const uint8_t* base, const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, hipStream_t s);
 // zg_k_gather (zg_walk.h): the same chunks the other way round — segments whose src_off is an ADDRESS in device memory of the caller (the entries

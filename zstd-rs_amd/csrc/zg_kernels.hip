@@ -1764,8 +1764,30 @@ __global__ void __launch_bounds__(256) zg_k_xxh64(const uint8_t* base, const ZgH
   const ZgHashRange x = r[i];
   out[x.slot] = zgx::xxh64(base + x.off, x.len, 0);
 }
+// The same digests with a QUAD of lanes per range (zg_xxh64_dev.h: lane l owns accumulator v_l and reads word l of every stripe, a round of
+// stripes in flight while the last one is mixed). A wave carries 16 ranges and is a workgroup of its own, so that few long ranges land on
+// different CUs instead of streaming through one CU's cache. The four lanes of a quad take the same branches (they share the range's length),
+// so a quad is whole wherever it is; every lane reaches the shuffles — a range shorter than 32 bytes, or a quad behind the last range, brings
+// its seed values and reads nothing — and lane 0 alone merges, reads the tail and writes the digest.
+__global__ void __launch_bounds__(64) zg_k_xxh64q(const uint8_t* base, const ZgHashRange* r, uint64_t* out, uint32_t n) {
+  const uint32_t t = threadIdx.x, l = t & 3u, i = blockIdx.x * ZG_XXH64Q_RANGES + (t >> 2);
+  const bool live = i < n;
+  ZgHashRange x{0, 0, 0, 0};
+  if (live) x = r[i];
+  const uint8_t* p = base + x.off;
+  const uint64_t v = zgx::xxh64q_acc(p, x.len, 0, l);
+  const int q0 = (int)(t & ~3u);
+  const uint64_t v0 = __shfl(v, q0, 64), v1 = __shfl(v, q0 + 1, 64), v2 = __shfl(v, q0 + 2, 64), v3 = __shfl(v, q0 + 3, 64);
+  if (live && l == 0) out[x.slot] = zgx::xxh64q_finish(p, x.len, 0, v0, v1, v2, v3);
+}
+void zg_launch_xxh64_with(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s, int kernel) {
+  if (!n) return;
+  if (kernel == 0) kernel = n <= ZG_XXH64Q_MAX_RANGES ? 4 : 1;
+  if (kernel == 4) hipLaunchKernelGGL(zg_k_xxh64q, dim3((n + ZG_XXH64Q_RANGES - 1) / ZG_XXH64Q_RANGES), dim3(64), 0, s, base, ranges, out, n);
+  else hipLaunchKernelGGL(zg_k_xxh64, dim3((n + 255) / 256), dim3(256), 0, s, base, ranges, out, n);
+}
 void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* out, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(zg_k_xxh64, dim3((n + 255) / 256), dim3(256), 0, s, base, ranges, out, n);
+  zg_launch_xxh64_with(base, ranges, out, n, s, 0);
 }
 
 // A submit's plaintext to the caller's device memory (zgpu_decode_frames_device): one workgroup per chunk of the host's plan, grid-stride

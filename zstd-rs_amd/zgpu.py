@@ -22,6 +22,7 @@ E_FAILED_READ_BLOCK_HEADER, E_FAILED_READ_BLOCK_BODY, E_FAILED_READ_CHECKSUM = 9
 E_TARGET_TOO_SMALL = 12
 E_FAILED_SKIP_FRAME = 13
 E_RESERVED_BLOCK, E_BLOCK_SIZE_TOO_LARGE = 20, 21
+E_CHECKSUM_MISMATCH = 70    # decode_frames_device / decode_frames_device_src with verify=True only (no counterpart in the reference)
 E_UNSUPPORTED = 80
 E_HIP = 92
 
@@ -161,7 +162,7 @@ NO_READ_AHEAD = 1
 EXPORTS = [
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
-    "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats",
+    "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats", "zgpu_debug_hash_ranges", "zgpu_debug_hash_ranges_us",
     "zgpu_set_frames_shared_dicts", "zgpu_frames_shared_dicts", "zgpu_debug_frames_dict_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
@@ -229,6 +230,9 @@ def _declare(L):
     L.zgpu_decode_frames.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(EntryResultC)]
     L.zgpu_decode_frames_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
     L.zgpu_debug_frames_device_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_debug_hash_ranges.argtypes = [vp, vp, P(C.c_uint64), P(C.c_uint64), C.c_uint32, C.c_int, P(C.c_uint64)]
+    L.zgpu_debug_hash_ranges_us.argtypes = [vp]
+    L.zgpu_debug_hash_ranges_us.restype = C.c_uint64
     L.zgpu_decode_frames_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
     L.zgpu_debug_frames_device_src_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_frames_index_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC)]
@@ -477,12 +481,15 @@ class Context:
     def _bounds(self, srcs, lens, n):
         return [self.L.zgpu_plaintext_bound(C.cast(C.c_void_p(srcs[i]), C.c_char_p), lens[i]) for i in range(n)]
 
-    def decode_frames_device(self, entries, ptrs, caps, hash_max=0, no_hash=False):
+    def decode_frames_device(self, entries, ptrs, caps, hash_max=0, no_hash=False, verify=False):
         """zgpu_decode_frames_device: decode_frames with the plaintext left in DEVICE memory the caller owns. ptrs[i] is the address of caps[i]
         bytes on this context's device (any alignment; a torch tensor's data_ptr()); the library checks every one with the HIP runtime before it
         launches anything, and a pointer that is not such memory gives that entry E_BAD_ARG. Nothing in flight may touch the destinations during
         the call; when it returns, the bytes are there for every stream. hash_max: frames up to this many bytes are hashed on the device
-        (0: 4 MiB), longer ones are counted in checksums_unverified; no_hash: hash nothing. Returns one DeviceEntryResult per entry."""
+        (0: 4 MiB), longer ones are counted in checksums_unverified; no_hash: hash nothing. verify (ZGPU_DEVICE_VERIFY): an entry that decodes
+        but holds a hashed frame whose XXH64 differs from its Content_Checksum gets E_CHECKSUM_MISMATCH, written = nframes = 0, and no byte of
+        its destination is written (checksums / checksum_mismatches still say which count failed); hash_max=0 then means no limit for frames
+        that carry a checksum. verify with no_hash raises E_BAD_ARG. Returns one DeviceEntryResult per entry."""
         n = len(entries)
         if len(ptrs) != n or len(caps) != n:
             raise ValueError("decode_frames_device: one pointer and one capacity per entry")
@@ -490,7 +497,7 @@ class Context:
         dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
         for i in range(n):
             dsts[i], capa[i] = int(ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), 1 if no_hash else 0, 0)
+        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
         res = (DeviceEntryResultC * max(n, 1))()
         st = self.L.zgpu_decode_frames_device(self.h, srcs, lens, n, dsts, capa, C.byref(opts), res)
         del keep
@@ -511,19 +518,39 @@ class Context:
             outl.append(e)
         return outl
 
-    def frames_device_stats(self):
-        """the last decode_frames_device call (zgpu_debug_frames_device_stats)"""
-        a = (C.c_uint64 * 7)()
-        k = self.L.zgpu_debug_frames_device_stats(self.h, a, 7)
-        keys = ["submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed", "entries_alone"]
+    def frames_device_stats(self, verify=False):
+        """the last decode_frames_device call (zgpu_debug_frames_device_stats). verify=True: with the two fields of verification as well —
+        entries_failed_verify (out[7]) and hash_us (out[8], the hash kernel's time, HIP events)."""
+        m = 9 if verify else 7
+        a = (C.c_uint64 * 9)()
+        k = self.L.zgpu_debug_frames_device_stats(self.h, a, m)
+        keys = ["submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed", "entries_alone",
+                "entries_failed_verify", "hash_us"]
         return dict(zip(keys[:k], [int(x) for x in a][:k]))
 
-    def decode_frames_device_src(self, src_ptrs, lens, dst_ptrs, caps, hash_max=0, no_hash=False):
+    def hash_ranges(self, ptr, offs, lens, kernel=0):
+        """zgpu_debug_hash_ranges: XXH64 (seed 0) of the ranges [ptr + offs[i], + lens[i]) of device memory by the hash kernels of the device
+        calls. kernel 0: the library's choice, 1: zg_k_xxh64 (one lane per range), 4: zg_k_xxh64q (four lanes per range). ptr must be device
+        memory of this context's device that holds every range (else E_BAD_ARG, nothing launched). Returns the digests in the caller's order;
+        hash_ranges_us() is the kernel's time in that call."""
+        n = len(offs)
+        if len(lens) != n:
+            raise ValueError("hash_ranges: one length per offset")
+        o, ln, out = (C.c_uint64 * max(n, 1))(*offs), (C.c_uint64 * max(n, 1))(*lens), (C.c_uint64 * max(n, 1))()
+        st = self.L.zgpu_debug_hash_ranges(self.h, int(ptr) or None, o, ln, n, int(kernel), out)
+        if st:
+            raise ZgpuError(st, "zgpu_debug_hash_ranges")
+        return [int(out[i]) for i in range(n)]
+
+    def hash_ranges_us(self):
+        return int(self.L.zgpu_debug_hash_ranges_us(self.h))
+
+    def decode_frames_device_src(self, src_ptrs, lens, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False):
         """zgpu_decode_frames_device_src: decode_frames_device with the compressed input in DEVICE memory too. src_ptrs[i] is the address of
         lens[i] bytes on this context's device (any alignment), dst_ptrs[i] of caps[i] bytes; sources pass the same check as destinations
         (a pointer that is not such memory gives that entry E_BAD_ARG), are never written, and no byte outside [src, src + len) is read.
         Nothing in flight may write the sources or touch the destinations during the call. Results are those of decode_frames_device on a
-        host copy of the same bytes. Returns one DeviceEntryResult per entry."""
+        host copy of the same bytes, verify included. Returns one DeviceEntryResult per entry."""
         n = len(src_ptrs)
         if len(lens) != n or len(dst_ptrs) != n or len(caps) != n:
             raise ValueError("decode_frames_device_src: one length, one destination and one capacity per source")
@@ -532,7 +559,7 @@ class Context:
         for i in range(n):
             srcs[i], lena[i] = int(src_ptrs[i]) or None, int(lens[i])
             dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), 1 if no_hash else 0, 0)
+        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
         res = (DeviceEntryResultC * max(n, 1))()
         st = self.L.zgpu_decode_frames_device_src(self.h, srcs, lena, n, dsts, capa, C.byref(opts), res)
         if st:
@@ -620,12 +647,13 @@ class Context:
         if len(hip) > 1:
             raise RuntimeError("two HIP runtimes are loaded (%s): import torch before creating the first zgpu.Context" % ", ".join(sorted(hip)))
 
-    def decode_tensors(self, tensors, caps=None, hash_max=0, no_hash=False):
+    def decode_tensors(self, tensors, caps=None, hash_max=0, no_hash=False, verify=False):
         """decode_frames_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
         compressed bytes. The plaintext goes to ONE new torch.uint8 tensor, every entry's slot 256-byte aligned with caps[i] bytes of room.
         caps=None sizes the slots with frames_index_device — zgpu_plaintext_bound of every entry, taken on the device from its headers: no
         byte of the input crosses to the host. Returns (tensors, results) like decode_frames_to_tensors, under the same single-runtime rule
-        (import torch before creating the first Context). torch is imported here, not by `import zgpu`."""
+        (import torch before creating the first Context). verify: as decode_frames_device — an entry that fails its checksum comes back as an
+        empty view with E_CHECKSUM_MISMATCH. torch is imported here, not by `import zgpu`."""
         import torch
         self._tensor_check(tensors, "decode_tensors")
         dev = torch.device("cuda", self.device)
@@ -641,10 +669,10 @@ class Context:
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
         base = buf.data_ptr()
-        res = self.decode_frames_device_src(ptrs, lens, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
+        res = self.decode_frames_device_src(ptrs, lens, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
         return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
 
-    def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False):
+    def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False, verify=False):
         """decode_frames_device into ONE torch.uint8 tensor on this context's device, every entry's slot 256-byte aligned (caps: bytes of room per
         entry, default plaintext_bound of the entry). Returns (tensors, results): tensors[i] is a view of entry i's slot cut to `written` bytes
         (empty unless status == 0), results[i] its DeviceEntryResult. torch is imported here, not by `import zgpu`.
@@ -668,7 +696,7 @@ class Context:
             torch.cuda.current_stream().synchronize()
         base = buf.data_ptr()
         ents = [(srcs[i] or 0, lens[i]) for i in range(n)]
-        res = self.decode_frames_device(ents, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash)
+        res = self.decode_frames_device(ents, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
         del keep
         return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
 
