@@ -67,6 +67,10 @@ enum zgpu_status {
    * zgpu_decode_frames_device / zgpu_decode_frames_device_src called with ZGPU_DEVICE_VERIFY gets it: the entry decoded, and the XXH64 of a
    * frame's plaintext differs from the checksum stored in the frame. */
   ZGPU_E_CHECKSUM_MISMATCH = 70,
+  /* No counterpart in the reference, which never compares a frame's length with its Frame_Content_Size (libzstd does: its corruption_detected /
+   * srcSize_wrong). Only an entry of zgpu_decode_ranges_device_src gets it: a frame of the selection declares a size and decoded to another
+   * length, so the plaintext coordinates the range was asked in do not hold. */
+  ZGPU_E_CONTENT_SIZE_MISMATCH = 71,
   /* Input the reference tolerates but this engine rejects. No conforming encoder produces any of it:
    *  - offsets >= 2^30 (offset codes 30, 31) while >= 1 GiB of the frame is held undrained (FrameDecoder::decode_blocks(All) on a
    *    frame beyond 1 GiB that nobody reads from): ZGPU_E_UNSUPPORTED. With less than 1 GiB held — always the case in decode_all
@@ -323,6 +327,70 @@ int zgpu_frames_table_device(zgpu_ctx*, const void* const* device_srcs, const si
 /* diagnostics of the context's last index / table call: out[0] launches, [1] kernel microseconds (HIP events), [2] bytes downloaded,
  * [3] input bytes that crossed to the host (always 0). Returns how many were written. */
 int zgpu_debug_frames_index_stats(const zgpu_ctx*, uint64_t* out, int n);
+
+/* ---- byte ranges of device-resident multi-frame entries ------------------------------------------------------------------------------------
+ * Shards and columnar pages are cut into many independent frames so that a part of one can be read. zgpu_decode_ranges_device_src writes
+ * plaintext bytes [begin, begin + len) of entry i to device_dsts[i] and decodes only the frames that hold them: one lane per entry follows the
+ * header chain on the device (zg_k_seek: three bytes per block, never a block body, ONE launch for the whole call, 64 bytes per entry come back
+ * and no byte of the input), and the whole frames it selects, (src + src_lo, src_hi - src_lo), go through the machinery of
+ * zgpu_decode_frames_device_src — walk, submits cut by the selection's bound, gather, decode, hash, one scatter launch per submit whose segments
+ * are clipped to the range. zgpu_frames_seek_device is the selection alone.
+ *  - Plaintext coordinates are DECLARED coordinates: the offset of a frame is the sum of the Frame_Content_Size fields in front of it (from the
+ *    anchor on). The rule, one definition (zg_seek.h): from p = anchor_src, pos = anchor_plain — a skippable frame is passed over (in front of
+ *    the selection while nothing is taken, inside it afterwards); a zstd frame that declares a size fcs, with nothing taken yet and
+ *    pos + fcs <= begin, is skipped (pos += fcs); any other frame is taken (the first sets src_lo and plain_lo = pos; a sized frame adds its fcs
+ *    to pos, an unsized one makes the selection open-ended); behind a taken frame the chain stops with src_hi = p once the selection is not
+ *    open-ended and pos >= begin + len (saturating). An open-ended selection runs to the end of the chain: an unsized frame and everything
+ *    behind it is decoded. Where the chain breaks (why != 0), in a skipped or a taken frame, src_hi = lens[i] and, if nothing was taken, src_lo
+ *    = the broken frame's begin: the decode of those bytes then reports what zgpu_decode_all reports for them. The end of the entry with
+ *    nothing taken (the range lies behind the plaintext) sets bit 2, and the decode call answers status 0, written 0.
+ *  - What random access means: frames in front of the range are never decoded, so a defect in their bodies or checksums is NOT seen; a
+ *    skipped frame whose declared size is false shifts the coordinates of everything behind it, silently; frames behind the range are not
+ *    read at all. A TAKEN frame that declares a size and decodes to another length fails its entry with ZGPU_E_CONTENT_SIZE_MISMATCH — behind
+ *    a decode error, a walk error and BAD_ARG, in front of TARGET_TOO_SMALL and of the checksum verdict of ZGPU_DEVICE_VERIFY. The check is
+ *    per frame, and the order is one — decode and walk, size, TARGET_TOO_SMALL, checksum — for every entry: with or without dictionary
+ *    frames, in a shared submit or decoded alone (an entry's status does not depend on zgpu_set_frames_shared_dicts).
+ *  - results[i].d is zgpu_decode_frames_device_src's result for the selection, except: written is the CLIPPED count — the bytes of
+ *    [begin - plain_lo, begin - plain_lo + len) that the taken frames' concatenation has — and ZGPU_E_TARGET_TOO_SMALL is decided by that
+ *    count against caps[i], not by the decoded size; nframes counts the frames decoded. The destination holds exactly those bytes.
+ *  - Anchors: a caller that reads many ranges of one entry indexes it once (zgpu_frames_table_device), keeps the table, and starts each chain
+ *    at a frame boundary in front of begin: anchor_src = that frame's src_begin, anchor_plain = the declared sizes in front of it. Nothing in
+ *    front of anchor_src is read. An anchor is the caller's promise; a wrong one shifts the coordinates like a false size.
+ *  - Guarantees that carry over: entries are isolated and their order does not matter; no byte of a failed entry's destination is written and
+ *    no byte at or behind dst + written; the hash rule and ZGPU_DEVICE_VERIFY act on the taken frames, hashed whole in the engine's output
+ *    (a corrupted checksum in a skipped frame is not seen); every source and destination passes the pointer check before anything is
+ *    launched; no lane reads a byte outside [src, src + lens[i]), in front of anchor_src, or inside a block body; streams are synchronised
+ *    on return. Entries decoded alone (dictionary frames with the shared switch off, Unsupported / Internal verdicts) download only
+ *    [src_lo, src_hi) and upload only the clipped bytes. zgpu_debug_frames_submits / _device_stats / _device_src_stats / _dict_stats are
+ *    filled as by zgpu_decode_frames_device_src. */
+typedef struct {
+  uint64_t begin, len;          /* plaintext bytes [begin, begin + len) of the entry (saturating); len == 0: nothing of the entry is checked, read
+                                   or written (its lane reads no byte), the record is all zeros */
+  uint64_t anchor_src;          /* a frame boundary of the entry at which the header chain starts (0: its first byte) ... */
+  uint64_t anchor_plain;        /* ... and the plaintext offset of that boundary (0 with anchor_src 0). From a cached zgpu_frames_table_device. */
+} zgpu_range;
+typedef struct {                /* 64 bytes: what one lane found; also what the decode call acted on */
+  uint64_t src_lo, src_hi;      /* the bytes of the entry that are decoded: whole frames (skippable frames between them included) */
+  uint64_t plain_lo;            /* plaintext offset, in the entry's coordinates, of the first byte the frame at src_lo yields */
+  uint64_t bound;               /* == zgpu_plaintext_bound of a host copy of [src_lo, src_hi) */
+  uint64_t plain_seen;          /* declared plaintext offset where the chain stopped */
+  uint32_t status;              /* 0 or ZGPU_E_BAD_ARG (pointer check, anchor_src > lens[i], anchor_plain > begin): then every other field 0 */
+  uint32_t frames_skipped, frames_taken, nblocks;   /* zstd frames (skippable frames are not counted; a frame in which the chain broke counts as
+                                   taken); nblocks: block headers read, skipped and taken frames together */
+  uint32_t why;                 /* ZGPU_CHAIN_*: why the chain ended, 0 if it stopped because the range was covered or the entry ended */
+  uint32_t flags;               /* bit 0 open-ended (an unsized frame was taken), bit 1 the chain broke, bit 2 nothing taken: the range lies behind the plaintext */
+} zgpu_seek;
+typedef struct { zgpu_device_entry_result d; zgpu_seek seek; } zgpu_range_result;
+/* out[i] for every entry; one launch, 64 bytes per entry come back, no byte of the input does */
+int zgpu_frames_seek_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out);
+int zgpu_decode_ranges_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                  void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts_or_null, zgpu_range_result* results);
+/* diagnostics of the context's last seek / ranges call: out[0] seek launches, [1] seek kernel microseconds (HIP events), [2] bytes downloaded by
+ * the seek (64 * n), [3] input bytes that crossed to the host (entries decoded alone only), [4] frames skipped, [5] frames decoded, [6] plaintext
+ * bytes decoded, [7] bytes written to destinations ([3], [5] - [7]: 0 after zgpu_frames_seek_device). [5] and [6] are work done, not bytes
+ * delivered: an entry that decoded and then failed a later check (size, TARGET_TOO_SMALL, checksum) is counted, and every entry is counted
+ * once, in its submit or alone. Returns how many were written. */
+int zgpu_debug_ranges_stats(const zgpu_ctx*, uint64_t* out, int n);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

@@ -80,6 +80,7 @@ const char* zgpu_status_name(int s) {
     case ZGPU_E_EXE_DICT_TOO_SMALL: return "NotEnoughBytesInDictionary";
     case ZGPU_E_DICT_DECODE: return "DictionaryDecodeError";
     case ZGPU_E_CHECKSUM_MISMATCH: return "ChecksumMismatch";
+    case ZGPU_E_CONTENT_SIZE_MISMATCH: return "ContentSizeMismatch";
     case ZGPU_E_UNSUPPORTED: return "Unsupported";
     case ZGPU_E_INTERNAL: return "Internal";
     case ZGPU_E_NOMEM: return "OutOfMemory";
@@ -852,8 +853,9 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
   int st = zgpu_decoder_create(c, &d);
   if (st) return st;
   // (sums: the content checksums of the frames decoded, as zgpu_decode_frames reports them — the decoder hashes what is drained)
-  auto note = [&]() {
+  auto note = [&](uint64_t yielded) {
     if (!sums) return;
+    if (d->fh.has_fcs() && d->fh.frame_content_size != yielded) sums->size_lies++;
     uint32_t v = 0;
     const bool has = zgpu_decoder_checksum_from_data(d, &v) != 0;
     const uint32_t calc = zgpu_decoder_calculated_checksum(d);
@@ -888,6 +890,7 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
       if (st) break;
       d->drain_rule = ZG_DRAIN_NONE;
       p = frame_at + hdr;
+      const size_t before = total;
       for (;;) {
         st = zgpu_decoder_decode_blocks(d, src + p, len - p, &used, ZGPU_STRAT_UPTO_BYTES, (size_t)1 << 20, &fin);
         p += used;
@@ -898,14 +901,15 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
       }
       d->drain_rule = ZG_DRAIN_DECODE_ALL;
       if (st) break;
-      note();
+      note(total - before);
       continue;
     }
     p += used;
     if (st) break;
-    total += zgpu_decoder_read(d, dst + total, cap - total);
+    const size_t got = zgpu_decoder_read(d, dst + total, cap - total);
+    total += got;
     if (zgpu_decoder_can_collect(d) != 0) { st = ZGPU_E_TARGET_TOO_SMALL; break; }
-    note();
+    note(got);
   }
   zgpu_decoder_destroy(d);
   if (!st) *written = total;

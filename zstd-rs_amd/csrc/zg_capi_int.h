@@ -32,6 +32,7 @@ struct zgpu_ctx {
   uint64_t frames_device_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
   uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)
   uint64_t frames_index_stats[4] = {0, 0, 0, 0};              // of the last zgpu_frames_index_device / zgpu_frames_table_device call (zgpu_debug_frames_index_stats)
+  uint64_t ranges_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // of the last zgpu_frames_seek_device / zgpu_decode_ranges_device_src call (zgpu_debug_ranges_stats)
   uint64_t hash_ranges_us = 0;                                // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
@@ -77,7 +78,8 @@ size_t zg_stream_take(zg::StreamCore* c, uint8_t* dst, size_t n);   // n <= can_
 
 // (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); sums, if given, collects the
 // content checksums of the frames it decoded (zgpu_decode_frames)
-struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0; };
+// size_lies: frames that declare a Frame_Content_Size and yielded another number of bytes
+struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0, size_lies = 0; };
 int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums);
 // (zg_stream.cpp) the process-wide cache of pinned host blocks the streams use; nullptr if none can be had
 void* zg_pinned_get(size_t n);

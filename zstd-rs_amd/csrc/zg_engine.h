@@ -247,6 +247,10 @@ class Engine {
   // pass says about every entry (the caller compares). An entry of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
   // events), bytes downloaded.
   int index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, const zgi::Entry* sum, zgi::Entry* out, zgi::FrameRec* recs, uint64_t* stats);
+  // Which whole frames of such entries hold a plaintext range (zgpu_frames_seek_device / zgpu_decode_ranges_device_src): ONE zg_k_seek launch
+  // (zg_seek.h) over all n lanes, out[i] = lane i's record. A lane of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
+  // events), bytes downloaded (64 per lane).
+  int seek_pass(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes

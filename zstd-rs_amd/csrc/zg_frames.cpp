@@ -26,6 +26,7 @@
 // buffer bookkeeping for every such frame as it does for a one-frame run. The verdict of an entry that holds a dictionary frame is put together
 // in zgpu_decode_all's order for such an entry — frame by frame (zg_decode_all_per_frame) — and what the submit cannot serve exactly (an
 // unregistered id, Unsupported / Internal: the dictionary splice behind a drain inside decode_all, zg_exact.h) goes alone as before.
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -120,6 +121,18 @@ struct Call {
   const uint64_t* bound = nullptr;                 //   plaintext_bound of every entry, from its records
   uint64_t* sstats = nullptr;                      //   zgpu_ctx::frames_device_src_stats
   const DictLookup* dicts = nullptr;               // shared dictionaries (zgpu_set_frames_shared_dicts): what the walks resolve ids with; else nullptr
+  // ranges (zgpu_decode_ranges_device_src): the entries are the selections zg_k_seek found, and of the concatenation of an entry's decoded frames
+  // only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
+  struct Clip { uint64_t skip, len, declared; };
+  const Clip* clip = nullptr;
+  uint64_t* rstats = nullptr;                      //   zgpu_ctx::ranges_stats
+  uint64_t alone_written = 0;                      //   bytes the entries decoded alone brought to their destinations
+  // what of `bytes` decoded bytes of entry i its destination gets
+  uint64_t clipped(uint32_t i, uint64_t bytes) const {
+    if (!clip) return bytes;
+    const uint64_t rest = bytes > clip[i].skip ? bytes - clip[i].skip : 0;
+    return rest < clip[i].len ? rest : clip[i].len;
+  }
   zgpu_entry_result& result(uint32_t i) const { return dres ? dres[i].r : res[i]; }
 };
 
@@ -214,20 +227,25 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     int dev = 0;
     uint64_t bytes = 0;
     bool small = false;   // (has_dict) the entry's output up to a frame in front of the first failing one does not fit
+    bool lied = false;    // (ranges) a frame that declares a size decoded to another length: the coordinates of the range mean nothing
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (!dev && fo[f].status) dev = (int)fo[f].status;
       bytes += fo[f].out_size;
-      if (has_dict[j] && !dev && !b->info[f].host_status && bytes > k.caps[i]) small = true;
+      if (has_dict[j] && !dev && !b->info[f].host_status && k.clipped(i, bytes) > k.caps[i]) small = true;
+      if (k.clip && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
     }
     if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[4] += has_dict[j]; continue; }
+    if (k.rstats) { k.rstats[5] += ff[j + 1] - ff[j]; k.rstats[6] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
     // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
     // next one is looked at), so a frame that does not fit ends it with TargetTooSmall BEFORE a later frame's error or the walk's; without one,
     // zgpu_decode_all's one submit reports a device error first, then the walk's, then TargetTooSmall.
-    if (has_dict[j]) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j];
-    else r.status = dev ? dev : walk[j] ? walk[j] : bytes > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
+    // (ranges have ONE order, with or without dictionary frames, in a submit or alone: the decode and walk verdicts, ContentSizeMismatch,
+    // TargetTooSmall by the clipped count — taken in coordinates that the declared sizes define —, then the checksum verdict)
+    if (has_dict[j] && !k.clip) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j] ? walk[j] : ZGPU_OK;
+    else r.status = dev ? dev : walk[j] ? walk[j] : lied ? ZGPU_E_CONTENT_SIZE_MISMATCH : k.clipped(i, bytes) > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
     if (r.status) continue;
     if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[0] += b->bb.frames[f].dict_len ? 1u : 0u;
-    r.written = bytes;
+    r.written = k.clipped(i, bytes);
     r.nframes = ff[j + 1] - ff[j];
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (fo[f].out_size <= k.hash_max || (k.hash_all && b->info[f].has_checksum)) u.cand.push_back(f);   // (candidates)
@@ -306,10 +324,15 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     for (uint32_t j = 0; j < n; j++) {
       const zgpu_entry_result& r = k.dres[idx[j]].r;
       if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
-      uint64_t at = 0;
+      // (ranges: a frame's segment is clipped to [lo, hi) of the concatenation of the entry's frames; a clipped frame is just a shorter segment)
+      const uint64_t lo = k.clip ? k.clip[idx[j]].skip : 0, hi = k.clip && k.clip[idx[j]].len < UINT64_MAX - lo ? lo + k.clip[idx[j]].len : UINT64_MAX;
+      uint64_t cat = 0, at = 0;
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-        if (fo[f].out_size) segs.push_back(zgs::Seg{fo[f].out_base, (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, fo[f].out_size});
-        at += fo[f].out_size;
+        const uint64_t a = cat, e = cat + fo[f].out_size, s = a > lo ? a : lo, t = e < hi ? e : hi;
+        cat = e;
+        if (s >= t) continue;
+        segs.push_back(zgs::Seg{fo[f].out_base + (s - a), (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, t - s});
+        at += t - s;
       }
       if (at != r.written || at > k.caps[idx[j]]) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
       bytes += at;
@@ -379,7 +402,8 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
 
 // an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
 // which also hashes what it hands out)
-int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr, const uint8_t* host_src = nullptr) {
+int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr, const uint8_t* host_src = nullptr,
+                 uint32_t* size_lies = nullptr) {
   const uint8_t* src = host_src ? host_src : k.srcs[i];   // (device sources: the entry's bytes downloaded by decode_alone_device)
   zgpu_entry_result& r = k.result(i);
   memset(&r, 0, sizeof r);
@@ -408,6 +432,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
   r.status = st;
   if (st) return ZGPU_OK;
   if (summed) *summed = sums_ok;
+  if (size_lies) *size_lies = sums.size_lies;
   if (!sums_ok) {   // the frames are counted from their headers; no checksum is reported
     std::vector<FrameSpan> sp;
     (void)split_frames(src, k.lens[i], &sp);
@@ -432,14 +457,28 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   }
   const uint8_t* src = k.sk ? down.data() : k.srcs[i];
   const uint64_t bound = plaintext_bound(src, k.lens[i]);
-  const size_t cap = k.caps[i] < bound ? k.caps[i] : (size_t)bound;   // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i])
+  // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i]. Ranges: the whole selection is decoded, and clipped below)
+  const size_t cap = k.clip ? (size_t)bound : k.caps[i] < bound ? k.caps[i] : (size_t)bound;
   uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
   if (!tmp) return ZGPU_E_NOMEM;
   bool summed = false;
-  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src);
+  uint32_t size_lies = 0;
+  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies);
   zgpu_device_entry_result& d = k.dres[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
+  if (k.rstats && !st && !d.r.status) { k.rstats[5] += d.r.nframes; k.rstats[6] += d.r.written; }
+  // ranges, in the order of a submit's verdicts (decode_submit): the size check, TargetTooSmall by the clipped count, then the checksums.
+  // The size check is per frame, from the frame-by-frame pass; should that pass have failed (never seen), the frames are measured together.
+  // The buffer holds the selection's bound: every frame's declared size, or what its block headers allow where that is less. Only a frame
+  // that yields more than it declares can overflow it.
+  if (k.clip && !st && d.r.status == ZGPU_E_TARGET_TOO_SMALL) { memset(&d, 0, sizeof d); d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH; }
+  if (k.clip && !st && !d.r.status &&
+      (summed ? size_lies != 0 : k.clip[i].declared != UINT64_MAX && d.r.written != k.clip[i].declared)) {
+    memset(&d, 0, sizeof d);
+    d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH;
+  }
+  if (k.clip && !st && !d.r.status && k.clipped(i, d.r.written) > k.caps[i]) { memset(&d, 0, sizeof d); d.r.status = ZGPU_E_TARGET_TOO_SMALL; }
   // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its one H2D
   if (!st && !d.r.status && k.verify && summed && !k.no_hash && d.r.checksum_mismatches) {
     const uint32_t sums = d.r.checksums, bad = d.r.checksum_mismatches;
@@ -449,8 +488,15 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
     d.r.checksums = sums; d.r.checksum_mismatches = bad;
     k.stats[7]++;
   }
+  size_t from = 0;   // ranges: only the clipped bytes are uploaded
+  if (k.clip && !st && !d.r.status) {
+    const uint64_t w = k.clipped(i, d.r.written);
+    from = (size_t)(k.clip[i].skip < d.r.written ? k.clip[i].skip : d.r.written);
+    d.r.written = w;
+  }
   if (!st && !d.r.status) {
-    if (d.r.written && hipMemcpy(k.dsts[i], tmp, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    if (d.r.written && hipMemcpy(k.dsts[i], tmp + from, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    k.alone_written += d.r.written;
     const bool hashed = summed && !k.no_hash && d.r.nframes;
     if (k.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
     d.first_hashed = hashed ? 1u : 0u;
@@ -759,6 +805,133 @@ extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, 
   if (!c || !out) return 0;
   int k = 0;
   for (; k < n && k < 9; k++) out[k] = c->frames_device_stats[k];
+  return k;
+}
+
+// ---- byte ranges of device-resident entries (zg_seek.h) --------------------------------------------------------------------------------------
+static_assert(sizeof(zgpu_range) == 32 && sizeof(zgpu_seek) == sizeof(zgk::Seek) && sizeof(zgpu_range_result) == sizeof(zgpu_device_entry_result) + 64,
+              "include/zgpu.h");
+static_assert(offsetof(zgpu_seek, plain_seen) == offsetof(zgk::Seek, plain_seen) && offsetof(zgpu_seek, status) == offsetof(zgk::Seek, status) &&
+              offsetof(zgpu_seek, flags) == offsetof(zgk::Seek, flags) && ZGPU_E_BAD_ARG == zgk::kBadArg, "zgk::Seek is zgpu_seek");
+namespace {
+// Both calls up to the records: every pointer checked, ONE zg_k_seek launch over all n lanes (a refused entry and a range of length 0 have
+// length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations.
+int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* dsts, const size_t* caps,
+                std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+  for (uint64_t& x : c->ranges_stats) x = 0;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  std::vector<zgk::Lane> lanes(n);
+  out->assign(n, zgk::Seek{});
+  refused->assign(n, 0);
+  std::vector<DevRange> known;
+  for (uint32_t i = 0; i < n; i++) {
+    const zgpu_range& g = ranges[i];
+    bool bad = false;
+    if (g.len) {
+      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]);
+      if (!bad && lens[i]) bad = !check_device_range(c->eng->device(), srcs[i], lens[i], known);
+      if (!bad && dsts && caps[i]) bad = !check_device_range(c->eng->device(), dsts[i], caps[i], known);
+    }
+    (*refused)[i] = bad;
+    lanes[i] = zgk::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
+  }
+  int st = c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats);
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  if (st) return st;
+  for (uint32_t i = 0; i < n; i++) {
+    zgk::Seek& s = (*out)[i];
+    if ((*refused)[i]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
+    if (s.src_lo > s.src_hi || s.src_hi > lens[i] || (s.status && s.status != ZGPU_E_BAD_ARG)) {   // (never)
+      c->eng->last_error = "zgpu_frames_seek_device: a record that leaves its entry";
+      return ZGPU_E_INTERNAL;
+    }
+    c->ranges_stats[4] += s.frames_skipped;
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused);
+  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
+  return st;
+}
+
+// The selections become the entries of zgpu_decode_frames_device_src's machinery: (src + src_lo, src_hi - src_lo) is walked, cut into submits,
+// gathered, decoded and hashed as any entry is, and only the verdict (the size check), the scatter list (clipped) and the entries that go
+// alone (the selection downloaded, the clipped bytes uploaded) know of the range.
+extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
+  for (uint64_t& x : c->frames_device_stats) x = 0;
+  for (uint64_t& x : c->frames_device_src_stats) x = 0;
+  for (uint64_t& x : c->frames_dict_stats) x = 0;
+  c->frames_submits = 0;
+  for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  int st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &refused);
+  if (st) return st;
+  std::vector<const uint8_t*> srcs(n);
+  std::vector<size_t> sub(n);
+  std::vector<Engine::DevEntry> dev(n);
+  std::vector<Call::Clip> clip(n);
+  std::vector<uint64_t> bound(n, 0);
+  std::vector<zgpu_device_entry_result> dres(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const zgk::Seek& s = recs[i];
+    if (s.status) refused[i] = 1;                                  // (an anchor behind the entry or behind begin)
+    const bool none = refused[i] || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
+    srcs[i] = (const uint8_t*)device_srcs[i] + (none ? 0 : s.src_lo);
+    sub[i] = none ? 0 : (size_t)(s.src_hi - s.src_lo);
+    dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
+    const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
+    clip[i] = Call::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, closed && !none ? s.plain_seen - s.plain_lo : UINT64_MAX};
+  }
+  Call k{c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
+  k.dres = dres.data();
+  k.no_hash = opts && (opts->flags & 1u);
+  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
+  k.hash_all = k.verify && !opts->hash_max_bytes;
+  k.stats = c->frames_device_stats;
+  k.sstats = c->frames_device_src_stats;
+  k.clip = clip.data();
+  k.rstats = c->ranges_stats;
+  const DictLookup lookup{shared_find, c};
+  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
+  Engine::Skeleton sk;
+  st = c->eng->walk_entries(dev.data(), n, &sk, k.sstats);
+  for (uint32_t i = 0; i < n && !st; i++) {
+    bool consistent = true;
+    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent, k.dicts);
+    // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number)
+    if (!consistent || (!k.dicts && sub[i] && bound[i] != recs[i].bound)) {
+      c->eng->last_error = "zgpu_decode_ranges_device_src: a source changed between the seek and the walk";
+      st = ZGPU_E_INTERNAL;
+    }
+  }
+  if (!st) {
+    k.sk = &sk; k.dev = dev.data(); k.refused = refused.data(); k.bound = bound.data();
+    st = decode_entries(k, n);
+  }
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  k.stats[0] = c->frames_submits;
+  k.rstats[3] = k.sstats[5];
+  k.rstats[7] = k.stats[2] + k.alone_written;
+  for (uint32_t i = 0; i < n; i++) {
+    if (!st) results[i].d = dres[i];
+    memcpy(&results[i].seek, &recs[i], sizeof results[i].seek);
+  }
+  return st;
+}
+extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c || !out) return 0;
+  int k = 0;
+  for (; k < n && k < 8; k++) out[k] = c->ranges_stats[k];
   return k;
 }
 

@@ -17,7 +17,7 @@
 // Summary pass (EMIT = false): one 48-byte Entry per lane. Emit pass (EMIT = true, the table call only, after the host's prefix sum over
 // Entry::nrec): lane i writes frame records first .. first + limit and checks the limit before every store; an input that changed between the
 // passes ends in a count the host refuses (ZGPU_E_INTERNAL), not in a store outside the range.
-// gfx950 ISA of zg_k_index (hipcc -O3 --save-temps): zg_k_index<false> 48 VGPRs (zg_k_walk<false>: 28; both below the 64 up to which a wave64
+// gfx950 ISA of zg_k_index (hipcc -O3 --save-temps): zg_k_index<false> 47 VGPRs (zg_k_walk<false>: 28; both below the 64 up to which a wave64
 // kernel keeps full occupancy), no scratch, no LDS. The loads that remain are one global_load_dwordx4 of the lane's src and len and the 24
 // global_load_ubyte of the chain, each group issued together in front of its waits: 4 of the magic, the descriptor, 4 of a dictionary id and
 // 8 of the content size (a shorter field reads its last byte again), 4 of a skippable frame's length, and the 3 of a block header — the
@@ -57,6 +57,61 @@ struct alignas(16) FrameRec {
 };
 static_assert(sizeof(FrameRec) == 64, "frame record");
 
+// The fields of a zstd frame's header that the chain and the bound need, at p (descriptor d, header of hs bytes: zgw::header_stop has said they
+// are all there). ONE definition: index_entry below and zgk::seek_entry (zg_seek.h) both read a header with it.
+struct FrameHead { uint64_t fcs; uint32_t id, fl; bool has_ck; };   // fl: bytes of the Frame_Content_Size field (0: the frame declares none)
+template <class R> ZG_WK_FN FrameHead frame_head(const R& r, uint64_t p, uint8_t d, uint32_t hs) {
+  // frame.rs:212-239: the sizes of the dictionary id and content size fields; the content size is the header's last field
+  const uint32_t single = (d >> 5) & 1u, did = d & 3u, fc = d >> 6;
+  const uint32_t dl = did == 3 ? 4u : did, fl = fc == 0 ? single : (fc == 1 ? 2u : (fc == 2 ? 4u : 8u));
+  uint32_t id = 0;
+  uint64_t fcs = 0;
+  // (a field's loads are issued together: byte i of a shorter field is its last byte again, and is masked out)
+  if (dl) {
+ZG_WK_UNROLL
+    for (uint32_t i = 0; i < 4; i++) { const uint32_t v = r.ld1(p + hs - fl - dl + (i < dl ? i : dl - 1)); id |= i < dl ? v << (8 * i) : 0u; }
+  }
+  if (fl) {
+    uint32_t lo = 0, hi = 0;
+ZG_WK_UNROLL
+    for (uint32_t i = 0; i < 8; i++) {
+      const uint32_t v = r.ld1(p + hs - fl + (i < fl ? i : fl - 1)), x = i < fl ? v << (8 * (i & 3)) : 0u;
+      if (i < 4) lo |= x; else hi |= x;
+    }
+    fcs = lo | ((uint64_t)hi << 32);
+  }
+  if (fl == 2) fcs += 256;   // frame.rs:78-80
+  return FrameHead{fcs, id, fl, (bool)((d >> 2) & 1u)};
+}
+// The blocks of a zstd frame from *p (behind its header) on: three header bytes per block, never a body. *p ends behind the frame (its
+// Content_Checksum included) or where the chain broke; *fb += what the blocks count towards the bound, *nblocks += the headers read; *done:
+// the last block was seen and the checksum is all there. Returns why the chain broke, kEnd if it did not.
+template <class R> ZG_WK_FN uint32_t frame_blocks(const R& r, uint64_t len, bool has_ck, uint64_t* p, uint64_t* fb, uint32_t* nblocks, bool* done) {
+  uint32_t why;
+  *done = false;
+  for (;;) {
+    if (len - *p < 3) { why = zgw::kShortBlockHeader; break; }
+    const uint8_t b0 = r.ld1(*p), b1 = r.ld1(*p + 1), b2 = r.ld1(*p + 2);
+    (*nblocks)++;
+    zgw::BlockHdr bh;
+    why = zgw::block_stop(b0, b1, b2, len - (*p + 3), &bh);
+    if (why == zgw::kReservedBlock || why == zgw::kBlockTooLarge) break;   // (read_block_header fails: the block counts nothing)
+    *fb += bh.type == 2 ? (uint64_t)zgw::kBlockMax : (uint64_t)bh.size;
+    if (why) break;                                                        // (the body runs past the entry: the block has counted)
+    *p += 3 + (uint64_t)bh.content;
+    if (bh.last) {
+      *done = true;
+      if (has_ck) {
+        const uint32_t nc = zgw::checksum_bytes(len, *p);
+        *p += nc;
+        if (nc < 4) { why = zgw::kShortChecksum; *done = false; }
+      }
+      break;
+    }
+  }
+  return why;
+}
+
 // What the lane of one entry does. R reads the entry (ld1(off), off counted from the entry's first byte; the routine asks for no off >= len
 // and for no byte of a block body); W writes frame records (put(index, rec)); EMIT = false is the summary pass, which writes no record.
 template <bool EMIT, class R, class W> ZG_WK_FN Entry index_entry(const R& r, const W& w, uint64_t len, uint64_t first, uint64_t limit) {
@@ -85,53 +140,15 @@ template <bool EMIT, class R, class W> ZG_WK_FN Entry index_entry(const R& r, co
       if (!why) {
         nfr++;
         nb = hs;
-        // frame.rs:212-239: the sizes of the dictionary id and content size fields; the content size is the header's last field
-        const uint32_t single = (d >> 5) & 1u, did = d & 3u, fc = d >> 6;
-        const uint32_t dl = did == 3 ? 4u : did, fl = fc == 0 ? single : (fc == 1 ? 2u : (fc == 2 ? 4u : 8u));
-        const bool has_ck = (d >> 2) & 1u;
-        uint32_t id = 0;
-        uint64_t fcs = 0;
-        // (a field's loads are issued together: byte i of a shorter field is its last byte again, and is masked out)
-        if (dl) {
-ZG_WK_UNROLL
-          for (uint32_t i = 0; i < 4; i++) { const uint32_t v = r.ld1(p + hs - fl - dl + (i < dl ? i : dl - 1)); id |= i < dl ? v << (8 * i) : 0u; }
-        }
-        if (fl) {
-          uint32_t lo = 0, hi = 0;
-ZG_WK_UNROLL
-          for (uint32_t i = 0; i < 8; i++) {
-            const uint32_t v = r.ld1(p + hs - fl + (i < fl ? i : fl - 1)), x = i < fl ? v << (8 * (i & 3)) : 0u;
-            if (i < 4) lo |= x; else hi |= x;
-          }
-          fcs = lo | ((uint64_t)hi << 32);
-        }
-        if (fl == 2) fcs += 256;   // frame.rs:78-80
-        if (id) any_dict = true;   // (a dictionary id of 0 names none, frame.rs:60-62)
-        if (has_ck) any_ck = true;
-        if (!fl) all_sized = false;
+        const FrameHead h = frame_head(r, p, d, hs);
+        if (h.id) any_dict = true;   // (a dictionary id of 0 names none, frame.rs:60-62)
+        if (h.has_ck) any_ck = true;
+        if (!h.fl) all_sized = false;
         p += hs;
-        bool done = false;
-        for (;;) {
-          if (len - p < 3) { why = zgw::kShortBlockHeader; break; }
-          const uint8_t b0 = r.ld1(p), b1 = r.ld1(p + 1), b2 = r.ld1(p + 2);
-          nbl++; fblocks++;
-          zgw::BlockHdr bh;
-          why = zgw::block_stop(b0, b1, b2, len - (p + 3), &bh);
-          if (why == zgw::kReservedBlock || why == zgw::kBlockTooLarge) break;   // (read_block_header fails: the block counts nothing)
-          fb += bh.type == 2 ? (uint64_t)zgw::kBlockMax : (uint64_t)bh.size;
-          if (why) break;                                                        // (the body runs past the entry: the block has counted)
-          p += 3 + (uint64_t)bh.content;
-          if (bh.last) {
-            done = true;
-            if (has_ck) {
-              const uint32_t nc = zgw::checksum_bytes(len, p);
-              p += nc;
-              if (nc < 4) { why = zgw::kShortChecksum; done = false; }
-            }
-            break;
-          }
-        }
-        share = fl && fcs < fb ? fcs : fb;
+        bool done;
+        why = frame_blocks(r, len, h.has_ck, &p, &fb, &fblocks, &done);
+        nbl += fblocks;
+        share = h.fl && h.fcs < fb ? h.fcs : fb;
         if (done) fflags = kComplete; else all_done = false;
       }
     }

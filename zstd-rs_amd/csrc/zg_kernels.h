@@ -7,6 +7,7 @@
 #include "zg_dictfill.h"
 #include "zg_walk.h"
 #include "zg_index.h"
+#include "zg_seek.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -67,3 +68,6 @@ void zg_launch_walk(const zgw::Lane* lanes, uint32_t n, zgw::End* ends, zgw::Rec
 // zg_k_index (zg_index.h): one lane per entry follows the entry's header chain without touching a block body; entries[i] = the summary of lane i.
 // recs == nullptr: the summary pass (nothing else is written); else lane i also writes frame records lanes[i].first .. + lanes[i].limit of recs
 void zg_launch_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zgi::FrameRec* recs, hipStream_t s);
+// zg_k_seek (zg_seek.h): one lane per entry selects the whole frames that hold a plaintext range of the entry, from frame and block headers alone;
+// out[i] = the record of lane i. ONE launch for all n entries
+void zg_launch_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s);

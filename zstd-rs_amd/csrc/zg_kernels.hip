@@ -1893,6 +1893,27 @@ void zg_launch_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zg
   else hipLaunchKernelGGL(zg_k_index<false>, g, t, 0, s, lanes, n, entries, recs);
 }
 
+// Which frames of entries that lie in device memory hold a plaintext range, one lane per entry (zg_seek.h has the rule, the record and the ISA
+// notes). The host checked every [src, src + len) against the runtime's allocations; a lane reads nothing outside [src + anchor_src, src + len),
+// no byte of a block body, and writes its own 64-byte record only.
+__global__ void __launch_bounds__(zgk::kThreads) zg_k_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out) {
+  const uint32_t i = blockIdx.x * zgk::kThreads + threadIdx.x;
+  if (i >= n) return;
+  const zgk::Lane l = lanes[i];
+  const zgk::Seek o = zgk::seek_entry(ZgWalkRead{l.src}, l.len, l.begin, l.rlen, l.anchor_src, l.anchor_plain);
+  // the record leaves as four 16-byte stores (volatile: the compiler otherwise cuts the last 32 bytes into 8 + 12 + 12 to save register moves)
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  volatile __attribute__((address_space(1))) u32x4* d = (volatile __attribute__((address_space(1))) u32x4*)(uintptr_t)&out[i];
+  d[0] = u32x4{(uint32_t)o.src_lo, (uint32_t)(o.src_lo >> 32), (uint32_t)o.src_hi, (uint32_t)(o.src_hi >> 32)};
+  d[1] = u32x4{(uint32_t)o.plain_lo, (uint32_t)(o.plain_lo >> 32), (uint32_t)o.bound, (uint32_t)(o.bound >> 32)};
+  d[2] = u32x4{(uint32_t)o.plain_seen, (uint32_t)(o.plain_seen >> 32), o.status, o.frames_skipped};
+  d[3] = u32x4{o.frames_taken, o.nblocks, o.why, o.flags};
+}
+void zg_launch_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_seek, dim3((n + zgk::kThreads - 1) / zgk::kThreads), dim3(zgk::kThreads), 0, s, lanes, n, out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

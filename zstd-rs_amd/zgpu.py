@@ -23,6 +23,7 @@ E_TARGET_TOO_SMALL = 12
 E_FAILED_SKIP_FRAME = 13
 E_RESERVED_BLOCK, E_BLOCK_SIZE_TOO_LARGE = 20, 21
 E_CHECKSUM_MISMATCH = 70    # decode_frames_device / decode_frames_device_src with verify=True only (no counterpart in the reference)
+E_CONTENT_SIZE_MISMATCH = 71   # decode_ranges_device_src only: a taken frame decoded to another length than it declares (no counterpart in the reference)
 E_UNSUPPORTED = 80
 E_HIP = 92
 
@@ -119,6 +120,67 @@ class FrameIndex:
             self.entry, self.src_begin, self.src_end, self.bound, self.nblocks, self.header_status, self.flags)
 
 
+class RangeC(C.Structure):
+    """zgpu_range (include/zgpu.h)"""
+    _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("anchor_src", C.c_uint64), ("anchor_plain", C.c_uint64)]
+
+
+class SeekC(C.Structure):
+    """zgpu_seek (include/zgpu.h)"""
+    _fields_ = [("src_lo", C.c_uint64), ("src_hi", C.c_uint64), ("plain_lo", C.c_uint64), ("bound", C.c_uint64), ("plain_seen", C.c_uint64),
+                ("status", C.c_uint32), ("frames_skipped", C.c_uint32), ("frames_taken", C.c_uint32), ("nblocks", C.c_uint32),
+                ("why", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RangeResultC(C.Structure):
+    """zgpu_range_result (include/zgpu.h)"""
+    _fields_ = [("d", DeviceEntryResultC), ("seek", SeekC)]
+
+
+class Seek:
+    """One entry of Context.frames_seek_device (zgpu_seek): the whole frames [src_lo, src_hi) of the entry that hold the range, the plaintext
+    offset plain_lo of the first of them, bound = plaintext_bound of those bytes. flags: open_ended (an unsized frame was taken: everything
+    behind it is decoded too), broken (the header chain broke: why says how), nothing (the range lies behind the plaintext)."""
+    __slots__ = ("src_lo", "src_hi", "plain_lo", "bound", "plain_seen", "status", "frames_skipped", "frames_taken", "nblocks", "why", "flags",
+                 "open_ended", "broken", "nothing")
+    FIELDS = __slots__[:11]
+
+    def __init__(self, c):
+        for k in self.FIELDS:
+            setattr(self, k, int(getattr(c, k)))
+        self.open_ended, self.broken, self.nothing = bool(self.flags & 1), bool(self.flags & 2), bool(self.flags & 4)
+
+    def key(self):
+        return tuple(getattr(self, k) for k in self.FIELDS)
+
+    def __repr__(self):
+        return "Seek(status=%d, src=[%d, %d), plain_lo=%d, bound=%d, skipped=%d, taken=%d, nblocks=%d, why=%d, flags=%#x)" % (
+            self.status, self.src_lo, self.src_hi, self.plain_lo, self.bound, self.frames_skipped, self.frames_taken, self.nblocks, self.why,
+            self.flags)
+
+
+def anchor_before(frames, offset, entry=0):
+    """The anchor nearest in front of plaintext offset `offset` of entry `entry`, from the FrameIndex records of Context.frames_table_device:
+    (anchor_src, anchor_plain) of the last frame boundary whose declared plaintext offset is <= offset, with every zstd frame in front of it
+    declaring its content size (behind an unsized frame no offset is known, so no later boundary is an anchor). (0, 0) if there is none."""
+    best, plain = (0, 0), 0
+    for f in frames:
+        if f.entry != entry:
+            continue
+        if plain <= offset:
+            best = (f.src_begin, plain)
+        if f.header_status != 0:
+            if f.header_status == E_SKIP_FRAME:
+                continue
+            break
+        if not f.has_content_size or not f.complete:
+            break
+        plain += f.frame_content_size
+        if plain > offset:
+            break
+    return best
+
+
 def plaintext_bound(buf):
     """zgpu_plaintext_bound: an upper bound of the plaintext of concatenated frames from frame and block headers only (a frame's declared
     content size when smaller; a compressed block counts 128 KiB); the walk stops where a header cannot be read. Decode_frames' default
@@ -160,6 +222,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
     "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats", "zgpu_debug_hash_ranges", "zgpu_debug_hash_ranges_us",
@@ -238,6 +301,9 @@ def _declare(L):
     L.zgpu_frames_index_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC)]
     L.zgpu_frames_table_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC), P(C.c_uint64), P(FrameIndexC), sz, P(sz)]
     L.zgpu_debug_frames_index_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_frames_seek_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(RangeC), P(SeekC)]
+    L.zgpu_decode_ranges_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(RangeC), P(vp), P(sz), P(DeviceOptsC), P(RangeResultC)]
+    L.zgpu_debug_ranges_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_set_frames_shared_dicts.argtypes = [vp, C.c_int]
     L.zgpu_set_frames_shared_dicts.restype = None
     L.zgpu_frames_shared_dicts.argtypes = [vp]
@@ -620,6 +686,82 @@ class Context:
         k = self.L.zgpu_debug_frames_index_stats(self.h, a, 4)
         keys = ["launches", "kernel_us", "bytes_downloaded", "input_bytes_to_host"]
         return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    @staticmethod
+    def _ranges(ranges, anchors, n):
+        if len(ranges) != n or (anchors is not None and len(anchors) != n):
+            raise ValueError("one range (and one anchor) per source")
+        rg = (RangeC * max(n, 1))()
+        for i in range(n):
+            a = anchors[i] if anchors is not None and anchors[i] is not None else (0, 0)
+            rg[i] = RangeC(int(ranges[i][0]), int(ranges[i][1]), int(a[0]), int(a[1]))
+        return rg
+
+    def frames_seek_device(self, src_ptrs, lens, ranges, anchors=None):
+        """zgpu_frames_seek_device: which whole frames of entries in DEVICE memory hold plaintext bytes [begin, begin + len) of them, from
+        frame and block headers alone. ranges[i] = (begin, len); anchors[i] = (anchor_src, anchor_plain) or None: a frame boundary of the entry
+        at which the header chain starts and its plaintext offset (anchor_before gives one from a cached frames_table_device). One kernel
+        launch, 64 bytes per entry come back, no byte of the input does. Returns one Seek per entry."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        rg = self._ranges(ranges, anchors, n)
+        out = (SeekC * max(n, 1))()
+        st = self.L.zgpu_frames_seek_device(self.h, srcs, lena, n, rg, out)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return [Seek(out[i]) for i in range(n)]
+
+    def decode_ranges_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, anchors=None, hash_max=0, no_hash=False, verify=False):
+        """zgpu_decode_ranges_device_src: plaintext bytes ranges[i] = (begin, len) of entry i (device memory, as decode_frames_device_src takes
+        it) written to dst_ptrs[i] (caps[i] bytes of device memory); only the frames that hold the range are decoded. Frames in front of the
+        range are never decoded (a defect in them is not seen, a false declared size in them shifts the coordinates); frames behind it are
+        not read. Returns (results, seeks): one DeviceEntryResult per entry — written is the clipped count, E_CONTENT_SIZE_MISMATCH a taken
+        frame that decoded to another length than it declares — and the Seek record the call acted on."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        if len(dst_ptrs) != n or len(caps) != n:
+            raise ValueError("decode_ranges_device_src: one destination and one capacity per source")
+        rg = self._ranges(ranges, anchors, n)
+        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
+        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
+        res = (RangeResultC * max(n, 1))()
+        st = self.L.zgpu_decode_ranges_device_src(self.h, srcs, lena, n, rg, dsts, capa, C.byref(opts), res)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        dres = (DeviceEntryResultC * max(n, 1))(*[res[i].d for i in range(n)])
+        return self._device_results(dres, n), [Seek(res[i].seek) for i in range(n)]
+
+    def ranges_stats(self):
+        """the last frames_seek_device / decode_ranges_device_src call (zgpu_debug_ranges_stats)"""
+        a = (C.c_uint64 * 8)()
+        k = self.L.zgpu_debug_ranges_stats(self.h, a, 8)
+        keys = ["seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
+                "plaintext_decoded", "bytes_written"]
+        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+
+    def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False):
+        """decode_ranges_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
+        compressed bytes, ranges[i] = (begin, len) the plaintext bytes wanted of it. The bytes go to ONE new torch.uint8 tensor, every entry's
+        slot 256-byte aligned and sized by min(len, seek.bound) — a frames_seek_device call of its own finds the bound, so no byte of the
+        input crosses to the host. Returns (tensors, results, seeks): tensors[i] is a view of entry i's slot cut to `written` bytes (empty
+        unless status == 0). Same single-runtime rule as decode_tensors. torch is imported here, not by `import zgpu`."""
+        import torch
+        self._tensor_check(tensors, "decode_tensor_ranges")
+        dev = torch.device("cuda", self.device)
+        ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
+        seeks = self.frames_seek_device(ptrs, lens, ranges, anchors)
+        caps = [min(int(r[1]), s.bound) for r, s in zip(ranges, seeks)]
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (int(c) + 255) & ~255
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+        base = buf.data_ptr()
+        res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, anchors=anchors, hash_max=hash_max,
+                                                   no_hash=no_hash, verify=verify)
+        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res, seeks
 
     def _tensor_check(self, tensors, what):
         import torch
