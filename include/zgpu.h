@@ -71,6 +71,9 @@ enum zgpu_status {
    * srcSize_wrong). Only an entry of zgpu_decode_ranges_device_src gets it: a frame of the selection declares a size and decoded to another
    * length, so the plaintext coordinates the range was asked in do not hold. */
   ZGPU_E_CONTENT_SIZE_MISMATCH = 71,
+  /* No counterpart in the reference, which knows no seekable format. Only an entry of zgpu_frames_seek_table_device /
+   * zgpu_decode_ranges_seek_table_device_src gets it: the entry does not end in a usable seek table; zgpu_seek.why (ZGPU_SEEKTAB_*) says why. */
+  ZGPU_E_SEEK_TABLE = 72,
   /* Input the reference tolerates but this engine rejects. No conforming encoder produces any of it:
    *  - offsets >= 2^30 (offset codes 30, 31) while >= 1 GiB of the frame is held undrained (FrameDecoder::decode_blocks(All) on a
    *    frame beyond 1 GiB that nobody reads from): ZGPU_E_UNSUPPORTED. With less than 1 GiB held — always the case in decode_all
@@ -391,6 +394,57 @@ int zgpu_decode_ranges_device_src(zgpu_ctx*, const void* const* device_srcs, con
  * delivered: an entry that decoded and then failed a later check (size, TARGET_TOO_SMALL, checksum) is counted, and every entry is counted
  * once, in its submit or alone. Returns how many were written. */
 int zgpu_debug_ranges_stats(const zgpu_ctx*, uint64_t* out, int n);
+
+/* ---- byte ranges through the seek table of zstd's seekable format ------------------------------------------------------------------------------
+ * Files written for random access (libzstd's contrib/seekable_format, t2sz, shard and columnar writers) are compressed as a stream, so their
+ * frames usually declare no Frame_Content_Size: zgpu_decode_ranges_device_src then takes the first frame, is open-ended and decodes the whole
+ * entry. Such files carry the index themselves: ONE skippable frame at the entry's end, the seek table (all fields little-endian) —
+ *    Skippable_Magic 0x184D2A5E | Frame_Size = nframes * es + 9 | nframes x { Compressed_Size u32, Decompressed_Size u32 [, Checksum u32] } |
+ *    Number_Of_Frames u32 (<= 0x8000000) | Seek_Table_Descriptor u8 (bit 7 Checksum_Flag; bits 6..2 reserved, 0; bits 1..0 ignored) | 0x8F92EAB1
+ * es = 8, or 12 with checksums. Entry k describes the k-th frame of the entry (a skippable frame is entered with decompressed size 0); it lies
+ * at source offset C_k, the compressed sizes in front of it, and yields plaintext [D_k, D_k + d_k), D_k the decompressed sizes in front of it.
+ * zgpu_frames_seek_table_device reads that table on the device, one WAVE per entry (zg_k_seektab, ONE launch for the whole call: coalesced loads,
+ * two wave-wide prefix sums, a ballot; no frame or block header is touched, 64 bytes per entry come back and no byte of the input), and
+ * zgpu_decode_ranges_seek_table_device_src runs the selections through the machinery of zgpu_decode_ranges_device_src.
+ *  - Plaintext coordinates are the TABLE's coordinates, not declared ones. The rule, one definition (zg_seektab.h), end = begin + len saturating:
+ *    first = the smallest k with D_k + d_k > begin; last = the smallest k >= first with D_k + d_k >= end, else nframes - 1. The record: src_lo =
+ *    C_first, src_hi = C_last + c_last, plain_lo = D_first, plain_seen = D_last + d_last, bound = plain_seen - plain_lo — what the table
+ *    promises, not zgpu_plaintext_bound of the bytes —, frames_skipped = first, frames_taken = last - first + 1 (table entries, zero-size ones
+ *    included), nblocks = 0, flags 0. No first (the range lies behind the plaintext): flags bit 2, src_lo = src_hi = C_n, plain_lo = plain_seen
+ *    = D_n, frames_skipped = nframes, frames_taken = 0, and the decode call answers status 0, written 0. For an entry whose frames all declare
+ *    their true size this selects the bytes zgpu_frames_seek_device selects.
+ *  - A table that is not usable: status = ZGPU_E_SEEK_TABLE, why = ZGPU_SEEKTAB_*, every other field 0; in the decode call the entry fails with
+ *    that status, is not read further and not written. The checks, in order: the entry is shorter than 17 bytes or does not end in the seekable
+ *    magic (NONE); reserved descriptor bits (RESERVED_BITS); more than 0x8000000 frames, or a table larger than the entry (TOO_LARGE); no
+ *    skippable magic or another Frame_Size where the table frame must begin (BAD_FRAME); compressed sizes that lead past the table frame's begin
+ *    (PAST_TABLE). The wave reads bytes of the table frame only, nothing in front of it and nothing at or behind lens[i]: an entry may end flush
+ *    with its allocation, and the table may begin at any alignment.
+ *  - A range with anchor_src != 0 or anchor_plain != 0 gets ZGPU_E_BAD_ARG in its record: the table is the index, there is nothing to anchor.
+ *  - The decode call decodes (src + src_lo, src_hi - src_lo) as zgpu_decode_ranges_device_src decodes its selections — walk, submits cut by the
+ *    walk's bound, gather, decode, hash, clipped scatter, entries that go alone — and results[i] means the same, with one more check: an entry
+ *    whose taken frames decode to another total than the table promises (plain_seen - plain_lo) fails with ZGPU_E_CONTENT_SIZE_MISMATCH, in
+ *    the rank that verdict has (behind a decode or walk error, in front of TARGET_TOO_SMALL and the checksum verdict), in a shared submit and
+ *    alone. The check is on the entry's total: two lies that cancel out go unseen (one frame yields 10 bytes fewer than its table entry says
+ *    and the next 10 more). A frame that declares a Frame_Content_Size is still held to it, per frame.
+ *  - A false table is a status, never a fault: compressed sizes that put src_lo inside a frame give what zgpu_decode_all reports for those
+ *    bytes, and every access stays inside the entry. Frames in front of the range are not decoded, so a false size in their table entries
+ *    shifts the coordinates silently.
+ *  - Out of scope: the table's own Checksum fields are not read or verified (ZGPU_DEVICE_VERIFY acts on frames that carry a Content_Checksum,
+ *    as in the other calls).
+ *  - Everything else carries over from zgpu_decode_ranges_device_src: isolation and order independence, no byte of a failed entry and no byte at
+ *    or behind dst + written is written, the pointer checks before any launch, streams synchronised on return, and the same diagnostics
+ *    (zgpu_debug_ranges_stats, zgpu_debug_frames_submits, _device_stats, _device_src_stats, _dict_stats). */
+enum {                                /* zgpu_seek.why of an entry with status ZGPU_E_SEEK_TABLE */
+  ZGPU_SEEKTAB_NONE = 16,
+  ZGPU_SEEKTAB_RESERVED_BITS = 17,
+  ZGPU_SEEKTAB_TOO_LARGE = 18,
+  ZGPU_SEEKTAB_BAD_FRAME = 19,
+  ZGPU_SEEKTAB_PAST_TABLE = 20
+};
+int zgpu_frames_seek_table_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out);
+int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts_or_null,
+                                             zgpu_range_result* results);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

@@ -470,6 +470,29 @@ int Engine::seek_pass(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, uint64
   return ZG_OK;
 }
 
+int Engine::seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats) {
+  Engine* eng = this;
+  if (!n) return ZG_OK;
+  ZG_HIP(hipSetDevice(device_));
+  hipStream_t s = stream_;
+  IndexTmp t;
+  int st;
+  if ((st = t.lanes.reserve((size_t)n * sizeof(zgt::Lane))) || (st = t.ents.reserve((size_t)n * sizeof(zgk::Seek)))) return st;
+  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
+  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes, (size_t)n * sizeof(zgt::Lane), hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
+  ZG_HIP(hipEventRecord(t.ev[0], s));
+  zg_launch_seektab(t.lanes.as<zgt::Lane>(), n, t.ents.as<zgk::Seek>(), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(t.ev[1], s));
+  ZG_HIP(hipMemcpyAsync(out, t.ents.p, (size_t)n * sizeof(zgk::Seek), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgk::Seek);
+  return ZG_OK;
+}
+
 int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
                                    std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts) {
   Batch* b = new Batch();

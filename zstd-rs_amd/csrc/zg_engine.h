@@ -251,6 +251,9 @@ class Engine {
   // (zg_seek.h) over all n lanes, out[i] = lane i's record. A lane of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
   // events), bytes downloaded (64 per lane).
   int seek_pass(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
+  // The same from the seekable format's seek table at each entry's end (zgpu_frames_seek_table_device / zgpu_decode_ranges_seek_table_device_src):
+  // ONE zg_k_seektab launch (zg_seektab.h), a wave per entry. stats as seek_pass.
+  int seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes

@@ -117,7 +117,8 @@ struct Call {
   // device sources (zgpu_decode_frames_device_src): srcs[i] is device memory; what was found out about every entry before the first submit
   const Engine::Skeleton* sk = nullptr;            //   the records zg_k_walk brought back
   const Engine::DevEntry* dev = nullptr;           //   the entries as the engine takes them (a refused entry: length 0)
-  const uint8_t* refused = nullptr;                //   entries whose source or destination failed the pointer check
+  const uint8_t* refused = nullptr;                //   entries whose source or destination failed the pointer check (1), or the status (> 1) of
+                                                   //   an entry that is refused for another reason (ZGPU_E_SEEK_TABLE)
   const uint64_t* bound = nullptr;                 //   plaintext_bound of every entry, from its records
   uint64_t* sstats = nullptr;                      //   zgpu_ctx::frames_device_src_stats
   const DictLookup* dicts = nullptr;               // shared dictionaries (zgpu_set_frames_shared_dicts): what the walks resolve ids with; else nullptr
@@ -125,6 +126,7 @@ struct Call {
   // only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
   struct Clip { uint64_t skip, len, declared; };
   const Clip* clip = nullptr;
+  bool promise = false;                            //   (zgpu_decode_ranges_seek_table_device_src) declared is the seek table's promise: it always holds
   uint64_t* rstats = nullptr;                      //   zgpu_ctx::ranges_stats
   uint64_t alone_written = 0;                      //   bytes the entries decoded alone brought to their destinations
   // what of `bytes` decoded bytes of entry i its destination gets
@@ -234,6 +236,7 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       if (has_dict[j] && !dev && !b->info[f].host_status && k.clipped(i, bytes) > k.caps[i]) small = true;
       if (k.clip && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
     }
+    if (k.promise && bytes != k.clip[i].declared) lied = true;   // (the selection yields another length than its seek table says)
     if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[4] += has_dict[j]; continue; }
     if (k.rstats) { k.rstats[5] += ff[j + 1] - ff[j]; k.rstats[6] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
     // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
@@ -474,7 +477,8 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   // that yields more than it declares can overflow it.
   if (k.clip && !st && d.r.status == ZGPU_E_TARGET_TOO_SMALL) { memset(&d, 0, sizeof d); d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH; }
   if (k.clip && !st && !d.r.status &&
-      (summed ? size_lies != 0 : k.clip[i].declared != UINT64_MAX && d.r.written != k.clip[i].declared)) {
+      ((summed ? size_lies != 0 : k.clip[i].declared != UINT64_MAX && d.r.written != k.clip[i].declared) ||
+       (k.promise && d.r.written != k.clip[i].declared))) {
     memset(&d, 0, sizeof d);
     d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH;
   }
@@ -548,7 +552,7 @@ int decode_entries(Call& k, uint32_t n) {
       bool bad = (!k.srcs[i] && k.lens[i]) || (!k.dsts[i] && k.caps[i]);   // (what zgpu_decode_all returns)
       if (k.sk) bad = k.refused[i] != 0;                                   // (device sources: checked before the walk)
       else if (!bad && k.dres && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
-      if (bad) { k.result(i).status = ZGPU_E_BAD_ARG; continue; }
+      if (bad) { k.result(i).status = k.sk && k.refused[i] > 1 ? k.refused[i] : ZGPU_E_BAD_ARG; continue; }   // (refused[i] > 1: the status itself)
       bound = k.sk ? k.bound[i] : plaintext_bound(k.srcs[i], k.lens[i], k.dicts);   // (with its dictionary frames' gaps)
     }
     // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
@@ -813,14 +817,19 @@ static_assert(sizeof(zgpu_range) == 32 && sizeof(zgpu_seek) == sizeof(zgk::Seek)
               "include/zgpu.h");
 static_assert(offsetof(zgpu_seek, plain_seen) == offsetof(zgk::Seek, plain_seen) && offsetof(zgpu_seek, status) == offsetof(zgk::Seek, status) &&
               offsetof(zgpu_seek, flags) == offsetof(zgk::Seek, flags) && ZGPU_E_BAD_ARG == zgk::kBadArg, "zgk::Seek is zgpu_seek");
+static_assert(ZGPU_E_SEEK_TABLE == zgt::kSeekTable && ZGPU_SEEKTAB_NONE == zgt::kNone && ZGPU_SEEKTAB_RESERVED_BITS == zgt::kReservedBits &&
+              ZGPU_SEEKTAB_TOO_LARGE == zgt::kTooLarge && ZGPU_SEEKTAB_BAD_FRAME == zgt::kBadFrame && ZGPU_SEEKTAB_PAST_TABLE == zgt::kPastTable,
+              "zg_seektab.h");
 namespace {
 // Both calls up to the records: every pointer checked, ONE zg_k_seek launch over all n lanes (a refused entry and a range of length 0 have
-// length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations.
+// length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations. table: the selection
+// comes from the seek table at the entry's end (ONE zg_k_seektab launch, a wave per entry); an anchored range is refused, the table is the index.
 int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* dsts, const size_t* caps,
-                std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+                std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused, bool table) {
   for (uint64_t& x : c->ranges_stats) x = 0;
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  std::vector<zgk::Lane> lanes(n);
+  std::vector<zgk::Lane> lanes(table ? 0 : n);
+  std::vector<zgt::Lane> waves(table ? n : 0);
   out->assign(n, zgk::Seek{});
   refused->assign(n, 0);
   std::vector<DevRange> known;
@@ -828,20 +837,21 @@ int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32
     const zgpu_range& g = ranges[i];
     bool bad = false;
     if (g.len) {
-      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]);
+      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]) || (table && (g.anchor_src || g.anchor_plain));
       if (!bad && lens[i]) bad = !check_device_range(c->eng->device(), srcs[i], lens[i], known);
       if (!bad && dsts && caps[i]) bad = !check_device_range(c->eng->device(), dsts[i], caps[i], known);
     }
     (*refused)[i] = bad;
-    lanes[i] = zgk::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
+    if (table) waves[i] = zgt::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len};
+    else lanes[i] = zgk::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
   }
-  int st = c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats);
+  int st = table ? c->eng->seektab_pass(waves.data(), n, out->data(), c->ranges_stats) : c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats);
   if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
   if (st) return st;
   for (uint32_t i = 0; i < n; i++) {
     zgk::Seek& s = (*out)[i];
     if ((*refused)[i]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
-    if (s.src_lo > s.src_hi || s.src_hi > lens[i] || (s.status && s.status != ZGPU_E_BAD_ARG)) {   // (never)
+    if (s.src_lo > s.src_hi || s.src_hi > lens[i] || (s.status && s.status != (table ? (uint32_t)ZGPU_E_SEEK_TABLE : (uint32_t)ZGPU_E_BAD_ARG))) {   // (never)
       c->eng->last_error = "zgpu_frames_seek_device: a record that leaves its entry";
       return ZGPU_E_INTERNAL;
     }
@@ -855,7 +865,16 @@ extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_sr
   if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
   std::vector<zgk::Seek> recs;
   std::vector<uint8_t> refused;
-  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused);
+  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, false);
+  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
+  return st;
+}
+extern "C" int zgpu_frames_seek_table_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, true);
   for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
   return st;
 }
@@ -863,8 +882,12 @@ extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_sr
 // The selections become the entries of zgpu_decode_frames_device_src's machinery: (src + src_lo, src_hi - src_lo) is walked, cut into submits,
 // gathered, decoded and hashed as any entry is, and only the verdict (the size check), the scatter list (clipped) and the entries that go
 // alone (the selection downloaded, the clipped bytes uploaded) know of the range.
-extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
-                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results) {
+// table (zgpu_decode_ranges_seek_table_device_src): the selections are zg_k_seektab's. Three things differ: the seek's bound is the table's
+// promise and is not compared with the walk's header bound; Clip::declared is that promise, and an entry whose decoded total differs from it
+// fails with ContentSizeMismatch (Call::promise); an entry whose table is not usable is refused with ZGPU_E_SEEK_TABLE, unread and unwritten.
+namespace {
+int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* device_dsts,
+                  const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results, bool table) {
   if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
   if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
   for (uint64_t& x : c->frames_device_stats) x = 0;
@@ -874,7 +897,7 @@ extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* dev
   for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
   std::vector<zgk::Seek> recs;
   std::vector<uint8_t> refused;
-  int st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &refused);
+  int st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &refused, table);
   if (st) return st;
   std::vector<const uint8_t*> srcs(n);
   std::vector<size_t> sub(n);
@@ -884,13 +907,13 @@ extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* dev
   std::vector<zgpu_device_entry_result> dres(n);
   for (uint32_t i = 0; i < n; i++) {
     const zgk::Seek& s = recs[i];
-    if (s.status) refused[i] = 1;                                  // (an anchor behind the entry or behind begin)
+    if (s.status) refused[i] = (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1);   // (an anchor behind the entry or behind begin; no usable table)
     const bool none = refused[i] || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
     srcs[i] = (const uint8_t*)device_srcs[i] + (none ? 0 : s.src_lo);
     sub[i] = none ? 0 : (size_t)(s.src_hi - s.src_lo);
     dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
     const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
-    clip[i] = Call::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, closed && !none ? s.plain_seen - s.plain_lo : UINT64_MAX};
+    clip[i] = Call::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX};   // (table: an entry of which nothing is taken promises nothing)
   }
   Call k{c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
   k.dres = dres.data();
@@ -900,6 +923,7 @@ extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* dev
   k.stats = c->frames_device_stats;
   k.sstats = c->frames_device_src_stats;
   k.clip = clip.data();
+  k.promise = table;
   k.rstats = c->ranges_stats;
   const DictLookup lookup{shared_find, c};
   if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
@@ -909,7 +933,7 @@ extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* dev
     bool consistent = true;
     bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent, k.dicts);
     // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number)
-    if (!consistent || (!k.dicts && sub[i] && bound[i] != recs[i].bound)) {
+    if (!consistent || (!table && !k.dicts && sub[i] && bound[i] != recs[i].bound)) {
       c->eng->last_error = "zgpu_decode_ranges_device_src: a source changed between the seek and the walk";
       st = ZGPU_E_INTERNAL;
     }
@@ -927,6 +951,17 @@ extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* dev
     memcpy(&results[i].seek, &recs[i], sizeof results[i].seek);
   }
   return st;
+}
+}  // namespace
+
+extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results) {
+  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, false);
+}
+extern "C" int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                        const zgpu_range* ranges, void* const* device_dsts, const size_t* caps,
+                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
+  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, true);
 }
 extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
   if (!c || !out) return 0;

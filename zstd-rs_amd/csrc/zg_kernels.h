@@ -8,6 +8,7 @@
 #include "zg_walk.h"
 #include "zg_index.h"
 #include "zg_seek.h"
+#include "zg_seektab.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -71,3 +72,6 @@ void zg_launch_index(const zgw::Lane* lanes, uint32_t n, zgi::Entry* entries, zg
 // zg_k_seek (zg_seek.h): one lane per entry selects the whole frames that hold a plaintext range of the entry, from frame and block headers alone;
 // out[i] = the record of lane i. ONE launch for all n entries
 void zg_launch_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s);
+// zg_k_seektab (zg_seektab.h): one wave per entry answers the same from the seekable format's seek table at the entry's end; one 64-thread
+// workgroup per entry, out[i] = entry i's record
+void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s);

@@ -1914,6 +1914,31 @@ void zg_launch_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, hipStrea
   hipLaunchKernelGGL(zg_k_seek, dim3((n + zgk::kThreads - 1) / zgk::kThreads), dim3(zgk::kThreads), 0, s, lanes, n, out);
 }
 
+// The same question answered from the seek table of zstd's seekable format at the entry's end, one WAVE per entry (zg_seektab.h has the format,
+// the rule, the record and the ISA notes; the body is written against the zx_* primitives). The host checked every [src, src + len) against
+// the runtime's allocations; a wave reads nothing outside the table frame and lane 0 writes the entry's 64-byte record only.
+#include "zg_seektab.h"
+struct ZgTabRead {
+  uint64_t base;
+  __device__ __forceinline__ uint32_t ld1(uint64_t off) const { return *(const __attribute__((address_space(1))) uint8_t*)(base + off); }
+  __device__ __forceinline__ uint32_t ld4(uint64_t off) const { return ((const __attribute__((address_space(1))) zg_u32u*)(base + off))->v; }
+  __device__ __forceinline__ void ld8(uint64_t off, uint32_t* a, uint32_t* b) const {
+    const uint64_t v = ((const __attribute__((address_space(1))) zg_u64u*)(base + off))->v;
+    *a = (uint32_t)v; *b = (uint32_t)(v >> 32);
+  }
+};
+__global__ void __launch_bounds__(zgt::kThreads) zg_k_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const zgt::Lane l = lanes[i];
+  const zgk::Seek o = zgt::seektab_entry(ZgTabRead{l.src}, l.len, l.begin, l.rlen);
+  if (threadIdx.x == 0) zgt::seektab_store(&out[i], o);
+}
+void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_seektab, dim3(n), dim3(zgt::kThreads), 0, s, lanes, n, out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

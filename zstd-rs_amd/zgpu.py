@@ -23,6 +23,8 @@ E_TARGET_TOO_SMALL = 12
 E_FAILED_SKIP_FRAME = 13
 E_RESERVED_BLOCK, E_BLOCK_SIZE_TOO_LARGE = 20, 21
 E_CHECKSUM_MISMATCH = 70    # decode_frames_device / decode_frames_device_src with verify=True only (no counterpart in the reference)
+E_SEEK_TABLE = 72              # the seek-table calls only: the entry does not end in a usable seek table (Seek.why: SEEKTAB_*)
+SEEKTAB_NONE, SEEKTAB_RESERVED_BITS, SEEKTAB_TOO_LARGE, SEEKTAB_BAD_FRAME, SEEKTAB_PAST_TABLE = 16, 17, 18, 19, 20
 E_CONTENT_SIZE_MISMATCH = 71   # decode_ranges_device_src only: a taken frame decoded to another length than it declares (no counterpart in the reference)
 E_UNSUPPORTED = 80
 E_HIP = 92
@@ -181,6 +183,27 @@ def anchor_before(frames, offset, entry=0):
     return best
 
 
+def seek_table_frame(csizes, dsizes, checksums=None):
+    """The seek table of zstd's seekable format for frames of csizes[k] compressed and dsizes[k] decompressed bytes (a skippable frame is
+    entered with dsize 0): the skippable frame that, appended behind those frames, makes an entry seekable for
+    Context.decode_ranges_seek_table_device_src. checksums[k]: the low 32 bits of the XXH64 (seed 0) of frame k's plaintext; None: the table
+    carries none. Host only."""
+    import struct
+    n = len(csizes)
+    if len(dsizes) != n or (checksums is not None and len(checksums) != n):
+        raise ValueError("seek_table_frame: one size pair (and one checksum) per frame")
+    if n > 0x8000000:
+        raise ValueError("seek_table_frame: more than 0x8000000 frames")
+    es = 8 if checksums is None else 12
+    out = [struct.pack("<II", 0x184D2A5E, n * es + 9)]
+    for k in range(n):
+        out.append(struct.pack("<II", int(csizes[k]), int(dsizes[k])))
+        if checksums is not None:
+            out.append(struct.pack("<I", int(checksums[k]) & 0xFFFFFFFF))
+    out.append(struct.pack("<IBI", n, 0 if checksums is None else 0x80, 0x8F92EAB1))
+    return b"".join(out)
+
+
 def plaintext_bound(buf):
     """zgpu_plaintext_bound: an upper bound of the plaintext of concatenated frames from frame and block headers only (a frame's declared
     content size when smaller; a compressed block counts 128 KiB); the walk stops where a header cannot be read. Decode_frames' default
@@ -222,6 +245,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
@@ -304,6 +328,8 @@ def _declare(L):
     L.zgpu_frames_seek_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(RangeC), P(SeekC)]
     L.zgpu_decode_ranges_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(RangeC), P(vp), P(sz), P(DeviceOptsC), P(RangeResultC)]
     L.zgpu_debug_ranges_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_frames_seek_table_device.argtypes = L.zgpu_frames_seek_device.argtypes
+    L.zgpu_decode_ranges_seek_table_device_src.argtypes = L.zgpu_decode_ranges_device_src.argtypes
     L.zgpu_set_frames_shared_dicts.argtypes = [vp, C.c_int]
     L.zgpu_set_frames_shared_dicts.restype = None
     L.zgpu_frames_shared_dicts.argtypes = [vp]
@@ -731,25 +757,60 @@ class Context:
         dres = (DeviceEntryResultC * max(n, 1))(*[res[i].d for i in range(n)])
         return self._device_results(dres, n), [Seek(res[i].seek) for i in range(n)]
 
+    def frames_seek_table_device(self, src_ptrs, lens, ranges):
+        """zgpu_frames_seek_table_device: frames_seek_device answered from the seekable format's seek table at each entry's end (seek_table_frame
+        writes one), one wave per entry: no frame or block header is read, frames need not declare a size. Returns one Seek per entry, in the
+        table's coordinates; an entry without a usable table has status E_SEEK_TABLE and why SEEKTAB_*."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        rg = self._ranges(ranges, None, n)
+        out = (SeekC * max(n, 1))()
+        st = self.L.zgpu_frames_seek_table_device(self.h, srcs, lena, n, rg, out)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        return [Seek(out[i]) for i in range(n)]
+
+    def decode_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False):
+        """zgpu_decode_ranges_seek_table_device_src: decode_ranges_device_src with the selection taken from each entry's seek table. Only the
+        frames the table names for the range are decoded, whether or not they declare a size. Returns (results, seeks) as
+        decode_ranges_device_src does; E_SEEK_TABLE: no usable table, E_CONTENT_SIZE_MISMATCH: the taken frames decoded to another total than
+        the table promises."""
+        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        if len(dst_ptrs) != n or len(caps) != n:
+            raise ValueError("decode_ranges_seek_table_device_src: one destination and one capacity per source")
+        rg = self._ranges(ranges, None, n)
+        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        for i in range(n):
+            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
+        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
+        res = (RangeResultC * max(n, 1))()
+        st = self.L.zgpu_decode_ranges_seek_table_device_src(self.h, srcs, lena, n, rg, dsts, capa, C.byref(opts), res)
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
+        dres = (DeviceEntryResultC * max(n, 1))(*[res[i].d for i in range(n)])
+        return self._device_results(dres, n), [Seek(res[i].seek) for i in range(n)]
+
     def ranges_stats(self):
-        """the last frames_seek_device / decode_ranges_device_src call (zgpu_debug_ranges_stats)"""
+        """the last frames_seek_device / decode_ranges_device_src call or seek-table call (zgpu_debug_ranges_stats)"""
         a = (C.c_uint64 * 8)()
         k = self.L.zgpu_debug_ranges_stats(self.h, a, 8)
         keys = ["seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
                 "plaintext_decoded", "bytes_written"]
         return dict(zip(keys[:k], [int(x) for x in a][:k]))
 
-    def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False):
+    def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False, seek_table=False):
         """decode_ranges_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
         compressed bytes, ranges[i] = (begin, len) the plaintext bytes wanted of it. The bytes go to ONE new torch.uint8 tensor, every entry's
         slot 256-byte aligned and sized by min(len, seek.bound) — a frames_seek_device call of its own finds the bound, so no byte of the
         input crosses to the host. Returns (tensors, results, seeks): tensors[i] is a view of entry i's slot cut to `written` bytes (empty
-        unless status == 0). Same single-runtime rule as decode_tensors. torch is imported here, not by `import zgpu`."""
+        unless status == 0). Same single-runtime rule as decode_tensors. torch is imported here, not by `import zgpu`.
+        seek_table=True: the selections come from the entries' seek tables (decode_ranges_seek_table_device_src; anchors must be None)."""
         import torch
         self._tensor_check(tensors, "decode_tensor_ranges")
+        if seek_table and anchors is not None:
+            raise ValueError("decode_tensor_ranges: a seek table is the index, there is nothing to anchor")
         dev = torch.device("cuda", self.device)
         ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
-        seeks = self.frames_seek_device(ptrs, lens, ranges, anchors)
+        seeks = self.frames_seek_table_device(ptrs, lens, ranges) if seek_table else self.frames_seek_device(ptrs, lens, ranges, anchors)
         caps = [min(int(r[1]), s.bound) for r, s in zip(ranges, seeks)]
         offs, total = [], 0
         for c in caps:
@@ -759,8 +820,12 @@ class Context:
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
         base = buf.data_ptr()
-        res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, anchors=anchors, hash_max=hash_max,
-                                                   no_hash=no_hash, verify=verify)
+        if seek_table:
+            res, seeks = self.decode_ranges_seek_table_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, hash_max=hash_max,
+                                                                  no_hash=no_hash, verify=verify)
+        else:
+            res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, anchors=anchors, hash_max=hash_max,
+                                                       no_hash=no_hash, verify=verify)
         return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res, seeks
 
     def _tensor_check(self, tensors, what):
