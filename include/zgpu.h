@@ -645,7 +645,16 @@ uint64_t zgpu_frame_blocks_decoded(const zgpu_frame*);   /* frame_decoder.rs:297
  *   - nothing behind the frame's last block (+ checksum) is taken from the source.
  * What differs, because blocks are decoded before the reader asks: the source is consumed earlier (by whole runs), and
  * zgpu_decoder_blocks_decoded / zgpu_decoder_bytes_read_from_source of the decoder behind the stream count what has been decoded, which
- * runs ahead of what read() has returned. zgpu_stream_opts.read_ahead_bytes = 1 switches all of that off (the reference's schedule). */
+ * runs ahead of what read() has returned. zgpu_stream_opts.read_ahead_bytes = 1 switches all of that off (the reference's schedule).
+ * Engine errors (ZGPU_E_HIP, ZGPU_E_NOMEM, ZGPU_E_INTERNAL from the engine — not a block's verdict, which stays the reference's) end the
+ * stream: the first one is kept, the read() that meets it returns it with *n == 0, and so does every later read(), without touching the
+ * engine or the source again. Bytes that were decoded and had reached the host before it are still handed out by the reads they can serve
+ * in full, so every byte a read() returns is the frame's plaintext at its position and the calculated checksum is the XXH64 of exactly the
+ * bytes returned; a read() that fails returns none, whatever it had written to dst. The stream's threads are gone and its ring is released
+ * when that read() returns; zgpu_streaming_destroy is all that is left to do. Two things are NOT errors and stay invisible: when the worker
+ * thread's side cannot be set up — the engine refuses (no device memory for the larger window) or there is no pinned memory for the ring or a
+ * staging buffer — the stream goes on decoding on the caller's thread. Host memory that cannot be got inside a read() (ZGPU_E_NOMEM
+ * from the library's own buffers) ends the stream in the same way. */
 typedef struct zgpu_streaming zgpu_streaming;
 typedef size_t (*zgpu_read_fn)(void* user, uint8_t* dst, size_t n);   /* io::Read::read of the source: 0 = end of input */
 typedef struct {
@@ -667,12 +676,17 @@ int zgpu_streaming_create_slice(zgpu_ctx*, const uint8_t* src, size_t len, const
 size_t zgpu_streaming_source_position(const zgpu_streaming*);   /* slice sources: bytes of src taken so far (runs ahead of the reader) */
 void zgpu_streaming_destroy(zgpu_streaming*);
 /* get_ref / get_mut (:66-85): the decoder behind the stream — its accessors (is_finished, the checksums, the counters), can_collect / collect /
- * read (they hand out what the stream has buffered). decode_blocks / decode_from_to on it return ZGPU_E_BAD_ARG: the stream feeds it. */
+ * read (they hand out what the stream has buffered). decode_blocks / decode_from_to on it return ZGPU_E_BAD_ARG: the stream feeds it.
+ * collect / read return byte counts and cannot report an error: behind a stream that an engine error has ended they return 0,
+ * can_collect is 0 and is_finished stays 0 — zgpu_decoder_stream_error tells that state from a frame that merely has nothing buffered. */
 zgpu_decoder* zgpu_streaming_decoder(zgpu_streaming*);
-/* read (:119-155): *n = bytes written to dst (0 = end of frame) */
+int zgpu_decoder_stream_error(const zgpu_decoder*);   /* the engine error that ended the stream this decoder is behind; 0: none, or no stream */
+/* read (:119-155): *n = bytes written to dst (0 = end of frame). A nonzero return that is an engine error is final (see above): every
+ * later call returns the same code and *n == 0. */
 int zgpu_streaming_read(zgpu_streaming*, uint8_t* dst, size_t cap, size_t* n);
 /* std::io::copy(&mut decoder, &mut writer) with a buffer of buf_size bytes (the reference's CLI: 8 KiB, cli/src/main.rs:142-144);
- * write == NULL is io::sink(). *total = bytes copied. */
+ * write == NULL is io::sink(). *total = bytes copied: what the writer got before the call ended, also when it returns an error. Behind
+ * an engine error the stream is over; calling again returns the same code and *total == 0. */
 int zgpu_streaming_copy(zgpu_streaming*, size_t buf_size, zgpu_write_fn write, void* user, uint64_t* total);
 /* A stream that used a worker thread leaves its engine (streams, device buffers sized to its runs; at most two per device) and its pinned ring /
  * staging memory (at most 3 GiB) to the next stream of the process: allocating them is what a short-lived stream would otherwise spend its time on.

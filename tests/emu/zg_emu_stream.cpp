@@ -3,9 +3,12 @@
 // stand-in for the engine. The stand-in knows the frame's plaintext and, per block, how many bytes it yields, whether it fails and
 // whether it "sets an offset beyond the window" (tests choose these freely): a run reports what the engine would report for those
 // blocks, and checks that the bytes it is handed ARE those blocks. Not part of the product, nothing here is a decoder.
+// It can also FAIL: zgemu_stream_fail makes the nth call of one kind return an engine error without doing its work (a fetch queues no
+// copy, a fetch_wait copies nothing, a host_alloc returns null), and zgemu_stream_stats2 tells what the core did about it.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <vector>
 #include "../../zstd-rs_amd/csrc/zg_stream.h"
 
@@ -25,9 +28,28 @@ struct Table {
   uint32_t checksum = 0;
 };
 
+enum FaultKind { F_PREPARE = 0, F_LAUNCH, F_WAIT, F_RUN, F_COMMIT, F_FETCH, F_FETCH_WAIT, F_REBASE, F_PIPE_BEGIN, F_HOST_ALLOC, F_KINDS };
+std::atomic<int64_t> g_live_allocs{0};   // host_alloc without its host_free, over all streams of the process
+
 class TableBackend : public StreamBackend {
  public:
   Table* t;
+  // the one fault of this stream: the nth call (1-based) of fault_kind returns fault_code. Calls come from the reader's thread and from
+  // the worker's, so everything here is atomic.
+  int fault_kind = -1;
+  uint64_t fault_nth = 0;
+  int fault_code = 0;
+  std::atomic<uint64_t> calls[F_KINDS] = {};
+  std::atomic<bool> fired{false};
+  std::atomic<uint64_t> calls_after{0};  // calls of the ten kinds that came after the fault had been returned
+  std::atomic<int64_t> live{0};
+  bool hit(int kind) {
+    const uint64_t n = calls[kind].fetch_add(1, std::memory_order_relaxed) + 1;
+    if (fired.load(std::memory_order_acquire)) { calls_after.fetch_add(1, std::memory_order_relaxed); return false; }
+    if (kind != fault_kind || n != fault_nth) return false;
+    fired.store(true, std::memory_order_release);
+    return true;
+  }
   uint32_t next = 0;                   // first block that is not committed yet
   uint64_t produced = 0;
   // the run in flight
@@ -48,13 +70,19 @@ class TableBackend : public StreamBackend {
   const uint8_t* p_src = nullptr; size_t p_len = 0; uint32_t p_nblocks = 0; bool have_prep = false;
   StreamRun cur;
   bool launched = false;
+  int run(const uint8_t* src, size_t len, uint32_t nblocks, uint64_t keep, StreamRun* out) override {
+    if (hit(F_RUN)) return fault_code;
+    return StreamBackend::run(src, len, nblocks, keep, out);
+  }
   int prepare(const uint8_t* src, size_t len, uint32_t nblocks) override {
+    if (hit(F_PREPARE)) return fault_code;
     if (have_prep) obj(7);
     p_src = src; p_len = len; p_nblocks = nblocks; have_prep = true;
     return ZG_OK;
   }
   void drop_prepared() override { have_prep = false; }
   int launch(uint64_t keep) override {
+    if (hit(F_LAUNCH)) return fault_code;
     if (!have_prep) { obj(8); return ZG_INTERNAL; }
     have_prep = false;
     const int e = run_now(p_src, p_len, p_nblocks, keep, &cur);
@@ -62,6 +90,7 @@ class TableBackend : public StreamBackend {
     return e;
   }
   int wait(StreamRun* o) override {
+    if (hit(F_WAIT)) return fault_code;
     if (!launched) { obj(9); return ZG_INTERNAL; }
     launched = false;
     *o = cur;
@@ -93,6 +122,7 @@ class TableBackend : public StreamBackend {
   }
 
   int commit() override {
+    if (hit(F_COMMIT)) return fault_code;
     if (!have_run) { obj(5); return ZG_INTERNAL; }
     have_run = false; ncommits++;
     committed_off = t->out_off[next];
@@ -100,21 +130,40 @@ class TableBackend : public StreamBackend {
     return ZG_OK;
   }
   void discard() override { if (have_run) ndiscards++; have_run = false; }
-  int fetch(uint8_t* dst, uint64_t off, uint64_t n) override { pend.push_back(Pending{dst, off, n}); return ZG_OK; }   // lands at fetch_wait, like a DMA
+  int fetch(uint8_t* dst, uint64_t off, uint64_t n) override {           // lands at fetch_wait, like a DMA
+    if (hit(F_FETCH)) return fault_code;
+    pend.push_back(Pending{dst, off, n});
+    return ZG_OK;
+  }
   int fetch_wait() override {
+    if (hit(F_FETCH_WAIT)) return fault_code;
     for (const Pending& p : pend) memcpy(p.dst, t->plain.data() + committed_off + p.off, p.n);
     pend.clear();
     return ZG_OK;
   }
   int rebase(const uint8_t* held, uint64_t n) override {
+    if (hit(F_REBASE)) return fault_code;
     nrebase++; rebase_bytes = n;
     if (n > produced || memcmp(held, t->plain.data() + produced - n, n) != 0) obj(6);
     return ZG_OK;
   }
-  int pipe_begin(uint64_t) override { pipe_begins++; in_pipe = true; return ZG_OK; }
-  void pipe_end() override { in_pipe = false; }
-  void* host_alloc(size_t n) override { return malloc(n); }
-  void host_free(void* p, size_t) override { free(p); }
+  int pipe_begin(uint64_t) override {
+    if (hit(F_PIPE_BEGIN)) return fault_code;
+    pipe_begins++; in_pipe = true; pipe_ends_owed++;
+    return ZG_OK;
+  }
+  void pipe_end() override { in_pipe = false; pipe_ends_owed = 0; }
+  uint64_t pipe_ends_owed = 0;         // a pipe_begin that succeeded and has not seen its pipe_end
+  void* host_alloc(size_t n) override {
+    if (hit(F_HOST_ALLOC)) return nullptr;
+    void* p = malloc(n);
+    if (p) { live.fetch_add(1, std::memory_order_relaxed); g_live_allocs.fetch_add(1, std::memory_order_relaxed); }
+    return p;
+  }
+  void host_free(void* p, size_t) override {
+    if (p) { live.fetch_sub(1, std::memory_order_relaxed); g_live_allocs.fetch_sub(1, std::memory_order_relaxed); }
+    free(p);
+  }
 };
 
 struct Harness {
@@ -124,11 +173,16 @@ struct Harness {
   // callback source
   size_t cb_pos = 0, cb_chunk = 0;
   uint64_t cb_calls = 0;
+  bool err_returned = false;           // a read() has returned the injected code to the caller
+  uint64_t cb_after = 0;               // source callbacks behind that
+  uint64_t cb_after_fault = 0;         // source callbacks after the backend had returned the fault (the worker's faults race with the reader's pulls)
 };
 
 size_t cb_read(void* user, uint8_t* dst, size_t n) {
   Harness* h = (Harness*)user;
   h->cb_calls++;
+  if (h->err_returned) h->cb_after++;
+  if (h->be.fired.load(std::memory_order_acquire)) h->cb_after_fault++;
   size_t k = h->t.src.size() - h->cb_pos;
   if (k > n) k = n;
   if (h->cb_chunk && k > h->cb_chunk) k = h->cb_chunk;                  // a source that returns short reads
@@ -176,7 +230,36 @@ void* zgemu_stream_new(const uint8_t* src, size_t src_len, const uint8_t* plain,
   return h;
 }
 void zgemu_stream_free(void* hp) { Harness* h = (Harness*)hp; if (!h) return; delete h->core; delete h; }
-int zgemu_stream_read(void* hp, uint8_t* dst, size_t cap, size_t* n) { return ((Harness*)hp)->core->read(dst, cap, n); }
+int zgemu_stream_read(void* hp, uint8_t* dst, size_t cap, size_t* n) {
+  Harness* h = (Harness*)hp;
+  const int e = h->core->read(dst, cap, n);
+  if (e && h->be.fired.load() && e == h->be.fault_code) h->err_returned = true;
+  return e;
+}
+// One fault per stream, set before the first read: the nth call (1-based) of `kind` — 0 prepare, 1 launch, 2 wait, 3 run (the three in one,
+// as the caller's thread uses them), 4 commit, 5 fetch, 6 fetch_wait, 7 rebase, 8 pipe_begin, 9 host_alloc — returns `code` and does
+// nothing (host_alloc: returns null).
+void zgemu_stream_fail(void* hp, int kind, uint64_t nth, int code) {
+  Harness* h = (Harness*)hp;
+  h->be.fault_kind = kind; h->be.fault_nth = nth; h->be.fault_code = code;
+}
+// out: [0..9] calls per kind (as above) [10] the fault fired [11] calls of these kinds that the backend got after it had returned the fault
+// [12] source callbacks after a read() had returned the fault's code to the caller (the worker meets a fault while the reader may be
+// taking a run from the source: what counts is what happens once the caller knows) [13] host allocations of this stream still live
+// [14] the engine error the core has stored [15] a pipe_begin still waits for its pipe_end [16] source callbacks after the backend had
+// returned the fault (0 whenever the fault was met on the caller's thread). out holds 20 values.
+void zgemu_stream_stats2(void* hp, uint64_t* out) {
+  Harness* h = (Harness*)hp;
+  for (int k = 0; k < F_KINDS; k++) out[k] = h->be.calls[k].load();
+  out[10] = h->be.fired.load() ? 1u : 0u;
+  out[11] = h->be.calls_after.load();
+  out[12] = h->cb_after;
+  out[13] = (uint64_t)h->be.live.load();
+  out[14] = (uint64_t)h->core->error();
+  out[15] = h->be.pipe_ends_owed;
+  out[16] = h->cb_after_fault; out[17] = out[18] = out[19] = 0;
+}
+int64_t zgemu_stream_live_allocs(void) { return g_live_allocs.load(); }   // over all streams, freed ones included: 0 when every host_alloc had its host_free
 uint32_t zgemu_stream_checksum(void* hp) { return ((Harness*)hp)->core->calculated_checksum(); }
 // out: [0] mode [1] runs taken [2] runs dropped [3] backend runs [4] commits [5] discards [6] rebases [7] bytes the source has given
 // [8] things the stand-in objected to (wrong source bytes, a run on top of a run, too little kept) [9] is_finished [10] blocks decoded

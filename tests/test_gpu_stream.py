@@ -297,8 +297,10 @@ def test_decoder_behind_the_stream(ctx):
     for kw in (dict(), dict(pipe_after=1, read_ahead=6 << 20), dict(read_ahead=1)):
         s = zgpu.CStreamingDecoder(ctx, data=z, **kw)
         L, d = s.L, s._dec()
+        assert s.error() == 0
         got = s.read(1 << 20)
         assert got == data[:1 << 20]
+        assert L.zgpu_decoder_stream_error(d) == 0                      # (no engine error: include/zgpu.h at zgpu_streaming_read)
         n = L.zgpu_decoder_can_collect(d)
         buf = C.create_string_buffer(max(n, 1))
         assert L.zgpu_decoder_collect(d, buf, n) == n
@@ -315,6 +317,7 @@ def test_decoder_behind_the_stream(ctx):
                 break
             got += c
         assert got == data and s.get_calculated_checksum() == s.get_checksum_from_data()
+        assert s.error() == 0 and s.is_finished()
         s.close()
     ctx.L.zgpu_release_caches()          # the worker engine and the pinned ring the streams above left behind
     s = zgpu.CStreamingDecoder(ctx, data=z, pipe_after=1, read_ahead=6 << 20)

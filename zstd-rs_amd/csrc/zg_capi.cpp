@@ -576,6 +576,8 @@ int zgpu_decoder_is_finished(const zgpu_decoder* d) {
   if (d->fh.content_checksum()) return d->frame_finished && d->has_checksum;
   return d->frame_finished;
 }
+// behind a stream that an engine error has ended: is_finished 0, can_collect / collect / read 0 — and this tells why (0 otherwise)
+int zgpu_decoder_stream_error(const zgpu_decoder* d) { return (d && d->stream) ? zg_stream_error(d->stream) : 0; }
 size_t zgpu_decoder_can_collect(const zgpu_decoder* d) {
   if (!d->has_state) return 0;
   if (d->stream) return zg_stream_can_collect(d->stream);

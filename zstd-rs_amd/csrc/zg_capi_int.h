@@ -74,6 +74,7 @@ uint64_t zg_stream_bytes_read(const zg::StreamCore* c);
 bool zg_stream_checksum_from_data(const zg::StreamCore* c, uint32_t* out);
 uint32_t zg_stream_calculated_checksum(zg::StreamCore* c);
 uint64_t zg_stream_host_bytes(const zg::StreamCore* c);
+int zg_stream_error(const zg::StreamCore* c);                          // the engine error that ended the stream (0: none)
 size_t zg_stream_take(zg::StreamCore* c, uint8_t* dst, size_t n);   // n <= can_collect: bytes that are buffered already
 
 // (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); sums, if given, collects the

@@ -179,12 +179,12 @@ class GpuStreamBackend : public StreamBackend {
     const int parts = n >= (8u << 20) ? 3 : 1;
     const uint64_t piece = ((n / parts) + 4095) & ~4095ull;
     uint64_t o = 0;
+    fetching_ = true;                   // (before the first piece: when a later one cannot be enqueued, fetch_wait() / pipe_end() still wait for the earlier ones before dst goes back)
     for (int i = 0; i < parts && o < n; i++) {
       const uint64_t k = (i == parts - 1 || n - o < piece) ? n - o : piece;
       if (hipMemcpyAsync(dst + o, src + o, k, hipMemcpyDeviceToHost, ss[i]) != hipSuccess) return ZGPU_E_HIP;
       o += k;
     }
-    fetching_ = true;
     return ZGPU_OK;
   }
   int fetch_wait() override {
@@ -284,6 +284,8 @@ uint64_t zg_stream_bytes_read(const StreamCore* c) { return c->bytes_read_from_s
 bool zg_stream_checksum_from_data(const StreamCore* c, uint32_t* out) { return c->checksum_from_data(out); }
 uint32_t zg_stream_calculated_checksum(StreamCore* c) { return c->calculated_checksum(); }
 uint64_t zg_stream_host_bytes(const StreamCore* c) { return c->host_bytes(); }
+int zg_stream_error(const StreamCore* c) { return c->error(); }
+// (a stream that an engine error ended has nothing collectable, so n is 0 here and nothing is asked of it: zgpu_decoder_stream_error tells)
 size_t zg_stream_take(StreamCore* c, uint8_t* dst, size_t n) { size_t got = 0; return (n && c->read(dst, n, &got) == ZGPU_OK) ? got : 0; }
 
 extern "C" {

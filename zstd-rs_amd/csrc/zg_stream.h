@@ -19,6 +19,11 @@
 // the run is dropped, its good prefix is decoded again on its own, the rest of its source bytes is handed back, and the stream goes on
 // in LOCKSTEP from exactly the state the reference would be in: same bytes, same error, same read() call. (Conforming streams are
 // always clean.)
+// Engine errors: a nonzero return of a StreamBackend call (HIP, memory, internal — not a block's verdict, StreamRun::status) ends the
+// stream. The first one is stored (fail()); the read() that meets it and every read() behind it return it with 0 bytes, without another
+// call to the engine or the source. What had been committed and had landed in the host buffer or the ring before it is still handed out
+// by the reads it can serve in full. Two things are no errors: PIPE that cannot start because the engine refuses its part (pipe_begin)
+// or there is no memory for the ring or a staging buffer — the stream stays INLINE.
 //
 // The engine is behind StreamBackend, so that this file — threads, ring, hand-offs, fallback — runs on the CPU in tests/emu against a
 // table-driven stand-in (tests/test_stream_cpu.py, also under ThreadSanitizer); the product's backend is in zg_stream.cpp.
@@ -64,7 +69,7 @@ class StreamBackend {
   virtual int launch(uint64_t keep) = 0;
   virtual int wait(StreamRun* out) = 0;
   virtual void drop_prepared() = 0;
-  int run(const uint8_t* src, size_t len, uint32_t nblocks, uint64_t keep, StreamRun* out) {
+  virtual int run(const uint8_t* src, size_t len, uint32_t nblocks, uint64_t keep, StreamRun* out) {
     int e = prepare(src, len, nblocks);
     if (!e) e = launch(keep);
     if (!e) e = wait(out);
@@ -328,6 +333,7 @@ class StreamCore {
   uint64_t bytes_read_from_source() const { return header_bytes + src_bytes_.load(std::memory_order_relaxed); }
   bool checksum_from_data(uint32_t* out) const { if (!have_cs_.load(std::memory_order_acquire)) return false; *out = cs_; return true; }
   size_t can_collect() const {
+    if (dead_) return 0;                                                     // (an engine error: nothing is handed out any more)
     const uint64_t a = avail();
     if (is_finished()) return (size_t)a;
     return a > window ? (size_t)(a - window) : 0;
@@ -340,16 +346,31 @@ class StreamCore {
     }
     return (uint32_t)hash_.digest();
   }
+  int error() const { return dead_; }                 // the engine error that ended the stream (0: none)
   Mode mode() const { return mode_; }
   uint64_t runs() const { return runs_; }             // runs decoded ahead and taken (tests)
   uint64_t dropped_runs() const { return dropped_; }  // runs decoded ahead and dropped (tests)
   uint64_t host_bytes() const { return buf_.capacity() + ring_cap_; }
 
   // impl Read for StreamingDecoder (streaming_decoder.rs:119-155)
+  // (memory the host side could not get — a bad_alloc of the host buffer — ends the stream like an engine error: state that an exception
+  // left half-way is never read again)
   int read(uint8_t* dst, size_t cap, size_t* n_out) {
+    try {
+      return read_frame(dst, cap, n_out);
+    } catch (...) {
+      *n_out = 0;
+      return fail(ZG_NOMEM);
+    }
+  }
+
+ private:
+  int read_frame(uint8_t* dst, size_t cap, size_t* n_out) {
     *n_out = 0;
+    if (dead_) return dead_;
     if (is_finished() && avail() == 0) return ZG_OK;                       // :125-130
     size_t done = 0;
+    snap_set_ = false;
     for (;;) {
       if (mode_ == PIPE) {
         bool again = false;
@@ -371,7 +392,6 @@ class StreamCore {
     return ZG_OK;
   }
 
- private:
   StreamBackend* be_;
   StreamOpts o_;
   Mode mode_;
@@ -388,6 +408,22 @@ class StreamCore {
   std::atomic<bool> have_cs_{false};
   uint32_t cs_ = 0;
   std::atomic<uint64_t> blocks_{0}, src_bytes_{0};
+
+  // ---- engine errors. Every exit that an engine error takes ends here, on the reader's thread (the worker reports its own through
+  // P_FAILED, read_pipe brings it here): the threads are joined, the engine gets its pipe_end(), the ring and the staging buffers go
+  // back, and nothing is called any more. A read that had drained pieces into dst (read_pipe, reads larger than a run) returns 0 bytes
+  // like any other: the hash goes back to what it was when that read began, so that it stays the hash of what reads have delivered.
+  int dead_ = 0;
+  Xxh64 snap_;
+  bool snap_set_ = false;
+  int fail(int e) {
+    if (!dead_) {
+      dead_ = e ? e : ZG_INTERNAL;
+      stop_pipe(false);
+      if (snap_set_) hash_ = snap_;
+    }
+    return dead_;
+  }
 
   size_t held_buf() const { return buf_.size() - head_; }
   uint64_t avail() const { return held_buf() + (pub_.load(std::memory_order_acquire) - tail_.load(std::memory_order_relaxed)); }
@@ -433,6 +469,7 @@ class StreamCore {
     buf_.resize(old + n);
     int st = be_->fetch(buf_.data() + old, 0, n);
     if (!st) st = be_->fetch_wait();
+    if (st) buf_.resize(old);                                               // (nothing that was not written counts as decoded)
     return st;
   }
 
@@ -447,9 +484,9 @@ class StreamCore {
     if (st.nblocks) {
       StreamRun r;
       int e = be_->run(st.p, st.len, st.nblocks, held_buf(), &r);
-      if (e) return e;
-      if ((e = be_->commit())) return e;                                     // (a failed run too: what its good blocks produced is there, like the reference's buffer)
-      if ((e = fetch_to_buf(r.out_size))) return e;
+      if (e) return fail(e);
+      if ((e = be_->commit())) return fail(e);                               // (a failed run too: what its good blocks produced is there, like the reference's buffer)
+      if ((e = fetch_to_buf(r.out_size))) return fail(e);
       const size_t good_len = r.good_blocks == st.nblocks ? st.len : stream_prefix_len(st.p, st.len, r.good_blocks);
       account(r, good_len, r.good_blocks);
       if (r.status) { count_failed_header(r.status); return r.status; }
@@ -463,7 +500,7 @@ class StreamCore {
   int step_inline(size_t missing) {
     if (o_.allow_pipe && !last_seen_ && (decoded_ >= o_.pipe_after || (decoded_ == 0 && content_size >= o_.pipe_after))) {
       const int st = start_pipe();
-      if (st == ZG_OK) return ZG_OK;
+      if (st == ZG_OK) return dead_;                                          // (0, unless the fall back behind a thread that could not be started met an engine error)
       o_.allow_pipe = false;                                                  // (no memory for the ring ...: stay inline)
     }
     uint32_t m = (uint32_t)((missing - can_collect() + kMaxBlockSize - 1) / kMaxBlockSize);
@@ -474,9 +511,9 @@ class StreamCore {
     if (st.nblocks == 0) { mode_ = LOCKSTEP; return ZG_OK; }                  // the next block cannot be read whole: the error belongs to the read() that needs it
     StreamRun r;
     int e = be_->run(st.p, st.len, st.nblocks, held_buf(), &r);
-    if (e) return e;
+    if (e) return fail(e);
     if (clean(r, st.nblocks)) {
-      if ((e = be_->commit()) || (e = fetch_to_buf(r.out_size))) return e;
+      if ((e = be_->commit()) || (e = fetch_to_buf(r.out_size))) return fail(e);
       account(r, st.len, st.nblocks);
       runs_++;
       if (st.stop) mode_ = LOCKSTEP;
@@ -485,7 +522,7 @@ class StreamCore {
     be_->discard();
     dropped_++;
     size_t used = 0;
-    if ((e = salvage(st.p, st.len, r, &used, false))) return e;
+    if ((e = salvage(st.p, st.len, r, &used, false))) return fail(e);
     src.unget(st.p + used, st.len - used);
     mode_ = LOCKSTEP;
     return ZG_OK;
@@ -495,6 +532,7 @@ class StreamCore {
 
   // A dropped run: the blocks in front of the one that failed are decoded again as a run of their own (clean by construction unless a
   // far offset hides among them: then nothing is taken). *used = source bytes taken. to_ring: PIPE (worker thread) -> ring, else -> buf_.
+  // A nonzero return is an engine error (the caller's to report: fail() on the reader's thread, P_FAILED on the worker's).
   int salvage(const uint8_t* p, size_t len, const StreamRun& bad, size_t* used, bool to_ring) {
     *used = 0;
     const uint32_t j = bad.far ? 0u : bad.good_blocks;
@@ -586,7 +624,8 @@ class StreamCore {
       if (hasher_on_) hasher_ = std::thread([this]() { hasher_main(); });
     } catch (...) {                       // a thread could not be started: the reference's schedule from what the ring holds
       const int st2 = stop_pipe(true);
-      return st2 ? st2 : ZG_OK;
+      if (st2) fail(st2);
+      return ZG_OK;
     }
     produce_jobs();
     return ZG_OK;
@@ -679,6 +718,14 @@ class StreamCore {
     cv_reader_.notify_all();
     return ZG_OK;
   }
+  // worker: the engine failed. Nothing goes back to the source and the engine is asked for nothing more; it only drops what it holds — a
+  // run in flight (the backend waits for the device before it lets go of it) and a prepared one — so that the device is idle before the
+  // reader learns of the failure (when the ring cannot serve a read: read_pipe -> fail()) and gives the ring and the staging buffers back.
+  void worker_failed(int e) {
+    be_->discard();
+    be_->drop_prepared();
+    set_pstate(P_FAILED, e ? e : ZG_INTERNAL);
+  }
   void set_pstate(int s, int err) {
     { std::lock_guard<std::mutex> lk(mu_); pipe_err_ = err; pstate_.store(s, std::memory_order_release); }
     cv_reader_.notify_all();
@@ -705,7 +752,7 @@ class StreamCore {
       if (g == 2) return;
       if (g == 1) { set_pstate(P_STOPPED, 0); return; }     // the source ran dry in front of the frame's end before a single run
       { Tick tk(&tus[1]); e = be_->prepare(cur.p, cur.len, cur.nblocks); if (!e) e = be_->launch(window); }
-      if (e) { give_back(&cur, nullptr, 0); set_pstate(P_FAILED, e); return; }
+      if (e) { worker_failed(e); return; }
     }
     for (;;) {
       // run `cur` is on the device: meanwhile the next one is taken from the queue, walked and uploaded
@@ -713,27 +760,26 @@ class StreamCore {
       if (have_nxt && !nxt_ready) {
         Tick tk(&tus[1]);
         e = be_->prepare(nxt.p, nxt.len, nxt.nblocks);
-        if (e) { StreamRun dummy; (void)be_->wait(&dummy); be_->discard(); give_back(&cur, &nxt, 0); set_pstate(P_FAILED, e); return; }
+        if (e) { worker_failed(e); return; }
         nxt_ready = true;
       }
       StreamRun r;
       { Tick tk(&tus[1]); e = be_->wait(&r); }
-      int e2;
-      { Tick tk(&tus[2]); e2 = land_fetch(); }  // the run in front travelled to the ring meanwhile
-      if (!e) e = e2;
-      if (e) { be_->discard(); be_->drop_prepared(); give_back(&cur, have_nxt ? &nxt : nullptr, 0); set_pstate(P_FAILED, e); return; }
+      if (!e) { Tick tk(&tus[2]); e = land_fetch(); }  // the run in front travelled to the ring meanwhile
+      if (e) { worker_failed(e); return; }
       if (!clean(r, cur.nblocks)) {
         be_->discard();
         be_->drop_prepared();
         dropped_++;
         size_t used = 0;
         e = salvage(cur.p, cur.len, r, &used, true);
+        if (e) { worker_failed(e); return; }
         give_back(&cur, have_nxt ? &nxt : nullptr, used);
-        set_pstate(e ? P_FAILED : P_STOPPED, e);
+        set_pstate(P_STOPPED, 0);
         return;
       }
       { Tick tk(&tus[3]); e = be_->commit(); }
-      if (e) { be_->drop_prepared(); set_pstate(P_FAILED, e); return; }
+      if (e) { worker_failed(e); return; }
       account(r, cur.len, cur.nblocks, true);
       runs_++;
       e = fetch_to_ring(r.out_size, false);
@@ -742,17 +788,21 @@ class StreamCore {
         if (cur.stage >= 0) stages_[cur.stage].busy = false;
         taken_--;
       }
-      if (e) { be_->drop_prepared(); set_pstate(P_FAILED, e); return; }
+      if (e) { worker_failed(e); return; }
       if (r.saw_last || cur.stop) {
-        e = land_fetch();
-        if (!e) publish_fin();
-        set_pstate(e ? P_FAILED : (r.saw_last ? P_DONE : P_STOPPED), e);
+        if ((e = land_fetch())) { worker_failed(e); return; }
+        publish_fin();
+        set_pstate(r.saw_last ? P_DONE : P_STOPPED, 0);
         return;
       }
       if (!have_nxt) {
         const int g = take_job(&nxt, true);
         if (g == 2) break;
-        if (g == 1) { e = land_fetch(); set_pstate(e ? P_FAILED : P_STOPPED, e); return; }   // nothing more will come: the source ran dry in front of the frame's end
+        if (g == 1) {                                       // nothing more will come: the source ran dry in front of the frame's end
+          if ((e = land_fetch())) { worker_failed(e); return; }
+          set_pstate(P_STOPPED, 0);
+          return;
+        }
         have_nxt = true;
       }
       if (!nxt_ready) {
@@ -760,7 +810,7 @@ class StreamCore {
         e = be_->prepare(nxt.p, nxt.len, nxt.nblocks);
       }
       if (!e) { Tick tk(&tus[1]); e = be_->launch(window); }
-      if (e) { be_->drop_prepared(); give_back(&nxt, nullptr, 0); set_pstate(P_FAILED, e); return; }
+      if (e) { worker_failed(e); return; }
       cur = nxt; have_nxt = false; nxt_ready = false;
     }
     (void)land_fetch();
@@ -841,6 +891,11 @@ class StreamCore {
         return ZG_OK;
       }
       if (want > holdable && coll > 0) {
+        if (hasher_on_ && !snap_set_) {                     // (the hash in front of this read's first piece: fail())
+          const uint64_t t = tail_.load(std::memory_order_relaxed);
+          while (hashed_.load(std::memory_order_acquire) != t) std::this_thread::yield();
+          snap_ = hash_; snap_set_ = true;
+        }
         drain_ring(dst ? dst + *done : nullptr, (size_t)coll);
         *done += (size_t)coll;
         pump((size_t)coll);
@@ -861,10 +916,9 @@ class StreamCore {
       }
       // the worker has stopped in front of the frame's end (a run was dropped, the source ran dry, the engine failed)
       if (pub_.load(std::memory_order_acquire) - tail_.load(std::memory_order_relaxed) != a) continue;   // its last publish came in between
-      const int err = pipe_err_;
+      if (ps == P_FAILED) return fail(pipe_err_);           // (pipe_err_: written before P_FAILED was, under mu_)
       const int st = stop_pipe(true);
-      if (ps == P_FAILED) return err ? err : ZG_INTERNAL;
-      if (st) return st;
+      if (st) return fail(st);
       *again = true;
       return ZG_OK;
     }
@@ -875,7 +929,7 @@ class StreamCore {
     if (last_pump_ >= (1u << 20)) { last_pump_ = 0; if (pstate_.load(std::memory_order_relaxed) == P_RUNNING) produce_jobs(); }
   }
 
-  // Join the threads. to_lockstep: the stream goes on on the caller's thread — what the ring still holds moves to the host buffer, the
+  // Join the threads (after an engine error too: fail()). to_lockstep: the stream goes on on the caller's thread — what the ring still holds moves to the host buffer, the
   // source gets back what was not taken, the device gets everything the reader still holds in reach again.
   int stop_pipe(bool to_lockstep) {
     if (!pipe_up_) return ZG_OK;

@@ -266,7 +266,7 @@ EXPORTS = [
     "zgpu_frame_begin", "zgpu_frame_end", "zgpu_blocks_submit", "zgpu_sync", "zgpu_available", "zgpu_read", "zgpu_device_output",
     "zgpu_frame_checksum", "zgpu_frame_blocks_decoded", "zgpu_decoder_device_bytes", "zgpu_debug_tuning",
     "zgpu_streaming_create_ex", "zgpu_streaming_create_slice", "zgpu_streaming_source_position", "zgpu_streaming_copy", "zgpu_streaming_stats",
-    "zgpu_decoder_set_hash", "zgpu_decoder_set_read_ahead", "zgpu_release_caches",
+    "zgpu_decoder_set_hash", "zgpu_decoder_set_read_ahead", "zgpu_release_caches", "zgpu_decoder_stream_error",
 ]
 WRITE_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
@@ -418,6 +418,7 @@ def _declare(L):
     L.zgpu_streaming_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_decoder_set_hash.argtypes = [vp, C.c_int]
     L.zgpu_decoder_set_read_ahead.argtypes = [vp, C.c_uint64]
+    L.zgpu_decoder_stream_error.argtypes = [vp]
     for f in ("zgpu_decoder_is_finished", "zgpu_decoder_checksum_from_data"):
         getattr(L, f).argtypes = [vp] if f.endswith("finished") else [vp, P(C.c_uint32)]
     return L
@@ -1322,6 +1323,10 @@ class CStreamingDecoder:
 
     def bytes_read_from_source(self):
         return self.L.zgpu_decoder_bytes_read_from_source(self._dec())
+
+    def error(self):
+        """the engine error that ended the stream (every read() returns it from then on); 0: none"""
+        return self.L.zgpu_decoder_stream_error(self._dec())
 
     def source_position(self):
         return self.L.zgpu_streaming_source_position(self.h)
