@@ -21,19 +21,34 @@ struct ZgDictDev {   // a dictionary's one device copy per context (zg_dictfill.
   zg::DevBuf buf;
   zgd::DictImage im{};
 };
+// The slots of the context's statistics arrays, each under the key zgpu.py reports it by (include/zgpu.h: the zgpu_debug_*_stats getters).
+// The arrays an engine pass is handed begin with its three slots (zg_engine.h: kPassLaunches, kPassUs, kPassBytes).
+enum { kDictStatFramesShared = 0, kDictStatFillLaunches, kDictStatBytesReplicated, kDictStatFillUs, kDictStatEntriesAlone, kDictStatCount };
+enum { kDevStatSubmits = 0, kDevStatScatterLaunches, kDevStatBytesScattered, kDevStatScatterUs, kDevStatFramesHashed, kDevStatFramesNotHashed,
+       kDevStatEntriesAlone, kDevStatEntriesFailedVerify, kDevStatHashUs, kDevStatCount };
+enum { kSrcStatWalkLaunches = 0, kSrcStatWalkUs, kSrcStatSkeletonBytes, kSrcStatGatherLaunches, kSrcStatGatherUs, kSrcStatInputBytesToHost, kSrcStatCount };
+enum { kIndexStatLaunches = 0, kIndexStatKernelUs, kIndexStatBytesDownloaded, kIndexStatInputBytesToHost, kIndexStatCount };
+enum { kRangeStatSeekLaunches = 0, kRangeStatSeekUs, kRangeStatSeekBytesDownloaded, kRangeStatInputBytesToHost, kRangeStatFramesSkipped,
+       kRangeStatFramesDecoded, kRangeStatPlaintextDecoded, kRangeStatBytesWritten, kRangeStatCount };
+static_assert(kSrcStatWalkLaunches == zg::kPassLaunches && kSrcStatWalkUs == zg::kPassUs && kSrcStatSkeletonBytes == zg::kPassBytes &&
+              kIndexStatLaunches == zg::kPassLaunches && kIndexStatKernelUs == zg::kPassUs && kIndexStatBytesDownloaded == zg::kPassBytes &&
+              kRangeStatSeekLaunches == zg::kPassLaunches && kRangeStatSeekUs == zg::kPassUs && kRangeStatSeekBytesDownloaded == zg::kPassBytes,
+              "the arrays handed to Engine::walk_entries, index_pass and seek_pass / seektab_pass");
+
 struct zgpu_ctx {
   zg::Engine* eng = nullptr;
   std::map<uint32_t, ZgDict> dicts;   // FrameDecoder::dicts (frame_decoder.rs:82)
   std::map<uint32_t, zg::DictFacts> dict_facts;   // what the walk of a shared submit is told of each (zgpu_add_dict keeps it in step with dicts)
   std::map<uint32_t, ZgDictDev> dict_dev;         // freed with the context; an entry goes when zgpu_add_dict replaces its dictionary
   bool frames_shared_dicts = false;               // zgpu_set_frames_shared_dicts
-  uint64_t frames_dict_stats[5] = {0, 0, 0, 0, 0};   // of the last zgpu_decode_frames* call (zgpu_debug_frames_dict_stats)
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
-  uint64_t frames_device_stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device call (zgpu_debug_frames_device_stats)
-  uint64_t frames_device_src_stats[6] = {0, 0, 0, 0, 0, 0};   // of the last zgpu_decode_frames_device_src call (zgpu_debug_frames_device_src_stats)
-  uint64_t frames_index_stats[4] = {0, 0, 0, 0};              // of the last zgpu_frames_index_device / zgpu_frames_table_device call (zgpu_debug_frames_index_stats)
-  uint64_t ranges_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // of the last zgpu_frames_seek_device / zgpu_decode_ranges_device_src call (zgpu_debug_ranges_stats)
-  uint64_t hash_ranges_us = 0;                                // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
+  // of the last call of their family (zg_frames.cpp: reset_stats says which call owns which)
+  uint64_t frames_dict_stats[kDictStatCount] = {};        // zgpu_decode_frames* and the decode_ranges calls (zgpu_debug_frames_dict_stats)
+  uint64_t frames_device_stats[kDevStatCount] = {};       // the calls with a device sink (zgpu_debug_frames_device_stats)
+  uint64_t frames_device_src_stats[kSrcStatCount] = {};   // the calls with device sources (zgpu_debug_frames_device_src_stats)
+  uint64_t frames_index_stats[kIndexStatCount] = {};      // zgpu_frames_index_device / zgpu_frames_table_device (zgpu_debug_frames_index_stats)
+  uint64_t ranges_stats[kRangeStatCount] = {};            // the seek and decode_ranges calls (zgpu_debug_ranges_stats)
+  uint64_t hash_ranges_us = 0;                            // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
 

@@ -304,18 +304,22 @@ int parse_block_run(const uint8_t* src, size_t len, uint64_t window, bool has_ch
   return st;
 }
 
-
-int Engine::prepare(const uint8_t* src, size_t len, Batch** out) {
-  Batch* b = new Batch();
-  b->eng = this;
-  b->src_len = len;
-  b->parse_status = parse_frames(src, len, max_window, &b->bb, &b->info);
+// a parsed submit whose frames all declare a Frame_Content_Size: their sum (the output can be sized before the run)
+static void sum_declared(Batch* b) {
   b->all_declared = !b->info.empty();
   for (const FrameInfo& fi : b->info) {
     if (!fi.header.has_fcs()) { b->all_declared = false; break; }
     b->declared_total += fi.header.frame_content_size;
   }
   if (!b->all_declared || b->declared_total > (1ull << 40)) { b->all_declared = false; b->declared_total = 0; }
+}
+
+int Engine::prepare(const uint8_t* src, size_t len, Batch** out) {
+  Batch* b = new Batch();
+  b->eng = this;
+  b->src_len = len;
+  b->parse_status = parse_frames(src, len, max_window, &b->bb, &b->info);
+  sum_declared(b);
   return upload(b, src, len, out);
 }
 
@@ -332,52 +336,57 @@ int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off,
     if (!b->parse_status) b->parse_status = (*walk)[i];
   }
   (*first_frame)[n] = (uint32_t)b->info.size();
-  b->all_declared = !b->info.empty();
-  for (const FrameInfo& fi : b->info) {
-    if (!fi.header.has_fcs()) { b->all_declared = false; break; }
-    b->declared_total += fi.header.frame_content_size;
-  }
-  if (!b->all_declared || b->declared_total > (1ull << 40)) { b->all_declared = false; b->declared_total = 0; }
+  sum_declared(b);
   return upload(b, src, len, out);
 }
 
-namespace {
-struct WalkTmp {   // device memory and events of one walk_entries call
-  DevBuf lanes, ends, recs;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~WalkTmp() {
-    lanes.release(); ends.release(); recs.release();
+// device memory and events of the lane passes of one call
+struct Engine::LaneTmp {
+  DevBuf lanes, out, extra;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~LaneTmp() {
+    lanes.release(); out.release(); extra.release();
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
-}  // namespace
+
+template <class Launch>
+int Engine::lane_pass(LaneTmp& t, const void* lanes, size_t lane_bytes, Down out, Down extra, uint64_t* stats, Launch launch) {
+  Engine* eng = this;
+  ZG_HIP(hipSetDevice(device_));
+  hipStream_t s = stream_;
+  int st;
+  if ((st = t.lanes.reserve(lane_bytes)) || (st = t.out.reserve(out.bytes)) || (extra.host && (st = t.extra.reserve(extra.bytes)))) return st;
+  for (hipEvent_t& x : t.ev) if (!x) ZG_HIP(hipEventCreate(&x));
+  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes, lane_bytes, hipMemcpyHostToDevice, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
+  ZG_HIP(hipEventRecord(t.ev[0], s));
+  launch(t, s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(t.ev[1], s));
+  ZG_HIP(hipMemcpyAsync(out.host, t.out.p, out.bytes, hipMemcpyDeviceToHost, s));
+  if (extra.bytes) ZG_HIP(hipMemcpyAsync(extra.host, t.extra.p, extra.bytes, hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  stats[kPassLaunches] += 1; stats[kPassUs] += (uint64_t)(ms * 1000.0f + 0.5f); stats[kPassBytes] += out.bytes + extra.bytes;
+  return ZG_OK;
+}
 
 int Engine::walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats) {
-  Engine* eng = this;
   sk->recs.clear();
   sk->first.assign((size_t)n + 1, 0);
   sk->ends.assign(n, zgw::End{0, 0, 0});
   if (!n) return ZG_OK;
-  ZG_HIP(hipSetDevice(device_));
-  hipStream_t s = stream_;
-  WalkTmp t;
+  LaneTmp t;
   std::vector<zgw::Lane> lanes(n);
   for (uint32_t i = 0; i < n; i++) lanes[i] = zgw::Lane{e[i].src, e[i].len, 0, 0};
-  int st;
-  if ((st = t.lanes.reserve((size_t)n * sizeof(zgw::Lane))) || (st = t.ends.reserve((size_t)n * sizeof(zgw::End)))) return st;
-  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
+  const size_t lane_bytes = (size_t)n * sizeof(zgw::Lane), end_bytes = (size_t)n * sizeof(zgw::End);
   // count pass: how many records every entry has
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
-  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
-  ZG_HIP(hipEventRecord(t.ev[0], s));
-  zg_launch_walk(t.lanes.as<zgw::Lane>(), n, t.ends.as<zgw::End>(), nullptr, s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[1], s));
-  ZG_HIP(hipMemcpyAsync(sk->ends.data(), t.ends.p, (size_t)n * sizeof(zgw::End), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgw::End);
+  int st = lane_pass(t, lanes.data(), lane_bytes, Down{sk->ends.data(), end_bytes}, Down{}, stats, [&](LaneTmp& d, hipStream_t s) {
+    zg_launch_walk(d.lanes.as<zgw::Lane>(), n, d.out.as<zgw::End>(), nullptr, s);
+  });
+  if (st) return st;
   for (uint32_t i = 0; i < n; i++) {
     lanes[i].first = sk->first[i];
     lanes[i].limit = sk->ends[i].nrec;
@@ -387,19 +396,10 @@ int Engine::walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* 
   if (!total) return ZG_OK;
   // emit pass: every lane writes its own range of records, and no other
   sk->recs.resize(total);
-  if ((st = t.recs.reserve(total * sizeof(zgw::Rec)))) return st;
   std::vector<zgw::End> again(n);
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  ZG_HIP(hipEventRecord(t.ev[2], s));
-  zg_launch_walk(t.lanes.as<zgw::Lane>(), n, t.ends.as<zgw::End>(), t.recs.as<zgw::Rec>(), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[3], s));
-  ZG_HIP(hipMemcpyAsync(again.data(), t.ends.p, (size_t)n * sizeof(zgw::End), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipMemcpyAsync(sk->recs.data(), t.recs.p, total * sizeof(zgw::Rec), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[2], t.ev[3]));
-  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgw::End) + total * sizeof(zgw::Rec);
+  st = lane_pass(t, lanes.data(), lane_bytes, Down{again.data(), end_bytes}, Down{sk->recs.data(), total * sizeof(zgw::Rec)}, stats,
+                 [&](LaneTmp& d, hipStream_t s) { zg_launch_walk(d.lanes.as<zgw::Lane>(), n, d.out.as<zgw::End>(), d.extra.as<zgw::Rec>(), s); });
+  if (st) return st;
   for (uint32_t i = 0; i < n; i++)   // (a source that changed between the passes: the caller's promise broken, nothing of the skeleton is used)
     if (again[i].nrec != sk->ends[i].nrec || again[i].stop_off != sk->ends[i].stop_off || again[i].why != sk->ends[i].why) {
       last_error = "zgpu_decode_frames_device_src: a source changed while it was walked";
@@ -408,89 +408,35 @@ int Engine::walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* 
   return ZG_OK;
 }
 
-namespace {
-struct IndexTmp {   // device memory and events of one index_entries / index_frames call
-  DevBuf lanes, ents, recs;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~IndexTmp() {
-    lanes.release(); ents.release(); recs.release();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
-
 int Engine::index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, const zgi::Entry* sum, zgi::Entry* out, zgi::FrameRec* recs, uint64_t* stats) {
-  Engine* eng = this;
   if (!n) return ZG_OK;
-  ZG_HIP(hipSetDevice(device_));
-  hipStream_t s = stream_;
-  IndexTmp t;
-  const uint64_t total = first ? first[n] : 0;
+  LaneTmp t;
   std::vector<zgw::Lane> lanes(n);
   for (uint32_t i = 0; i < n; i++) lanes[i] = zgw::Lane{e[i].src, e[i].len, first ? first[i] : 0, first ? (uint64_t)sum[i].nrec : 0};
-  int st;
-  if ((st = t.lanes.reserve((size_t)n * sizeof(zgw::Lane))) || (st = t.ents.reserve((size_t)n * sizeof(zgi::Entry)))) return st;
-  if (first && (st = t.recs.reserve((total ? total : 1) * sizeof(zgi::FrameRec)))) return st;
-  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes.data(), (size_t)n * sizeof(zgw::Lane), hipMemcpyHostToDevice, s));
-  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
-  ZG_HIP(hipEventRecord(t.ev[0], s));
-  zg_launch_index(t.lanes.as<zgw::Lane>(), n, t.ents.as<zgi::Entry>(), first ? t.recs.as<zgi::FrameRec>() : nullptr, s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[1], s));
-  ZG_HIP(hipMemcpyAsync(out, t.ents.p, (size_t)n * sizeof(zgi::Entry), hipMemcpyDeviceToHost, s));
-  if (total) ZG_HIP(hipMemcpyAsync(recs, t.recs.p, total * sizeof(zgi::FrameRec), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgi::Entry) + total * sizeof(zgi::FrameRec);
-  return ZG_OK;
+  const Down down_recs = first ? Down{recs, (size_t)first[n] * sizeof(zgi::FrameRec)} : Down{};
+  return lane_pass(t, lanes.data(), (size_t)n * sizeof(zgw::Lane), Down{out, (size_t)n * sizeof(zgi::Entry)}, down_recs, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_index(d.lanes.as<zgw::Lane>(), n, d.out.as<zgi::Entry>(), d.extra.as<zgi::FrameRec>(), s); });
 }
 
 int Engine::seek_pass(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats) {
-  Engine* eng = this;
   if (!n) return ZG_OK;
-  ZG_HIP(hipSetDevice(device_));
-  hipStream_t s = stream_;
-  IndexTmp t;
-  int st;
-  if ((st = t.lanes.reserve((size_t)n * sizeof(zgk::Lane))) || (st = t.ents.reserve((size_t)n * sizeof(zgk::Seek)))) return st;
-  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes, (size_t)n * sizeof(zgk::Lane), hipMemcpyHostToDevice, s));
-  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
-  ZG_HIP(hipEventRecord(t.ev[0], s));
-  zg_launch_seek(t.lanes.as<zgk::Lane>(), n, t.ents.as<zgk::Seek>(), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[1], s));
-  ZG_HIP(hipMemcpyAsync(out, t.ents.p, (size_t)n * sizeof(zgk::Seek), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgk::Seek);
-  return ZG_OK;
+  LaneTmp t;
+  return lane_pass(t, lanes, (size_t)n * sizeof(zgk::Lane), Down{out, (size_t)n * sizeof(zgk::Seek)}, Down{}, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_seek(d.lanes.as<zgk::Lane>(), n, d.out.as<zgk::Seek>(), s); });
 }
 
 int Engine::seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats) {
-  Engine* eng = this;
   if (!n) return ZG_OK;
-  ZG_HIP(hipSetDevice(device_));
-  hipStream_t s = stream_;
-  IndexTmp t;
-  int st;
-  if ((st = t.lanes.reserve((size_t)n * sizeof(zgt::Lane))) || (st = t.ents.reserve((size_t)n * sizeof(zgk::Seek)))) return st;
-  for (hipEvent_t& x : t.ev) ZG_HIP(hipEventCreate(&x));
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes, (size_t)n * sizeof(zgt::Lane), hipMemcpyHostToDevice, s));
-  ZG_HIP(hipStreamSynchronize(s));   // (pageable)
-  ZG_HIP(hipEventRecord(t.ev[0], s));
-  zg_launch_seektab(t.lanes.as<zgt::Lane>(), n, t.ents.as<zgk::Seek>(), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[1], s));
-  ZG_HIP(hipMemcpyAsync(out, t.ents.p, (size_t)n * sizeof(zgk::Seek), hipMemcpyDeviceToHost, s));
-  ZG_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-  stats[0] += 1; stats[1] += (uint64_t)(ms * 1000.0f + 0.5f); stats[2] += (uint64_t)n * sizeof(zgk::Seek);
-  return ZG_OK;
+  LaneTmp t;
+  return lane_pass(t, lanes, (size_t)n * sizeof(zgt::Lane), Down{out, (size_t)n * sizeof(zgk::Seek)}, Down{}, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_seektab(d.lanes.as<zgt::Lane>(), n, d.out.as<zgk::Seek>(), s); });
+}
+
+int Engine::hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats) {
+  if (!n) return ZG_OK;
+  LaneTmp t;
+  return lane_pass(t, ranges, (size_t)n * sizeof(ZgHashRange), Down{digests, (size_t)n * sizeof(uint64_t)}, Down{}, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_xxh64_with(base, d.lanes.as<ZgHashRange>(), d.out.as<uint64_t>(), n, s, kernel); });
 }
 
 int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
@@ -510,12 +456,7 @@ int Engine::prepare_entries_device(const DevEntry* e, const Skeleton& sk, const 
     if (!b->parse_status) b->parse_status = (*walk)[j];
   }
   (*first_frame)[n] = (uint32_t)b->info.size();
-  b->all_declared = !b->info.empty();
-  for (const FrameInfo& fi : b->info) {
-    if (!fi.header.has_fcs()) { b->all_declared = false; break; }
-    b->declared_total += fi.header.frame_content_size;
-  }
-  if (!b->all_declared || b->declared_total > (1ull << 40)) { b->all_declared = false; b->declared_total = 0; }
+  sum_declared(b);
   const GatherPlan g{e, idx, off, n};
   return upload(b, nullptr, total, out, false, &g);
 }

@@ -117,6 +117,10 @@ struct Tuning {
 
 class Engine;
 
+// What every lane pass of an engine adds to the statistics array it is handed (Engine::lane_pass); the arrays of zg_capi_int.h that a pass
+// fills begin with these three slots.
+enum { kPassLaunches = 0, kPassUs = 1, kPassBytes = 2 };
+
 // One submit: parsed input + its device state. Created by Engine::prepare.
 class Batch {
  public:
@@ -230,9 +234,10 @@ class Engine {
   int prepare_entries(const uint8_t* src, size_t len, const uint64_t* off, const uint64_t* elen, uint32_t n, Batch** out,
                       std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts = nullptr);
   // The same for entries whose compressed bytes lie in DEVICE memory of the caller (zgpu_decode_frames_device_src, which has checked every range
-  // against the runtime's allocations). walk_entries: zg_k_walk (zg_walk.h) follows the header chain of all n entries in two launches, count
+  // against the runtime's allocations). walk_entries: zg_k_walk (zg_walk.h) follows the header chain of all n entries in two lane passes, count
   // and emit, and brings back the skeleton: entry i's records are sk->recs[sk->first[i] .. sk->first[i + 1]), sk->ends[i] where its lane
-  // stopped. An entry of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP events), bytes downloaded.
+  // stopped. An entry of length 0 is not read; the emit pass is skipped when no entry has a record; a lane that stops elsewhere in the emit
+  // pass than in the count pass (a source that changed meanwhile) is ZG_INTERNAL.
   // prepare_entries_device: entries idx[0 .. n) of that skeleton parsed with the host's one walk (parse_frames_skel) into ONE submit, as
   // prepare_entries does with bytes; off[j] = where entry idx[j] lies in the submit's input (back to back, total bytes). The compressed bytes
   // reach the engine's source buffer by ONE zg_k_gather launch instead of the H2D copy; everything behind that is shared.
@@ -241,19 +246,23 @@ class Engine {
   int walk_entries(const DevEntry* e, uint32_t n, Skeleton* sk, uint64_t* stats);
   int prepare_entries_device(const DevEntry* e, const Skeleton& sk, const uint32_t* idx, const uint64_t* off, uint32_t n, size_t total, Batch** out,
                              std::vector<int>* walk, std::vector<uint32_t>* first_frame, const DictLookup* dicts = nullptr);
-  // What such entries hold, from their headers alone (zgpu_frames_index_device / zgpu_frames_table_device): ONE zg_k_index launch (zg_index.h)
-  // over all n entries. first == nullptr: the summary pass, out[i] = entry i's summary. Else the emit pass: sum = the summaries of the summary
+  // The lane passes: ONE launch over n lanes whose records come back to the host (lane_pass below is the one routine behind all of them, and
+  // behind walk_entries' two). Every pass adds to stats[kPassLaunches], stats[kPassUs] (the kernel's time between two HIP events) and
+  // stats[kPassBytes] (bytes downloaded); n == 0 is no pass at all, not even a hipSetDevice.
+  // index_pass — what such entries hold, from their headers alone (zgpu_frames_index_device / zgpu_frames_table_device): zg_k_index
+  // (zg_index.h). first == nullptr: the summary pass, out[i] = entry i's summary. Else the emit pass: sum = the summaries of the summary
   // pass, first[i] .. first[i + 1] (their prefix sum, n + 1 slots) the frame records lane i may write of recs[0 .. first[n]); out = what this
-  // pass says about every entry (the caller compares). An entry of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
-  // events), bytes downloaded.
+  // pass says about every entry (the caller compares). An entry of length 0 is not read.
   int index_pass(const DevEntry* e, uint32_t n, const uint64_t* first, const zgi::Entry* sum, zgi::Entry* out, zgi::FrameRec* recs, uint64_t* stats);
-  // Which whole frames of such entries hold a plaintext range (zgpu_frames_seek_device / zgpu_decode_ranges_device_src): ONE zg_k_seek launch
-  // (zg_seek.h) over all n lanes, out[i] = lane i's record. A lane of length 0 is not read. stats[0..2] += launches, kernel microseconds (HIP
-  // events), bytes downloaded (64 per lane).
+  // seek_pass — which whole frames of such entries hold a plaintext range (zgpu_frames_seek_device / zgpu_decode_ranges_device_src): zg_k_seek
+  // (zg_seek.h), out[i] = lane i's record (64 bytes per lane come back). A lane of length 0 is not read.
   int seek_pass(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
-  // The same from the seekable format's seek table at each entry's end (zgpu_frames_seek_table_device / zgpu_decode_ranges_seek_table_device_src):
-  // ONE zg_k_seektab launch (zg_seektab.h), a wave per entry. stats as seek_pass.
+  // seektab_pass — the same from the seekable format's seek table at each entry's end (zgpu_frames_seek_table_device /
+  // zgpu_decode_ranges_seek_table_device_src): zg_k_seektab (zg_seektab.h), a wave per entry.
   int seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
+  // hash_ranges_pass — XXH64 of ranges[0 .. n) of base (device memory the caller has checked) by the hash kernel `kernel` chooses
+  // (zg_launch_xxh64_with); digests[i] is ranges[i]'s (zgpu_debug_hash_ranges).
+  int hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats);
   // Same for a run of blocks of ONE frame that starts at a block header (the FrameDecoder mirror parsed the frame
   // header itself). *consumed = bytes of the run (block headers, bodies, checksum).
   // max_blocks: 0 = up to the last block of the frame. fs carries the frame's state across calls; keep = frame bytes
@@ -289,6 +298,12 @@ class Engine {
   Scratch* acquire();
   void recycle(Scratch* s);
   int fail(hipError_t e, const char* what);
+  // One lane pass on the first stream: t's buffers reserved (they and its two events are reused by a second pass of the same call), lane_bytes
+  // of lanes uploaded and the stream synchronised (the lane array is pageable), event, launch(t, stream), hipGetLastError, event, out — and
+  // extra, the second array of an emit pass, if it has a host side — downloaded, the stream synchronised, the three kPass* slots of stats added to.
+  struct LaneTmp;
+  struct Down { void* host = nullptr; size_t bytes = 0; };   // bytes of a device array (LaneTmp::out / extra) that come back to host
+  template <class Launch> int lane_pass(LaneTmp& t, const void* lanes, size_t lane_bytes, Down out, Down extra, uint64_t* stats, Launch launch);
   struct GatherPlan { const DevEntry* e; const uint32_t* idx; const uint64_t* off; uint32_t n; };
   // g: the len bytes come from device memory, entry g->idx[j] to offset g->off[j], by one zg_k_gather launch (src is not looked at)
   int upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool side = false, const GatherPlan* g = nullptr);

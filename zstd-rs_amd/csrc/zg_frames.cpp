@@ -26,6 +26,14 @@
 // buffer bookkeeping for every such frame as it does for a one-frame run. The verdict of an entry that holds a dictionary frame is put together
 // in zgpu_decode_all's order for such an entry — frame by frame (zg_decode_all_per_frame) — and what the submit cannot serve exactly (an
 // unregistered id, Unsupported / Internal: the dictionary splice behind a drain inside decode_all, zg_exact.h) goes alone as before.
+//
+// How a call is put together. A Call is what every call has (context, sources, lengths, destinations, capacities, the shared-dictionary
+// lookup) plus up to three parts that an entry point builds and hangs in: DeviceSink (device_sink: the options, the one place that refuses
+// ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY), DeviceSources (check_entries + device_sources: pointer checks, zg_k_walk, bounds) and Ranges
+// (decode_ranges: the clips). decode_submit, the sinks, decode_alone_device and decode_entries ask for a part by its pointer — `if (k.sink)`,
+// `if (k.src)`, `if (k.ranges)` — never by which field happens to be set. Around them: reset_stats zeroes the statistics a call family owns
+// (kOwns*), check_entries is the one pointer check in front of the engine's lane passes, drain the two-stream wait every call ends with,
+// SubmitHash the hashing both sinks start before they copy. Every statistics slot is written under its name (zg_capi_int.h, kPass*).
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -99,45 +107,6 @@ struct Staging {
   ~Staging() { if (p) { if (pinned) zg_pinned_put(p); else free(p); } }
 };
 
-struct Call {
-  zgpu_ctx* c;
-  const uint8_t* const* srcs;
-  const size_t* lens;
-  uint8_t* const* dsts;                            // host sink: host memory; device sink: device memory of the caller (checked)
-  const size_t* caps;
-  zgpu_entry_result* res;                          // host sink
-  bool hash_forced;                                // (development build, ZGPU_HASH_DEVICE_MAX) frames up to hash_max on the device, no estimate
-  uint64_t hash_max;
-  std::vector<std::pair<uint32_t, bool>> again;   // entries decoded again on their own after the submits (true: the walk met a dictionary frame)
-  zgpu_device_entry_result* dres = nullptr;        // device sink (zgpu_decode_frames_device): its results; hash_max is the caller's, no estimate
-  bool no_hash = false;                            //   flags bit 0: hash no frame
-  bool verify = false;                             //   flags bit 1 (ZGPU_DEVICE_VERIFY): a mismatch fails the entry, with nothing of it written
-  bool hash_all = false;                           //   verify with hash_max_bytes == 0: every frame that carries a Content_Checksum is hashed
-  uint64_t* stats = nullptr;                       //   zgpu_ctx::frames_device_stats
-  // device sources (zgpu_decode_frames_device_src): srcs[i] is device memory; what was found out about every entry before the first submit
-  const Engine::Skeleton* sk = nullptr;            //   the records zg_k_walk brought back
-  const Engine::DevEntry* dev = nullptr;           //   the entries as the engine takes them (a refused entry: length 0)
-  const uint8_t* refused = nullptr;                //   entries whose source or destination failed the pointer check (1), or the status (> 1) of
-                                                   //   an entry that is refused for another reason (ZGPU_E_SEEK_TABLE)
-  const uint64_t* bound = nullptr;                 //   plaintext_bound of every entry, from its records
-  uint64_t* sstats = nullptr;                      //   zgpu_ctx::frames_device_src_stats
-  const DictLookup* dicts = nullptr;               // shared dictionaries (zgpu_set_frames_shared_dicts): what the walks resolve ids with; else nullptr
-  // ranges (zgpu_decode_ranges_device_src): the entries are the selections zg_k_seek found, and of the concatenation of an entry's decoded frames
-  // only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
-  struct Clip { uint64_t skip, len, declared; };
-  const Clip* clip = nullptr;
-  bool promise = false;                            //   (zgpu_decode_ranges_seek_table_device_src) declared is the seek table's promise: it always holds
-  uint64_t* rstats = nullptr;                      //   zgpu_ctx::ranges_stats
-  uint64_t alone_written = 0;                      //   bytes the entries decoded alone brought to their destinations
-  // what of `bytes` decoded bytes of entry i its destination gets
-  uint64_t clipped(uint32_t i, uint64_t bytes) const {
-    if (!clip) return bytes;
-    const uint64_t rest = bytes > clip[i].skip ? bytes - clip[i].skip : 0;
-    return rest < clip[i].len ? rest : clip[i].len;
-  }
-  zgpu_entry_result& result(uint32_t i) const { return dres ? dres[i].r : res[i]; }
-};
-
 // the lookup of a shared submit's walks: the context's registered dictionaries. One without content is not resolved — its frames go alone, as
 // with the switch off (ZgFrame::dict_len != 0 is what marks a dictionary frame for the engine).
 const DictFacts* shared_find(const void* user, uint32_t id) {
@@ -145,6 +114,66 @@ const DictFacts* shared_find(const void* user, uint32_t id) {
   auto it = c->dict_facts.find(id);
   return it == c->dict_facts.end() || it->second.content_len == 0 ? nullptr : &it->second;
 }
+
+// The three parts only some calls have; each lives in its entry point's frame, and an absent one is a null pointer in the Call.
+// destinations in device memory of the caller (zgpu_decode_frames_device and every call built on it)
+struct DeviceSink {
+  zgpu_device_entry_result* res = nullptr;
+  uint64_t hash_max = 0;          // the caller's (no estimate): frames up to this length are hashed
+  bool no_hash = false;           // ZGPU_DEVICE_NO_HASH: hash no frame
+  bool verify = false;            // ZGPU_DEVICE_VERIFY: a mismatch fails the entry, with nothing of it written
+  bool hash_all = false;          // verify with hash_max_bytes == 0: every frame that carries a Content_Checksum is hashed
+  uint64_t* stats = nullptr;      // zgpu_ctx::frames_device_stats (kDevStat*)
+  uint64_t alone_written = 0;     // bytes the entries decoded alone brought to their destinations
+};
+// sources in device memory (zgpu_decode_frames_device_src): Call::srcs[i] is device memory; what was found out about every entry before the
+// first submit
+struct DeviceSources {
+  Engine::Skeleton sk;                  // the records zg_k_walk brought back
+  std::vector<Engine::DevEntry> dev;    // the entries as the engine takes them (a refused entry: length 0)
+  std::vector<uint8_t> refused;         // entries whose source or destination failed the pointer check (1), or the status (> 1) of an entry
+                                        // that is refused for another reason (ZGPU_E_SEEK_TABLE)
+  std::vector<uint64_t> bound;          // plaintext_bound of every entry, from its records
+  uint64_t* stats = nullptr;            // zgpu_ctx::frames_device_src_stats (kSrcStat*)
+};
+// ranges (zgpu_decode_ranges_device_src): the entries are the selections zg_k_seek found, and of the concatenation of an entry's decoded frames
+// only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
+struct Ranges {
+  struct Clip { uint64_t skip, len, declared; };
+  std::vector<Clip> clip;
+  bool promise = false;                 // (zgpu_decode_ranges_seek_table_device_src) declared is the seek table's promise: it always holds
+  uint64_t* stats = nullptr;            // zgpu_ctx::ranges_stats (kRangeStat*)
+};
+
+struct Call {
+  zgpu_ctx* c;
+  const uint8_t* const* srcs;
+  const size_t* lens;
+  uint8_t* const* dsts;                            // host sink: host memory; device sink: device memory of the caller (checked)
+  const size_t* caps;
+  zgpu_entry_result* res = nullptr;                // the host sink's results (nullptr with a device sink)
+  bool hash_forced = false;                        // host sink, development build (ZGPU_HASH_DEVICE_MAX): frames up to its hash_max on the device, no estimate
+  uint64_t host_hash_max = kHashDeviceMax;
+  DictLookup lookup;                               // shared dictionaries (zgpu_set_frames_shared_dicts): what the walks resolve ids with
+  bool shared;                                     //   the switch is on and a dictionary is registered: dicts() hands the lookup out
+  std::vector<std::pair<uint32_t, bool>> again;    // entries decoded again on their own after the submits (true: the walk met a dictionary frame)
+  DeviceSink* sink = nullptr;
+  DeviceSources* src = nullptr;
+  Ranges* ranges = nullptr;
+
+  Call(zgpu_ctx* ctx, const uint8_t* const* s, const size_t* l, uint8_t* const* d, const size_t* cp)
+      : c(ctx), srcs(s), lens(l), dsts(d), caps(cp), lookup{shared_find, ctx}, shared(ctx->frames_shared_dicts && !ctx->dicts.empty()) {}
+  const DictLookup* dicts() const { return shared ? &lookup : nullptr; }
+  uint64_t hash_max() const { return sink ? sink->hash_max : host_hash_max; }
+  // what of `bytes` decoded bytes of entry i its destination gets
+  uint64_t clipped(uint32_t i, uint64_t bytes) const {
+    if (!ranges) return bytes;
+    const Ranges::Clip& cl = ranges->clip[i];
+    const uint64_t rest = bytes > cl.skip ? bytes - cl.skip : 0;
+    return rest < cl.len ? rest : cl.len;
+  }
+  zgpu_entry_result& result(uint32_t i) const { return sink ? sink->res[i].r : res[i]; }
+};
 
 // the device copy of a registered dictionary, uploaded at first use (zg_dictfill.h: DictImage; the formats are zg_apply_dict's)
 int dict_image(zgpu_ctx* c, uint32_t id, zgd::DictImage* out) {
@@ -191,18 +220,18 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   std::vector<int>& walk = u.walk;
   std::vector<uint32_t>& ff = u.ff;
   int st;
-  if (k.sk) {   // the bytes are on the device: no staging, no upload — the skeleton is parsed, one zg_k_gather launch moves the entries
-    if ((st = k.c->eng->prepare_entries_device(k.dev, *k.sk, idx, off.data(), n, total_in, &u.b, &walk, &ff, k.dicts))) return st;
-    k.sstats[3] += u.b->gather_launched ? 1u : 0u; k.sstats[4] += u.b->gather_us;
+  if (k.src) {   // the bytes are on the device: no staging, no upload — the skeleton is parsed, one zg_k_gather launch moves the entries
+    if ((st = k.c->eng->prepare_entries_device(k.src->dev.data(), k.src->sk, idx, off.data(), n, total_in, &u.b, &walk, &ff, k.dicts()))) return st;
+    k.src->stats[kSrcStatGatherLaunches] += u.b->gather_launched ? 1u : 0u; k.src->stats[kSrcStatGatherUs] += u.b->gather_us;
   } else {
     if ((st = in.get(total_in))) return st;
     parallel_for(n, total_in, 8u << 20, [&](uint32_t j) { if (len[j]) memcpy(in.p + off[j], k.srcs[idx[j]], len[j]); });
-    if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff, k.dicts))) return st;
+    if ((st = k.c->eng->prepare_entries(in.p, total_in, off.data(), len.data(), n, &u.b, &walk, &ff, k.dicts()))) return st;
   }
   Batch* b = u.b;
   // the submit's dictionary frames (none unless the walks had a lookup): their dictionaries' device copies, for zg_k_dictfill
   std::vector<uint8_t> has_dict(n, 0);
-  if (k.dicts) {
+  if (k.shared) {
     std::vector<zgd::DictImage> images(b->info.size(), zgd::DictImage{});
     if (b->info.size() != b->bb.frames.size()) return ZGPU_E_INTERNAL;
     for (uint32_t j = 0; j < n; j++)
@@ -218,14 +247,14 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   const std::vector<ZgFrameOut>& fo = b->frame_out;
   if (fo.size() != b->info.size()) return ZGPU_E_INTERNAL;
   uint64_t* ds = k.c->frames_dict_stats;
-  ds[1] += b->dictfill_launches; ds[2] += b->dictfill_bytes; ds[3] += b->dictfill_us;
+  ds[kDictStatFillLaunches] += b->dictfill_launches; ds[kDictStatBytesReplicated] += b->dictfill_bytes; ds[kDictStatFillUs] += b->dictfill_us;
 
   // verdicts (zgpu_decode_all, zg_capi.cpp, on the entry's own frames)
   for (uint32_t j = 0; j < n; j++) {
     const uint32_t i = idx[j];
     zgpu_entry_result& r = k.result(i);
     // zgpu_decode_all's frame-by-frame path (the switch off, or an id the lookup did not resolve)
-    if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); ds[4] += k.dicts ? 1u : 0u; continue; }
+    if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); ds[kDictStatEntriesAlone] += k.shared ? 1u : 0u; continue; }
     int dev = 0;
     uint64_t bytes = 0;
     bool small = false;   // (has_dict) the entry's output up to a frame in front of the first failing one does not fit
@@ -234,24 +263,24 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       if (!dev && fo[f].status) dev = (int)fo[f].status;
       bytes += fo[f].out_size;
       if (has_dict[j] && !dev && !b->info[f].host_status && k.clipped(i, bytes) > k.caps[i]) small = true;
-      if (k.clip && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
+      if (k.ranges && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
     }
-    if (k.promise && bytes != k.clip[i].declared) lied = true;   // (the selection yields another length than its seek table says)
-    if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[4] += has_dict[j]; continue; }
-    if (k.rstats) { k.rstats[5] += ff[j + 1] - ff[j]; k.rstats[6] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
+    if (k.ranges && k.ranges->promise && bytes != k.ranges->clip[i].declared) lied = true;   // (the selection yields another length than its seek table says)
+    if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[kDictStatEntriesAlone] += has_dict[j]; continue; }
+    if (k.ranges) { k.ranges->stats[kRangeStatFramesDecoded] += ff[j + 1] - ff[j]; k.ranges->stats[kRangeStatPlaintextDecoded] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
     // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
     // next one is looked at), so a frame that does not fit ends it with TargetTooSmall BEFORE a later frame's error or the walk's; without one,
     // zgpu_decode_all's one submit reports a device error first, then the walk's, then TargetTooSmall.
     // (ranges have ONE order, with or without dictionary frames, in a submit or alone: the decode and walk verdicts, ContentSizeMismatch,
     // TargetTooSmall by the clipped count — taken in coordinates that the declared sizes define —, then the checksum verdict)
-    if (has_dict[j] && !k.clip) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j] ? walk[j] : ZGPU_OK;
+    if (has_dict[j] && !k.ranges) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j] ? walk[j] : ZGPU_OK;
     else r.status = dev ? dev : walk[j] ? walk[j] : lied ? ZGPU_E_CONTENT_SIZE_MISMATCH : k.clipped(i, bytes) > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
     if (r.status) continue;
-    if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[0] += b->bb.frames[f].dict_len ? 1u : 0u;
+    if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[kDictStatFramesShared] += b->bb.frames[f].dict_len ? 1u : 0u;
     r.written = k.clipped(i, bytes);
     r.nframes = ff[j + 1] - ff[j];
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (fo[f].out_size <= k.hash_max || (k.hash_all && b->info[f].has_checksum)) u.cand.push_back(f);   // (candidates)
+      if (fo[f].out_size <= k.hash_max() || (k.sink && k.sink->hash_all && b->info[f].has_checksum)) u.cand.push_back(f);   // (candidates)
       const uint64_t e = fo[f].out_base + fo[f].out_size;
       if (e > u.down) u.down = e;
     }
@@ -259,28 +288,47 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   return ZGPU_OK;
 }
 
+// A device-sink entry fails with `status`: written = nframes = 0 like any failed entry (sums / bad: the two counts of the checksum verdict,
+// which say why). The arguments are taken by value: they may be d's own fields.
+void fail_entry(zgpu_device_entry_result& d, int status, uint32_t sums = 0, uint32_t bad = 0) {
+  memset(&d, 0, sizeof d);
+  d.r.status = status;
+  d.r.checksums = sums; d.r.checksum_mismatches = bad;
+}
+
+// What both sinks do about hashing: the frames of u.cand, as the sink left that list, are hashed by the device — launch() enqueues the kernel
+// on the first stream, and the sink does its copying beside it; wait() collects the digests (*kernel_us, if asked for: the kernel's time).
+struct SubmitHash {
+  std::vector<uint8_t> on_dev;    // per frame of the submit: hashed on the device
+  std::vector<uint64_t> digest;   // per frame: its XXH64 (on_dev frames after wait(); the host sink fills in the others)
+  int launch(const Submit& u) {
+    on_dev.assign(u.b->frame_out.size(), 0);
+    for (uint32_t f : u.cand) on_dev[f] = 1;
+    return u.b->hash_launch(u.cand.data(), (uint32_t)u.cand.size());
+  }
+  int wait(const Submit& u, uint64_t* kernel_us = nullptr) {
+    digest.assign(u.b->frame_out.size(), 0);
+    std::vector<uint64_t> dh(u.cand.size());
+    const int st = u.b->hash_wait(dh.data(), kernel_us);
+    for (size_t q = 0; q < u.cand.size() && !st; q++) digest[u.cand[q]] = dh[q];
+    return st;
+  }
+};
+
 // the host sink: the plaintext comes back, goes to the callers' buffers on the host threads, and the frames the device did not hash are hashed there
 int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   Batch* b = u.b;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
   const std::vector<int>& walk = u.walk;
   const std::vector<uint32_t>& ff = u.ff;
-  std::vector<uint32_t>& dev_hash = u.cand;   // frames hashed on the device
   const uint64_t down = u.down;                // output bytes the host needs (of entries that succeed)
   int st;
-  if (!k.hash_forced && !hash_on_device(dev_hash, fo)) dev_hash.clear();
-  std::vector<uint8_t> on_dev(fo.size(), 0);
-  for (uint32_t f : dev_hash) on_dev[f] = 1;
+  if (!k.hash_forced && !hash_on_device(u.cand, fo)) u.cand.clear();   // (what stays is hashed on the device)
+  SubmitHash h;
   // the device hashes its frames while the output comes back
-  if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) return st;
+  if ((st = h.launch(u))) return st;
   Staging out;
-  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down))) return st;
-  std::vector<uint64_t> digest(fo.size(), 0);
-  {
-    std::vector<uint64_t> dh(dev_hash.size());
-    if ((st = b->hash_wait(dh.data()))) return st;
-    for (size_t q = 0; q < dev_hash.size(); q++) digest[dev_hash[q]] = dh[q];
-  }
+  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down)) || (st = h.wait(u))) return st;
   // bytes to the callers' buffers; the long frames hashed here, from those bytes
   parallel_for(n, down, 4u << 20, [&](uint32_t j) {
     zgpu_entry_result& r = k.res[idx[j]];
@@ -291,7 +339,7 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       const uint8_t* s = out.p + fo[f].out_base;
       if (fo[f].out_size) memcpy(d + at, s, fo[f].out_size);
       at += fo[f].out_size;
-      if (!on_dev[f]) digest[f] = zgx::xxh64(s, fo[f].out_size, 0);
+      if (!h.on_dev[f]) h.digest[f] = zgx::xxh64(s, fo[f].out_size, 0);
     }
   });
   for (uint32_t j = 0; j < n; j++) {
@@ -299,7 +347,7 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if (r.status || r.nframes == 0) continue;
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       const FrameInfo& fi = b->info[f];
-      const uint32_t calc = (uint32_t)digest[f];
+      const uint32_t calc = (uint32_t)h.digest[f];
       if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = calc; }
       if (fi.has_checksum) { r.checksums++; if (fi.checksum != calc) r.checksum_mismatches++; }
     }
@@ -315,20 +363,21 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   Batch* b = u.b;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
   const std::vector<uint32_t>& ff = u.ff;
-  std::vector<uint32_t>& dev_hash = u.cand;
-  if (k.no_hash) dev_hash.clear();
-  std::vector<uint8_t> on_dev(fo.size(), 0);
-  for (uint32_t f : dev_hash) on_dev[f] = 1;
+  DeviceSink& sink = *k.sink;
+  zgpu_device_entry_result* const dres = sink.res;
+  if (sink.no_hash) u.cand.clear();
+  SubmitHash h;
   int st;
-  if ((st = b->hash_launch(dev_hash.data(), (uint32_t)dev_hash.size()))) return st;
+  if ((st = h.launch(u))) return st;
   uint64_t bytes = 0;
   auto scatter = [&]() -> int {   // the frames of every entry that stands at status 0, in one launch
     std::vector<zgs::Seg> segs;
     for (uint32_t j = 0; j < n; j++) {
-      const zgpu_entry_result& r = k.dres[idx[j]].r;
+      const zgpu_entry_result& r = dres[idx[j]].r;
       if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
       // (ranges: a frame's segment is clipped to [lo, hi) of the concatenation of the entry's frames; a clipped frame is just a shorter segment)
-      const uint64_t lo = k.clip ? k.clip[idx[j]].skip : 0, hi = k.clip && k.clip[idx[j]].len < UINT64_MAX - lo ? lo + k.clip[idx[j]].len : UINT64_MAX;
+      const Ranges::Clip* cl = k.ranges ? &k.ranges->clip[idx[j]] : nullptr;
+      const uint64_t lo = cl ? cl->skip : 0, hi = cl && cl->len < UINT64_MAX - lo ? lo + cl->len : UINT64_MAX;
       uint64_t cat = 0, at = 0;
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
         const uint64_t a = cat, e = cat + fo[f].out_size, s = a > lo ? a : lo, t = e < hi ? e : hi;
@@ -343,52 +392,46 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
     return b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk);
   };
-  if (!k.verify && (st = scatter())) return st;
-  std::vector<uint64_t> digest(fo.size(), 0);
-  {
-    std::vector<uint64_t> dh(dev_hash.size());
-    uint64_t hash_us = 0;
-    if ((st = b->hash_wait(dh.data(), &hash_us))) return st;
-    k.stats[8] += hash_us;
-    for (size_t q = 0; q < dev_hash.size(); q++) digest[dev_hash[q]] = dh[q];
-  }
-  if (k.verify) {
+  if (!sink.verify && (st = scatter())) return st;
+  uint64_t hash_us = 0;
+  if ((st = h.wait(u, &hash_us))) return st;
+  sink.stats[kDevStatHashUs] += hash_us;
+  auto count_frame = [&](uint32_t f) { sink.stats[h.on_dev[f] ? kDevStatFramesHashed : kDevStatFramesNotHashed]++; };
+  if (sink.verify) {
     // the verdict of verification ranks behind every other one: only entries that stand at status 0 are looked at
     for (uint32_t j = 0; j < n; j++) {
-      zgpu_entry_result& r = k.dres[idx[j]].r;
+      zgpu_entry_result& r = dres[idx[j]].r;
       if (r.status || r.nframes == 0) continue;
       uint32_t sums = 0, bad = 0;
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
         const FrameInfo& fi = b->info[f];
         if (!fi.has_checksum) continue;
         sums++;
-        if (on_dev[f] && fi.checksum != (uint32_t)digest[f]) bad++;
+        if (h.on_dev[f] && fi.checksum != (uint32_t)h.digest[f]) bad++;
       }
       if (!bad) continue;
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) k.stats[on_dev[f] ? 4 : 5]++;
-      memset(&k.dres[idx[j]], 0, sizeof k.dres[idx[j]]);   // written = nframes = 0, like any failed entry; the two counts say why
-      r.status = ZGPU_E_CHECKSUM_MISMATCH;
-      r.checksums = sums; r.checksum_mismatches = bad;
-      k.stats[7]++;
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
+      fail_entry(dres[idx[j]], ZGPU_E_CHECKSUM_MISMATCH, sums, bad);
+      sink.stats[kDevStatEntriesFailedVerify]++;
     }
     if ((st = scatter())) return st;
   }
   uint64_t us = 0;
   bool launched = false;
   if ((st = b->scatter_wait(&us, &launched))) return st;
-  k.stats[1] += launched ? 1u : 0u; k.stats[2] += bytes; k.stats[3] += us;
+  sink.stats[kDevStatScatterLaunches] += launched ? 1u : 0u; sink.stats[kDevStatBytesScattered] += bytes; sink.stats[kDevStatScatterUs] += us;
   for (uint32_t j = 0; j < n; j++) {
-    zgpu_device_entry_result& d = k.dres[idx[j]];
+    zgpu_device_entry_result& d = dres[idx[j]];
     zgpu_entry_result& r = d.r;
     if (r.status || r.nframes == 0) continue;
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       const FrameInfo& fi = b->info[f];
-      const uint32_t calc = (uint32_t)digest[f];
-      k.stats[on_dev[f] ? 4 : 5]++;
-      if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = on_dev[f] ? calc : 0u; d.first_hashed = on_dev[f]; }
+      const uint32_t calc = (uint32_t)h.digest[f];
+      count_frame(f);
+      if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = h.on_dev[f] ? calc : 0u; d.first_hashed = h.on_dev[f]; }
       if (!fi.has_checksum) continue;
       r.checksums++;
-      if (!on_dev[f]) d.checksums_unverified++;
+      if (!h.on_dev[f]) d.checksums_unverified++;
       else if (fi.checksum != calc) r.checksum_mismatches++;
     }
   }
@@ -400,7 +443,7 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
   Submit u;
   int st = decode_submit(k, idx, n, u);
   if (st) return st;
-  return k.dres ? sink_device(k, idx, n, u) : sink_host(k, idx, n, u);
+  return k.sink ? sink_device(k, idx, n, u) : sink_host(k, idx, n, u);
 }
 
 // an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
@@ -452,62 +495,60 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
 // the device sink's form of decode_alone: into a host buffer (no larger than the entry can need), then one H2D to the caller's memory. The host
 // hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
 int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
+  DeviceSink& sink = *k.sink;
+  const Ranges::Clip* clip = k.ranges ? &k.ranges->clip[i] : nullptr;
   std::vector<uint8_t> down;   // device sources: the entry comes to the host with one D2H (rare; correct first)
-  if (k.sk) {
+  if (k.src) {
     try { down.resize(k.lens[i] ? k.lens[i] : 1); } catch (...) { return ZGPU_E_NOMEM; }
     if (k.lens[i] && hipMemcpy(down.data(), k.srcs[i], k.lens[i], hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-    k.sstats[5] += k.lens[i];
+    k.src->stats[kSrcStatInputBytesToHost] += k.lens[i];
   }
-  const uint8_t* src = k.sk ? down.data() : k.srcs[i];
+  const uint8_t* src = k.src ? down.data() : k.srcs[i];
   const uint64_t bound = plaintext_bound(src, k.lens[i]);
   // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i]. Ranges: the whole selection is decoded, and clipped below)
-  const size_t cap = k.clip ? (size_t)bound : k.caps[i] < bound ? k.caps[i] : (size_t)bound;
+  const size_t cap = clip ? (size_t)bound : k.caps[i] < bound ? k.caps[i] : (size_t)bound;
   uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
   if (!tmp) return ZGPU_E_NOMEM;
   bool summed = false;
   uint32_t size_lies = 0;
   int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies);
-  zgpu_device_entry_result& d = k.dres[i];
+  zgpu_device_entry_result& d = sink.res[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
-  if (k.rstats && !st && !d.r.status) { k.rstats[5] += d.r.nframes; k.rstats[6] += d.r.written; }
+  const bool ok = !st;   // (the call itself goes on; below, `ok && !d.r.status` is an entry that still stands)
+  if (k.ranges && ok && !d.r.status) { k.ranges->stats[kRangeStatFramesDecoded] += d.r.nframes; k.ranges->stats[kRangeStatPlaintextDecoded] += d.r.written; }
   // ranges, in the order of a submit's verdicts (decode_submit): the size check, TargetTooSmall by the clipped count, then the checksums.
   // The size check is per frame, from the frame-by-frame pass; should that pass have failed (never seen), the frames are measured together.
   // The buffer holds the selection's bound: every frame's declared size, or what its block headers allow where that is less. Only a frame
   // that yields more than it declares can overflow it.
-  if (k.clip && !st && d.r.status == ZGPU_E_TARGET_TOO_SMALL) { memset(&d, 0, sizeof d); d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH; }
-  if (k.clip && !st && !d.r.status &&
-      ((summed ? size_lies != 0 : k.clip[i].declared != UINT64_MAX && d.r.written != k.clip[i].declared) ||
-       (k.promise && d.r.written != k.clip[i].declared))) {
-    memset(&d, 0, sizeof d);
-    d.r.status = ZGPU_E_CONTENT_SIZE_MISMATCH;
-  }
-  if (k.clip && !st && !d.r.status && k.clipped(i, d.r.written) > k.caps[i]) { memset(&d, 0, sizeof d); d.r.status = ZGPU_E_TARGET_TOO_SMALL; }
+  if (clip && ok && d.r.status == ZGPU_E_TARGET_TOO_SMALL) fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
+  if (clip && ok && !d.r.status &&
+      ((summed ? size_lies != 0 : clip->declared != UINT64_MAX && d.r.written != clip->declared) ||
+       (k.ranges->promise && d.r.written != clip->declared)))
+    fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
+  if (clip && ok && !d.r.status && k.clipped(i, d.r.written) > k.caps[i]) fail_entry(d, ZGPU_E_TARGET_TOO_SMALL);
   // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its one H2D
-  if (!st && !d.r.status && k.verify && summed && !k.no_hash && d.r.checksum_mismatches) {
-    const uint32_t sums = d.r.checksums, bad = d.r.checksum_mismatches;
-    k.stats[4] += d.r.nframes;
-    memset(&d, 0, sizeof d);
-    d.r.status = ZGPU_E_CHECKSUM_MISMATCH;
-    d.r.checksums = sums; d.r.checksum_mismatches = bad;
-    k.stats[7]++;
+  if (ok && !d.r.status && sink.verify && summed && !sink.no_hash && d.r.checksum_mismatches) {
+    sink.stats[kDevStatFramesHashed] += d.r.nframes;
+    fail_entry(d, ZGPU_E_CHECKSUM_MISMATCH, d.r.checksums, d.r.checksum_mismatches);
+    sink.stats[kDevStatEntriesFailedVerify]++;
   }
   size_t from = 0;   // ranges: only the clipped bytes are uploaded
-  if (k.clip && !st && !d.r.status) {
+  if (clip && ok && !d.r.status) {
     const uint64_t w = k.clipped(i, d.r.written);
-    from = (size_t)(k.clip[i].skip < d.r.written ? k.clip[i].skip : d.r.written);
+    from = (size_t)(clip->skip < d.r.written ? clip->skip : d.r.written);
     d.r.written = w;
   }
-  if (!st && !d.r.status) {
+  if (ok && !d.r.status) {
     if (d.r.written && hipMemcpy(k.dsts[i], tmp + from, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
-    k.alone_written += d.r.written;
-    const bool hashed = summed && !k.no_hash && d.r.nframes;
-    if (k.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
+    sink.alone_written += d.r.written;
+    const bool hashed = summed && !sink.no_hash && d.r.nframes;
+    if (sink.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
     d.first_hashed = hashed ? 1u : 0u;
-    k.stats[hashed ? 4 : 5] += d.r.nframes;
+    sink.stats[hashed ? kDevStatFramesHashed : kDevStatFramesNotHashed] += d.r.nframes;
   }
   free(tmp);
-  k.stats[6]++;
+  sink.stats[kDevStatEntriesAlone]++;
   return st;
 }
 
@@ -533,13 +574,91 @@ bool check_device_range(int device, const void* p, size_t cap, std::vector<DevRa
   return true;
 }
 
+// Every pointer of a call's entries checked, and the entries as the engine takes them: a refused entry has length 0 — nothing of it is
+// read — and refused[i] = 1. dsts / caps: nullptr for a call without destinations. pre(i), the call's own reasons: kCheck — the pointers
+// decide; kRefuse — refused without a look at them; kPass — never refused, whatever its pointers are (nothing of it will be touched).
+enum { kCheck = 0, kRefuse, kPass };
+template <class Pre>
+void check_entries(zgpu_ctx* c, const void* const* srcs, const size_t* lens, void* const* dsts, const size_t* caps, uint32_t n, Pre pre,
+                   std::vector<Engine::DevEntry>* dev, std::vector<uint8_t>* refused) {
+  dev->resize(n);
+  refused->assign(n, 0);
+  std::vector<DevRange> known;   // (per call: what the runtime says of an allocation holds for as long as the caller keeps its promise)
+  const int device = c->eng->device();
+  for (uint32_t i = 0; i < n; i++) {
+    const int p = pre(i);
+    bool bad = p == kRefuse;
+    if (p == kCheck) {
+      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]);
+      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
+      if (!bad && dsts && caps[i]) bad = !check_device_range(device, dsts[i], caps[i], known);
+    }
+    (*refused)[i] = bad;
+    (*dev)[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i]};
+  }
+}
+inline int check_all(uint32_t) { return kCheck; }
+
+// the zgpu_debug_*_stats getters: the first n slots of an array, or all it has; returns how many
+template <size_t N> int copy_stats(const uint64_t (&a)[N], uint64_t* out, int n) {
+  if (!out) return 0;
+  int k = 0;
+  for (; k < n && k < (int)N; k++) out[k] = a[k];
+  return k;
+}
+
+// The statistics a call family owns, zeroed at its start (after its arguments passed): the one place that says which arrays a call writes.
+enum : unsigned { kOwnsDecode = 1 /* frames_submits, frames_dict_stats */, kOwnsDevice = 2, kOwnsSrc = 4, kOwnsIndex = 8, kOwnsRanges = 16 };
+void reset_stats(zgpu_ctx* c, unsigned owned) {
+  auto zero = [](auto& a) { for (uint64_t& x : a) x = 0; };
+  if (owned & kOwnsDecode) { c->frames_submits = 0; zero(c->frames_dict_stats); }
+  if (owned & kOwnsDevice) zero(c->frames_device_stats);
+  if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
+  if (owned & kOwnsIndex) zero(c->frames_index_stats);
+  if (owned & kOwnsRanges) zero(c->ranges_stats);
+}
+
+// The end of every call that launched something: nothing of it is in flight on the engine's two streams (the scatter ran on the second), so
+// every later operation on any stream sees its bytes. The call's first status stands.
+int drain(zgpu_ctx* c, int st) {
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  return st;
+}
+
+// The device sink of a call, from its options. ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY (hash nothing, verify everything) is refused: *st.
+DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st) {
+  const uint32_t flags = opts ? opts->flags : 0u;
+  DeviceSink s;
+  s.res = results;
+  s.hash_max = opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax;
+  s.no_hash = (flags & ZGPU_DEVICE_NO_HASH) != 0;
+  s.verify = (flags & ZGPU_DEVICE_VERIFY) != 0;
+  s.hash_all = s.verify && !opts->hash_max_bytes;
+  s.stats = c->frames_device_stats;
+  *st = s.no_hash && s.verify ? ZGPU_E_BAD_ARG : ZGPU_OK;
+  return s;
+}
+
+// The device sources of a call whose pointers are checked (src->dev, src->refused): every entry's header chain walked on the device (two
+// launches for the whole call) and its bound taken from the records, before the first submit is cut.
+int device_sources(const Call& k, uint32_t n, DeviceSources* src) {
+  src->stats = k.c->frames_device_src_stats;
+  src->bound.assign(n, 0);
+  int st = k.c->eng->walk_entries(src->dev.data(), n, &src->sk, src->stats);
+  for (uint32_t i = 0; i < n && !st; i++) {
+    bool consistent = true;
+    const Engine::Skeleton& sk = src->sk;
+    src->bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)src->dev[i].len, &consistent, k.dicts());
+    if (!consistent) { k.c->eng->last_error = "zg_k_walk: an entry's records out of step with its length"; st = ZGPU_E_INTERNAL; }   // (never)
+  }
+  return st;
+}
+
 // the entries cut into submits (an entry is never split), then the again-list
 int decode_entries(Call& k, uint32_t n) {
   zgpu_ctx* c = k.c;
   const Tuning& tn = c->eng->tuning();
   const uint64_t S = tn.frames_submit_bytes ? tn.frames_submit_bytes : kFramesSubmitBytes;
-  c->frames_submits = 0;
-  for (uint64_t& x : c->frames_dict_stats) x = 0;
   std::vector<DevRange> known;
   std::vector<uint32_t> group;
   uint64_t in_group = 0, in_bytes = 0;   // plaintext bound and input bytes of the submit being gathered (both bounded by S)
@@ -547,13 +666,13 @@ int decode_entries(Call& k, uint32_t n) {
   for (uint32_t i = 0; i <= n && !st; i++) {
     uint64_t bound = 0;
     if (i < n) {
-      if (k.dres) memset(&k.dres[i], 0, sizeof k.dres[i]);
+      if (k.sink) memset(&k.sink->res[i], 0, sizeof k.sink->res[i]);
       else memset(&k.res[i], 0, sizeof k.res[i]);
       bool bad = (!k.srcs[i] && k.lens[i]) || (!k.dsts[i] && k.caps[i]);   // (what zgpu_decode_all returns)
-      if (k.sk) bad = k.refused[i] != 0;                                   // (device sources: checked before the walk)
-      else if (!bad && k.dres && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
-      if (bad) { k.result(i).status = k.sk && k.refused[i] > 1 ? k.refused[i] : ZGPU_E_BAD_ARG; continue; }   // (refused[i] > 1: the status itself)
-      bound = k.sk ? k.bound[i] : plaintext_bound(k.srcs[i], k.lens[i], k.dicts);   // (with its dictionary frames' gaps)
+      if (k.src) bad = k.src->refused[i] != 0;                             // (device sources: checked before the walk)
+      else if (!bad && k.sink && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
+      if (bad) { k.result(i).status = k.src && k.src->refused[i] > 1 ? k.src->refused[i] : ZGPU_E_BAD_ARG; continue; }   // (refused[i] > 1: the status itself)
+      bound = k.src ? k.src->bound[i] : plaintext_bound(k.srcs[i], k.lens[i], k.dicts());   // (with its dictionary frames' gaps)
     }
     // the submit is full (or this is the end): run it. An entry larger than S is a submit of its own. (The input is bounded too: entries that
     // yield nothing — skippable frames, garbage — still travel to the device, through the pinned staging.)
@@ -567,8 +686,16 @@ int decode_entries(Call& k, uint32_t n) {
   }
   for (size_t q = 0; q < k.again.size() && !st; q++) {
     const uint32_t i = k.again[q].first;
-    st = k.dres ? decode_alone_device(k, i, k.again[q].second) : decode_alone(k, i, k.again[q].second, k.dsts[i], k.caps[i]);
+    st = k.sink ? decode_alone_device(k, i, k.again[q].second) : decode_alone(k, i, k.again[q].second, k.dsts[i], k.caps[i]);
   }
+  return st;
+}
+
+// a device-sink call from its first submit to its end: the streams drained, the submits counted
+int finish_device_call(Call& k, uint32_t n, int st) {
+  if (!st) st = decode_entries(k, n);
+  st = drain(k.c, st);
+  k.sink->stats[kDevStatSubmits] = k.c->frames_submits;
   return st;
 }
 
@@ -577,32 +704,26 @@ int decode_entries(Call& k, uint32_t n) {
 extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, uint8_t* const* dsts, const size_t* caps,
                                   zgpu_entry_result* results) {
   if (!c || (n && (!srcs || !lens || !dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  reset_stats(c, kOwnsDecode);
   const Tuning& tn = c->eng->tuning();
-  Call k{c, srcs, lens, dsts, caps, results, tn.hash_device_max_set, tn.hash_device_max_set ? tn.hash_device_max : kHashDeviceMax, {}};
-  const DictLookup lookup{shared_find, c};
-  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
+  Call k(c, srcs, lens, dsts, caps);
+  k.res = results;
+  k.hash_forced = tn.hash_device_max_set;
+  if (tn.hash_device_max_set) k.host_hash_max = tn.hash_device_max;
   return decode_entries(k, n);
 }
 
 extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
                                          const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
   if (!c || (n && (!srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
-  for (uint64_t& x : c->frames_device_stats) x = 0;
+  int st;
+  DeviceSink sink = device_sink(c, opts, results, &st);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice);
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  Call k{c, srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
-  k.dres = results;
-  k.no_hash = opts && (opts->flags & 1u);
-  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
-  k.hash_all = k.verify && !opts->hash_max_bytes;
-  k.stats = c->frames_device_stats;
-  const DictLookup lookup{shared_find, c};
-  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
-  int st = decode_entries(k, n);
-  // every later operation on any stream sees the bytes: nothing of this call is in flight on the engine's streams (the scatter ran on the second)
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
-  k.stats[0] = c->frames_submits;
-  return st;
+  Call k(c, srcs, lens, (uint8_t* const*)device_dsts, caps);
+  k.sink = &sink;
+  return finish_device_call(k, n, ZGPU_OK);
 }
 
 // Sources in device memory: every pointer is checked, every entry's header chain walked on the device (two launches for the whole call) and
@@ -610,50 +731,19 @@ extern "C" int zgpu_decode_frames_device(zgpu_ctx* c, const uint8_t* const* srcs
 extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, void* const* device_dsts,
                                              const size_t* caps, const zgpu_device_opts* opts, zgpu_device_entry_result* results) {
   if (!c || (n && (!device_srcs || !lens || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
-  for (uint64_t& x : c->frames_device_stats) x = 0;
-  for (uint64_t& x : c->frames_device_src_stats) x = 0;
+  int st;
+  DeviceSink sink = device_sink(c, opts, results, &st);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc);
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  Call k{c, (const uint8_t* const*)device_srcs, lens, (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
-  k.dres = results;
-  k.no_hash = opts && (opts->flags & 1u);
-  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
-  k.hash_all = k.verify && !opts->hash_max_bytes;
-  k.stats = c->frames_device_stats;
-  k.sstats = c->frames_device_src_stats;
-  const DictLookup lookup{shared_find, c};
-  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
-  for (uint64_t& x : c->frames_dict_stats) x = 0;
-  std::vector<uint8_t> refused(n, 0);
-  std::vector<Engine::DevEntry> dev(n);
-  std::vector<uint64_t> bound(n, 0);
-  Engine::Skeleton sk;
-  {
-    std::vector<DevRange> known;
-    for (uint32_t i = 0; i < n; i++) {
-      bool bad = (!device_srcs[i] && lens[i]) || (!device_dsts[i] && caps[i]);
-      if (!bad && lens[i]) bad = !check_device_range(c->eng->device(), device_srcs[i], lens[i], known);
-      if (!bad && caps[i]) bad = !check_device_range(c->eng->device(), device_dsts[i], caps[i], known);
-      refused[i] = bad;
-      dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)device_srcs[i], bad ? 0u : (uint64_t)lens[i]};   // (a refused entry is not read)
-    }
-  }
-  int st = c->eng->walk_entries(dev.data(), n, &sk, k.sstats);
-  for (uint32_t i = 0; i < n && !st; i++) {
-    bool consistent = true;
-    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent, k.dicts);
-    if (!consistent) st = ZGPU_E_INTERNAL;
-  }
-  if (!st) {
-    k.sk = &sk; k.dev = dev.data(); k.refused = refused.data(); k.bound = bound.data();
-    st = decode_entries(k, n);
-  } else {
+  Call k(c, (const uint8_t* const*)device_srcs, lens, (uint8_t* const*)device_dsts, caps);
+  k.sink = &sink;
+  DeviceSources src;
+  check_entries(c, device_srcs, lens, device_dsts, caps, n, check_all, &src.dev, &src.refused);
+  if ((st = device_sources(k, n, &src)))   // (no submit is cut: every entry reports nothing)
     for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
-    c->frames_submits = 0;
-  }
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
-  k.stats[0] = c->frames_submits;
-  return st;
+  k.src = &src;
+  return finish_device_call(k, n, st);
 }
 // ---- the hash kernels on ranges of the caller's choice (measurement and tests) ---------------------------------------------------------------
 // [base, base + max(off + len)) passes the check the device sources pass before anything is launched; the ranges are sorted longest first as
@@ -674,25 +764,10 @@ extern "C" int zgpu_debug_hash_ranges(zgpu_ctx* c, const void* device_base, cons
   std::vector<ZgHashRange> r(n);
   for (uint32_t i = 0; i < n; i++) r[i] = ZgHashRange{offs[i], lens[i], i, 0};
   std::stable_sort(r.begin(), r.end(), [](const ZgHashRange& a, const ZgHashRange& b) { return a.len > b.len; });
-  const size_t rb = (size_t)n * sizeof(ZgHashRange);
-  DevBuf buf;
-  int st = buf.reserve(rb + (size_t)n * 8);
+  uint64_t pass[3] = {0, 0, 0};   // (one engine lane pass: the ranges are its lanes, the digests its records)
+  const int st = c->eng->hash_ranges_pass((const uint8_t*)device_base, r.data(), n, kernel, digests, pass);
   if (st) return st;
-  hipStream_t s = c->eng->stream();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  float ms = 0;
-  const bool ok = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess &&
-                  hipMemcpyAsync(buf.p, r.data(), rb, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
-                  hipEventRecord(ev[0], s) == hipSuccess &&
-                  (zg_launch_xxh64_with((const uint8_t*)device_base, buf.as<ZgHashRange>(), (uint64_t*)((uint8_t*)buf.p + rb), n, s, kernel), hipGetLastError() == hipSuccess) &&
-                  hipEventRecord(ev[1], s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
-                  hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess &&
-                  hipMemcpy(digests, (uint8_t*)buf.p + rb, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  if (!ok) (void)hipGetLastError();
-  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  buf.release();
-  if (!ok) return ZGPU_E_HIP;
-  c->hash_ranges_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  c->hash_ranges_us = pass[kPassUs];
   return ZGPU_OK;
 }
 extern "C" uint64_t zgpu_debug_hash_ranges_us(const zgpu_ctx* c) { return c ? c->hash_ranges_us : 0; }
@@ -708,19 +783,16 @@ namespace {
 // Both calls up to the summaries: every source checked, ONE summary launch over the entries that passed, entries[] filled.
 int index_summaries(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, zgpu_entry_index* entries,
                     std::vector<Engine::DevEntry>* dev, std::vector<zgi::Entry>* sum) {
-  for (uint64_t& x : c->frames_index_stats) x = 0;
+  reset_stats(c, kOwnsIndex);
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  dev->resize(n);
   sum->assign(n, zgi::Entry{});
-  std::vector<DevRange> known;
+  std::vector<uint8_t> refused;
+  check_entries(c, device_srcs, lens, nullptr, nullptr, n, check_all, dev, &refused);
   for (uint32_t i = 0; i < n; i++) {
     memset(&entries[i], 0, sizeof entries[i]);
-    const bool bad = lens[i] && !check_device_range(c->eng->device(), device_srcs[i], lens[i], known);
-    if (bad) entries[i].status = ZGPU_E_BAD_ARG;
-    (*dev)[i] = Engine::DevEntry{(uint64_t)(uintptr_t)device_srcs[i], bad ? 0u : (uint64_t)lens[i]};   // (a refused entry is not read)
+    if (refused[i]) entries[i].status = ZGPU_E_BAD_ARG;
   }
-  int st = c->eng->index_pass(dev->data(), n, nullptr, nullptr, sum->data(), nullptr, c->frames_index_stats);
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  const int st = drain(c, c->eng->index_pass(dev->data(), n, nullptr, nullptr, sum->data(), nullptr, c->frames_index_stats));
   if (st) return st;
   for (uint32_t i = 0; i < n; i++) {
     if (entries[i].status) { (*sum)[i] = zgi::Entry{}; continue; }
@@ -756,8 +828,7 @@ extern "C" int zgpu_frames_table_device(zgpu_ctx* c, const void* const* device_s
   if (!total) return ZGPU_OK;
   std::vector<zgi::Entry> again(n);
   std::vector<zgi::FrameRec> recs(total);
-  st = c->eng->index_pass(dev.data(), n, frame_first, sum.data(), again.data(), recs.data(), c->frames_index_stats);
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  st = drain(c, c->eng->index_pass(dev.data(), n, frame_first, sum.data(), again.data(), recs.data(), c->frames_index_stats));
   if (st) return st;
   for (uint32_t i = 0; i < n; i++) {
     if (entries[i].status) continue;
@@ -785,32 +856,12 @@ extern "C" int zgpu_frames_table_device(zgpu_ctx* c, const void* const* device_s
   }
   return ZGPU_OK;
 }
-extern "C" int zgpu_debug_frames_index_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c || !out) return 0;
-  int k = 0;
-  for (; k < n && k < 4; k++) out[k] = c->frames_index_stats[k];
-  return k;
-}
-extern "C" int zgpu_debug_frames_device_src_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c || !out) return 0;
-  int k = 0;
-  for (; k < n && k < 6; k++) out[k] = c->frames_device_src_stats[k];
-  return k;
-}
+extern "C" int zgpu_debug_frames_index_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_index_stats, out, n) : 0; }
+extern "C" int zgpu_debug_frames_device_src_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_device_src_stats, out, n) : 0; }
 extern "C" void zgpu_set_frames_shared_dicts(zgpu_ctx* c, int on) { if (c) c->frames_shared_dicts = on != 0; }
 extern "C" int zgpu_frames_shared_dicts(const zgpu_ctx* c) { return c && c->frames_shared_dicts ? 1 : 0; }
-extern "C" int zgpu_debug_frames_dict_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c || !out) return 0;
-  int k = 0;
-  for (; k < n && k < 5; k++) out[k] = c->frames_dict_stats[k];
-  return k;
-}
-extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c || !out) return 0;
-  int k = 0;
-  for (; k < n && k < 9; k++) out[k] = c->frames_device_stats[k];
-  return k;
-}
+extern "C" int zgpu_debug_frames_dict_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_dict_stats, out, n) : 0; }
+extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_device_stats, out, n) : 0; }
 
 // ---- byte ranges of device-resident entries (zg_seek.h) --------------------------------------------------------------------------------------
 static_assert(sizeof(zgpu_range) == 32 && sizeof(zgpu_seek) == sizeof(zgk::Seek) && sizeof(zgpu_range_result) == sizeof(zgpu_device_entry_result) + 64,
@@ -826,27 +877,21 @@ namespace {
 // comes from the seek table at the entry's end (ONE zg_k_seektab launch, a wave per entry); an anchored range is refused, the table is the index.
 int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* dsts, const size_t* caps,
                 std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused, bool table) {
-  for (uint64_t& x : c->ranges_stats) x = 0;
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   std::vector<zgk::Lane> lanes(table ? 0 : n);
   std::vector<zgt::Lane> waves(table ? n : 0);
   out->assign(n, zgk::Seek{});
-  refused->assign(n, 0);
-  std::vector<DevRange> known;
+  std::vector<Engine::DevEntry> dev;
+  // (a range of length 0 is never refused: nothing of its entry is touched; with a seek table an anchored range is refused, the table is the index)
+  check_entries(c, srcs, lens, dsts, caps, n,
+                [&](uint32_t i) { return !ranges[i].len ? kPass : table && (ranges[i].anchor_src || ranges[i].anchor_plain) ? kRefuse : kCheck; }, &dev, refused);
   for (uint32_t i = 0; i < n; i++) {
     const zgpu_range& g = ranges[i];
-    bool bad = false;
-    if (g.len) {
-      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]) || (table && (g.anchor_src || g.anchor_plain));
-      if (!bad && lens[i]) bad = !check_device_range(c->eng->device(), srcs[i], lens[i], known);
-      if (!bad && dsts && caps[i]) bad = !check_device_range(c->eng->device(), dsts[i], caps[i], known);
-    }
-    (*refused)[i] = bad;
-    if (table) waves[i] = zgt::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len};
-    else lanes[i] = zgk::Lane{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i], g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
+    const bool bad = (*refused)[i] != 0;
+    if (table) waves[i] = zgt::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len};
+    else lanes[i] = zgk::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
   }
-  int st = table ? c->eng->seektab_pass(waves.data(), n, out->data(), c->ranges_stats) : c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats);
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  const int st = drain(c, table ? c->eng->seektab_pass(waves.data(), n, out->data(), c->ranges_stats) : c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats));
   if (st) return st;
   for (uint32_t i = 0; i < n; i++) {
     zgk::Seek& s = (*out)[i];
@@ -855,28 +900,29 @@ int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32
       c->eng->last_error = "zgpu_frames_seek_device: a record that leaves its entry";
       return ZGPU_E_INTERNAL;
     }
-    c->ranges_stats[4] += s.frames_skipped;
+    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
   }
   return ZGPU_OK;
+}
+// the two seek calls: the records themselves are the answer
+int seek_only(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out, bool table) {
+  reset_stats(c, kOwnsRanges);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, table);
+  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
+  return st;
 }
 }  // namespace
 
 extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out) {
   if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, false);
-  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
-  return st;
+  return seek_only(c, device_srcs, lens, n, ranges, out, false);
 }
 extern "C" int zgpu_frames_seek_table_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
                                              zgpu_seek* out) {
   if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, true);
-  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
-  return st;
+  return seek_only(c, device_srcs, lens, n, ranges, out, true);
 }
 
 // The selections become the entries of zgpu_decode_frames_device_src's machinery: (src + src_lo, src_hi - src_lo) is walked, cut into submits,
@@ -889,63 +935,47 @@ namespace {
 int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* device_dsts,
                   const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results, bool table) {
   if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  if (opts && (opts->flags & ZGPU_DEVICE_NO_HASH) && (opts->flags & ZGPU_DEVICE_VERIFY)) return ZGPU_E_BAD_ARG;   // (hash nothing, verify everything)
-  for (uint64_t& x : c->frames_device_stats) x = 0;
-  for (uint64_t& x : c->frames_device_src_stats) x = 0;
-  for (uint64_t& x : c->frames_dict_stats) x = 0;
-  c->frames_submits = 0;
+  std::vector<zgpu_device_entry_result> dres(n);
+  int st;
+  DeviceSink sink = device_sink(c, opts, dres.data(), &st);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
   for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
   std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  int st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &refused, table);
-  if (st) return st;
+  DeviceSources src;
+  if ((st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &src.refused, table))) return st;
+  // the ranges part: the selections as entries (src.dev, in place of the whole entries seek_ranges checked) and what of each is wanted
   std::vector<const uint8_t*> srcs(n);
   std::vector<size_t> sub(n);
-  std::vector<Engine::DevEntry> dev(n);
-  std::vector<Call::Clip> clip(n);
-  std::vector<uint64_t> bound(n, 0);
-  std::vector<zgpu_device_entry_result> dres(n);
+  Ranges rg;
+  rg.clip.resize(n);
+  rg.promise = table;
+  rg.stats = c->ranges_stats;
+  src.dev.resize(n);
   for (uint32_t i = 0; i < n; i++) {
     const zgk::Seek& s = recs[i];
-    if (s.status) refused[i] = (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1);   // (an anchor behind the entry or behind begin; no usable table)
-    const bool none = refused[i] || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
+    if (s.status) src.refused[i] = (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1);   // (an anchor behind the entry or behind begin; no usable table)
+    const bool none = src.refused[i] || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
     srcs[i] = (const uint8_t*)device_srcs[i] + (none ? 0 : s.src_lo);
     sub[i] = none ? 0 : (size_t)(s.src_hi - s.src_lo);
-    dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
+    src.dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
     const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
-    clip[i] = Call::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX};   // (table: an entry of which nothing is taken promises nothing)
+    rg.clip[i] = Ranges::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX};   // (table: an entry of which nothing is taken promises nothing)
   }
-  Call k{c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps, nullptr, true, opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax, {}};
-  k.dres = dres.data();
-  k.no_hash = opts && (opts->flags & 1u);
-  k.verify = opts && (opts->flags & ZGPU_DEVICE_VERIFY);
-  k.hash_all = k.verify && !opts->hash_max_bytes;
-  k.stats = c->frames_device_stats;
-  k.sstats = c->frames_device_src_stats;
-  k.clip = clip.data();
-  k.promise = table;
-  k.rstats = c->ranges_stats;
-  const DictLookup lookup{shared_find, c};
-  if (c->frames_shared_dicts && !c->dicts.empty()) k.dicts = &lookup;
-  Engine::Skeleton sk;
-  st = c->eng->walk_entries(dev.data(), n, &sk, k.sstats);
-  for (uint32_t i = 0; i < n && !st; i++) {
-    bool consistent = true;
-    bound[i] = plaintext_bound_skel(sk.recs.data() + sk.first[i], (uint32_t)(sk.first[i + 1] - sk.first[i]), (size_t)dev[i].len, &consistent, k.dicts);
-    // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number)
-    if (!consistent || (!table && !k.dicts && sub[i] && bound[i] != recs[i].bound)) {
+  Call k(c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps);
+  k.sink = &sink;
+  k.ranges = &rg;
+  st = device_sources(k, n, &src);
+  // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number; the table's bound is its promise instead)
+  for (uint32_t i = 0; i < n && !st && !table && !k.shared; i++)
+    if (sub[i] && src.bound[i] != recs[i].bound) {
       c->eng->last_error = "zgpu_decode_ranges_device_src: a source changed between the seek and the walk";
       st = ZGPU_E_INTERNAL;
     }
-  }
-  if (!st) {
-    k.sk = &sk; k.dev = dev.data(); k.refused = refused.data(); k.bound = bound.data();
-    st = decode_entries(k, n);
-  }
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
-  k.stats[0] = c->frames_submits;
-  k.rstats[3] = k.sstats[5];
-  k.rstats[7] = k.stats[2] + k.alone_written;
+  k.src = &src;
+  st = finish_device_call(k, n, st);
+  rg.stats[kRangeStatInputBytesToHost] = src.stats[kSrcStatInputBytesToHost];
+  rg.stats[kRangeStatBytesWritten] = sink.stats[kDevStatBytesScattered] + sink.alone_written;
   for (uint32_t i = 0; i < n; i++) {
     if (!st) results[i].d = dres[i];
     memcpy(&results[i].seek, &recs[i], sizeof results[i].seek);
@@ -963,12 +993,7 @@ extern "C" int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx* c, const void*
                                                         const zgpu_device_opts* opts, zgpu_range_result* results) {
   return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, true);
 }
-extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c || !out) return 0;
-  int k = 0;
-  for (; k < n && k < 8; k++) out[k] = c->ranges_stats[k];
-  return k;
-}
+extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->ranges_stats, out, n) : 0; }
 
 extern "C" uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len) { return src || !len ? plaintext_bound(src, len) : 0; }
 extern "C" uint32_t zgpu_debug_frames_submits(const zgpu_ctx* c) { return c ? c->frames_submits : 0u; }
