@@ -7,12 +7,12 @@ import sys
 
 import pytest
 
+from devmem import MAGIC, oracle_alone, xxh64
 from golden_io import read_manifest, read_pack
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-MAGIC = (0xFD2FB528).to_bytes(4, "little")
 sys.path.insert(0, os.path.join(ROOT, "tools"))   # zgdata: the workload generators
 
 
@@ -22,19 +22,6 @@ def ctx():
     c = zgpu.Context(0)
     yield c
     c.close()
-
-
-def _xxh64(b):
-    import oracle
-    return oracle.lib().zor_xxh64(b, len(b), 0)
-
-
-def _oracle_alone(z, cap, dict_raw=None):
-    import oracle
-    d = oracle.FrameDecoder()
-    if dict_raw is not None:
-        d.add_dict(dict_raw)
-    return d.decode_all(z, cap)
 
 
 def _oracle_first_frame(z, dict_raw=None):
@@ -56,7 +43,7 @@ def _zgpu_alone(ctx, z, cap):
 def _check(ctx, entries, caps, res, dict_raw=None, first_frame=True):
     assert len(res) == len(entries)
     for i, (z, cap, r) in enumerate(zip(entries, caps, res)):
-        st, out = _oracle_alone(z, cap, dict_raw)
+        st, out = oracle_alone(z, cap, dict_raw)
         assert r.status == st, (i, r, st)
         zs, zout = _zgpu_alone(ctx, z, cap)
         assert r.status == zs, (i, r, zs)
@@ -133,7 +120,7 @@ def _isolation_entries():
     out += good
     caps = []
     for z in out:
-        st, o = _oracle_alone(z, 8 << 20)
+        st, o = oracle_alone(z, 8 << 20)
         caps.append(len(o) if st == 0 else (8 << 20))
     caps[-1] -= 1                                                           # one byte short: TargetTooSmall
     return out, caps
@@ -161,7 +148,7 @@ def _raw_frame(payload, checksum=True):
     bh = (1 | (0 << 1) | (len(payload) << 3)).to_bytes(3, "little")
     z = h + bh + payload
     if checksum:
-        z += (_xxh64(payload) & 0xFFFFFFFF).to_bytes(4, "little")
+        z += (xxh64(payload) & 0xFFFFFFFF).to_bytes(4, "little")
     return z
 
 
@@ -183,17 +170,17 @@ def test_checksums_reported_not_enforced(ctx):
     _check(ctx, entries, caps, res)
     r = res[0]
     assert (r.status, r.nframes, r.checksums, r.checksum_mismatches) == (0, 1, 1, 0)
-    assert r.calculated_checksum == r.checksum_from_data == _xxh64(text) & 0xFFFFFFFF
+    assert r.calculated_checksum == r.checksum_from_data == xxh64(text) & 0xFFFFFFFF
     r = res[1]
     assert (r.status, r.checksums, r.checksum_mismatches) == (0, 1, 1) and r.data == text
     r = res[2]
     assert (r.status, r.checksums, r.checksum_mismatches) == (0, 1, 0)
     r = res[3]
     assert (r.status, r.checksums, r.checksum_mismatches) == (0, 1, 1)
-    assert r.data == plain_bad and r.calculated_checksum == _xxh64(plain_bad) & 0xFFFFFFFF
+    assert r.data == plain_bad and r.calculated_checksum == xxh64(plain_bad) & 0xFFFFFFFF
     r = res[4]
     assert (r.status, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data) == (0, 1, 0, 0, 0)
-    assert r.calculated_checksum == _xxh64(text) & 0xFFFFFFFF
+    assert r.calculated_checksum == xxh64(text) & 0xFFFFFFFF
     r = res[5]
     assert (r.status, r.nframes, r.checksums, r.checksum_mismatches) == (0, 2, 2, 0)
 
@@ -216,7 +203,7 @@ def _check_small(ctx, entries, plains):
     for i, (r, p) in enumerate(zip(res, plains)):
         assert r.status == 0 and r.data == p, i
         assert (r.nframes, r.checksums, r.checksum_mismatches) == (1, 1, 0), i
-        assert r.calculated_checksum == r.checksum_from_data == _xxh64(p) & 0xFFFFFFFF, i
+        assert r.calculated_checksum == r.checksum_from_data == xxh64(p) & 0xFFFFFFFF, i
     caps = [len(p) for p in plains]
     for i in list(range(0, 4096, 509)) + list(range(4096, len(entries))):
         _check(ctx, [entries[i]], [caps[i]], [res[i]])
@@ -277,6 +264,6 @@ def test_batch_checksums(ctx):
     for f in range(b.nframes):
         fi = b.frame_info(f)
         failed += fi.status != 0
-        assert cs[f] == _xxh64(b.read(fi.out_base, fi.out_size)), f
+        assert cs[f] == xxh64(b.read(fi.out_base, fi.out_size)), f
     assert failed == 1
     b.close()

@@ -10,74 +10,21 @@ import sys
 import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime, Context.decode_frames_to_tensors)
 
+import zgpu
+from devmem import ALL, MAGIC, SENT, Arena, entry_key, oracle_alone, xxh64
 from golden_io import read_manifest, read_pack
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-MAGIC = (0xFD2FB528).to_bytes(4, "little")
 sys.path.insert(0, os.path.join(ROOT, "tools"))   # zgdata: the workload generators
-SENT = 0xA5
-GUARD = 256
-ALL = 1 << 40                                      # hash_max: every frame hashed
-E_BAD_ARG = 93
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    import zgpu
     c = zgpu.Context(0)
     yield c
     c.close()
-
-
-def _xxh64(b):
-    import oracle
-    return oracle.lib().zor_xxh64(b, len(b), 0)
-
-
-def _oracle_alone(z, cap, dict_raw=None):
-    import oracle
-    d = oracle.FrameDecoder()
-    if dict_raw is not None:
-        d.add_dict(dict_raw)
-    return d.decode_all(z, cap)
-
-
-class Arena:
-    """slots of caps[i] bytes in one device tensor full of the sentinel; slot i starts at offset shifts[i] (default 0) from a 256-byte aligned
-    address, with at least GUARD bytes of sentinel on both sides"""
-
-    def __init__(self, caps, shifts=None):
-        self.caps = list(caps)
-        self.offs, at = [], GUARD
-        for i, c in enumerate(self.caps):
-            at = (at + 255) & ~255
-            self.offs.append(at + (shifts[i] if shifts else 0))
-            at = self.offs[-1] + c + GUARD
-        self.t = torch.full((at + GUARD,), SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        assert self.t.data_ptr() % 256 == 0
-        self.ptrs = [self.t.data_ptr() + o for o in self.offs]
-
-    def check(self, plains):
-        """plains[i]: what slot i must start with, or None if it must be untouched"""
-        torch.cuda.synchronize()
-        got = self.t.cpu().numpy().tobytes()
-        want = bytearray([SENT]) * len(got)
-        for o, c, p in zip(self.offs, self.caps, plains):
-            if p is not None:
-                assert len(p) <= c
-                want[o:o + len(p)] = p
-        if got != bytes(want):
-            for i, (o, c, p) in enumerate(zip(self.offs, self.caps, plains)):
-                lo, hi = o - GUARD, o + c + GUARD
-                assert got[lo:hi] == bytes(want[lo:hi]), "slot %d (cap %d, %s) or its guards" % (i, c, "untouched" if p is None else len(p))
-            assert False, "bytes between the slots changed"
-
-
-def _key(r):
-    return (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data, r.calculated_checksum)
 
 
 def _run(c, entries, caps, shifts=None, **kw):
@@ -98,10 +45,10 @@ def test_corpus_in_one_call(ctx):
     a, res = _run(ctx, entries, caps, hash_max=ALL)
     plains = []
     for i, (z, cap, r, h) in enumerate(zip(entries, caps, res, host)):
-        st, out = _oracle_alone(z, cap)
+        st, out = oracle_alone(z, cap)
         assert (st, r.status) == (0, 0), (names[i], st, r)
         assert h.data == out
-        assert _key(r) == (h.status, len(h.data), h.nframes, h.checksums, h.checksum_mismatches, h.checksum_from_data, h.calculated_checksum), names[i]
+        assert entry_key(r) == (h.status, len(h.data), h.nframes, h.checksums, h.checksum_mismatches, h.checksum_from_data, h.calculated_checksum), names[i]
         assert r.checksums_unverified == 0 and r.first_hashed == 1, names[i]
         plains.append(out)
     a.check(plains)
@@ -113,7 +60,6 @@ def test_corpus_in_one_call(ctx):
 
 # 2 ---------------------------------------------------------------------------------------------------------------------------------
 def test_dict_corpus_takes_the_alone_path():
-    import zgpu
     pack, man = read_pack("dict_tests.pack"), read_manifest("dict_tests.json")
     raw = pack["dictionary"]
     names = sorted(n for n in man if n != "dictionary")
@@ -131,9 +77,9 @@ def test_dict_corpus_takes_the_alone_path():
         a, res = _run(c, entries, caps, hash_max=ALL)
         plains = []
         for i, (z, cap, r, h) in enumerate(zip(entries, caps, res, host)):
-            st, out = _oracle_alone(z, cap, raw)
+            st, out = oracle_alone(z, cap, raw)
             assert (st, r.status, h.status) == (0, 0, 0), names[i]
-            assert h.data == out and _key(r)[:5] == (0, len(out), h.nframes, h.checksums, h.checksum_mismatches), names[i]
+            assert h.data == out and entry_key(r)[:5] == (0, len(out), h.nframes, h.checksums, h.checksum_mismatches), names[i]
             plains.append(out)
         a.check(plains)
         assert c.frames_device_stats()["entries_alone"] > 0
@@ -166,16 +112,15 @@ def _isolation_entries():
     out += good
     caps = []
     for z in out:
-        st, o = _oracle_alone(z, 8 << 20)
+        st, o = oracle_alone(z, 8 << 20)
         caps.append(len(o) if st == 0 else (1 << 20))
     caps[-1] -= 1                                                           # cap = size - 1: TargetTooSmall
     return out, caps
 
 
 def test_isolation_and_order(ctx):
-    import zgpu
     entries, caps = _isolation_entries()
-    verdicts = [_oracle_alone(z, cap) for z, cap in zip(entries, caps)]
+    verdicts = [oracle_alone(z, cap) for z, cap in zip(entries, caps)]
     assert verdicts[-1][0] == zgpu.E_TARGET_TOO_SMALL
     assert any(st not in (0, zgpu.E_TARGET_TOO_SMALL) for st, _ in verdicts) and any(st == 0 for st, _ in verdicts)
     orders = [list(range(len(entries))), list(range(len(entries)))]
@@ -197,7 +142,7 @@ def _raw_frame(payload):
     for k, o in enumerate(cuts):
         part = payload[o:o + (128 << 10)]
         z += ((1 if k == len(cuts) - 1 else 0) | (0 << 1) | (len(part) << 3)).to_bytes(3, "little") + part
-    return z + (_xxh64(payload) & 0xFFFFFFFF).to_bytes(4, "little")
+    return z + (xxh64(payload) & 0xFFFFFFFF).to_bytes(4, "little")
 
 
 def test_alignment_of_sources_and_destinations(ctx):
@@ -210,12 +155,12 @@ def test_alignment_of_sources_and_destinations(ctx):
         for n in order:
             p = rng.randbytes(n)
             z = _raw_frame(p)
-            assert _oracle_alone(z, n) == (0, p), n          # the hand-built frame is what the reference reads it as
+            assert oracle_alone(z, n) == (0, p), n          # the hand-built frame is what the reference reads it as
             entries.append(z)
             plains.append(p)
     multi = [rng.randbytes(n) for n in (33, 0, 4097, 17, 131073, 1)]
     z = b"".join(_raw_frame(p) for p in multi)
-    assert _oracle_alone(z, 1 << 20) == (0, b"".join(multi))
+    assert oracle_alone(z, 1 << 20) == (0, b"".join(multi))
     entries.append(z)                                        # one entry of several frames: they lie back to back in its destination
     plains.append(b"".join(multi))
     while len(entries) % 32:                                 # every destination offset 0 .. 31 is used, by entries of every kind
@@ -237,7 +182,6 @@ def test_alignment_of_sources_and_destinations(ctx):
 # 5 ---------------------------------------------------------------------------------------------------------------------------------
 def _cut(entries, S):
     """the submits zgpu_decode_frames cuts (zg_frames.cpp): by the plaintext bound and by the input bytes"""
-    import zgpu
     groups, cur, pb, ib = [], [], 0, 0
     for i, z in enumerate(entries):
         b = zgpu.plaintext_bound(z)
@@ -254,7 +198,6 @@ def _cut(entries, S):
 
 def test_several_submits(ctx, monkeypatch):
     import zgdata
-    import zgpu
     rng = random.Random(5)
     texts = [zgdata.text_like(300000 + 1000 * k, seed=40 + k) for k in range(6)]
     comp = [zgdata.zstd_compress(t) for t in texts]
@@ -280,7 +223,7 @@ def test_several_submits(ctx, monkeypatch):
         c.close()
     groups = _cut(entries, S)
     assert len(groups) >= 4 and st["submits"] == len(groups)
-    assert [_key(r) for r in res] == [_key(r) for r in one]
+    assert [entry_key(r) for r in res] == [entry_key(r) for r in one]
     assert [r.status == 0 for r in res] == [p is not None for p in plains]
     a.check(plains)
     with_success = sum(1 for g in groups if any(res[i].status == 0 for i in g))
@@ -302,7 +245,7 @@ def test_wrong_pointers_become_a_status(ctx):
     ptrs[4] = 16                      # inside no allocation
     res = ctx.decode_frames_device([z] * 6, ptrs, caps)
     for i in (1, 3, 4):
-        assert (res[i].status, res[i].written, res[i].nframes) == (E_BAD_ARG, 0, 0), (i, res[i])
+        assert (res[i].status, res[i].written, res[i].nframes) == (zgpu.E_BAD_ARG, 0, 0), (i, res[i])
     for i in (0, 2, 5):
         assert (res[i].status, res[i].written) == (0, len(text)), (i, res[i])
     a.check([text, None, text, None, None, text])
@@ -311,7 +254,7 @@ def test_wrong_pointers_become_a_status(ctx):
     beyond = a.t.data_ptr() + a.t.numel() - 1000
     big = torch.cuda.get_device_properties(0).total_memory * 4
     res = ctx.decode_frames_device([z, z], [beyond, a.ptrs[0]], [big, caps[0]])
-    assert res[0].status == E_BAD_ARG and res[1].status == 0
+    assert res[0].status == zgpu.E_BAD_ARG and res[1].status == 0
     a.check([text, None, text, None, None, text])
 
 
@@ -331,7 +274,7 @@ def test_checksums_hashed_on_the_device_or_counted(ctx):
     entries = [z_small, bytes(z_flip), z_long, z_none, z_text + z_long]
     plains = [p_small, text, p_long, text, text + p_long]
     caps = [len(p) for p in plains]
-    low = lambda b: _xxh64(b) & 0xFFFFFFFF                 # noqa: E731
+    low = lambda b: xxh64(b) & 0xFFFFFFFF                 # noqa: E731
 
     a, res = _run(ctx, entries, caps, hash_max=65536)      # z_long is longer than hash_max_bytes
     a.check(plains)
@@ -350,7 +293,7 @@ def test_checksums_hashed_on_the_device_or_counted(ctx):
         (1, 0, 0, 1), (1, 1, 0, 1), (1, 0, 0, 1), (0, 0, 0, 1), (2, 0, 0, 1)]
     assert res[2].calculated_checksum == res[2].checksum_from_data == low(p_long)
     host = ctx.decode_frames(entries, caps)
-    assert [_key(r) for r in res] == [(h.status, h.written, h.nframes, h.checksums, h.checksum_mismatches, h.checksum_from_data,
+    assert [entry_key(r) for r in res] == [(h.status, h.written, h.nframes, h.checksums, h.checksum_mismatches, h.checksum_from_data,
                                        h.calculated_checksum) for h in host]
 
     a, res = _run(ctx, entries, caps, no_hash=True)        # flags bit 0: nothing is hashed
@@ -377,7 +320,7 @@ def test_scale_to_tensors(ctx):
         assert t.device.type == "cuda" and t.dtype == torch.uint8 and t.numel() == size and t.data_ptr() % 256 == 0
         assert torch.equal(t, want[k % 8]), k
     for k in (0, 63):
-        assert _oracle_alone(entries[k], size) == (0, tensors[k].cpu().numpy().tobytes())
+        assert oracle_alone(entries[k], size) == (0, tensors[k].cpu().numpy().tobytes())
     st = ctx.frames_device_stats()
     assert st["bytes_scattered"] == 64 * size and st["scatter_launches"] == st["submits"] >= 1
     # explicit capacities, a failing entry among them: its view is empty

@@ -11,8 +11,10 @@ import sys
 import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime)
 
+import zgpu
+from devmem import ALL, MAGIC, Arena, RawDevice, RawSources, Sources, full_key, oracle_alone, xxh64
 from golden_io import read_manifest, read_pack
-from test_gpu_decode_frames_device import ALL, E_BAD_ARG, GOLDEN, MAGIC, Arena, _cut, _isolation_entries, _oracle_alone, _raw_frame, _xxh64
+from test_gpu_decode_frames_device import GOLDEN, _cut, _isolation_entries, _raw_frame
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,39 +23,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 @pytest.fixture(scope="module")
 def ctx():
-    import zgpu
     c = zgpu.Context(0)
     yield c
     c.close()
-
-
-def _full(r):
-    return (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data, r.calculated_checksum,
-            r.checksums_unverified, r.first_hashed)
-
-
-class Sources:
-    """the entries in ONE torch device tensor: entry j starts shifts[j] bytes behind a 32-byte boundary (default 0), other bytes between them
-    are a sentinel the decoder must never need; the last entry ends with the tensor"""
-
-    def __init__(self, entries, shifts=None):
-        self.offs, at = [], 0
-        for j, z in enumerate(entries):
-            at = ((at + 31) & ~31) + (shifts[j] if shifts else 0)
-            self.offs.append(at)
-            at += len(z)
-        host = bytearray([0x3C]) * max(at, 1)
-        for o, z in zip(self.offs, entries):
-            host[o:o + len(z)] = z
-        self.host = bytes(host)
-        self.t = torch.frombuffer(bytearray(self.host), dtype=torch.uint8).to("cuda:0")
-        torch.cuda.synchronize()
-        self.lens = [len(z) for z in entries]
-        self.ptrs = [self.t.data_ptr() + o if n else 0 for o, n in zip(self.offs, self.lens)]
-
-    def unchanged(self):
-        torch.cuda.synchronize()
-        return self.t.cpu().numpy().tobytes() == self.host
 
 
 def _both(c, entries, caps, shifts=None, src_shifts=None, src=None, **kw):
@@ -67,7 +39,7 @@ def _both(c, entries, caps, shifts=None, src_shifts=None, src=None, **kw):
     res = c.decode_frames_device_src(s.ptrs, s.lens, b.ptrs, caps, **kw)
     assert len(res) == len(entries)
     for j, (x, y) in enumerate(zip(ref, res)):
-        assert _full(x) == _full(y), (j, _full(x), _full(y))
+        assert full_key(x) == full_key(y), (j, full_key(x), full_key(y))
     torch.cuda.synchronize()
     assert torch.equal(a.t, b.t)
     assert s.unchanged()
@@ -92,7 +64,6 @@ def _all_golden():
 
 # 1 ---------------------------------------------------------------------------------------------------------------------------------
 def test_golden_corpus_in_one_call(ctx):
-    import zgpu
     pack, man = read_pack("decodecorpus.pack"), read_manifest("decodecorpus.json")
     entries = _all_golden()
     assert len(entries) > 190
@@ -103,7 +74,7 @@ def test_golden_corpus_in_one_call(ctx):
         caps[k] = man[n]["size"] + (k % 3) * 100
     b, res, st = _both(ctx, entries, caps, hash_max=ALL)
     for k, n in enumerate(names):
-        stt, out = _oracle_alone(entries[k], caps[k])
+        stt, out = oracle_alone(entries[k], caps[k])
         assert (stt, res[k].status, res[k].written) == (0, 0, len(out)), n
         o = b.offs[k]
         assert b.t[o:o + len(out)].cpu().numpy().tobytes() == out, n
@@ -148,7 +119,6 @@ def test_4096_text_frames_of_128k(ctx):
 
 # 4 ---------------------------------------------------------------------------------------------------------------------------------
 def test_mix_of_failing_entries_and_permutation(ctx):
-    import zgpu
     entries, caps = _isolation_entries()          # failing, truncated, garbage, empty, skippable-only, several frames, TargetTooSmall
     assert b"" in entries
     base = None
@@ -159,7 +129,7 @@ def test_mix_of_failing_entries_and_permutation(ctx):
                            src_shifts=[(3 * j) % 18 for j in range(len(perm))])
         back = [None] * len(perm)
         for j, i in enumerate(perm):
-            back[i] = _full(res[j])
+            back[i] = full_key(res[j])
         if base is None:
             base = back
         assert back == base                        # permuting the entries permutes the results
@@ -169,57 +139,6 @@ def test_mix_of_failing_entries_and_permutation(ctx):
 
 
 # 5 ---------------------------------------------------------------------------------------------------------------------------------
-class RawDevice:
-    """n bytes from the HIP runtime itself (hipMalloc through the one runtime the process has loaded): an allocation whose end is the
-    end the runtime knows, which a torch tensor's — a piece of the caching allocator's block — is not"""
-
-    def __init__(self, data):
-        paths = sorted(set(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln))
-        assert len(paths) == 1, paths
-        self.hip = C.CDLL(paths[0])
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), len(data)) == 0
-        self.ptr, self.n, self.data = p.value, len(data), bytes(data)
-        assert self.hip.hipMemcpy(self.ptr, self.data, self.n, 1) == 0
-
-    def read(self):
-        out = C.create_string_buffer(self.n)
-        assert self.hip.hipMemcpy(out, self.ptr, self.n, 2) == 0
-        return out.raw
-
-    def free(self):
-        if self.ptr:
-            self.hip.hipFree(self.ptr)
-            self.ptr = None
-
-
-class RawSources:
-    """entries back to back (shifted) in one RawDevice allocation; the last entry ends flush with the allocation"""
-
-    def __init__(self, entries, shifts):
-        self.offs, at = [], 0
-        for z, s in zip(entries, shifts):
-            at = ((at + 31) & ~31) + s
-            self.offs.append(at)
-            at += len(z)
-        host = bytearray([0x3C]) * at
-        for o, z in zip(self.offs, entries):
-            host[o:o + len(z)] = z
-        self.dev = RawDevice(host)
-        self.lens = [len(z) for z in entries]
-        self.ptrs = [self.dev.ptr + o if n else 0 for o, n in zip(self.offs, self.lens)]
-        assert self.offs[-1] + self.lens[-1] == self.dev.n and self.lens[-1] > 0
-
-    def unchanged(self):
-        return self.dev.read() == self.dev.data
-
-    def free(self):
-        self.dev.free()
-
-
 def test_alignment_of_sources_and_flush_end(ctx):
     rng = random.Random(0x5A11)
     lengths = [0, 1, 2, 3, 15, 16, 17, 31, 33, 4095, 4097, 65537, 131071]
@@ -268,17 +187,17 @@ def test_wrong_source_pointers_become_a_status(ctx):
         a = Arena(caps)
         res = ctx.decode_frames_device_src(ptrs, lens, a.ptrs, caps)
         for i in (1, 2, 3, 4):
-            assert (res[i].status, res[i].written, res[i].nframes) == (E_BAD_ARG, 0, 0), (i, res[i])
+            assert (res[i].status, res[i].written, res[i].nframes) == (zgpu.E_BAD_ARG, 0, 0), (i, res[i])
         for i in (0, 5):
             assert (res[i].status, res[i].written) == (0, len(text)), (i, res[i])
         a.check([text, None, None, None, None, text])
         # the same allocation, used inside its bounds: the whole of it, and a range that ends flush with it
         res = ctx.decode_frames_device_src([raw.ptr, raw.ptr + 100], [len(z), len(z) - 100], [a.ptrs[1], a.ptrs[2]], caps[:2])
-        assert (res[0].status, res[0].written) == (0, len(text)) and res[1].status not in (0, E_BAD_ARG)
+        assert (res[0].status, res[0].written) == (0, len(text)) and res[1].status not in (0, zgpu.E_BAD_ARG)
         a.check([text, text, None, None, None, text])
         # a destination that is host memory, with a good source: that entry only
         res = ctx.decode_frames_device_src(good.ptrs[:2], good.lens[:2], [pinned.data_ptr(), a.ptrs[3]], [len(z), caps[3]])
-        assert res[0].status == E_BAD_ARG and (res[1].status, res[1].written) == (0, len(text))
+        assert res[0].status == zgpu.E_BAD_ARG and (res[1].status, res[1].written) == (0, len(text))
         a.check([text, text, None, text, None, text])
         assert good.unchanged() and raw.read() == z and bytes(pinned.numpy()) == z and host_buf.raw == z
         # a length of 0: nothing is checked, nothing is read — any pointer value will do
@@ -291,7 +210,6 @@ def test_wrong_source_pointers_become_a_status(ctx):
 # 7 ---------------------------------------------------------------------------------------------------------------------------------
 def test_submits_are_cut_as_for_host_sources(monkeypatch):
     import zgdata
-    import zgpu
     rng = random.Random(5)
     texts = [zgdata.text_like(300000 + 1000 * k, seed=40 + k) for k in range(6)]
     comp = [zgdata.zstd_compress(t) for t in texts]
@@ -320,7 +238,6 @@ def test_submits_are_cut_as_for_host_sources(monkeypatch):
 
 # 8 ---------------------------------------------------------------------------------------------------------------------------------
 def test_dictionary_entries_take_the_alone_path():
-    import zgpu
     pack, man = read_pack("dict_tests.pack"), read_manifest("dict_tests.json")
     rawd = pack["dictionary"]
     names = sorted(n for n in man if n != "dictionary")[:60]
@@ -339,7 +256,7 @@ def test_dictionary_entries_take_the_alone_path():
         b, res, st = _both(c, entries, caps, hash_max=ALL)
         plains = []
         for i, (z, cap, r) in enumerate(zip(entries, caps, res)):
-            stt, out = _oracle_alone(z, cap, rawd)
+            stt, out = oracle_alone(z, cap, rawd)
             assert (stt, r.status, r.written) == (0, 0, len(out)), i
             plains.append(out)
         b.check(plains)
@@ -365,7 +282,7 @@ def test_checksum_options(ctx):
     entries = [z_small, bytes(z_flip), z_long, z_none, z_text + z_long]
     plains = [p_small, text, p_long, text, text + p_long]
     caps = [len(p) for p in plains]
-    low = lambda b: _xxh64(b) & 0xFFFFFFFF                 # noqa: E731
+    low = lambda b: xxh64(b) & 0xFFFFFFFF                 # noqa: E731
 
     b, res, _ = _both(ctx, entries, caps, hash_max=65536)  # z_long is longer than hash_max
     b.check(plains)

@@ -1,8 +1,8 @@
 """zgpu_decode_ranges_device_src / zgpu_frames_seek_device (Context.decode_ranges_device_src, frames_seek_device, decode_tensor_ranges) on
 the GPU: plaintext bytes [begin, begin + len) of multi-frame entries that lie in device memory, written to device memory, with only the
 frames that hold the range decoded. The expectation of every case comes from the oracle: a small pure-Python chain walker (select, below)
-computes the selection S = entry[src_lo:src_hi] and plain_lo by the rule of zg_seek.h, _oracle_alone(S) gives the status and the bytes, a
-taken frame that declares a size and decodes to another length gives E_CONTENT_SIZE_MISMATCH, and the destination must hold
+computes the selection S = entry[src_lo:src_hi] and plain_lo by the rule of zg_seek.h, oracle_alone(S) gives the status and the bytes, a
+taken frame that declares a size and decodes to another length gives zgpu.E_CONTENT_SIZE_MISMATCH, and the destination must hold
 out[begin - plain_lo:][:len] — with guard bytes, everything behind `written` and every byte of a failed entry's slot untouched (Arena.check
 compares the whole arena)."""
 import ctypes as C
@@ -12,18 +12,16 @@ import time
 import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime)
 
+import zgpu
+from devmem import ALL, Arena, RawSources, Sources, oracle_alone
 from golden_io import read_manifest, read_pack
-from test_gpu_decode_frames_device import ALL, E_BAD_ARG, Arena, _oracle_alone
-from test_gpu_decode_frames_device_src import RawSources, Sources
 
 pytestmark = pytest.mark.gpu
-E_TARGET_TOO_SMALL, E_CHECKSUM_MISMATCH, E_CONTENT_SIZE_MISMATCH = 12, 70, 71
 TOP = 2 ** 64 - 1
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    import zgpu
     c = zgpu.Context(0)
     yield c
     c.close()
@@ -119,10 +117,9 @@ _CACHE = {}
 
 
 def _decode(z, dict_raw=None):
-    import zgpu
     key = (z, dict_raw)
     if key not in _CACHE:
-        _CACHE[key] = _oracle_alone(z, zgpu.plaintext_bound(z) + 64, dict_raw)
+        _CACHE[key] = oracle_alone(z, zgpu.plaintext_bound(z) + 64, dict_raw)
     return _CACHE[key]
 
 
@@ -139,10 +136,10 @@ def expect(z, rg, cap=None, dict_raw=None, anchor=(0, 0)):
         return st, None
     for f in taken:
         if f.fcs is not None and len(_decode(z[f.begin:f.end], dict_raw)[1]) != f.fcs:
-            return E_CONTENT_SIZE_MISMATCH, None
+            return zgpu.E_CONTENT_SIZE_MISMATCH, None
     clip = out[begin - plo:][:n]
     if cap is not None and len(clip) > cap:
-        return E_TARGET_TOO_SMALL, None
+        return zgpu.E_TARGET_TOO_SMALL, None
     return 0, clip
 
 
@@ -273,12 +270,12 @@ def test_defects(ctx):
     good = plains[3][100:5100]
     assert exps[0] == exps[1] == exps[3] == exps[5] == (0, good)                     # (a): the defect is not seen
     assert res[1].status == 0
-    assert exps[2][0] not in (0, E_CONTENT_SIZE_MISMATCH) and seeks[2].broken and seeks[2].src_lo == fr[1].begin and seeks[2].src_hi == len(z)   # (b)
-    assert exps[4][0] not in (0, E_CONTENT_SIZE_MISMATCH) and res[4].written == 0                       # (c)
+    assert exps[2][0] not in (0, zgpu.E_CONTENT_SIZE_MISMATCH) and seeks[2].broken and seeks[2].src_lo == fr[1].begin and seeks[2].src_hi == len(z)   # (b)
+    assert exps[4][0] not in (0, zgpu.E_CONTENT_SIZE_MISMATCH) and res[4].written == 0                       # (c)
     assert exps[6][0] != 0 and seeks[6].broken and exps[7] == (0, plains[0][7:107]) and not seeks[7].broken   # (d)
-    assert res[8].status == E_CONTENT_SIZE_MISMATCH                                                     # (e)
+    assert res[8].status == zgpu.E_CONTENT_SIZE_MISMATCH                                                     # (e)
     assert exps[9] == (0, plains[3][95:5095]) and res[9].status == 0                                    # (f): shifted by the lie
-    assert res[10].status == E_CONTENT_SIZE_MISMATCH                                                    # ... and taken, the lie is found
+    assert res[10].status == zgpu.E_CONTENT_SIZE_MISMATCH                                                    # ... and taken, the lie is found
     assert exps[11] == (0, plains[2][-1:] + plains[3][:1]) and res[11].nframes == 2
     assert exps[12] == (0, b"") and seeks[12].nothing and seeks[12].frames_skipped == 6  # the range lies behind the plaintext
 
@@ -295,7 +292,7 @@ def test_verify_acts_on_the_taken_frames_only(ctx):
     caps = [3000] * 3
     a = Arena(caps)
     res, seeks = ctx.decode_ranges_device_src(s.ptrs, s.lens, rgs, a.ptrs, caps, verify=True)
-    assert [(r.status, r.written) for r in res] == [(E_CHECKSUM_MISMATCH, 0), (0, 3000), (0, 3000)]
+    assert [(r.status, r.written) for r in res] == [(zgpu.E_CHECKSUM_MISMATCH, 0), (0, 3000), (0, 3000)]
     assert (res[0].checksums, res[0].checksum_mismatches) == (1, 1)
     want = plains[3][10:3010]
     a.check([None, want, want])
@@ -335,9 +332,9 @@ def test_destinations_and_pointers(ctx):
     dsts[3] = pinned.data_ptr()                                    # ... as destination
     anchors = [None, None, None, None, (len(z) + 1, 0), (0, rg[0] + 1), None]
     res, seeks = ctx.decode_ranges_device_src(ptrs, s.lens * 7, [rg] * 7, dsts, caps, anchors=anchors)
-    assert [r.status for r in res] == [E_TARGET_TOO_SMALL, 0, E_BAD_ARG, E_BAD_ARG, E_BAD_ARG, E_BAD_ARG, 0]
-    assert [k.status for k in seeks] == [0, 0, E_BAD_ARG, E_BAD_ARG, E_BAD_ARG, E_BAD_ARG, 0]
-    assert all(k.key() == (0,) * 5 + (E_BAD_ARG,) + (0,) * 5 for k in seeks[2:6])
+    assert [r.status for r in res] == [zgpu.E_TARGET_TOO_SMALL, 0, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, 0]
+    assert [k.status for k in seeks] == [0, 0, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, 0]
+    assert all(k.key() == (0,) * 5 + (zgpu.E_BAD_ARG,) + (0,) * 5 for k in seeks[2:6])
     want = whole[rg[0]:rg[0] + 500]
     a.check([None, want, None, None, None, None, want])
     assert s.unchanged() and host_buf.raw == z
@@ -345,7 +342,6 @@ def test_destinations_and_pointers(ctx):
 
 # ---- 6: anchors ----------------------------------------------------------------------------------------------------------------------------
 def test_anchors_from_the_frame_table(ctx):
-    import zgpu
     z, plains = _mixed_entry()
     rgs = [r for r in _mixed_ranges(z) if r[1]]
     s = Sources([z])
@@ -367,7 +363,6 @@ def test_anchors_from_the_frame_table(ctx):
 
 # ---- 7: dictionaries -----------------------------------------------------------------------------------------------------------------------
 def test_dictionary_entries_shared_and_alone():
-    import zgpu
     pack, man = read_pack("dict_tests.pack"), read_manifest("dict_tests.json")
     rawd = pack["dictionary"]
     names = sorted(n for n in man if n != "dictionary")[:48]
@@ -406,7 +401,6 @@ def test_an_entry_has_one_verdict_in_a_shared_submit_and_alone():
     verdict of ZGPU_DEVICE_VERIFY — does not depend on whether the entry's dictionary frames stay in the submit or the entry is decoded alone:
     two taken frames whose false sizes compensate, a taken frame that declares less than it holds, and a corrupted Content_Checksum with caps
     one byte short and exact."""
-    import zgpu
     pack, man = read_pack("dict_tests.pack"), read_manifest("dict_tests.json")
     rawd = pack["dictionary"]
     names = sorted(n for n in man if n != "dictionary")[:6]
@@ -426,13 +420,13 @@ def test_an_entry_has_one_verdict_in_a_shared_submit_and_alone():
         for shared in (1, 0):
             c.set_frames_shared_dicts(shared)
             a, res, seeks, exps = run_and_check(c, None, [rg] * 3, entries=[both, under, z], dict_raw=rawd, hash_max=ALL)
-            assert [r.status for r in res] == [E_CONTENT_SIZE_MISMATCH, E_CONTENT_SIZE_MISMATCH, 0], shared
+            assert [r.status for r in res] == [zgpu.E_CONTENT_SIZE_MISMATCH, zgpu.E_CONTENT_SIZE_MISMATCH, 0], shared
             assert c.frames_device_stats()["entries_alone"] == (0 if shared else 3)
             s = Sources([badsum, badsum, z, badsum])
             caps = [rg[1] - 1, rg[1], rg[1], rg[1] - 1]
             a = Arena(caps)
             res, _ = c.decode_ranges_device_src(s.ptrs, s.lens, [rg] * 4, a.ptrs, caps, verify=True)
-            assert [r.status for r in res] == [E_TARGET_TOO_SMALL, E_CHECKSUM_MISMATCH, 0, E_TARGET_TOO_SMALL], shared
+            assert [r.status for r in res] == [zgpu.E_TARGET_TOO_SMALL, zgpu.E_CHECKSUM_MISMATCH, 0, zgpu.E_TARGET_TOO_SMALL], shared
             assert all(r.written == 0 for r in (res[0], res[1], res[3])) and res[2].written == rg[1]
             a.check([None, None, want, None])
             assert s.unchanged()
@@ -445,7 +439,6 @@ def test_an_entry_has_one_verdict_in_a_shared_submit_and_alone():
 # ---- 8: selectivity ------------------------------------------------------------------------------------------------------------------------
 def test_selectivity_on_512_frames_of_128k(ctx):
     import zgdata
-    import zgpu
     size, n = 128 << 10, 512
     texts = [zgdata.text_like(size, seed=0x512 + k) for k in range(8)]
     comp = [zgdata.zstd_compress(t) for t in texts]

@@ -13,9 +13,11 @@ import sys
 import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime)
 
+import zgpu
+from devmem import MAGIC, Arena, RawDevice, RawSources, Sources, oracle_alone
 from golden_io import read_manifest, read_pack
-from test_gpu_decode_frames_device import E_BAD_ARG, MAGIC, Arena, _isolation_entries, _oracle_alone, _raw_frame
-from test_gpu_decode_frames_device_src import RawDevice, RawSources, Sources, _all_golden
+from test_gpu_decode_frames_device import _isolation_entries, _raw_frame
+from test_gpu_decode_frames_device_src import _all_golden
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -222,7 +224,7 @@ def test_zero_length_entries_wrong_pointers_and_permutation(ctx):
         for call in (ctx.frames_index_device, lambda p, n: ctx.frames_table_device(p, n)[0]):
             res = call(ptrs, lens)
             for i in (1, 2, 3, 4):
-                assert _key(res[i]) == (0, 0, E_BAD_ARG, 0, 0, 0, 0, 0), (i, res[i])
+                assert _key(res[i]) == (0, 0, zgpu.E_BAD_ARG, 0, 0, 0, 0, 0), (i, res[i])
             for i in (0, 5):
                 assert (res[i].status, res[i].bound, res[i].nframes) == (0, len(text), 1), (i, res[i])
         ents, first, frames = ctx.frames_table_device(ptrs, lens)
@@ -268,7 +270,7 @@ def test_decode_tensors_sizes_itself_without_a_download(ctx):
     assert ctx.frames_device_src_stats()["input_bytes_to_host"] == 0
     idx = ctx.frames_index_device([t.data_ptr() if t.numel() else 0 for t in ins], [t.numel() for t in ins])
     for z, t, r, e in zip(comp + [multi, b""], outs, res, idx):
-        st, ref = _oracle_alone(z, 4 << 20)
+        st, ref = oracle_alone(z, 4 << 20)
         assert (st, r.status, r.written) == (0, 0, len(ref)) and t.cpu().numpy().tobytes() == ref
         assert r.nframes == e.nframes and r.written <= e.bound                # the index agrees with the decode
     assert outs[4].cpu().numpy().tobytes() == texts[1] + texts[3]
@@ -327,7 +329,7 @@ def test_one_long_frame_of_more_than_2048_blocks(ctx):
     assert res[1].nblocks < nblocks and res[1].why != 0 and not res[1].all_complete
     ents, first, frames = ctx.frames_table_device(s.ptrs, s.lens)
     assert (frames[0].nblocks, frames[0].bound, frames[0].src_end, frames[0].window_size) == (nblocks, total, len(z), host[0].window_size)
-    st, ref = _oracle_alone(z, total)
+    st, ref = oracle_alone(z, total)
     t = torch.frombuffer(bytearray(z), dtype=torch.uint8).to("cuda:0")
     outs, r = ctx.decode_tensors([t])
     assert (st, r[0].status, r[0].written) == (0, 0, total) and outs[0].cpu().numpy().tobytes() == ref

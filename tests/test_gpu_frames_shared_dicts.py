@@ -12,72 +12,15 @@ import torch   # (before the library is loaded: the process must run on one HIP 
 
 import dictframes
 import oracle
+import zgpu
+from devmem import ALL, MAGIC, Arena, Sources, entry_key, xxh32
 from golden_io import read_manifest, read_pack
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "zstd-rs_amd"))
-MAGIC = (0xFD2FB528).to_bytes(4, "little")
 SKIP = (0x184D2A53).to_bytes(4, "little") + (5).to_bytes(4, "little") + b"12345"
-SENT = 0xA5
-GUARD = 256
-ALL = 1 << 40                                      # hash_max: every frame hashed
 K = 128 << 10
-E_DICT_NOT_PROVIDED = 7
-
-
-class Arena:
-    """slots of caps[i] bytes in one device tensor full of the sentinel; slot i starts at offset shifts[i] (default 0) from a 256-byte aligned
-    address, with at least GUARD bytes of sentinel on both sides"""
-
-    def __init__(self, caps, shifts=None):
-        self.caps = list(caps)
-        self.offs, at = [], GUARD
-        for i, c in enumerate(self.caps):
-            at = (at + 255) & ~255
-            self.offs.append(at + (shifts[i] if shifts else 0))
-            at = self.offs[-1] + c + GUARD
-        self.t = torch.full((at + GUARD,), SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        assert self.t.data_ptr() % 256 == 0
-        self.ptrs = [self.t.data_ptr() + o for o in self.offs]
-
-    def check(self, plains):
-        """plains[i]: what slot i must start with, or None if it must be untouched"""
-        torch.cuda.synchronize()
-        got = self.t.cpu().numpy().tobytes()
-        want = bytearray([SENT]) * len(got)
-        for o, c, p in zip(self.offs, self.caps, plains):
-            if p is not None:
-                assert len(p) <= c
-                want[o:o + len(p)] = p
-        if got != bytes(want):
-            for i, (o, c, p) in enumerate(zip(self.offs, self.caps, plains)):
-                lo, hi = o - GUARD, o + c + GUARD
-                assert got[lo:hi] == bytes(want[lo:hi]), "slot %d (cap %d, %s) or its guards" % (i, c, "untouched" if p is None else len(p))
-            assert False, "bytes between the slots changed"
-
-
-class Sources:
-    """the entries in ONE torch device tensor: entry j starts shifts[j] bytes behind a 32-byte boundary (default 0)"""
-
-    def __init__(self, entries, shifts=None):
-        self.offs, at = [], 0
-        for j, z in enumerate(entries):
-            at = ((at + 31) & ~31) + (shifts[j] if shifts else 0)
-            self.offs.append(at)
-            at += len(z)
-        host = bytearray([0x3C]) * max(at, 1)
-        for o, z in zip(self.offs, entries):
-            host[o:o + len(z)] = z
-        self.t = torch.frombuffer(host, dtype=torch.uint8).to("cuda:0")
-        torch.cuda.synchronize()
-        self.lens = [len(z) for z in entries]
-        self.ptrs = [self.t.data_ptr() + o if n else 0 for o, n in zip(self.offs, self.lens)]
-
-
-def _xxh32(b):
-    return oracle.lib().zor_xxh64(b, len(b), 0) & 0xFFFFFFFF
 
 
 class Want:
@@ -103,17 +46,13 @@ class Want:
                 st, plain = dec().decode_all(z, 1 << 24)
                 assert st == 0
                 has = bool(z[4] & 4)
-                stored, calc = int.from_bytes(z[-4:], "little") if has else 0, _xxh32(plain)
+                stored, calc = int.from_bytes(z[-4:], "little") if has else 0, xxh32(plain)
                 if n == 0:
                     first = (stored, calc)
                 n += 1
                 ck += has
                 bad += has and stored != calc
             self.key = (0, len(out), n, ck, bad) + first
-
-
-def _dkey(r):
-    return (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data, r.calculated_checksum)
 
 
 def _three_calls(c, wants, caps, shifts=None, src_shifts=None):
@@ -124,12 +63,12 @@ def _three_calls(c, wants, caps, shifts=None, src_shifts=None):
     host = c.decode_frames(entries, caps)
     stats["host"] = (c.frames_dict_stats(), c.frames_submits(), None, None)
     for i, (r, w) in enumerate(zip(host, wants)):
-        assert _dkey(r) == w.key and r.data == w.data, ("host", i, _dkey(r), w.key)
+        assert entry_key(r) == w.key and r.data == w.data, ("host", i, entry_key(r), w.key)
     a = Arena(caps, shifts)
     res = c.decode_frames_device(entries, a.ptrs, caps, hash_max=ALL)
     stats["device"] = (c.frames_dict_stats(), c.frames_submits(), c.frames_device_stats(), None)
     for i, (r, w) in enumerate(zip(res, wants)):
-        assert _dkey(r) == w.key, ("device", i, _dkey(r), w.key)
+        assert entry_key(r) == w.key, ("device", i, entry_key(r), w.key)
         assert r.checksums_unverified == 0 and r.first_hashed == (1 if w.status == 0 and w.key[2] else 0), ("device", i)
     a.check(plains)
     b = Arena(caps, shifts)
@@ -137,7 +76,7 @@ def _three_calls(c, wants, caps, shifts=None, src_shifts=None):
     res = c.decode_frames_device_src(s.ptrs, s.lens, b.ptrs, caps, hash_max=ALL)
     stats["device_src"] = (c.frames_dict_stats(), c.frames_submits(), c.frames_device_stats(), c.frames_device_src_stats())
     for i, (r, w) in enumerate(zip(res, wants)):
-        assert _dkey(r) == w.key, ("device_src", i, _dkey(r), w.key)
+        assert entry_key(r) == w.key, ("device_src", i, entry_key(r), w.key)
     b.check(plains)
     return stats
 
@@ -158,7 +97,6 @@ def corpus_wants(corpus):
 
 @pytest.fixture(scope="module")
 def ctx(corpus):
-    import zgpu
     c = zgpu.Context(0)
     c.add_dict(corpus[0])
     c.set_frames_shared_dicts(True)
@@ -168,7 +106,6 @@ def ctx(corpus):
 
 # 1, 2 ------------------------------------------------------------------------------------------------------------------------------
 def test_dict_corpus_shared_then_switched_off(corpus, corpus_wants):
-    import zgpu
     raw, frames, sizes = corpus
     c = zgpu.Context(0)
     try:
@@ -251,7 +188,6 @@ def test_isolation_of_mutated_dictionary_frames(ctx, corpus):
 
 # 5 ---------------------------------------------------------------------------------------------------------------------------------
 def test_two_dictionaries_and_an_unregistered_id(corpus):
-    import zgpu
     raw, frames, sizes = corpus
     did = int.from_bytes(raw[4:8], "little")
     raw2 = raw[:4] + (did + 1).to_bytes(4, "little") + raw[8:]
@@ -265,7 +201,7 @@ def test_two_dictionaries_and_an_unregistered_id(corpus):
             items.append(([z], sizes[k]))
         items.insert(17, ([dictframes.patch_dict_id(frames[70], did + 2)], sizes[70]))     # a third id nobody registered
         wants = [Want(p, cap, [raw, raw2]) for p, cap in items]
-        assert [w.status for w in wants] == [0] * 17 + [E_DICT_NOT_PROVIDED] + [0] * 43
+        assert [w.status for w in wants] == [0] * 17 + [zgpu.E_DICT_NOT_PROVIDED] + [0] * 43
         stats = _three_calls(c, wants, [cap for _, cap in items])
         for call, (ds, submits, dev, src) in stats.items():
             assert submits == 1 and ds["frames_shared"] == 60 and ds["entries_alone"] == 1, (call, ds)   # (the unregistered id: today's path, today's answer)
@@ -355,7 +291,7 @@ def test_many_entries_from_device_sources(ctx, corpus, corpus_wants):
     assert ctx.frames_submits() == 1 and ds["entries_alone"] == 0 and ds["frames_shared"] == n and src["input_bytes_to_host"] == 0, (ds, src)
     for j in range(0, n, 64):                                                     # every 64th entry against the oracle, computed here
         w = Want([entries[j]], caps[j], [raw])
-        assert _dkey(res[j]) == w.key and w.data == corpus_wants[idx[j]].data, j
+        assert entry_key(res[j]) == w.key and w.data == corpus_wants[idx[j]].data, j
     for j, r in enumerate(res):
-        assert _dkey(r) == corpus_wants[idx[j]].key, j
+        assert entry_key(r) == corpus_wants[idx[j]].key, j
     a.check([corpus_wants[k].data for k in idx])

@@ -3,7 +3,7 @@ frames_seek_table_device, decode_tensor_ranges(seek_table=True)) on the GPU: pla
 format that lie in device memory, selected through the seek table at the entry's end (zg_k_seektab, a wave per entry). The expectation of
 every case comes from the oracle on the selection that tests/seektabs.py's model of the rule computes: S = entry[src_lo:src_hi],
 _oracle_alone(S) gives the status and the bytes, a selection that decodes to another total than the table promises (or a frame that declares
-a size and decodes to another) gives E_CONTENT_SIZE_MISMATCH, an unusable table E_SEEK_TABLE, and the destination must hold
+a size and decodes to another) gives zgpu.E_CONTENT_SIZE_MISMATCH, an unusable table zgpu.E_SEEK_TABLE, and the destination must hold
 out[begin - plain_lo:][:len] — with guard bytes, everything behind `written` and every byte of a failed entry's slot untouched."""
 import ctypes as C
 import random
@@ -14,19 +14,17 @@ import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime)
 
 import seektabs
+import zgpu
+from devmem import ALL, Arena, RawSources, Sources
 from golden_io import read_manifest, read_pack
 from seektabs import U64, model
-from test_gpu_decode_frames_device import ALL, E_BAD_ARG, Arena
-from test_gpu_decode_frames_device_src import RawSources, Sources
 from test_gpu_decode_ranges import _decode, _edit, chain
 
 pytestmark = pytest.mark.gpu
-E_TARGET_TOO_SMALL, E_CHECKSUM_MISMATCH, E_CONTENT_SIZE_MISMATCH, E_SEEK_TABLE = 12, 70, 71, 72
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    import zgpu
     c = zgpu.Context(0)
     yield c
     c.close()
@@ -34,7 +32,6 @@ def ctx():
 
 def seekable(frames, sizes, lie=None, checksums=None):
     """the frames and their seek table; lie(csizes, dsizes) may falsify the table"""
-    import zgpu
     cs, ds = [len(f) for f in frames], list(sizes)
     if lie:
         lie(cs, ds)
@@ -55,12 +52,12 @@ def expect(z, rg, cap=None, dict_raw=None):
         return st, None
     for f in chain(z[lo:hi]):
         if f.kind == "frame" and f.fcs is not None and len(_decode(z[lo + f.begin:lo + f.end], dict_raw)[1]) != f.fcs:
-            return E_CONTENT_SIZE_MISMATCH, None
+            return zgpu.E_CONTENT_SIZE_MISMATCH, None
     if len(out) != bound:
-        return E_CONTENT_SIZE_MISMATCH, None
+        return zgpu.E_CONTENT_SIZE_MISMATCH, None
     clip = out[begin - plo:][:n]
     if cap is not None and len(clip) > cap:
-        return E_TARGET_TOO_SMALL, None
+        return zgpu.E_TARGET_TOO_SMALL, None
     return 0, clip
 
 
@@ -221,7 +218,6 @@ def _six_unsized():
 
 
 def test_false_tables_become_a_status(ctx):
-    import zgpu
     frames, plains = _six_unsized()
     sizes = [len(p) for p in plains]
     good = seekable(frames, sizes)
@@ -254,12 +250,12 @@ def test_false_tables_become_a_status(ctx):
     whys = [zgpu.SEEKTAB_NONE, zgpu.SEEKTAB_NONE, zgpu.SEEKTAB_RESERVED_BITS, zgpu.SEEKTAB_TOO_LARGE, zgpu.SEEKTAB_TOO_LARGE,
             zgpu.SEEKTAB_BAD_FRAME, zgpu.SEEKTAB_BAD_FRAME, zgpu.SEEKTAB_PAST_TABLE]
     for i, why in enumerate(whys, 1):
-        assert (res[i].status, res[i].written, seeks[i].status, seeks[i].why) == (E_SEEK_TABLE, 0, E_SEEK_TABLE, why), (i, res[i], seeks[i])
-        assert seeks[i].key() == (0,) * 5 + (E_SEEK_TABLE, 0, 0, 0, why, 0)
+        assert (res[i].status, res[i].written, seeks[i].status, seeks[i].why) == (zgpu.E_SEEK_TABLE, 0, zgpu.E_SEEK_TABLE, why), (i, res[i], seeks[i])
+        assert seeks[i].key() == (0,) * 5 + (zgpu.E_SEEK_TABLE, 0, 0, 0, why, 0)
     want = plains[3][100:5100]
     assert exps[0] == exps[14] == (0, want) and res[0].status == res[14].status == 0     # the others of the call are unaffected
-    assert res[9].status == res[10].status == E_CONTENT_SIZE_MISMATCH
-    assert exps[11][0] not in (0, E_CONTENT_SIZE_MISMATCH, E_SEEK_TABLE) and res[11].status == exps[11][0]   # the oracle's verdict on those bytes
+    assert res[9].status == res[10].status == zgpu.E_CONTENT_SIZE_MISMATCH
+    assert exps[11][0] not in (0, zgpu.E_CONTENT_SIZE_MISMATCH, zgpu.E_SEEK_TABLE) and res[11].status == exps[11][0]   # the oracle's verdict on those bytes
     assert res[12].status == exps[12][0]
     assert exps[13] == (0, plains[3][95:5095]) and res[13].status == 0
     # a range with an anchor: the table is the index, there is nothing to anchor
@@ -267,12 +263,12 @@ def test_false_tables_become_a_status(ctx):
     srcs, lens = (C.c_void_p * 2)(s.ptrs[0], s.ptrs[0]), (C.c_size_t * 2)(n, n)
     rg, out = (zgpu.RangeC * 2)(zgpu.RangeC(mid[0], mid[1], 0, 1), zgpu.RangeC(mid[0], mid[1], 0, 0)), (zgpu.SeekC * 2)()
     assert ctx.L.zgpu_frames_seek_table_device(ctx.h, srcs, lens, 2, rg, out) == 0
-    assert zgpu.Seek(out[0]).key() == (0,) * 5 + (E_BAD_ARG,) + (0,) * 5 and zgpu.Seek(out[1]).key() == model(good, *mid)[0]
+    assert zgpu.Seek(out[0]).key() == (0,) * 5 + (zgpu.E_BAD_ARG,) + (0,) * 5 and zgpu.Seek(out[1]).key() == model(good, *mid)[0]
     rg[0] = zgpu.RangeC(mid[0], mid[1], 8, 0)
     a = Arena([5000, 5000])
     dsts, caps, rr = (C.c_void_p * 2)(*a.ptrs), (C.c_size_t * 2)(5000, 5000), (zgpu.RangeResultC * 2)()
     assert ctx.L.zgpu_decode_ranges_seek_table_device_src(ctx.h, srcs, lens, 2, rg, dsts, caps, None, rr) == 0
-    assert (rr[0].d.r.status, rr[0].seek.status, rr[1].d.r.status, rr[1].d.r.written) == (E_BAD_ARG, E_BAD_ARG, 0, 5000)
+    assert (rr[0].d.r.status, rr[0].seek.status, rr[1].d.r.status, rr[1].d.r.written) == (zgpu.E_BAD_ARG, zgpu.E_BAD_ARG, 0, 5000)
     a.check([None, want])
 
 
@@ -292,8 +288,8 @@ def test_capacities_and_verify(ctx):
     s = Sources(entries)
     a = Arena(caps)
     res, seeks = ctx.decode_ranges_seek_table_device_src(s.ptrs, s.lens, [rg] * 6, a.ptrs, caps, verify=True)
-    assert [(r.status, r.written) for r in res] == [(E_TARGET_TOO_SMALL, 0), (0, 3000), (E_CHECKSUM_MISMATCH, 0), (0, 3000), (0, 3000),
-                                                    (E_TARGET_TOO_SMALL, 0)]
+    assert [(r.status, r.written) for r in res] == [(zgpu.E_TARGET_TOO_SMALL, 0), (0, 3000), (zgpu.E_CHECKSUM_MISMATCH, 0), (0, 3000), (0, 3000),
+                                                    (zgpu.E_TARGET_TOO_SMALL, 0)]
     assert (res[2].checksums, res[2].checksum_mismatches) == (2, 1) and all(k.frames_taken == 2 for k in seeks)
     a.check([None, want, None, want, want, None])
     assert s.unchanged()
@@ -304,7 +300,6 @@ def test_capacities_and_verify(ctx):
 
 # ---- 7: dictionaries ----------------------------------------------------------------------------------------------------------------------------
 def test_dictionary_frames_shared_and_alone():
-    import zgpu
     pack, man = read_pack("dict_tests.pack"), read_manifest("dict_tests.json")
     rawd = pack["dictionary"]
     names = sorted(n for n in man if n != "dictionary")[:24]
@@ -324,7 +319,7 @@ def test_dictionary_frames_shared_and_alone():
         for shared in (1, 0):
             c.set_frames_shared_dicts(shared)
             a, res, seeks, exps = run_and_check(c, entries, rgs, dict_raw=rawd, hash_max=ALL)
-            assert [r.status for r in res] == [0, 0, 0, 0, E_CONTENT_SIZE_MISMATCH], shared
+            assert [r.status for r in res] == [0, 0, 0, 0, zgpu.E_CONTENT_SIZE_MISMATCH], shared
             assert all(r.written == rg[1] for r, rg in zip(res[:4], rgs)) and all(k.frames_skipped == 2 and k.frames_taken == 2 for k in seeks)
             alone, st = c.frames_device_stats()["entries_alone"], c.ranges_stats()
             assert alone == (0 if shared else 5) and (st["input_bytes_to_host"] == 0) == bool(shared)
@@ -337,7 +332,6 @@ def test_dictionary_frames_shared_and_alone():
 # ---- 8: what it costs (printed; LABNOTES "seek_table" holds a run's values) ----------------------------------------------------------------------
 def test_selectivity_on_512_frames_of_128k(ctx):
     import zgdata
-    import zgpu
     size, n = 128 << 10, 512
     texts = [zgdata.text_like(size, seed=0x512 + k) for k in range(8)]
     total, mib = n * size, 1 << 20

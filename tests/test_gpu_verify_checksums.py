@@ -11,31 +11,14 @@ import random
 import pytest
 import torch   # (before the library is loaded: the process must run on one HIP runtime)
 
+import zgpu
+from devmem import MAGIC, Arena, full_key, oracle_alone, xxh32
 from golden_io import read_pack
 
 pytestmark = pytest.mark.gpu
-MAGIC = (0xFD2FB528).to_bytes(4, "little")
-SENT = 0xA5
-GUARD = 256
-E_CHECKSUM_MISMATCH = 70
-E_TARGET_TOO_SMALL = 12
-E_BAD_ARG = 93
 BLOCK = 128 << 10
 LENS = [0, 1, 31, 32, 33, 255, 256, 257, BLOCK + 1, 5 << 20]     # (the 5 MiB frame lies above the 4 MiB default of hash_max_bytes)
 BIG = len(LENS) - 1
-
-
-def _xxh32(b):
-    import oracle
-    return oracle.lib().zor_xxh64(b, len(b), 0) & 0xFFFFFFFF
-
-
-def _oracle_alone(z, cap, dict_raw=None):
-    import oracle
-    d = oracle.FrameDecoder()
-    if dict_raw is not None:
-        d.add_dict(dict_raw)
-    return d.decode_all(z, cap)
 
 
 def make_frame(plain, checksum=True, dict_id=None):
@@ -61,7 +44,7 @@ def make_frame(plain, checksum=True, dict_id=None):
         if last:
             break
     if checksum:
-        z += _xxh32(plain).to_bytes(4, "little")
+        z += xxh32(plain).to_bytes(4, "little")
     return bytes(z), body0
 
 
@@ -75,43 +58,12 @@ def flip_payload(z, body0, k=0):
     return z[:at] + bytes([z[at] ^ 0x01]) + z[at + 1:]
 
 
-class Arena:
-    """slots of caps[i] bytes in one device tensor full of the sentinel, at least GUARD bytes of sentinel on both sides of each"""
-
-    def __init__(self, caps):
-        self.caps = list(caps)
-        self.offs, at = [], GUARD
-        for i, c in enumerate(self.caps):
-            at = (at + 255) & ~255
-            self.offs.append(at + (i % 5))                        # (destinations at any alignment)
-            at = self.offs[-1] + c + GUARD
-        self.t = torch.full((at + GUARD,), SENT, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        self.ptrs = [self.t.data_ptr() + o for o in self.offs]
-
-    def check(self, plains):
-        """plains[i]: what slot i must start with, or None if it must be untouched"""
-        torch.cuda.synchronize()
-        got = self.t.cpu().numpy().tobytes()
-        want = bytearray([SENT]) * len(got)
-        for o, c, p in zip(self.offs, self.caps, plains):
-            if p is not None:
-                assert len(p) <= c
-                want[o:o + len(p)] = p
-        if got != bytes(want):
-            for i, (o, c, p) in enumerate(zip(self.offs, self.caps, plains)):
-                lo, hi = o - GUARD, o + c + GUARD
-                assert got[lo:hi] == bytes(want[lo:hi]), "slot %d (cap %d, %s) or its guards" % (i, c, "untouched" if p is None else len(p))
-            assert False, "bytes between the slots changed"
-
-
-def _full(r):
-    return (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data, r.calculated_checksum,
-            r.checksums_unverified, r.first_hashed)
+def _arena(caps):
+    return Arena(caps, shifts=[i % 5 for i in range(len(caps))])                  # (destinations at any alignment)
 
 
 def _run(c, entries, caps, **kw):
-    a = Arena(caps)
+    a = _arena(caps)
     res = c.decode_frames_device(entries, a.ptrs, caps, **kw)
     assert len(res) == len(entries)
     return a, res
@@ -119,7 +71,6 @@ def _run(c, entries, caps, **kw):
 
 @pytest.fixture(scope="module")
 def ctx():
-    import zgpu
     c = zgpu.Context(0)
     yield c
     c.close()
@@ -141,16 +92,16 @@ def good_run(ctx, good):
     caps = [len(p) + 7 for p in plains]
     a, res = _run(ctx, frames, caps, verify=True)
     for z, p, cap, r in zip(frames, plains, caps, res):
-        st, out = _oracle_alone(z, cap)
+        st, out = oracle_alone(z, cap)
         assert (st, out) == (0, p)
-        assert (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches) == (0, len(p), 1, 1, 0), (len(p), _full(r))
+        assert (r.status, r.written, r.nframes, r.checksums, r.checksum_mismatches) == (0, len(p), 1, 1, 0), (len(p), full_key(r))
         assert r.checksums_unverified == 0 and r.first_hashed == 1, len(p)
-        assert r.checksum_from_data == r.calculated_checksum == _xxh32(p)
+        assert r.checksum_from_data == r.calculated_checksum == xxh32(p)
     a.check(plains)
     st = ctx.frames_device_stats(verify=True)
     assert st["entries_failed_verify"] == 0 and st["frames_hashed"] == len(LENS) and st["frames_not_hashed"] == 0
     assert st["scatter_launches"] == 1 and st["entries_alone"] == 0
-    return caps, [_full(r) for r in res]
+    return caps, [full_key(r) for r in res]
 
 
 def test_all_good_with_verify(good_run):
@@ -176,9 +127,9 @@ def test_mismatch_fails_the_entry_and_writes_nothing(ctx, good, good_run):
     a, res = _run(ctx, entries, caps, verify=True)
     for i, r in enumerate(res):
         if i in (a_bad, b_bad):
-            assert _full(r) == (E_CHECKSUM_MISMATCH, 0, 0, 1, 1, 0, 0, 0, 0), (i, _full(r))
+            assert full_key(r) == (zgpu.E_CHECKSUM_MISMATCH, 0, 0, 1, 1, 0, 0, 0, 0), (i, full_key(r))
         else:
-            assert _full(r) == ref[i], i
+            assert full_key(r) == ref[i], i
     a.check([None if i in (a_bad, b_bad) else p for i, p in enumerate(plains)])
     st = ctx.frames_device_stats(verify=True)
     assert st["entries_failed_verify"] == 2 and st["frames_hashed"] == len(LENS)
@@ -187,7 +138,7 @@ def test_mismatch_fails_the_entry_and_writes_nothing(ctx, good, good_run):
     a, res = _run(ctx, entries, caps)
     for i, r in enumerate(res):
         bad = i in (a_bad, b_bad)
-        assert (r.status, r.written, r.checksums, r.checksum_mismatches) == (0, len(plains[i]), 1, 1 if bad else 0), (i, _full(r))
+        assert (r.status, r.written, r.checksums, r.checksum_mismatches) == (0, len(plains[i]), 1, 1 if bad else 0), (i, full_key(r))
         assert r.checksums_unverified == (1 if i == BIG else 0)                  # (the 5 MiB frame: above the default limit, not hashed)
     a.check([wrong if i == b_bad else p for i, p in enumerate(plains)])
     assert ctx.frames_device_stats(verify=True)["entries_failed_verify"] == 0
@@ -200,11 +151,11 @@ def test_isolation_and_entry_order(ctx, good, good_run):
     small = [0, 1, 2, 5, 7]
     entries = [frames[i] for i in small] + [three]
     ecaps = [caps[i] for i in small] + [400]
-    want = [ref[i] for i in small] + [(E_CHECKSUM_MISMATCH, 0, 0, 3, 1, 0, 0, 0, 0)]
+    want = [ref[i] for i in small] + [(zgpu.E_CHECKSUM_MISMATCH, 0, 0, 3, 1, 0, 0, 0, 0)]
     wplain = [plains[i] for i in small] + [None]
     for perm in ([0, 1, 2, 3, 4, 5], [5, 4, 3, 2, 1, 0], [2, 5, 0, 4, 1, 3]):
         a, res = _run(ctx, [entries[k] for k in perm], [ecaps[k] for k in perm], verify=True)
-        assert [_full(r) for r in res] == [want[k] for k in perm], perm
+        assert [full_key(r) for r in res] == [want[k] for k in perm], perm
         a.check([wplain[k] for k in perm])
         assert ctx.frames_device_stats(verify=True)["entries_failed_verify"] == 1
 
@@ -217,10 +168,10 @@ def test_precedence(ctx, good, good_run):
     entries, caps = [no_sum, broken, too_small, frames[2]], [len(plains[5]), len(plains[8]), len(plains[6]) - 1, len(plains[2])]
     a0, plain_res = _run(ctx, entries, caps)
     a, res = _run(ctx, entries, caps, verify=True)
-    assert [_full(r) for r in res] == [_full(r) for r in plain_res]
-    st_broken, _ = _oracle_alone(broken, caps[1])
-    assert st_broken not in (0, E_CHECKSUM_MISMATCH) and res[1].status == st_broken
-    assert res[2].status == E_TARGET_TOO_SMALL
+    assert [full_key(r) for r in res] == [full_key(r) for r in plain_res]
+    st_broken, _ = oracle_alone(broken, caps[1])
+    assert st_broken not in (0, zgpu.E_CHECKSUM_MISMATCH) and res[1].status == st_broken
+    assert res[2].status == zgpu.E_TARGET_TOO_SMALL
     assert (res[0].status, res[0].written, res[0].checksums, res[0].first_hashed) == (0, len(plains[5]), 0, 1)
     assert res[3].status == 0
     for x in (a0, a):
@@ -236,26 +187,25 @@ def test_hash_max_still_bounds_what_is_hashed(ctx, good, good_run):
     entries, caps = [big_bad, flip_checksum(frames[7]), frames[4]], [len(plains[BIG]), len(plains[7]), len(plains[4])]
     a, res = _run(ctx, entries, caps, verify=True, hash_max=1 << 20)
     assert (res[0].status, res[0].written, res[0].checksums, res[0].checksums_unverified, res[0].checksum_mismatches) == (0, len(wrong), 1, 1, 0)
-    assert res[1].status == E_CHECKSUM_MISMATCH and res[2].status == 0
+    assert res[1].status == zgpu.E_CHECKSUM_MISMATCH and res[2].status == 0
     a.check([bytes(wrong), None, plains[4]])
     # with no limit the same frame is caught
     a, res = _run(ctx, entries, caps, verify=True)
-    assert [r.status for r in res] == [E_CHECKSUM_MISMATCH, E_CHECKSUM_MISMATCH, 0]
+    assert [r.status for r in res] == [zgpu.E_CHECKSUM_MISMATCH, zgpu.E_CHECKSUM_MISMATCH, 0]
     a.check([None, None, plains[4]])
 
 
 def test_verify_with_no_hash_is_bad_arg(ctx, good):
-    import zgpu
     plains, frames, _ = good
     caps = [len(plains[2]), len(plains[6])]
-    a = Arena(caps)
+    a = _arena(caps)
     with pytest.raises(zgpu.ZgpuError) as e:
         ctx.decode_frames_device([frames[2], frames[6]], a.ptrs, caps, verify=True, no_hash=True)
-    assert e.value.status == E_BAD_ARG
+    assert e.value.status == zgpu.E_BAD_ARG
     src = torch.frombuffer(bytearray(frames[2]), dtype=torch.uint8).to("cuda:0")
     with pytest.raises(zgpu.ZgpuError) as e:
         ctx.decode_frames_device_src([src.data_ptr()], [src.numel()], a.ptrs[:1], caps[:1], verify=True, no_hash=True)
-    assert e.value.status == E_BAD_ARG
+    assert e.value.status == zgpu.E_BAD_ARG
     a.check([None, None])
 
 
@@ -275,18 +225,17 @@ def test_device_sources_give_the_same(ctx, good, good_run):
         blob += z
     src = torch.frombuffer(blob, dtype=torch.uint8).to("cuda:0")
     keep = src.clone()
-    b = Arena(caps)
+    b = _arena(caps)
     res = ctx.decode_frames_device_src([src.data_ptr() + o for o in offs], [len(z) for z in entries], b.ptrs, caps, verify=True)
-    assert [_full(r) for r in res] == [_full(r) for r in ref]
+    assert [full_key(r) for r in res] == [full_key(r) for r in ref]
     torch.cuda.synchronize()
     assert torch.equal(a.t, b.t) and torch.equal(src, keep)
     st = ctx.frames_device_stats(verify=True)
     assert st["entries_failed_verify"] == ref_stats["entries_failed_verify"] == 3
-    assert [r.status for r in res].count(E_CHECKSUM_MISMATCH) == 3
+    assert [r.status for r in res].count(zgpu.E_CHECKSUM_MISMATCH) == 3
 
 
 def test_dictionary_frame_alone_and_in_the_shared_submit(good):
-    import zgpu
     raw = read_pack("dict_tests.pack")["dictionary"]
     plains, frames, _ = good
     c = zgpu.Context(0)
@@ -294,7 +243,7 @@ def test_dictionary_frame_alone_and_in_the_shared_submit(good):
         did = c.add_dict(raw)
         plain = plains[7]
         z, _ = make_frame(plain, dict_id=did)
-        assert _oracle_alone(z, len(plain), raw) == (0, plain)
+        assert oracle_alone(z, len(plain), raw) == (0, plain)
         entries, caps = [flip_checksum(z), frames[4], z], [len(plain), len(plains[4]), len(plain)]
         for shared in (False, True):
             c.set_frames_shared_dicts(shared)
@@ -304,7 +253,7 @@ def test_dictionary_frame_alone_and_in_the_shared_submit(good):
             assert (c.frames_device_stats()["entries_alone"] > 0) == (not shared)
             assert (c.frames_dict_stats()["frames_shared"] > 0) == shared
             a, res = _run(c, entries, caps, verify=True)
-            assert _full(res[0]) == (E_CHECKSUM_MISMATCH, 0, 0, 1, 1, 0, 0, 0, 0), (shared, _full(res[0]))
+            assert full_key(res[0]) == (zgpu.E_CHECKSUM_MISMATCH, 0, 0, 1, 1, 0, 0, 0, 0), (shared, full_key(res[0]))
             assert [(r.status, r.written, r.checksum_mismatches) for r in res[1:]] == [(0, len(plains[4]), 0), (0, len(plain), 0)]
             a.check([None, plains[4], plain])
             assert c.frames_device_stats(verify=True)["entries_failed_verify"] == 1
@@ -313,7 +262,6 @@ def test_dictionary_frame_alone_and_in_the_shared_submit(good):
 
 
 def test_status_name():
-    import zgpu
-    assert zgpu.load_library().zgpu_status_name(E_CHECKSUM_MISMATCH) == b"ChecksumMismatch"
-    assert zgpu.E_CHECKSUM_MISMATCH == E_CHECKSUM_MISMATCH
-    assert "ChecksumMismatch" in str(zgpu.ZgpuError(E_CHECKSUM_MISMATCH))
+    assert zgpu.load_library().zgpu_status_name(zgpu.E_CHECKSUM_MISMATCH) == b"ChecksumMismatch"
+    assert zgpu.E_CHECKSUM_MISMATCH == 70
+    assert "ChecksumMismatch" in str(zgpu.ZgpuError(zgpu.E_CHECKSUM_MISMATCH))

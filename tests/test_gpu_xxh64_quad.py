@@ -9,7 +9,6 @@ import torch   # (before the library is loaded: the process must run on one HIP 
 from test_xxh64_quad_cpu import DATA_BYTES, quad_cases, quad_data
 
 pytestmark = pytest.mark.gpu
-E_BAD_ARG = 93
 R = 16                                             # zgx::kQuadRound (test_round_constant reads it from the header)
 
 
@@ -97,11 +96,11 @@ def test_bad_pointers_are_refused_before_any_launch(ctx, data):
     for kernel in (0, 1, 4):
         with pytest.raises(zgpu.ZgpuError) as e:                       # a host pointer
             ctx.hash_ranges(C.addressof(hb), [0], [4096], kernel=kernel)
-        assert e.value.status == E_BAD_ARG
+        assert e.value.status == zgpu.E_BAD_ARG
         with pytest.raises(zgpu.ZgpuError) as e:                       # a range that leads past the allocation (by far: no neighbour holds it)
             ctx.hash_ranges(t.data_ptr(), [0, 64], [32, 1 << 40], kernel=kernel)
-        assert e.value.status == E_BAD_ARG
+        assert e.value.status == zgpu.E_BAD_ARG
     with pytest.raises(zgpu.ZgpuError) as e:                           # a kernel that does not exist
         ctx.hash_ranges(t.data_ptr(), [0], [32], kernel=2)
-    assert e.value.status == E_BAD_ARG
+    assert e.value.status == zgpu.E_BAD_ARG
     _check(ctx, data, [(0, 4096)])                                     # (the context is as good as before)

@@ -5,6 +5,8 @@ if libzgpu.so is missing or no gfx950 device is usable, construction raises.
 """
 import ctypes as C
 import os
+import struct
+from array import array
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZGPU_LIB") or os.path.join(HERE, "libzgpu.so")   # ZGPU_LIB: a profiling build (tools/dev)
@@ -28,6 +30,45 @@ SEEKTAB_NONE, SEEKTAB_RESERVED_BITS, SEEKTAB_TOO_LARGE, SEEKTAB_BAD_FRAME, SEEKT
 E_CONTENT_SIZE_MISMATCH = 71   # decode_ranges_device_src only: a taken frame decoded to another length than it declares (no counterpart in the reference)
 E_UNSUPPORTED = 80
 E_HIP = 92
+E_BAD_ARG = 93
+
+# The statistics getters: the C function each reads and the keys of its slots, in the order of the enumerators that are named after them
+# (csrc/zg_capi_int.h: kDictStat*, kDevStat*, kSrcStat*, kIndexStat*, kRangeStat*). _read_stats reads through it.
+_TIMING_KEYS = ("tables", "huf", "seq", "seqpost", "scan", "lit", "flat", "sweep", "lz", "total")   # csrc/zg_engine.h: ZG_T_*
+_STATS = {
+    "Context.frames_dict_stats": ("zgpu_debug_frames_dict_stats", C.c_uint64,
+                                  ("frames_shared", "fill_launches", "bytes_replicated", "fill_us", "entries_alone")),
+    "Context.frames_device_stats": ("zgpu_debug_frames_device_stats", C.c_uint64,
+                                    ("submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed",
+                                     "entries_alone", "entries_failed_verify", "hash_us")),
+    "Context.frames_device_src_stats": ("zgpu_debug_frames_device_src_stats", C.c_uint64,
+                                        ("walk_launches", "walk_us", "skeleton_bytes", "gather_launches", "gather_us", "input_bytes_to_host")),
+    "Context.frames_index_stats": ("zgpu_debug_frames_index_stats", C.c_uint64,
+                                   ("launches", "kernel_us", "bytes_downloaded", "input_bytes_to_host")),
+    "Context.ranges_stats": ("zgpu_debug_ranges_stats", C.c_uint64,
+                             ("seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
+                              "plaintext_decoded", "bytes_written")),
+    "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
+                       ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
+    "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
+                        ("units", "direct_units", "noseq_units", "pointer_units", "sweep_steps", "pointer_bytes", "direct_bytes")),
+    "CStreamingDecoder.stats": ("zgpu_streaming_stats", C.c_uint64,
+                                ("mode", "runs", "dropped", "host_bytes", "us_worker_idle", "us_run", "us_land", "us_commit", "us_ring_full",
+                                 "us_reader_wait", "us_reader_copy", "us_pull", "us_prepare", "us_kernels") + tuple("k_" + k for k in _TIMING_KEYS)),
+}
+
+
+def _read_stats(L, getter, *handle, slots=None, counted=True):
+    """What getter's C function (_STATS) writes for handle, under the table's keys. slots: how many to ask for (default: all). counted: the
+    function returns how many slots it filled, and the dict holds those; else it returns a status, raised unless 0."""
+    fn, ctype, keys = _STATS[getter]
+    a = (ctype * len(keys))()
+    k = getattr(L, fn)(*handle, a, len(keys) if slots is None else slots)
+    if not counted:
+        if k:
+            raise ZgpuError(k)
+        k = len(keys)
+    return dict(zip(keys[:k], a[:k]))
 
 
 class EntryResultC(C.Structure):
@@ -188,7 +229,6 @@ def seek_table_frame(csizes, dsizes, checksums=None):
     entered with dsize 0): the skippable frame that, appended behind those frames, makes an entry seekable for
     Context.decode_ranges_seek_table_device_src. checksums[k]: the low 32 bits of the XXH64 (seed 0) of frame k's plaintext; None: the table
     carries none. Host only."""
-    import struct
     n = len(csizes)
     if len(dsizes) != n or (checksums is not None and len(checksums) != n):
         raise ValueError("seek_table_frame: one size pair (and one checksum) per frame")
@@ -419,8 +459,6 @@ def _declare(L):
     L.zgpu_decoder_set_hash.argtypes = [vp, C.c_int]
     L.zgpu_decoder_set_read_ahead.argtypes = [vp, C.c_uint64]
     L.zgpu_decoder_stream_error.argtypes = [vp]
-    for f in ("zgpu_decoder_is_finished", "zgpu_decoder_checksum_from_data"):
-        getattr(L, f).argtypes = [vp] if f.endswith("finished") else [vp, P(C.c_uint32)]
     return L
 
 
@@ -429,6 +467,58 @@ class ZgpuError(Exception):
         self.status = status
         name = load_library().zgpu_status_name(status).decode()
         super().__init__("%s (status %d) %s" % (name, status, what))
+
+
+# ---- marshalling of the calls that take parallel lists, one element per entry ---------------------------------------------------------------
+def _ptr_array(ptrs):
+    """void*[max(n, 1)] of n addresses (integers); 0 is NULL"""
+    return (C.c_void_p * max(len(ptrs), 1)).from_buffer_copy(array("Q", ptrs if len(ptrs) else (0,)))   # (one copy of 64-bit words: no Python loop)
+
+
+def _size_array(sizes):
+    """size_t[max(n, 1)] of n sizes (integers)"""
+    return (C.c_size_t * max(len(sizes), 1)).from_buffer_copy(array("Q", sizes if len(sizes) else (0,)))
+
+
+def _one_per(method, n, *lists):
+    """every list (None: not given) holds one element for each of the call's n entries"""
+    for x in lists:
+        if x is not None and len(x) != n:
+            raise ValueError("%s: %d entries, but a parallel list of %d elements" % (method, n, len(x)))
+
+
+def _opts(hash_max, no_hash, verify):
+    return DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
+
+
+# what _results makes of an array of each record: the record's fields in the order of _fields_ as a struct format — a zgpu_range_result begins with
+# its zgpu_device_entry_result (.d), the zgpu_seek behind it is passed over — and the class of the Python object
+_RESULT_RECORDS = {EntryResultC: ("<QiIIIII", EntryResult), DeviceEntryResultC: ("<QiIIIIIII", DeviceEntryResult),
+                   RangeResultC: ("<QiIIIIIII64x", DeviceEntryResult)}
+
+
+def _results(res, n):
+    """The first n records of a ctypes array of zgpu_entry_result (as EntryResult objects, data left to the caller), zgpu_device_entry_result or
+    zgpu_range_result (as DeviceEntryResult objects): every field as it stands, whatever the status. The array is read in one pass over its
+    memory: one ctypes access per field costs more than the rest of the conversion."""
+    fmt, cls = _RESULT_RECORDS[res._type_]
+    out = []
+    for v in struct.iter_unpack(fmt, memoryview(res).cast("B")[:n * C.sizeof(res._type_)]):
+        e = cls()
+        e.written, e.status, e.nframes, e.checksums, e.checksum_mismatches, e.checksum_from_data, e.calculated_checksum = v[:7]
+        if cls is DeviceEntryResult:
+            e.checksums_unverified, e.first_hashed = v[7:]
+        out.append(e)
+    return out
+
+
+def _slots(caps):
+    """(offs, total): slots of caps[i] bytes back to back, each on a 256-byte boundary"""
+    offs, total = [], 0
+    for c in caps:
+        offs.append(total)
+        total += (int(c) + 255) & ~255
+    return offs, total
 
 
 class Context:
@@ -452,10 +542,7 @@ class Context:
 
     def tuning(self):
         """the switches this context's engine took when it was created (zgpu_debug_tuning): all defaults in the product library"""
-        a = (C.c_uint32 * 8)()
-        n = self.L.zgpu_debug_tuning(self.h, a, 8)
-        keys = ["dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder"]
-        d = dict(zip(keys[:n], [int(x) for x in a][:n]))
+        d = _read_stats(self.L, "Context.tuning", self.h)
         for k in ("seq_packed", "flat4"):
             if d.get(k, 0) >= 1 << 31:
                 d[k] -= 1 << 32
@@ -506,6 +593,14 @@ class Context:
     def prepare(self, src):
         return Batch(self, src)
 
+    def _check(self, st, what=None):
+        """the one error path of the calls below: a status other than 0 raises with the context's last error (or the fixed text `what`)"""
+        if st:
+            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode() if what is None else what)
+
+    def _stats(self, getter, slots=None):
+        return _read_stats(self.L, "Context." + getter, self.h, slots=slots)
+
     def decode_frames(self, entries, caps=None):
         """zgpu_decode_frames: many independent buffers (bytes, or (address, length) of memory the caller keeps alive), each what decode_all
         takes, in few submits. caps: bytes of room per entry (default: plaintext_bound of the entry). Returns one EntryResult per entry, which is
@@ -515,27 +610,14 @@ class Context:
         srcs, lens, keep = self._entries(entries)
         if caps is None:
             caps = self._bounds(srcs, lens, n)
-        offs = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            offs[1:] = np.cumsum(np.asarray(caps, dtype=np.uint64))
-        out = np.empty(max(int(offs[-1]), 1), dtype=np.uint8)
+        offs = [0] + (np.cumsum(np.asarray(caps, dtype=np.uint64)).tolist() if n else [])
+        out = np.empty(max(offs[-1], 1), dtype=np.uint8)
         base = out.ctypes.data
-        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            dsts[i], capa[i] = base + int(offs[i]), int(caps[i])
         res = (EntryResultC * max(n, 1))()
-        st = self.L.zgpu_decode_frames(self.h, srcs, lens, n, dsts, capa, res)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        outl = []
-        for i in range(n):
-            r, e = res[i], EntryResult()
-            e.status, e.written, e.nframes = r.status, r.written, r.nframes
-            e.checksums, e.checksum_mismatches = r.checksums, r.checksum_mismatches
-            e.checksum_from_data, e.calculated_checksum = r.checksum_from_data, r.calculated_checksum
-            o = int(offs[i])
-            e.data = out[o:o + r.written].tobytes() if r.status == 0 else None
-            outl.append(e)
+        self._check(self.L.zgpu_decode_frames(self.h, srcs, lens, n, _ptr_array([base + o for o in offs[:n]]), _size_array(caps), res))
+        outl = _results(res, n)
+        for o, e in zip(offs, outl):
+            e.data = out[o:o + e.written].tobytes() if e.status == 0 else None
         return outl
 
     def frames_submits(self):
@@ -552,24 +634,22 @@ class Context:
 
     def frames_dict_stats(self):
         """the last decode_frames / decode_frames_device / decode_frames_device_src call (zgpu_debug_frames_dict_stats)"""
-        a = (C.c_uint64 * 5)()
-        k = self.L.zgpu_debug_frames_dict_stats(self.h, a, 5)
-        keys = ["frames_shared", "fill_launches", "bytes_replicated", "fill_us", "entries_alone"]
-        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+        return self._stats("frames_dict_stats")
 
     @staticmethod
     def _entries(entries):
         """(srcs, lens, what keeps them alive) of entries: bytes, or (address, length) of memory the caller keeps alive"""
-        n = len(entries)
-        srcs, lens, keep = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), []
-        for i, e in enumerate(entries):
+        ptrs, lens, keep = [], [], []
+        for e in entries:
             if isinstance(e, tuple):
-                srcs[i], lens[i] = e[0], e[1]
+                ptrs.append(e[0])
+                lens.append(e[1])
             else:
                 b = C.c_char_p(bytes(e))                   # (no copy of a bytes object)
                 keep.append(b)
-                srcs[i], lens[i] = C.cast(b, C.c_void_p).value, len(e)
-        return srcs, lens, keep
+                ptrs.append(C.cast(b, C.c_void_p).value)
+                lens.append(len(e))
+        return _ptr_array(ptrs), _size_array(lens), keep
 
     def _bounds(self, srcs, lens, n):
         return [self.L.zgpu_plaintext_bound(C.cast(C.c_void_p(srcs[i]), C.c_char_p), lens[i]) for i in range(n)]
@@ -584,42 +664,19 @@ class Context:
         its destination is written (checksums / checksum_mismatches still say which count failed); hash_max=0 then means no limit for frames
         that carry a checksum. verify with no_hash raises E_BAD_ARG. Returns one DeviceEntryResult per entry."""
         n = len(entries)
-        if len(ptrs) != n or len(caps) != n:
-            raise ValueError("decode_frames_device: one pointer and one capacity per entry")
+        _one_per("decode_frames_device", n, ptrs, caps)
         srcs, lens, keep = self._entries(entries)
-        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            dsts[i], capa[i] = int(ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
         res = (DeviceEntryResultC * max(n, 1))()
-        st = self.L.zgpu_decode_frames_device(self.h, srcs, lens, n, dsts, capa, C.byref(opts), res)
+        st = self.L.zgpu_decode_frames_device(self.h, srcs, lens, n, _ptr_array(ptrs), _size_array(caps),
+                                              C.byref(_opts(hash_max, no_hash, verify)), res)
         del keep
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return self._device_results(res, n)
-
-    @staticmethod
-    def _device_results(res, n):
-        outl = []
-        for i in range(n):
-            d, e = res[i], DeviceEntryResult()
-            r = d.r
-            e.status, e.written, e.nframes = r.status, r.written, r.nframes
-            e.checksums, e.checksum_mismatches = r.checksums, r.checksum_mismatches
-            e.checksum_from_data, e.calculated_checksum = r.checksum_from_data, r.calculated_checksum
-            e.checksums_unverified, e.first_hashed = d.checksums_unverified, d.first_hashed
-            outl.append(e)
-        return outl
+        self._check(st)
+        return _results(res, n)
 
     def frames_device_stats(self, verify=False):
         """the last decode_frames_device call (zgpu_debug_frames_device_stats). verify=True: with the two fields of verification as well —
         entries_failed_verify (out[7]) and hash_us (out[8], the hash kernel's time, HIP events)."""
-        m = 9 if verify else 7
-        a = (C.c_uint64 * 9)()
-        k = self.L.zgpu_debug_frames_device_stats(self.h, a, m)
-        keys = ["submits", "scatter_launches", "bytes_scattered", "scatter_us", "frames_hashed", "frames_not_hashed", "entries_alone",
-                "entries_failed_verify", "hash_us"]
-        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+        return self._stats("frames_device_stats", 9 if verify else 7)
 
     def hash_ranges(self, ptr, offs, lens, kernel=0):
         """zgpu_debug_hash_ranges: XXH64 (seed 0) of the ranges [ptr + offs[i], + lens[i]) of device memory by the hash kernels of the device
@@ -627,13 +684,10 @@ class Context:
         memory of this context's device that holds every range (else E_BAD_ARG, nothing launched). Returns the digests in the caller's order;
         hash_ranges_us() is the kernel's time in that call."""
         n = len(offs)
-        if len(lens) != n:
-            raise ValueError("hash_ranges: one length per offset")
+        _one_per("hash_ranges", n, lens)
         o, ln, out = (C.c_uint64 * max(n, 1))(*offs), (C.c_uint64 * max(n, 1))(*lens), (C.c_uint64 * max(n, 1))()
-        st = self.L.zgpu_debug_hash_ranges(self.h, int(ptr) or None, o, ln, n, int(kernel), out)
-        if st:
-            raise ZgpuError(st, "zgpu_debug_hash_ranges")
-        return [int(out[i]) for i in range(n)]
+        self._check(self.L.zgpu_debug_hash_ranges(self.h, int(ptr) or None, o, ln, n, int(kernel), out), "zgpu_debug_hash_ranges")
+        return out[:n]
 
     def hash_ranges_us(self):
         return int(self.L.zgpu_debug_hash_ranges_us(self.h))
@@ -645,54 +699,34 @@ class Context:
         Nothing in flight may write the sources or touch the destinations during the call. Results are those of decode_frames_device on a
         host copy of the same bytes, verify included. Returns one DeviceEntryResult per entry."""
         n = len(src_ptrs)
-        if len(lens) != n or len(dst_ptrs) != n or len(caps) != n:
-            raise ValueError("decode_frames_device_src: one length, one destination and one capacity per source")
-        srcs, lena = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            srcs[i], lena[i] = int(src_ptrs[i]) or None, int(lens[i])
-            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
+        _one_per("decode_frames_device_src", n, lens, dst_ptrs, caps)
         res = (DeviceEntryResultC * max(n, 1))()
-        st = self.L.zgpu_decode_frames_device_src(self.h, srcs, lena, n, dsts, capa, C.byref(opts), res)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return self._device_results(res, n)
+        self._check(self.L.zgpu_decode_frames_device_src(self.h, _ptr_array(src_ptrs), _size_array(lens), n, _ptr_array(dst_ptrs), _size_array(caps),
+                                                         C.byref(_opts(hash_max, no_hash, verify)), res))
+        return _results(res, n)
 
     def frames_device_src_stats(self):
         """the last decode_frames_device_src call (zgpu_debug_frames_device_src_stats)"""
-        a = (C.c_uint64 * 6)()
-        k = self.L.zgpu_debug_frames_device_src_stats(self.h, a, 6)
-        keys = ["walk_launches", "walk_us", "skeleton_bytes", "gather_launches", "gather_us", "input_bytes_to_host"]
-        return dict(zip(keys[:k], [int(x) for x in a][:k]))
-
-    @staticmethod
-    def _device_sources(src_ptrs, lens):
-        n = len(src_ptrs)
-        if len(lens) != n:
-            raise ValueError("one length per source")
-        srcs, lena = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            srcs[i], lena[i] = int(src_ptrs[i]) or None, int(lens[i])
-        return n, srcs, lena
+        return self._stats("frames_device_src_stats")
 
     def frames_index_device(self, src_ptrs, lens):
         """zgpu_frames_index_device: what entries in DEVICE memory hold, from frame and block headers alone. src_ptrs[i] is the address of
         lens[i] bytes on this context's device (any alignment; checked like the sources of decode_frames_device_src: a pointer that is not
         such memory gives that entry E_BAD_ARG). One kernel launch, 48 bytes per entry come back, no byte of the input does. Returns one
         EntryIndex per entry; .bound is plaintext_bound of the entry: room enough for decode_frames_device_src."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        n = len(src_ptrs)
+        _one_per("frames_index_device", n, lens)
         ents = (EntryIndexC * max(n, 1))()
-        st = self.L.zgpu_frames_index_device(self.h, srcs, lena, n, ents)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return [EntryIndex(ents[i]) for i in range(n)]
+        self._check(self.L.zgpu_frames_index_device(self.h, _ptr_array(src_ptrs), _size_array(lens), n, ents))
+        return [EntryIndex(c) for c in ents[:n]]
 
     def frames_table_device(self, src_ptrs, lens, room=None):
         """zgpu_frames_table_device: frames_index_device plus one FrameIndex per frame (zstd or skippable) of every entry. Returns
         (entries, frame_first, frames): frames[frame_first[i]:frame_first[i + 1]] are entry i's, in order. room: records to make room for in the
         first call (default: two per entry); a table that turns out too small is sized by a second call."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
+        n = len(src_ptrs)
+        _one_per("frames_table_device", n, lens)
+        srcs, lena = _ptr_array(src_ptrs), _size_array(lens)
         ents = (EntryIndexC * max(n, 1))()
         first = (C.c_uint64 * (n + 1))()
         need = C.c_size_t(0)
@@ -703,39 +737,47 @@ class Context:
             if st != E_TARGET_TOO_SMALL:
                 break
             cap = need.value
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return [EntryIndex(ents[i]) for i in range(n)], [int(x) for x in first], [FrameIndex(frames[k]) for k in range(need.value)]
+        self._check(st)
+        return [EntryIndex(c) for c in ents[:n]], first[:], [FrameIndex(c) for c in frames[:need.value]]
 
     def frames_index_stats(self):
         """the last frames_index_device / frames_table_device call (zgpu_debug_frames_index_stats)"""
-        a = (C.c_uint64 * 4)()
-        k = self.L.zgpu_debug_frames_index_stats(self.h, a, 4)
-        keys = ["launches", "kernel_us", "bytes_downloaded", "input_bytes_to_host"]
-        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+        return self._stats("frames_index_stats")
 
     @staticmethod
-    def _ranges(ranges, anchors, n):
-        if len(ranges) != n or (anchors is not None and len(anchors) != n):
-            raise ValueError("one range (and one anchor) per source")
+    def _ranges(ranges, anchors):
+        n = len(ranges)
         rg = (RangeC * max(n, 1))()
         for i in range(n):
             a = anchors[i] if anchors is not None and anchors[i] is not None else (0, 0)
             rg[i] = RangeC(int(ranges[i][0]), int(ranges[i][1]), int(a[0]), int(a[1]))
         return rg
 
+    def _frames_seek(self, what, src_ptrs, lens, ranges, anchors):
+        """the body of the two seek calls: zgpu_<what> on the sources and ranges (anchors: None for the seek-table form)"""
+        n = len(src_ptrs)
+        _one_per(what, n, lens, ranges, anchors)
+        out = (SeekC * max(n, 1))()
+        fn = getattr(self.L, "zgpu_" + what)
+        self._check(fn(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors), out))
+        return [Seek(c) for c in out[:n]]
+
+    def _decode_ranges(self, what, src_ptrs, lens, ranges, anchors, dst_ptrs, caps, opts):
+        """the body of the two range-decode calls: zgpu_<what> (anchors: None for the seek-table form)"""
+        n = len(src_ptrs)
+        _one_per(what, n, lens, ranges, anchors, dst_ptrs, caps)
+        res = (RangeResultC * max(n, 1))()
+        fn = getattr(self.L, "zgpu_" + what)
+        self._check(fn(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors), _ptr_array(dst_ptrs), _size_array(caps),
+                       C.byref(opts), res))
+        return _results(res, n), [Seek(res[i].seek) for i in range(n)]
+
     def frames_seek_device(self, src_ptrs, lens, ranges, anchors=None):
         """zgpu_frames_seek_device: which whole frames of entries in DEVICE memory hold plaintext bytes [begin, begin + len) of them, from
         frame and block headers alone. ranges[i] = (begin, len); anchors[i] = (anchor_src, anchor_plain) or None: a frame boundary of the entry
         at which the header chain starts and its plaintext offset (anchor_before gives one from a cached frames_table_device). One kernel
         launch, 64 bytes per entry come back, no byte of the input does. Returns one Seek per entry."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
-        rg = self._ranges(ranges, anchors, n)
-        out = (SeekC * max(n, 1))()
-        st = self.L.zgpu_frames_seek_device(self.h, srcs, lena, n, rg, out)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return [Seek(out[i]) for i in range(n)]
+        return self._frames_seek("frames_seek_device", src_ptrs, lens, ranges, anchors)
 
     def decode_ranges_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, anchors=None, hash_max=0, no_hash=False, verify=False):
         """zgpu_decode_ranges_device_src: plaintext bytes ranges[i] = (begin, len) of entry i (device memory, as decode_frames_device_src takes
@@ -743,60 +785,25 @@ class Context:
         range are never decoded (a defect in them is not seen, a false declared size in them shifts the coordinates); frames behind it are
         not read. Returns (results, seeks): one DeviceEntryResult per entry — written is the clipped count, E_CONTENT_SIZE_MISMATCH a taken
         frame that decoded to another length than it declares — and the Seek record the call acted on."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
-        if len(dst_ptrs) != n or len(caps) != n:
-            raise ValueError("decode_ranges_device_src: one destination and one capacity per source")
-        rg = self._ranges(ranges, anchors, n)
-        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
-        res = (RangeResultC * max(n, 1))()
-        st = self.L.zgpu_decode_ranges_device_src(self.h, srcs, lena, n, rg, dsts, capa, C.byref(opts), res)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        dres = (DeviceEntryResultC * max(n, 1))(*[res[i].d for i in range(n)])
-        return self._device_results(dres, n), [Seek(res[i].seek) for i in range(n)]
+        return self._decode_ranges("decode_ranges_device_src", src_ptrs, lens, ranges, anchors, dst_ptrs, caps, _opts(hash_max, no_hash, verify))
 
     def frames_seek_table_device(self, src_ptrs, lens, ranges):
         """zgpu_frames_seek_table_device: frames_seek_device answered from the seekable format's seek table at each entry's end (seek_table_frame
         writes one), one wave per entry: no frame or block header is read, frames need not declare a size. Returns one Seek per entry, in the
         table's coordinates; an entry without a usable table has status E_SEEK_TABLE and why SEEKTAB_*."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
-        rg = self._ranges(ranges, None, n)
-        out = (SeekC * max(n, 1))()
-        st = self.L.zgpu_frames_seek_table_device(self.h, srcs, lena, n, rg, out)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        return [Seek(out[i]) for i in range(n)]
+        return self._frames_seek("frames_seek_table_device", src_ptrs, lens, ranges, None)
 
     def decode_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False):
         """zgpu_decode_ranges_seek_table_device_src: decode_ranges_device_src with the selection taken from each entry's seek table. Only the
         frames the table names for the range are decoded, whether or not they declare a size. Returns (results, seeks) as
         decode_ranges_device_src does; E_SEEK_TABLE: no usable table, E_CONTENT_SIZE_MISMATCH: the taken frames decoded to another total than
         the table promises."""
-        n, srcs, lena = self._device_sources(src_ptrs, lens)
-        if len(dst_ptrs) != n or len(caps) != n:
-            raise ValueError("decode_ranges_seek_table_device_src: one destination and one capacity per source")
-        rg = self._ranges(ranges, None, n)
-        dsts, capa = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        for i in range(n):
-            dsts[i], capa[i] = int(dst_ptrs[i]) or None, int(caps[i])
-        opts = DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
-        res = (RangeResultC * max(n, 1))()
-        st = self.L.zgpu_decode_ranges_seek_table_device_src(self.h, srcs, lena, n, rg, dsts, capa, C.byref(opts), res)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode())
-        dres = (DeviceEntryResultC * max(n, 1))(*[res[i].d for i in range(n)])
-        return self._device_results(dres, n), [Seek(res[i].seek) for i in range(n)]
+        return self._decode_ranges("decode_ranges_seek_table_device_src", src_ptrs, lens, ranges, None, dst_ptrs, caps,
+                                   _opts(hash_max, no_hash, verify))
 
     def ranges_stats(self):
         """the last frames_seek_device / decode_ranges_device_src call or seek-table call (zgpu_debug_ranges_stats)"""
-        a = (C.c_uint64 * 8)()
-        k = self.L.zgpu_debug_ranges_stats(self.h, a, 8)
-        keys = ["seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
-                "plaintext_decoded", "bytes_written"]
-        return dict(zip(keys[:k], [int(x) for x in a][:k]))
+        return self._stats("ranges_stats")
 
     def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False, seek_table=False):
         """decode_ranges_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
@@ -805,29 +812,24 @@ class Context:
         input crosses to the host. Returns (tensors, results, seeks): tensors[i] is a view of entry i's slot cut to `written` bytes (empty
         unless status == 0). Same single-runtime rule as decode_tensors. torch is imported here, not by `import zgpu`.
         seek_table=True: the selections come from the entries' seek tables (decode_ranges_seek_table_device_src; anchors must be None)."""
-        import torch
         self._tensor_check(tensors, "decode_tensor_ranges")
         if seek_table and anchors is not None:
             raise ValueError("decode_tensor_ranges: a seek table is the index, there is nothing to anchor")
-        dev = torch.device("cuda", self.device)
         ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
         seeks = self.frames_seek_table_device(ptrs, lens, ranges) if seek_table else self.frames_seek_device(ptrs, lens, ranges, anchors)
         caps = [min(int(r[1]), s.bound) for r, s in zip(ranges, seeks)]
-        offs, total = [], 0
-        for c in caps:
-            offs.append(total)
-            total += (int(c) + 255) & ~255
-        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=dev)
+        buf, offs, dsts = self._slot_tensor(caps)
+        if seek_table:
+            res, seeks = self.decode_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
+        else:
+            res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, dsts, caps, anchors=anchors, hash_max=hash_max, no_hash=no_hash,
+                                                       verify=verify)
+        return self._views(buf, offs, res), res, seeks
+
+    def _torch_sync(self):
+        import torch
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
-        base = buf.data_ptr()
-        if seek_table:
-            res, seeks = self.decode_ranges_seek_table_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, hash_max=hash_max,
-                                                                  no_hash=no_hash, verify=verify)
-        else:
-            res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, [base + o for o in offs], caps, anchors=anchors, hash_max=hash_max,
-                                                       no_hash=no_hash, verify=verify)
-        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res, seeks
 
     def _tensor_check(self, tensors, what):
         import torch
@@ -836,9 +838,22 @@ class Context:
         for t in tensors:
             if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
                 raise ValueError("%s: contiguous torch.uint8 tensors on %s" % (what, dev))
-        # the tensors may still be written on torch's stream
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream().synchronize()
+        self._torch_sync()                       # the tensors may still be written on torch's stream
+
+    def _slot_tensor(self, caps):
+        """(tensor, offs, addresses): ONE new torch.uint8 tensor on this context's device with a slot of caps[i] bytes per entry (_slots), handed
+        out once torch's current stream there has drained — the caching allocator may hand out memory that is still in use on it"""
+        import torch
+        offs, total = _slots(caps)
+        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        self._torch_sync()
+        base = buf.data_ptr()
+        return buf, offs, [base + o for o in offs]
+
+    @staticmethod
+    def _views(buf, offs, res):
+        """entry i's slot of buf cut to `written` bytes (empty unless status == 0)"""
+        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)]
 
     def split_tensor_frames(self, tensor):
         """One view per zstd frame of a contiguous torch.uint8 tensor on this context's device that holds concatenated frames, cut at the frame
@@ -862,23 +877,13 @@ class Context:
         byte of the input crosses to the host. Returns (tensors, results) like decode_frames_to_tensors, under the same single-runtime rule
         (import torch before creating the first Context). verify: as decode_frames_device — an entry that fails its checksum comes back as an
         empty view with E_CHECKSUM_MISMATCH. torch is imported here, not by `import zgpu`."""
-        import torch
         self._tensor_check(tensors, "decode_tensors")
-        dev = torch.device("cuda", self.device)
         ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
         if caps is None:
             caps = [e.bound for e in self.frames_index_device(ptrs, lens)]
-        offs, total = [], 0
-        for c in caps:
-            offs.append(total)
-            total += (int(c) + 255) & ~255
-        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=dev)
-        # the inputs may still be written, and the caching allocator may hand out memory that is still in use, on torch's stream
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream().synchronize()
-        base = buf.data_ptr()
-        res = self.decode_frames_device_src(ptrs, lens, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
-        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
+        buf, offs, dsts = self._slot_tensor(caps)
+        res = self.decode_frames_device_src(ptrs, lens, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
+        return self._views(buf, offs, res), res
 
     def decode_frames_to_tensors(self, entries, caps=None, hash_max=0, no_hash=False, verify=False):
         """decode_frames_device into ONE torch.uint8 tensor on this context's device, every entry's slot 256-byte aligned (caps: bytes of room per
@@ -886,27 +891,16 @@ class Context:
         (empty unless status == 0), results[i] its DeviceEntryResult. torch is imported here, not by `import zgpu`.
         torch wheels ship a HIP runtime of their own: the process must run on ONE runtime for torch's memory to be known to this library,
         which it does when torch is imported before the first Context is created (load_library); otherwise this raises."""
-        import torch
-        hip = set(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln) if os.path.exists("/proc/self/maps") else ()
-        if len(hip) > 1:
-            raise RuntimeError("two HIP runtimes are loaded (%s): import torch before creating the first zgpu.Context" % ", ".join(sorted(hip)))
+        import torch   # noqa: F401 (before the check: its runtime has to be among the loaded ones)
+        self._one_hip_runtime()
         n = len(entries)
         srcs, lens, keep = self._entries(entries)
         if caps is None:
             caps = self._bounds(srcs, lens, n)
-        offs, total = [], 0
-        for c in caps:
-            offs.append(total)
-            total += (int(c) + 255) & ~255
-        buf = torch.empty(max(total, 256), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        # the caching allocator may hand out memory that is still in use on torch's stream
-        with torch.cuda.device(self.device):
-            torch.cuda.current_stream().synchronize()
-        base = buf.data_ptr()
-        ents = [(srcs[i] or 0, lens[i]) for i in range(n)]
-        res = self.decode_frames_device(ents, [base + o for o in offs], caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
+        buf, offs, dsts = self._slot_tensor(caps)
+        res = self.decode_frames_device([(srcs[i] or 0, lens[i]) for i in range(n)], dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
         del keep
-        return [buf[o:o + (r.written if r.status == 0 else 0)] for o, r in zip(offs, res)], res
+        return self._views(buf, offs, res), res
 
 
 class Batch:
@@ -930,22 +924,20 @@ class Batch:
     __del__ = close
 
     def run(self):
-        st = self.L.zgpu_batch_run(self.h)
-        if st:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.ctx.h).decode())
+        self.ctx._check(self.L.zgpu_batch_run(self.h))
 
     def sync(self):
         tot, bf, bs = C.c_uint64(), C.c_uint32(), C.c_uint32()
         st = self.L.zgpu_batch_sync(self.h, C.byref(tot), C.byref(bf), C.byref(bs))
-        if st and st != E_UNSUPPORTED:
-            raise ZgpuError(st, self.L.zgpu_last_error(self.ctx.h).decode())
+        if st != E_UNSUPPORTED:
+            self.ctx._check(st)
         self.total_out, self.bad_frame, self.bad_status = tot.value, bf.value, bs.value or st
         return self.total_out
 
     def timings(self):
         a = (C.c_float * 10)()
         self.L.zgpu_batch_timings(self.h, a, 10)
-        return dict(zip(["tables", "huf", "seq", "seqpost", "scan", "lit", "flat", "sweep", "lz", "total"], list(a)))
+        return dict(zip(_TIMING_KEYS, list(a)))
 
     def debug_timers(self):
         a = (C.c_uint64 * 1024)()
@@ -1218,15 +1210,11 @@ class Pool:
         if st:
             raise ZgpuError(st)
         self.last_njobs = nj.value
-        return dict(zip(["tables", "huf", "seq", "seqpost", "scan", "lit", "flat", "sweep", "lz", "total"], list(a))), pb.value, cb.value, nb.value
+        return dict(zip(_TIMING_KEYS, list(a))), pb.value, cb.value, nb.value
 
     def plan_stats(self, g=0):
         """the LZ77 plan of GPU g's resident jobs after a run (zgpu_pool_plan_stats)"""
-        a = (C.c_uint64 * 7)()
-        st = self.L.zgpu_pool_plan_stats(self.h, g, a, 7)
-        if st:
-            raise ZgpuError(st)
-        return dict(zip(["units", "direct_units", "noseq_units", "pointer_units", "sweep_steps", "pointer_bytes", "direct_bytes"], [int(x) for x in a]))
+        return _read_stats(self.L, "Pool.plan_stats", self.h, g, counted=False)
 
     def frame(self, i):
         gpu, size, st = C.c_int(), C.c_uint64(), C.c_uint32()
@@ -1332,11 +1320,7 @@ class CStreamingDecoder:
         return self.L.zgpu_streaming_source_position(self.h)
 
     def stats(self):
-        a = (C.c_uint64 * 24)()
-        self.L.zgpu_streaming_stats(self.h, a, 24)
-        return dict(zip(["mode", "runs", "dropped", "host_bytes", "us_worker_idle", "us_run", "us_land", "us_commit", "us_ring_full", "us_reader_wait",
-                         "us_reader_copy", "us_pull", "us_prepare", "us_kernels", "k_tables", "k_huf", "k_seq", "k_seqpost", "k_scan", "k_lit", "k_flat",
-                         "k_sweep", "k_lz", "k_total"], [int(x) for x in a]))
+        return _read_stats(self.L, "CStreamingDecoder.stats", self.h)
 
     def close(self):
         if getattr(self, "h", None):
