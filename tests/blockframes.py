@@ -5,8 +5,10 @@ zg_k_sparse, zg_k_lz and the sweep gather from their bytes). The frames come fro
 of what was asked for, checked there against the oracle and libzstd (except the names of BLOCK_LIBZSTD_DIFFERS).
 
 Every valid frame is (name, zst, plaintext); invalid ones have plaintext None and STATUS[name] holds the oracle's answer."""
+import functools
 import random
 
+import framesuite
 import oracle
 import tabframes
 from tabframes import Block
@@ -362,31 +364,16 @@ FAMILIES = {
     "invalid": invalid,
 }
 
-_CACHE = {}
 
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    """[(family, name, zst, plaintext or None)]; checks the BLOCK_LIBZSTD_DIFFERS cap once every family is built"""
-    out = [(fam, *f) for fam in FAMILIES for f in family(fam)]
-    names = [n for _, n, _, p in out if p is not None]
-    assert len(set(n for _, n, _, _ in out)) == len(out), "frame names repeat"
+def _check_differs(frames):
+    """the BLOCK_LIBZSTD_DIFFERS cap, once every family is built"""
+    names = [n for _, n, _, p in frames if p is not None]
     assert set(BLOCK_LIBZSTD_DIFFERS) <= set(names), "BLOCK_LIBZSTD_DIFFERS may hold only frames the oracle accepts"
     assert len(BLOCK_LIBZSTD_DIFFERS) * 10 <= len(names), "BLOCK_LIBZSTD_DIFFERS holds more than a tenth of the valid frames"
-    return out
 
 
-def valid_frames():
-    return [f for f in all_frames() if f[3] is not None]
-
-
-def invalid_frames():
-    return [f for f in all_frames() if f[3] is None]
+_F = framesuite.Families(FAMILIES, _check_differs)
+family, all_frames, valid_frames, invalid_frames = _F.family, _F.all_frames, _F.valid_frames, _F.invalid_frames
 
 
 BATCH_REPS = ("lit_sizes_raw_small", "lit_sizes_rle_mid", "lit_sizes_lit_raw_small", "lit_sizes_lit_rle_small", "lit_sizes_lit_huf4_mid",
@@ -394,12 +381,11 @@ BATCH_REPS = ("lit_sizes_raw_small", "lit_sizes_rle_mid", "lit_sizes_lit_raw_sma
               "src_overlap_rle")
 
 
+@functools.lru_cache(None)
 def batch_alignment():
     """a submit order, not new frames: each of BATCH_REPS sixteen times, behind a pad frame (one Raw block) of 0 .. 15 bytes sized so
     that the frame's place in the output (frame_out.out_base: ualign in zg_flat4.h, lead in both flatten bodies, zg_k_lit's
     stores) takes each residue mod 16 once. Returns ([(name, zst, plaintext)], {name: [indices in the list]})"""
-    if "_batch" in _CACHE:
-        return _CACHE["_batch"]
     rng = random.Random(606)
     by_name = {n: (n, z, p) for _, n, z, p in valid_frames()}
     pads = [_build("pad%d" % p, [("raw", rng.randbytes(p))]) for p in range(16)]
@@ -412,7 +398,6 @@ def batch_alignment():
             assert at % 16 == r
             where[n].append(len(order) - 1)
             at += len(by_name[n][2])
-    _CACHE["_batch"] = order, where
     return order, where
 
 

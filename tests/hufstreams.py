@@ -21,6 +21,7 @@ import random
 import re
 
 import blockcheck
+import framesuite
 import tabframes
 from tabframes import META, STATUS, Block, RevBits, build, huf_codes, huf_table, lit_header, weights_direct, _lits_covering, _simple_seqs
 
@@ -42,13 +43,7 @@ for _r in (1, 2, 5):
 
 def kernel_constants():
     """the chunking of zg_k_huf, read out of its source"""
-    text = open(_SRC).read()
-    out = {}
-    for k in ("ZG_HP_CB", "ZG_HP_CB_DENSE", "ZG_HP_ROWS", "ZG_HP_WARM"):
-        m = re.search(r"^#define\s+%s\s+(\d+)\b" % k, text, re.M)
-        assert m, k
-        out[k] = int(m.group(1))
-    return out
+    return framesuite.defines(_SRC, ("ZG_HP_CB", "ZG_HP_CB_DENSE", "ZG_HP_ROWS", "ZG_HP_WARM"))
 
 
 def direct_rule():
@@ -477,31 +472,16 @@ FAMILIES = {
     "groups": groups,
 }
 
-_CACHE = {}
 
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    """[(family, name, zst, plaintext or None)]; checks the LIBZSTD_DIFFERS cap once every family is built"""
-    out = [(fam, *f) for fam in FAMILIES for f in family(fam)]
-    names = [n for _, n, _, p in out if p is not None]
-    assert len(set(n for _, n, _, _ in out)) == len(out), "frame names repeat"
+def _check_differs(frames):
+    """the LIBZSTD_DIFFERS cap, once every family is built"""
+    names = [n for _, n, _, p in frames if p is not None]
     assert set(LIBZSTD_DIFFERS) <= set(names), ("LIBZSTD_DIFFERS may hold only frames the oracle accepts", sorted(set(LIBZSTD_DIFFERS) - set(names)))
     assert len(LIBZSTD_DIFFERS) * 10 <= len(names), "LIBZSTD_DIFFERS holds more than a tenth of the valid frames"
-    return out
 
 
-def valid_frames():
-    return [f for f in all_frames() if f[3] is not None]
-
-
-def invalid_frames():
-    return [f for f in all_frames() if f[3] is None]
+_F = framesuite.Families(FAMILIES, _check_differs)
+family, all_frames, valid_frames, invalid_frames = _F.family, _F.all_frames, _F.valid_frames, _F.invalid_frames
 
 
 def coverage(frames):

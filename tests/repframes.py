@@ -15,6 +15,7 @@ import os
 import random
 import re
 
+import framesuite
 import oracle
 import seqframes
 import tabframes
@@ -30,12 +31,9 @@ GOOD = {}          # invalid frames: the plaintext of the blocks in front of the
 def kernel_constants():
     """zg_k_seqpost's threads and sequences per thread, and zg_launch_scan's forms [(largest nblocks or None, T, I)], read out of
     zg_kernels.hip so that a retune moves the frames"""
-    text = open(os.path.join(_CSRC, "zg_kernels.hip")).read()
-    out = {}
-    for k in ("ZG_SP_T", "ZG_SP_S"):
-        m = re.search(r"^#define\s+%s\s+(\d+)\b" % k, text, re.M)
-        assert m, k
-        out[k] = int(m.group(1))
+    src = os.path.join(_CSRC, "zg_kernels.hip")
+    out = framesuite.defines(src, ("ZG_SP_T", "ZG_SP_S"))
+    text = open(src).read()
     body = text[text.index("void zg_launch_scan("):]
     body = body[:body.index("zg_k_scanf")]
     forms = re.findall(r"(?:max_frame_blocks <= (\d+)u\) )?hipLaunchKernelGGL\(\(zg_k_scan<(\d+), (\d+)>\)", body)
@@ -460,28 +458,8 @@ FAMILIES = {
     "invalid": invalid,
 }
 
-_CACHE = {}
-
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    """[(family, name, zst, plaintext or None)]"""
-    out = [(fam, *f) for fam in FAMILIES for f in family(fam)]
-    assert len(set(n for _, n, _, _ in out)) == len(out), "frame names repeat"
-    return out
-
-
-def valid_frames():
-    return [f for f in all_frames() if f[3] is not None]
-
-
-def invalid_frames():
-    return [f for f in all_frames() if f[3] is None]
+_F = framesuite.Families(FAMILIES)
+family, all_frames, valid_frames, invalid_frames = _F.family, _F.all_frames, _F.valid_frames, _F.invalid_frames
 
 
 def big(name):

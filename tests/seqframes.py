@@ -10,6 +10,7 @@ import os
 import random
 import sys
 
+import framesuite
 import oracle
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -286,17 +287,8 @@ FAMILIES = {
     "literal_modes": literal_modes,
 }
 
-_CACHE = {}
-
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    return [(fam, *f) for fam in FAMILIES for f in family(fam)]
+_F = framesuite.Families(FAMILIES)
+family, all_frames, valid_frames = _F.family, _F.all_frames, _F.valid_frames
 
 
 def window_size(z):

@@ -25,6 +25,7 @@ import random
 import re
 
 import blockcheck
+import framesuite
 from tabframes import DEFAULTS, FIELDS, LL_BASE, LL_BITS, MAX_LOG, META, ML_BASE, ML_BITS, STATUS, Block, build, fse_desc, fse_table, nbseq
 
 _SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zstd-rs_amd", "csrc", "zg_kernels.hip")
@@ -43,13 +44,8 @@ LIBZSTD_DIFFERS = {n: BIG_BLOCK for n in ("mrv_w27", "mrv_w25", "burst_low_high_
 
 def kernel_constants():
     """the ring and phase sizes of zg_k_seq, read out of its source"""
-    text = open(_SRC).read()
-    out = {}
-    for k in ("ZG_SEQ_CH", "ZG_SEQ_CMAX", "ZG_SEQ_RING", "ZG_SEQ_G"):
-        m = re.search(r"^#define\s+%s\s+(\d+)\b" % k, text, re.M)
-        assert m, k
-        out[k] = int(m.group(1))
-    m = re.search(r"^#define\s+ZG_SEQ_MARGIN\s+\((\d+) \* ZG_SEQ_CMAX \+ (\d+)\)", text, re.M)
+    out = framesuite.defines(_SRC, ("ZG_SEQ_CH", "ZG_SEQ_CMAX", "ZG_SEQ_RING", "ZG_SEQ_G"))
+    m = re.search(r"^#define\s+ZG_SEQ_MARGIN\s+\((\d+) \* ZG_SEQ_CMAX \+ (\d+)\)", open(_SRC).read(), re.M)
     assert m, "ZG_SEQ_MARGIN has another form"
     out["ZG_SEQ_MARGIN"] = int(m.group(1)) * out["ZG_SEQ_CMAX"] + int(m.group(2))
     assert out["ZG_SEQ_CMAX"] * 8 >= out["ZG_SEQ_CH"] * MAX_SEQ_BITS, "a phase of 89-bit sequences does not fit ZG_SEQ_CMAX"
@@ -546,35 +542,20 @@ FAMILIES = {
 }
 LARGE = ("mrv_w27", "mrv_w25", "ring_hi_offsets", "burst_low_high_low", "burst_high_low_high")     # histories of 16 and 64 MiB
 
-_CACHE = {}
 
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    """[(family, name, zst, plaintext or None)]; checks LIBZSTD_DIFFERS once every family is built"""
-    out = [(fam, *f) for fam in FAMILIES for f in family(fam)]
-    names = [n for _, n, _, p in out if p is not None]
-    assert len(set(n for _, n, _, _ in out)) == len(out), "frame names repeat"
+def _check_differs(frames):
+    """LIBZSTD_DIFFERS, once every family is built"""
+    names = [n for _, n, _, p in frames if p is not None]
     assert set(LIBZSTD_DIFFERS) <= set(names), ("LIBZSTD_DIFFERS may hold only frames the oracle accepts", sorted(set(LIBZSTD_DIFFERS) - set(names)))
     assert len(LIBZSTD_DIFFERS) * 5 <= len(names), "LIBZSTD_DIFFERS holds more than a fifth of the valid frames"
     for n, reason in LIBZSTD_DIFFERS.items():
         assert reason == BIG_BLOCK and max(r["lit_regen"] for r in META[n]["ss"]) > 131072, (n, "on LIBZSTD_DIFFERS for another reason")
     for n in names:
         assert n in LIBZSTD_DIFFERS or all(r["lit_regen"] <= 131072 for r in META[n]["ss"]), n
-    return out
 
 
-def valid_frames():
-    return [f for f in all_frames() if f[3] is not None]
-
-
-def invalid_frames():
-    return [f for f in all_frames() if f[3] is None]
+_F = framesuite.Families(FAMILIES, _check_differs)
+family, all_frames, valid_frames, invalid_frames = _F.family, _F.all_frames, _F.valid_frames, _F.invalid_frames
 
 
 def mix_submit():

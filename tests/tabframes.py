@@ -10,6 +10,7 @@ side knows of a frame (coverage() reads it)."""
 import random
 
 import blockcheck
+import framesuite
 import oracle
 import seqframes
 
@@ -1088,31 +1089,16 @@ FAMILIES = {
     "invalid_tables": invalid_tables,
 }
 
-_CACHE = {}
 
-
-def family(name):
-    if name not in _CACHE:
-        _CACHE[name] = FAMILIES[name]()
-    return _CACHE[name]
-
-
-def all_frames():
-    """[(family, name, zst, plaintext or None)]; checks the LIBZSTD_DIFFERS cap once every family is built"""
-    out = [(fam, *f) for fam in FAMILIES for f in family(fam)]
-    names = [n for _, n, _, p in out if p is not None]
-    assert len(set(n for _, n, _, _ in out)) == len(out), "frame names repeat"
+def _check_differs(frames):
+    """the LIBZSTD_DIFFERS cap, once every family is built"""
+    names = [n for _, n, _, p in frames if p is not None]
     assert set(LIBZSTD_DIFFERS) <= set(names), "LIBZSTD_DIFFERS may hold only frames the oracle accepts"
     assert len(LIBZSTD_DIFFERS) * 10 <= len(names), "LIBZSTD_DIFFERS holds more than a tenth of the valid frames"
-    return out
 
 
-def valid_frames():
-    return [f for f in all_frames() if f[3] is not None]
-
-
-def invalid_frames():
-    return [f for f in all_frames() if f[3] is None]
+_F = framesuite.Families(FAMILIES, _check_differs)
+family, all_frames, valid_frames, invalid_frames = _F.family, _F.all_frames, _F.valid_frames, _F.invalid_frames
 
 
 def coverage(frames):

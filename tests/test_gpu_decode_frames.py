@@ -8,6 +8,7 @@ import sys
 import pytest
 
 from devmem import MAGIC, oracle_alone, xxh64
+from framesuite import check_entries
 from golden_io import read_manifest, read_pack
 
 pytestmark = pytest.mark.gpu
@@ -24,38 +25,6 @@ def ctx():
     c.close()
 
 
-def _oracle_first_frame(z, dict_raw=None):
-    """(checksum_from_data or 0, calculated_checksum) of the entry's first frame, as the reference's FrameDecoder reports them"""
-    import oracle
-    _, d = oracle.decode_frame_all(z, dict_raw=dict_raw)
-    v = d.checksum_from_data()
-    return (v or 0), d.calculated_checksum()
-
-
-def _zgpu_alone(ctx, z, cap):
-    import zgpu
-    try:
-        return 0, ctx.decode_all(z, cap)
-    except zgpu.ZgpuError as e:
-        return e.status, None
-
-
-def _check(ctx, entries, caps, res, dict_raw=None, first_frame=True):
-    assert len(res) == len(entries)
-    for i, (z, cap, r) in enumerate(zip(entries, caps, res)):
-        st, out = oracle_alone(z, cap, dict_raw)
-        assert r.status == st, (i, r, st)
-        zs, zout = _zgpu_alone(ctx, z, cap)
-        assert r.status == zs, (i, r, zs)
-        if st:
-            assert r.written == 0 and r.data is None, i
-            continue
-        assert r.data == out == zout, i
-        assert r.written == len(out)
-        if first_frame and r.nframes and z[:4] == MAGIC:
-            assert (r.checksum_from_data, r.calculated_checksum) == _oracle_first_frame(z, dict_raw), i
-
-
 def _key(r):
     return (r.status, r.data, r.nframes, r.checksums, r.checksum_mismatches, r.checksum_from_data, r.calculated_checksum)
 
@@ -67,7 +36,7 @@ def test_corpus_in_one_call(ctx):
     entries = [pack[n] for n in names]
     caps = [man[n]["size"] for n in names]
     res = ctx.decode_frames(entries, caps)
-    _check(ctx, entries, caps, res)
+    check_entries(ctx, entries, caps, res)
     for n, r in zip(names, res):
         assert r.status == 0 and r.nframes >= 1, n
         assert r.checksum_mismatches == 0, n
@@ -90,7 +59,7 @@ def test_dict_corpus_in_one_call():
         assert all(r.status == zgpu.E_DICT_NOT_PROVIDED for r in before)   # (no dictionary registered: decode_all's answer)
         c.add_dict(raw)
         res = c.decode_frames(entries, caps)
-        _check(c, entries, caps, res, dict_raw=raw)
+        check_entries(c, entries, caps, res, dict_raw=raw)
         assert all(r.status == 0 for r in res)
     finally:
         c.close()
@@ -130,7 +99,7 @@ def test_isolation_and_order(ctx):
     import zgpu
     entries, caps = _isolation_entries()
     res = ctx.decode_frames(entries, caps)
-    _check(ctx, entries, caps, res)
+    check_entries(ctx, entries, caps, res)
     assert res[-1].status == zgpu.E_TARGET_TOO_SMALL
     assert any(r.status not in (0, zgpu.E_TARGET_TOO_SMALL) for r in res)
     for seed in (1, 2):
@@ -167,7 +136,7 @@ def test_checksums_reported_not_enforced(ctx):
     entries = [z, bytes(zc), zr, bytes(zr_bad), zn, z + zr]
     caps = [len(text), len(text), len(payload), len(payload), len(text), len(text) + len(payload)]
     res = ctx.decode_frames(entries, caps)
-    _check(ctx, entries, caps, res)
+    check_entries(ctx, entries, caps, res)
     r = res[0]
     assert (r.status, r.nframes, r.checksums, r.checksum_mismatches) == (0, 1, 1, 0)
     assert r.calculated_checksum == r.checksum_from_data == xxh64(text) & 0xFFFFFFFF
@@ -206,7 +175,7 @@ def _check_small(ctx, entries, plains):
         assert r.calculated_checksum == r.checksum_from_data == xxh64(p) & 0xFFFFFFFF, i
     caps = [len(p) for p in plains]
     for i in list(range(0, 4096, 509)) + list(range(4096, len(entries))):
-        _check(ctx, [entries[i]], [caps[i]], [res[i]])
+        check_entries(ctx, [entries[i]], [caps[i]], [res[i]])
 
 
 def test_many_small_frames(ctx, monkeypatch):
@@ -243,7 +212,7 @@ def test_input_bytes_bound_the_submits(monkeypatch):
     try:
         res = c.decode_frames(entries, [0] * len(entries))
         assert c.frames_submits() >= 4
-        _check(c, entries, [0] * len(entries), res)
+        check_entries(c, entries, [0] * len(entries), res)
     finally:
         c.close()
 

@@ -9,35 +9,13 @@ on the CPU side, once per module (about 20 s, most of it the five frames of 8191
 asserts what they reach."""
 import pytest
 
-import blockcheck
+import framesuite
 import oracle
 import repframes
+from framesuite import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import zgpu
-    c = zgpu.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def valid():
-    return repframes.valid_frames()        # [(family, name, zst, plaintext)]
-
-
-@pytest.fixture(scope="module")
-def invalid():
-    return repframes.invalid_frames()      # [(family, name, zst, None)]
-
-
-@pytest.fixture(scope="module")
-def oblocks(valid):
-    """the oracle's per-block records of every valid frame, once"""
-    return {name: blockcheck.oracle_blocks(z) for _, name, z, _ in valid}
+valid, invalid, oblocks = framesuite.frame_fixtures(repframes)
 
 
 def test_decode_all_each_frame(ctx, valid):
@@ -45,30 +23,10 @@ def test_decode_all_each_frame(ctx, valid):
     assert not bad, bad
 
 
-def _submit(c, frames, oblocks=None):
-    b = c.prepare(b"".join(z for _, _, z, _ in frames))
-    try:
-        assert b.parse_status == 0 and b.nframes == len(frames)
-        b.run()
-        b.sync()
-        assert b.bad_status == 0, (b.bad_frame, b.bad_status)
-        assert b.total_out == sum(len(p) for _, _, _, p in frames)
-        bad = [name for f, (_, name, _, plain) in enumerate(frames) if b.frame_bytes(f) != plain]
-        assert not bad, bad
-        if oblocks is not None:
-            first = 0
-            for f, (_, name, _, _) in enumerate(frames):
-                assert b.frame_info(f).nblocks == len(oblocks[name]), name
-                first += blockcheck.check_frame(b, first, oblocks[name], name)
-            assert first == b.nblocks
-    finally:
-        b.close()
-
-
 def test_one_batch_with_intermediates(ctx, valid, oblocks):
     """all valid frames in one submit: every frame's bytes, the history at every block start (zg_k_scan<1024, 8>: the largest frame
     picks the form for all) and every sequence (zg_k_seqpost) against the oracle's"""
-    _submit(ctx, valid, oblocks)
+    framesuite.submit(ctx, valid, oblocks)
 
 
 def test_small_frames_in_the_one_wave_scan(ctx, valid, oblocks):
@@ -77,8 +35,8 @@ def test_small_frames_in_the_one_wave_scan(ctx, valid, oblocks):
     small = [f for f in valid if repframes.META[f[1]]["nblocks"] <= lo]
     medium = [f for f in valid if repframes.META[f[1]]["nblocks"] <= mid]
     assert len(small) >= 100 and len(medium) >= len(small) + 3
-    _submit(ctx, small, oblocks)
-    _submit(ctx, medium, oblocks)
+    framesuite.submit(ctx, small, oblocks)
+    framesuite.submit(ctx, medium, oblocks)
 
 
 def test_scan_frames_alone(ctx, valid, oblocks):
@@ -87,94 +45,34 @@ def test_scan_frames_alone(ctx, valid, oblocks):
     seen = set()
     for fr in valid:
         if fr[0] == "scan_edges":
-            _submit(ctx, [fr], oblocks)
+            framesuite.submit(ctx, [fr], oblocks)
             seen.add(repframes.META[fr[1]]["nblocks"])
     assert seen == set(repframes.NBLOCKS)
 
 
-DEV_PATHS = [
-    {"ZGPU_UNIT_BLOCKS": "1"},
-    {"ZGPU_UNIT_BLOCKS": "3", "ZGPU_FLAT_T": "512"},
-    {"ZGPU_DIRECT": "0"},
-    {"ZGPU_FORCE_INORDER": "1"},
-    {"ZGPU_SPARSE_MAX": "0"},
-    {"ZGPU_SPARSE_MAX": "100000000"},
-    {"ZGPU_SEQ_PACKED": "1"},
-    {"ZGPU_SWEEP_SPLIT": "0"},
-]
-
-
-@pytest.mark.parametrize("env", DEV_PATHS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
+@pytest.mark.parametrize("env", framesuite.DEV_PATHS, ids=framesuite.env_id)
 def test_development_paths(valid, env, monkeypatch):
     """the valid frames in one submit of the development build under each switch, so that every consumer of a symbolic offset
     resolves them: zg_flat1.h and zg_flat4.h in other unit and tile shapes, zg_k_lz in order, zg_k_sparse for every frame and for
     none, zg_k_seq's packed tables in front of the post-pass, the plain sweep chain"""
-    import zgpu
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = zgpu.Context(0, dev=True)
-    try:
-        _submit(c, valid)
-    finally:
-        c.close()
+    with framesuite.dev_context(monkeypatch, env) as c:
+        framesuite.submit(c, valid)
 
 
 def _mixed(valid, invalid):
     """the invalid frames among the valid ones of fewer than 1000 blocks, one after every third"""
     small = [f for f in valid if repframes.META[f[1]]["nblocks"] < 1000]
     assert len(small) >= 3 * len(invalid)
-    frames = []
-    for i, f in enumerate(small):
-        frames.append(f)
-        if i % 3 == 2 and i // 3 < len(invalid):
-            frames.append(invalid[i // 3])
-    assert len(frames) == len(small) + len(invalid)
-    return frames
+    return framesuite.interleave(small, invalid, 3)
 
 
 def test_decode_frames(ctx, valid, invalid):
     """every frame an entry of one decode_frames call, the invalid ones among the valid: each gets what decode_all of it alone gives
     and the oracle's verdict and bytes; a valid entry's content checksum matches"""
-    from test_gpu_decode_frames import _check
     big = [f for f in valid if repframes.META[f[1]]["nblocks"] >= 1000]
     frames = _mixed(valid, invalid) + big
     assert len(frames) == len(valid) + len(invalid)
-    entries = [z for _, _, z, _ in frames]
-    caps = [len(p) if p is not None else 1 << 20 for _, _, _, p in frames]
-    res = ctx.decode_frames(entries, caps)
-    _check(ctx, entries, caps, res)
-    for (_, name, _, plain), r in zip(frames, res):
-        if plain is None:
-            assert r.status == repframes.STATUS[name] and r.data is None, (name, r.status)
-        else:
-            assert r.status == 0 and r.data == plain, name
-            assert r.nframes == 1 and r.checksums == 1 and r.checksum_mismatches == 0, (name, r)
-
-
-def _stepwise(ctx, name, z, plain, k):
-    import zgpu
-    d, o = zgpu.FrameDecoder(ctx), oracle.FrameDecoder()
-    try:
-        st, c, _, _ = d.init(z)
-        ost, oc, _, _ = o.init(z)
-        assert (st, c) == (ost, oc) and st == 0, name
-        pos, out = c, bytearray()
-        for _ in range(repframes.META[name]["nblocks"] // k + 2):
-            st, used, fin = d.decode_blocks(z[pos:], zgpu.STRAT_UPTO_BLOCKS, k)
-            ost, oused, ofin = o.decode_blocks(z[pos:], oracle.STRAT_UPTO_BLOCKS, k)
-            assert (st, used, fin) == (ost, oused, ofin) and st == 0, (name, k, st, ost)
-            pos += used
-            assert d.blocks_decoded() == o.blocks_decoded() and d.bytes_read_from_source() == o.bytes_read_from_source(), name
-            assert d.can_collect() == o.can_collect(), name
-            got = d.collect()
-            assert got == o.collect(), (name, k, d.blocks_decoded())
-            out += got
-            if fin:
-                break
-        assert bytes(out) == plain and d.is_finished(), name
-        assert d.get_calculated_checksum() == o.calculated_checksum(), name
-    finally:
-        d.close()
+    framesuite.check_decode_frames(ctx, frames, repframes.STATUS)
 
 
 STEP_FRAMES = ["scan_%d" % (repframes.SCAN_LIMITS[1] + 1), "scan_%d" % (repframes.CHUNK + 8), "dec_n%d_slot1" % (repframes.WAVE + 1),
@@ -189,18 +87,17 @@ def test_decode_blocks_upto(ctx, valid, name, k):
     checksum, equal the oracle's"""
     fr = [f for f in valid if f[1] == name]
     assert len(fr) == 1, name
-    _stepwise(ctx, name, fr[0][2], fr[0][3], k)
+    st, out, _ = framesuite.lockstep(ctx, name, fr[0][2], k)
+    assert st == 0 and out == fr[0][3], (name, k, st)
 
 
 def test_invalid_frames_alone(ctx, invalid):
     """each invalid frame alone: decode_all's status; a one-frame submit's status, failing block and the good blocks' bytes;
     FrameDecoder.decode_blocks(All): the status, the counters and the bytes held after the Err (zg_k_partial) against the oracle's"""
     import zgpu
+    framesuite.invalid_alone(ctx, invalid, repframes.STATUS)
     for _, name, z, _ in invalid:
         want, good, at = repframes.STATUS[name], repframes.GOOD[name], repframes.META[name]["bad_block"]
-        with pytest.raises(zgpu.ZgpuError) as e:
-            ctx.decode_all(z, 1 << 20)
-        assert e.value.status == want, (name, e.value.status, want)
         b = ctx.prepare(z)
         try:
             b.run()

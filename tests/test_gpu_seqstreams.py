@@ -11,28 +11,12 @@ once; tests/test_seqstreams_cpu.py asserts what they reach."""
 import pytest
 
 import blockcheck
-import oracle
+import framesuite
 import seqstreams
+from framesuite import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import zgpu
-    c = zgpu.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def valid():
-    return seqstreams.valid_frames()        # [(family, name, zst, plaintext)]
-
-
-@pytest.fixture(scope="module")
-def invalid():
-    return seqstreams.invalid_frames()      # [(family, name, zst, None)]
+valid, invalid, _ = framesuite.frame_fixtures(seqstreams)
 
 
 def _split(valid):
@@ -46,25 +30,6 @@ def test_decode_all_each_frame(ctx, valid):
     """each frame alone: its stream lies at the front of the source buffer (the floorA clamp of the ring's fill)"""
     bad = [name for _, name, z, plain in valid if ctx.decode_all(z, len(plain)) != plain]
     assert not bad, bad
-
-
-def _one_submit(c, frames):
-    b = c.prepare(b"".join(z for _, _, z, _ in frames))
-    try:
-        assert b.parse_status == 0 and b.nframes == len(frames)
-        b.run()
-        b.sync()
-        assert b.bad_status == 0, (b.bad_frame, b.bad_status)
-        assert b.total_out == sum(len(p) for _, _, _, p in frames)
-        first = 0
-        for f, (_, name, z, plain) in enumerate(frames):
-            assert b.frame_bytes(f) == plain, name
-            ob = seqstreams.oracle_blocks(name, z)
-            assert b.frame_info(f).nblocks == len(ob), name
-            first += blockcheck.check_frame(b, first, ob, name)
-        assert first == b.nblocks
-    finally:
-        b.close()
 
 
 def _ring_submit(c):
@@ -92,13 +57,13 @@ def test_one_batch_with_intermediates(ctx, valid):
     """all valid frames but the large-history ones in one submit (the streams start wherever the frames in front leave them): every
     frame's bytes, and block by block the sequences (zg_k_seq's states through zg_k_seqpost), the FSE tables and the offset history
     against the oracle's, entry for entry"""
-    _one_submit(ctx, _split(valid)[1])
+    framesuite.submit(ctx, _split(valid)[1], seqstreams.oracle_blocks)
 
 
 def test_large_history_batch_with_intermediates(ctx, valid):
     """the frames over 16 and 64 MiB of RLE blocks in a submit of their own: offset codes 24 and 26, blocks that regenerate up to
     10 MB (their ZgSeq positions are compared mod 2^17, blockcheck.check_frame), so == 31 and 32"""
-    _one_submit(ctx, _split(valid)[0])
+    framesuite.submit(ctx, _split(valid)[0], seqstreams.oracle_blocks)
 
 
 def test_ring_submit(ctx):
@@ -107,20 +72,14 @@ def test_ring_submit(ctx):
     _ring_submit(ctx)
 
 
-@pytest.mark.parametrize("env", [{"ZGPU_SEQ_PACKED": "1"}, {"ZGPU_FORCE_INORDER": "1"}], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
+@pytest.mark.parametrize("env", [{"ZGPU_SEQ_PACKED": "1"}, {"ZGPU_FORCE_INORDER": "1"}], ids=framesuite.env_id)
 def test_development_paths(valid, env, monkeypatch):
     """the same three submits in the development build with zg_k_seq's packed tables and with zg_k_lz in order"""
-    import zgpu
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    c = zgpu.Context(0, dev=True)
-    try:
+    with framesuite.dev_context(monkeypatch, env) as c:
         large, small = _split(valid)
-        _one_submit(c, small)
-        _one_submit(c, large)
+        framesuite.submit(c, small, seqstreams.oracle_blocks)
+        framesuite.submit(c, large, seqstreams.oracle_blocks)
         _ring_submit(c)
-    finally:
-        c.close()
 
 
 def test_decode_frames(ctx, valid, invalid):
@@ -129,71 +88,27 @@ def test_decode_frames(ctx, valid, invalid):
     in the CAREFUL one, with bits left over, in the execution) while their wave neighbours run on. Behind them every other frame
     but the large-history ones, an invalid one after every second valid one. Every entry gets what decode_all of it alone gives
     and the oracle's verdict and bytes; every invalid entry carries the oracle's status and every valid neighbour is untouched"""
-    from test_gpu_decode_frames import _check
     mix = [("workgroup_mixes", *f) for f in seqstreams.mix_submit()]
     assert len(mix) == seqstreams.G and sum(f[3] is None for f in mix) == 4
     names = {f[1] for f in mix}
     v = [f for f in _split(valid)[1] if f[1] not in names]
     inv = [f for f in invalid if f[1] not in names]
-    frames = list(mix)
-    for i, f in enumerate(v):
-        frames.append(f)
-        if i % 2 == 1 and i // 2 < len(inv):
-            frames.append(inv[i // 2])
-    frames += inv[len(v) // 2:]
+    frames = mix + framesuite.interleave(v, inv, 2)
     assert len(frames) == len(valid) - len(seqstreams.LARGE) + len(invalid)
-    entries = [z for _, _, z, _ in frames]
-    caps = [len(p) if p is not None else 1 << 20 for _, _, _, p in frames]
-    res = ctx.decode_frames(entries, caps)
-    _check(ctx, entries, caps, res)
-    for (_, name, _, plain), r in zip(frames, res):
-        if plain is None:
-            assert r.status == seqstreams.STATUS[name] and r.data is None, (name, r.status)
-        else:
-            assert r.status == 0 and r.data == plain, name
-            assert r.nframes == 1 and r.checksums == 1 and r.checksum_mismatches == 0, (name, r)
+    framesuite.check_decode_frames(ctx, frames, seqstreams.STATUS)
 
 
 def test_invalid_frames_alone(ctx, invalid):
-    import zgpu
-    got = []
-    for _, name, z, _ in invalid:
-        try:
-            ctx.decode_all(z, 1 << 20)
-            got.append((name, 0, seqstreams.STATUS[name]))
-        except zgpu.ZgpuError as e:
-            got.append((name, e.status, seqstreams.STATUS[name]))
-    assert [g for g in got if g[1] != g[2]] == []
+    framesuite.invalid_alone(ctx, invalid, seqstreams.STATUS)
 
 
 def test_rejected_frames_call_by_call(ctx):
     """the max_rate_rejected frames as they are (a raw block or RLE blocks in front of the failing one): FrameDecoder.decode_blocks(
     UptoBlocks, 1) agrees with the oracle call by call (status, the bytes used by a call that succeeds, the counters and what may be
     collected after every call, the failing one included: the bytes the reference keeps in front of the failure)"""
-    import zgpu
     frames = seqstreams.family("max_rate_rejected")
     assert len(frames) == 4
     for name, z, plain in frames:
         assert plain is None
-        d, o = zgpu.FrameDecoder(ctx), oracle.FrameDecoder()
-        try:
-            st, c, _, _ = d.reset(z)
-            ost, oc, _, _ = o.init(z)
-            assert (st, c) == (ost, oc) == (0, 6), name
-            pos, calls = c, 0
-            for _ in range(16):
-                st, used, fin = d.decode_blocks(z[pos:], zgpu.STRAT_UPTO_BLOCKS, 1)
-                ost, oused, ofin = o.decode_blocks(z[pos:], oracle.STRAT_UPTO_BLOCKS, 1)
-                calls += 1
-                assert st == ost, (name, st, ost)
-                if not st:                                   # (an error carries neither a count nor "finished": include/zgpu.h)
-                    assert (used, fin) == (oused, ofin), name
-                pos += used
-                assert d.blocks_decoded() == o.blocks_decoded() and d.bytes_read_from_source() == o.bytes_read_from_source(), name
-                assert d.can_collect() == o.can_collect(), name
-                assert d.collect() == o.collect(), name
-                if st or fin:
-                    break
-            assert st == seqstreams.STATUS[name] and calls >= 2, (name, st, calls)
-        finally:
-            d.close()
+        st, _, calls = framesuite.lockstep(ctx, name, z, header=(0, 6))
+        assert st == seqstreams.STATUS[name] and calls >= 2, (name, st, calls)

@@ -6,8 +6,7 @@ blocks without sequences, straight in the output. The coverage test asserts that
 build of the same source is checked on the same frames by tests/test_gpu_hufstreams.py."""
 import pytest
 
-import blockcheck
-import emu
+import framesuite
 import hufstreams
 from hufstreams import META, STATUS
 from test_huf_cpu import _lib, check_against_model, run_huf
@@ -20,18 +19,7 @@ def test_family_matches_plaintext_and_oracle(fam):
     """frame bytes == plaintext; per-block literals, sequences, offset history and Huffman tables == the oracle's; an invalid
     frame gets the oracle's status"""
     for name, z, plain in hufstreams.family(fam):
-        if plain is None:
-            assert emu.decode_all_verdict(z) == STATUS[name], name
-            continue
-        e = emu.EmuBatch(z, max_window=1 << 31)
-        assert e.parse_status == 0 and e.nframes == 1, name
-        out, st = e.frame_bytes(0)
-        assert st == 0 and out == plain, name
-        ob = blockcheck.oracle_blocks(z)
-        assert e.nblocks == len(ob), name
-        blockcheck.check_frame(e, 0, ob, name)
-        ex = e.exact(drain_rule=1)
-        assert ex[0][0] == 0, (name, ex)
+        framesuite.check_on_harness(name, z, plain, STATUS)
 
 
 def _kernel_source(name, z, plain, direct):

@@ -14,6 +14,7 @@ import pytest
 
 import blockcheck
 import emu
+import framesuite
 import repframes
 from repframes import META, STATUS
 
@@ -29,7 +30,7 @@ def test_family_matches_plaintext_and_oracle(fam):
     for name, z, plain in repframes.family(fam):
         m = META[name]
         if plain is None:
-            assert emu.decode_all_verdict(z) == STATUS[name], name
+            framesuite.check_on_harness(name, z, None, STATUS)
             e = emu.EmuBatch(z, max_window=1 << 31)
             out, st = e.frame_bytes(0)
             assert st and e.frame(0)[3] == m["bad_block"], (name, st, e.frame(0))      # (the verdict is zg_exact.h's, above: the harness's serial executor only stops there)

@@ -6,6 +6,7 @@ import pytest
 
 import blockcheck
 import emu
+import framesuite
 import seqframes
 import test_flat1_cpu
 import test_flat4_cpu
@@ -16,15 +17,7 @@ def test_family_matches_plaintext_and_oracle(fam):
     """frame bytes == plaintext; per-block literals, sequences, offset history, Huffman and FSE tables == the oracle's;
     zg_k_exact's source (drain rule 1) accepts"""
     for name, z, plain in seqframes.family(fam):
-        e = emu.EmuBatch(z, max_window=1 << 31)
-        assert e.parse_status == 0 and e.nframes == 1, name
-        out, st = e.frame_bytes(0)
-        assert st == 0 and out == plain, name
-        ob = blockcheck.oracle_blocks(z)
-        assert e.nblocks == len(ob), name
-        blockcheck.check_frame(e, 0, ob, name)
-        ex = e.exact(drain_rule=1)
-        assert ex[0][0] == 0, (name, ex)
+        framesuite.check_on_harness(name, z, plain, None)
 
 
 def test_single_block_frames_hold_their_sequences():

@@ -9,8 +9,8 @@ The frames are built once per module: 3.7 s here for all six families (94 frames
 64 MiB of RLE blocks are 210 MB), measured alone on an idle machine."""
 import pytest
 
-import blockcheck
 import emu
+import framesuite
 import seqstreams
 from seqstreams import CH, META, RING, STATUS
 
@@ -22,18 +22,7 @@ def test_family_matches_plaintext_and_oracle(fam):
     """frame bytes == plaintext; per-block literals, sequences, offset history and FSE tables == the oracle's; an invalid frame gets
     the oracle's status. The harness takes blocks that regenerate more than 128 KiB and the 64 MiB histories as they are"""
     for name, z, plain in seqstreams.family(fam):
-        if plain is None:
-            assert emu.decode_all_verdict(z) == STATUS[name], name
-            continue
-        e = emu.EmuBatch(z, max_window=1 << 31)
-        assert e.parse_status == 0 and e.nframes == 1, name
-        out, st = e.frame_bytes(0)
-        assert st == 0 and out == plain, name
-        ob = seqstreams.oracle_blocks(name, z)
-        assert e.nblocks == len(ob), name
-        blockcheck.check_frame(e, 0, ob, name)
-        ex = e.exact(drain_rule=1)
-        assert ex[0][0] == 0, (name, ex)
+        framesuite.check_on_harness(name, z, plain, STATUS, lambda z: seqstreams.oracle_blocks(name, z))
 
 
 def test_ring_submit_in_the_harness():

@@ -5,8 +5,8 @@ that the families really reach what they aim at. The harness builds its tables w
 builders of zg_k_tables and zg_k_ftab are proven by tests/test_gpu_tabframes.py on the same frames."""
 import pytest
 
-import blockcheck
 import emu
+import framesuite
 import tabframes
 
 VALID = [f for f in sorted(tabframes.FAMILIES) if f != "invalid_tables"]
@@ -17,15 +17,7 @@ def test_family_matches_plaintext_and_oracle(fam):
     """frame bytes == plaintext; per-block literals, sequences, offset history, Huffman and FSE tables == the oracle's;
     zg_k_exact's source (drain rule 1) accepts"""
     for name, z, plain in tabframes.family(fam):
-        e = emu.EmuBatch(z, max_window=1 << 31)
-        assert e.parse_status == 0 and e.nframes == 1, name
-        out, st = e.frame_bytes(0)
-        assert st == 0 and out == plain, name
-        ob = blockcheck.oracle_blocks(z)
-        assert e.nblocks == len(ob), name
-        blockcheck.check_frame(e, 0, ob, name)
-        ex = e.exact(drain_rule=1)
-        assert ex[0][0] == 0, (name, ex)
+        framesuite.check_on_harness(name, z, plain, tabframes.STATUS)
 
 
 def test_invalid_frames_get_the_oracles_status():
