@@ -74,6 +74,10 @@ enum zgpu_status {
   /* No counterpart in the reference, which knows no seekable format. Only an entry of zgpu_frames_seek_table_device /
    * zgpu_decode_ranges_seek_table_device_src gets it: the entry does not end in a usable seek table; zgpu_seek.why (ZGPU_SEEKTAB_*) says why. */
   ZGPU_E_SEEK_TABLE = 72,
+  /* No counterpart in the reference (libzstd's seekable reader has it: its corruption_detected on a frame checksum). Only an entry of
+   * zgpu_decode_ranges_seek_table_device_src called with ZGPU_DEVICE_VERIFY_SEEK_TABLE gets it: the entry decoded, and its seek table does not
+   * vouch for the bytes — a frame's XXH64 differs from the table's Checksum, a decoded frame matches no table row, or the table has no checksums. */
+  ZGPU_E_SEEK_CHECKSUM_MISMATCH = 73,
   /* Input the reference tolerates but this engine rejects. No conforming encoder produces any of it:
    *  - offsets >= 2^30 (offset codes 30, 31) while >= 1 GiB of the frame is held undrained (FrameDecoder::decode_blocks(All) on a
    *    frame beyond 1 GiB that nobody reads from): ZGPU_E_UNSUPPORTED. With less than 1 GiB held — always the case in decode_all
@@ -171,7 +175,8 @@ uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
  *  - Entries the one-submit path does not serve — dictionary frames while dictionaries are registered, Unsupported / Internal verdicts — are
  *    decoded again alone, as by zgpu_decode_frames, into a host buffer and then copied to the destination with one H2D (rare; correct first).
  *  - Checksums: the bytes never reach the host, so frames are hashed on the device only (zg_k_xxh64, one lane per frame, ~226 MB/s per lane;
- *    zg_k_xxh64q, four lanes per frame, is built and tested but not yet the library's choice for any launch: LABNOTES.md "xxh64q").
+ *    zg_k_xxh64q, four lanes per frame and ~1.1 - 1.4 GB/s per frame, is the choice of the calls that carry ZGPU_DEVICE_VERIFY_SEEK_TABLE only:
+ *    LABNOTES.md "xxh64q").
  *    r.checksums counts the frames that carry a Content_Checksum, r.checksum_mismatches only those among the HASHED frames; the rest are
  *    counted in checksums_unverified. By default nothing fails on a mismatch, as in the reference, and the scatter runs beside the hash: a
  *    corrupted frame's bytes are in the destination when the caller reads the counter. (Entries decoded alone are hashed on the host,
@@ -191,11 +196,13 @@ uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
  *    Bit 1 together with bit 0 is a contradiction: the call returns ZGPU_E_BAD_ARG and launches nothing. */
 #define ZGPU_DEVICE_NO_HASH 1u
 #define ZGPU_DEVICE_VERIFY 2u
+#define ZGPU_DEVICE_VERIFY_SEEK_TABLE 4u   /* zgpu_decode_ranges_seek_table_device_src only (see there); ZGPU_E_BAD_ARG on every other call */
 typedef struct {
   uint64_t hash_max_bytes;   /* frames whose plaintext is at most this long are hashed on the device; longer ones are not hashed.
                                 0: default 4 MiB — except under ZGPU_DEVICE_VERIFY, where 0 means no limit for frames that carry a checksum */
   uint32_t flags;            /* bit 0 (ZGPU_DEVICE_NO_HASH): hash no frame at all; bit 1 (ZGPU_DEVICE_VERIFY): a checksum mismatch fails the
-                                entry with ZGPU_E_CHECKSUM_MISMATCH and nothing of it is written */
+                                entry with ZGPU_E_CHECKSUM_MISMATCH and nothing of it is written; bit 2 (ZGPU_DEVICE_VERIFY_SEEK_TABLE): the seek table's
+                                checksums are enforced (zgpu_decode_ranges_seek_table_device_src only), hash_max_bytes == 0 means no limit */
   uint32_t pad;
 } zgpu_device_opts;
 typedef struct {
@@ -392,7 +399,9 @@ int zgpu_decode_ranges_device_src(zgpu_ctx*, const void* const* device_srcs, con
  * the seek (64 * n), [3] input bytes that crossed to the host (entries decoded alone only), [4] frames skipped, [5] frames decoded, [6] plaintext
  * bytes decoded, [7] bytes written to destinations ([3], [5] - [7]: 0 after zgpu_frames_seek_device). [5] and [6] are work done, not bytes
  * delivered: an entry that decoded and then failed a later check (size, TARGET_TOO_SMALL, checksum) is counted, and every entry is counted
- * once, in its submit or alone. Returns how many were written. */
+ * once, in its submit or alone. ZGPU_DEVICE_VERIFY_SEEK_TABLE: [8] checksum-compare launches (zg_k_seeksums, one per submit that holds
+ * such entries), [9] their kernel microseconds (HIP events), [10] bytes they brought back (32 per entry), [11] frames compared, [12] entries
+ * failed by the flag. A caller that asks for 8 gets what it always got. Returns how many were written. */
 int zgpu_debug_ranges_stats(const zgpu_ctx*, uint64_t* out, int n);
 
 /* ---- byte ranges through the seek table of zstd's seekable format ------------------------------------------------------------------------------
@@ -429,8 +438,28 @@ int zgpu_debug_ranges_stats(const zgpu_ctx*, uint64_t* out, int n);
  *  - A false table is a status, never a fault: compressed sizes that put src_lo inside a frame give what zgpu_decode_all reports for those
  *    bytes, and every access stays inside the entry. Frames in front of the range are not decoded, so a false size in their table entries
  *    shifts the coordinates silently.
- *  - Out of scope: the table's own Checksum fields are not read or verified (ZGPU_DEVICE_VERIFY acts on frames that carry a Content_Checksum,
- *    as in the other calls).
+ *  - The table's own Checksum fields — the low 32 bits of XXH64 (seed 0) of each frame's plaintext, the only integrity information of files
+ *    whose frames carry no Content_Checksum — are enforced by ZGPU_DEVICE_VERIFY_SEEK_TABLE (flags bit 2; without it they are not read, and
+ *    ZGPU_DEVICE_VERIFY acts on frames that carry a Content_Checksum, as in the other calls). The comparison runs on the device (zg_k_seeksums,
+ *    one wave per entry, one launch per submit behind the hash kernel; 32 bytes per entry come back, no byte of the table). The rule, one
+ *    definition (zg_seeksums.h). For an entry whose selection is table rows [first, first + taken), with R_k = C_k - C_first:
+ *      - a decoded zstd frame COINCIDES with row k if it begins at selection offset R_k and is c_k bytes long;
+ *      - a frame that coincides with a row and was hashed is COMPARED: the low 32 bits of its digest against the row's Checksum;
+ *      - rows that no decoded zstd frame coincides with are not looked at: skippable frames entered with size 0, and rows outside the
+ *        selection. A false checksum in a skipped frame's row is not seen, exactly as a false size there shifts the coordinates silently;
+ *      - the entry fails with ZGPU_E_SEEK_CHECKSUM_MISMATCH if any compared frame differs, if any decoded zstd frame coincides with no row
+ *        (nothing vouches for such a frame), or if the table carries no checksums (Checksum_Flag clear);
+ *      - an entry of which no zstd frame is decoded (a range of length 0, nothing taken, skippable frames only) is not looked at at all.
+ *    Every decoded zstd frame of such an entry is hashed, with or without a Content_Checksum: hash_max_bytes == 0 means NO limit under this
+ *    flag; a nonzero value still bounds what is hashed, and longer frames pass uncompared, as under ZGPU_DEVICE_VERIFY. The verdict ranks
+ *    last: behind decode and walk errors, ZGPU_E_CONTENT_SIZE_MISMATCH, ZGPU_E_TARGET_TOO_SMALL and ZGPU_E_CHECKSUM_MISMATCH. A failed entry
+ *    has written = nframes = 0 and NO byte of its destination is written (the verdict comes before the scatter list is built); r.checksums is
+ *    the frames compared, r.checksum_mismatches those that differ, checksums_unverified the decoded frames not compared (no coinciding row,
+ *    not hashed, or no checksums in the table), every other field 0; results[i].seek stays the selection's record. Other entries are
+ *    unaffected, in any order and with zgpu_set_frames_shared_dicts on or off: entries decoded alone get the same verdict on the host, from
+ *    the footer and rows [first, first + taken) (counted in the input bytes that crossed to the host), before their one H2D. A table that
+ *    changed between the seek and the compare fails the CALL with ZGPU_E_INTERNAL. The flag may be combined with ZGPU_DEVICE_VERIFY; with
+ *    ZGPU_DEVICE_NO_HASH, or on any other call that takes zgpu_device_opts, the call returns ZGPU_E_BAD_ARG and launches nothing.
  *  - Everything else carries over from zgpu_decode_ranges_device_src: isolation and order independence, no byte of a failed entry and no byte at
  *    or behind dst + written is written, the pointer checks before any launch, streams synchronised on return, and the same diagnostics
  *    (zgpu_debug_ranges_stats, zgpu_debug_frames_submits, _device_stats, _device_src_stats, _dict_stats). */

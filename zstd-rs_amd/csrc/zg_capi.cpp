@@ -82,6 +82,7 @@ const char* zgpu_status_name(int s) {
     case ZGPU_E_CHECKSUM_MISMATCH: return "ChecksumMismatch";
     case ZGPU_E_CONTENT_SIZE_MISMATCH: return "ContentSizeMismatch";
     case ZGPU_E_SEEK_TABLE: return "SeekTable";
+    case ZGPU_E_SEEK_CHECKSUM_MISMATCH: return "SeekChecksumMismatch";
     case ZGPU_E_UNSUPPORTED: return "Unsupported";
     case ZGPU_E_INTERNAL: return "Internal";
     case ZGPU_E_NOMEM: return "OutOfMemory";
@@ -856,7 +857,7 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
   int st = zgpu_decoder_create(c, &d);
   if (st) return st;
   // (sums: the content checksums of the frames decoded, as zgpu_decode_frames reports them — the decoder hashes what is drained)
-  auto note = [&](uint64_t yielded) {
+  auto note = [&](uint64_t yielded, size_t begin, size_t end) {
     if (!sums) return;
     if (d->fh.has_fcs() && d->fh.frame_content_size != yielded) sums->size_lies++;
     uint32_t v = 0;
@@ -864,6 +865,7 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
     const uint32_t calc = zgpu_decoder_calculated_checksum(d);
     if (sums->nframes == 0) { sums->first_data = has ? v : 0u; sums->first_calc = calc; }
     sums->nframes++;
+    sums->frames.push_back(ZgFrameSum{begin, end, yielded, calc});
     if (has) { sums->checksums++; if (v != calc) sums->mismatches++; }
   };
   d->drain_rule = ZG_DRAIN_DECODE_ALL;   // one decode_blocks(All) per frame stands for the reference's rounds of UptoBytes(1 MiB) + read(): same verdicts
@@ -904,7 +906,7 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
       }
       d->drain_rule = ZG_DRAIN_DECODE_ALL;
       if (st) break;
-      note(total - before);
+      note(total - before, frame_at, p);
       continue;
     }
     p += used;
@@ -912,7 +914,7 @@ int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t
     const size_t got = zgpu_decoder_read(d, dst + total, cap - total);
     total += got;
     if (zgpu_decoder_can_collect(d) != 0) { st = ZGPU_E_TARGET_TOO_SMALL; break; }
-    note(got);
+    note(got, frame_at, p);
   }
   zgpu_decoder_destroy(d);
   if (!st) *written = total;

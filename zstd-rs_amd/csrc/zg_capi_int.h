@@ -29,7 +29,9 @@ enum { kDevStatSubmits = 0, kDevStatScatterLaunches, kDevStatBytesScattered, kDe
 enum { kSrcStatWalkLaunches = 0, kSrcStatWalkUs, kSrcStatSkeletonBytes, kSrcStatGatherLaunches, kSrcStatGatherUs, kSrcStatInputBytesToHost, kSrcStatCount };
 enum { kIndexStatLaunches = 0, kIndexStatKernelUs, kIndexStatBytesDownloaded, kIndexStatInputBytesToHost, kIndexStatCount };
 enum { kRangeStatSeekLaunches = 0, kRangeStatSeekUs, kRangeStatSeekBytesDownloaded, kRangeStatInputBytesToHost, kRangeStatFramesSkipped,
-       kRangeStatFramesDecoded, kRangeStatPlaintextDecoded, kRangeStatBytesWritten, kRangeStatCount };
+       kRangeStatFramesDecoded, kRangeStatPlaintextDecoded, kRangeStatBytesWritten,
+       // ZGPU_DEVICE_VERIFY_SEEK_TABLE (zg_seeksums.h): zg_k_seeksums launches, their time, the bytes they brought back, frames compared, entries failed
+       kRangeStatCompareLaunches, kRangeStatCompareUs, kRangeStatCompareBytesDownloaded, kRangeStatFramesCompared, kRangeStatEntriesFailedTable, kRangeStatCount };
 static_assert(kSrcStatWalkLaunches == zg::kPassLaunches && kSrcStatWalkUs == zg::kPassUs && kSrcStatSkeletonBytes == zg::kPassBytes &&
               kIndexStatLaunches == zg::kPassLaunches && kIndexStatKernelUs == zg::kPassUs && kIndexStatBytesDownloaded == zg::kPassBytes &&
               kRangeStatSeekLaunches == zg::kPassLaunches && kRangeStatSeekUs == zg::kPassUs && kRangeStatSeekBytesDownloaded == zg::kPassBytes,
@@ -95,7 +97,9 @@ size_t zg_stream_take(zg::StreamCore* c, uint8_t* dst, size_t n);   // n <= can_
 // (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); sums, if given, collects the
 // content checksums of the frames it decoded (zgpu_decode_frames)
 // size_lies: frames that declare a Frame_Content_Size and yielded another number of bytes
-struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0, size_lies = 0; };
+// frames: every decoded frame's bytes [begin, end) of src, what it yielded and the low 32 bits of the XXH64 of that
+struct ZgFrameSum { uint64_t begin, end, yielded; uint32_t calc; };
+struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0, size_lies = 0; std::vector<ZgFrameSum> frames; };
 int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums);
 // (zg_stream.cpp) the process-wide cache of pinned host blocks the streams use; nullptr if none can be had
 void* zg_pinned_get(size_t n);

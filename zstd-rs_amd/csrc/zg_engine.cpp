@@ -175,6 +175,8 @@ Batch::~Batch() {
   if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
   for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_hash_) if (e) (void)hipEventDestroy(e);
+  if (d_seeksums_.p && eng) { (void)hipSetDevice(eng->device_); d_seeksums_.release(); }
+  for (hipEvent_t e : ev_seeksums_) if (e) (void)hipEventDestroy(e);
   for (DevBuf& x : d_fill_) if (x.p && eng) { (void)hipSetDevice(eng->device_); x.release(); }
   for (hipEvent_t e : ev_fill_) if (e) (void)hipEventDestroy(e);
   if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
@@ -1108,7 +1110,7 @@ int Batch::read_output(uint64_t off, uint8_t* dst, uint64_t n) {
   }
   return ZG_OK;
 }
-int Batch::hash_launch(const uint32_t* frames, uint32_t n) {
+int Batch::hash_launch(const uint32_t* frames, uint32_t n, uint32_t quad_max_ranges) {
   ZG_HIP(hipSetDevice(eng->device_));
   hash_n_ = 0;
   if (!n) return ZG_OK;
@@ -1130,7 +1132,7 @@ int Batch::hash_launch(const uint32_t* frames, uint32_t n) {
   ZG_HIP(hipStreamSynchronize(s));   // (r is pageable and goes out of scope)
   for (hipEvent_t& e : ev_hash_) if (!e) ZG_HIP(hipEventCreate(&e));
   ZG_HIP(hipEventRecord(ev_hash_[0], s));
-  zg_launch_xxh64(dev.dst, d_hash_.as<ZgHashRange>(), (uint64_t*)((uint8_t*)d_hash_.p + rb), n, s);
+  zg_launch_xxh64_with(dev.dst, d_hash_.as<ZgHashRange>(), (uint64_t*)((uint8_t*)d_hash_.p + rb), n, s, n <= quad_max_ranges ? 4 : 0);
   ZG_HIP(hipGetLastError());
   ZG_HIP(hipEventRecord(ev_hash_[1], s));
   hash_n_ = n;
@@ -1186,6 +1188,48 @@ int Batch::scatter_wait(uint64_t* kernel_us, bool* launched) {
   float ms = 0;
   ZG_HIP(hipEventElapsedTime(&ms, ev_scatter_[0], ev_scatter_[1]));
   *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  return ZG_OK;
+}
+int Batch::seeksums_launch(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  seeksums_n_ = 0;
+  if (!n) return ZG_OK;
+  if (!synced) return ZG_BAD_ARG;
+  for (uint32_t i = 0; i < n; i++)   // a wave reads its own slice of the list and the digests that slice names, and nothing else (zg_seeksums.h)
+    if (lanes[i].frame_lo > nframes || lanes[i].frame_n > nframes - lanes[i].frame_lo) return ZG_INTERNAL;
+  for (uint32_t q = 0; q < nframes; q++)
+    if (frames[q].slot != zgv::kNotHashed && frames[q].slot >= hash_n_) return ZG_INTERNAL;
+  const size_t lb = (size_t)n * sizeof(zgv::Lane), fb = (size_t)nframes * sizeof(zgv::Frame), ob = (size_t)n * sizeof(zgv::Sums);
+  int st = d_seeksums_.reserve(lb + fb + ob);
+  if (st) return st;
+  for (hipEvent_t& e : ev_seeksums_) if (!e) ZG_HIP(hipEventCreate(&e));
+  // the tables travel on the second stream (idle: the scatter waits for the verdicts) and the kernel goes behind the hash kernel on the first,
+  // which is not waited for
+  hipStream_t up = eng->stream2_, s = eng->stream_;
+  ZG_HIP(hipMemcpyAsync(d_seeksums_.p, lanes, lb, hipMemcpyHostToDevice, up));
+  if (fb) ZG_HIP(hipMemcpyAsync((uint8_t*)d_seeksums_.p + lb, frames, fb, hipMemcpyHostToDevice, up));
+  ZG_HIP(hipStreamSynchronize(up));   // (the tables are pageable)
+  const uint64_t* dig = hash_n_ ? (const uint64_t*)((uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange)) : nullptr;
+  ZG_HIP(hipEventRecord(ev_seeksums_[0], s));
+  zg_launch_seeksums(d_seeksums_.as<zgv::Lane>(), n, (const zgv::Frame*)((uint8_t*)d_seeksums_.p + lb), dig, hash_n_,
+                     (zgv::Sums*)((uint8_t*)d_seeksums_.p + lb + fb), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev_seeksums_[1], s));
+  seeksums_n_ = n;
+  seeksums_out_ = lb + fb;
+  return ZG_OK;
+}
+int Batch::seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
+  *kernel_us = 0; *bytes = 0;
+  if (!seeksums_n_) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  ZG_HIP(hipStreamSynchronize(eng->stream_));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, ev_seeksums_[0], ev_seeksums_[1]));
+  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  *bytes = (uint64_t)seeksums_n_ * sizeof(zgv::Sums);
+  ZG_HIP(hipMemcpy(out, (uint8_t*)d_seeksums_.p + seeksums_out_, (size_t)*bytes, hipMemcpyDeviceToHost));
+  seeksums_n_ = 0;
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

@@ -174,7 +174,9 @@ class Batch {
   // after sync(): XXH64 (seed 0) of the output bytes of frames[0 .. n) as sync() left them ([out_base, out_base + out_size): a failed frame's
   // good blocks), one lane or one quad of lanes per frame (zg_k_xxh64 / zg_k_xxh64q: zg_launch_xxh64 chooses), enqueued on the engine's first
   // stream; hash_wait() waits and writes digest i of frames[i]; *kernel_us, if asked for: the kernel's time between two HIP events
-  int hash_launch(const uint32_t* frames, uint32_t n);
+  // quad_max_ranges: up to this many frames the launch is zg_k_xxh64q's whatever zg_launch_xxh64 would choose (0: its choice; the calls that
+  // carry ZGPU_DEVICE_VERIFY_SEEK_TABLE hash few mid-sized frames per range, LABNOTES.md "xxh64q")
+  int hash_launch(const uint32_t* frames, uint32_t n, uint32_t quad_max_ranges = 0);
   int hash_wait(uint64_t* out, uint64_t* kernel_us = nullptr);
   // after sync(): zg_k_scatter (zg_scatter.h) copies segs[0 .. n) of the output to their destinations — device memory of the CALLER, which it
   // has checked (zgpu_decode_frames_device) — in one launch on the engine's second stream, beside hash_launch's kernel on the first. Segments
@@ -182,6 +184,13 @@ class Batch {
   // scatter_wait() waits for the kernel; *kernel_us = its time between two HIP events, *launched = whether there was one (no bytes: none)
   int scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk);
   int scatter_wait(uint64_t* kernel_us, bool* launched);
+  // between hash_launch and hash_wait: zg_k_seeksums (zg_seeksums.h) compares the Checksum fields of the seek tables of lanes[0 .. n) — whole
+  // entries in device memory of the CALLER, which it has checked — with the digests hash_launch's kernel writes, for frames[0 .. nframes) (a
+  // lane's slice; Frame::slot: the index of the frame in hash_launch's list). One launch on the engine's first stream, behind the hash kernel:
+  // no wait in between. A slice or a slot that leaves its array is refused (ZGPU_E_INTERNAL) before anything is launched. seeksums_wait()
+  // waits and writes record i of lanes[i]; *kernel_us = the kernel's time between two HIP events, *bytes = what came back
+  int seeksums_launch(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes);
+  int seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -210,6 +219,10 @@ class Batch {
   DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
   hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
   bool scatter_on_ = false;
+  DevBuf d_seeksums_;                    // seeksums_launch: the lanes, the frame list, then the records
+  hipEvent_t ev_seeksums_[2] = {nullptr, nullptr};
+  uint32_t seeksums_n_ = 0;
+  size_t seeksums_out_ = 0;              //   where the records begin
   std::vector<zgd::DictImage> frame_dicts_;   // set_frame_dicts
   DevBuf d_fill_[2];                          // dictfill_launch: the segments, then the chunk table (0: tables, 1: contents)
   hipEvent_t ev_fill_[4] = {nullptr, nullptr, nullptr, nullptr};

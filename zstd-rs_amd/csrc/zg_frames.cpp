@@ -45,6 +45,7 @@
 #include <vector>
 #include "zg_capi_int.h"
 #include "zg_scatter.h"
+#include "zg_seeksums.h"
 #include "zg_xxh64_dev.h"
 
 using namespace zg;
@@ -61,6 +62,11 @@ constexpr uint64_t kFramesSubmitBytes = 512ull << 20;
 constexpr uint64_t kHashDeviceMax = 4ull << 20;
 constexpr double kLaneBytesPerUs = 225.0, kDeviceBytesPerUs = 1.0e6, kHostBytesPerUs = 1.0e4, kLaunchUs = 50.0;
 constexpr unsigned kHostThreads = 16;
+// ZGPU_DEVICE_VERIFY_SEEK_TABLE hashes the few mid-sized frames a range takes and waits for them: up to this many frames a submit of such a call
+// is hashed by zg_k_xxh64q (four lanes per frame). From tools/dev/hash_ranges.py on an MI355X (LABNOTES.md "xxh64q"): the quad kernel is 5.1 x
+// (8 x 128 KiB) to 10.3 x (4096 x 128 KiB) the one-lane kernel on ranges of this kind; 4096 is the largest count of mid-sized ranges measured.
+// No other call hashes differently: ZG_XXH64Q_MAX_RANGES (zg_kernels.h) stays 0.
+constexpr uint32_t kTableQuadMaxRanges = 4096;
 
 unsigned host_threads() {
   const unsigned t = std::thread::hardware_concurrency();
@@ -123,6 +129,12 @@ struct DeviceSink {
   bool no_hash = false;           // ZGPU_DEVICE_NO_HASH: hash no frame
   bool verify = false;            // ZGPU_DEVICE_VERIFY: a mismatch fails the entry, with nothing of it written
   bool hash_all = false;          // verify with hash_max_bytes == 0: every frame that carries a Content_Checksum is hashed
+  // ZGPU_DEVICE_VERIFY_SEEK_TABLE (zg_seeksums.h): the WHOLE entries — Call::srcs are the selections — and the table rows of each selection;
+  // empty: the flag is not set. An entry with taken == 0 is not looked at. table_all: hash_max_bytes == 0, every frame of such an entry is hashed
+  struct TableEntry { uint64_t src, len; uint32_t first, taken; };
+  std::vector<TableEntry> table_verify;
+  bool table_flag = false, table_all = false;
+  bool table(uint32_t i) const { return !table_verify.empty() && table_verify[i].taken != 0; }
   uint64_t* stats = nullptr;      // zgpu_ctx::frames_device_stats (kDevStat*)
   uint64_t alone_written = 0;     // bytes the entries decoded alone brought to their destinations
 };
@@ -206,6 +218,7 @@ struct Submit {
   Batch* b = nullptr;
   std::vector<int> walk;
   std::vector<uint32_t> ff;       // entry j's frames are [ff[j], ff[j + 1])
+  std::vector<uint64_t> off;      // entry j lies at off[j] of the submit's input (FrameInfo::src_begin / src_end are counted from its begin)
   std::vector<uint32_t> cand;     // frames of successful entries short enough to be hashed on the device
   uint64_t down = 0;              // output bytes the successful entries reach up to
   ~Submit() { delete b; }
@@ -213,7 +226,9 @@ struct Submit {
 
 // one submit, up to its verdicts: the entries idx[0 .. n) staged, walked, decoded; status / written / nframes of every entry it serves
 int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
-  std::vector<uint64_t> off(n), len(n);
+  std::vector<uint64_t>& off = u.off;
+  std::vector<uint64_t> len(n);
+  off.assign(n, 0);
   uint64_t total_in = 0;
   for (uint32_t j = 0; j < n; j++) { off[j] = total_in; len[j] = k.lens[idx[j]]; total_in += len[j]; }
   Staging& in = u.in;
@@ -279,8 +294,9 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[kDictStatFramesShared] += b->bb.frames[f].dict_len ? 1u : 0u;
     r.written = k.clipped(i, bytes);
     r.nframes = ff[j + 1] - ff[j];
+    const bool table_all = k.sink && k.sink->table_all && k.sink->table(i);   // (the seek table's checksums: every frame, with or without a Content_Checksum)
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (fo[f].out_size <= k.hash_max() || (k.sink && k.sink->hash_all && b->info[f].has_checksum)) u.cand.push_back(f);   // (candidates)
+      if (fo[f].out_size <= k.hash_max() || (k.sink && k.sink->hash_all && b->info[f].has_checksum) || table_all) u.cand.push_back(f);   // (candidates)
       const uint64_t e = fo[f].out_base + fo[f].out_size;
       if (e > u.down) u.down = e;
     }
@@ -290,21 +306,32 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
 
 // A device-sink entry fails with `status`: written = nframes = 0 like any failed entry (sums / bad: the two counts of the checksum verdict,
 // which say why). The arguments are taken by value: they may be d's own fields.
-void fail_entry(zgpu_device_entry_result& d, int status, uint32_t sums = 0, uint32_t bad = 0) {
+void fail_entry(zgpu_device_entry_result& d, int status, uint32_t sums = 0, uint32_t bad = 0, uint32_t unverified = 0) {
   memset(&d, 0, sizeof d);
   d.r.status = status;
   d.r.checksums = sums; d.r.checksum_mismatches = bad;
+  d.checksums_unverified = unverified;
 }
+// The verdict of ZGPU_DEVICE_VERIFY_SEEK_TABLE on an entry of nframes decoded zstd frames that stands at status 0, from its record (zg_seeksums.h:
+// vouched). A failed entry reports the frames compared, those that differ and the decoded frames not compared. Returns whether it failed.
+bool table_verdict(zgpu_device_entry_result& d, const zgv::Sums& s, uint32_t nframes, uint64_t* range_stats) {
+  range_stats[kRangeStatFramesCompared] += s.compared;
+  if (zgv::vouched(s, nframes)) return false;
+  fail_entry(d, ZGPU_E_SEEK_CHECKSUM_MISMATCH, s.compared, s.differing, nframes - s.compared);
+  range_stats[kRangeStatEntriesFailedTable]++;
+  return true;
+}
+const char* const kTableChanged = "zgpu_decode_ranges_seek_table_device_src: a seek table changed between the seek and the checksum compare";
 
 // What both sinks do about hashing: the frames of u.cand, as the sink left that list, are hashed by the device — launch() enqueues the kernel
 // on the first stream, and the sink does its copying beside it; wait() collects the digests (*kernel_us, if asked for: the kernel's time).
 struct SubmitHash {
   std::vector<uint8_t> on_dev;    // per frame of the submit: hashed on the device
   std::vector<uint64_t> digest;   // per frame: its XXH64 (on_dev frames after wait(); the host sink fills in the others)
-  int launch(const Submit& u) {
+  int launch(const Submit& u, uint32_t quad_max_ranges = 0) {
     on_dev.assign(u.b->frame_out.size(), 0);
     for (uint32_t f : u.cand) on_dev[f] = 1;
-    return u.b->hash_launch(u.cand.data(), (uint32_t)u.cand.size());
+    return u.b->hash_launch(u.cand.data(), (uint32_t)u.cand.size(), quad_max_ranges);
   }
   int wait(const Submit& u, uint64_t* kernel_us = nullptr) {
     digest.assign(u.b->frame_out.size(), 0);
@@ -359,6 +386,8 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
 // (an entry's frames back to back) while the hash kernel (zg_launch_xxh64) hashes the candidates beside it; frames that are not hashed are
 // counted, not verified. With ZGPU_DEVICE_VERIFY the order is hash launch, hash wait, verdicts, and only then the scatter of the entries that
 // passed: an entry with a hashed frame whose digest differs from its Content_Checksum fails, and nothing of it is ever in the scatter list.
+// With ZGPU_DEVICE_VERIFY_SEEK_TABLE (zg_seeksums.h) the order is hash launch, seeksums launch (behind the hash kernel on its stream), the two
+// waits, the verdicts of ZGPU_DEVICE_VERIFY, the table's verdicts on what still stands, then the scatter of what still stands.
 int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   Batch* b = u.b;
   const std::vector<ZgFrameOut>& fo = b->frame_out;
@@ -368,7 +397,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   if (sink.no_hash) u.cand.clear();
   SubmitHash h;
   int st;
-  if ((st = h.launch(u))) return st;
+  if ((st = h.launch(u, sink.table_flag ? kTableQuadMaxRanges : 0u))) return st;
   uint64_t bytes = 0;
   auto scatter = [&]() -> int {   // the frames of every entry that stands at status 0, in one launch
     std::vector<zgs::Seg> segs;
@@ -392,10 +421,42 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
     return b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk);
   };
-  if (!sink.verify && (st = scatter())) return st;
+  // ZGPU_DEVICE_VERIFY_SEEK_TABLE: one zg_k_seeksums launch for the submit's entries that stand at status 0, behind the hash kernel on its stream
+  std::vector<uint32_t> tv;   // their j
+  if (sink.table_flag) {
+    std::vector<zgv::Lane> lanes;
+    std::vector<zgv::Frame> list;
+    std::vector<uint32_t> slot(fo.size(), zgv::kNotHashed);
+    for (size_t q = 0; q < u.cand.size(); q++) slot[u.cand[q]] = (uint32_t)q;
+    for (uint32_t j = 0; j < n; j++) {
+      const zgpu_entry_result& r = dres[idx[j]].r;
+      if (r.status || r.nframes == 0 || !sink.table(idx[j])) continue;
+      const DeviceSink::TableEntry& e = sink.table_verify[idx[j]];
+      const uint32_t lo = (uint32_t)list.size();
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+        const FrameInfo& fi = b->info[f];
+        if (fi.src_begin < u.off[j] || fi.src_end < fi.src_begin) return ZGPU_E_INTERNAL;   // (never)
+        if (fi.src_end - fi.src_begin > 0xFFFFFFFFull) continue;   // (no row can hold its length: it coincides with none)
+        list.push_back(zgv::Frame{fi.src_begin - u.off[j], (uint32_t)(fi.src_end - fi.src_begin), slot[f]});
+      }
+      lanes.push_back(zgv::Lane{e.src, e.len, e.first, e.taken, lo, (uint32_t)list.size() - lo});
+      tv.push_back(j);
+    }
+    if (list.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
+    if ((st = b->seeksums_launch(lanes.data(), (uint32_t)lanes.size(), list.data(), (uint32_t)list.size()))) return st;
+  }
+  const bool gated = sink.verify || sink.table_flag;   // the scatter waits for the verdicts
+  if (!gated && (st = scatter())) return st;
   uint64_t hash_us = 0;
   if ((st = h.wait(u, &hash_us))) return st;
   sink.stats[kDevStatHashUs] += hash_us;
+  std::vector<zgv::Sums> sums(tv.size());
+  if (!tv.empty()) {
+    uint64_t us = 0, back = 0;
+    if ((st = b->seeksums_wait(sums.data(), &us, &back))) return st;
+    uint64_t* rs = k.ranges->stats;
+    rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
+  }
   auto count_frame = [&](uint32_t f) { sink.stats[h.on_dev[f] ? kDevStatFramesHashed : kDevStatFramesNotHashed]++; };
   if (sink.verify) {
     // the verdict of verification ranks behind every other one: only entries that stand at status 0 are looked at
@@ -414,8 +475,16 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       fail_entry(dres[idx[j]], ZGPU_E_CHECKSUM_MISMATCH, sums, bad);
       sink.stats[kDevStatEntriesFailedVerify]++;
     }
-    if ((st = scatter())) return st;
   }
+  // the table's verdict ranks last: only what still stands is looked at
+  for (size_t t = 0; t < tv.size(); t++) {
+    const uint32_t j = tv[t];
+    if (sums[t].why) { k.c->eng->last_error = kTableChanged; return ZGPU_E_INTERNAL; }
+    if (dres[idx[j]].r.status) continue;
+    if (table_verdict(dres[idx[j]], sums[t], ff[j + 1] - ff[j], k.ranges->stats))
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
+  }
+  if (gated && (st = scatter())) return st;
   uint64_t us = 0;
   bool launched = false;
   if ((st = b->scatter_wait(&us, &launched))) return st;
@@ -449,7 +518,7 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
 // an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
 // which also hashes what it hands out)
 int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr, const uint8_t* host_src = nullptr,
-                 uint32_t* size_lies = nullptr) {
+                 uint32_t* size_lies = nullptr, std::vector<ZgFrameSum>* frames = nullptr) {
   const uint8_t* src = host_src ? host_src : k.srcs[i];   // (device sources: the entry's bytes downloaded by decode_alone_device)
   zgpu_entry_result& r = k.result(i);
   memset(&r, 0, sizeof r);
@@ -479,6 +548,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
   if (st) return ZGPU_OK;
   if (summed) *summed = sums_ok;
   if (size_lies) *size_lies = sums.size_lies;
+  if (frames && sums_ok) frames->swap(sums.frames);
   if (!sums_ok) {   // the frames are counted from their headers; no checksum is reported
     std::vector<FrameSpan> sp;
     (void)split_frames(src, k.lens[i], &sp);
@@ -511,7 +581,8 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   if (!tmp) return ZGPU_E_NOMEM;
   bool summed = false;
   uint32_t size_lies = 0;
-  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies);
+  std::vector<ZgFrameSum> frames;   // (ZGPU_DEVICE_VERIFY_SEEK_TABLE) where every decoded frame lies in the selection, and its digest
+  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies, sink.table(i) ? &frames : nullptr);
   zgpu_device_entry_result& d = sink.res[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
@@ -532,6 +603,38 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
     sink.stats[kDevStatFramesHashed] += d.r.nframes;
     fail_entry(d, ZGPU_E_CHECKSUM_MISMATCH, d.r.checksums, d.r.checksum_mismatches);
     sink.stats[kDevStatEntriesFailedVerify]++;
+  }
+  // ZGPU_DEVICE_VERIFY_SEEK_TABLE, last: zg_seeksums.h's rule over rows the host holds — the footer and rows [first, first + taken) come down (the
+  // entry crossed to the host anyway), the host hashed every frame (a frame longer than a nonzero hash_max_bytes passes uncompared, as in a
+  // submit). Should the frame-by-frame pass have failed (never seen), nothing is known of the frames and nothing vouches for them.
+  if (ok && !d.r.status && d.r.nframes && sink.table(i)) {
+    const DeviceSink::TableEntry& e = sink.table_verify[i];
+    zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
+    if (summed && e.len >= zgt::kFraming) {
+      uint8_t footer[9];
+      uint32_t es = 8;
+      uint64_t rows_off = 0;
+      if (hipMemcpy(footer, (const uint8_t*)(uintptr_t)e.src + (e.len - 9), 9, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
+      rec.why = zgv::locate_rows(footer, e.len, e.first, e.taken, &es, &rows_off);
+      std::vector<uint8_t> rows;
+      if (!rec.why) {
+        try { rows.resize((size_t)e.taken * es); } catch (...) { free(tmp); return ZGPU_E_NOMEM; }
+        if (hipMemcpy(rows.data(), (const uint8_t*)(uintptr_t)e.src + rows_off, rows.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
+        k.src->stats[kSrcStatInputBytesToHost] += 9 + rows.size();
+        std::vector<zgv::Frame> list;
+        std::vector<uint64_t> dig;
+        for (const ZgFrameSum& f : frames) {
+          if (f.end - f.begin > 0xFFFFFFFFull) continue;
+          const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
+          list.push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig.size() : zgv::kNotHashed});
+          if (hashed) dig.push_back(f.calc);
+        }
+        rec = zgv::sums_rows(rows.data(), es, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
+      }
+    } else if (summed) rec.why = zgt::kNone;
+    if (rec.why) { k.c->eng->last_error = kTableChanged; free(tmp); return ZGPU_E_INTERNAL; }
+    const uint32_t nframes = d.r.nframes;
+    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
   }
   size_t from = 0;   // ranges: only the clipped bytes are uploaded
   if (clip && ok && !d.r.status) {
@@ -626,7 +729,8 @@ int drain(zgpu_ctx* c, int st) {
 }
 
 // The device sink of a call, from its options. ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY (hash nothing, verify everything) is refused: *st.
-DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st) {
+// ZGPU_DEVICE_VERIFY_SEEK_TABLE is refused the same way with ZGPU_DEVICE_NO_HASH, and on every call but the one that has a seek table (table).
+DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st, bool table = false) {
   const uint32_t flags = opts ? opts->flags : 0u;
   DeviceSink s;
   s.res = results;
@@ -635,7 +739,9 @@ DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_en
   s.verify = (flags & ZGPU_DEVICE_VERIFY) != 0;
   s.hash_all = s.verify && !opts->hash_max_bytes;
   s.stats = c->frames_device_stats;
-  *st = s.no_hash && s.verify ? ZGPU_E_BAD_ARG : ZGPU_OK;
+  s.table_flag = (flags & ZGPU_DEVICE_VERIFY_SEEK_TABLE) != 0;
+  s.table_all = s.table_flag && !opts->hash_max_bytes;
+  *st = (s.no_hash && (s.verify || s.table_flag)) || (s.table_flag && !table) ? ZGPU_E_BAD_ARG : ZGPU_OK;
   return s;
 }
 
@@ -871,6 +977,7 @@ static_assert(offsetof(zgpu_seek, plain_seen) == offsetof(zgk::Seek, plain_seen)
 static_assert(ZGPU_E_SEEK_TABLE == zgt::kSeekTable && ZGPU_SEEKTAB_NONE == zgt::kNone && ZGPU_SEEKTAB_RESERVED_BITS == zgt::kReservedBits &&
               ZGPU_SEEKTAB_TOO_LARGE == zgt::kTooLarge && ZGPU_SEEKTAB_BAD_FRAME == zgt::kBadFrame && ZGPU_SEEKTAB_PAST_TABLE == zgt::kPastTable,
               "zg_seektab.h");
+static_assert(ZGPU_E_SEEK_CHECKSUM_MISMATCH == zgv::kSeekChecksumMismatch, "zg_seeksums.h");
 namespace {
 // Both calls up to the records: every pointer checked, ONE zg_k_seek launch over all n lanes (a refused entry and a range of length 0 have
 // length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations. table: the selection
@@ -937,7 +1044,7 @@ int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* len
   if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
   std::vector<zgpu_device_entry_result> dres(n);
   int st;
-  DeviceSink sink = device_sink(c, opts, dres.data(), &st);
+  DeviceSink sink = device_sink(c, opts, dres.data(), &st, table);
   if (st) return st;
   reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
   for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
@@ -952,6 +1059,7 @@ int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* len
   rg.promise = table;
   rg.stats = c->ranges_stats;
   src.dev.resize(n);
+  if (sink.table_flag) sink.table_verify.resize(n);
   for (uint32_t i = 0; i < n; i++) {
     const zgk::Seek& s = recs[i];
     if (s.status) src.refused[i] = (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1);   // (an anchor behind the entry or behind begin; no usable table)
@@ -959,6 +1067,7 @@ int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* len
     srcs[i] = (const uint8_t*)device_srcs[i] + (none ? 0 : s.src_lo);
     sub[i] = none ? 0 : (size_t)(s.src_hi - s.src_lo);
     src.dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
+    if (sink.table_flag) sink.table_verify[i] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[i], (uint64_t)lens[i], s.frames_skipped, none ? 0u : s.frames_taken};
     const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
     rg.clip[i] = Ranges::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX};   // (table: an entry of which nothing is taken promises nothing)
   }

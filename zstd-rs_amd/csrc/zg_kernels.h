@@ -9,6 +9,7 @@
 #include "zg_index.h"
 #include "zg_seek.h"
 #include "zg_seektab.h"
+#include "zg_seeksums.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -49,8 +50,9 @@ void zg_launch_xxh64(const uint8_t* base, const ZgHashRange* ranges, uint64_t* o
 // zg_k_xxh64q: the same digests, four lanes per range (lane l owns accumulator l), 16 ranges per wave, one wave per workgroup. A range costs more
 // wave-instructions this way (~17/16 of a lane's share per stripe against 54/64), so it is the kernel for launches whose ranges are too few to
 // fill the chip, where the rate PER RANGE decides: zg_launch_xxh64 takes it for up to ZG_XXH64Q_MAX_RANGES ranges. That threshold comes from
-// tools/dev/hash_ranges.py on an MI355X; the measurement has not been taken yet (LABNOTES.md "xxh64q"), so it is 0 and every launch of the
-// library is still zg_k_xxh64 — the quad kernel runs only where it is asked for by name.
+// tools/dev/hash_ranges.py on an MI355X (LABNOTES.md "xxh64q": the quad kernel won on every workload measured, 1.35 x to 26 x). It is still 0:
+// the launches of the existing calls are zg_k_xxh64 as before, and the quad kernel runs where it is asked for by name — zgpu_debug_hash_ranges,
+// and Batch::hash_launch's quad_max_ranges, which the calls that carry ZGPU_DEVICE_VERIFY_SEEK_TABLE set (zg_frames.cpp: kTableQuadMaxRanges).
 // zg_launch_xxh64_with: kernel 0 the rule above, 1 zg_k_xxh64, 4 zg_k_xxh64q (zgpu_debug_hash_ranges).
 #define ZG_XXH64Q_RANGES 16u
 #define ZG_XXH64Q_MAX_RANGES 0u
@@ -75,3 +77,6 @@ void zg_launch_seek(const zgk::Lane* lanes, uint32_t n, zgk::Seek* out, hipStrea
 // zg_k_seektab (zg_seektab.h): one wave per entry answers the same from the seekable format's seek table at the entry's end; one 64-thread
 // workgroup per entry, out[i] = entry i's record
 void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipStream_t s);
+// zg_k_seeksums (zg_seeksums.h): one wave per entry compares the Checksum fields of the entry's seek table with the digests the hash kernel wrote
+// (digests[0 .. ndig), device memory) for the entry's slice of frames; one 64-thread workgroup per entry, out[i] = entry i's 32-byte record
+void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, const uint64_t* digests, uint32_t ndig, zgv::Sums* out, hipStream_t s);

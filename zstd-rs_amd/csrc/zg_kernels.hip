@@ -1939,6 +1939,46 @@ void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipSt
   hipLaunchKernelGGL(zg_k_seektab, dim3(n), dim3(zgt::kThreads), 0, s, lanes, n, out);
 }
 
+// Does an entry's seek table vouch for the frames decoded of it (ZGPU_DEVICE_VERIFY_SEEK_TABLE)? One WAVE per entry of a submit, behind the hash
+// kernel on the same stream: the table's Checksum fields against the digests that kernel left in device memory (zg_seeksums.h has the rule,
+// the record, the access bounds and the ISA notes). The host checked every [src, src + len) against the runtime's allocations and every
+// lane's slice and slot against the arrays it uploaded (Batch::seeksums_launch); lane 0 writes the entry's 32-byte record only.
+#include "zg_seeksums.h"
+struct __attribute__((packed)) zg_u96u { uint32_t a, b, c; };
+struct ZgSumsRead : ZgTabRead {
+  __device__ __forceinline__ void ld12(uint64_t off, uint32_t* a, uint32_t* b, uint32_t* c) const {
+    zg_u96u v;
+    __builtin_memcpy(&v, (const __attribute__((address_space(1))) void*)(base + off), 12);
+    *a = v.a; *b = v.b; *c = v.c;
+  }
+};
+struct ZgSumsList {
+  const __attribute__((address_space(1))) zgv::Frame* fr;
+  const __attribute__((address_space(1))) uint64_t* dig;
+  __device__ __forceinline__ uint64_t begin(uint32_t i) const { return fr[i].begin; }
+  __device__ __forceinline__ void frame(uint32_t i, uint64_t* b, uint32_t* c, uint32_t* slot) const {
+    const zg_v4u v = *(const zg_gv4u*)&fr[i];
+    *b = ((uint64_t)v.y << 32) | v.x; *c = v.z; *slot = v.w;
+  }
+  __device__ __forceinline__ uint32_t digest(uint32_t slot) const { return *(const __attribute__((address_space(1))) uint32_t*)&dig[slot]; }
+};
+__global__ void __launch_bounds__(zgv::kThreads) zg_k_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, const uint64_t* digests,
+                                                               uint32_t ndig, zgv::Sums* out) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const zgv::Lane l = lanes[i];
+  const ZgSumsList list{(const __attribute__((address_space(1))) zgv::Frame*)(uintptr_t)(frames + l.frame_lo),
+                        (const __attribute__((address_space(1))) uint64_t*)(uintptr_t)digests};
+  ZgSumsRead rd;
+  rd.base = l.src;
+  const zgv::Sums o = zgv::seeksums_entry(rd, list, l.len, l.first, l.taken, l.frame_n, ndig);
+  if (threadIdx.x == 0) zgv::seeksums_store(&out[i], o);
+}
+void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, const uint64_t* digests, uint32_t ndig, zgv::Sums* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_seeksums, dim3(n), dim3(zgv::kThreads), 0, s, lanes, n, frames, digests, ndig, out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

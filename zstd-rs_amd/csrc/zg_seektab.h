@@ -10,7 +10,8 @@
 //   Number_Of_Frames u32 | Seek_Table_Descriptor u8 (bit 7 Checksum_Flag, bits 6..2 reserved and 0, bits 1..0 ignored) | 0x8F92EAB1
 // es is 8, or 12 with checksums; Number_Of_Frames <= 0x8000000. Entry k describes the k-th frame of the entry (a skippable frame is entered
 // with decompressed size 0): it lies at source offset C_k = the compressed sizes in front of it and yields plaintext [D_k, D_k + d_k), D_k =
-// the decompressed sizes in front of it. The Checksum fields are not read.
+// the decompressed sizes in front of it. zg_k_seektab does not read the Checksum fields; zg_k_seeksums (zg_seeksums.h) compares them with the
+// digests of the decoded frames where ZGPU_DEVICE_VERIFY_SEEK_TABLE asks for it.
 //
 // Locating the table, wave-uniform, in this order (the first that fails is `why`):
 //   1. len < 17 or the last four bytes are not the seekable magic                              kNone

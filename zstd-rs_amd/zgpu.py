@@ -28,6 +28,7 @@ E_CHECKSUM_MISMATCH = 70    # decode_frames_device / decode_frames_device_src wi
 E_SEEK_TABLE = 72              # the seek-table calls only: the entry does not end in a usable seek table (Seek.why: SEEKTAB_*)
 SEEKTAB_NONE, SEEKTAB_RESERVED_BITS, SEEKTAB_TOO_LARGE, SEEKTAB_BAD_FRAME, SEEKTAB_PAST_TABLE = 16, 17, 18, 19, 20
 E_CONTENT_SIZE_MISMATCH = 71   # decode_ranges_device_src only: a taken frame decoded to another length than it declares (no counterpart in the reference)
+E_SEEK_CHECKSUM_MISMATCH = 73  # decode_ranges_seek_table_device_src with verify_table=True only: the entry decoded, and its seek table does not vouch for the bytes
 E_UNSUPPORTED = 80
 E_HIP = 92
 E_BAD_ARG = 93
@@ -47,7 +48,8 @@ _STATS = {
                                    ("launches", "kernel_us", "bytes_downloaded", "input_bytes_to_host")),
     "Context.ranges_stats": ("zgpu_debug_ranges_stats", C.c_uint64,
                              ("seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
-                              "plaintext_decoded", "bytes_written")),
+                              "plaintext_decoded", "bytes_written",
+                              "compare_launches", "compare_us", "compare_bytes_downloaded", "frames_compared", "entries_failed_table")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
                        ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
     "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
@@ -487,8 +489,12 @@ def _one_per(method, n, *lists):
             raise ValueError("%s: %d entries, but a parallel list of %d elements" % (method, n, len(x)))
 
 
-def _opts(hash_max, no_hash, verify):
-    return DeviceOptsC(int(hash_max), (1 if no_hash else 0) | (2 if verify else 0), 0)
+DEVICE_NO_HASH, DEVICE_VERIFY, DEVICE_VERIFY_SEEK_TABLE = 1, 2, 4   # zgpu_device_opts.flags
+
+
+def _opts(hash_max, no_hash, verify, verify_table=False):
+    return DeviceOptsC(int(hash_max), (DEVICE_NO_HASH if no_hash else 0) | (DEVICE_VERIFY if verify else 0) |
+                       (DEVICE_VERIFY_SEEK_TABLE if verify_table else 0), 0)
 
 
 # what _results makes of an array of each record: the record's fields in the order of _fields_ as a struct format — a zgpu_range_result begins with
@@ -793,25 +799,35 @@ class Context:
         table's coordinates; an entry without a usable table has status E_SEEK_TABLE and why SEEKTAB_*."""
         return self._frames_seek("frames_seek_table_device", src_ptrs, lens, ranges, None)
 
-    def decode_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False):
+    def decode_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
+                                            verify_table=False):
         """zgpu_decode_ranges_seek_table_device_src: decode_ranges_device_src with the selection taken from each entry's seek table. Only the
         frames the table names for the range are decoded, whether or not they declare a size. Returns (results, seeks) as
         decode_ranges_device_src does; E_SEEK_TABLE: no usable table, E_CONTENT_SIZE_MISMATCH: the taken frames decoded to another total than
-        the table promises."""
+        the table promises. verify_table (ZGPU_DEVICE_VERIFY_SEEK_TABLE): the table's Checksum fields are enforced on the device — every
+        decoded frame is hashed (hash_max=0: no limit) and compared with the row it coincides with; an entry with a frame that differs, a frame
+        that coincides with no row, or a table without checksums gets E_SEEK_CHECKSUM_MISMATCH, written = nframes = 0 and no byte of its
+        destination is written (checksums: frames compared, checksum_mismatches: those that differ, checksums_unverified: decoded frames not
+        compared). verify_table with no_hash raises E_BAD_ARG."""
         return self._decode_ranges("decode_ranges_seek_table_device_src", src_ptrs, lens, ranges, None, dst_ptrs, caps,
-                                   _opts(hash_max, no_hash, verify))
+                                   _opts(hash_max, no_hash, verify, verify_table))
 
-    def ranges_stats(self):
-        """the last frames_seek_device / decode_ranges_device_src call or seek-table call (zgpu_debug_ranges_stats)"""
-        return self._stats("ranges_stats")
+    def ranges_stats(self, verify_table=False):
+        """the last frames_seek_device / decode_ranges_device_src call or seek-table call (zgpu_debug_ranges_stats). verify_table=True: with the
+        five fields of verify_table as well — compare_launches (out[8]), compare_us (zg_k_seeksums' time, HIP events), compare_bytes_downloaded
+        (32 per entry), frames_compared and entries_failed_table (out[12])."""
+        return self._stats("ranges_stats", 13 if verify_table else 8)
 
-    def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False, seek_table=False):
+    def decode_tensor_ranges(self, tensors, ranges, anchors=None, hash_max=0, no_hash=False, verify=False, seek_table=False, verify_table=False):
         """decode_ranges_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding entry i's
         compressed bytes, ranges[i] = (begin, len) the plaintext bytes wanted of it. The bytes go to ONE new torch.uint8 tensor, every entry's
         slot 256-byte aligned and sized by min(len, seek.bound) — a frames_seek_device call of its own finds the bound, so no byte of the
         input crosses to the host. Returns (tensors, results, seeks): tensors[i] is a view of entry i's slot cut to `written` bytes (empty
         unless status == 0). Same single-runtime rule as decode_tensors. torch is imported here, not by `import zgpu`.
-        seek_table=True: the selections come from the entries' seek tables (decode_ranges_seek_table_device_src; anchors must be None)."""
+        seek_table=True: the selections come from the entries' seek tables (decode_ranges_seek_table_device_src; anchors must be None), and
+        verify_table=True enforces the tables' checksums (only with seek_table=True: there is no table otherwise)."""
+        if verify_table and not seek_table:
+            raise ValueError("decode_tensor_ranges: verify_table needs seek_table=True")
         self._tensor_check(tensors, "decode_tensor_ranges")
         if seek_table and anchors is not None:
             raise ValueError("decode_tensor_ranges: a seek table is the index, there is nothing to anchor")
@@ -820,7 +836,8 @@ class Context:
         caps = [min(int(r[1]), s.bound) for r, s in zip(ranges, seeks)]
         buf, offs, dsts = self._slot_tensor(caps)
         if seek_table:
-            res, seeks = self.decode_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
+            res, seeks = self.decode_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify,
+                                                                  verify_table=verify_table)
         else:
             res, seeks = self.decode_ranges_device_src(ptrs, lens, ranges, dsts, caps, anchors=anchors, hash_max=hash_max, no_hash=no_hash,
                                                        verify=verify)
