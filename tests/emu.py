@@ -54,6 +54,13 @@ def lib():
         L.zgemu_seq_block.argtypes = [C.c_void_p, C.c_uint32]
         L.zgemu_seq_block.restype = C.c_uint32
         L.zgemu_exact.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        if hasattr(L, "zgemu_inorder_lz"):          # (zg_emu_inorder.cpp: in libzg_emu.so only, not in the `make asan` build)
+            L.zgemu_inorder_lz.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.zgemu_inorder_sparse.argtypes = [C.c_void_p, C.c_char_p]
+            L.zgemu_inorder_partial.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+            L.zgemu_block_pad.argtypes = [C.c_void_p, C.c_uint32]
+            L.zgemu_block_pad.restype = C.c_uint32
         u32p = C.POINTER(C.c_uint32)
         L.zgemu_map_apply.argtypes = [C.POINTER(C.c_uint32 * 3), C.c_uint32, u32p]
         L.zgemu_map_compose.argtypes = [C.POINTER(C.c_uint32 * 3), C.POINTER(C.c_uint32 * 3), C.POINTER(C.c_uint32 * 3)]
@@ -167,6 +174,35 @@ class EmuBatch:
         st, bad, cnt = (C.c_uint32 * n)(), (C.c_uint32 * n)(), (C.c_uint64 * n)()
         assert self.L.zgemu_exact(self.h, drain_rule, dict_len, prior_out, prior_reach, prior_counted, st, bad, cnt) == 0
         return [(st[i], bad[i], cnt[i]) for i in range(n)]
+
+    def total_out(self):
+        return max((sum(self.frame(f)[:2]) for f in range(self.nframes)), default=0)
+
+    def inorder_lz(self):
+        """zg_k_lz's source (zg_inorder.h, 256 threads) on every frame of this submit, as under ZGPU_FORCE_INORDER: (the output of all
+        frames, 0xAA where nothing was written; [(status, bad_block)] per frame)"""
+        n = self.nframes
+        buf, st, bad = C.create_string_buffer(self.total_out() + 1), (C.c_uint32 * n)(), (C.c_uint32 * n)()
+        assert self.L.zgemu_inorder_lz(self.h, buf, st, bad) == 0
+        return buf.raw[:-1], [(st[i], bad[i]) for i in range(n)]
+
+    def inorder_sparse(self):
+        """zg_k_sparse's source on the frames the plan marks sparse, their literal runs put in place first: (the output of all frames, 0xAA
+        where nothing was written — the matches of every frame that is not sparse; the number of sparse frames)"""
+        buf = C.create_string_buffer(self.total_out() + 1)
+        n = self.L.zgemu_inorder_sparse(self.h, buf)
+        return buf.raw[:-1], n
+
+    def inorder_partial(self, f, b, nexec, lits_of_next, limit, room):
+        """zg_k_partial's source on block b (index in the submit) of frame f: (the `room` bytes behind the frame's good blocks, 0xAA
+        where nothing was written; where they start in the frame's output; totals[5])"""
+        buf, at, left = C.create_string_buffer(room + 1), C.c_uint64(), C.c_uint32()
+        assert self.L.zgemu_inorder_partial(self.h, f, b, nexec, 1 if lits_of_next else 0, limit, room, buf, C.byref(at), C.byref(left)) == 0
+        return buf.raw[:room], at.value, left.value
+
+    def block_pad(self, b):
+        """1 + the sequence of block b that cannot be executed (zg_k_seqpost's model, or exact() where it decided); 0: none"""
+        return self.L.zgemu_block_pad(self.h, b)
 
     def block(self, b):
         a = (C.c_uint32 * 12)()

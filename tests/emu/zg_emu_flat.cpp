@@ -1,7 +1,8 @@
-// zg_emu_flat.cpp — TEST-ONLY: runs the SOURCE of the direct-unit flatten (zstd-rs_amd/csrc/zg_flat4.h, a body of zg_k_flatten)
-// on the CPU through the SIMT emulator of zg_simt.h, on the intermediates the harness of zg_emu.cpp produced for a submit
-// (host parser + table routines + serial model of the entropy stages). What comes out — the plaintext of the direct units — is
-// compared with the oracle by tests/test_flat4_cpu.py. Not part of the product; nothing here is linked into libzgpu.so.
+// zg_emu_flat.cpp — TEST-ONLY: runs the SOURCE of both bodies of zg_k_flatten (zstd-rs_amd/csrc/zg_flat4.h for direct units,
+// zg_flat1.h for pointer-mode units) and of zg_k_sparse (zg_inorder.h) on the CPU through the SIMT emulator of zg_simt.h, on the
+// intermediates the harness of zg_emu.cpp produced for a submit (host parser + table routines + serial model of the entropy
+// stages); zg_k_sweep is a plain model. What comes out — plaintext and scratch words — is compared with the oracle by
+// tests/test_flat4_cpu.py and tests/test_flat1_cpu.py. Not part of the product; nothing here is linked into libzgpu.so.
 #include <stdint.h>
 #include <string.h>
 #include <vector>
@@ -9,6 +10,7 @@
 #include "zg_simt.h"
 #include "../../zstd-rs_amd/csrc/zg_flat4.h"
 #include "../../zstd-rs_amd/csrc/zg_flat1.h"
+#include "../../zstd-rs_amd/csrc/zg_inorder.h"
 #include "zg_emu_batch.h"
 
 namespace {
@@ -35,7 +37,7 @@ extern "C" {
 //   dst_out   [total output bytes] the plaintext after the sweep
 //   og_out    [total output bytes] the flatten scratch (effective offsets; untouched words: 0xEEEEEEEE)
 //   unit_mode [units] 0 pointer, 1 no sequences, 2 direct; may be null
-// Frames marked sparse (no scratch): zg_flat1_unit places their literal runs, a model of zg_k_sparse copies their matches in order.
+// Frames marked sparse (no scratch): zg_flat1_unit places their literal runs, zg_sparse_frame (zg_inorder.h, the body of zg_k_sparse) copies their matches in order.
 int zgemu_flatten(void* h, int shape, uint8_t* dst_out, uint32_t* og_out, uint32_t* unit_mode) {
   EmuBatch* e = (EmuBatch*)h;
   const zg::BatchBuilder& bb = e->bb;
@@ -61,6 +63,7 @@ int zgemu_flatten(void* h, int shape, uint8_t* dst_out, uint32_t* og_out, uint32
   d.frame_out = fout.data(); d.dst = dst.data() + 256; d.dst_cap = total; d.totals = totals;
   d.units = bb.units.data(); d.nunits = nu; d.unit_info = uinfo.data();
   d.og = og.data(); d.og_words = total;
+  d.seq_blocks = bb.seq_blocks.data(); d.nseq_blocks = (uint32_t)bb.seq_blocks.size();
   // zg_k_lit: raw and RLE blocks and blocks without sequences are final before the flatten runs
   for (uint32_t b = 0; b < nb; b++) {
     const ZgBlock& blk = bb.blocks[b];
@@ -96,25 +99,12 @@ int zgemu_flatten(void* h, int shape, uint8_t* dst_out, uint32_t* og_out, uint32
     const uint64_t size = uinfo[u].size;
     if (fout[un.frame].err_packed != 0xFFFFFFFFu) { memcpy(dst.data() + 256 + at, e->dst.data() + at, size); continue; }
     uint8_t* o = dst.data() + 256 + at;
-    if (bb.frames[un.frame].sparse) {
-      // model of zg_k_sparse: zg_flat1_unit has put the literal runs in place; the matches follow in order
-      for (uint32_t k = 0; k < un.nblocks; k++) {
-        const uint32_t b = un.first_block + k;
-        const ZgBlock& blk = bb.blocks[b];
-        if (!e->pos[b].active) break;
-        if (blk.btype != ZG_BT_COMPRESSED || !blk.nseq) continue;
-        uint8_t* ob = dst.data() + 256 + e->fout[un.frame].out_base + e->pos[b].out_base;
-        for (uint32_t i = 0; i < blk.nseq; i++) {
-          const ZgSeq& q = seqs[blk.seq_base + i];
-          const uint32_t off = zg_sym_resolve(q.of, e->pos[b].hist_init), ml = ZG_SEQ_ML(q), md = ZG_SEQ_MDST(q);
-          for (uint32_t x = 0; x < ml; x++) ob[md + x] = *(ob + md + x - (int64_t)off);
-        }
-      }
-      continue;
-    }
+    if (bb.frames[un.frame].sparse) continue;                   // (zg_sparse_frame below)
     const uint32_t* w = og.data() + fout[un.frame].og_base + e->pos[un.first_block].out_base;
     for (uint64_t x = 0; x < size; x++) if (w[x]) o[x] = *(o + x - (int64_t)w[x]);
   }
+  // zg_k_sparse: the matches of the sparse frames, in order, behind the literal runs zg_flat1_unit has placed
+  for (uint32_t f = 0; f < nf; f++) simt::run(64, [&]() { zg_sparse_frame(d, f); });
   int first_status = 0;
   for (uint32_t f = 0; f < nf; f++) {
     if (fout[f].err_packed != 0xFFFFFFFFu) { if (!first_status) first_status = (int)(fout[f].err_packed & 0xFF); }

@@ -1,4 +1,5 @@
-// zg_simt.h — TEST-ONLY: a small SIMT emulator for kernels written against the zx_* primitives (zg_flat4.h). One workgroup
+// zg_simt.h — TEST-ONLY: a small SIMT emulator for kernels written against the zx_* primitives (zg_huf.h, zg_flat1.h, zg_flat4.h,
+// zg_exact.h, zg_inorder.h, zg_seektab.h, zg_seeksums.h). One workgroup
 // at a time; every GPU thread is a fiber (ucontext) that runs the kernel body verbatim and yields at workgroup barriers
 // and wave collectives; lanes of a wave are 64 consecutive threads. Deterministic (threads run in index order between
 // synchronisation points), so a data race does not show as flakiness here — what it checks is the kernel's logic, against
@@ -117,9 +118,23 @@ static inline uint32_t zx_shfl(uint32_t v, int l) {
   simt::yield(simt::WAVE_WAIT);
   return r;
 }
+static inline uint32_t zx_shfl_xor(uint32_t v, int x) {
+  simt::Machine* m = simt::M();
+  const uint32_t me = m->cur, w0 = me & ~63u;
+  m->slot[me] = v;
+  simt::yield(simt::WAVE_WAIT);
+  const uint32_t r = (uint32_t)m->slot[w0 + (((me & 63u) ^ (uint32_t)x) & 63u)];
+  simt::yield(simt::WAVE_WAIT);
+  return r;
+}
 static inline bool zx_any(bool p) { return zx_ballot(p) != 0ull; }
 // the lanes of a wave run one after the other here: what they wrote to LDS is complete for all of them behind this point
 static inline void zx_wave_sync() { (void)zx_ballot(true); }
+static inline void zx_cas_lds(uint32_t* p, uint32_t cmp, uint32_t v) { if (*p == cmp) *p = v; }
+// a no-op here: threads run one after the other up to the next collective or barrier, and every store has landed by then. What the
+// kernels need from it — a round's copies visible to the lanes that read them after the next collective — holds by construction
+static inline void zx_fence_block() {}
+static inline void zx_syncthreads() { simt::yield(simt::WG_WAIT); }
 static inline void zx_max_glb(uint32_t* p, uint32_t v) { if (v > *p) *p = v; }
 static inline void zx_gst128(void* p, const ZxU4& v) {
   if ((uintptr_t)p % 16) { fprintf(stderr, "simt: misaligned 16-byte global store\n"); abort(); }

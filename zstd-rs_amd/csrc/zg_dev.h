@@ -46,6 +46,17 @@ struct __attribute__((packed)) zg_u16u { uint16_t v; };
 ZG_HD uint64_t zg_ld64(const uint8_t* p) { return ((const zg_u64u*)p)->v; }
 ZG_HD uint32_t zg_ld32(const uint8_t* p) { return ((const zg_u32u*)p)->v; }
 ZG_HD uint32_t zg_ld16(const uint8_t* p) { return ((const zg_u16u*)p)->v; }
+// n bytes copied / filled by T threads together (thread t of T): 8 bytes at a time, then the tail
+ZG_HD void zg_wg_copy(uint8_t* dst, const uint8_t* src, uint64_t n, uint32_t t, uint32_t T) {
+  uint64_t n8 = n >> 3;
+  for (uint64_t i = t; i < n8; i += T) ((zg_u64u*)(dst + i * 8))->v = zg_ld64(src + i * 8);
+  for (uint64_t i = (n8 << 3) + t; i < n; i += T) dst[i] = src[i];
+}
+ZG_HD void zg_wg_fill(uint8_t* dst, uint8_t byte, uint64_t n, uint32_t t, uint32_t T) {
+  uint64_t v = 0x0101010101010101ull * byte, n8 = n >> 3;
+  for (uint64_t i = t; i < n8; i += T) ((zg_u64u*)(dst + i * 8))->v = v;
+  for (uint64_t i = (n8 << 3) + t; i < n; i += T) dst[i] = byte;
+}
 ZG_HD unsigned zg_hbit(uint32_t x) { return 32u - (unsigned)__builtin_clz(x); }  // highest_bit_set, x > 0
 
 // bits [lo, lo+n) of the stream seen as one little-endian integer, n <= 32, lo >= 0.

@@ -84,7 +84,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t zg_make_rsrc(const void* p, ui
 
 // ------------------------------------------------------------------------------------------------------------
 // The zx_* primitives: kernel bodies that also run under the CPU emulator (tests/emu/zg_simt.h) are written against them —
-// zg_huf.h (zg_k_huf), zg_flat4.h (direct units of zg_k_flatten), zg_exact.h (zg_k_exact).
+// zg_huf.h (zg_k_huf), zg_flat1.h and zg_flat4.h (zg_k_flatten), zg_exact.h (zg_k_exact), zg_inorder.h (zg_k_lz, zg_k_sparse,
+// zg_k_partial), zg_seektab.h (zg_k_seektab), zg_seeksums.h (zg_k_seeksums).
 // ------------------------------------------------------------------------------------------------------------
 #define ZX_DEV __device__ __forceinline__
 // "not needed": an offset no resource of the flatten covers (they are all far below 2^31 bytes). Not 0xFFFFFFFF: the compiler narrows
@@ -135,6 +136,12 @@ ZX_DEV ZxU4 zx_gld128(const void* p) { const zg_v4u v = *(const zg_gv4u*)p; ZxU4
 // what the lanes of a wave wrote to LDS is read by the other lanes afterwards (a wave runs in lockstep: no hardware barrier, but the
 // compiler must not move the reads ahead)
 ZX_DEV void zx_wave_sync() { zg_wave_publish(); }
+ZX_DEV uint32_t zx_shfl_xor(uint32_t v, int m) { return __shfl_xor(v, m, 64); }
+ZX_DEV void zx_cas_lds(uint32_t* p, uint32_t cmp, uint32_t v) { atomicCAS(p, cmp, v); }
+// what this thread stored to global memory is visible to the other threads of its workgroup (same CU, shared L1)
+ZX_DEV void zx_fence_block() { __threadfence_block(); }
+// workgroup barrier that also orders global memory: __syncthreads()
+ZX_DEV void zx_syncthreads() { __syncthreads(); }
 
 // ------------------------------------------------------------------------------------------------------------
 // zg_k_tables: Huffman tree descriptions of the literals sections (HuffmanTable::build_decoder, huff0_decoder.rs:117-124
@@ -1335,17 +1342,6 @@ __global__ void __launch_bounds__(1024) zg_k_scanf(ZgBatchDev d) {
 // compressed blocks without sequences (block_decoder.rs:184-194: the literals are the block). Literal runs of blocks
 // WITH sequences (DecodeBuffer::push, decode_buffer.rs:74-77) are placed by zg_k_flatten (flatten path) or zg_k_lz.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void zg_wg_copy(uint8_t* dst, const uint8_t* src, uint64_t n, uint32_t t, uint32_t T) {
-  uint64_t n8 = n >> 3;
-  for (uint64_t i = t; i < n8; i += T) ((zg_u64u*)(dst + i * 8))->v = zg_ld64(src + i * 8);
-  for (uint64_t i = (n8 << 3) + t; i < n; i += T) dst[i] = src[i];
-}
-__device__ __forceinline__ void zg_wg_fill(uint8_t* dst, uint8_t byte, uint64_t n, uint32_t t, uint32_t T) {
-  uint64_t v = 0x0101010101010101ull * byte, n8 = n >> 3;
-  for (uint64_t i = t; i < n8; i += T) ((zg_u64u*)(dst + i * 8))->v = v;
-  for (uint64_t i = (n8 << 3) + t; i < n; i += T) dst[i] = byte;
-}
-
 __global__ void __launch_bounds__(256) zg_k_lit(ZgBatchDev d) {
   if (d.totals[2]) return;
   const uint32_t b = blockIdx.x, t = threadIdx.x;
@@ -1606,123 +1602,16 @@ __global__ void __launch_bounds__(256) zg_k_fin(ZgBatchDev d) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// zg_k_lz: in-order execution (execute_sequences, sequence_execution.rs:5-54; DecodeBuffer::push / repeat,
-// decode_buffer.rs:74-141) for frames that left the flatten path (a block regenerating more than 128 KiB: not
-// conforming). One workgroup walks its frame. Positions are rebuilt here from the exact fields of the records
-// (ml, ll): a batch of ZG_LZ_T consecutive sequences is scanned, every lane places its literal run, then the matches
-// are resolved in rounds: a match is copied once all of its source bytes lie below the high-water mark (the
-// destination of the first match of the batch that is still pending); the first pending match always qualifies.
-// ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void zg_lane_match_copy(uint8_t* dst, uint32_t off, uint32_t ml) {
-  const uint8_t* src = dst - off;
-  uint32_t k = 0;
-  if (off >= 8) {
-    for (; k + 8 <= ml; k += 8) ((zg_u64u*)(dst + k))->v = zg_ld64(src + k);
-  }
-  for (; k < ml; k++) dst[k] = src[k];  // also the overlapping case (offset < match length): periodic extension
-}
-
+// The in-order kernels (zg_inorder.h): zg_k_lz, one workgroup per frame that left the flatten path; zg_k_sparse, one wave per frame
+// that has hardly any sequences; zg_k_partial, one wave for what a block wrote before its sequence execution failed (Batch::sync).
+#include "zg_inorder.h"
 __global__ void __launch_bounds__(ZG_LZ_T) zg_k_lz(ZgBatchDev d) {
-  __shared__ uint32_t s_min[ZG_LZ_T / 64];
-  __shared__ uint32_t s_so[ZG_LZ_T / 64], s_sl[ZG_LZ_T / 64];
-  __shared__ uint32_t s_err;
-  __shared__ uint32_t s_errblk;
-  if (d.totals[2]) return;
-  const uint32_t f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const ZgFrame fr = d.frames[f];
-  const ZgFrameOut fo = d.frame_out[f];
-  if (fo.fast) return;
-  uint8_t* frame_out = d.dst + fo.out_base;
-  if (t == 0) { s_err = 0; s_errblk = 0; }
-  __syncthreads();
-  for (uint32_t bi = 0; bi < fo.good_blocks; bi++) {
-    const uint32_t b = fr.first_block + bi;
-    const ZgBlock* blk = &d.blocks[b];
-    if (blk->btype != ZG_BT_COMPRESSED || blk->nseq == 0) continue;
-    const uint32_t nseq = blk->nseq;
-    const ZgBlockPos p = d.pos[b];
-    const ZgBlockSeqOut so = d.seq_out[b];
-    const ZgSeq* sq = d.seq_arena + blk->seq_base;
-    const uint8_t* body = d.src + blk->src_off;
-    const bool lit_rle = blk->lit_type == ZG_LT_RLE;
-    const uint8_t* lit = blk->lit_type <= ZG_LT_RLE ? body + blk->lit_off : d.lit_arena + blk->lit_base;
-    uint32_t carry_out = 0, carry_lit = 0;      // block-relative output position / literal index before the batch
-    for (uint32_t s0 = 0; s0 < nseq; s0 += ZG_LZ_T) {
-      const uint32_t i = s0 + t;
-      bool pending = false;
-      uint32_t off = 0, ml = 0, ll = 0, mdst = 0xFFFFFFFFu;
-      if (i < nseq) {
-        const ZgSeq q = sq[i];
-        const uint32_t nx = i + 1 < nseq ? ZG_SEQ_LIT(sq[i + 1]) : so.sum_ll;
-        ml = ZG_SEQ_ML(q); ll = (nx - ZG_SEQ_LIT(q)) & 0x1FFFFu;
-        off = zg_sym_resolve(q.of, p.hist_init);
-      }
-      // exclusive scans of ll + ml and ll over the batch
-      uint32_t io = ll + ml, il = ll;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t vo = __shfl_up(io, o, 64), vl = __shfl_up(il, o, 64);
-        if ((int)lane >= o) { io += vo; il += vl; }
-      }
-      if (lane == 63) { s_so[wv] = io; s_sl[wv] = il; }
-      __syncthreads();
-      uint32_t bo = carry_out, bl = carry_lit, to = carry_out, tl = carry_lit;
-      for (uint32_t w = 0; w < ZG_LZ_T / 64; w++) { if (w < wv) { bo += s_so[w]; bl += s_sl[w]; } to += s_so[w]; tl += s_sl[w]; }
-      const uint32_t lit_start = bl + il - ll;
-      uint64_t dpos = 0;  // frame-relative position of the match destination
-      if (i < nseq) {
-        mdst = bo + io - ml;
-        dpos = p.out_base + mdst;
-        uint8_t* o = frame_out + dpos - ll;
-        if (lit_rle) { const uint8_t v = lit[0]; for (uint32_t k = 0; k < ll; k++) o[k] = v; }
-        else { const uint8_t* s = lit + lit_start; for (uint32_t k = 0; k < ll; k++) o[k] = s[k]; }
-        if (off == 0) { atomicCAS(&s_err, 0u, (uint32_t)ZG_EXE_ZERO_OFFSET); }
-        else if ((uint64_t)off > dpos + fr.prior_reach + fr.dict_len || off >= ZG_OFF_HUGE - 2u) { atomicCAS(&s_err, 0u, (uint32_t)(dpos + fr.prior_out <= fr.window_size ? ZG_EXE_DICT_TOO_SMALL : ZG_EXE_OFFSET_TOO_BIG)); }
-        else pending = ml > 0;
-      }
-      carry_out = to; carry_lit = tl;
-      __syncthreads();
-      if (s_err) break;
-      for (uint32_t guard = 0;; guard++) {                       // (every round retires the first pending match at least: <= ZG_LZ_T rounds)
-        if (guard > ZG_LZ_T) { if (t == 0) s_err = ZG_INTERNAL; __syncthreads(); break; }
-        // high-water mark = smallest destination among pending matches of this batch
-        uint32_t m = pending ? mdst : 0xFFFFFFFFu;
-        for (int sh = 32; sh >= 1; sh >>= 1) { uint32_t o = __shfl_xor(m, sh, 64); m = o < m ? o : m; }
-        if (lane == 0) s_min[wv] = m;
-        __syncthreads();
-        uint32_t hwm = s_min[0];
-        for (int w = 1; w < ZG_LZ_T / 64; w++) hwm = s_min[w] < hwm ? s_min[w] : hwm;
-        if (hwm == 0xFFFFFFFFu) break;
-        if (pending) {
-          // source bytes that must already exist: [dpos - off, min(dpos - off + ml, dpos))
-          const int64_t src_end = (int64_t)dpos - (int64_t)off + (int64_t)ml;   // (<= 0: all of the source lies in front of the frame)
-          const uint64_t need_end = ml < off ? (src_end > 0 ? (uint64_t)src_end : 0ull) : dpos;
-          if (need_end <= p.out_base + hwm) {
-            zg_lane_match_copy(frame_out + dpos, off, ml);
-            pending = false;
-          }
-        }
-        __syncthreads();  // makes the copies visible to the other waves of this workgroup (same CU, shared L1)
-      }
-      __syncthreads();
-    }
-    if (s_err) { if (t == 0) s_errblk = bi; break; }
-    // trailing literals (sequence_execution.rs:40-44)
-    {
-      const uint32_t rest = blk->regen_size - so.sum_ll;
-      uint8_t* o = frame_out + p.out_base + ((uint64_t)so.sum_ll + so.sum_ml);
-      if (lit_rle) zg_wg_fill(o, lit[0], rest, t, ZG_LZ_T);
-      else zg_wg_copy(o, lit + so.sum_ll, rest, t, ZG_LZ_T);
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  if (t == 0 && s_err) {
-    d.frame_out[f].status = s_err;
-    d.frame_out[f].bad_block = s_errblk;
-    d.frame_out[f].good_blocks = s_errblk;
-  }
+  __shared__ ZgLzLds<ZG_LZ_T> s_l;
+  zg_lz_frame<ZG_LZ_T>(d, blockIdx.x, s_l);
+}
+__global__ void __launch_bounds__(64) zg_k_sparse(ZgBatchDev d) { zg_sparse_frame(d, blockIdx.x); }
+__global__ void __launch_bounds__(64) zg_k_partial(ZgBatchDev d, uint32_t f, uint32_t b, uint32_t nexec, uint32_t lits_of_next, uint32_t limit) {
+  zg_partial_block(d, f, b, nexec, lits_of_next, limit);
 }
 
 // Known-traffic kernels that calibrate the profiler's HBM byte counters per access pattern (tools/dev/profile.sh): the
@@ -2057,129 +1946,6 @@ void zg_launch_scan(const ZgBatchDev& d, hipStream_t s, uint32_t max_frame_block
 }
 void zg_launch_lit(const ZgBatchDev& d, hipStream_t s) {
   if (d.nblocks) hipLaunchKernelGGL(zg_k_lit, dim3(d.nblocks), dim3(256), 0, s, d);
-}
-// ------------------------------------------------------------------------------------------------------------
-// zg_k_sparse: the matches of a frame that has hardly any (literal-heavy data: a sequence or two in one block out of twenty).
-// zg_k_flatten has placed the literals and checked the offsets; what is left is a few hundred short copies per frame, which one
-// wave does in order (a match may copy from an earlier one) in the time of a few sweep launches — of which the frame would
-// need one per unit. One wave per frame, 64 sequences at a time, the same "copy what no pending match can still write"
-// rule as zg_k_lz.
-// ------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) zg_k_sparse(ZgBatchDev d) {
-  if (d.totals[2]) return;
-  const uint32_t f = blockIdx.x, lane = threadIdx.x;
-  const ZgFrame fr = d.frames[f];
-  if (!fr.sparse) return;
-  const ZgFrameOut fo = d.frame_out[f];
-  if (!fo.fast) return;                                        // the in-order path has it
-  const uint32_t stop = fo.err_packed == 0xFFFFFFFFu ? 0xFFFFFFFFu : fo.err_packed >> 8;   // zg_k_flatten found a sequence that cannot be executed: the blocks in front of its block are
-  uint8_t* frame_out = d.dst + fo.out_base;
-  for (uint32_t e = 0; e < fr.seq_count; e++) {
-    const uint32_t b = d.seq_blocks[fr.seq_first + e];
-    const ZgBlockPos p = d.pos[b];
-    if (!p.active || b - fr.first_block >= stop) break;
-    const ZgBlock* blk = &d.blocks[b];
-    const uint32_t nseq = blk->nseq;
-    const ZgSeq* sq = d.seq_arena + blk->seq_base;
-    for (uint32_t s0 = 0; s0 < nseq; s0 += 64) {
-      const uint32_t i = s0 + lane;
-      bool pending = false;
-      uint32_t off = 0, ml = 0, mdst = 0xFFFFFFFFu;
-      uint64_t dpos = 0;
-      if (i < nseq) {
-        const ZgSeq q = sq[i];
-        ml = ZG_SEQ_ML(q); mdst = ZG_SEQ_MDST(q);
-        off = zg_sym_resolve(q.of, p.hist_init);
-        dpos = p.out_base + mdst;
-        pending = ml > 0;
-      }
-      for (uint32_t guard = 0;; guard++) {                       // (every round retires the first pending match at least: <= 64 rounds)
-        if (guard > 64u) { if (lane == 0) d.frame_out[f].status = ZG_INTERNAL; return; }
-        uint32_t hwm = pending ? mdst : 0xFFFFFFFFu;            // the lowest destination a pending match of the batch still has to write
-        for (int sh = 32; sh >= 1; sh >>= 1) { const uint32_t o = __shfl_xor(hwm, sh, 64); hwm = o < hwm ? o : hwm; }
-        if (hwm == 0xFFFFFFFFu) break;
-        if (pending) {
-          // source bytes that must exist: [dpos - off, need_end). What lies in front of the frame (dictionary, earlier submits) exists.
-          const int64_t src_end = (int64_t)dpos - (int64_t)off + (int64_t)ml;
-          const uint64_t need_end = ml < off ? (src_end > 0 ? (uint64_t)src_end : 0ull) : dpos;
-          if (need_end <= p.out_base + hwm) { zg_lane_match_copy(frame_out + dpos, off, ml); pending = false; }
-        }
-        __threadfence_block();                                   // the copies are visible to the lanes that copy from them next
-      }
-    }
-  }
-}
-// ------------------------------------------------------------------------------------------------------------
-// zg_k_partial: what the reference's decode buffer holds of a block whose sequence EXECUTION failed. execute_sequences
-// (sequence_execution.rs:6-52) pushes a sequence's literals, then its match, one sequence after the other, and returns at the first one it
-// cannot execute: the output of the sequences in front of it stays in the buffer (and that sequence's literals, unless it was the
-// literals that ran out), where collect() / read() still find it after the Err. The fast path produces a block as a whole or not at
-// all; for the ONE block that failed, of a frame that is decoded run by run (FrameDecoder mirror, thin boundary, streaming decoder),
-// Batch::sync() runs this kernel: sequences [0, nexec) in order behind the bytes of the good blocks, plus the literals of sequence
-// nexec when lits_of_next is set. One wave, 64 sequences per round (zg_k_sparse's scheme: a match is copied once everything below the
-// lowest pending destination is final); an error path, at most 128 KiB.
-// ------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) zg_k_partial(ZgBatchDev d, uint32_t f, uint32_t b, uint32_t nexec, uint32_t lits_of_next, uint32_t limit) {
-  const uint32_t lane = threadIdx.x;
-  const ZgFrameOut fo = d.frame_out[f];
-  const ZgBlockPos p = d.pos[b];
-  const ZgBlock* blk = &d.blocks[b];
-  uint8_t* frame_out = d.dst + fo.out_base;
-  const ZgSeq* sq = d.seq_arena + blk->seq_base;
-  const uint8_t* body = d.src + blk->src_off;
-  const bool lit_rle = blk->lit_type == ZG_LT_RLE;
-  const uint8_t* lit = blk->lit_type <= ZG_LT_RLE ? body + blk->lit_off : d.lit_arena + blk->lit_base;
-  const uint32_t total = nexec + (lits_of_next ? 1u : 0u);          // sequences whose literals go out
-  // Positions are rebuilt from the exact fields of the records, as in zg_k_lz (a block beyond 128 KiB wraps the position fields): the
-  // literal run of sequence i is what lies between the end of sequence i - 1 and its match, (mdst_i - mdst_(i-1) - ml_(i-1)) mod 2^17.
-  // pass 0 only measures (the host has reserved `limit` bytes behind the run: more than that is not written at all), pass 1 executes.
-  for (int pass = 0; pass < 2; pass++) {
-    uint32_t carry = 0;                                              // block-relative end of the sequences in front of the batch
-    for (uint32_t s0 = 0; s0 < total; s0 += 64) {
-      const uint32_t i = s0 + lane;
-      bool pending = false;
-      uint32_t off = 0, ml = 0, ll = 0, lp = 0;
-      if (i < total) {
-        const ZgSeq q = sq[i];
-        uint32_t prev_end = 0;
-        if (i) { const ZgSeq pq = sq[i - 1]; prev_end = ZG_SEQ_MDST(pq) + ZG_SEQ_ML(pq); }
-        ll = (ZG_SEQ_MDST(q) - prev_end) & 0x1FFFFu;
-        lp = ZG_SEQ_LIT(q);
-        if (i < nexec) { ml = ZG_SEQ_ML(q); off = zg_sym_resolve(q.of, p.hist_init); }
-      }
-      uint32_t io = ll + ml;                                         // inclusive scan over the batch
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(io, o, 64); if ((int)lane >= o) io += v; }
-      const uint32_t start = carry + io - (ll + ml);                 // where this sequence's literals start
-      const uint32_t mdst = start + ll;                              // ... and its match
-      carry += __shfl(io, 63, 64);
-      if (pass == 0) continue;
-      uint64_t dpos = 0;
-      if (i < total) {
-        uint8_t* o = frame_out + p.out_base + start;
-        if (lit_rle) { const uint8_t v = lit[0]; for (uint32_t k = 0; k < ll; k++) o[k] = v; }
-        else for (uint32_t k = 0; k < ll; k++) o[k] = lit[lp + k];
-        dpos = p.out_base + mdst;
-        pending = i < nexec && ml > 0;
-      }
-      __threadfence_block();                                         // the literals are in place for the matches that copy from them
-      for (uint32_t guard = 0; guard <= 64u; guard++) {              // (every round retires the first pending match at least)
-        uint32_t hwm = pending ? mdst : 0xFFFFFFFFu;
-        for (int sh = 32; sh >= 1; sh >>= 1) { const uint32_t o2 = __shfl_xor(hwm, sh, 64); hwm = o2 < hwm ? o2 : hwm; }
-        if (hwm == 0xFFFFFFFFu) break;
-        if (pending) {
-          const int64_t src_end = (int64_t)dpos - (int64_t)off + (int64_t)ml;
-          const uint64_t need_end = ml < off ? (src_end > 0 ? (uint64_t)src_end : 0ull) : dpos;
-          if (need_end <= p.out_base + hwm) { zg_lane_match_copy(frame_out + dpos, off, ml); pending = false; }
-        }
-        __threadfence_block();
-      }
-    }
-    if (pass == 0) {
-      if (lane == 0) d.totals[5] = carry <= limit ? carry : 0xFFFFFFFFu;   // what the block leaves behind; 0xFFFFFFFF: more than was reserved, nothing written
-      if (carry > limit) return;
-    }
-  }
 }
 void zg_launch_partial(const ZgBatchDev& d, hipStream_t s, uint32_t frame, uint32_t block, uint32_t nexec, bool lits_of_next, uint32_t limit) {
   hipLaunchKernelGGL(zg_k_partial, dim3(1), dim3(64), 0, s, d, frame, block, nexec, lits_of_next ? 1u : 0u, limit);
