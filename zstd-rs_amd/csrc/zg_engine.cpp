@@ -687,11 +687,7 @@ int Batch::run() {
     fr0.hist_init[0] = fs->hist[0]; fr0.hist_init[1] = fs->hist[1]; fr0.hist_init[2] = fs->hist[2];
     ZG_HIP(hipMemcpyAsync((void*)d.frames, bb.frames.data(), sizeof(ZgFrame), hipMemcpyHostToDevice, s));
   }
-  ZG_HIP(hipMemsetAsync(d.status, 0, 3 * ((size_t)d.nblocks * 4 + 16), s));
-  ZG_HIP(hipMemsetAsync(d.huf_maxbits, 0, d.nhuf_slots + 16, s));
-  ZG_HIP(hipMemsetAsync(d.slot_log, 0, (size_t)d.nslots * 4, s));
-  ZG_HIP(hipMemsetAsync(d.totals, 0, 64, s));
-  if (d.dbg) ZG_HIP(hipMemsetAsync(d.dbg, 0, 8192, s));
+  zg_launch_reset(d, s);   // status words, slot logs, totals, d.dbg: one kernel (in front of the carried tables and dictionary fills, which write into what it clears)
   if (fs && fs->carry_mask) {   // tables carried into this run: the frame's carry slots of the two arenas
     const ZgFrame& fr = bb.frames[0];
     ZG_HIP(hipMemcpyAsync(d.fse_arena + (size_t)fr.carry_slot * ZG_FSE_SLOT_U32, fs->d_fse.p, ZG_FSE_SLOT_U32 * 4, hipMemcpyDeviceToDevice, s));
@@ -704,7 +700,6 @@ int Batch::run() {
   // state chains -> post-pass) of a block are independent, and all of these kernels are latency-bound chains that leave most
   // of the chip idle: the two chains run side by side on two streams and meet again in zg_k_merge.
   hipStream_t s2 = eng->stream2_;
-  ZG_HIP(hipMemsetAsync(d.totals + 3, 0, 4, s));   // "a match reaches beyond its frame's window" (zg_k_seqpost)
   zg_launch_tables(d, s, 1);
   ZG_HIP(hipEventRecord(ev[1], s));
   // The literals chain starts when the FSE tables are done, i.e. together with zg_k_seq: the dispatcher then places the

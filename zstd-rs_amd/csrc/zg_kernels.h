@@ -28,6 +28,7 @@ struct ZgSweepStep { uint32_t list_off, nunits, slices, pad; };
 // head_lds: unused LDS a head workgroup asks for (keeps the heads to a few workgroups per CU)
 struct ZgSweepTuning { uint32_t mode = 0, nbatch = 0, group = 16, head_lds = 52u * 1024u, head_nbatch = 0; };   // nbatch 0: chosen by zg_launch_sweep
 
+void zg_launch_reset(const ZgBatchDev& d, hipStream_t s);   // status words, table logs, totals (and d.dbg) to zero: the first kernel of a submit
 void zg_launch_tables(const ZgBatchDev& d, hipStream_t s, int part);   // part 0: Huffman trees, part 1: FSE tables
 void zg_launch_huf(const ZgBatchDev& d, hipStream_t s);
 void zg_launch_seq(const ZgBatchDev& d, hipStream_t s, bool packed);   // packed: 16-bit table entries, three workgroups per CU (submits of more blocks than one round holds)

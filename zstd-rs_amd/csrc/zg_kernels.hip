@@ -2,6 +2,7 @@
 //
 // Pipeline of one submit (two HIP streams; the host reads the frame sizes once, between zg_k_scanf and zg_k_lit):
 //   sequences chain (high-priority stream)
+//     zg_k_reset    a few workgroups           status words, table logs, totals -> 0
 //     zg_k_ftab     one wave per block         FSE table descriptions -> FSE arena (+ the predefined tables)
 //     zg_k_seq      decoder + mover wave per 16 blocks, four lanes per block
 //                                              the three FSE state chains of a block -> the states of every sequence (8 B)
@@ -100,6 +101,25 @@ ZX_DEV void zx_barrier() { zg_lds_barrier(); }
 ZX_DEV void zx_barrier_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); zg_lds_barrier(); }
 ZX_DEV unsigned long long zx_ballot(bool p) { return __ballot(p); }
 ZX_DEV uint32_t zx_shfl_up(uint32_t v, int o) { return __shfl_up(v, o, 64); }
+// Wave scans on DPP. (__shfl_up is ds_bpermute_b32: one 6-step scan of one value is 48 VALU, 6 LDS instructions and 6 dependent LDS
+// round trips; with DPP the shift is an operand modifier of the add: 6 VALU, no LDS.) A scan is four shifts inside the rows of 16 lanes
+// (row_shr:1/2/4/8), then lane 15 of rows 0 and 2 to all of rows 1 and 3 (row_bcast:15, row mask 0xA), then lane 31 to all of rows 2
+// and 3 (row_bcast:31, row mask 0xC). zx_scan_src<S>(v, fill): what a lane combines with at step S = 0..5 — the value of the lane that
+// step reads, `fill` where it reads none (bound_ctrl off: such a lane keeps `old`). zx_scan_takes<S>: whether the lane reads one. Every lane
+// of the wave must be active. (The builtin, not inline assembly: with fill = 0 the compiler folds the mov into v_add_u32_dpp.)
+template <int S> ZX_DEV uint32_t zx_scan_src(uint32_t v, uint32_t fill) {
+  static_assert(S >= 0 && S < 6, "six steps");
+  constexpr int ctrl = S < 4 ? 0x110 + (1 << S) : S == 4 ? 0x142 : 0x143, rows = S == 4 ? 0xA : S == 5 ? 0xC : 0xF;
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, ctrl, rows, 0xF, false);
+}
+template <int S> ZX_DEV bool zx_scan_takes(uint32_t lane) { return S < 4 ? (lane & 15u) >= (1u << S) : (lane & (S == 4 ? 16u : 32u)) != 0u; }
+ZX_DEV uint32_t zx_scan_incl_add(uint32_t v) {
+  v += zx_scan_src<0>(v, 0u); v += zx_scan_src<1>(v, 0u); v += zx_scan_src<2>(v, 0u); v += zx_scan_src<3>(v, 0u);
+  v += zx_scan_src<4>(v, 0u); v += zx_scan_src<5>(v, 0u);
+  return v;
+}
+// the value of the lane below (wave_shr:1); lane 0 gets `fill`
+ZX_DEV uint32_t zx_shr1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false); }
 ZX_DEV void zx_or_lds(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 ZX_DEV void zx_min_lds(uint32_t* p, uint32_t v) { atomicMin(p, v); }
 ZX_DEV void zx_min_lds64(unsigned long long* p, unsigned long long v) { atomicMin(p, v); }
@@ -634,15 +654,18 @@ struct ZgSeqChain {        // one lane's view of its block's chain
   int32_t pr;              // bit position + ring phase
   uint32_t e, s;           // the lane's table entry: baseline << 4 | state bits; all bits its symbol takes
   uint32_t st;             // the lane's state (what gets recorded)
-  uint32_t w0, w1, w2, w3, wlo;   // the window below the position and the bit address of its first dword plus 2^32 - 96... see zg_seq_window
+  uint32_t w0, w1, w2, w3, r0;    // the window below the position; the position's own bit in it: 96 + pr % 32 (see zg_seq_window)
 };
-// request the four dwords around the position and remember where they start
+// request the four dwords around the position and remember where in them the position is
 __device__ __forceinline__ void zg_seq_window(ZgSeqChain& c, const uint8_t* store4) {
   const uint32_t a = __builtin_amdgcn_ubfe((uint32_t)c.pr, 5u, 7u);
   const uint32_t* w = (const uint32_t*)(store4 + a * 4u);
   c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.w3 = w[3];
-  c.wlo = ((uint32_t)c.pr & ~31u) - 96u;
+  c.r0 = ((uint32_t)c.pr & 31u) | 96u;
 }
+// m ? a : b for a lane mask m (0 or ~0) held in a VGPR: v_bfi_b32. A v_cndmask needs its mask in SGPRs, and on gfx950 a VALU that reads
+// SGPRs a VALU has just written waits two more slots.
+__device__ __forceinline__ uint32_t zg_bfi(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }
 // One step of the chain. FAST: no checks (see above). Otherwise `act`, `left`, `cnt` are maintained and a finished or
 // failed block keeps its state.
 // PK (round 5): ONE 16-bit entry per state instead of a u16 and a u8 — [9:0] (baseline << 1) | (1 << state bits): a baseline is a multiple of
@@ -667,27 +690,41 @@ __device__ __forceinline__ void zg_seq_step(ZgSeqChain& c, const uint16_t* tab, 
                                             int32_t rbits, bool& act, uint32_t& left, uint32_t& cnt, const uint32_t to2 = 0, const uint32_t to1 = 0) {
   const uint32_t nb0 = PK ? (uint32_t)__builtin_ctz(c.e) : c.e & 15u;
   if (PK) c.s = c.e >> 10;
-  uint32_t nb = nb0, pk = c.s | (nb0 << 8);          // pk: [7:0] all bits this lane's symbol takes, [15:8] its state bits
-  if (!FAST) { const bool last = left == 1u; nb = last ? 0u : nb0; pk = last ? c.s - nb0 : pk; }   // no state update after the last sequence (:203)
-  // quad prefix sums, lanes in stream order from the low end: OF state, ML state, LL state (the extra bits above them are skipped as one count)
-  const uint32_t i1 = pk + (uint32_t)__builtin_amdgcn_mov_dpp((int)pk, 0x93, 0xF, 0xF, true);     // quad_perm [3,0,1,2]
-  const uint32_t incl = i1 + (uint32_t)__builtin_amdgcn_mov_dpp((int)pk, 0x4F, 0xF, 0xF, true);   // quad_perm [3,3,0,1]
-  const uint32_t tot = (uint32_t)__builtin_amdgcn_mov_dpp((int)incl, 0xAA, 0xF, 0xF, true) & 255u; // quad_perm [2,2,2,2]
-  const int32_t q = c.pr - (int32_t)tot;              // where the sequence ends
-  // this lane's nb state bits start (incl - pk) >> 8 bits above q; q >= position - 89, so they are inside the window
-  const uint32_t rel = (uint32_t)q - c.wlo + ((incl - pk) >> 8);
-  const bool up = rel >= 64u, odd = (rel & 32u) != 0u;
-  const uint32_t a0 = up ? c.w2 : c.w0, a1 = up ? c.w3 : c.w1, a2 = up ? c.w3 : c.w2;
-  const uint32_t d0 = odd ? a1 : a0, d1 = odd ? a2 : a1;
+  uint32_t nb = nb0, sb = c.s;                        // this lane's state bits; all bits its symbol takes
+  if (!FAST) { const bool last = left == 1u; nb = last ? 0u : nb0; sb = last ? c.s - nb0 : c.s; }   // no state update after the last sequence (:203)
+  // Quad sums over the lanes in stream order from the low end: OF state, ML state, LL state (the extra bits above them are skipped as one
+  // count); the spare lane holds zeros. (Round 7. Before: ONE prefix sum over nb << 8 | all bits — its three DPP moves had to wait for the
+  // packing, the total's move for the sum (two s_nop 1), and the two fields had to be taken apart again. Now the total is a butterfly over the
+  // bit counts as the table delivered them — DPP is an operand of its two adds — and the two moves of the state bits stand where the butterfly's
+  // second step would wait for its first. A DPP operand must be two instructions old: no s_nop is left in the unpacked form.)
+  const uint32_t t2 = sb + (uint32_t)__builtin_amdgcn_mov_dpp((int)sb, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+  const uint32_t e1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)nb, 0x93, 0xF, 0xF, true);           // quad_perm [3,0,1,2]: the lane below
+  const uint32_t e2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)nb, 0x4F, 0xF, 0xF, true);           // quad_perm [3,3,0,1]: the lane below that one
+  const uint32_t tot = t2 + (uint32_t)__builtin_amdgcn_mov_dpp((int)t2, 0x4E, 0xF, 0xF, true);     // quad_perm [2,3,0,1]: all bits of the sequence
+  // this lane's nb state bits start e1 + e2 bits above the sequence's end q = position - tot; q >= position - 89, so they are inside the
+  // window: 7 <= rel < 128
+  const uint32_t rel = c.r0 - tot + e1 + e2;
+  // bits 6 and 5 of rel as lane masks (v_bfe_i32). The empty asm makes them new to the compiler, which otherwise turns mask and v_bfi
+  // back into compare and select (ONE statement for both: behind an asm between the selects the compiler puts an s_nop)
+  uint32_t up = (uint32_t)__builtin_amdgcn_sbfe((int32_t)rel, 6u, 1u), odd = (uint32_t)__builtin_amdgcn_sbfe((int32_t)rel, 5u, 1u);
+  asm("" : "+v"(up), "+v"(odd));
+  const uint32_t a0 = zg_bfi(up, c.w2, c.w0), a1 = zg_bfi(up, c.w3, c.w1), a2 = zg_bfi(up, c.w3, c.w2);
+  const uint32_t d0 = zg_bfi(odd, a1, a0), d1 = zg_bfi(odd, a2, a1);
   const uint32_t bits = __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(d1, d0, rel), 0u, nb);
   const uint32_t st2 = PK ? ((c.e & 0x3FFu) >> 1) + bits - ((1u << nb0) >> 1) : (c.e >> 4) + bits;
   if (FAST) {
-    *rec = (uint16_t)c.st;
-    c.pr = q; c.st = st2;
+    // the table look-up is the chain: it is requested first, and everything that does not wait for it — the window's address and
+    // loads, the record — is issued behind it, while it is under way
+    const uint32_t st = c.st;
+    c.st = st2;
     c.e = ZG_SEQ_LD16(tab, st2); if (!PK) c.s = ZG_SEQ_LD8(xtab, st2);
+    __builtin_amdgcn_sched_barrier(0);
+    c.pr -= (int32_t)tot;                             // where the sequence ends
     zg_seq_window(c, store4);
+    *rec = (uint16_t)st;
     __builtin_amdgcn_sched_barrier(0);
   } else {
+    const int32_t q = c.pr - (int32_t)tot;            // where the sequence ends
     const bool ok = act && q >= rbits;                // :209-211
     rec[cnt * 4u] = (uint16_t)c.st;                   // (not recorded unless cnt advances)
     cnt += ok ? 1u : 0u;
@@ -698,7 +735,7 @@ __device__ __forceinline__ void zg_seq_step(ZgSeqChain& c, const uint16_t* tab, 
     n.pr = q; n.st = st2; n.e = ZG_SEQ_LD16(tab, st2); if (!PK) n.s = ZG_SEQ_LD8(xtab, st2);
     zg_seq_window(n, store4);
     __builtin_amdgcn_sched_barrier(0);
-    if (was) { c.pr = n.pr; c.wlo = n.wlo; c.w0 = n.w0; c.w1 = n.w1; c.w2 = n.w2; c.w3 = n.w3; }
+    if (was) { c.pr = n.pr; c.r0 = n.r0; c.w0 = n.w0; c.w1 = n.w1; c.w2 = n.w2; c.w3 = n.w3; }
     if (act) { c.st = n.st; c.e = n.e; c.s = n.s; }
   }
 }
@@ -947,6 +984,25 @@ __global__ void __launch_bounds__(128) zg_k_seq(ZgBatchDev d) {
 #define ZG_SP_T 256
 #define ZG_SP_S 8           // consecutive sequences per thread: the history inside them is stepped directly, only thread totals are scanned
 // (ZgHistMap, zg_map_identity, zg_map_apply, zg_map_compose: zg_dev.h, next to zg_hist_step; the CPU harness folds the same maps)
+// Inclusive scan of history maps over the wave (lane order = stream order), for zg_k_seqpost: the six DPP steps of
+// zx_scan_incl_add with zg_map_compose in place of the add. Composition does not commute: what a step reads covers the lanes right
+// below what the lane already holds, so it goes in front. A lane that reads nothing at a step gets the identity and keeps its map.
+template <int S> __device__ __forceinline__ void zg_map_scan_step(ZgHistMap& m, uint32_t lane) {
+  ZgHistMap pm;
+  pm.s[0] = zx_scan_src<S>(m.s[0], 1u << 30); pm.s[1] = zx_scan_src<S>(m.s[1], 2u << 30); pm.s[2] = zx_scan_src<S>(m.s[2], 3u << 30);
+  if (zx_scan_takes<S>(lane)) m = zg_map_compose(pm, m);
+}
+__device__ __forceinline__ ZgHistMap zg_map_scan_incl(ZgHistMap m, uint32_t lane) {
+  zg_map_scan_step<0>(m, lane); zg_map_scan_step<1>(m, lane); zg_map_scan_step<2>(m, lane); zg_map_scan_step<3>(m, lane);
+  zg_map_scan_step<4>(m, lane); zg_map_scan_step<5>(m, lane);
+  return m;
+}
+// the inclusive map of the lane below: what the lanes in front of this one did (lane 0: nothing)
+__device__ __forceinline__ ZgHistMap zg_map_shr1(const ZgHistMap& m) {
+  ZgHistMap r;
+  r.s[0] = zx_shr1(m.s[0], 1u << 30); r.s[1] = zx_shr1(m.s[1], 2u << 30); r.s[2] = zx_shr1(m.s[2], 3u << 30);
+  return r;
+}
 __global__ void __launch_bounds__(ZG_SP_T, 4) zg_k_seqpost(ZgBatchDev d) {
   __shared__ ZgHistMap s_wm[ZG_SP_T / 64];
   __shared__ uint32_t s_wl[ZG_SP_T / 64], s_wo[ZG_SP_T / 64], s_wx[ZG_SP_T / 64];
@@ -1011,9 +1067,7 @@ __global__ void __launch_bounds__(ZG_SP_T, 4) zg_k_seqpost(ZgBatchDev d) {
         P[j] = tx;
         tx += have ? of_code + (vl >> 24) + (vm >> 24) + upd : 0u;
       }
-      uint32_t sx = tx;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const uint32_t px = __shfl_up(sx, off, 64); if ((int)lane >= off) sx += px; }
+      const uint32_t sx = zx_scan_incl_add(tx);
       if (lane == 63) s_wx[wv] = sx;
       __syncthreads();
       uint32_t before = sx - tx, all = 0;
@@ -1061,24 +1115,10 @@ __global__ void __launch_bounds__(ZG_SP_T, 4) zg_k_seqpost(ZgBatchDev d) {
       tl += ll[j]; to += ll[j] + ml[j];
     }
     // inclusive scans over the wave of the thread totals
-    uint32_t sl = tl, so = to;
-    ZgHistMap sc = {{h0, h1, h2}};
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t pl = __shfl_up(sl, off, 64), po = __shfl_up(so, off, 64);
-      if ((int)lane >= off) { sl += pl; so += po; }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      ZgHistMap pm;
-      pm.s[0] = __shfl_up(sc.s[0], off, 64); pm.s[1] = __shfl_up(sc.s[1], off, 64); pm.s[2] = __shfl_up(sc.s[2], off, 64);
-      if ((int)lane >= off) sc = zg_map_compose(pm, sc);
-    }
+    const uint32_t sl = zx_scan_incl_add(tl), so = zx_scan_incl_add(to);
+    const ZgHistMap sc = zg_map_scan_incl(ZgHistMap{{h0, h1, h2}}, lane);
     if (lane == 63) { s_wm[wv] = sc; s_wl[wv] = sl; s_wo[wv] = so; }
-    // exclusive: what the lanes before this one did
-    ZgHistMap ex;
-    ex.s[0] = __shfl_up(sc.s[0], 1, 64); ex.s[1] = __shfl_up(sc.s[1], 1, 64); ex.s[2] = __shfl_up(sc.s[2], 1, 64);
-    if (lane == 0) ex = zg_map_identity();
+    const ZgHistMap ex = zg_map_shr1(sc);          // exclusive: what the lanes before this one did
     __syncthreads();
     ZgHistMap pre = carry, tot = carry;           // tot runs through the waves' maps; pre is its value in front of this wave
     uint32_t pl = lit_carry, po = out_carry, totl = lit_carry, toto = out_carry;
@@ -1225,6 +1265,8 @@ __global__ void __launch_bounds__(ZG_SCAN_T) zg_k_scan(ZgBatchDev d) {
       tmapl = zg_map_compose(tmapl, m[j]);
     }
     // inclusive scans over the threads of the chunk: inside the wave with shuffles, across the waves through LDS
+    // (round 7: the DPP scan of zg_k_seqpost was tried here and measured no faster — 55.3 .. 55.5 us before, 55.4 .. 57.0 with it: one wave
+    //  scan per pass of a kernel that is one memory round trip and four barriers long — so the shuffles stayed)
     uint64_t isz = tsum;
     ZgHistMap im = tmapl;
     {
@@ -1871,6 +1913,26 @@ void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* fr
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------
+// zg_k_reset: everything a submit's kernels expect to find zero, in ONE launch in front of them: the three status words of every block
+// (status, tab_status, lit_status: one array), the Huffman slots' max_bits, the FSE slots' logs, the totals and, in a run with timers, d.dbg.
+// (Until round 7 these were five fills on the critical stream, each a ~2 us kernel of its own with a launch gap behind it.)
+__global__ void __launch_bounds__(256) zg_k_reset(ZgBatchDev d) {
+  const uint32_t i0 = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  const uint32_t nst = 3u * (d.nblocks + 4u), nhb = d.nhuf_slots + 16u;     // dwords of the status arrays; BYTES of huf_maxbits
+  for (uint32_t i = i0; i < nst; i += step) d.status[i] = 0u;
+  for (uint32_t i = i0; i < nhb / 4u; i += step) ((uint32_t*)d.huf_maxbits)[i] = 0u;
+  if (i0 < (nhb & 3u)) d.huf_maxbits[(nhb & ~3u) + i0] = 0;
+  for (uint32_t i = i0; i < d.nslots; i += step) ((uint32_t*)d.slot_log)[i] = 0u;   // four logs per slot
+  if (i0 < 16u) d.totals[i0] = 0u;
+  if (d.dbg) for (uint32_t i = i0; i < 1024u; i += step) d.dbg[i] = 0ull;
+}
+void zg_launch_reset(const ZgBatchDev& d, hipStream_t s) {
+  uint32_t n = 3u * (d.nblocks + 4u);
+  if (d.nhuf_slots / 4u + 4u > n) n = d.nhuf_slots / 4u + 4u;
+  if (d.nslots > n) n = d.nslots;
+  const uint32_t wgs = (n + 255u) / 256u;
+  hipLaunchKernelGGL(zg_k_reset, dim3(wgs < 256u ? wgs : 256u), dim3(256), 0, s, d);
+}
 void zg_launch_tables(const ZgBatchDev& d, hipStream_t s, int part) {
   uint32_t n = d.nblocks + 1;
   if (part == 0) hipLaunchKernelGGL(zg_k_tables, dim3((n + ZG_HT_W - 1) / ZG_HT_W), dim3(64 * ZG_HT_W), 0, s, d);
