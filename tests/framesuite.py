@@ -111,17 +111,19 @@ def dev_context(monkeypatch, env):
         c.close()
 
 
-def submit(c, frames, oblocks=None, extra=()):
+def submit(c, frames, oblocks=None, extra=(), lit_direct=None):
     """frames in one submit, `extra` (more valid frames) behind them: parse_status, nframes, bad_status, total_out, every frame's
     out_size and bytes (from one read of the whole output and from b.frame_bytes); with oblocks (name -> the oracle's records, or a
     callable (name, zst)) nblocks and the per-block intermediates of every frame of `frames`, and without `extra` that these are all
-    the submit's blocks. Returns the out_base of every frame"""
+    the submit's blocks; with lit_direct (True / False) that the run decoded its literals after the scan, or did not
+    (b.lit_direct()). Returns the out_base of every frame"""
     every = [f[-3:] for f in list(frames) + list(extra)]
     b = c.prepare(b"".join(z for _, z, _ in every))
     try:
         assert b.parse_status == 0 and b.nframes == len(every)
         b.run()
         b.sync()
+        assert lit_direct is None or b.lit_direct() == lit_direct, ("literals after the scan", b.lit_direct())
         assert b.bad_status == 0, (b.bad_frame, b.bad_status)
         assert b.total_out == sum(len(p) for _, _, p in every)
         out = b.read(0, b.total_out) if b.total_out else b""
@@ -137,6 +139,32 @@ def submit(c, frames, oblocks=None, extra=()):
                 first += blockcheck.check_frame(b, first, ob, name)
             assert extra or first == b.nblocks
         return [fi.out_base for fi in info]
+    finally:
+        b.close()
+
+
+def submit_verdicts(c, frames, status, good, bad_block, lit_direct=None, parse_status=0):
+    """frames, invalid among valid, in one submit: an invalid frame (plaintext None) has the oracle's status[name], failing block
+    bad_block(name) and out_size, and holds good[name], the bytes of its good blocks; a valid one has status 0 and its plaintext;
+    with lit_direct (True / False) the run decoded its literals after the scan, or did not. parse_status: what the host's walk
+    finds in the last frame, where that frame is one that ends the walk"""
+    frames = [f[-3:] for f in frames]
+    b = c.prepare(b"".join(z for _, z, _ in frames))
+    try:
+        assert b.parse_status == parse_status and b.nframes == len(frames), (b.parse_status, b.nframes, len(frames))
+        b.run()
+        b.sync()
+        assert lit_direct is None or b.lit_direct() == lit_direct, ("literals after the scan", b.lit_direct())
+        wrong = []
+        for f, (name, _, plain) in enumerate(frames):
+            fi = b.frame_info(f)
+            if plain is None:
+                ok = (fi.status, fi.bad_block, fi.out_size) == (status[name], bad_block(name), len(good[name])) and b.frame_bytes(f) == good[name]
+            else:
+                ok = fi.status == 0 and b.frame_bytes(f) == plain
+            if not ok:
+                wrong.append((name, fi.status, fi.bad_block, fi.out_size))
+        assert not wrong, (len(wrong), wrong[:20])
     finally:
         b.close()
 

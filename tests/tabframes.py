@@ -513,7 +513,8 @@ def _bh(last, btype, size):
 
 
 def build(name, blocks, window_log=17, valid=True, differs=None):
-    """blocks: Block | ("raw", bytes) | ("rle", byte, n) | ("bytes", block content as it is: a compressed block, invalid frames).
+    """blocks: Block | ("raw", bytes) | ("rle", byte, n) | ("bytes", block content as it is: a compressed block, invalid frames) |
+    ("hdr", block type, size field, the bytes behind the header: a block header as it is, invalid frames).
     Returns (name, zst, plaintext or None). A valid frame is checked against the oracle (bytes and tables) and libzstd (differs: the
     caller's own list of frames libzstd does not return the plaintext for, in place of LIBZSTD_DIFFERS)."""
     fr = _Frame()
@@ -529,6 +530,8 @@ def build(name, blocks, window_log=17, valid=True, differs=None):
             z += _bh(last, 1, b[2]) + bytes([b[1]])
             flat_lits += bytes([b[1]]) * b[2]
             pending += b[2]
+        elif isinstance(b, tuple) and b[0] == "hdr":
+            z += _bh(last, b[1], b[2]) + b[3]
         elif isinstance(b, tuple):
             z += _bh(last, 2, len(b[1])) + b[1]
         else:

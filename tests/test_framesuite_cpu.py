@@ -115,3 +115,61 @@ def test_families():
     assert twice.family("a") and twice.family("b")
     with pytest.raises(AssertionError, match="frame names repeat"):
         twice.all_frames()
+
+
+class _Info:
+    def __init__(self, status, bad_block, out_size):
+        self.status, self.bad_block, self.out_size = status, bad_block, out_size
+
+
+class FakeContext:
+    """prepare() gives a batch that reports `table`: per frame (status, bad_block, bytes); lit_direct() reports `late`"""
+
+    def __init__(self, table, late=True, parse_status=0):
+        self.table, self.late, self.parse_status = table, late, parse_status
+
+    def prepare(self, src):
+        return FakeBatch(self)
+
+
+class FakeBatch:
+    def __init__(self, c):
+        self.c, self.parse_status, self.nframes = c, c.parse_status, len(c.table)
+
+    def run(self):
+        pass
+
+    sync = close = run
+
+    def lit_direct(self):
+        return self.c.late
+
+    def frame_info(self, f):
+        st, at, data = self.c.table[f]
+        return _Info(st, at, len(data))
+
+    def frame_bytes(self, f):
+        return self.c.table[f][2]
+
+
+def test_submit_verdicts():
+    """the one-submit check of invalid among valid frames passes on what the oracle says and fails on one wrong status, failing
+    block, size or byte, on a valid frame with a status or other bytes, on a walk that stopped, and on the other literals path"""
+    frames = [("f", "v0", b"z", b"plain"), ("f", "i0", b"z", None), ("v1", b"z", b"")]
+    status, good, at = {"i0": 33}, {"i0": b"good"}, {"i0": 2}
+    right = [(0, 0, b"plain"), (33, 2, b"good"), (0, 0, b"")]
+    framesuite.submit_verdicts(FakeContext(right), frames, status, good, at.get)
+    framesuite.submit_verdicts(FakeContext(right), frames, status, good, at.get, lit_direct=True)
+    framesuite.submit_verdicts(FakeContext(right, late=False), frames, status, good, at.get, lit_direct=False)
+    for f, entry in ((1, (34, 2, b"good")), (1, (33, 1, b"good")), (1, (33, 2, b"goo")), (1, (33, 2, b"gooD")), (1, (0, 0, b"good")),
+                     (0, (0, 0, b"plaiN")), (0, (33, 0, b"plain")), (2, (0, 0, b"x"))):
+        table = list(right)
+        table[f] = entry
+        with pytest.raises(AssertionError):
+            framesuite.submit_verdicts(FakeContext(table), frames, status, good, at.get)
+    with pytest.raises(AssertionError):
+        framesuite.submit_verdicts(FakeContext(right, parse_status=20), frames, status, good, at.get)
+    framesuite.submit_verdicts(FakeContext(right, parse_status=20), frames, status, good, at.get, parse_status=20)
+    for late in (False, True):
+        with pytest.raises(AssertionError):
+            framesuite.submit_verdicts(FakeContext(right, late=late), frames, status, good, at.get, lit_direct=not late)

@@ -58,8 +58,8 @@ def test_direct_literals(ctx, valid, oblocks):
     sequences / a must exceed b * loss_us + c, with loss_us = per_seq * the most sequences a block has (one round of chains: the
     submit has far fewer blocks with sequences than the 32 chains per CU). hufstreams.direct_rule and blockframes.loss_per_sequence
     read a, b, c and per_seq out of that source and fail if the rule has another form. All valid frames go in front; copies of the
-    131072-byte four-stream frame behind them bring the literals a tenth above what the rule asks for. The submit's flags are not
-    exported, so that the path was taken is not asserted here"""
+    131072-byte four-stream frame behind them bring the literals a tenth above what the rule asks for; b.lit_direct() says that the
+    path was taken"""
     import emu
     frames = [f[1:] for f in valid]
     per_us, factor, floor_us = hufstreams.direct_rule()
@@ -79,7 +79,7 @@ def test_direct_literals(ctx, valid, oblocks):
     need = 1.1 * per_us * (factor * per_seq * max_nseq + floor_us)
     reps = int((need - have) // len(filler[2])) + 1
     assert (have + reps * len(filler[2])) / per_us > factor * per_seq * max_nseq + floor_us and reps * len(filler[1]) < 1 << 27
-    framesuite.submit(ctx, frames, oblocks, extra=[filler] * reps)
+    framesuite.submit(ctx, frames, oblocks, extra=[filler] * reps, lit_direct=True)
 
 
 def test_decode_frames(ctx, valid, invalid):

@@ -41,8 +41,7 @@ def test_direct_literals(ctx, valid, oblocks):
     "literals after the scan?"; zg_engine.cpp sets the flag from it): lit_direct = gain_us > b * loss_us + c with gain_us = the
     Huffman literals of blocks without sequences / a, and loss_us = 0 in a submit without sequences. hufstreams.direct_rule reads
     a, b and c out of that source (2.5e6, 1.5 and 20: 50 MB) and fails if the rule has another form; the set is repeated until
-    it holds a tenth more literals than the rule asks for. The submit's flags are not exported, so that the path was taken is not
-    asserted here"""
+    it holds a tenth more literals than the rule asks for; b.lit_direct() says that the path was taken"""
     noseq = [f for f in valid if f[1].endswith("_n")]
     assert len(noseq) * 2 == len(valid)
     for _, name, _, _ in noseq:
@@ -56,6 +55,7 @@ def test_direct_literals(ctx, valid, oblocks):
         assert b.parse_status == 0 and b.nframes == len(noseq) * reps
         b.run()
         b.sync()
+        assert b.lit_direct()
         assert b.bad_status == 0, (b.bad_frame, b.bad_status)
         assert b.total_out == sum(len(p) for _, _, _, p in noseq) * reps
         out = b.read(0, b.total_out)

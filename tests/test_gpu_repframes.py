@@ -125,22 +125,4 @@ def test_invalid_frames_alone(ctx, invalid):
 def test_invalid_among_valid_in_one_submit(ctx, valid, invalid):
     """all invalid frames among valid ones in one submit: the oracle's status per frame, the failing block, the good blocks' bytes;
     every valid neighbour untouched"""
-    frames = _mixed(valid, invalid)
-    b = ctx.prepare(b"".join(z for _, _, z, _ in frames))
-    try:
-        assert b.parse_status == 0 and b.nframes == len(frames)
-        b.run()
-        b.sync()
-        wrong = []
-        for f, (_, name, _, plain) in enumerate(frames):
-            fi = b.frame_info(f)
-            if plain is None:
-                good = repframes.GOOD[name]
-                ok = (fi.status, fi.bad_block, fi.out_size) == (repframes.STATUS[name], repframes.META[name]["bad_block"], len(good)) and b.frame_bytes(f) == good
-            else:
-                ok = fi.status == 0 and b.frame_bytes(f) == plain
-            if not ok:
-                wrong.append((name, fi.status, fi.bad_block, fi.out_size))
-        assert not wrong, wrong
-    finally:
-        b.close()
+    framesuite.submit_verdicts(ctx, _mixed(valid, invalid), repframes.STATUS, repframes.GOOD, lambda name: repframes.META[name]["bad_block"])

@@ -93,6 +93,7 @@ Tuning Tuning::from_env() {
   num("ZGPU_RAMP", &t.ramp_percent, false);
   t.sparse_set = num("ZGPU_SPARSE_MAX", &t.sparse_max, false);
   if (is0("ZGPU_LIT_DIRECT")) t.lit_direct = 0;
+  else { const char* e = getenv("ZGPU_LIT_DIRECT"); if (e && e[0] == '1') t.lit_direct = 1; }
   { uint32_t v = 0; if (num("ZGPU_DIRECT_SHARE", &v, true) && v >= 10) t.direct_share10 = v; }
   t.debug_timers = getenv("ZGPU_DEBUG_TIMERS") != nullptr;
   { const char* e = getenv("ZGPU_FORCE_INORDER"); t.force_inorder = e && e[0] == '1'; }
@@ -531,6 +532,7 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
   b->bb.flat_slots = (uint32_t)cus_ * (flat_shape_ == 0 ? 1u : 2u);   // zg_k_flatten: workgroups the device holds at once
   b->bb.chain_slots = (uint32_t)cus_ * 32u;                            // zg_k_seq: blocks whose chains run at once
   if (tn.lit_direct == 0) b->bb.lit_direct_allowed = false;
+  b->bb.lit_direct_force = tn.lit_direct == 1;
   b->bb.seq_packed_force = tn.seq_packed;
   if (tn.direct_share10) b->bb.direct_share10 = tn.direct_share10;   // (measurement) tenths
   b->bb.finish();

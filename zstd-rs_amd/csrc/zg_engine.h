@@ -89,7 +89,7 @@ struct Tuning {
   uint32_t ramp_percent = 0;       // ZGPU_RAMP
   bool sparse_set = false;         // ZGPU_SPARSE_MAX given
   uint32_t sparse_max = 0;
-  int lit_direct = -1;             // ZGPU_LIT_DIRECT: 0 never, else the host's choice
+  int lit_direct = -1;             // ZGPU_LIT_DIRECT: 0 never, 1 always, else the host's choice
   uint32_t direct_share10 = 0;     // ZGPU_DIRECT_SHARE (tenths, >= 10)
   bool debug_timers = false;       // ZGPU_DEBUG_TIMERS
   bool force_inorder = false;      // ZGPU_FORCE_INORDER=1
@@ -168,6 +168,7 @@ class Batch {
   bool split_sweep = false;              // the last run used the split sweep: sync() checks that it was entitled to
   bool synced = false;                   // sync() ran after the last run(): outputs may be read
   uint32_t sweep_mode = 0;               // of the last run: 0 plain chain of steps, 1 split, 2 split and then repeated as a plain chain (tests)
+  bool lit_direct() const { return (dev.flags & ZG_FLAG_LIT_DIRECT) != 0u; }   // the last run decoded its Huffman literals after the scan (tests)
   int read_output(uint64_t off, uint8_t* dst, uint64_t n);   // D2H
   int read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s);
   const uint8_t* device_output() const { return dev.dst; }

@@ -374,6 +374,7 @@ void BatchBuilder::finish() {
     const uint64_t rounds = (nsb + slots - 1) / slots;
     const double gain_us = (double)huf_noseq / 2.5e6, loss_us = 0.12 * (double)max_nseq * (double)(rounds ? rounds : 1);
     lit_direct = lit_direct_allowed && gain_us > 1.5 * loss_us + 20.0;
+    if (lit_direct_force) lit_direct = true;
   }
   for (uint32_t i = 0; i < nb; i++) {
     ZgBlock& b = blocks[i];

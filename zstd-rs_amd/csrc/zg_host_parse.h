@@ -86,6 +86,7 @@ class BatchBuilder {
   // chain behind the sequences chain instead of beside it
   bool lit_direct = false;
   bool lit_direct_allowed = true;   // (ZGPU_LIT_DIRECT=0: measurement / tests)
+  bool lit_direct_force = false;    // (ZGPU_LIT_DIRECT=1, development build: tests) whatever the rule says
   uint32_t chain_slots = 8192;      // sequence chains the device runs at once (engine: CUs x 32)
   int seq_packed_force = -1;        // (ZGPU_SEQ_PACKED, development build) 0 / 1: never / always the packed form of zg_k_seq
   bool seq_packed = false;          // finish(): zg_k_seq runs in its packed-entry form (more blocks with sequences than one round holds)
