@@ -196,13 +196,14 @@ uint32_t zgpu_debug_frames_submits(const zgpu_ctx*);
  *    Bit 1 together with bit 0 is a contradiction: the call returns ZGPU_E_BAD_ARG and launches nothing. */
 #define ZGPU_DEVICE_NO_HASH 1u
 #define ZGPU_DEVICE_VERIFY 2u
-#define ZGPU_DEVICE_VERIFY_SEEK_TABLE 4u   /* zgpu_decode_ranges_seek_table_device_src only (see there); ZGPU_E_BAD_ARG on every other call */
+#define ZGPU_DEVICE_VERIFY_SEEK_TABLE 4u   /* the two decode calls that have a seek table only — zgpu_decode_ranges_seek_table_device_src (see there) and
+                                              zgpu_gather_ranges_seek_table_device_src; ZGPU_E_BAD_ARG on every other call */
 typedef struct {
   uint64_t hash_max_bytes;   /* frames whose plaintext is at most this long are hashed on the device; longer ones are not hashed.
                                 0: default 4 MiB — except under ZGPU_DEVICE_VERIFY, where 0 means no limit for frames that carry a checksum */
   uint32_t flags;            /* bit 0 (ZGPU_DEVICE_NO_HASH): hash no frame at all; bit 1 (ZGPU_DEVICE_VERIFY): a checksum mismatch fails the
                                 entry with ZGPU_E_CHECKSUM_MISMATCH and nothing of it is written; bit 2 (ZGPU_DEVICE_VERIFY_SEEK_TABLE): the seek table's
-                                checksums are enforced (zgpu_decode_ranges_seek_table_device_src only), hash_max_bytes == 0 means no limit */
+                                checksums are enforced (the calls that have a seek table only), hash_max_bytes == 0 means no limit */
   uint32_t pad;
 } zgpu_device_opts;
 typedef struct {
@@ -474,6 +475,52 @@ int zgpu_frames_seek_table_device(zgpu_ctx*, const void* const* device_srcs, con
 int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
                                              void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts_or_null,
                                              zgpu_range_result* results);
+
+/* ---- many byte ranges of few seekable entries, each frame decoded once ---------------------------------------------------------------------------
+ * A data loader pulls hundreds of records out of each of a few large seekable shards that sit in device memory. The calls above take one range
+ * per entry: every range scans its entry's table again, a frame that holds ten records is decoded ten times, and a frame's plaintext can reach
+ * only one destination. These two calls take n entries and m ranges, each range naming its entry (ranges[j].entry < n, pad = 0):
+ *  - every entry that a range of nonzero length names is located once (zg_k_seekmany_locate, one lane per entry; 32 bytes per entry come back,
+ *    no byte of a table) and its table is scanned ONCE into 64-bit exclusive prefix sums C[k], D[k], k = 0 .. nframes, in device scratch of
+ *    16 * (nframes + 1) bytes per entry (two launches, one wave per chunk of 2048 rows; ZGPU_E_NOMEM if the scratch cannot be had);
+ *  - every range finds its rows by binary search on D, one lane per range (zg_k_seekmany_find, one launch). zg_seekmany.h has the kernels.
+ * Selection. out[j], and results[j].seek, is the full record zgpu_frames_seek_table_device returns for (entry, begin, len) of range j — the
+ * rule above, one definition (zg_seektab.h): ZGPU_E_SEEK_TABLE and every why, ZGPU_SEEKTAB_PAST_TABLE decided per range from its own
+ * C_last + c_last > tab. A range of length 0 gives a record of zeros and reads no byte. A range with entry >= n or pad != 0 gets ZGPU_E_BAD_ARG
+ * in its record, as does one whose entry or (gather call, caps[j] > 0) destination is not device memory of this context's device; the other
+ * ranges are unaffected. An entry that no range of nonzero length names is neither checked nor read.
+ * Groups (the gather call). Of the ranges of ONE entry with status 0 and frames_taken > 0, those whose row intervals [frames_skipped,
+ * frames_skipped + frames_taken) share at least one row belong to one group, transitively. A group's rows are the union [gfirst, glast] of its
+ * ranges' intervals, and the group is decoded ONCE, exactly as zgpu_decode_ranges_seek_table_device_src decodes a selection of those rows:
+ * (src + C_gfirst, C_{glast + 1} - C_gfirst) is walked, cut into submits (a group is never split), gathered, decoded and hashed; it promises
+ * D_{glast + 1} - D_gfirst bytes; a frame that declares a size is held to it; dictionary frames and entries that go alone are served as there
+ * (a group that goes alone downloads its selection once, and every range's clipped bytes are uploaded to that range's destination).
+ * RANGES THAT SHARE A FRAME SHARE THE FATE OF EVERY FRAME OF THEIR GROUP: a defect in any frame of [gfirst, glast] fails every range of the
+ * group, also those that take no byte of that frame. The verdict of range j, in the rank order of the calls above:
+ *   1. the group's decode or walk error, or ZGPU_E_CONTENT_SIZE_MISMATCH (the group's total against the table's promise, declared sizes per frame);
+ *   2. ZGPU_E_TARGET_TOO_SMALL, by the range's OWN clipped count against its OWN caps[j]: a range that is too small does not disturb the
+ *      other ranges of its group;
+ *   3. the group's ZGPU_E_CHECKSUM_MISMATCH under ZGPU_DEVICE_VERIFY;
+ *   4. the group's ZGPU_E_SEEK_CHECKSUM_MISMATCH under ZGPU_DEVICE_VERIFY_SEEK_TABLE (rows [gfirst, glast] of the entry's table).
+ * written is the range's own clipped count; nframes and the checksum fields are the group's. A range that is alone in its group gets, field
+ * for field and byte for byte, what zgpu_decode_ranges_seek_table_device_src gives for it.
+ * Carried over: groups are isolated from each other, and the order of ranges and of entries does not matter; no byte of a failed range's
+ * destination is written, and none at or behind dst + written; every source and every destination with caps[j] > 0 and len > 0 is checked
+ * against the runtime's allocations before any launch; no lane reads outside [tab, lens[i]) of an entry during the selection, nor outside
+ * [src, src + lens[i]) at any time; the streams are synchronised on return; destinations that overlap each other or a source are undefined;
+ * all three option flags are accepted, with the contradictions they have on zgpu_decode_ranges_seek_table_device_src.
+ * Diagnostics: zgpu_debug_ranges_stats appends out[13] groups decoded, [14] prefix launches, [15] their microseconds (HIP events), [16] find
+ * launches, [17] their microseconds, [18] bytes of prefix scratch; out[0] - [2] are the locate pass (32 * entries + 64 * m bytes come
+ * back). [5] and [6], frames decoded and plaintext bytes decoded, count each GROUP once: a frame that ten ranges share is counted once. A
+ * caller that asks for 13 gets what it always got.
+ * Out of scope: a prefix handle cached across calls, a sibling for entries that declare sizes instead of carrying a table, a sibling for host
+ * sources, several GPUs, isolation of single rows inside a group. */
+typedef struct { uint64_t begin, len; uint32_t entry, pad; } zgpu_entry_range;   /* plaintext [begin, begin + len) of entry `entry` */
+int zgpu_frames_seek_table_many_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_entry_range* ranges,
+                                       uint32_t m, zgpu_seek* out /* m */);
+int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                             const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts /* m */,
+                                             const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

@@ -32,6 +32,9 @@ enum { kRangeStatSeekLaunches = 0, kRangeStatSeekUs, kRangeStatSeekBytesDownload
        kRangeStatFramesDecoded, kRangeStatPlaintextDecoded, kRangeStatBytesWritten,
        // ZGPU_DEVICE_VERIFY_SEEK_TABLE (zg_seeksums.h): zg_k_seeksums launches, their time, the bytes they brought back, frames compared, entries failed
        kRangeStatCompareLaunches, kRangeStatCompareUs, kRangeStatCompareBytesDownloaded, kRangeStatFramesCompared, kRangeStatEntriesFailedTable, kRangeStatCount };
+// what zgpu_debug_ranges_stats appends behind the slots above (out[13] ...): the calls that take many ranges per entry (zg_seekmany.h)
+enum { kManyStatGroupsDecoded = 0, kManyStatPrefixLaunches, kManyStatPrefixUs, kManyStatFindLaunches, kManyStatFindUs, kManyStatPrefixScratchBytes,
+       kManyStatCount };
 static_assert(kSrcStatWalkLaunches == zg::kPassLaunches && kSrcStatWalkUs == zg::kPassUs && kSrcStatSkeletonBytes == zg::kPassBytes &&
               kIndexStatLaunches == zg::kPassLaunches && kIndexStatKernelUs == zg::kPassUs && kIndexStatBytesDownloaded == zg::kPassBytes &&
               kRangeStatSeekLaunches == zg::kPassLaunches && kRangeStatSeekUs == zg::kPassUs && kRangeStatSeekBytesDownloaded == zg::kPassBytes,
@@ -50,7 +53,8 @@ struct zgpu_ctx {
   uint64_t frames_device_src_stats[kSrcStatCount] = {};   // the calls with device sources (zgpu_debug_frames_device_src_stats)
   uint64_t frames_index_stats[kIndexStatCount] = {};      // zgpu_frames_index_device / zgpu_frames_table_device (zgpu_debug_frames_index_stats)
   uint64_t ranges_stats[kRangeStatCount] = {};            // the seek and decode_ranges calls (zgpu_debug_ranges_stats)
-  uint64_t hash_ranges_us = 0;                            // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
+  uint64_t ranges_many_stats[kManyStatCount] = {};        //   the slots behind them (zgpu_frames_seek_table_many_device, zgpu_gather_ranges_seek_table_device_src)
+  uint64_t hash_ranges_us = 0;                           // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
 

@@ -274,6 +274,14 @@ class Engine {
   // seektab_pass — the same from the seekable format's seek table at each entry's end (zgpu_frames_seek_table_device /
   // zgpu_decode_ranges_seek_table_device_src): zg_k_seektab (zg_seektab.h), a wave per entry.
   int seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uint64_t* stats);
+  // seekmany_pass — m ranges over ne such entries, each table scanned ONCE (zgpu_frames_seek_table_many_device /
+  // zgpu_gather_ranges_seek_table_device_src; zg_seekmany.h): a locate pass (one lane per entry; 32 bytes per entry come back, from which the
+  // prefix scratch and the grids are sized), the two prefix launches, a find pass (one lane per range; out[j] = range j's record). ranges[j].entry
+  // indexes e; a range of rlen 0 reads nothing. The scratch — 16 * (nframes + 1) bytes of prefixes per entry with a usable table, plus its
+  // chunk totals — lives for the call; ZG_NOMEM if it cannot be had. locate's three kPass* slots go to stats, the rest to *more.
+  struct ManyRange { uint64_t begin, rlen; uint32_t entry; };
+  struct ManyStats { uint64_t prefix_launches = 0, prefix_us = 0, find_launches = 0, find_us = 0, scratch_bytes = 0; };
+  int seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* ranges, uint32_t m, zgk::Seek* out, uint64_t* stats, ManyStats* more);
   // hash_ranges_pass — XXH64 of ranges[0 .. n) of base (device memory the caller has checked) by the hash kernel `kernel` chooses
   // (zg_launch_xxh64_with); digests[i] is ranges[i]'s (zgpu_debug_hash_ranges).
   int hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats);

@@ -27,6 +27,11 @@
 // in zgpu_decode_all's order for such an entry — frame by frame (zg_decode_all_per_frame) — and what the submit cannot serve exactly (an
 // unregistered id, Unsupported / Internal: the dictionary splice behind a drain inside decode_all, zg_exact.h) goes alone as before.
 //
+// zgpu_gather_ranges_seek_table_device_src takes m ranges that each name one of n seekable entries (zg_seekmany.h: every table scanned once,
+// every range a binary search). The ranges of one entry whose table rows overlap form a group; a group is ONE entry of this file's machinery,
+// decoded once, and every range of it is a clip of the group's span (Ranges) with its own destination. The calls with one range per entry are
+// the case of spans of one clip.
+//
 // How a call is put together. A Call is what every call has (context, sources, lengths, destinations, capacities, the shared-dictionary
 // lookup) plus up to three parts that an entry point builds and hangs in: DeviceSink (device_sink: the options, the one place that refuses
 // ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY), DeviceSources (check_entries + device_sources: pointer checks, zg_k_walk, bounds) and Ranges
@@ -150,9 +155,14 @@ struct DeviceSources {
 };
 // ranges (zgpu_decode_ranges_device_src): the entries are the selections zg_k_seek found, and of the concatenation of an entry's decoded frames
 // only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
+// A sub-entry has a SPAN of clips, clip[first[i] .. first[i + 1]): each takes its own bytes to its own destination (the calls with one range
+// per entry have spans of one; zgpu_gather_ranges_seek_table_device_src one clip per range of a group). small / written: the clip's own verdict
+// and count once the sub-entry's frames are measured (Call::fit); they mean something only where the sub-entry stands at status 0.
 struct Ranges {
-  struct Clip { uint64_t skip, len, declared; };
+  struct Clip { uint64_t skip, len; uint8_t* dst; uint64_t cap; uint64_t written; bool small; };
   std::vector<Clip> clip;
+  std::vector<uint32_t> first;          // n + 1 slots
+  std::vector<uint64_t> declared;       // per sub-entry
   bool promise = false;                 // (zgpu_decode_ranges_seek_table_device_src) declared is the seek table's promise: it always holds
   uint64_t* stats = nullptr;            // zgpu_ctx::ranges_stats (kRangeStat*)
 };
@@ -177,12 +187,22 @@ struct Call {
       : c(ctx), srcs(s), lens(l), dsts(d), caps(cp), lookup{shared_find, ctx}, shared(ctx->frames_shared_dicts && !ctx->dicts.empty()) {}
   const DictLookup* dicts() const { return shared ? &lookup : nullptr; }
   uint64_t hash_max() const { return sink ? sink->hash_max : host_hash_max; }
-  // what of `bytes` decoded bytes of entry i its destination gets
-  uint64_t clipped(uint32_t i, uint64_t bytes) const {
-    if (!ranges) return bytes;
-    const Ranges::Clip& cl = ranges->clip[i];
-    const uint64_t rest = bytes > cl.skip ? bytes - cl.skip : 0;
-    return rest < cl.len ? rest : cl.len;
+  // What of `bytes` decoded bytes of entry i its destinations get, and *too_small: none of them has room. Ranges: every clip of the entry's
+  // span is measured by its own count against its own capacity (Clip::written, Clip::small); a clip that is too small gets nothing and
+  // does not disturb the others, and the entry as a whole is too small only if every clip is.
+  uint64_t fit(uint32_t i, uint64_t bytes, bool* too_small) const {
+    if (!ranges) { *too_small = bytes > caps[i]; return bytes; }
+    uint64_t sum = 0;
+    bool any = false;
+    for (uint32_t q = ranges->first[i]; q < ranges->first[i + 1]; q++) {
+      Ranges::Clip& cl = ranges->clip[q];
+      const uint64_t rest = bytes > cl.skip ? bytes - cl.skip : 0, w = rest < cl.len ? rest : cl.len;
+      cl.small = w > cl.cap;
+      cl.written = cl.small ? 0 : w;
+      if (!cl.small) { sum += w; any = true; }
+    }
+    *too_small = !any;
+    return sum;
   }
   zgpu_entry_result& result(uint32_t i) const { return sink ? sink->res[i].r : res[i]; }
 };
@@ -277,10 +297,10 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (!dev && fo[f].status) dev = (int)fo[f].status;
       bytes += fo[f].out_size;
-      if (has_dict[j] && !dev && !b->info[f].host_status && k.clipped(i, bytes) > k.caps[i]) small = true;
+      if (has_dict[j] && !k.ranges && !dev && !b->info[f].host_status && bytes > k.caps[i]) small = true;
       if (k.ranges && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
     }
-    if (k.ranges && k.ranges->promise && bytes != k.ranges->clip[i].declared) lied = true;   // (the selection yields another length than its seek table says)
+    if (k.ranges && k.ranges->promise && bytes != k.ranges->declared[i]) lied = true;  // (the selection yields another length than its seek table says)
     if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[kDictStatEntriesAlone] += has_dict[j]; continue; }
     if (k.ranges) { k.ranges->stats[kRangeStatFramesDecoded] += ff[j + 1] - ff[j]; k.ranges->stats[kRangeStatPlaintextDecoded] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
     // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
@@ -288,11 +308,14 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     // zgpu_decode_all's one submit reports a device error first, then the walk's, then TargetTooSmall.
     // (ranges have ONE order, with or without dictionary frames, in a submit or alone: the decode and walk verdicts, ContentSizeMismatch,
     // TargetTooSmall by the clipped count — taken in coordinates that the declared sizes define —, then the checksum verdict)
+    // (ranges with several clips: TargetTooSmall is each clip's own verdict, and the entry's only where no clip has room)
+    bool too_small = false;
+    const uint64_t fits = k.fit(i, bytes, &too_small);
     if (has_dict[j] && !k.ranges) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j] ? walk[j] : ZGPU_OK;
-    else r.status = dev ? dev : walk[j] ? walk[j] : lied ? ZGPU_E_CONTENT_SIZE_MISMATCH : k.clipped(i, bytes) > k.caps[i] ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
+    else r.status = dev ? dev : walk[j] ? walk[j] : lied ? ZGPU_E_CONTENT_SIZE_MISMATCH : too_small ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
     if (r.status) continue;
     if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[kDictStatFramesShared] += b->bb.frames[f].dict_len ? 1u : 0u;
-    r.written = k.clipped(i, bytes);
+    r.written = fits;
     r.nframes = ff[j + 1] - ff[j];
     const bool table_all = k.sink && k.sink->table_all && k.sink->table(i);   // (the seek table's checksums: every frame, with or without a Content_Checksum)
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
@@ -404,19 +427,38 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     for (uint32_t j = 0; j < n; j++) {
       const zgpu_entry_result& r = dres[idx[j]].r;
       if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
-      // (ranges: a frame's segment is clipped to [lo, hi) of the concatenation of the entry's frames; a clipped frame is just a shorter segment)
-      const Ranges::Clip* cl = k.ranges ? &k.ranges->clip[idx[j]] : nullptr;
-      const uint64_t lo = cl ? cl->skip : 0, hi = cl && cl->len < UINT64_MAX - lo ? lo + cl->len : UINT64_MAX;
-      uint64_t cat = 0, at = 0;
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-        const uint64_t a = cat, e = cat + fo[f].out_size, s = a > lo ? a : lo, t = e < hi ? e : hi;
-        cat = e;
-        if (s >= t) continue;
-        segs.push_back(zgs::Seg{fo[f].out_base + (s - a), (uint64_t)(uintptr_t)k.dsts[idx[j]] + at, t - s});
-        at += t - s;
+      // (ranges: a frame's segment is clipped to [lo, hi) of the concatenation of the entry's frames; a clipped frame is just a shorter segment.
+      // Every clip of the entry's span that has room takes its own segments to its own destination: the frames are in the output once)
+      const uint32_t q0 = k.ranges ? k.ranges->first[idx[j]] : 0, q1 = k.ranges ? k.ranges->first[idx[j] + 1] : 1;
+      uint64_t total = 0;
+      std::vector<uint64_t> ends;   // (several clips) where every frame ends in the concatenation: a clip starts at the frame a search finds
+      if (q1 - q0 > 1) {
+        uint64_t cat = 0;
+        for (uint32_t f = ff[j]; f < ff[j + 1]; f++) { cat += fo[f].out_size; ends.push_back(cat); }
       }
-      if (at != r.written || at > k.caps[idx[j]]) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
-      bytes += at;
+      for (uint32_t q = q0; q < q1; q++) {
+        const Ranges::Clip* cl = k.ranges ? &k.ranges->clip[q] : nullptr;
+        if (cl && cl->small) continue;
+        const uint64_t lo = cl ? cl->skip : 0, hi = cl && cl->len < UINT64_MAX - lo ? lo + cl->len : UINT64_MAX;
+        const uint64_t dst = (uint64_t)(uintptr_t)(cl ? cl->dst : k.dsts[idx[j]]), cap = cl ? cl->cap : k.caps[idx[j]];
+        uint32_t f0 = ff[j];
+        uint64_t cat = 0, at = 0;
+        if (!ends.empty()) {   // the first frame that ends behind lo
+          f0 = ff[j] + (uint32_t)(std::upper_bound(ends.begin(), ends.end(), lo) - ends.begin());
+          cat = f0 > ff[j] ? ends[f0 - ff[j] - 1] : 0;
+        }
+        for (uint32_t f = f0; f < ff[j + 1] && cat < hi; f++) {
+          const uint64_t a = cat, e = cat + fo[f].out_size, s = a > lo ? a : lo, t = e < hi ? e : hi;
+          cat = e;
+          if (s >= t) continue;
+          segs.push_back(zgs::Seg{fo[f].out_base + (s - a), dst + at, t - s});
+          at += t - s;
+        }
+        if ((cl && at != cl->written) || at > cap) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
+        total += at;
+      }
+      if (total != r.written) return ZGPU_E_INTERNAL;   // (never)
+      bytes += total;
     }
     if (segs.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
     return b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk);
@@ -566,7 +608,7 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
 // hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
 int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   DeviceSink& sink = *k.sink;
-  const Ranges::Clip* clip = k.ranges ? &k.ranges->clip[i] : nullptr;
+  const bool clip = k.ranges != nullptr;   // (the entry's span of clips: Call::fit, and the uploads below)
   std::vector<uint8_t> down;   // device sources: the entry comes to the host with one D2H (rare; correct first)
   if (k.src) {
     try { down.resize(k.lens[i] ? k.lens[i] : 1); } catch (...) { return ZGPU_E_NOMEM; }
@@ -594,10 +636,15 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   // that yields more than it declares can overflow it.
   if (clip && ok && d.r.status == ZGPU_E_TARGET_TOO_SMALL) fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
   if (clip && ok && !d.r.status &&
-      ((summed ? size_lies != 0 : clip->declared != UINT64_MAX && d.r.written != clip->declared) ||
-       (k.ranges->promise && d.r.written != clip->declared)))
+      ((summed ? size_lies != 0 : k.ranges->declared[i] != UINT64_MAX && d.r.written != k.ranges->declared[i]) ||
+       (k.ranges->promise && d.r.written != k.ranges->declared[i])))
     fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
-  if (clip && ok && !d.r.status && k.clipped(i, d.r.written) > k.caps[i]) fail_entry(d, ZGPU_E_TARGET_TOO_SMALL);
+  uint64_t fits = 0;   // (ranges) what the clips that have room get together
+  if (clip && ok && !d.r.status) {
+    bool too_small = false;
+    fits = k.fit(i, d.r.written, &too_small);
+    if (too_small) fail_entry(d, ZGPU_E_TARGET_TOO_SMALL);
+  }
   // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its one H2D
   if (ok && !d.r.status && sink.verify && summed && !sink.no_hash && d.r.checksum_mismatches) {
     sink.stats[kDevStatFramesHashed] += d.r.nframes;
@@ -636,14 +683,18 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
     const uint32_t nframes = d.r.nframes;
     if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
   }
-  size_t from = 0;   // ranges: only the clipped bytes are uploaded
+  // ranges: only the clipped bytes are uploaded, every clip of the span that has room to its own destination
   if (clip && ok && !d.r.status) {
-    const uint64_t w = k.clipped(i, d.r.written);
-    from = (size_t)(clip->skip < d.r.written ? clip->skip : d.r.written);
-    d.r.written = w;
+    const uint64_t decoded = d.r.written;
+    d.r.written = fits;
+    for (uint32_t q = k.ranges->first[i]; q < k.ranges->first[i + 1] && !st; q++) {
+      const Ranges::Clip& cl = k.ranges->clip[q];
+      const size_t from = (size_t)(cl.skip < decoded ? cl.skip : decoded);
+      if (!cl.small && cl.written && hipMemcpy(cl.dst, tmp + from, cl.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    }
   }
   if (ok && !d.r.status) {
-    if (d.r.written && hipMemcpy(k.dsts[i], tmp + from, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    if (!clip && d.r.written && hipMemcpy(k.dsts[i], tmp, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
     sink.alone_written += d.r.written;
     const bool hashed = summed && !sink.no_hash && d.r.nframes;
     if (sink.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
@@ -718,7 +769,7 @@ void reset_stats(zgpu_ctx* c, unsigned owned) {
   if (owned & kOwnsDevice) zero(c->frames_device_stats);
   if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
   if (owned & kOwnsIndex) zero(c->frames_index_stats);
-  if (owned & kOwnsRanges) zero(c->ranges_stats);
+  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); }
 }
 
 // The end of every call that launched something: nothing of it is in flight on the engine's two streams (the scatter ran on the second), so
@@ -729,7 +780,7 @@ int drain(zgpu_ctx* c, int st) {
 }
 
 // The device sink of a call, from its options. ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY (hash nothing, verify everything) is refused: *st.
-// ZGPU_DEVICE_VERIFY_SEEK_TABLE is refused the same way with ZGPU_DEVICE_NO_HASH, and on every call but the one that has a seek table (table).
+// ZGPU_DEVICE_VERIFY_SEEK_TABLE is refused the same way with ZGPU_DEVICE_NO_HASH, and on every call but the two that have a seek table (table).
 DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st, bool table = false) {
   const uint32_t flags = opts ? opts->flags : 0u;
   DeviceSink s;
@@ -1056,6 +1107,9 @@ int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* len
   std::vector<size_t> sub(n);
   Ranges rg;
   rg.clip.resize(n);
+  rg.declared.resize(n);
+  rg.first.resize((size_t)n + 1);   // (one range per entry: spans of one clip)
+  for (uint32_t i = 0; i <= n; i++) rg.first[i] = i;
   rg.promise = table;
   rg.stats = c->ranges_stats;
   src.dev.resize(n);
@@ -1069,7 +1123,8 @@ int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* len
     src.dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
     if (sink.table_flag) sink.table_verify[i] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[i], (uint64_t)lens[i], s.frames_skipped, none ? 0u : s.frames_taken};
     const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
-    rg.clip[i] = Ranges::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX};   // (table: an entry of which nothing is taken promises nothing)
+    rg.clip[i] = Ranges::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, (uint8_t*)device_dsts[i], caps[i], 0, false};
+    rg.declared[i] = none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX;   // (table: an entry of which nothing is taken promises nothing)
   }
   Call k(c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps);
   k.sink = &sink;
@@ -1102,7 +1157,176 @@ extern "C" int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx* c, const void*
                                                         const zgpu_device_opts* opts, zgpu_range_result* results) {
   return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, true);
 }
-extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->ranges_stats, out, n) : 0; }
+// ---- many ranges over few seekable entries (zg_seekmany.h) ------------------------------------------------------------------------------------
+static_assert(sizeof(zgpu_entry_range) == 24 && offsetof(zgpu_entry_range, entry) == 16, "include/zgpu.h");
+namespace {
+// Both calls up to the records. Every range is looked at on its own: entry >= n or pad != 0 refuses it (ZGPU_E_BAD_ARG in its record), a length
+// of 0 passes untouched, and an entry is checked — once — only when a range of nonzero length names it; an entry that fails the pointer check
+// refuses the ranges that name it, a destination that fails it refuses its own range. Then Engine::seekmany_pass over the entries that passed:
+// each table scanned once, every range a binary search. dsts / caps: nullptr for the seek call.
+int seek_many(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_entry_range* ranges, uint32_t m, void* const* dsts,
+              const size_t* caps, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  out->assign(m, zgk::Seek{});
+  refused->assign(m, 0);
+  std::vector<DevRange> known;
+  const int device = c->eng->device();
+  std::vector<uint8_t> seen(n, 0);   // 0: no range of nonzero length has named it yet, 1: passed, 2: refused
+  std::vector<uint32_t> live_of(n, 0);
+  std::vector<Engine::DevEntry> live;
+  std::vector<Engine::ManyRange> mr(m);
+  for (uint32_t j = 0; j < m; j++) {
+    const zgpu_entry_range& g = ranges[j];
+    mr[j] = Engine::ManyRange{g.begin, 0, 0};
+    if (g.entry >= n || g.pad) { (*refused)[j] = 1; continue; }
+    if (!g.len) continue;
+    const uint32_t i = g.entry;
+    if (!seen[i]) {
+      bool bad = !srcs[i] && lens[i];
+      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
+      seen[i] = bad ? 2 : 1;
+      if (!bad) { live_of[i] = (uint32_t)live.size(); live.push_back(Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)lens[i]}); }
+    }
+    bool bad = seen[i] == 2;
+    if (!bad && dsts) {
+      bad = !dsts[j] && caps[j];
+      if (!bad && caps[j]) bad = !check_device_range(device, dsts[j], caps[j], known);
+    }
+    if (bad) { (*refused)[j] = 1; continue; }
+    mr[j] = Engine::ManyRange{g.begin, g.len, live_of[i]};
+  }
+  Engine::ManyStats more;
+  const int st = drain(c, c->eng->seekmany_pass(live.data(), (uint32_t)live.size(), mr.data(), m, out->data(), c->ranges_stats, &more));
+  uint64_t* ms = c->ranges_many_stats;
+  ms[kManyStatPrefixLaunches] = more.prefix_launches; ms[kManyStatPrefixUs] = more.prefix_us;
+  ms[kManyStatFindLaunches] = more.find_launches; ms[kManyStatFindUs] = more.find_us; ms[kManyStatPrefixScratchBytes] = more.scratch_bytes;
+  if (st) return st;
+  for (uint32_t j = 0; j < m; j++) {
+    zgk::Seek& s = (*out)[j];
+    if ((*refused)[j]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
+    if (s.src_lo > s.src_hi || (ranges[j].len && s.src_hi > lens[ranges[j].entry]) || (s.status && s.status != (uint32_t)ZGPU_E_SEEK_TABLE)) {   // (never)
+      c->eng->last_error = "zgpu_frames_seek_table_many_device: a record that leaves its entry";
+      return ZGPU_E_INTERNAL;
+    }
+    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_frames_seek_table_many_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                  const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
+  reset_stats(c, kOwnsRanges);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = seek_many(c, device_srcs, lens, n, ranges, m, nullptr, nullptr, &recs, &refused);
+  for (uint32_t j = 0; j < m; j++) { if (st) memset(&out[j], 0, sizeof out[j]); else memcpy(&out[j], &recs[j], sizeof out[j]); }
+  return st;
+}
+
+// The ranges of one entry whose rows overlap form a GROUP, and a group is ONE sub-entry of decode_ranges' machinery — the rows [gfirst, glast]
+// its ranges take together: (src + C_gfirst, C_{glast + 1} - C_gfirst) is walked, cut into submits, gathered, decoded and hashed once, and
+// every range is a clip of the group's span with its own destination. What a group's frames do — a decode or walk error, a size that differs
+// from the table's promise, a checksum verdict — is the verdict of every range in it; TargetTooSmall is each range's own.
+extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                        const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  int st;
+  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  if ((st = seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, &recs, &refused))) return st;
+  // the groups: the ranges that take rows, sorted by (entry, first row, last row); one that begins at or in front of the last row of the group
+  // in front of it joins that group
+  std::vector<uint32_t> order;
+  for (uint32_t j = 0; j < m; j++)
+    if (!refused[j] && ranges[j].len && !recs[j].status && recs[j].frames_taken) order.push_back(j);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    const zgk::Seek& x = recs[a], & y = recs[b];
+    if (ranges[a].entry != ranges[b].entry) return ranges[a].entry < ranges[b].entry;
+    if (x.frames_skipped != y.frames_skipped) return x.frames_skipped < y.frames_skipped;
+    if (x.frames_taken != y.frames_taken) return x.frames_taken < y.frames_taken;
+    return a < b;
+  });
+  struct Group { uint32_t entry, gfirst, glast; uint64_t c_lo, c_hi, d_lo, d_hi; };
+  std::vector<Group> groups;
+  std::vector<uint32_t> group_of(m, 0), clip_of(m, 0);
+  Ranges rg;
+  rg.promise = true;
+  rg.stats = c->ranges_stats;
+  for (uint32_t j : order) {
+    const zgk::Seek& s = recs[j];
+    const uint32_t first = s.frames_skipped, last = s.frames_skipped + s.frames_taken - 1;
+    if (groups.empty() || groups.back().entry != ranges[j].entry || first > groups.back().glast) {
+      groups.push_back(Group{ranges[j].entry, first, last, s.src_lo, s.src_hi, s.plain_lo, s.plain_seen});
+      rg.first.push_back((uint32_t)rg.clip.size());
+    } else if (last > groups.back().glast) {
+      Group& g = groups.back();
+      g.glast = last; g.c_hi = s.src_hi; g.d_hi = s.plain_seen;
+    }
+    group_of[j] = (uint32_t)groups.size() - 1;
+    clip_of[j] = (uint32_t)rg.clip.size();
+    rg.clip.push_back(Ranges::Clip{ranges[j].begin - groups.back().d_lo, ranges[j].len, (uint8_t*)device_dsts[j], caps[j], 0, false});
+  }
+  rg.first.push_back((uint32_t)rg.clip.size());
+  const uint32_t G = (uint32_t)groups.size();
+  // the groups as the entries of the machinery; its own per-entry destinations are not used (every clip has its own)
+  std::vector<zgpu_device_entry_result> dres(G);
+  std::vector<const uint8_t*> srcs(G);
+  std::vector<size_t> sub(G), no_caps(G, 0);
+  std::vector<uint8_t*> no_dsts(G, nullptr);
+  DeviceSources src;
+  src.dev.resize(G);
+  src.refused.assign(G, 0);
+  rg.declared.resize(G);
+  sink.res = dres.data();
+  if (sink.table_flag) sink.table_verify.resize(G);
+  for (uint32_t g = 0; g < G; g++) {
+    const Group& gr = groups[g];
+    if (gr.c_lo > gr.c_hi || gr.d_lo > gr.d_hi) { c->eng->last_error = "zgpu_gather_ranges_seek_table_device_src: records of one table out of step"; return ZGPU_E_INTERNAL; }   // (never)
+    srcs[g] = (const uint8_t*)device_srcs[gr.entry] + gr.c_lo;
+    sub[g] = (size_t)(gr.c_hi - gr.c_lo);
+    src.dev[g] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[g], (uint64_t)sub[g]};
+    rg.declared[g] = gr.d_hi - gr.d_lo;
+    if (sink.table_flag) sink.table_verify[g] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[gr.entry], (uint64_t)lens[gr.entry], gr.gfirst, gr.glast - gr.gfirst + 1};
+  }
+  Call k(c, srcs.data(), sub.data(), no_dsts.data(), no_caps.data());
+  k.sink = &sink;
+  k.ranges = &rg;
+  st = device_sources(k, G, &src);
+  k.src = &src;
+  st = finish_device_call(k, G, st);
+  rg.stats[kRangeStatInputBytesToHost] = src.stats[kSrcStatInputBytesToHost];
+  rg.stats[kRangeStatBytesWritten] = sink.stats[kDevStatBytesScattered] + sink.alone_written;
+  c->ranges_many_stats[kManyStatGroupsDecoded] = G;
+  // every range's result: the group's, with the range's own count — or its own TargetTooSmall, which ranks behind the group's decode, walk
+  // and size verdicts and in front of its checksum verdicts
+  for (uint32_t j = 0; j < m; j++) {
+    memcpy(&results[j].seek, &recs[j], sizeof results[j].seek);
+    if (st) continue;
+    zgpu_device_entry_result& d = results[j].d;
+    if (refused[j] || recs[j].status) { d.r.status = refused[j] ? ZGPU_E_BAD_ARG : (int)recs[j].status; continue; }
+    if (!ranges[j].len || !recs[j].frames_taken) continue;   // (nothing is read, decoded or written: status 0, written 0)
+    const zgpu_device_entry_result& gd = dres[group_of[j]];
+    const Ranges::Clip& cl = rg.clip[clip_of[j]];
+    const bool checks = gd.r.status == ZGPU_E_CHECKSUM_MISMATCH || gd.r.status == ZGPU_E_SEEK_CHECKSUM_MISMATCH;
+    if (gd.r.status == ZGPU_E_TARGET_TOO_SMALL || ((!gd.r.status || checks) && cl.small)) { d.r.status = ZGPU_E_TARGET_TOO_SMALL; continue; }
+    d = gd;
+    if (!gd.r.status) d.r.written = cl.written;
+  }
+  return st;
+}
+
+extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c) return 0;
+  const int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others)
+  return k < (int)kRangeStatCount || !out ? k : k + copy_stats(c->ranges_many_stats, out + k, n - k);
+}
 
 extern "C" uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len) { return src || !len ? plaintext_bound(src, len) : 0; }
 extern "C" uint32_t zgpu_debug_frames_submits(const zgpu_ctx* c) { return c ? c->frames_submits : 0u; }

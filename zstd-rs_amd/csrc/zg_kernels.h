@@ -10,6 +10,7 @@
 #include "zg_seek.h"
 #include "zg_seektab.h"
 #include "zg_seeksums.h"
+#include "zg_seekmany.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -81,3 +82,9 @@ void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipSt
 // zg_k_seeksums (zg_seeksums.h): one wave per entry compares the Checksum fields of the entry's seek table with the digests the hash kernel wrote
 // (digests[0 .. ndig), device memory) for the entry's slice of frames; one 64-thread workgroup per entry, out[i] = entry i's 32-byte record
 void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, const uint64_t* digests, uint32_t ndig, zgv::Sums* out, hipStream_t s);
+// zg_seekmany.h: the seek tables of a few entries scanned once, many ranges answered from the prefix sums. locate: one lane per entry, out[i] =
+// what entry i's table frame is. prefix: two launches over the nw chunks of work — zg_k_seekmany_total, then zg_k_seekmany_prefix — that fill
+// pairs[], the scratch the host laid out. find: one lane per range, out[j] = range j's record
+void zg_launch_seekmany_locate(const zgm::Ent* ents, uint32_t n, zgm::Loc* out, hipStream_t s);
+void zg_launch_seekmany_prefix(const zgm::Work* work, uint32_t nw, zgm::Pair* pairs, hipStream_t s);
+void zg_launch_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out, hipStream_t s);

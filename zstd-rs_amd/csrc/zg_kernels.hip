@@ -1910,6 +1910,60 @@ void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* fr
   hipLaunchKernelGGL(zg_k_seeksums, dim3(n), dim3(zgv::kThreads), 0, s, lanes, n, frames, digests, ndig, out);
 }
 
+// Many ranges over few seekable entries (zg_seekmany.h has the passes, the scratch layout, the access bounds and the ISA notes): the tables are
+// scanned once into prefix sums, every range is a binary search. The host checked every [src, src + len) against the runtime's allocations,
+// sized the scratch from the located row counts and handed every wave and lane its indices into it.
+#include "zg_seekmany.h"
+struct ZgPairs {   // the prefix scratch: pairs of 64-bit sums, 16 bytes each, 16-byte aligned
+  uint64_t base;
+  __device__ __forceinline__ void ld(uint64_t i, uint64_t* c, uint64_t* d) const {
+    const zg_v4u v = *(const zg_gv4u*)(base + 16 * i);
+    *c = ((uint64_t)v.y << 32) | v.x; *d = ((uint64_t)v.w << 32) | v.z;
+  }
+  __device__ __forceinline__ uint64_t ld_d(uint64_t i) const { return *(const __attribute__((address_space(1))) uint64_t*)(base + 16 * i + 8); }
+  __device__ __forceinline__ void st(uint64_t i, uint64_t c, uint64_t d) const {
+    const zg_v4u w = {(uint32_t)c, (uint32_t)(c >> 32), (uint32_t)d, (uint32_t)(d >> 32)};
+    *(zg_gv4u*)(base + 16 * i) = w;
+  }
+};
+__global__ void __launch_bounds__(zgm::kThreads) zg_k_seekmany_locate(const zgm::Ent* ents, uint32_t n, zgm::Loc* out) {
+  const uint32_t i = blockIdx.x * zgm::kThreads + threadIdx.x;
+  if (i >= n) return;
+  const zgm::Ent e = ents[i];
+  zgm::seekmany_store_loc(&out[i], zgm::seekmany_locate(ZgTabRead{e.src}, e.len));
+}
+template <uint32_t CH> __global__ void __launch_bounds__(zgm::kThreads) zg_k_seekmany_total(const zgm::Work* work, uint32_t nw, zgm::Pair* pairs) {
+  const uint32_t i = blockIdx.x;
+  if (i >= nw) return;
+  const zgm::Work w = work[i];
+  zgm::seekmany_total<CH>(ZgTabRead{w.src}, ZgPairs{(uint64_t)(uintptr_t)pairs}, w);
+}
+template <uint32_t CH> __global__ void __launch_bounds__(zgm::kThreads) zg_k_seekmany_prefix(const zgm::Work* work, uint32_t nw, zgm::Pair* pairs) {
+  const uint32_t i = blockIdx.x;
+  if (i >= nw) return;
+  const zgm::Work w = work[i];
+  zgm::seekmany_prefix<CH>(ZgTabRead{w.src}, ZgPairs{(uint64_t)(uintptr_t)pairs}, w);
+}
+__global__ void __launch_bounds__(zgm::kThreads) zg_k_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out) {
+  const uint32_t j = blockIdx.x * zgm::kThreads + threadIdx.x;
+  if (j >= m) return;
+  const zgm::Find f = lanes[j];
+  zgt::seektab_store(&out[j], zgm::seekmany_find(ZgPairs{(uint64_t)(uintptr_t)pairs}, f));
+}
+void zg_launch_seekmany_locate(const zgm::Ent* ents, uint32_t n, zgm::Loc* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_seekmany_locate, dim3((n + zgm::kThreads - 1) / zgm::kThreads), dim3(zgm::kThreads), 0, s, ents, n, out);
+}
+void zg_launch_seekmany_prefix(const zgm::Work* work, uint32_t nw, zgm::Pair* pairs, hipStream_t s) {
+  if (!nw) return;
+  hipLaunchKernelGGL(zg_k_seekmany_total<zgm::kChunkRows>, dim3(nw), dim3(zgm::kThreads), 0, s, work, nw, pairs);
+  hipLaunchKernelGGL(zg_k_seekmany_prefix<zgm::kChunkRows>, dim3(nw), dim3(zgm::kThreads), 0, s, work, nw, pairs);
+}
+void zg_launch_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out, hipStream_t s) {
+  if (!m) return;
+  hipLaunchKernelGGL(zg_k_seekmany_find, dim3((m + zgm::kThreads - 1) / zgm::kThreads), dim3(zgm::kThreads), 0, s, lanes, m, pairs, out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

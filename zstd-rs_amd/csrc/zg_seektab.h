@@ -82,14 +82,10 @@ ZX_DEV uint64_t lane64(uint64_t v, uint32_t l) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-// What the wave of one entry does; every lane calls it and every lane gets the record. R reads the entry (ld1 / ld4 / ld8 at an offset counted
-// from the entry's first byte, any alignment; ld8 gives the two dwords of a table entry).
-template <class R> ZX_DEV zgk::Seek seektab_entry(const R& r, uint64_t len, uint64_t begin, uint64_t rlen) {
-  const uint32_t lane = zx_tid() & 63u;
-  zgk::Seek o;
-  o.src_lo = o.src_hi = o.plain_lo = o.bound = o.plain_seen = 0;
-  o.status = o.frames_skipped = o.frames_taken = o.nblocks = o.why = o.flags = 0;
-  if (!rlen) return o;
+// Checks 1 to 4 above, in that order, on the footer and the table frame's header: the `why` of a table that is not usable, else 0 and the
+// number of rows, their size and where the table frame begins. No wave primitive: a wave calls it with every lane (the loads are wave-uniform),
+// zg_seekmany.h's locate pass with one lane per entry. The rule's one definition.
+template <class R> ZX_DEV uint32_t seektab_locate(const R& r, uint64_t len, uint32_t* nframes, uint32_t* entry_size, uint64_t* table) {
   uint32_t why = 0, nf = 0, es = 8;
   uint64_t tab = 0;
   if (len < kFraming) why = kNone;
@@ -107,12 +103,49 @@ template <class R> ZX_DEV zgk::Seek seektab_entry(const R& r, uint64_t len, uint
       if (m != kSkipMagic || fs != (uint32_t)(size - 8)) why = kBadFrame;
     }
   }
+  *nframes = nf; *entry_size = es; *table = tab;
+  return why;
+}
+
+// The record of a range of nonzero length from what the search found (the rules above: no first, src_hi > tab, a why). c_lo / d_lo: C_first,
+// D_first; c_hi / d_hi: C_last + c_last, D_last + d_last; without a first all four are C_n, D_n. The record's one definition.
+ZX_DEV zgk::Seek seektab_record(uint32_t why, uint64_t tab, uint32_t nf, bool have_first, uint32_t first, uint32_t last, uint64_t c_lo,
+                                uint64_t d_lo, uint64_t c_hi, uint64_t d_hi) {
+  zgk::Seek o;
+  o.src_lo = o.src_hi = o.plain_lo = o.bound = o.plain_seen = 0;
+  o.status = o.frames_skipped = o.frames_taken = o.nblocks = o.why = o.flags = 0;
+  if (!why) {
+    if (c_hi > tab) why = kPastTable;
+    else {
+      o.src_lo = c_lo; o.src_hi = c_hi; o.plain_lo = d_lo; o.plain_seen = d_hi; o.bound = d_hi - d_lo;
+      o.frames_skipped = have_first ? first : nf; o.frames_taken = have_first ? last - first + 1 : 0u;
+      o.flags = have_first ? 0u : zgk::kNothing;
+    }
+  }
+  if (why) { o.status = kSeekTable; o.why = why; }
+  return o;
+}
+
+// What the wave of one entry does; every lane calls it and every lane gets the record. R reads the entry (ld1 / ld4 / ld8 at an offset counted
+// from the entry's first byte, any alignment; ld8 gives the two dwords of a table entry).
+template <class R> ZX_DEV zgk::Seek seektab_entry(const R& r, uint64_t len, uint64_t begin, uint64_t rlen) {
+  const uint32_t lane = zx_tid() & 63u;
+  if (!rlen) {
+    zgk::Seek o;
+    o.src_lo = o.src_hi = o.plain_lo = o.bound = o.plain_seen = 0;
+    o.status = o.frames_skipped = o.frames_taken = o.nblocks = o.why = o.flags = 0;
+    return o;
+  }
+  uint32_t nf = 0, es = 8;
+  uint64_t tab = 0;
+  const uint32_t why = seektab_locate(r, len, &nf, &es, &tab);
+  uint64_t cc = 0, cd = 0;                   // the sizes in front of this step
+  uint64_t c_lo = 0, d_lo = 0, c_hi = 0, d_hi = 0;
+  uint32_t first = 0, last = 0;
+  bool have_first = false, have_last = false;
   if (!why) {
     const uint64_t end = rlen > UINT64_MAX - begin ? UINT64_MAX : begin + rlen, ent = tab + 8;
-    uint64_t cc = 0, cd = 0;                   // the sizes in front of this step
-    uint64_t c_lo = 0, d_lo = 0, c_hi = 0, d_hi = 0;
-    uint32_t first = 0, last = 0, c = 0, d = 0;
-    bool have_first = false, have_last = false;
+    uint32_t c = 0, d = 0;
     if (lane < nf) r.ld8(ent + (uint64_t)lane * es, &c, &d);
     for (uint32_t base = 0; base < nf; base += 64) {
       uint32_t nc = 0, nd = 0;
@@ -140,17 +173,10 @@ template <class R> ZX_DEV zgk::Seek seektab_entry(const R& r, uint64_t len, uint
       cc = lane64(ce, 63); cd = lane64(de, 63);
       c = nc; d = nd;
     }
-    if (!have_first) { c_lo = cc; d_lo = cd; first = nf; }
+    if (!have_first) { c_lo = cc; d_lo = cd; }
     if (!have_last) { c_hi = cc; d_hi = cd; last = nf - 1; }
-    if (c_hi > tab) why = kPastTable;
-    else {
-      o.src_lo = c_lo; o.src_hi = c_hi; o.plain_lo = d_lo; o.plain_seen = d_hi; o.bound = d_hi - d_lo;
-      o.frames_skipped = first; o.frames_taken = have_first ? last - first + 1 : 0u;
-      o.flags = have_first ? 0u : zgk::kNothing;
-    }
   }
-  if (why) { o.status = kSeekTable; o.why = why; }
-  return o;
+  return seektab_record(why, tab, nf, have_first, first, last, c_lo, d_lo, c_hi, d_hi);
 }
 
 // the record leaves as four 16-byte stores (out: 16-byte aligned)

@@ -170,6 +170,11 @@ class RangeC(C.Structure):
     _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("anchor_src", C.c_uint64), ("anchor_plain", C.c_uint64)]
 
 
+class EntryRangeC(C.Structure):
+    """zgpu_entry_range (include/zgpu.h)"""
+    _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64), ("entry", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class SeekC(C.Structure):
     """zgpu_seek (include/zgpu.h)"""
     _fields_ = [("src_lo", C.c_uint64), ("src_hi", C.c_uint64), ("plain_lo", C.c_uint64), ("bound", C.c_uint64), ("plain_seen", C.c_uint64),
@@ -287,6 +292,7 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
@@ -372,6 +378,9 @@ def _declare(L):
     L.zgpu_debug_ranges_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_frames_seek_table_device.argtypes = L.zgpu_frames_seek_device.argtypes
     L.zgpu_decode_ranges_seek_table_device_src.argtypes = L.zgpu_decode_ranges_device_src.argtypes
+    L.zgpu_frames_seek_table_many_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(SeekC)]
+    L.zgpu_gather_ranges_seek_table_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
+                                                           P(RangeResultC)]
     L.zgpu_set_frames_shared_dicts.argtypes = [vp, C.c_int]
     L.zgpu_set_frames_shared_dicts.restype = None
     L.zgpu_frames_shared_dicts.argtypes = [vp]
@@ -813,6 +822,81 @@ class Context:
         compared). verify_table with no_hash raises E_BAD_ARG."""
         return self._decode_ranges("decode_ranges_seek_table_device_src", src_ptrs, lens, ranges, None, dst_ptrs, caps,
                                    _opts(hash_max, no_hash, verify, verify_table))
+
+    @staticmethod
+    def _entry_ranges(ranges):
+        """zgpu_entry_range[max(m, 1)] of m triples (entry, begin, len); a fourth element, if given, is the record's pad (tests)"""
+        m = len(ranges)
+        rg = (EntryRangeC * max(m, 1))()
+        for j, r in enumerate(ranges):
+            rg[j] = EntryRangeC(int(r[1]), int(r[2]), int(r[0]), int(r[3]) if len(r) > 3 else 0)
+        return rg
+
+    def frames_seek_table_many_device(self, src_ptrs, lens, ranges):
+        """zgpu_frames_seek_table_many_device: frames_seek_table_device for MANY ranges over few entries. ranges[j] = (entry, begin, len) names
+        its entry, an index into src_ptrs. Every entry's table is scanned once into prefix sums on the device and every range is a binary
+        search in them. Returns one Seek per range, each equal to what frames_seek_table_device gives for that entry and range; a range whose
+        entry is out of range gets E_BAD_ARG in its record, the others are unaffected."""
+        n, m = len(src_ptrs), len(ranges)
+        _one_per("frames_seek_table_many_device", n, lens)
+        out = (SeekC * max(m, 1))()
+        self._check(self.L.zgpu_frames_seek_table_many_device(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m, out))
+        return [Seek(c) for c in out[:m]]
+
+    def gather_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
+                                            verify_table=False):
+        """zgpu_gather_ranges_seek_table_device_src: plaintext bytes ranges[j] = (entry, begin, len) of seekable entries in device memory,
+        range j to dst_ptrs[j] (caps[j] bytes of device memory). The tables are scanned once, and ranges of one entry whose table rows overlap
+        form a group whose frames are decoded ONCE, however many ranges take bytes of them. Ranges that share a frame share the fate of every
+        frame of their group (a decode error, a size that differs from the table's promise, a checksum verdict); E_TARGET_TOO_SMALL is each
+        range's own. A range alone in its group gets what decode_ranges_seek_table_device_src gives for it. The options are that call's.
+        Returns (results, seeks): one DeviceEntryResult and one Seek per range."""
+        n, m = len(src_ptrs), len(ranges)
+        _one_per("gather_ranges_seek_table_device_src", n, lens)
+        _one_per("gather_ranges_seek_table_device_src", m, dst_ptrs, caps)
+        res = (RangeResultC * max(m, 1))()
+        self._check(self.L.zgpu_gather_ranges_seek_table_device_src(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m,
+                                                                    _ptr_array(dst_ptrs), _size_array(caps),
+                                                                    C.byref(_opts(hash_max, no_hash, verify, verify_table)), res))
+        return _results(res, m), [Seek(res[j].seek) for j in range(m)]
+
+    # the slots zgpu_debug_ranges_stats appends behind _STATS["Context.ranges_stats"] (csrc/zg_capi_int.h: kManyStat*, an enumeration of its own)
+    GATHER_STATS = ("groups_decoded", "prefix_launches", "prefix_us", "find_launches", "find_us", "prefix_scratch_bytes")
+
+    def gather_ranges_stats(self):
+        """ranges_stats(verify_table=True) of the last call plus the slots zgpu_debug_ranges_stats appends for the calls that take many ranges
+        per entry (out[13] ...): groups_decoded, prefix_launches, prefix_us, find_launches, find_us (HIP events), prefix_scratch_bytes.
+        frames_decoded and plaintext_decoded count each group once."""
+        keys = _STATS["Context.ranges_stats"][2] + self.GATHER_STATS
+        a = (C.c_uint64 * len(keys))()
+        k = self.L.zgpu_debug_ranges_stats(self.h, a, len(keys))
+        return dict(zip(keys[:k], a[:k]))
+
+    def gather_tensor_ranges(self, tensors, ranges, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False):
+        """gather_ranges_seek_table_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding
+        seekable shard i, ranges[j] = (entry, begin, len) the record wanted of shard `entry`. A frames_seek_table_many_device call of its own
+        sizes the destinations by min(len, seek.bound), so no byte of the input crosses to the host. The bytes go to ONE new torch.uint8
+        tensor. Returns (tensors, results, seeks) — tensors[j] a view of range j's 256-byte aligned slot cut to `written` bytes (empty unless
+        status == 0) — or, packed=True, (buffer, offsets, results, seeks): the slots back to back without padding, range j at
+        buffer[offsets[j]:offsets[j + 1]] (a failed range's slot keeps its room and holds nothing of the range). Same single-runtime rule as
+        decode_tensors. torch is imported here, not by `import zgpu`."""
+        self._tensor_check(tensors, "gather_tensor_ranges")
+        ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
+        seeks = self.frames_seek_table_many_device(ptrs, lens, ranges)
+        caps = [min(int(r[2]), s.bound) for r, s in zip(ranges, seeks)]
+        if packed:
+            offs = [0]
+            for cp in caps:
+                offs.append(offs[-1] + cp)
+            buf, _, base = self._slot_tensor([offs[-1]])
+            dsts = [base[0] + o for o in offs[:-1]]
+        else:
+            buf, offs, dsts = self._slot_tensor(caps)
+        res, seeks = self.gather_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify,
+                                                              verify_table=verify_table)
+        if packed:
+            return buf[:offs[-1]], offs, res, seeks
+        return self._views(buf, offs, res), res, seeks
 
     def ranges_stats(self, verify_table=False):
         """the last frames_seek_device / decode_ranges_device_src call or seek-table call (zgpu_debug_ranges_stats). verify_table=True: with the
