@@ -78,6 +78,10 @@ enum zgpu_status {
    * zgpu_decode_ranges_seek_table_device_src called with ZGPU_DEVICE_VERIFY_SEEK_TABLE gets it: the entry decoded, and its seek table does not
    * vouch for the bytes — a frame's XXH64 differs from the table's Checksum, a decoded frame matches no table row, or the table has no checksums. */
   ZGPU_E_SEEK_CHECKSUM_MISMATCH = 73,
+  /* No counterpart in the reference. Only an entry of a zgpu_seek_index, and the ranges that name it, get it: the entry's header chain yields
+   * no index; zgpu_seek_index_info.why says why — a ZGPU_CHAIN_* reason (the chain broke), ZGPU_INDEX_UNSIZED (a zstd frame declares no
+   * Frame_Content_Size) or ZGPU_SEEKTAB_TOO_LARGE (more than 2^27 rows). */
+  ZGPU_E_FRAME_INDEX = 74,
   /* Input the reference tolerates but this engine rejects. No conforming encoder produces any of it:
    *  - offsets >= 2^30 (offset codes 30, 31) while >= 1 GiB of the frame is held undrained (FrameDecoder::decode_blocks(All) on a
    *    frame beyond 1 GiB that nobody reads from): ZGPU_E_UNSUPPORTED. With less than 1 GiB held — always the case in decode_all
@@ -513,14 +517,81 @@ int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx*, const void* const* devic
  * launches, [17] their microseconds, [18] bytes of prefix scratch; out[0] - [2] are the locate pass (32 * entries + 64 * m bytes come
  * back). [5] and [6], frames decoded and plaintext bytes decoded, count each GROUP once: a frame that ten ranges share is counted once. A
  * caller that asks for 13 gets what it always got.
- * Out of scope: a prefix handle cached across calls, a sibling for entries that declare sizes instead of carrying a table, a sibling for host
- * sources, several GPUs, isolation of single rows inside a group. */
+ * Out of scope: a sibling for host sources, several GPUs, isolation of single rows inside a group. (A prefix handle cached across calls, and
+ * entries that declare sizes instead of carrying a table: zgpu_seek_index, below.) */
 typedef struct { uint64_t begin, len; uint32_t entry, pad; } zgpu_entry_range;   /* plaintext [begin, begin + len) of entry `entry` */
 int zgpu_frames_seek_table_many_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_entry_range* ranges,
                                        uint32_t m, zgpu_seek* out /* m */);
 int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n,
                                              const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts /* m */,
                                              const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
+
+/* ---- seek index handles: index a shard once, seek and gather any number of times -----------------------------------------------------------
+ * A zgpu_seek_index holds, per entry, the 64-bit exclusive prefix sums C[k], D[k], k = 0 .. nrows, of the entry's rows in DEVICE memory:
+ * row k is the entry's k-th frame (zstd or skippable), c_k its compressed bytes, d_k its plaintext bytes. The two calls above compute these
+ * pairs from a seek table and throw them away on return; the handle keeps them, and can also build them for entries WITHOUT a seek table
+ * whose frames declare their Frame_Content_Size (what ZSTD_compress writes): the common shard of one frame per record.
+ * Building (zgpu_seek_index_create_device). Every entry with lens[i] > 0 passes the pointer check of the device-source calls before any
+ * launch; one that fails has status ZGPU_E_BAD_ARG in its info, the others are unaffected; the return value reports engine failures only
+ * (ZGPU_E_NOMEM, ZGPU_E_HIP, ZGPU_E_INTERNAL: nothing is left behind, *out = NULL).
+ *  - ZGPU_INDEX_SEEK_TABLE: the locate, total and prefix passes of zg_seekmany.h; the pairs and what locate found (tab, nrows) are kept. An
+ *    unusable table: ZGPU_E_SEEK_TABLE, why = ZGPU_SEEKTAB_*.
+ *  - ZGPU_INDEX_DECLARED: the summary pass of zgpu_frames_index_device, then zg_k_seekidx_rows (zg_seekidx.h), one lane per entry: every frame
+ *    record of the header chain is a row, d_k = its declared Frame_Content_Size (the 2-byte form's + 256 included; 0 for a skippable frame;
+ *    a seek table at the entry's end is one more skippable row). Indexable: the chain reached the entry's end and every zstd frame declares
+ *    a size. Else ZGPU_E_FRAME_INDEX with why = the ZGPU_CHAIN_* reason, ZGPU_INDEX_UNSIZED, or ZGPU_SEEKTAB_TOO_LARGE (more than 2^27
+ *    rows). An entry of length 0 is a valid index without rows. The host accepts the pairs only where C[nrows] == lens[i]; an input that
+ *    changed between the two passes is ZGPU_E_INTERNAL, never a store outside the entry's pairs.
+ *  - ZGPU_INDEX_AUTO: the table is tried; an entry whose table answer is ZGPU_SEEKTAB_NONE, and only that one, is indexed by its chain. A
+ *    table that is present and malformed stays an error. info.kind says what an entry was indexed by.
+ * The handle owns 16 * (nrows + 1) bytes of device memory per indexed entry and the per-entry host records. No byte of an entry comes back
+ * to the host. It stores no source pointer: an index describes bytes, not an address. It belongs to one context and is destroyed before it.
+ * Selection (zgpu_frames_seek_indexed_device): ONE zg_k_seekmany_find launch over the handle's pairs; no byte of any entry is read. out[j] is
+ * the record of zg_seektab.h's rule applied to the entry's rows: for a table-kind entry all 64 bytes of what
+ * zgpu_frames_seek_table_many_device returns (ZGPU_SEEKTAB_PAST_TABLE decided per range against the kept tab); for a declared-kind entry tab
+ * is the entry's length — PAST_TABLE cannot arise — and src_lo, src_hi, plain_lo, plain_seen and flag bit 2 equal what
+ * zgpu_frames_seek_device answers for the range with anchor 0 (frames_skipped / frames_taken count ROWS, skippable frames included, and
+ * bound is the declared promise plain_seen - plain_lo). A range that names an entry the index refused gets that entry's status and why, every
+ * other field 0; entry >= entries or pad != 0: ZGPU_E_BAD_ARG; a length of 0: a record of zeros. A handle of another context fails the call
+ * with ZGPU_E_BAD_ARG.
+ * Gather (zgpu_gather_ranges_indexed_device_src): n must be the handle's entry count (else ZGPU_E_BAD_ARG). An entry that a range of nonzero
+ * length names must pass the pointer check and have lens[i] == info.len, else the ranges that name it get ZGPU_E_BAD_ARG and the others are
+ * unaffected; the pointer may differ from the one the index was built from. Behind the selection it IS
+ * zgpu_gather_ranges_seek_table_device_src — one routine —: groups by shared rows, each decoded once; the promise D[glast + 1] - D[gfirst]
+ * held against the group's total, declared sizes per frame; fate sharing within a group; ZGPU_E_TARGET_TOO_SMALL per range; the rank order
+ * of verdicts; dictionary frames; ZGPU_DEVICE_VERIFY; no byte of a failed range's destination written, none at or behind dst + written; the
+ * streams synchronised on return. ZGPU_DEVICE_VERIFY_SEEK_TABLE works for ranges of table-kind entries (the rows are read from the entry at
+ * verify time); a range of a declared-kind entry under that flag gets ZGPU_E_BAD_ARG in its result: there is no table to enforce.
+ * RANDOM ACCESS here means: a call costs one find launch plus the decode of the frames its ranges touch; nothing in front of them is read.
+ * THE INDEX IS THE CALLER'S PROMISE that the entry's bytes have not changed since it was built. A stale index is a status, never a fault:
+ * every record is held against lens[i] on the host (src_lo <= src_hi <= lens[i]) before anything is gathered, the bytes then go through the
+ * bounded device walk, and the range gets what zgpu_decode_all reports for those bytes, or ZGPU_E_CONTENT_SIZE_MISMATCH.
+ * Diagnostics: zgpu_seek_index_stats — [0] launches of the build, [1] their microseconds (HIP events), [2] bytes downloaded, [3] device bytes
+ * held, [4] rows, [5] input bytes that crossed to the host (always 0). zgpu_debug_ranges_stats after an indexed call: [0] - [2], [14], [15]
+ * and [18] are 0 (no locate, no prefix pass), [16] is 1 when any range has nonzero length, [13], [5], [6] count groups and their frames once.
+ * Out of scope: updating an index in place, entries with unsized frames (use a seek table), host sources, several GPUs, sharing one handle
+ * between contexts. */
+typedef struct zgpu_seek_index zgpu_seek_index;        /* belongs to one zgpu_ctx; destroy it before the context */
+enum { ZGPU_INDEX_SEEK_TABLE = 0, ZGPU_INDEX_DECLARED = 1, ZGPU_INDEX_AUTO = 2 };
+#define ZGPU_INDEX_UNSIZED 32u                         /* zgpu_seek_index_info.why: a zstd frame declares no Frame_Content_Size */
+typedef struct {
+  uint64_t len;          /* bytes of the entry the index was built from */
+  uint64_t compressed;   /* C[nrows] */
+  uint64_t plaintext;    /* D[nrows] */
+  uint32_t status;       /* 0, ZGPU_E_BAD_ARG (pointer check), ZGPU_E_SEEK_TABLE, ZGPU_E_FRAME_INDEX; != 0: nrows = compressed = plaintext = 0 */
+  uint32_t why;          /* ZGPU_SEEKTAB_* | ZGPU_CHAIN_* (the chain broke) | ZGPU_INDEX_UNSIZED */
+  uint32_t kind;         /* ZGPU_INDEX_SEEK_TABLE or ZGPU_INDEX_DECLARED: what this entry was indexed by */
+  uint32_t nrows;
+} zgpu_seek_index_info;
+int zgpu_seek_index_create_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t kind, zgpu_seek_index** out);
+void zgpu_seek_index_destroy(zgpu_seek_index*);
+uint32_t zgpu_seek_index_entries(const zgpu_seek_index*);
+int zgpu_seek_index_info_of(const zgpu_seek_index*, uint32_t i, zgpu_seek_index_info* out);
+int zgpu_seek_index_stats(const zgpu_seek_index*, uint64_t* out, int n);
+int zgpu_frames_seek_indexed_device(zgpu_ctx*, const zgpu_seek_index*, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out /* m */);
+int zgpu_gather_ranges_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                          const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts /* m */,
+                                          const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

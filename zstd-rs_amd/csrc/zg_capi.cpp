@@ -83,6 +83,7 @@ const char* zgpu_status_name(int s) {
     case ZGPU_E_CONTENT_SIZE_MISMATCH: return "ContentSizeMismatch";
     case ZGPU_E_SEEK_TABLE: return "SeekTable";
     case ZGPU_E_SEEK_CHECKSUM_MISMATCH: return "SeekChecksumMismatch";
+    case ZGPU_E_FRAME_INDEX: return "FrameIndex";
     case ZGPU_E_UNSUPPORTED: return "Unsupported";
     case ZGPU_E_INTERNAL: return "Internal";
     case ZGPU_E_NOMEM: return "OutOfMemory";

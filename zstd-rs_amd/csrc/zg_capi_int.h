@@ -58,6 +58,20 @@ struct zgpu_ctx {
   std::string err;
 };
 
+// A seek index (include/zgpu.h: zgpu_seek_index): the pairs { C[k], D[k] } of every indexed entry in device memory, and per entry where they
+// lie and what the selection needs besides. No source pointer: offsets only.
+enum { kSeekIdxStatLaunches = 0, kSeekIdxStatKernelUs, kSeekIdxStatBytesDownloaded, kSeekIdxStatDeviceBytes, kSeekIdxStatRows, kSeekIdxStatInputBytesToHost,
+       kSeekIdxStatCount };
+static_assert(kSeekIdxStatLaunches == zg::kPassLaunches && kSeekIdxStatKernelUs == zg::kPassUs && kSeekIdxStatBytesDownloaded == zg::kPassBytes,
+              "the array handed to the passes of the build");
+struct zgpu_seek_index {
+  zgpu_ctx* ctx = nullptr;
+  zg::DevBuf pairs;                      // 16 * (nrows + 1) bytes per indexed entry, back to back
+  struct Ent { zgpu_seek_index_info info; uint64_t pre, tab; };   // pre: the index of the entry's pair 0; tab: where its table frame begins (declared kind: len)
+  std::vector<Ent> ents;
+  uint64_t stats[kSeekIdxStatCount] = {};
+};
+
 namespace zg { class StreamCore; }
 
 // ---- FrameDecoder mirror (frame_decoder.rs:80-627) ---------------------------------------------------------------------------

@@ -435,25 +435,24 @@ int Engine::seektab_pass(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, uin
                    [&](LaneTmp& d, hipStream_t s) { zg_launch_seektab(d.lanes.as<zgt::Lane>(), n, d.out.as<zgk::Seek>(), s); });
 }
 
-int Engine::seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* ranges, uint32_t m, zgk::Seek* out, uint64_t* stats, ManyStats* more) {
-  if (!m) return ZG_OK;
+int Engine::seekmany_prefixes(const DevEntry* e, uint32_t ne, zgm::Loc* loc, uint64_t* pre, DevBuf* scratch, uint64_t* npairs, uint64_t* stats, ManyStats* more) {
   Engine* eng = this;
+  *npairs = 0;
   // locate: what every entry's table frame is
-  std::vector<zgm::Loc> loc(ne);
   if (ne) {
     LaneTmp t;
     std::vector<zgm::Ent> ents(ne);
     for (uint32_t i = 0; i < ne; i++) ents[i] = zgm::Ent{e[i].src, e[i].len};
-    const int st = lane_pass(t, ents.data(), (size_t)ne * sizeof(zgm::Ent), Down{loc.data(), (size_t)ne * sizeof(zgm::Loc)}, Down{}, stats,
+    const int st = lane_pass(t, ents.data(), (size_t)ne * sizeof(zgm::Ent), Down{loc, (size_t)ne * sizeof(zgm::Loc)}, Down{}, stats,
                              [&](LaneTmp& d, hipStream_t s) { zg_launch_seekmany_locate(d.lanes.as<zgm::Ent>(), ne, d.out.as<zgm::Loc>(), s); });
     if (st) return st;
   }
   // the scratch laid out from the located row counts: every usable entry's prefixes, then every usable entry's chunk totals
-  std::vector<uint64_t> pre(ne, 0);
   std::vector<zgm::Work> work;
   uint64_t pairs = 0, chunks = 0;
   for (uint32_t i = 0; i < ne; i++) {
     const zgm::Loc& l = loc[i];
+    pre[i] = 0;
     if (l.why) continue;
     // (what the host relies on below is checked here, not believed: the rows lie inside the entry)
     if (l.nf > zgt::kMaxFrames || (l.es != 8 && l.es != 12) || l.tab > e[i].len || (uint64_t)l.nf * l.es + zgt::kFraming != e[i].len - l.tab) {
@@ -465,50 +464,75 @@ int Engine::seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* range
     chunks += zgm::chunks_of(l.nf, zgm::kChunkRows);
   }
   if (chunks > 0xFFFFFFFFull || pairs + chunks > SIZE_MAX / sizeof(zgm::Pair)) return ZG_NOMEM;
-  LaneTmp tp;   // (extra: the scratch; lanes: the chunks of work)
-  if (pairs) {
-    work.reserve((size_t)chunks);
-    uint64_t tot = pairs;
-    for (uint32_t i = 0; i < ne; i++) {
-      const zgm::Loc& l = loc[i];
-      if (l.why) continue;
-      const uint32_t nq = zgm::chunks_of(l.nf, zgm::kChunkRows);
-      for (uint32_t q = 0; q < nq; q++) work.push_back(zgm::Work{e[i].src, l.tab + 8, pre[i], tot, l.nf, l.es, q, nq});
-      tot += nq;
-    }
-    const size_t scratch = (size_t)(pairs + chunks) * sizeof(zgm::Pair), wbytes = work.size() * sizeof(zgm::Work);
-    ZG_HIP(hipSetDevice(device_));
-    int st;
-    if ((st = tp.extra.reserve(scratch)) || (st = tp.lanes.reserve(wbytes))) return st;
-    for (hipEvent_t& x : tp.ev) if (!x) ZG_HIP(hipEventCreate(&x));
-    ZG_HIP(hipMemcpyAsync(tp.lanes.p, work.data(), wbytes, hipMemcpyHostToDevice, stream_));
-    ZG_HIP(hipStreamSynchronize(stream_));   // (pageable)
-    ZG_HIP(hipEventRecord(tp.ev[0], stream_));
-    zg_launch_seekmany_prefix(tp.lanes.as<zgm::Work>(), (uint32_t)work.size(), tp.extra.as<zgm::Pair>(), stream_);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipEventRecord(tp.ev[1], stream_));
-    ZG_HIP(hipStreamSynchronize(stream_));
-    float ms = 0;
-    ZG_HIP(hipEventElapsedTime(&ms, tp.ev[0], tp.ev[1]));
-    more->prefix_launches += 2; more->prefix_us += (uint64_t)(ms * 1000.0f + 0.5f); more->scratch_bytes += (uint64_t)pairs * sizeof(zgm::Pair);
+  if (!pairs) return ZG_OK;
+  LaneTmp tp;   // (lanes: the chunks of work)
+  work.reserve((size_t)chunks);
+  uint64_t tot = pairs;
+  for (uint32_t i = 0; i < ne; i++) {
+    const zgm::Loc& l = loc[i];
+    if (l.why) continue;
+    const uint32_t nq = zgm::chunks_of(l.nf, zgm::kChunkRows);
+    for (uint32_t q = 0; q < nq; q++) work.push_back(zgm::Work{e[i].src, l.tab + 8, pre[i], tot, l.nf, l.es, q, nq});
+    tot += nq;
   }
-  // find: one lane per range
-  std::vector<zgm::Find> lanes(m);
-  for (uint32_t j = 0; j < m; j++) {
-    const ManyRange& r = ranges[j];
-    if (!r.rlen || r.entry >= ne) { lanes[j] = zgm::Find{r.begin, 0, 0, 0, 0, 0, 0, 0}; continue; }
-    const zgm::Loc& l = loc[r.entry];
-    lanes[j] = zgm::Find{r.begin, r.rlen, pre[r.entry], l.tab, l.why ? 0u : l.nf, l.why, 0, 0};
-  }
+  const size_t bytes = (size_t)(pairs + chunks) * sizeof(zgm::Pair), wbytes = work.size() * sizeof(zgm::Work);
+  ZG_HIP(hipSetDevice(device_));
+  int st;
+  if ((st = scratch->reserve(bytes)) || (st = tp.lanes.reserve(wbytes))) return st;
+  for (hipEvent_t& x : tp.ev) if (!x) ZG_HIP(hipEventCreate(&x));
+  ZG_HIP(hipMemcpyAsync(tp.lanes.p, work.data(), wbytes, hipMemcpyHostToDevice, stream_));
+  ZG_HIP(hipStreamSynchronize(stream_));   // (pageable)
+  ZG_HIP(hipEventRecord(tp.ev[0], stream_));
+  zg_launch_seekmany_prefix(tp.lanes.as<zgm::Work>(), (uint32_t)work.size(), scratch->as<zgm::Pair>(), stream_);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(tp.ev[1], stream_));
+  ZG_HIP(hipStreamSynchronize(stream_));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, tp.ev[0], tp.ev[1]));
+  more->prefix_launches += 2; more->prefix_us += (uint64_t)(ms * 1000.0f + 0.5f); more->scratch_bytes += (uint64_t)pairs * sizeof(zgm::Pair);
+  *npairs = pairs;
+  return ZG_OK;
+}
+
+int Engine::seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out, uint64_t* stats, ManyStats* more) {
+  if (!m) return ZG_OK;
   LaneTmp t;
   uint64_t pass[3] = {0, 0, 0};
-  const zgm::Pair* dp = tp.extra.as<zgm::Pair>();
-  const int st = lane_pass(t, lanes.data(), (size_t)m * sizeof(zgm::Find), Down{out, (size_t)m * sizeof(zgk::Seek)}, Down{}, pass,
-                           [&](LaneTmp& d, hipStream_t s) { zg_launch_seekmany_find(d.lanes.as<zgm::Find>(), m, dp, d.out.as<zgk::Seek>(), s); });
+  const int st = lane_pass(t, lanes, (size_t)m * sizeof(zgm::Find), Down{out, (size_t)m * sizeof(zgk::Seek)}, Down{}, pass,
+                           [&](LaneTmp& d, hipStream_t s) { zg_launch_seekmany_find(d.lanes.as<zgm::Find>(), m, pairs, d.out.as<zgk::Seek>(), s); });
   if (st) return st;
   more->find_launches += pass[kPassLaunches]; more->find_us += pass[kPassUs];
-  stats[kPassBytes] += pass[kPassBytes];
+  if (stats) stats[kPassBytes] += pass[kPassBytes];
   return ZG_OK;
+}
+
+int Engine::seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* ranges, uint32_t m, zgk::Seek* out, uint64_t* stats, ManyStats* more) {
+  if (!m) return ZG_OK;
+  std::vector<zgm::Loc> loc(ne);
+  std::vector<uint64_t> pre(ne, 0);
+  DevBuf scratch;   // (lives for the call)
+  uint64_t npairs = 0;
+  int st = seekmany_prefixes(e, ne, loc.data(), pre.data(), &scratch, &npairs, stats, more);
+  if (!st) {
+    // find: one lane per range
+    std::vector<zgm::Find> lanes(m);
+    for (uint32_t j = 0; j < m; j++) {
+      const ManyRange& r = ranges[j];
+      if (!r.rlen || r.entry >= ne) { lanes[j] = zgm::Find{r.begin, 0, 0, 0, 0, 0, 0, 0}; continue; }
+      const zgm::Loc& l = loc[r.entry];
+      lanes[j] = zgm::Find{r.begin, r.rlen, pre[r.entry], l.tab, l.why ? 0u : l.nf, l.why, 0, 0};
+    }
+    st = seekmany_find(lanes.data(), m, scratch.as<zgm::Pair>(), out, stats, more);
+  }
+  scratch.release();
+  return st;
+}
+
+int Engine::seekidx_rows_pass(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, uint64_t* stats) {
+  if (!n) return ZG_OK;
+  LaneTmp t;
+  return lane_pass(t, lanes, (size_t)n * sizeof(zgx::Lane), Down{out, (size_t)n * sizeof(zgx::Rows)}, Down{}, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_seekidx_rows(d.lanes.as<zgx::Lane>(), n, pairs, d.out.as<zgx::Rows>(), s); });
 }
 
 int Engine::hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats) {

@@ -282,6 +282,15 @@ class Engine {
   struct ManyRange { uint64_t begin, rlen; uint32_t entry; };
   struct ManyStats { uint64_t prefix_launches = 0, prefix_us = 0, find_launches = 0, find_us = 0, scratch_bytes = 0; };
   int seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* ranges, uint32_t m, zgk::Seek* out, uint64_t* stats, ManyStats* more);
+  // The two halves of seekmany_pass, for a caller that keeps the pairs (zgpu_seek_index, zg_frames.cpp). seekmany_prefixes: the locate pass
+  // and the two prefix launches; loc[i] = what locate found of entry i, pre[i] = the index of its pair 0 in *scratch (usable tables only),
+  // *npairs = the pairs of prefixes at the front of *scratch (the chunk totals lie behind them); the caller releases *scratch.
+  // seekmany_find: ONE find launch over m lanes the caller laid out on `pairs`; its download is added to stats[kPassBytes] (stats may be null).
+  int seekmany_prefixes(const DevEntry* e, uint32_t ne, zgm::Loc* loc, uint64_t* pre, DevBuf* scratch, uint64_t* npairs, uint64_t* stats, ManyStats* more);
+  int seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out, uint64_t* stats, ManyStats* more);
+  // seekidx_rows_pass — the same pairs from the header chain of entries that declare their sizes (zg_seekidx.h): zg_k_seekidx_rows, one lane
+  // per entry, stores into pairs[lanes[i].pre .. + lanes[i].limit] (device memory of the caller); out[i] = what lane i found.
+  int seekidx_rows_pass(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, uint64_t* stats);
   // hash_ranges_pass — XXH64 of ranges[0 .. n) of base (device memory the caller has checked) by the hash kernel `kernel` chooses
   // (zg_launch_xxh64_with); digests[i] is ranges[i]'s (zgpu_debug_hash_ranges).
   int hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats);

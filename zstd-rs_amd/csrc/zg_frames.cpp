@@ -30,7 +30,9 @@
 // zgpu_gather_ranges_seek_table_device_src takes m ranges that each name one of n seekable entries (zg_seekmany.h: every table scanned once,
 // every range a binary search). The ranges of one entry whose table rows overlap form a group; a group is ONE entry of this file's machinery,
 // decoded once, and every range of it is a clip of the group's span (Ranges) with its own destination. The calls with one range per entry are
-// the case of spans of one clip.
+// the case of spans of one clip. zgpu_gather_ranges_indexed_device_src is the same call behind another selection: a zgpu_seek_index keeps
+// the prefix sums of its entries' rows in device memory — built from their seek tables, or from their header chains where every frame
+// declares its size (zg_seekidx.h) —, indexed_ranges finds every range's rows in them with one launch, and gather_groups is shared.
 //
 // How a call is put together. A Call is what every call has (context, sources, lengths, destinations, capacities, the shared-dictionary
 // lookup) plus up to three parts that an entry point builds and hangs in: DeviceSink (device_sink: the options, the one place that refuses
@@ -1229,18 +1231,13 @@ extern "C" int zgpu_frames_seek_table_many_device(zgpu_ctx* c, const void* const
 // its ranges take together: (src + C_gfirst, C_{glast + 1} - C_gfirst) is walked, cut into submits, gathered, decoded and hashed once, and
 // every range is a clip of the group's span with its own destination. What a group's frames do — a decode or walk error, a size that differs
 // from the table's promise, a checksum verdict — is the verdict of every range in it; TargetTooSmall is each range's own.
-extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
-                                                        const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
-                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
-  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+// Everything behind the selection, for both gather calls (the seek-table one and the indexed one): recs / refused are the m records and
+// refusals the selection left, whatever produced the pairs they were found in.
+namespace {
+int gather_groups(zgpu_ctx* c, DeviceSink& sink, const void* const* device_srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
+                  void* const* device_dsts, const size_t* caps, const std::vector<zgk::Seek>& recs, const std::vector<uint8_t>& refused,
+                  zgpu_range_result* results) {
   int st;
-  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
-  if (st) return st;
-  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
-  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  if ((st = seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, &recs, &refused))) return st;
   // the groups: the ranges that take rows, sorted by (entry, first row, last row); one that begins at or in front of the last row of the group
   // in front of it joins that group
   std::vector<uint32_t> order;
@@ -1320,6 +1317,247 @@ extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void*
     if (!gd.r.status) d.r.written = cl.written;
   }
   return st;
+}
+}  // namespace
+
+extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                        const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  int st;
+  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  if ((st = seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, &recs, &refused))) return st;
+  return gather_groups(c, sink, device_srcs, lens, ranges, m, device_dsts, caps, recs, refused, results);
+}
+
+// ---- seek index handles (include/zgpu.h: zgpu_seek_index; zg_seekidx.h) -------------------------------------------------------------------------
+static_assert(sizeof(zgpu_seek_index_info) == 40 && ZGPU_INDEX_UNSIZED == zgx::kUnsized && ZGPU_E_FRAME_INDEX == 74, "include/zgpu.h");
+namespace {
+// an entry the index refuses: nothing of it is held
+void refuse_index(zgpu_seek_index::Ent& e, uint32_t status, uint32_t why, uint32_t kind) {
+  e.info.status = status; e.info.why = why; e.info.kind = kind;
+  e.info.nrows = 0; e.info.compressed = 0; e.info.plaintext = 0;
+  e.pre = 0; e.tab = 0;
+}
+
+// The build. The table pass works in a scratch of its own (its chunk totals lie behind the prefixes); the handle's buffer is sized exactly —
+// 16 * (nrows + 1) bytes per indexed entry —, gets the table entries' pairs by one device copy each, and the declared entries' pairs straight
+// from zg_k_seekidx_rows.
+int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, uint32_t kind) {
+  zg::Engine* eng = c->eng;
+  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  std::vector<Engine::DevEntry> dev;
+  std::vector<uint8_t> refused;
+  check_entries(c, srcs, lens, nullptr, nullptr, n, check_all, &dev, &refused);
+  x->ents.assign(n, zgpu_seek_index::Ent{});
+  std::vector<uint8_t> by_chain(n, 0);   // entries the chain is asked about
+  for (uint32_t i = 0; i < n; i++) {
+    x->ents[i].info.len = lens[i];
+    if (refused[i]) refuse_index(x->ents[i], ZGPU_E_BAD_ARG, 0, kind == ZGPU_INDEX_DECLARED ? ZGPU_INDEX_DECLARED : ZGPU_INDEX_SEEK_TABLE);
+    else by_chain[i] = kind == ZGPU_INDEX_DECLARED;
+  }
+  uint64_t* stats = x->stats;
+  // the tables
+  zg::DevBuf scratch;
+  std::vector<zgm::Loc> loc;
+  std::vector<uint64_t> tpre;
+  std::vector<uint32_t> tab_of;   // the entries the table pass was asked about
+  struct Free { zg::DevBuf& b; ~Free() { b.release(); } } free_scratch{scratch};
+  if (kind != ZGPU_INDEX_DECLARED) {
+    std::vector<Engine::DevEntry> live;
+    for (uint32_t i = 0; i < n; i++) if (!refused[i]) { tab_of.push_back(i); live.push_back(dev[i]); }
+    loc.resize(live.size());
+    tpre.assign(live.size(), 0);
+    Engine::ManyStats more;
+    uint64_t npairs = 0;
+    const int st = eng->seekmany_prefixes(live.data(), (uint32_t)live.size(), loc.data(), tpre.data(), &scratch, &npairs, stats, &more);
+    stats[kSeekIdxStatLaunches] += more.prefix_launches; stats[kSeekIdxStatKernelUs] += more.prefix_us;
+    if (st) return st;
+    for (size_t q = 0; q < tab_of.size(); q++) {
+      zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+      if (loc[q].why == zgt::kNone && kind == ZGPU_INDEX_AUTO) by_chain[tab_of[q]] = 1;
+      else if (loc[q].why) refuse_index(e, ZGPU_E_SEEK_TABLE, loc[q].why, ZGPU_INDEX_SEEK_TABLE);
+      else { e.info.kind = ZGPU_INDEX_SEEK_TABLE; e.info.nrows = loc[q].nf; e.tab = loc[q].tab; }
+    }
+  }
+  // the chains: the summary pass says which entries can be indexed and how many rows each has
+  std::vector<uint32_t> ch_of;
+  std::vector<Engine::DevEntry> chain;
+  for (uint32_t i = 0; i < n; i++) if (by_chain[i]) { ch_of.push_back(i); chain.push_back(dev[i]); }
+  std::vector<zgi::Entry> sum(chain.size());
+  int st = eng->index_pass(chain.data(), (uint32_t)chain.size(), nullptr, nullptr, sum.data(), nullptr, stats);
+  if (st) return st;
+  for (size_t q = 0; q < ch_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
+    const uint32_t why = zgx::refusal(sum[q]);
+    if (sum[q].chain_end > lens[ch_of[q]]) { eng->last_error = "zgpu_seek_index_create_device: a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
+    if (why) refuse_index(e, ZGPU_E_FRAME_INDEX, why, ZGPU_INDEX_DECLARED);
+    else if (sum[q].nrec > zgt::kMaxFrames) refuse_index(e, ZGPU_E_FRAME_INDEX, ZGPU_SEEKTAB_TOO_LARGE, ZGPU_INDEX_DECLARED);
+    else { e.info.kind = ZGPU_INDEX_DECLARED; e.info.nrows = sum[q].nrec; e.tab = lens[ch_of[q]]; }
+  }
+  // the handle's pairs: every indexed entry's range
+  uint64_t pairs = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    zgpu_seek_index::Ent& e = x->ents[i];
+    if (e.info.status) continue;
+    e.pre = pairs;
+    pairs += (uint64_t)e.info.nrows + 1;
+  }
+  if (pairs > SIZE_MAX / sizeof(zgm::Pair)) return ZGPU_E_NOMEM;
+  if (pairs && (st = x->pairs.reserve((size_t)pairs * sizeof(zgm::Pair)))) return st;
+  stats[kSeekIdxStatDeviceBytes] = pairs * sizeof(zgm::Pair);
+  zgm::Pair* dp = x->pairs.as<zgm::Pair>();
+  hipStream_t s = eng->stream();
+  // table kind: the prefixes move over, and each entry's closing pair comes back (16 bytes: C[nrows], D[nrows])
+  std::vector<zgm::Pair> closing(tab_of.size(), zgm::Pair{0, 0});
+  for (size_t q = 0; q < tab_of.size(); q++) {
+    const zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
+    const zgm::Pair* from = scratch.as<zgm::Pair>() + tpre[q];
+    if (hipMemcpyAsync(dp + e.pre, from, ((size_t)e.info.nrows + 1) * sizeof(zgm::Pair), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(&closing[q], from + e.info.nrows, sizeof(zgm::Pair), hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+    stats[kSeekIdxStatBytesDownloaded] += sizeof(zgm::Pair);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  for (size_t q = 0; q < tab_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
+    e.info.compressed = closing[q].c; e.info.plaintext = closing[q].d;
+  }
+  // declared kind: the rows pass over the entries the summary pass accepted
+  std::vector<zgx::Lane> lanes;
+  std::vector<uint32_t> lane_of;
+  for (size_t q = 0; q < ch_of.size(); q++) {
+    const zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
+    if (e.info.status) continue;
+    lane_of.push_back(ch_of[q]);
+    lanes.push_back(zgx::Lane{chain[q].src, chain[q].len, e.pre, e.info.nrows});
+  }
+  std::vector<zgx::Rows> rows(lanes.size());
+  if ((st = eng->seekidx_rows_pass(lanes.data(), (uint32_t)lanes.size(), dp, rows.data(), stats))) return st;
+  for (size_t q = 0; q < lane_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[lane_of[q]];
+    // (a source that changed between the passes — the caller's promise broken —, or pairs that do not add up to the entry)
+    if (rows[q].why || rows[q].nrows != e.info.nrows || rows[q].c != e.info.len) {
+      eng->last_error = "zgpu_seek_index_create_device: a source changed while it was indexed";
+      return ZGPU_E_INTERNAL;
+    }
+    e.info.compressed = rows[q].c; e.info.plaintext = rows[q].d;
+  }
+  for (const zgpu_seek_index::Ent& e : x->ents) if (!e.info.status) stats[kSeekIdxStatRows] += e.info.nrows;
+  return ZGPU_OK;
+}
+
+// Both indexed calls up to the records. Every range is looked at on its own, as seek_many looks at it: entry >= entries or pad != 0 refuses
+// it, a length of 0 passes untouched, an entry the index refused gives its status and why. srcs != nullptr (the gather call): an entry that a
+// range of nonzero length names is checked once — its pointer, and lens[i] against the length it was indexed at —, a destination on its own.
+// table_flag: ZGPU_DEVICE_VERIFY_SEEK_TABLE refuses the ranges of declared-kind entries. Then ONE find launch over the handle's pairs.
+int indexed_ranges(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
+                   void* const* dsts, const size_t* caps, bool table_flag, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const uint32_t n = (uint32_t)x->ents.size();
+  out->assign(m, zgk::Seek{});
+  refused->assign(m, 0);
+  std::vector<DevRange> known;
+  const int device = c->eng->device();
+  std::vector<uint8_t> seen(n, 0);   // 0: no range of nonzero length has named it yet, 1: passed, 2: refused
+  std::vector<zgm::Find> lanes(m);
+  for (uint32_t j = 0; j < m; j++) {
+    const zgpu_entry_range& g = ranges[j];
+    lanes[j] = zgm::Find{g.begin, 0, 0, 0, 0, 0, 0, 0};
+    if (g.entry >= n || g.pad) { (*refused)[j] = 1; continue; }
+    if (!g.len) continue;
+    const uint32_t i = g.entry;
+    const zgpu_seek_index::Ent& e = x->ents[i];
+    if (e.info.status) continue;   // (the record is the entry's status and why: written below, nothing of the entry is looked at)
+    if (srcs && !seen[i]) {
+      bool bad = (!srcs[i] && lens[i]) || (uint64_t)lens[i] != e.info.len;
+      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
+      seen[i] = bad ? 2 : 1;
+    }
+    bool bad = seen[i] == 2 || (table_flag && e.info.kind != ZGPU_INDEX_SEEK_TABLE);
+    if (!bad && dsts) {
+      bad = !dsts[j] && caps[j];
+      if (!bad && caps[j]) bad = !check_device_range(device, dsts[j], caps[j], known);
+    }
+    if (bad) { (*refused)[j] = 1; continue; }
+    lanes[j] = zgm::Find{g.begin, g.len, e.pre, e.tab, e.info.nrows, 0, 0, 0};
+  }
+  Engine::ManyStats more;
+  const int st = drain(c, c->eng->seekmany_find(lanes.data(), m, x->pairs.as<zgm::Pair>(), out->data(), nullptr, &more));
+  c->ranges_many_stats[kManyStatFindLaunches] = more.find_launches; c->ranges_many_stats[kManyStatFindUs] = more.find_us;
+  if (st) return st;
+  for (uint32_t j = 0; j < m; j++) {
+    zgk::Seek& s = (*out)[j];
+    if ((*refused)[j]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
+    if (!ranges[j].len) continue;
+    const zgpu_seek_index::Ent& e = x->ents[ranges[j].entry];
+    if (e.info.status) { s = zgk::Seek{}; s.status = e.info.status; s.why = e.info.why; continue; }
+    // (every record is held against the entry's length before anything is gathered)
+    if (s.src_lo > s.src_hi || s.src_hi > e.info.len || (s.status && s.status != (uint32_t)ZGPU_E_SEEK_TABLE)) {   // (never)
+      c->eng->last_error = "zgpu_frames_seek_indexed_device: a record that leaves its entry";
+      return ZGPU_E_INTERNAL;
+    }
+    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_seek_index_create_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t kind,
+                                             zgpu_seek_index** out) {
+  if (out) *out = nullptr;
+  if (!c || !out || kind > ZGPU_INDEX_AUTO || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
+  zgpu_seek_index* x = new zgpu_seek_index();
+  x->ctx = c;
+  const int st = drain(c, build_index(c, x, device_srcs, lens, n, kind));
+  if (st) { zgpu_seek_index_destroy(x); return st; }   // (nothing is left behind)
+  *out = x;
+  return ZGPU_OK;
+}
+extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
+  if (!x) return;
+  if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
+  x->pairs.release();
+  delete x;
+}
+extern "C" uint32_t zgpu_seek_index_entries(const zgpu_seek_index* x) { return x ? (uint32_t)x->ents.size() : 0; }
+extern "C" int zgpu_seek_index_info_of(const zgpu_seek_index* x, uint32_t i, zgpu_seek_index_info* out) {
+  if (!x || !out || i >= x->ents.size()) return ZGPU_E_BAD_ARG;
+  *out = x->ents[i].info;
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) { return x ? copy_stats(x->stats, out, n) : 0; }
+
+extern "C" int zgpu_frames_seek_indexed_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
+  if (!c || !x || x->ctx != c || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
+  reset_stats(c, kOwnsRanges);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = indexed_ranges(c, x, nullptr, nullptr, ranges, m, nullptr, nullptr, false, &recs, &refused);
+  for (uint32_t j = 0; j < m; j++) { if (st) memset(&out[j], 0, sizeof out[j]); else memcpy(&out[j], &recs[j], sizeof out[j]); }
+  return st;
+}
+
+extern "C" int zgpu_gather_ranges_indexed_device_src(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                     const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                     const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results)))
+    return ZGPU_E_BAD_ARG;
+  int st;
+  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  if ((st = indexed_ranges(c, x, device_srcs, lens, ranges, m, device_dsts, caps, sink.table_flag, &recs, &refused))) return st;
+  return gather_groups(c, sink, device_srcs, lens, ranges, m, device_dsts, caps, recs, refused, results);
 }
 
 extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {

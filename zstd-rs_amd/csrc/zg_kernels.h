@@ -11,6 +11,7 @@
 #include "zg_seektab.h"
 #include "zg_seeksums.h"
 #include "zg_seekmany.h"
+#include "zg_seekidx.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -88,3 +89,6 @@ void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* fr
 void zg_launch_seekmany_locate(const zgm::Ent* ents, uint32_t n, zgm::Loc* out, hipStream_t s);
 void zg_launch_seekmany_prefix(const zgm::Work* work, uint32_t nw, zgm::Pair* pairs, hipStream_t s);
 void zg_launch_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair* pairs, zgk::Seek* out, hipStream_t s);
+// zg_k_seekidx_rows (zg_seekidx.h): one lane per entry follows the entry's header chain and stores the exclusive prefixes of its frame records
+// into pairs[lanes[i].pre .. + lanes[i].limit]: the pairs zg_k_seekmany_find reads; out[i] = what lane i found
+void zg_launch_seekidx_rows(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, hipStream_t s);

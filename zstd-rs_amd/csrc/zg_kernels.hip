@@ -1964,6 +1964,24 @@ void zg_launch_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair
   hipLaunchKernelGGL(zg_k_seekmany_find, dim3((m + zgm::kThreads - 1) / zgm::kThreads), dim3(zgm::kThreads), 0, s, lanes, m, pairs, out);
 }
 
+// The same pairs from the header chain of entries that carry no seek table, one lane per entry (zg_seekidx.h has the rows, the row limit, the
+// access bounds and the ISA notes). The host checked every [src, src + len) against the runtime's allocations and handed every lane its own
+// pair range; a lane reads no byte of a block body and writes that range and its own 32-byte record only.
+__global__ void __launch_bounds__(zgx::kThreads) zg_k_seekidx_rows(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out) {
+  const uint32_t i = blockIdx.x * zgx::kThreads + threadIdx.x;
+  if (i >= n) return;
+  const zgx::Lane l = lanes[i];
+  const zgx::Rows o = zgx::seekidx_rows(ZgWalkRead{l.src}, ZgPairs{(uint64_t)(uintptr_t)pairs}, l.len, l.pre, l.limit);
+  uint8_t* p = (uint8_t*)&out[i];
+  ZxU4 v;
+  v.x = (uint32_t)o.c; v.y = (uint32_t)(o.c >> 32); v.z = (uint32_t)o.d; v.w = (uint32_t)(o.d >> 32); zx_gst128(p, v);
+  v.x = o.nrows; v.y = o.why; v.z = 0; v.w = 0; zx_gst128(p + 16, v);
+}
+void zg_launch_seekidx_rows(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_seekidx_rows, dim3((n + zgx::kThreads - 1) / zgx::kThreads), dim3(zgx::kThreads), 0, s, lanes, n, pairs, out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------

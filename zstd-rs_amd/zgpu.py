@@ -29,6 +29,10 @@ E_SEEK_TABLE = 72              # the seek-table calls only: the entry does not e
 SEEKTAB_NONE, SEEKTAB_RESERVED_BITS, SEEKTAB_TOO_LARGE, SEEKTAB_BAD_FRAME, SEEKTAB_PAST_TABLE = 16, 17, 18, 19, 20
 E_CONTENT_SIZE_MISMATCH = 71   # decode_ranges_device_src only: a taken frame decoded to another length than it declares (no counterpart in the reference)
 E_SEEK_CHECKSUM_MISMATCH = 73  # decode_ranges_seek_table_device_src with verify_table=True only: the entry decoded, and its seek table does not vouch for the bytes
+E_FRAME_INDEX = 74             # a SeekIndex entry, and the ranges that name it: the header chain yields no index (SeekIndexInfo.why: CHAIN_* reason, INDEX_UNSIZED)
+INDEX_SEEK_TABLE, INDEX_DECLARED, INDEX_AUTO = 0, 1, 2   # zgpu_seek_index_create_device's kind
+INDEX_UNSIZED = 32             # SeekIndexInfo.why: a zstd frame declares no Frame_Content_Size
+_INDEX_KINDS = {"seek_table": INDEX_SEEK_TABLE, "declared": INDEX_DECLARED, "auto": INDEX_AUTO}
 E_UNSUPPORTED = 80
 E_HIP = 92
 E_BAD_ARG = 93
@@ -50,6 +54,8 @@ _STATS = {
                              ("seek_launches", "seek_us", "seek_bytes_downloaded", "input_bytes_to_host", "frames_skipped", "frames_decoded",
                               "plaintext_decoded", "bytes_written",
                               "compare_launches", "compare_us", "compare_bytes_downloaded", "frames_compared", "entries_failed_table")),
+    "SeekIndex.stats": ("zgpu_seek_index_stats", C.c_uint64,
+                        ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
                        ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
     "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
@@ -187,6 +193,27 @@ class RangeResultC(C.Structure):
     _fields_ = [("d", DeviceEntryResultC), ("seek", SeekC)]
 
 
+class SeekIndexInfoC(C.Structure):
+    """zgpu_seek_index_info (include/zgpu.h)"""
+    _fields_ = [("len", C.c_uint64), ("compressed", C.c_uint64), ("plaintext", C.c_uint64), ("status", C.c_uint32), ("why", C.c_uint32),
+                ("kind", C.c_uint32), ("nrows", C.c_uint32)]
+
+
+class SeekIndexInfo:
+    """One entry of a SeekIndex (zgpu_seek_index_info): len, the entry's bytes when it was indexed; compressed = C[nrows], plaintext = D[nrows];
+    status 0, E_BAD_ARG, E_SEEK_TABLE or E_FRAME_INDEX with why (SEEKTAB_*, a CHAIN_* reason, INDEX_UNSIZED); kind INDEX_SEEK_TABLE or
+    INDEX_DECLARED: what the entry was indexed by; nrows, its rows (frames, skippable ones included)."""
+    __slots__ = FIELDS = ("len", "compressed", "plaintext", "status", "why", "kind", "nrows")
+
+    def __init__(self, c):
+        for k in self.FIELDS:
+            setattr(self, k, int(getattr(c, k)))
+
+    def __repr__(self):
+        return "SeekIndexInfo(status=%d, why=%d, kind=%d, nrows=%d, len=%d, compressed=%d, plaintext=%d)" % (
+            self.status, self.why, self.kind, self.nrows, self.len, self.compressed, self.plaintext)
+
+
 class Seek:
     """One entry of Context.frames_seek_device (zgpu_seek): the whole frames [src_lo, src_hi) of the entry that hold the range, the plaintext
     offset plain_lo of the first of them, bound = plaintext_bound of those bytes. flags: open_ended (an unsized frame was taken: everything
@@ -292,6 +319,8 @@ class StreamOpts(C.Structure):
 NO_READ_AHEAD = 1
 
 EXPORTS = [
+    "zgpu_seek_index_create_device", "zgpu_seek_index_destroy", "zgpu_seek_index_entries", "zgpu_seek_index_info_of", "zgpu_seek_index_stats",
+    "zgpu_frames_seek_indexed_device", "zgpu_gather_ranges_indexed_device_src",
     "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
@@ -381,6 +410,16 @@ def _declare(L):
     L.zgpu_frames_seek_table_many_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(SeekC)]
     L.zgpu_gather_ranges_seek_table_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
                                                            P(RangeResultC)]
+    L.zgpu_seek_index_create_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, C.c_uint32, P(vp)]
+    L.zgpu_seek_index_destroy.argtypes = [vp]
+    L.zgpu_seek_index_destroy.restype = None
+    L.zgpu_seek_index_entries.argtypes = [vp]
+    L.zgpu_seek_index_entries.restype = C.c_uint32
+    L.zgpu_seek_index_info_of.argtypes = [vp, C.c_uint32, P(SeekIndexInfoC)]
+    L.zgpu_seek_index_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
+    L.zgpu_frames_seek_indexed_device.argtypes = [vp, vp, P(EntryRangeC), C.c_uint32, P(SeekC)]
+    L.zgpu_gather_ranges_indexed_device_src.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
+                                                        P(RangeResultC)]
     L.zgpu_set_frames_shared_dicts.argtypes = [vp, C.c_int]
     L.zgpu_set_frames_shared_dicts.restype = None
     L.zgpu_frames_shared_dicts.argtypes = [vp]
@@ -549,9 +588,12 @@ class Context:
             raise ZgpuError(st, "zgpu_ctx_create: no usable MI355X/HIP device — the engine has no CPU path")
         self.h = h
         self.device = device
+        self._indexes = []   # the SeekIndex handles that are still open: closed before the context
 
     def close(self):
         if getattr(self, "h", None):
+            for ix in list(getattr(self, "_indexes", ())):
+                ix.close()
             self.L.zgpu_ctx_destroy(self.h)
             self.h = None
 
@@ -872,17 +914,68 @@ class Context:
         k = self.L.zgpu_debug_ranges_stats(self.h, a, len(keys))
         return dict(zip(keys[:k], a[:k]))
 
-    def gather_tensor_ranges(self, tensors, ranges, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False):
+    def seek_index(self, src_ptrs, lens, kind="auto"):
+        """zgpu_seek_index_create_device: a SeekIndex over entries in DEVICE memory — per entry the prefix sums of its rows, built once on the
+        device and kept there. kind: "seek_table" (the entry's seek table), "declared" (its header chain: every frame declares its size),
+        "auto" (the table, and the chain for an entry that has none). An entry that cannot be indexed has a status in index.infos[i]; the
+        others are unaffected. Close it (or the context) when done; it also is a context manager."""
+        n = len(src_ptrs)
+        _one_per("seek_index", n, lens)
+        h = C.c_void_p()
+        self._check(self.L.zgpu_seek_index_create_device(self.h, _ptr_array(src_ptrs), _size_array(lens), n, _INDEX_KINDS[kind], C.byref(h)))
+        return SeekIndex(self, h)
+
+    def seek_index_tensors(self, tensors, kind="auto"):
+        """seek_index on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding shard i. The index
+        describes the bytes, not the tensor: a copy of the shard elsewhere is served by the same index."""
+        self._tensor_check(tensors, "seek_index_tensors")
+        return self.seek_index([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors], kind)
+
+    def _index_handle(self, index, what):
+        if not isinstance(index, SeekIndex) or not index.h:
+            raise ValueError("%s: an open SeekIndex" % what)
+        return index.h
+
+    def frames_seek_indexed_device(self, index, ranges):
+        """zgpu_frames_seek_indexed_device: one Seek per range (entry, begin, len) from the index alone — one find launch, no byte of any entry
+        is read. A table-kind entry answers what frames_seek_table_many_device answers; a declared-kind entry what frames_seek_device answers
+        in src_lo, src_hi, plain_lo, plain_seen and `nothing` (frames_skipped / frames_taken count rows, skippable frames included). A range
+        of an entry the index refused carries that entry's status and why."""
+        m = len(ranges)
+        out = (SeekC * max(m, 1))()
+        self._check(self.L.zgpu_frames_seek_indexed_device(self.h, self._index_handle(index, "frames_seek_indexed_device"), self._entry_ranges(ranges), m, out))
+        return [Seek(c) for c in out[:m]]
+
+    def gather_ranges_indexed_device_src(self, index, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
+                                         verify_table=False):
+        """zgpu_gather_ranges_indexed_device_src: gather_ranges_seek_table_device_src with the selection taken from a SeekIndex — one find
+        launch plus the decode, no locate and no prefix pass. src_ptrs / lens name the index's entries (all of them; an entry's length must
+        be the one it was indexed at, its address may differ). Everything behind the selection is that call: groups decoded once, fate
+        sharing, E_TARGET_TOO_SMALL per range, the options. verify_table serves table-kind entries; a range of a declared-kind entry gets
+        E_BAD_ARG under it. A stale index ends in a status per range, never in a fault. Returns (results, seeks), one of each per range."""
+        n, m = len(src_ptrs), len(ranges)
+        _one_per("gather_ranges_indexed_device_src", n, lens)
+        _one_per("gather_ranges_indexed_device_src", m, dst_ptrs, caps)
+        res = (RangeResultC * max(m, 1))()
+        self._check(self.L.zgpu_gather_ranges_indexed_device_src(self.h, self._index_handle(index, "gather_ranges_indexed_device_src"),
+                                                                 _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m,
+                                                                 _ptr_array(dst_ptrs), _size_array(caps),
+                                                                 C.byref(_opts(hash_max, no_hash, verify, verify_table)), res))
+        return _results(res, m), [Seek(res[j].seek) for j in range(m)]
+
+    def gather_tensor_ranges(self, tensors, ranges, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False, index=None):
         """gather_ranges_seek_table_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding
         seekable shard i, ranges[j] = (entry, begin, len) the record wanted of shard `entry`. A frames_seek_table_many_device call of its own
         sizes the destinations by min(len, seek.bound), so no byte of the input crosses to the host. The bytes go to ONE new torch.uint8
         tensor. Returns (tensors, results, seeks) — tensors[j] a view of range j's 256-byte aligned slot cut to `written` bytes (empty unless
         status == 0) — or, packed=True, (buffer, offsets, results, seeks): the slots back to back without padding, range j at
         buffer[offsets[j]:offsets[j + 1]] (a failed range's slot keeps its room and holds nothing of the range). Same single-runtime rule as
-        decode_tensors. torch is imported here, not by `import zgpu`."""
+        decode_tensors. torch is imported here, not by `import zgpu`.
+        index: a SeekIndex over these shards (seek_index_tensors) — the selection and the sizes come from it (frames_seek_indexed_device,
+        gather_ranges_indexed_device_src): index a shard once, gather per step. Without it the call is what it always was."""
         self._tensor_check(tensors, "gather_tensor_ranges")
         ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
-        seeks = self.frames_seek_table_many_device(ptrs, lens, ranges)
+        seeks = self.frames_seek_table_many_device(ptrs, lens, ranges) if index is None else self.frames_seek_indexed_device(index, ranges)
         caps = [min(int(r[2]), s.bound) for r, s in zip(ranges, seeks)]
         if packed:
             offs = [0]
@@ -892,8 +985,12 @@ class Context:
             dsts = [base[0] + o for o in offs[:-1]]
         else:
             buf, offs, dsts = self._slot_tensor(caps)
-        res, seeks = self.gather_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify,
-                                                              verify_table=verify_table)
+        if index is None:
+            res, seeks = self.gather_ranges_seek_table_device_src(ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify,
+                                                                  verify_table=verify_table)
+        else:
+            res, seeks = self.gather_ranges_indexed_device_src(index, ptrs, lens, ranges, dsts, caps, hash_max=hash_max, no_hash=no_hash,
+                                                               verify=verify, verify_table=verify_table)
         if packed:
             return buf[:offs[-1]], offs, res, seeks
         return self._views(buf, offs, res), res, seeks
@@ -1004,6 +1101,47 @@ class Context:
         res = self.decode_frames_device([(srcs[i] or 0, lens[i]) for i in range(n)], dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify)
         del keep
         return self._views(buf, offs, res), res
+
+
+class SeekIndex:
+    """A seek index handle (zgpu_seek_index; Context.seek_index makes one): per entry the prefix sums of its rows in device memory, reused by
+    any number of Context.frames_seek_indexed_device / gather_ranges_indexed_device_src calls. It belongs to its context, which closes the
+    indexes it still holds when it is closed. infos[i]: entry i's SeekIndexInfo."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.L, self.h = ctx, ctx.L, h
+        n = self.L.zgpu_seek_index_entries(h)
+        rec = SeekIndexInfoC()
+        self.infos = []
+        for i in range(n):
+            ctx._check(self.L.zgpu_seek_index_info_of(h, i, C.byref(rec)), "zgpu_seek_index_info_of")
+            self.infos.append(SeekIndexInfo(rec))
+        self.device_bytes = self.stats()["device_bytes"]
+        ctx._indexes.append(self)
+
+    def stats(self):
+        """the build (zgpu_seek_index_stats): launches, kernel_us (HIP events), bytes_downloaded, device_bytes held, rows, input_bytes_to_host
+        (always 0). Gather calls on the index do not change it: the index is never rebuilt."""
+        return _read_stats(self.L, "SeekIndex.stats", self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.zgpu_seek_index_destroy(self.h)
+            self.h = None
+            if self in self.ctx._indexes:
+                self.ctx._indexes.remove(self)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __len__(self):
+        return len(self.infos)
 
 
 class Batch:
