@@ -4,7 +4,8 @@
 // library), twice: as a shared library whose accessors count every access and every access outside the entry's window and outside the
 // scratch, and — with -DSEEKMANY_MAIN — as a stand-alone AddressSanitizer program in which every entry and the scratch lie in heap blocks of
 // exactly their length. Both hand back every record (and the library the prefix sums), and both can run zgt::seektab_entry's wave beside every
-// range and compare the two records (the program does for entries below 8 KiB, in its first round). Not part of the product.
+// range and compare the two records (the program does for entries below 8 KiB, in its first round). The library also exports the host-side
+// grouping of the gather calls (zgm::group_ranges), which needs no emulator. Not part of the product.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -133,6 +134,34 @@ extern "C" uint32_t zgemu_seekmany(const uint8_t* entry, uint64_t len, uint64_t 
   return differ;
 }
 extern "C" uint32_t zgemu_seekmany_chunk_rows() { return zgm::kChunkRows; }
+
+// The grouping of a gather call (zgm::group_ranges: host arithmetic, the header alone). in: m x (entry, begin, len, refused, status,
+// frames_skipped, frames_taken, src_lo, src_hi, plain_lo, plain_seen). groups: room for m x (entry, gfirst, glast, c_lo, c_hi, d_lo, d_hi); group_of, clip_of: m slots; order, skip:
+// m slots (one per clip); first: m + 1 slots. Returns the number of groups; counts[0]: the number of clips.
+extern "C" uint32_t zgemu_group_ranges(const uint64_t* in, uint32_t m, uint64_t* groups, uint32_t* group_of, uint32_t* clip_of, uint32_t* order,
+                                       uint32_t* first, uint64_t* skip, uint64_t* counts) {
+  struct Range { uint64_t begin, len; uint32_t entry; };
+  std::vector<Range> rg(m);
+  std::vector<zgk::Seek> recs(m);
+  std::vector<uint8_t> refused(m);
+  for (uint32_t j = 0; j < m; j++) {
+    const uint64_t* r = in + 11 * (size_t)j;
+    rg[j] = Range{r[1], r[2], (uint32_t)r[0]};
+    refused[j] = r[3] != 0;
+    recs[j] = zgk::Seek{r[7], r[8], r[9], 0, r[10], (uint32_t)r[4], (uint32_t)r[5], (uint32_t)r[6], 0, 0, 0};
+  }
+  const zgm::Groups g = zgm::group_ranges(rg.data(), recs.data(), refused.data(), m);
+  for (size_t k = 0; k < g.groups.size(); k++) {
+    const zgm::Group& x = g.groups[k];
+    const uint64_t row[7] = {x.entry, x.gfirst, x.glast, x.c_lo, x.c_hi, x.d_lo, x.d_hi};
+    memcpy(groups + 7 * k, row, sizeof row);
+  }
+  for (uint32_t j = 0; j < m; j++) { group_of[j] = g.group_of[j]; clip_of[j] = g.clip_of[j]; }
+  for (size_t q = 0; q < g.order.size(); q++) { order[q] = g.order[q]; skip[q] = g.skip[q]; }
+  for (size_t k = 0; k < g.first.size(); k++) first[k] = g.first[k];
+  counts[0] = g.order.size();
+  return (uint32_t)g.groups.size();
+}
 
 #ifdef SEEKMANY_MAIN
 // argv[1]: per entry [u64 length][u64 n][n x (u64 begin, u64 rlen)][bytes]; argv[2]: the records, 64 bytes each, in that order, once per chunk

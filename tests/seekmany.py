@@ -1,6 +1,6 @@
 """Many ranges over few seekable entries (zgpu_frames_seek_table_many_device, zgpu_gather_ranges_seek_table_device_src): a model in plain Python
-of how ranges form groups and of the order of a range's verdicts, written from the contract's text (include/zgpu.h), not from zg_frames.cpp.
-tests/test_seekmany_cpu.py checks it against hand-written cases; tests/test_gpu_gather_ranges.py takes its expectations from it."""
+of how ranges form groups and of the order of a range's verdicts, written from the contract's text (include/zgpu.h), not from zg_ranges.cpp.
+tests/test_seekmany_cpu.py checks it against hand-written cases and holds the C++ grouping (zg_seekmany.h: group_ranges) against it; tests/test_gpu_gather_ranges.py takes its expectations from it."""
 import zgpu
 
 E_TARGET_TOO_SMALL = zgpu.E_TARGET_TOO_SMALL

@@ -55,11 +55,10 @@ class Rec:
         self.status, self.frames_skipped, self.frames_taken = key[5], key[6], key[7]
 
 
-def group_decode(z, gfirst, glast, dict_raw=None):
-    """(status, bytes or None) of rows [gfirst, glast] of entry z: the oracle on those bytes, held to the sizes the frames declare and to the
-    table's promise — what test_gpu_seek_table.expect demands of a selection"""
-    cs, ds = rows(z)
-    C_, D_ = seekmany.prefixes(cs, ds)
+def group_verdict(z, C_, D_, gfirst, glast, dict_raw=None):
+    """(status, bytes or None) of rows [gfirst, glast] of an entry whose rows have the prefixes C_, D_, on the bytes z holds NOW: the oracle on
+    those bytes, held to the sizes the frames declare and to the promise of the table or index — what test_gpu_seek_table.expect demands of
+    a selection"""
     lo, hi = C_[gfirst], C_[glast + 1]
     st, out = _decode(z[lo:hi], dict_raw)
     if st:
@@ -72,12 +71,14 @@ def group_decode(z, gfirst, glast, dict_raw=None):
     return 0, out
 
 
-def expectations(entries, ranges, caps=None, dict_raw=None, group_status=None):
-    """(records, groups, group_of, [(status, bytes or None)]). group_status(entry, gfirst, glast): a checksum verdict the test knows of (it
-    ranks behind TARGET_TOO_SMALL), or 0"""
-    recs = [record(entries, r) for r in ranges]
-    grps, group_of = seekmany.groups(ranges, [Rec(k) for k in recs])
-    decoded = [group_decode(entries[e], a, b, dict_raw) for e, a, b, _ in grps]
+def group_decode(z, gfirst, glast, dict_raw=None):
+    """group_verdict on the entry's own seek table"""
+    return group_verdict(z, *seekmany.prefixes(*rows(z)), gfirst, glast, dict_raw)
+
+
+def range_verdicts(ranges, recs, grps, group_of, decoded, d_lo, caps=None, group_status=None):
+    """[(status, bytes or None)] per range, from its record, its group's (status, bytes) in decoded and where that group's plaintext begins,
+    d_lo(entry, gfirst). group_status(entry, gfirst, glast): a checksum verdict the test knows of (it ranks behind TARGET_TOO_SMALL), or 0"""
     out = []
     for j, (r, k) in enumerate(zip(ranges, recs)):
         if k[5]:
@@ -85,32 +86,49 @@ def expectations(entries, ranges, caps=None, dict_raw=None, group_status=None):
         elif group_of[j] is None:
             out.append((0, b""))
         else:
-            e, a, b, members = grps[group_of[j]]
+            e, a, b, _ = grps[group_of[j]]
             st, data = decoded[group_of[j]]
-            d_lo = seekmany.prefixes(*rows(entries[e]))[1][a]
-            clip = data[r[1] - d_lo:][:r[2]] if data is not None else None
+            clip = data[r[1] - d_lo(e, a):][:r[2]] if data is not None else None
             small = clip is not None and caps is not None and len(clip) > caps[j]
             st = seekmany.verdict(decode=st, small=small, checksum=group_status(e, a, b) if group_status and not st else 0)
             out.append((st, clip if st == 0 else None))
-            if len(members) == 1 and not (group_status and group_status(e, a, b)):   # alone in its group: today's call, the existing expectation
-                assert out[-1] == expect(entries[e], (r[1], r[2]), None if caps is None else caps[j], dict_raw), (j, r)
+    return out
+
+
+def expectations(entries, ranges, caps=None, dict_raw=None, group_status=None):
+    """(records, groups, group_of, [(status, bytes or None)]); group_status: as range_verdicts takes it"""
+    recs = [record(entries, r) for r in ranges]
+    grps, group_of = seekmany.groups(ranges, [Rec(k) for k in recs])
+    decoded = [group_decode(entries[e], a, b, dict_raw) for e, a, b, _ in grps]
+    out = range_verdicts(ranges, recs, grps, group_of, decoded, lambda e, a: seekmany.prefixes(*rows(entries[e]))[1][a], caps, group_status)
+    for e, a, b, members in grps:
+        if len(members) == 1 and not (group_status and group_status(e, a, b)):   # alone in its group: today's call, the existing expectation
+            j = members[0]
+            assert out[j] == expect(entries[e], ranges[j][1:3], None if caps is None else caps[j], dict_raw), (j, ranges[j])
     return recs, grps, group_of, out
+
+
+def run_checked(call, s, ranges, recs, exps, caps=None, shifts=None):
+    """call(dst_ptrs, caps) -> (results, seeks): ONE gather call of the ranges on the sources s into an arena with guard bytes, checked against
+    the models' records and expectations; (arena, results, seeks)"""
+    if caps is None:
+        caps = [(len(d) if d is not None else 96) + (7 if j % 2 else 0) for j, (_, d) in enumerate(exps)]
+    a = Arena(caps, shifts if shifts is not None else [j % 5 for j in range(len(ranges))])
+    res, seeks = call(a.ptrs, caps)
+    for j, ((st, d), r, k) in enumerate(zip(exps, res, seeks)):
+        assert k.key() == recs[j], (j, ranges[j], k, recs[j])
+        assert r.status == st, (j, ranges[j], r, k, st)
+        assert r.written == (len(d) if st == 0 else 0), (j, ranges[j], r, k)
+    a.check([d for _, d in exps])
+    assert s.unchanged()
+    return a, res, seeks
 
 
 def run_gather(c, entries, ranges, caps=None, shifts=None, dict_raw=None, group_status=None, src=None, **kw):
     """the ranges in ONE call, checked against the models; (arena, results, seeks, expectations, groups, group_of)"""
     s = src or Sources(entries)
     recs, grps, group_of, exps = expectations(entries, ranges, caps, dict_raw, group_status)
-    if caps is None:
-        caps = [(len(d) if d is not None else 96) + (7 if j % 2 else 0) for j, (_, d) in enumerate(exps)]
-    a = Arena(caps, shifts if shifts is not None else [j % 5 for j in range(len(ranges))])
-    res, seeks = c.gather_ranges_seek_table_device_src(s.ptrs, s.lens, ranges, a.ptrs, caps, **kw)
-    for j, ((st, d), r, k) in enumerate(zip(exps, res, seeks)):
-        assert k.key() == recs[j], (j, ranges[j], k)
-        assert r.status == st, (j, ranges[j], r, k, st)
-        assert r.written == (len(d) if st == 0 else 0), (j, ranges[j], r, k)
-    a.check([d for _, d in exps])
-    assert s.unchanged()
+    a, res, seeks = run_checked(lambda ptrs, cp: c.gather_ranges_seek_table_device_src(s.ptrs, s.lens, ranges, ptrs, cp, **kw), s, ranges, recs, exps, caps, shifts)
     return a, res, seeks, exps, grps, group_of
 
 

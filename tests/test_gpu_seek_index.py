@@ -21,7 +21,7 @@ from devmem import ALL, Arena, Sources, full_key, xxh32
 from golden_io import read_manifest, read_pack
 from seekidx import U64
 from test_gpu_decode_ranges import _decode, _edit, chain
-from test_gpu_gather_ranges import BAD_ARG_REC, Rec, _eight_frames
+from test_gpu_gather_ranges import BAD_ARG_REC, Rec, _eight_frames, group_verdict, range_verdicts, run_checked
 from test_gpu_seek_table import _unsized_entry, seekable
 from test_walk_cpu import skippable
 
@@ -50,21 +50,6 @@ def _six_declared():
     return [zgdata.zstd_compress(p, checksum=True, content_size=True) for p in plains], plains
 
 
-def group_verdict(z, C_, D_, gfirst, glast, dict_raw=None):
-    """(status, bytes or None) of rows [gfirst, glast] of an index with prefixes C_, D_ on the bytes z holds NOW: the oracle on those bytes,
-    held to the sizes the frames declare and to the index's promise"""
-    lo, hi = C_[gfirst], C_[glast + 1]
-    st, out = _decode(z[lo:hi], dict_raw)
-    if st:
-        return st, None
-    for f in chain(z[lo:hi]):
-        if f.kind == "frame" and f.fcs is not None and len(_decode(z[lo + f.begin:lo + f.end], dict_raw)[1]) != f.fcs:
-            return zgpu.E_CONTENT_SIZE_MISMATCH, None
-    if len(out) != D_[glast + 1] - D_[gfirst]:
-        return zgpu.E_CONTENT_SIZE_MISMATCH, None
-    return 0, out
-
-
 def expectations(entries, ranges, caps=None, dict_raw=None, group_status=None, indexed=None, now=None):
     """(records, groups, group_of, [(status, bytes or None)]) of declared-kind entries. indexed: the bytes the index was built from (default:
     entries); now: the bytes the entries hold when the gather runs (default: the same)"""
@@ -83,36 +68,14 @@ def expectations(entries, ranges, caps=None, dict_raw=None, group_status=None, i
             recs.append(seekidx.record(C_, D_, len(indexed[r[0]]), r[1], r[2]))
     grps, group_of = seekmany.groups(ranges, [Rec(k) for k in recs])
     decoded = [group_verdict(now[e], idx[e][1], idx[e][2], a, b, dict_raw) for e, a, b, _ in grps]
-    out = []
-    for j, (r, k) in enumerate(zip(ranges, recs)):
-        if k[5]:
-            out.append((k[5], None))
-        elif group_of[j] is None:
-            out.append((0, b""))
-        else:
-            e, a, b, _ = grps[group_of[j]]
-            st, data = decoded[group_of[j]]
-            clip = data[r[1] - idx[e][2][a]:][:r[2]] if data is not None else None
-            small = clip is not None and caps is not None and len(clip) > caps[j]
-            st = seekmany.verdict(decode=st, small=small, checksum=group_status(e, a, b) if group_status and not st else 0)
-            out.append((st, clip if st == 0 else None))
-    return recs, grps, group_of, out
+    return recs, grps, group_of, range_verdicts(ranges, recs, grps, group_of, decoded, lambda e, a: idx[e][2][a], caps, group_status)
 
 
 def run_indexed(c, index, s, entries, ranges, caps=None, lens=None, **kw):
     """the ranges in ONE indexed gather call, checked against the models; (arena, results, seeks, expectations, groups)"""
     gkw = {k: kw.pop(k) for k in ("dict_raw", "group_status", "indexed", "now") if k in kw}
     recs, grps, group_of, exps = expectations(entries, ranges, caps, **gkw)
-    if caps is None:
-        caps = [(len(d) if d is not None else 96) + (7 if j % 2 else 0) for j, (_, d) in enumerate(exps)]
-    a = Arena(caps, [j % 5 for j in range(len(ranges))])
-    res, seeks = c.gather_ranges_indexed_device_src(index, s.ptrs, lens or s.lens, ranges, a.ptrs, caps, **kw)
-    for j, ((st, d), r, k) in enumerate(zip(exps, res, seeks)):
-        assert k.key() == recs[j], (j, ranges[j], k, recs[j])
-        assert r.status == st, (j, ranges[j], r, k, st)
-        assert r.written == (len(d) if st == 0 else 0), (j, ranges[j], r, k)
-    a.check([d for _, d in exps])
-    assert s.unchanged()
+    a, res, seeks = run_checked(lambda ptrs, cp: c.gather_ranges_indexed_device_src(index, s.ptrs, lens or s.lens, ranges, ptrs, cp, **kw), s, ranges, recs, exps, caps)
     return a, res, seeks, exps, grps
 
 

@@ -238,22 +238,131 @@ def test_seekmany_argument_rules_need_no_gpu():
 S = lambda skipped, taken, status=0: NS(status=status, frames_skipped=skipped, frames_taken=taken)   # noqa: E731
 
 
-def test_group_model_on_hand_written_cases():
+def hand_written_groups():
+    """[(ranges, seeks, (groups, group_of))]: what the contract's text says of each case"""
+    out = []
     # rows: a [0, 2], b [2, 3] share row 2; c [4, 4] touches neither; d [3, 4] joins b and c to them: one group, transitively
     ranges = [(0, 0, 10), (0, 20, 10), (0, 40, 1)]
     seeks = [S(0, 3), S(2, 2), S(4, 1)]
-    assert seekmany.groups(ranges, seeks) == ([(0, 0, 3, [0, 1]), (0, 4, 4, [2])], [0, 0, 1])
-    assert seekmany.groups(ranges + [(0, 35, 6)], seeks + [S(3, 2)]) == ([(0, 0, 4, [0, 1, 2, 3])], [0, 0, 0, 0])
+    out.append((ranges, seeks, ([(0, 0, 3, [0, 1]), (0, 4, 4, [2])], [0, 0, 1])))
+    out.append((ranges + [(0, 35, 6)], seeks + [S(3, 2)], ([(0, 0, 4, [0, 1, 2, 3])], [0, 0, 0, 0])))
     # order does not matter; entries never share a group; adjacent rows that share none stay apart
     ranges = [(1, 0, 5), (0, 7, 5), (0, 0, 5), (1, 9, 5)]
     seeks = [S(0, 1), S(1, 1), S(0, 1), S(0, 2)]
-    assert seekmany.groups(ranges, seeks) == ([(0, 0, 0, [2]), (0, 1, 1, [1]), (1, 0, 1, [0, 3])], [2, 1, 0, 2])
+    out.append((ranges, seeks, ([(0, 0, 0, [2]), (0, 1, 1, [1]), (1, 0, 1, [0, 3])], [2, 1, 0, 2])))
     # no group: a length of 0, a failed record, nothing taken
     ranges = [(0, 0, 0), (0, 0, 5), (0, 99, 5), (0, 1, 1)]
     seeks = [S(0, 0), S(0, 0, zgpu.E_SEEK_TABLE), S(7, 0), S(0, 1)]
-    assert seekmany.groups(ranges, seeks) == ([(0, 0, 0, [3])], [None, None, None, 0])
+    out.append((ranges, seeks, ([(0, 0, 0, [3])], [None, None, None, 0])))
     # a range inside another one's interval
-    assert seekmany.groups([(0, 0, 99), (0, 50, 1)], [S(0, 9), S(4, 1)]) == ([(0, 0, 8, [0, 1])], [0, 0])
+    out.append(([(0, 0, 99), (0, 50, 1)], [S(0, 9), S(4, 1)], ([(0, 0, 8, [0, 1])], [0, 0])))
+    return out
+
+
+def test_group_model_on_hand_written_cases():
+    for ranges, seeks, want in hand_written_groups():
+        assert seekmany.groups(ranges, seeks) == want
+
+
+def c_groups(L, ranges, seeks, tables):
+    """zgm::group_ranges (zg_seekmany.h, through tests/emu/zg_emu_seekmany.cpp) on ranges[j] = (entry, begin, len) and their records, and the
+    demands that need no model: tables[entry] = (C, D), the prefix sums a record's byte and plaintext offsets are taken from — a group spans
+    [C[gfirst], C[glast + 1]) and [D[gfirst], D[glast + 1]), every range that takes rows is one clip of its group's span, in the order of the
+    sort, and the clip begins begin - D[gfirst] bytes into the group's plaintext. A range that takes no rows is handed offsets that would show
+    in a group if it were looked at. Returns (groups, group_of) in the form of seekmany.groups."""
+    m = len(ranges)
+    flat, takes = [], []
+    for r, s in zip(ranges, seeks):
+        takes.append(bool(r[2]) and s.status == 0 and s.frames_taken > 0)
+        C_, D_ = tables[r[0]]
+        a, b = s.frames_skipped, s.frames_skipped + s.frames_taken
+        ref = s.status == zgpu.E_BAD_ARG                      # (a refused range: told apart by its flag alone, as in front of accept_records)
+        flat += [r[0], r[1], r[2], int(ref), 0 if ref else s.status, a, b - a] + ([C_[a], C_[b], D_[a], D_[b]] if takes[-1] else [1 << 62, 5, 1 << 61, 3])
+    u32, u64 = C.c_uint32 * max(m, 1), C.c_uint64 * max(m, 1)
+    grp, group_of, clip_of, order, first, skip, counts = (C.c_uint64 * (7 * max(m, 1)))(), u32(), u32(), u32(), (C.c_uint32 * (m + 1))(), u64(), (C.c_uint64 * 1)()
+    G = L.zgemu_group_ranges((C.c_uint64 * max(len(flat), 1))(*flat), m, grp, group_of, clip_of, order, first, skip, counts)
+    nclips = counts[0]
+    assert nclips == sum(takes) and sorted(order[:nclips]) == [j for j in range(m) if takes[j]]
+    assert first[0] == 0 and first[G] == nclips and all(first[g] < first[g + 1] for g in range(G))
+    members = [[] for _ in range(G)]
+    for j in range(m):
+        if not takes[j]:
+            continue
+        g, q = group_of[j], clip_of[j]
+        entry, gfirst, glast, c_lo, c_hi, d_lo, d_hi = grp[7 * g:7 * g + 7]
+        C_, D_ = tables[entry]
+        assert entry == ranges[j][0] and first[g] <= q < first[g + 1] and order[q] == j, (j, g, q)
+        assert (c_lo, c_hi, d_lo, d_hi) == (C_[gfirst], C_[glast + 1], D_[gfirst], D_[glast + 1]), (j, g)
+        assert gfirst <= seeks[j].frames_skipped and seeks[j].frames_skipped + seeks[j].frames_taken - 1 <= glast
+        assert skip[q] == (ranges[j][1] - D_[gfirst]) % 2 ** 64, (j, skip[q])
+        members[g].append(j)
+    return [tuple(grp[7 * g:7 * g + 3]) + (members[g],) for g in range(G)], [group_of[j] if takes[j] else None for j in range(m)]
+
+
+def random_ranges(rng, tables, m):
+    """m ranges over the tables' entries with their records: short spans, spans that touch the one in front at one row, nested ones, duplicates,
+    lengths of 0, failed records, refused ranges and records that take nothing"""
+    ranges, seeks = [], []
+    for _ in range(m):
+        e = rng.randrange(len(tables))
+        D_ = tables[e][1]
+        nrows = len(D_) - 1
+        kind = rng.choice(["span", "span", "span", "touch", "nested", "same", "empty", "failed", "refused", "nothing"])
+        prev = [(r, s) for r, s in zip(ranges, seeks) if r[0] == e and r[2] and s.status == 0 and s.frames_taken]
+        if kind in ("touch", "nested", "same") and not prev:
+            kind = "span"
+        if kind == "span":
+            a = rng.randrange(nrows)
+            b = min(nrows - 1, a + rng.choice([0, 0, 0, 1, 2, 5]))
+        elif kind == "touch":       # begins at the last row of a range in front of it
+            r, s = rng.choice(prev)
+            a = s.frames_skipped + s.frames_taken - 1
+            b = min(nrows - 1, a + rng.choice([0, 1, 3]))
+        elif kind == "nested":
+            r, s = rng.choice(prev)
+            a = rng.randrange(s.frames_skipped, s.frames_skipped + s.frames_taken)
+            b = rng.randrange(a, s.frames_skipped + s.frames_taken)
+        if kind == "same":
+            r, s = rng.choice(prev)
+            ranges.append(r)
+            seeks.append(s)
+        elif kind == "empty":
+            ranges.append((e, rng.randrange(D_[-1] + 9), 0))
+            seeks.append(S(0, 0))
+        elif kind in ("failed", "refused"):
+            ranges.append((e, rng.randrange(D_[-1] + 9), rng.randint(1, 99)))
+            seeks.append(S(rng.randrange(nrows), rng.randint(0, 3), zgpu.E_SEEK_TABLE if kind == "failed" else zgpu.E_BAD_ARG))
+        elif kind == "nothing":
+            ranges.append((e, D_[-1] + rng.randrange(9), rng.randint(1, 99)))
+            seeks.append(S(nrows, 0))
+        else:
+            ranges.append((e, rng.randint(D_[a], D_[a + 1]), rng.randint(1, 2 * (D_[b + 1] - D_[a]) + 1)))
+            seeks.append(S(a, b - a + 1))
+    return ranges, seeks
+
+
+def test_the_grouping_of_the_gather_calls_equals_the_model(built):
+    """zgm::group_ranges is the code zg_ranges.cpp's gather_groups calls; the emulator build compiles zg_seekmany.h alone, so nothing here
+    depends on zg_frames.cpp, zg_ranges.cpp or a GPU."""
+    L, _, _ = built
+    vp = C.c_void_p
+    L.zgemu_group_ranges.argtypes = [vp, C.c_uint32] + [vp] * 7
+    L.zgemu_group_ranges.restype = C.c_uint32
+    flat = seekmany.prefixes([7] * 64, [100] * 64)           # the hand-written cases name rows, not bytes: any table serves
+    for ranges, seeks, want in hand_written_groups():
+        assert c_groups(L, ranges, seeks, [flat, flat]) == want == seekmany.groups(ranges, seeks)
+    assert c_groups(L, [], [], [flat]) == ([], [])
+    rng = random.Random(0x6E0095)
+    tables = [seekmany.prefixes([rng.randint(0, 9) for _ in range(nrows)], [rng.choice([0, 1, 50, 3000]) for _ in range(nrows)]) for nrows in (40, 17, 1)]
+    total, ngroups, shared = 0, 0, 0
+    for m in (6, 20, 60, 120, 250):                          # sparse calls, where most ranges are alone, to dense ones
+        ranges, seeks = random_ranges(rng, tables, m)
+        got = c_groups(L, ranges, seeks, tables)
+        assert got == seekmany.groups(ranges, seeks), m
+        total += m
+        ngroups += len(got[0])
+        shared += sum(len(g[3]) > 1 for g in got[0])
+    assert total > 400 and ngroups >= 30 and shared >= 15, (total, ngroups, shared)   # (the draw itself: groups of one range and of many)
 
 
 def test_verdict_model_keeps_the_rank_order():

@@ -47,7 +47,7 @@ struct zgpu_ctx {
   std::map<uint32_t, ZgDictDev> dict_dev;         // freed with the context; an entry goes when zgpu_add_dict replaces its dictionary
   bool frames_shared_dicts = false;               // zgpu_set_frames_shared_dicts
   uint32_t frames_submits = 0;        // submits the last zgpu_decode_frames call ran (zgpu_debug_frames_submits)
-  // of the last call of their family (zg_frames.cpp: reset_stats says which call owns which)
+  // of the last call of their family (zg_frames_int.h: reset_stats says which call owns which)
   uint64_t frames_dict_stats[kDictStatCount] = {};        // zgpu_decode_frames* and the decode_ranges calls (zgpu_debug_frames_dict_stats)
   uint64_t frames_device_stats[kDevStatCount] = {};       // the calls with a device sink (zgpu_debug_frames_device_stats)
   uint64_t frames_device_src_stats[kSrcStatCount] = {};   // the calls with device sources (zgpu_debug_frames_device_src_stats)

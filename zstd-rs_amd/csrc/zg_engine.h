@@ -282,7 +282,7 @@ class Engine {
   struct ManyRange { uint64_t begin, rlen; uint32_t entry; };
   struct ManyStats { uint64_t prefix_launches = 0, prefix_us = 0, find_launches = 0, find_us = 0, scratch_bytes = 0; };
   int seekmany_pass(const DevEntry* e, uint32_t ne, const ManyRange* ranges, uint32_t m, zgk::Seek* out, uint64_t* stats, ManyStats* more);
-  // The two halves of seekmany_pass, for a caller that keeps the pairs (zgpu_seek_index, zg_frames.cpp). seekmany_prefixes: the locate pass
+  // The two halves of seekmany_pass, for a caller that keeps the pairs (zgpu_seek_index, zg_ranges.cpp). seekmany_prefixes: the locate pass
   // and the two prefix launches; loc[i] = what locate found of entry i, pre[i] = the index of its pair 0 in *scratch (usable tables only),
   // *npairs = the pairs of prefixes at the front of *scratch (the chunk totals lie behind them); the caller releases *scratch.
   // seekmany_find: ONE find launch over m lanes the caller laid out on `pairs`; its download is added to stats[kPassBytes] (stats may be null).

@@ -27,20 +27,15 @@
 // in zgpu_decode_all's order for such an entry — frame by frame (zg_decode_all_per_frame) — and what the submit cannot serve exactly (an
 // unregistered id, Unsupported / Internal: the dictionary splice behind a drain inside decode_all, zg_exact.h) goes alone as before.
 //
-// zgpu_gather_ranges_seek_table_device_src takes m ranges that each name one of n seekable entries (zg_seekmany.h: every table scanned once,
-// every range a binary search). The ranges of one entry whose table rows overlap form a group; a group is ONE entry of this file's machinery,
-// decoded once, and every range of it is a clip of the group's span (Ranges) with its own destination. The calls with one range per entry are
-// the case of spans of one clip. zgpu_gather_ranges_indexed_device_src is the same call behind another selection: a zgpu_seek_index keeps
-// the prefix sums of its entries' rows in device memory — built from their seek tables, or from their header chains where every frame
-// declares its size (zg_seekidx.h) —, indexed_ranges finds every range's rows in them with one launch, and gather_groups is shared.
-//
 // How a call is put together. A Call is what every call has (context, sources, lengths, destinations, capacities, the shared-dictionary
-// lookup) plus up to three parts that an entry point builds and hangs in: DeviceSink (device_sink: the options, the one place that refuses
+// lookup) plus up to three parts that are built for it and hung in: DeviceSink (device_sink: the options, the one place that refuses
 // ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY), DeviceSources (check_entries + device_sources: pointer checks, zg_k_walk, bounds) and Ranges
-// (decode_ranges: the clips). decode_submit, the sinks, decode_alone_device and decode_entries ask for a part by its pointer — `if (k.sink)`,
-// `if (k.src)`, `if (k.ranges)` — never by which field happens to be set. Around them: reset_stats zeroes the statistics a call family owns
-// (kOwns*), check_entries is the one pointer check in front of the engine's lane passes, drain the two-stream wait every call ends with,
-// SubmitHash the hashing both sinks start before they copy. Every statistics slot is written under its name (zg_capi_int.h, kPass*).
+// (decode_selections: the clips; the one place that builds a Call with all three, for the range calls of zg_ranges.cpp, which are front-ends
+// of this machinery — zg_frames_int.h declares what crosses that seam). decode_submit, the sinks, decode_alone_device and
+// decode_entries ask for a part by its pointer — `if (k.sink)`, `if (k.src)`, `if (k.ranges)` — never by which field happens to be set.
+// Around them: reset_stats zeroes the statistics a call family owns (kOwns*), device_ptr_ok is the one question asked of a pointer and
+// check_entries / check_entry_ranges the two loops that ask it in front of the engine's lane passes, drain the two-stream wait every call
+// ends with, SubmitHash the hashing both sinks start before they copy. Every statistics slot is written under its name (zg_capi_int.h, kPass*).
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -50,12 +45,13 @@
 #include <thread>
 #include <utility>
 #include <vector>
-#include "zg_capi_int.h"
+#include "zg_frames_int.h"
 #include "zg_scatter.h"
 #include "zg_seeksums.h"
 #include "zg_xxh64_dev.h"
 
 using namespace zg;
+using namespace zgf;
 
 namespace {
 
@@ -128,23 +124,8 @@ const DictFacts* shared_find(const void* user, uint32_t id) {
   return it == c->dict_facts.end() || it->second.content_len == 0 ? nullptr : &it->second;
 }
 
-// The three parts only some calls have; each lives in its entry point's frame, and an absent one is a null pointer in the Call.
-// destinations in device memory of the caller (zgpu_decode_frames_device and every call built on it)
-struct DeviceSink {
-  zgpu_device_entry_result* res = nullptr;
-  uint64_t hash_max = 0;          // the caller's (no estimate): frames up to this length are hashed
-  bool no_hash = false;           // ZGPU_DEVICE_NO_HASH: hash no frame
-  bool verify = false;            // ZGPU_DEVICE_VERIFY: a mismatch fails the entry, with nothing of it written
-  bool hash_all = false;          // verify with hash_max_bytes == 0: every frame that carries a Content_Checksum is hashed
-  // ZGPU_DEVICE_VERIFY_SEEK_TABLE (zg_seeksums.h): the WHOLE entries — Call::srcs are the selections — and the table rows of each selection;
-  // empty: the flag is not set. An entry with taken == 0 is not looked at. table_all: hash_max_bytes == 0, every frame of such an entry is hashed
-  struct TableEntry { uint64_t src, len; uint32_t first, taken; };
-  std::vector<TableEntry> table_verify;
-  bool table_flag = false, table_all = false;
-  bool table(uint32_t i) const { return !table_verify.empty() && table_verify[i].taken != 0; }
-  uint64_t* stats = nullptr;      // zgpu_ctx::frames_device_stats (kDevStat*)
-  uint64_t alone_written = 0;     // bytes the entries decoded alone brought to their destinations
-};
+// The three parts only some calls have; each lives in the frame of the function that builds it, and an absent one is a null pointer in the
+// Call. DeviceSink: destinations in device memory of the caller (zg_frames_int.h).
 // sources in device memory (zgpu_decode_frames_device_src): Call::srcs[i] is device memory; what was found out about every entry before the
 // first submit
 struct DeviceSources {
@@ -155,18 +136,13 @@ struct DeviceSources {
   std::vector<uint64_t> bound;          // plaintext_bound of every entry, from its records
   uint64_t* stats = nullptr;            // zgpu_ctx::frames_device_src_stats (kSrcStat*)
 };
-// ranges (zgpu_decode_ranges_device_src): the entries are the selections zg_k_seek found, and of the concatenation of an entry's decoded frames
-// only [skip, skip + len) goes to its destination. declared: what the selection's frames declare together, UINT64_MAX if one declares nothing
-// A sub-entry has a SPAN of clips, clip[first[i] .. first[i + 1]): each takes its own bytes to its own destination (the calls with one range
-// per entry have spans of one; zgpu_gather_ranges_seek_table_device_src one clip per range of a group). small / written: the clip's own verdict
-// and count once the sub-entry's frames are measured (Call::fit); they mean something only where the sub-entry stands at status 0.
+// ranges (decode_selections): the entries are selections of whole entries, each with a span of clips (zg_frames_int.h: Selection, Clip)
 struct Ranges {
-  struct Clip { uint64_t skip, len; uint8_t* dst; uint64_t cap; uint64_t written; bool small; };
-  std::vector<Clip> clip;
-  std::vector<uint32_t> first;          // n + 1 slots
-  std::vector<uint64_t> declared;       // per sub-entry
-  bool promise = false;                 // (zgpu_decode_ranges_seek_table_device_src) declared is the seek table's promise: it always holds
-  uint64_t* stats = nullptr;            // zgpu_ctx::ranges_stats (kRangeStat*)
+  std::vector<Clip>& clip;
+  const std::vector<uint32_t>& first;   // n + 1 slots
+  std::vector<uint64_t> declared;       // per sub-entry (Selection::declared)
+  bool promise;                         // declared is a seek table's promise: it always holds
+  uint64_t* stats;                      // zgpu_ctx::ranges_stats (kRangeStat*)
 };
 
 struct Call {
@@ -197,7 +173,7 @@ struct Call {
     uint64_t sum = 0;
     bool any = false;
     for (uint32_t q = ranges->first[i]; q < ranges->first[i + 1]; q++) {
-      Ranges::Clip& cl = ranges->clip[q];
+      Clip& cl = ranges->clip[q];
       const uint64_t rest = bytes > cl.skip ? bytes - cl.skip : 0, w = rest < cl.len ? rest : cl.len;
       cl.small = w > cl.cap;
       cl.written = cl.small ? 0 : w;
@@ -439,7 +415,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
         for (uint32_t f = ff[j]; f < ff[j + 1]; f++) { cat += fo[f].out_size; ends.push_back(cat); }
       }
       for (uint32_t q = q0; q < q1; q++) {
-        const Ranges::Clip* cl = k.ranges ? &k.ranges->clip[q] : nullptr;
+        const Clip* cl = k.ranges ? &k.ranges->clip[q] : nullptr;
         if (cl && cl->small) continue;
         const uint64_t lo = cl ? cl->skip : 0, hi = cl && cl->len < UINT64_MAX - lo ? lo + cl->len : UINT64_MAX;
         const uint64_t dst = (uint64_t)(uintptr_t)(cl ? cl->dst : k.dsts[idx[j]]), cap = cl ? cl->cap : k.caps[idx[j]];
@@ -690,7 +666,7 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
     const uint64_t decoded = d.r.written;
     d.r.written = fits;
     for (uint32_t q = k.ranges->first[i]; q < k.ranges->first[i + 1] && !st; q++) {
-      const Ranges::Clip& cl = k.ranges->clip[q];
+      const Clip& cl = k.ranges->clip[q];
       const size_t from = (size_t)(cl.skip < decoded ? cl.skip : decoded);
       if (!cl.small && cl.written && hipMemcpy(cl.dst, tmp + from, cl.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
     }
@@ -706,96 +682,6 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   free(tmp);
   sink.stats[kDevStatEntriesAlone]++;
   return st;
-}
-
-// Is [p, p + cap) device memory of one allocation on the context's device? Asked of the HIP runtime, before any launch, of every destination
-// and — zgpu_decode_frames_device_src — of every source. `known` remembers the allocations already seen in this call: entries usually share a
-// few (a torch tensor cut into slots).
-struct DevRange { uintptr_t lo, hi; };
-bool check_device_range(int device, const void* p, size_t cap, std::vector<DevRange>& known) {
-  if (!p) return false;
-  const uintptr_t a = (uintptr_t)p;
-  if (cap > UINTPTR_MAX - a) return false;
-  for (const DevRange& r : known) if (a >= r.lo && a + cap <= r.hi) return true;
-  hipPointerAttribute_t at;
-  memset(&at, 0, sizeof at);
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (an address the runtime does not know)
-  if (at.type != hipMemoryTypeDevice || at.device != device) return false;                        // (host, managed, unregistered, another GPU)
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const uintptr_t lo = (uintptr_t)base;
-  if (a < lo || size > UINTPTR_MAX - lo || a + cap > lo + size) return false;
-  known.push_back(DevRange{lo, lo + size});
-  return true;
-}
-
-// Every pointer of a call's entries checked, and the entries as the engine takes them: a refused entry has length 0 — nothing of it is
-// read — and refused[i] = 1. dsts / caps: nullptr for a call without destinations. pre(i), the call's own reasons: kCheck — the pointers
-// decide; kRefuse — refused without a look at them; kPass — never refused, whatever its pointers are (nothing of it will be touched).
-enum { kCheck = 0, kRefuse, kPass };
-template <class Pre>
-void check_entries(zgpu_ctx* c, const void* const* srcs, const size_t* lens, void* const* dsts, const size_t* caps, uint32_t n, Pre pre,
-                   std::vector<Engine::DevEntry>* dev, std::vector<uint8_t>* refused) {
-  dev->resize(n);
-  refused->assign(n, 0);
-  std::vector<DevRange> known;   // (per call: what the runtime says of an allocation holds for as long as the caller keeps its promise)
-  const int device = c->eng->device();
-  for (uint32_t i = 0; i < n; i++) {
-    const int p = pre(i);
-    bool bad = p == kRefuse;
-    if (p == kCheck) {
-      bad = (!srcs[i] && lens[i]) || (dsts && !dsts[i] && caps[i]);
-      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
-      if (!bad && dsts && caps[i]) bad = !check_device_range(device, dsts[i], caps[i], known);
-    }
-    (*refused)[i] = bad;
-    (*dev)[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], bad ? 0u : (uint64_t)lens[i]};
-  }
-}
-inline int check_all(uint32_t) { return kCheck; }
-
-// the zgpu_debug_*_stats getters: the first n slots of an array, or all it has; returns how many
-template <size_t N> int copy_stats(const uint64_t (&a)[N], uint64_t* out, int n) {
-  if (!out) return 0;
-  int k = 0;
-  for (; k < n && k < (int)N; k++) out[k] = a[k];
-  return k;
-}
-
-// The statistics a call family owns, zeroed at its start (after its arguments passed): the one place that says which arrays a call writes.
-enum : unsigned { kOwnsDecode = 1 /* frames_submits, frames_dict_stats */, kOwnsDevice = 2, kOwnsSrc = 4, kOwnsIndex = 8, kOwnsRanges = 16 };
-void reset_stats(zgpu_ctx* c, unsigned owned) {
-  auto zero = [](auto& a) { for (uint64_t& x : a) x = 0; };
-  if (owned & kOwnsDecode) { c->frames_submits = 0; zero(c->frames_dict_stats); }
-  if (owned & kOwnsDevice) zero(c->frames_device_stats);
-  if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
-  if (owned & kOwnsIndex) zero(c->frames_index_stats);
-  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); }
-}
-
-// The end of every call that launched something: nothing of it is in flight on the engine's two streams (the scatter ran on the second), so
-// every later operation on any stream sees its bytes. The call's first status stands.
-int drain(zgpu_ctx* c, int st) {
-  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
-  return st;
-}
-
-// The device sink of a call, from its options. ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY (hash nothing, verify everything) is refused: *st.
-// ZGPU_DEVICE_VERIFY_SEEK_TABLE is refused the same way with ZGPU_DEVICE_NO_HASH, and on every call but the two that have a seek table (table).
-DeviceSink device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st, bool table = false) {
-  const uint32_t flags = opts ? opts->flags : 0u;
-  DeviceSink s;
-  s.res = results;
-  s.hash_max = opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax;
-  s.no_hash = (flags & ZGPU_DEVICE_NO_HASH) != 0;
-  s.verify = (flags & ZGPU_DEVICE_VERIFY) != 0;
-  s.hash_all = s.verify && !opts->hash_max_bytes;
-  s.stats = c->frames_device_stats;
-  s.table_flag = (flags & ZGPU_DEVICE_VERIFY_SEEK_TABLE) != 0;
-  s.table_all = s.table_flag && !opts->hash_max_bytes;
-  *st = (s.no_hash && (s.verify || s.table_flag)) || (s.table_flag && !table) ? ZGPU_E_BAD_ARG : ZGPU_OK;
-  return s;
 }
 
 // The device sources of a call whose pointers are checked (src->dev, src->refused): every entry's header chain walked on the device (two
@@ -827,9 +713,9 @@ int decode_entries(Call& k, uint32_t n) {
     if (i < n) {
       if (k.sink) memset(&k.sink->res[i], 0, sizeof k.sink->res[i]);
       else memset(&k.res[i], 0, sizeof k.res[i]);
-      bool bad = (!k.srcs[i] && k.lens[i]) || (!k.dsts[i] && k.caps[i]);   // (what zgpu_decode_all returns)
+      bool bad = !k.srcs[i] && k.lens[i];                                  // (host sources: what zgpu_decode_all returns)
       if (k.src) bad = k.src->refused[i] != 0;                             // (device sources: checked before the walk)
-      else if (!bad && k.sink && k.caps[i]) bad = !check_device_range(c->eng->device(), k.dsts[i], k.caps[i], known);
+      else if (!bad) bad = k.sink ? !device_ptr_ok(c->eng->device(), k.dsts[i], k.caps[i], known) : !k.dsts[i] && k.caps[i];
       if (bad) { k.result(i).status = k.src && k.src->refused[i] > 1 ? k.src->refused[i] : ZGPU_E_BAD_ARG; continue; }   // (refused[i] > 1: the status itself)
       bound = k.src ? k.src->bound[i] : plaintext_bound(k.srcs[i], k.lens[i], k.dicts());   // (with its dictionary frames' gaps)
     }
@@ -859,6 +745,54 @@ int finish_device_call(Call& k, uint32_t n, int st) {
 }
 
 }  // namespace
+
+// ---- what the front-ends share with the calls below (zg_frames_int.h) -------------------------------------------------------------------------
+bool zgf::check_device_range(int device, const void* p, size_t cap, std::vector<DevRange>& known) {
+  if (!p) return false;
+  const uintptr_t a = (uintptr_t)p;
+  if (cap > UINTPTR_MAX - a) return false;
+  for (const DevRange& r : known) if (a >= r.lo && a + cap <= r.hi) return true;
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (an address the runtime does not know)
+  if (at.type != hipMemoryTypeDevice || at.device != device) return false;                        // (host, managed, unregistered, another GPU)
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  const uintptr_t lo = (uintptr_t)base;
+  if (a < lo || size > UINTPTR_MAX - lo || a + cap > lo + size) return false;
+  known.push_back(DevRange{lo, lo + size});
+  return true;
+}
+
+void zgf::reset_stats(zgpu_ctx* c, unsigned owned) {
+  auto zero = [](auto& a) { for (uint64_t& x : a) x = 0; };
+  if (owned & kOwnsDecode) { c->frames_submits = 0; zero(c->frames_dict_stats); }
+  if (owned & kOwnsDevice) zero(c->frames_device_stats);
+  if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
+  if (owned & kOwnsIndex) zero(c->frames_index_stats);
+  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); }
+}
+
+int zgf::drain(zgpu_ctx* c, int st) {
+  if (hipStreamSynchronize(c->eng->stream()) != hipSuccess || hipStreamSynchronize(c->eng->copy_stream()) != hipSuccess) { (void)hipGetLastError(); if (!st) st = ZGPU_E_HIP; }
+  return st;
+}
+
+DeviceSink zgf::device_sink(zgpu_ctx* c, const zgpu_device_opts* opts, zgpu_device_entry_result* results, int* st, bool table) {
+  const uint32_t flags = opts ? opts->flags : 0u;
+  DeviceSink s;
+  s.res = results;
+  s.hash_max = opts && opts->hash_max_bytes ? opts->hash_max_bytes : kHashDeviceMax;
+  s.no_hash = (flags & ZGPU_DEVICE_NO_HASH) != 0;
+  s.verify = (flags & ZGPU_DEVICE_VERIFY) != 0;
+  s.hash_all = s.verify && !opts->hash_max_bytes;
+  s.stats = c->frames_device_stats;
+  s.table_flag = (flags & ZGPU_DEVICE_VERIFY_SEEK_TABLE) != 0;
+  s.table_all = s.table_flag && !opts->hash_max_bytes;
+  *st = (s.no_hash && (s.verify || s.table_flag)) || (s.table_flag && !table) ? ZGPU_E_BAD_ARG : ZGPU_OK;
+  return s;
+}
 
 extern "C" int zgpu_decode_frames(zgpu_ctx* c, const uint8_t* const* srcs, const size_t* lens, uint32_t n, uint8_t* const* dsts, const size_t* caps,
                                   zgpu_entry_result* results) {
@@ -903,6 +837,48 @@ extern "C" int zgpu_decode_frames_device_src(zgpu_ctx* c, const void* const* dev
     for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
   k.src = &src;
   return finish_device_call(k, n, st);
+}
+
+// The selections become the entries of that call's machinery: (src + lo, hi - lo) is walked, cut into submits, gathered, decoded and hashed as
+// any entry is, and only the verdict (the size check), the scatter list (clipped) and the entries that go alone (the selection downloaded, the
+// clipped bytes uploaded) know of the clips. The machinery's own per-entry destinations are not used: every clip has its own.
+int zgf::decode_selections(zgpu_ctx* c, DeviceSink& sink, const void* const* device_srcs, const size_t* lens, const std::vector<Selection>& sel,
+                           std::vector<Clip>& clip, const std::vector<uint32_t>& first, bool promise, const uint64_t* want_bound,
+                           zgpu_device_entry_result* dres) {
+  const uint32_t n = (uint32_t)sel.size();
+  std::vector<const uint8_t*> srcs(n);
+  std::vector<size_t> sub(n), no_caps(n, 0);
+  std::vector<uint8_t*> no_dsts(n, nullptr);
+  DeviceSources src;
+  src.dev.resize(n);
+  src.refused.resize(n);
+  Ranges rg{clip, first, std::vector<uint64_t>(n), promise, c->ranges_stats};
+  sink.res = dres;
+  if (sink.table_flag) sink.table_verify.resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const Selection& s = sel[i];
+    srcs[i] = (const uint8_t*)device_srcs[s.entry] + s.lo;
+    sub[i] = (size_t)(s.hi - s.lo);
+    src.dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
+    src.refused[i] = s.refused;
+    rg.declared[i] = s.declared;
+    if (sink.table_flag) sink.table_verify[i] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[s.entry], (uint64_t)lens[s.entry], s.first_row, s.rows};
+  }
+  Call k(c, srcs.data(), sub.data(), no_dsts.data(), no_caps.data());
+  k.sink = &sink;
+  k.ranges = &rg;
+  int st = device_sources(k, n, &src);
+  // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number)
+  for (uint32_t i = 0; i < n && !st && want_bound && !k.shared; i++)
+    if (sub[i] && src.bound[i] != want_bound[i]) {
+      c->eng->last_error = "zgpu_decode_ranges_device_src: a source changed between the seek and the walk";
+      st = ZGPU_E_INTERNAL;
+    }
+  k.src = &src;
+  st = finish_device_call(k, n, st);
+  rg.stats[kRangeStatInputBytesToHost] = src.stats[kSrcStatInputBytesToHost];
+  rg.stats[kRangeStatBytesWritten] = sink.stats[kDevStatBytesScattered] + sink.alone_written;
+  return st;
 }
 // ---- the hash kernels on ranges of the caller's choice (measurement and tests) ---------------------------------------------------------------
 // [base, base + max(off + len)) passes the check the device sources pass before anything is launched; the ranges are sorted longest first as
@@ -1021,550 +997,6 @@ extern "C" void zgpu_set_frames_shared_dicts(zgpu_ctx* c, int on) { if (c) c->fr
 extern "C" int zgpu_frames_shared_dicts(const zgpu_ctx* c) { return c && c->frames_shared_dicts ? 1 : 0; }
 extern "C" int zgpu_debug_frames_dict_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_dict_stats, out, n) : 0; }
 extern "C" int zgpu_debug_frames_device_stats(const zgpu_ctx* c, uint64_t* out, int n) { return c ? copy_stats(c->frames_device_stats, out, n) : 0; }
-
-// ---- byte ranges of device-resident entries (zg_seek.h) --------------------------------------------------------------------------------------
-static_assert(sizeof(zgpu_range) == 32 && sizeof(zgpu_seek) == sizeof(zgk::Seek) && sizeof(zgpu_range_result) == sizeof(zgpu_device_entry_result) + 64,
-              "include/zgpu.h");
-static_assert(offsetof(zgpu_seek, plain_seen) == offsetof(zgk::Seek, plain_seen) && offsetof(zgpu_seek, status) == offsetof(zgk::Seek, status) &&
-              offsetof(zgpu_seek, flags) == offsetof(zgk::Seek, flags) && ZGPU_E_BAD_ARG == zgk::kBadArg, "zgk::Seek is zgpu_seek");
-static_assert(ZGPU_E_SEEK_TABLE == zgt::kSeekTable && ZGPU_SEEKTAB_NONE == zgt::kNone && ZGPU_SEEKTAB_RESERVED_BITS == zgt::kReservedBits &&
-              ZGPU_SEEKTAB_TOO_LARGE == zgt::kTooLarge && ZGPU_SEEKTAB_BAD_FRAME == zgt::kBadFrame && ZGPU_SEEKTAB_PAST_TABLE == zgt::kPastTable,
-              "zg_seektab.h");
-static_assert(ZGPU_E_SEEK_CHECKSUM_MISMATCH == zgv::kSeekChecksumMismatch, "zg_seeksums.h");
-namespace {
-// Both calls up to the records: every pointer checked, ONE zg_k_seek launch over all n lanes (a refused entry and a range of length 0 have
-// length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations. table: the selection
-// comes from the seek table at the entry's end (ONE zg_k_seektab launch, a wave per entry); an anchored range is refused, the table is the index.
-int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* dsts, const size_t* caps,
-                std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused, bool table) {
-  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  std::vector<zgk::Lane> lanes(table ? 0 : n);
-  std::vector<zgt::Lane> waves(table ? n : 0);
-  out->assign(n, zgk::Seek{});
-  std::vector<Engine::DevEntry> dev;
-  // (a range of length 0 is never refused: nothing of its entry is touched; with a seek table an anchored range is refused, the table is the index)
-  check_entries(c, srcs, lens, dsts, caps, n,
-                [&](uint32_t i) { return !ranges[i].len ? kPass : table && (ranges[i].anchor_src || ranges[i].anchor_plain) ? kRefuse : kCheck; }, &dev, refused);
-  for (uint32_t i = 0; i < n; i++) {
-    const zgpu_range& g = ranges[i];
-    const bool bad = (*refused)[i] != 0;
-    if (table) waves[i] = zgt::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len};
-    else lanes[i] = zgk::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
-  }
-  const int st = drain(c, table ? c->eng->seektab_pass(waves.data(), n, out->data(), c->ranges_stats) : c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats));
-  if (st) return st;
-  for (uint32_t i = 0; i < n; i++) {
-    zgk::Seek& s = (*out)[i];
-    if ((*refused)[i]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
-    if (s.src_lo > s.src_hi || s.src_hi > lens[i] || (s.status && s.status != (table ? (uint32_t)ZGPU_E_SEEK_TABLE : (uint32_t)ZGPU_E_BAD_ARG))) {   // (never)
-      c->eng->last_error = "zgpu_frames_seek_device: a record that leaves its entry";
-      return ZGPU_E_INTERNAL;
-    }
-    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
-  }
-  return ZGPU_OK;
-}
-// the two seek calls: the records themselves are the answer
-int seek_only(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out, bool table) {
-  reset_stats(c, kOwnsRanges);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  const int st = seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, &recs, &refused, table);
-  for (uint32_t i = 0; i < n; i++) { if (st) memset(&out[i], 0, sizeof out[i]); else memcpy(&out[i], &recs[i], sizeof out[i]); }
-  return st;
-}
-}  // namespace
-
-extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out) {
-  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
-  return seek_only(c, device_srcs, lens, n, ranges, out, false);
-}
-extern "C" int zgpu_frames_seek_table_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
-                                             zgpu_seek* out) {
-  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
-  return seek_only(c, device_srcs, lens, n, ranges, out, true);
-}
-
-// The selections become the entries of zgpu_decode_frames_device_src's machinery: (src + src_lo, src_hi - src_lo) is walked, cut into submits,
-// gathered, decoded and hashed as any entry is, and only the verdict (the size check), the scatter list (clipped) and the entries that go
-// alone (the selection downloaded, the clipped bytes uploaded) know of the range.
-// table (zgpu_decode_ranges_seek_table_device_src): the selections are zg_k_seektab's. Three things differ: the seek's bound is the table's
-// promise and is not compared with the walk's header bound; Clip::declared is that promise, and an entry whose decoded total differs from it
-// fails with ContentSizeMismatch (Call::promise); an entry whose table is not usable is refused with ZGPU_E_SEEK_TABLE, unread and unwritten.
-namespace {
-int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* device_dsts,
-                  const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results, bool table) {
-  if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  std::vector<zgpu_device_entry_result> dres(n);
-  int st;
-  DeviceSink sink = device_sink(c, opts, dres.data(), &st, table);
-  if (st) return st;
-  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
-  for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
-  std::vector<zgk::Seek> recs;
-  DeviceSources src;
-  if ((st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &src.refused, table))) return st;
-  // the ranges part: the selections as entries (src.dev, in place of the whole entries seek_ranges checked) and what of each is wanted
-  std::vector<const uint8_t*> srcs(n);
-  std::vector<size_t> sub(n);
-  Ranges rg;
-  rg.clip.resize(n);
-  rg.declared.resize(n);
-  rg.first.resize((size_t)n + 1);   // (one range per entry: spans of one clip)
-  for (uint32_t i = 0; i <= n; i++) rg.first[i] = i;
-  rg.promise = table;
-  rg.stats = c->ranges_stats;
-  src.dev.resize(n);
-  if (sink.table_flag) sink.table_verify.resize(n);
-  for (uint32_t i = 0; i < n; i++) {
-    const zgk::Seek& s = recs[i];
-    if (s.status) src.refused[i] = (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1);   // (an anchor behind the entry or behind begin; no usable table)
-    const bool none = src.refused[i] || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
-    srcs[i] = (const uint8_t*)device_srcs[i] + (none ? 0 : s.src_lo);
-    sub[i] = none ? 0 : (size_t)(s.src_hi - s.src_lo);
-    src.dev[i] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)sub[i]};
-    if (sink.table_flag) sink.table_verify[i] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[i], (uint64_t)lens[i], s.frames_skipped, none ? 0u : s.frames_taken};
-    const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
-    rg.clip[i] = Ranges::Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, (uint8_t*)device_dsts[i], caps[i], 0, false};
-    rg.declared[i] = none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX;   // (table: an entry of which nothing is taken promises nothing)
-  }
-  Call k(c, srcs.data(), sub.data(), (uint8_t* const*)device_dsts, caps);
-  k.sink = &sink;
-  k.ranges = &rg;
-  st = device_sources(k, n, &src);
-  // (the walk and the seek read the same bytes: without dictionary gaps their bounds are one number; the table's bound is its promise instead)
-  for (uint32_t i = 0; i < n && !st && !table && !k.shared; i++)
-    if (sub[i] && src.bound[i] != recs[i].bound) {
-      c->eng->last_error = "zgpu_decode_ranges_device_src: a source changed between the seek and the walk";
-      st = ZGPU_E_INTERNAL;
-    }
-  k.src = &src;
-  st = finish_device_call(k, n, st);
-  rg.stats[kRangeStatInputBytesToHost] = src.stats[kSrcStatInputBytesToHost];
-  rg.stats[kRangeStatBytesWritten] = sink.stats[kDevStatBytesScattered] + sink.alone_written;
-  for (uint32_t i = 0; i < n; i++) {
-    if (!st) results[i].d = dres[i];
-    memcpy(&results[i].seek, &recs[i], sizeof results[i].seek);
-  }
-  return st;
-}
-}  // namespace
-
-extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
-                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results) {
-  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, false);
-}
-extern "C" int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
-                                                        const zgpu_range* ranges, void* const* device_dsts, const size_t* caps,
-                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
-  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, true);
-}
-// ---- many ranges over few seekable entries (zg_seekmany.h) ------------------------------------------------------------------------------------
-static_assert(sizeof(zgpu_entry_range) == 24 && offsetof(zgpu_entry_range, entry) == 16, "include/zgpu.h");
-namespace {
-// Both calls up to the records. Every range is looked at on its own: entry >= n or pad != 0 refuses it (ZGPU_E_BAD_ARG in its record), a length
-// of 0 passes untouched, and an entry is checked — once — only when a range of nonzero length names it; an entry that fails the pointer check
-// refuses the ranges that name it, a destination that fails it refuses its own range. Then Engine::seekmany_pass over the entries that passed:
-// each table scanned once, every range a binary search. dsts / caps: nullptr for the seek call.
-int seek_many(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_entry_range* ranges, uint32_t m, void* const* dsts,
-              const size_t* caps, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
-  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  out->assign(m, zgk::Seek{});
-  refused->assign(m, 0);
-  std::vector<DevRange> known;
-  const int device = c->eng->device();
-  std::vector<uint8_t> seen(n, 0);   // 0: no range of nonzero length has named it yet, 1: passed, 2: refused
-  std::vector<uint32_t> live_of(n, 0);
-  std::vector<Engine::DevEntry> live;
-  std::vector<Engine::ManyRange> mr(m);
-  for (uint32_t j = 0; j < m; j++) {
-    const zgpu_entry_range& g = ranges[j];
-    mr[j] = Engine::ManyRange{g.begin, 0, 0};
-    if (g.entry >= n || g.pad) { (*refused)[j] = 1; continue; }
-    if (!g.len) continue;
-    const uint32_t i = g.entry;
-    if (!seen[i]) {
-      bool bad = !srcs[i] && lens[i];
-      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
-      seen[i] = bad ? 2 : 1;
-      if (!bad) { live_of[i] = (uint32_t)live.size(); live.push_back(Engine::DevEntry{(uint64_t)(uintptr_t)srcs[i], (uint64_t)lens[i]}); }
-    }
-    bool bad = seen[i] == 2;
-    if (!bad && dsts) {
-      bad = !dsts[j] && caps[j];
-      if (!bad && caps[j]) bad = !check_device_range(device, dsts[j], caps[j], known);
-    }
-    if (bad) { (*refused)[j] = 1; continue; }
-    mr[j] = Engine::ManyRange{g.begin, g.len, live_of[i]};
-  }
-  Engine::ManyStats more;
-  const int st = drain(c, c->eng->seekmany_pass(live.data(), (uint32_t)live.size(), mr.data(), m, out->data(), c->ranges_stats, &more));
-  uint64_t* ms = c->ranges_many_stats;
-  ms[kManyStatPrefixLaunches] = more.prefix_launches; ms[kManyStatPrefixUs] = more.prefix_us;
-  ms[kManyStatFindLaunches] = more.find_launches; ms[kManyStatFindUs] = more.find_us; ms[kManyStatPrefixScratchBytes] = more.scratch_bytes;
-  if (st) return st;
-  for (uint32_t j = 0; j < m; j++) {
-    zgk::Seek& s = (*out)[j];
-    if ((*refused)[j]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
-    if (s.src_lo > s.src_hi || (ranges[j].len && s.src_hi > lens[ranges[j].entry]) || (s.status && s.status != (uint32_t)ZGPU_E_SEEK_TABLE)) {   // (never)
-      c->eng->last_error = "zgpu_frames_seek_table_many_device: a record that leaves its entry";
-      return ZGPU_E_INTERNAL;
-    }
-    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
-  }
-  return ZGPU_OK;
-}
-}  // namespace
-
-extern "C" int zgpu_frames_seek_table_many_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
-                                                  const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
-  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
-  reset_stats(c, kOwnsRanges);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  const int st = seek_many(c, device_srcs, lens, n, ranges, m, nullptr, nullptr, &recs, &refused);
-  for (uint32_t j = 0; j < m; j++) { if (st) memset(&out[j], 0, sizeof out[j]); else memcpy(&out[j], &recs[j], sizeof out[j]); }
-  return st;
-}
-
-// The ranges of one entry whose rows overlap form a GROUP, and a group is ONE sub-entry of decode_ranges' machinery — the rows [gfirst, glast]
-// its ranges take together: (src + C_gfirst, C_{glast + 1} - C_gfirst) is walked, cut into submits, gathered, decoded and hashed once, and
-// every range is a clip of the group's span with its own destination. What a group's frames do — a decode or walk error, a size that differs
-// from the table's promise, a checksum verdict — is the verdict of every range in it; TargetTooSmall is each range's own.
-// Everything behind the selection, for both gather calls (the seek-table one and the indexed one): recs / refused are the m records and
-// refusals the selection left, whatever produced the pairs they were found in.
-namespace {
-int gather_groups(zgpu_ctx* c, DeviceSink& sink, const void* const* device_srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
-                  void* const* device_dsts, const size_t* caps, const std::vector<zgk::Seek>& recs, const std::vector<uint8_t>& refused,
-                  zgpu_range_result* results) {
-  int st;
-  // the groups: the ranges that take rows, sorted by (entry, first row, last row); one that begins at or in front of the last row of the group
-  // in front of it joins that group
-  std::vector<uint32_t> order;
-  for (uint32_t j = 0; j < m; j++)
-    if (!refused[j] && ranges[j].len && !recs[j].status && recs[j].frames_taken) order.push_back(j);
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    const zgk::Seek& x = recs[a], & y = recs[b];
-    if (ranges[a].entry != ranges[b].entry) return ranges[a].entry < ranges[b].entry;
-    if (x.frames_skipped != y.frames_skipped) return x.frames_skipped < y.frames_skipped;
-    if (x.frames_taken != y.frames_taken) return x.frames_taken < y.frames_taken;
-    return a < b;
-  });
-  struct Group { uint32_t entry, gfirst, glast; uint64_t c_lo, c_hi, d_lo, d_hi; };
-  std::vector<Group> groups;
-  std::vector<uint32_t> group_of(m, 0), clip_of(m, 0);
-  Ranges rg;
-  rg.promise = true;
-  rg.stats = c->ranges_stats;
-  for (uint32_t j : order) {
-    const zgk::Seek& s = recs[j];
-    const uint32_t first = s.frames_skipped, last = s.frames_skipped + s.frames_taken - 1;
-    if (groups.empty() || groups.back().entry != ranges[j].entry || first > groups.back().glast) {
-      groups.push_back(Group{ranges[j].entry, first, last, s.src_lo, s.src_hi, s.plain_lo, s.plain_seen});
-      rg.first.push_back((uint32_t)rg.clip.size());
-    } else if (last > groups.back().glast) {
-      Group& g = groups.back();
-      g.glast = last; g.c_hi = s.src_hi; g.d_hi = s.plain_seen;
-    }
-    group_of[j] = (uint32_t)groups.size() - 1;
-    clip_of[j] = (uint32_t)rg.clip.size();
-    rg.clip.push_back(Ranges::Clip{ranges[j].begin - groups.back().d_lo, ranges[j].len, (uint8_t*)device_dsts[j], caps[j], 0, false});
-  }
-  rg.first.push_back((uint32_t)rg.clip.size());
-  const uint32_t G = (uint32_t)groups.size();
-  // the groups as the entries of the machinery; its own per-entry destinations are not used (every clip has its own)
-  std::vector<zgpu_device_entry_result> dres(G);
-  std::vector<const uint8_t*> srcs(G);
-  std::vector<size_t> sub(G), no_caps(G, 0);
-  std::vector<uint8_t*> no_dsts(G, nullptr);
-  DeviceSources src;
-  src.dev.resize(G);
-  src.refused.assign(G, 0);
-  rg.declared.resize(G);
-  sink.res = dres.data();
-  if (sink.table_flag) sink.table_verify.resize(G);
-  for (uint32_t g = 0; g < G; g++) {
-    const Group& gr = groups[g];
-    if (gr.c_lo > gr.c_hi || gr.d_lo > gr.d_hi) { c->eng->last_error = "zgpu_gather_ranges_seek_table_device_src: records of one table out of step"; return ZGPU_E_INTERNAL; }   // (never)
-    srcs[g] = (const uint8_t*)device_srcs[gr.entry] + gr.c_lo;
-    sub[g] = (size_t)(gr.c_hi - gr.c_lo);
-    src.dev[g] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[g], (uint64_t)sub[g]};
-    rg.declared[g] = gr.d_hi - gr.d_lo;
-    if (sink.table_flag) sink.table_verify[g] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[gr.entry], (uint64_t)lens[gr.entry], gr.gfirst, gr.glast - gr.gfirst + 1};
-  }
-  Call k(c, srcs.data(), sub.data(), no_dsts.data(), no_caps.data());
-  k.sink = &sink;
-  k.ranges = &rg;
-  st = device_sources(k, G, &src);
-  k.src = &src;
-  st = finish_device_call(k, G, st);
-  rg.stats[kRangeStatInputBytesToHost] = src.stats[kSrcStatInputBytesToHost];
-  rg.stats[kRangeStatBytesWritten] = sink.stats[kDevStatBytesScattered] + sink.alone_written;
-  c->ranges_many_stats[kManyStatGroupsDecoded] = G;
-  // every range's result: the group's, with the range's own count — or its own TargetTooSmall, which ranks behind the group's decode, walk
-  // and size verdicts and in front of its checksum verdicts
-  for (uint32_t j = 0; j < m; j++) {
-    memcpy(&results[j].seek, &recs[j], sizeof results[j].seek);
-    if (st) continue;
-    zgpu_device_entry_result& d = results[j].d;
-    if (refused[j] || recs[j].status) { d.r.status = refused[j] ? ZGPU_E_BAD_ARG : (int)recs[j].status; continue; }
-    if (!ranges[j].len || !recs[j].frames_taken) continue;   // (nothing is read, decoded or written: status 0, written 0)
-    const zgpu_device_entry_result& gd = dres[group_of[j]];
-    const Ranges::Clip& cl = rg.clip[clip_of[j]];
-    const bool checks = gd.r.status == ZGPU_E_CHECKSUM_MISMATCH || gd.r.status == ZGPU_E_SEEK_CHECKSUM_MISMATCH;
-    if (gd.r.status == ZGPU_E_TARGET_TOO_SMALL || ((!gd.r.status || checks) && cl.small)) { d.r.status = ZGPU_E_TARGET_TOO_SMALL; continue; }
-    d = gd;
-    if (!gd.r.status) d.r.written = cl.written;
-  }
-  return st;
-}
-}  // namespace
-
-extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
-                                                        const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
-                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
-  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  int st;
-  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
-  if (st) return st;
-  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
-  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  if ((st = seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, &recs, &refused))) return st;
-  return gather_groups(c, sink, device_srcs, lens, ranges, m, device_dsts, caps, recs, refused, results);
-}
-
-// ---- seek index handles (include/zgpu.h: zgpu_seek_index; zg_seekidx.h) -------------------------------------------------------------------------
-static_assert(sizeof(zgpu_seek_index_info) == 40 && ZGPU_INDEX_UNSIZED == zgx::kUnsized && ZGPU_E_FRAME_INDEX == 74, "include/zgpu.h");
-namespace {
-// an entry the index refuses: nothing of it is held
-void refuse_index(zgpu_seek_index::Ent& e, uint32_t status, uint32_t why, uint32_t kind) {
-  e.info.status = status; e.info.why = why; e.info.kind = kind;
-  e.info.nrows = 0; e.info.compressed = 0; e.info.plaintext = 0;
-  e.pre = 0; e.tab = 0;
-}
-
-// The build. The table pass works in a scratch of its own (its chunk totals lie behind the prefixes); the handle's buffer is sized exactly —
-// 16 * (nrows + 1) bytes per indexed entry —, gets the table entries' pairs by one device copy each, and the declared entries' pairs straight
-// from zg_k_seekidx_rows.
-int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, uint32_t kind) {
-  zg::Engine* eng = c->eng;
-  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  std::vector<Engine::DevEntry> dev;
-  std::vector<uint8_t> refused;
-  check_entries(c, srcs, lens, nullptr, nullptr, n, check_all, &dev, &refused);
-  x->ents.assign(n, zgpu_seek_index::Ent{});
-  std::vector<uint8_t> by_chain(n, 0);   // entries the chain is asked about
-  for (uint32_t i = 0; i < n; i++) {
-    x->ents[i].info.len = lens[i];
-    if (refused[i]) refuse_index(x->ents[i], ZGPU_E_BAD_ARG, 0, kind == ZGPU_INDEX_DECLARED ? ZGPU_INDEX_DECLARED : ZGPU_INDEX_SEEK_TABLE);
-    else by_chain[i] = kind == ZGPU_INDEX_DECLARED;
-  }
-  uint64_t* stats = x->stats;
-  // the tables
-  zg::DevBuf scratch;
-  std::vector<zgm::Loc> loc;
-  std::vector<uint64_t> tpre;
-  std::vector<uint32_t> tab_of;   // the entries the table pass was asked about
-  struct Free { zg::DevBuf& b; ~Free() { b.release(); } } free_scratch{scratch};
-  if (kind != ZGPU_INDEX_DECLARED) {
-    std::vector<Engine::DevEntry> live;
-    for (uint32_t i = 0; i < n; i++) if (!refused[i]) { tab_of.push_back(i); live.push_back(dev[i]); }
-    loc.resize(live.size());
-    tpre.assign(live.size(), 0);
-    Engine::ManyStats more;
-    uint64_t npairs = 0;
-    const int st = eng->seekmany_prefixes(live.data(), (uint32_t)live.size(), loc.data(), tpre.data(), &scratch, &npairs, stats, &more);
-    stats[kSeekIdxStatLaunches] += more.prefix_launches; stats[kSeekIdxStatKernelUs] += more.prefix_us;
-    if (st) return st;
-    for (size_t q = 0; q < tab_of.size(); q++) {
-      zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
-      if (loc[q].why == zgt::kNone && kind == ZGPU_INDEX_AUTO) by_chain[tab_of[q]] = 1;
-      else if (loc[q].why) refuse_index(e, ZGPU_E_SEEK_TABLE, loc[q].why, ZGPU_INDEX_SEEK_TABLE);
-      else { e.info.kind = ZGPU_INDEX_SEEK_TABLE; e.info.nrows = loc[q].nf; e.tab = loc[q].tab; }
-    }
-  }
-  // the chains: the summary pass says which entries can be indexed and how many rows each has
-  std::vector<uint32_t> ch_of;
-  std::vector<Engine::DevEntry> chain;
-  for (uint32_t i = 0; i < n; i++) if (by_chain[i]) { ch_of.push_back(i); chain.push_back(dev[i]); }
-  std::vector<zgi::Entry> sum(chain.size());
-  int st = eng->index_pass(chain.data(), (uint32_t)chain.size(), nullptr, nullptr, sum.data(), nullptr, stats);
-  if (st) return st;
-  for (size_t q = 0; q < ch_of.size(); q++) {
-    zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
-    const uint32_t why = zgx::refusal(sum[q]);
-    if (sum[q].chain_end > lens[ch_of[q]]) { eng->last_error = "zgpu_seek_index_create_device: a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
-    if (why) refuse_index(e, ZGPU_E_FRAME_INDEX, why, ZGPU_INDEX_DECLARED);
-    else if (sum[q].nrec > zgt::kMaxFrames) refuse_index(e, ZGPU_E_FRAME_INDEX, ZGPU_SEEKTAB_TOO_LARGE, ZGPU_INDEX_DECLARED);
-    else { e.info.kind = ZGPU_INDEX_DECLARED; e.info.nrows = sum[q].nrec; e.tab = lens[ch_of[q]]; }
-  }
-  // the handle's pairs: every indexed entry's range
-  uint64_t pairs = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    zgpu_seek_index::Ent& e = x->ents[i];
-    if (e.info.status) continue;
-    e.pre = pairs;
-    pairs += (uint64_t)e.info.nrows + 1;
-  }
-  if (pairs > SIZE_MAX / sizeof(zgm::Pair)) return ZGPU_E_NOMEM;
-  if (pairs && (st = x->pairs.reserve((size_t)pairs * sizeof(zgm::Pair)))) return st;
-  stats[kSeekIdxStatDeviceBytes] = pairs * sizeof(zgm::Pair);
-  zgm::Pair* dp = x->pairs.as<zgm::Pair>();
-  hipStream_t s = eng->stream();
-  // table kind: the prefixes move over, and each entry's closing pair comes back (16 bytes: C[nrows], D[nrows])
-  std::vector<zgm::Pair> closing(tab_of.size(), zgm::Pair{0, 0});
-  for (size_t q = 0; q < tab_of.size(); q++) {
-    const zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
-    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
-    const zgm::Pair* from = scratch.as<zgm::Pair>() + tpre[q];
-    if (hipMemcpyAsync(dp + e.pre, from, ((size_t)e.info.nrows + 1) * sizeof(zgm::Pair), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(&closing[q], from + e.info.nrows, sizeof(zgm::Pair), hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-    stats[kSeekIdxStatBytesDownloaded] += sizeof(zgm::Pair);
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  for (size_t q = 0; q < tab_of.size(); q++) {
-    zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
-    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
-    e.info.compressed = closing[q].c; e.info.plaintext = closing[q].d;
-  }
-  // declared kind: the rows pass over the entries the summary pass accepted
-  std::vector<zgx::Lane> lanes;
-  std::vector<uint32_t> lane_of;
-  for (size_t q = 0; q < ch_of.size(); q++) {
-    const zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
-    if (e.info.status) continue;
-    lane_of.push_back(ch_of[q]);
-    lanes.push_back(zgx::Lane{chain[q].src, chain[q].len, e.pre, e.info.nrows});
-  }
-  std::vector<zgx::Rows> rows(lanes.size());
-  if ((st = eng->seekidx_rows_pass(lanes.data(), (uint32_t)lanes.size(), dp, rows.data(), stats))) return st;
-  for (size_t q = 0; q < lane_of.size(); q++) {
-    zgpu_seek_index::Ent& e = x->ents[lane_of[q]];
-    // (a source that changed between the passes — the caller's promise broken —, or pairs that do not add up to the entry)
-    if (rows[q].why || rows[q].nrows != e.info.nrows || rows[q].c != e.info.len) {
-      eng->last_error = "zgpu_seek_index_create_device: a source changed while it was indexed";
-      return ZGPU_E_INTERNAL;
-    }
-    e.info.compressed = rows[q].c; e.info.plaintext = rows[q].d;
-  }
-  for (const zgpu_seek_index::Ent& e : x->ents) if (!e.info.status) stats[kSeekIdxStatRows] += e.info.nrows;
-  return ZGPU_OK;
-}
-
-// Both indexed calls up to the records. Every range is looked at on its own, as seek_many looks at it: entry >= entries or pad != 0 refuses
-// it, a length of 0 passes untouched, an entry the index refused gives its status and why. srcs != nullptr (the gather call): an entry that a
-// range of nonzero length names is checked once — its pointer, and lens[i] against the length it was indexed at —, a destination on its own.
-// table_flag: ZGPU_DEVICE_VERIFY_SEEK_TABLE refuses the ranges of declared-kind entries. Then ONE find launch over the handle's pairs.
-int indexed_ranges(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
-                   void* const* dsts, const size_t* caps, bool table_flag, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
-  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  const uint32_t n = (uint32_t)x->ents.size();
-  out->assign(m, zgk::Seek{});
-  refused->assign(m, 0);
-  std::vector<DevRange> known;
-  const int device = c->eng->device();
-  std::vector<uint8_t> seen(n, 0);   // 0: no range of nonzero length has named it yet, 1: passed, 2: refused
-  std::vector<zgm::Find> lanes(m);
-  for (uint32_t j = 0; j < m; j++) {
-    const zgpu_entry_range& g = ranges[j];
-    lanes[j] = zgm::Find{g.begin, 0, 0, 0, 0, 0, 0, 0};
-    if (g.entry >= n || g.pad) { (*refused)[j] = 1; continue; }
-    if (!g.len) continue;
-    const uint32_t i = g.entry;
-    const zgpu_seek_index::Ent& e = x->ents[i];
-    if (e.info.status) continue;   // (the record is the entry's status and why: written below, nothing of the entry is looked at)
-    if (srcs && !seen[i]) {
-      bool bad = (!srcs[i] && lens[i]) || (uint64_t)lens[i] != e.info.len;
-      if (!bad && lens[i]) bad = !check_device_range(device, srcs[i], lens[i], known);
-      seen[i] = bad ? 2 : 1;
-    }
-    bool bad = seen[i] == 2 || (table_flag && e.info.kind != ZGPU_INDEX_SEEK_TABLE);
-    if (!bad && dsts) {
-      bad = !dsts[j] && caps[j];
-      if (!bad && caps[j]) bad = !check_device_range(device, dsts[j], caps[j], known);
-    }
-    if (bad) { (*refused)[j] = 1; continue; }
-    lanes[j] = zgm::Find{g.begin, g.len, e.pre, e.tab, e.info.nrows, 0, 0, 0};
-  }
-  Engine::ManyStats more;
-  const int st = drain(c, c->eng->seekmany_find(lanes.data(), m, x->pairs.as<zgm::Pair>(), out->data(), nullptr, &more));
-  c->ranges_many_stats[kManyStatFindLaunches] = more.find_launches; c->ranges_many_stats[kManyStatFindUs] = more.find_us;
-  if (st) return st;
-  for (uint32_t j = 0; j < m; j++) {
-    zgk::Seek& s = (*out)[j];
-    if ((*refused)[j]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
-    if (!ranges[j].len) continue;
-    const zgpu_seek_index::Ent& e = x->ents[ranges[j].entry];
-    if (e.info.status) { s = zgk::Seek{}; s.status = e.info.status; s.why = e.info.why; continue; }
-    // (every record is held against the entry's length before anything is gathered)
-    if (s.src_lo > s.src_hi || s.src_hi > e.info.len || (s.status && s.status != (uint32_t)ZGPU_E_SEEK_TABLE)) {   // (never)
-      c->eng->last_error = "zgpu_frames_seek_indexed_device: a record that leaves its entry";
-      return ZGPU_E_INTERNAL;
-    }
-    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
-  }
-  return ZGPU_OK;
-}
-}  // namespace
-
-extern "C" int zgpu_seek_index_create_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t kind,
-                                             zgpu_seek_index** out) {
-  if (out) *out = nullptr;
-  if (!c || !out || kind > ZGPU_INDEX_AUTO || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
-  zgpu_seek_index* x = new zgpu_seek_index();
-  x->ctx = c;
-  const int st = drain(c, build_index(c, x, device_srcs, lens, n, kind));
-  if (st) { zgpu_seek_index_destroy(x); return st; }   // (nothing is left behind)
-  *out = x;
-  return ZGPU_OK;
-}
-extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
-  if (!x) return;
-  if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
-  x->pairs.release();
-  delete x;
-}
-extern "C" uint32_t zgpu_seek_index_entries(const zgpu_seek_index* x) { return x ? (uint32_t)x->ents.size() : 0; }
-extern "C" int zgpu_seek_index_info_of(const zgpu_seek_index* x, uint32_t i, zgpu_seek_index_info* out) {
-  if (!x || !out || i >= x->ents.size()) return ZGPU_E_BAD_ARG;
-  *out = x->ents[i].info;
-  return ZGPU_OK;
-}
-extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) { return x ? copy_stats(x->stats, out, n) : 0; }
-
-extern "C" int zgpu_frames_seek_indexed_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
-  if (!c || !x || x->ctx != c || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
-  reset_stats(c, kOwnsRanges);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  const int st = indexed_ranges(c, x, nullptr, nullptr, ranges, m, nullptr, nullptr, false, &recs, &refused);
-  for (uint32_t j = 0; j < m; j++) { if (st) memset(&out[j], 0, sizeof out[j]); else memcpy(&out[j], &recs[j], sizeof out[j]); }
-  return st;
-}
-
-extern "C" int zgpu_gather_ranges_indexed_device_src(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
-                                                     const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
-                                                     const zgpu_device_opts* opts, zgpu_range_result* results) {
-  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results)))
-    return ZGPU_E_BAD_ARG;
-  int st;
-  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
-  if (st) return st;
-  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
-  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
-  std::vector<zgk::Seek> recs;
-  std::vector<uint8_t> refused;
-  if ((st = indexed_ranges(c, x, device_srcs, lens, ranges, m, device_dsts, caps, sink.table_flag, &recs, &refused))) return st;
-  return gather_groups(c, sink, device_srcs, lens, ranges, m, device_dsts, caps, recs, refused, results);
-}
-
-extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
-  if (!c) return 0;
-  const int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others)
-  return k < (int)kRangeStatCount || !out ? k : k + copy_stats(c->ranges_many_stats, out + k, n - k);
-}
 
 extern "C" uint64_t zgpu_plaintext_bound(const uint8_t* src, size_t len) { return src || !len ? plaintext_bound(src, len) : 0; }
 extern "C" uint32_t zgpu_debug_frames_submits(const zgpu_ctx* c) { return c ? c->frames_submits : 0u; }

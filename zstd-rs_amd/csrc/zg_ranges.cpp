@@ -1,0 +1,448 @@
+// zg_ranges.cpp — the calls of include/zgpu.h that decode byte RANGES of device-resident entries: front-ends of zg_frames.cpp's machinery.
+// Each of them decides which bytes of its entries become sub-entries of that machinery (zg_frames_int.h: Selection) and what of a decoded
+// sub-entry goes to which destination (Clip), and hands both to decode_selections; the seek-only twin of each returns the records alone.
+// The calls with one range per entry (zg_seek.h: the header chain; zg_seektab.h: the seek table) hand over spans of one clip.
+//
+// zgpu_gather_ranges_seek_table_device_src takes m ranges that each name one of n seekable entries (zg_seekmany.h: every table scanned once,
+// every range a binary search). The ranges of one entry whose table rows overlap form a group; a group is ONE selection, decoded once, and
+// every range of it is a clip of the group's span with its own destination. zgpu_gather_ranges_indexed_device_src is the same call behind
+// another selection: a zgpu_seek_index keeps the prefix sums of its entries' rows in device memory — built from their seek tables, or from
+// their header chains where every frame declares its size (zg_seekidx.h) —, indexed_ranges finds every range's rows in them with one launch,
+// and gather_groups is shared.
+#include <stddef.h>
+#include <string.h>
+#include <vector>
+#include "zg_frames_int.h"
+#include "zg_seeksums.h"
+
+using namespace zg;
+using namespace zgf;
+
+// ---- byte ranges of device-resident entries (zg_seek.h) --------------------------------------------------------------------------------------
+static_assert(sizeof(zgpu_range) == 32 && sizeof(zgpu_seek) == sizeof(zgk::Seek) && sizeof(zgpu_range_result) == sizeof(zgpu_device_entry_result) + 64,
+              "include/zgpu.h");
+static_assert(offsetof(zgpu_seek, plain_seen) == offsetof(zgk::Seek, plain_seen) && offsetof(zgpu_seek, status) == offsetof(zgk::Seek, status) &&
+              offsetof(zgpu_seek, flags) == offsetof(zgk::Seek, flags) && ZGPU_E_BAD_ARG == zgk::kBadArg, "zgk::Seek is zgpu_seek");
+static_assert(ZGPU_E_SEEK_TABLE == zgt::kSeekTable && ZGPU_SEEKTAB_NONE == zgt::kNone && ZGPU_SEEKTAB_RESERVED_BITS == zgt::kReservedBits &&
+              ZGPU_SEEKTAB_TOO_LARGE == zgt::kTooLarge && ZGPU_SEEKTAB_BAD_FRAME == zgt::kBadFrame && ZGPU_SEEKTAB_PAST_TABLE == zgt::kPastTable,
+              "zg_seektab.h");
+static_assert(ZGPU_E_SEEK_CHECKSUM_MISMATCH == zgv::kSeekChecksumMismatch, "zg_seeksums.h");
+namespace {
+// The records a selection brought back, accepted: a refused range gets a record of zeros with ZGPU_E_BAD_ARG; every other record is held
+// against the length of its entry, len_of(j), and may carry no status but `allowed` — one that leaves its entry ends the call (never: `text`
+// in last_error) —; the frames in front of the selections are counted.
+template <class Len>
+int accept_records(zgpu_ctx* c, std::vector<zgk::Seek>* recs, const std::vector<uint8_t>& refused, Len len_of, uint32_t allowed, const char* text) {
+  for (uint32_t j = 0; j < (uint32_t)recs->size(); j++) {
+    zgk::Seek& s = (*recs)[j];
+    if (refused[j]) { s = zgk::Seek{}; s.status = ZGPU_E_BAD_ARG; continue; }
+    if (s.src_lo > s.src_hi || s.src_hi > len_of(j) || (s.status && s.status != allowed)) {   // (never)
+      c->eng->last_error = text;
+      return ZGPU_E_INTERNAL;
+    }
+    c->ranges_stats[kRangeStatFramesSkipped] += s.frames_skipped;
+  }
+  return ZGPU_OK;
+}
+// m records to the caller, record j to at(j): zeros when the call failed
+template <class At> void records_out(const std::vector<zgk::Seek>& recs, bool failed, uint32_t m, At at) {
+  for (uint32_t j = 0; j < m; j++) { if (failed) memset(at(j), 0, sizeof(zgpu_seek)); else memcpy(at(j), &recs[j], sizeof(zgpu_seek)); }
+}
+// the seek calls: the records themselves are the answer. select(&recs, &refused): the call's selection
+template <class Select> int seek_only(zgpu_ctx* c, uint32_t m, zgpu_seek* out, Select select) {
+  reset_stats(c, kOwnsRanges);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  const int st = select(&recs, &refused);
+  records_out(recs, st != 0, m, [&](uint32_t j) { return &out[j]; });
+  return st;
+}
+
+// Both calls up to the records: every pointer checked, ONE zg_k_seek launch over all n lanes (a refused entry and a range of length 0 have
+// length 0 for their lane: nothing of them is read). dsts / caps: nullptr for the seek call, which has no destinations. table: the selection
+// comes from the seek table at the entry's end (ONE zg_k_seektab launch, a wave per entry); an anchored range is refused, the table is the index.
+int seek_ranges(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* dsts, const size_t* caps,
+                std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused, bool table) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  std::vector<zgk::Lane> lanes(table ? 0 : n);
+  std::vector<zgt::Lane> waves(table ? n : 0);
+  out->assign(n, zgk::Seek{});
+  std::vector<Engine::DevEntry> dev;
+  // (a range of length 0 is never refused: nothing of its entry is touched; with a seek table an anchored range is refused, the table is the index)
+  check_entries(c, srcs, lens, dsts, caps, n,
+                [&](uint32_t i) { return !ranges[i].len ? kPass : table && (ranges[i].anchor_src || ranges[i].anchor_plain) ? kRefuse : kCheck; }, &dev, refused);
+  for (uint32_t i = 0; i < n; i++) {
+    const zgpu_range& g = ranges[i];
+    const bool bad = (*refused)[i] != 0;
+    if (table) waves[i] = zgt::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len};
+    else lanes[i] = zgk::Lane{dev[i].src, dev[i].len, g.begin, bad ? 0u : g.len, bad ? 0u : g.anchor_src, bad ? 0u : g.anchor_plain};
+  }
+  const int st = drain(c, table ? c->eng->seektab_pass(waves.data(), n, out->data(), c->ranges_stats) : c->eng->seek_pass(lanes.data(), n, out->data(), c->ranges_stats));
+  if (st) return st;
+  return accept_records(c, out, *refused, [&](uint32_t i) { return (uint64_t)lens[i]; }, table ? (uint32_t)ZGPU_E_SEEK_TABLE : (uint32_t)ZGPU_E_BAD_ARG,
+                        "zgpu_frames_seek_device: a record that leaves its entry");
+}
+}  // namespace
+
+extern "C" int zgpu_frames_seek_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
+  return seek_only(c, n, out, [&](auto* recs, auto* refused) { return seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, recs, refused, false); });
+}
+extern "C" int zgpu_frames_seek_table_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !out))) return ZGPU_E_BAD_ARG;
+  return seek_only(c, n, out, [&](auto* recs, auto* refused) { return seek_ranges(c, device_srcs, lens, n, ranges, nullptr, nullptr, recs, refused, true); });
+}
+
+// One selection per entry — the frames zg_k_seek found to hold its range —, one clip each: spans of one.
+// table (zgpu_decode_ranges_seek_table_device_src): the selections are zg_k_seektab's. Three things differ: the seek's bound is the table's
+// promise and is not compared with the walk's header bound; Selection::declared is that promise, and an entry whose decoded total differs from
+// it fails with ContentSizeMismatch; an entry whose table is not usable is refused with ZGPU_E_SEEK_TABLE, unread and unwritten.
+namespace {
+int decode_ranges(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges, void* const* device_dsts,
+                  const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results, bool table) {
+  if (!c || (n && (!device_srcs || !lens || !ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  int st;
+  DeviceSink sink = device_sink(c, opts, nullptr, &st, table);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  for (uint32_t i = 0; i < n; i++) memset(&results[i], 0, sizeof results[i]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  if ((st = seek_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, &recs, &refused, table))) return st;
+  // the selections (in place of the whole entries seek_ranges checked) and what of each is wanted. An entry of which nothing is taken stays a
+  // selection, an empty one: a submit that holds only such entries is still a submit
+  std::vector<Selection> sel(n);
+  std::vector<Clip> clip(n);
+  std::vector<uint32_t> first((size_t)n + 1);
+  std::vector<uint64_t> bound(n);
+  for (uint32_t i = 0; i <= n; i++) first[i] = i;
+  for (uint32_t i = 0; i < n; i++) {
+    const zgk::Seek& s = recs[i];
+    const uint8_t ref = s.status ? (uint8_t)(s.status == ZGPU_E_SEEK_TABLE ? ZGPU_E_SEEK_TABLE : 1) : refused[i];   // (a status: an anchor behind the entry or behind begin; no usable table)
+    const bool none = ref || !ranges[i].len || (s.flags & zgk::kNothing);   // (nothing is read, decoded or written)
+    const bool closed = !(s.flags & (zgk::kOpenEnded | zgk::kBroken));
+    const uint64_t declared = none ? (table ? 0 : UINT64_MAX) : closed ? s.plain_seen - s.plain_lo : UINT64_MAX;   // (table: an entry of which nothing is taken promises nothing)
+    sel[i] = Selection{i, none ? 0 : s.src_lo, none ? 0 : s.src_hi, declared, s.frames_skipped, none ? 0u : s.frames_taken, ref};
+    clip[i] = Clip{none ? 0 : ranges[i].begin - s.plain_lo, ranges[i].len, (uint8_t*)device_dsts[i], caps[i], 0, false};
+    bound[i] = s.bound;
+  }
+  std::vector<zgpu_device_entry_result> dres(n);
+  st = decode_selections(c, sink, device_srcs, lens, sel, clip, first, table, table ? nullptr : bound.data(), dres.data());   // (the table's bound is its promise: not compared)
+  for (uint32_t i = 0; i < n && !st; i++) results[i].d = dres[i];
+  records_out(recs, false, n, [&](uint32_t i) { return &results[i].seek; });
+  return st;
+}
+}  // namespace
+
+extern "C" int zgpu_decode_ranges_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, const zgpu_range* ranges,
+                                             void* const* device_dsts, const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results) {
+  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, false);
+}
+extern "C" int zgpu_decode_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                        const zgpu_range* ranges, void* const* device_dsts, const size_t* caps,
+                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
+  return decode_ranges(c, device_srcs, lens, n, ranges, device_dsts, caps, opts, results, true);
+}
+// ---- many ranges over few seekable entries (zg_seekmany.h) ------------------------------------------------------------------------------------
+static_assert(sizeof(zgpu_entry_range) == 24 && offsetof(zgpu_entry_range, entry) == 16, "include/zgpu.h");
+namespace {
+// Both calls up to the records. Every range is looked at on its own (check_entry_ranges; a refused range has ZGPU_E_BAD_ARG in its record),
+// then Engine::seekmany_pass over the entries that passed: each table scanned once, every range a binary search. dsts / caps: nullptr for
+// the seek call.
+int seek_many(zgpu_ctx* c, const void* const* srcs, const size_t* lens, uint32_t n, const zgpu_entry_range* ranges, uint32_t m, void* const* dsts,
+              const size_t* caps, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  out->assign(m, zgk::Seek{});
+  std::vector<uint8_t> is_live;
+  std::vector<uint32_t> passed;
+  check_entry_ranges(c, srcs, lens, n, ranges, m, dsts, caps, check_all, refused, &is_live, &passed);
+  // an entry that passed is a live entry of the pass, in the order in which it passed
+  std::vector<uint32_t> live_of(n, 0);
+  std::vector<Engine::DevEntry> live(passed.size());
+  for (uint32_t q = 0; q < (uint32_t)passed.size(); q++) {
+    live_of[passed[q]] = q;
+    live[q] = Engine::DevEntry{(uint64_t)(uintptr_t)srcs[passed[q]], (uint64_t)lens[passed[q]]};
+  }
+  std::vector<Engine::ManyRange> mr(m);
+  for (uint32_t j = 0; j < m; j++)
+    mr[j] = is_live[j] ? Engine::ManyRange{ranges[j].begin, ranges[j].len, live_of[ranges[j].entry]} : Engine::ManyRange{ranges[j].begin, 0, 0};
+  Engine::ManyStats more;
+  const int st = drain(c, c->eng->seekmany_pass(live.data(), (uint32_t)live.size(), mr.data(), m, out->data(), c->ranges_stats, &more));
+  uint64_t* ms = c->ranges_many_stats;
+  ms[kManyStatPrefixLaunches] = more.prefix_launches; ms[kManyStatPrefixUs] = more.prefix_us;
+  ms[kManyStatFindLaunches] = more.find_launches; ms[kManyStatFindUs] = more.find_us; ms[kManyStatPrefixScratchBytes] = more.scratch_bytes;
+  if (st) return st;
+  return accept_records(c, out, *refused, [&](uint32_t j) { return (uint64_t)lens[ranges[j].entry]; }, (uint32_t)ZGPU_E_SEEK_TABLE,
+                        "zgpu_frames_seek_table_many_device: a record that leaves its entry");
+}
+}  // namespace
+
+extern "C" int zgpu_frames_seek_table_many_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                  const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
+  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
+  return seek_only(c, m, out, [&](auto* recs, auto* refused) { return seek_many(c, device_srcs, lens, n, ranges, m, nullptr, nullptr, recs, refused); });
+}
+
+// The ranges of one entry whose rows overlap form a GROUP (zg_seekmany.h: group_ranges), and a group is ONE selection — the rows
+// [gfirst, glast] its ranges take together: (src + C_gfirst, C_{glast + 1} - C_gfirst) is walked, cut into submits, gathered, decoded and
+// hashed once, and every range is a clip of the group's span with its own destination. What a group's frames do — a decode or walk error, a
+// size that differs from the table's promise, a checksum verdict — is the verdict of every range in it; TargetTooSmall is each range's own.
+// Both gather calls (the seek-table one and the indexed one) around their selection: select(sink, &recs, &refused) leaves the m records and
+// refusals, whatever produced the pairs they were found in, and everything behind it is shared.
+namespace {
+template <class Select>
+int gather_groups(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts,
+                  const size_t* caps, const zgpu_device_opts* opts, zgpu_range_result* results, Select select) {
+  int st;
+  DeviceSink sink = device_sink(c, opts, nullptr, &st, true);
+  if (st) return st;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgk::Seek> recs;
+  std::vector<uint8_t> refused;
+  if ((st = select(sink, &recs, &refused))) return st;
+  const zgm::Groups gs = zgm::group_ranges(ranges, recs.data(), refused.data(), m);
+  const uint32_t G = (uint32_t)gs.groups.size();
+  // the groups as selections, each with the clips of its ranges
+  std::vector<Selection> sel(G);
+  for (uint32_t g = 0; g < G; g++) {
+    const zgm::Group& gr = gs.groups[g];
+    if (gr.c_lo > gr.c_hi || gr.d_lo > gr.d_hi) { c->eng->last_error = "zgpu_gather_ranges_seek_table_device_src: records of one table out of step"; return ZGPU_E_INTERNAL; }   // (never)
+    sel[g] = Selection{gr.entry, gr.c_lo, gr.c_hi, gr.d_hi - gr.d_lo, gr.gfirst, gr.glast - gr.gfirst + 1, 0};
+  }
+  std::vector<Clip> clip(gs.order.size());
+  for (size_t q = 0; q < clip.size(); q++) {
+    const uint32_t j = gs.order[q];
+    clip[q] = Clip{gs.skip[q], ranges[j].len, (uint8_t*)device_dsts[j], caps[j], 0, false};
+  }
+  std::vector<zgpu_device_entry_result> dres(G);
+  st = decode_selections(c, sink, device_srcs, lens, sel, clip, gs.first, true, nullptr, dres.data());
+  c->ranges_many_stats[kManyStatGroupsDecoded] = G;
+  // every range's result: the group's, with the range's own count — or its own TargetTooSmall, which ranks behind the group's decode, walk
+  // and size verdicts and in front of its checksum verdicts
+  records_out(recs, false, m, [&](uint32_t j) { return &results[j].seek; });
+  for (uint32_t j = 0; j < m && !st; j++) {
+    zgpu_device_entry_result& d = results[j].d;
+    if (refused[j] || recs[j].status) { d.r.status = refused[j] ? ZGPU_E_BAD_ARG : (int)recs[j].status; continue; }
+    if (!ranges[j].len || !recs[j].frames_taken) continue;   // (nothing is read, decoded or written: status 0, written 0)
+    const zgpu_device_entry_result& gd = dres[gs.group_of[j]];
+    const Clip& cl = clip[gs.clip_of[j]];
+    const bool checks = gd.r.status == ZGPU_E_CHECKSUM_MISMATCH || gd.r.status == ZGPU_E_SEEK_CHECKSUM_MISMATCH;
+    if (gd.r.status == ZGPU_E_TARGET_TOO_SMALL || ((!gd.r.status || checks) && cl.small)) { d.r.status = ZGPU_E_TARGET_TOO_SMALL; continue; }
+    d = gd;
+    if (!gd.r.status) d.r.written = cl.written;
+  }
+  return st;
+}
+}  // namespace
+
+extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                        const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                        const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
+  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](const DeviceSink&, auto* recs, auto* refused) {
+    return seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, recs, refused);
+  });
+}
+
+// ---- seek index handles (include/zgpu.h: zgpu_seek_index; zg_seekidx.h) -------------------------------------------------------------------------
+static_assert(sizeof(zgpu_seek_index_info) == 40 && ZGPU_INDEX_UNSIZED == zgx::kUnsized && ZGPU_E_FRAME_INDEX == 74, "include/zgpu.h");
+namespace {
+// an entry the index refuses: nothing of it is held
+void refuse_index(zgpu_seek_index::Ent& e, uint32_t status, uint32_t why, uint32_t kind) {
+  e.info.status = status; e.info.why = why; e.info.kind = kind;
+  e.info.nrows = 0; e.info.compressed = 0; e.info.plaintext = 0;
+  e.pre = 0; e.tab = 0;
+}
+
+// The build. The table pass works in a scratch of its own (its chunk totals lie behind the prefixes); the handle's buffer is sized exactly —
+// 16 * (nrows + 1) bytes per indexed entry —, gets the table entries' pairs by one device copy each, and the declared entries' pairs straight
+// from zg_k_seekidx_rows.
+int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, uint32_t kind) {
+  zg::Engine* eng = c->eng;
+  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  std::vector<Engine::DevEntry> dev;
+  std::vector<uint8_t> refused;
+  check_entries(c, srcs, lens, nullptr, nullptr, n, check_all, &dev, &refused);
+  x->ents.assign(n, zgpu_seek_index::Ent{});
+  std::vector<uint8_t> by_chain(n, 0);   // entries the chain is asked about
+  for (uint32_t i = 0; i < n; i++) {
+    x->ents[i].info.len = lens[i];
+    if (refused[i]) refuse_index(x->ents[i], ZGPU_E_BAD_ARG, 0, kind == ZGPU_INDEX_DECLARED ? ZGPU_INDEX_DECLARED : ZGPU_INDEX_SEEK_TABLE);
+    else by_chain[i] = kind == ZGPU_INDEX_DECLARED;
+  }
+  uint64_t* stats = x->stats;
+  // the tables
+  zg::DevBuf scratch;
+  std::vector<zgm::Loc> loc;
+  std::vector<uint64_t> tpre;
+  std::vector<uint32_t> tab_of;   // the entries the table pass was asked about
+  struct Free { zg::DevBuf& b; ~Free() { b.release(); } } free_scratch{scratch};
+  if (kind != ZGPU_INDEX_DECLARED) {
+    std::vector<Engine::DevEntry> live;
+    for (uint32_t i = 0; i < n; i++) if (!refused[i]) { tab_of.push_back(i); live.push_back(dev[i]); }
+    loc.resize(live.size());
+    tpre.assign(live.size(), 0);
+    Engine::ManyStats more;
+    uint64_t npairs = 0;
+    const int st = eng->seekmany_prefixes(live.data(), (uint32_t)live.size(), loc.data(), tpre.data(), &scratch, &npairs, stats, &more);
+    stats[kSeekIdxStatLaunches] += more.prefix_launches; stats[kSeekIdxStatKernelUs] += more.prefix_us;
+    if (st) return st;
+    for (size_t q = 0; q < tab_of.size(); q++) {
+      zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+      if (loc[q].why == zgt::kNone && kind == ZGPU_INDEX_AUTO) by_chain[tab_of[q]] = 1;
+      else if (loc[q].why) refuse_index(e, ZGPU_E_SEEK_TABLE, loc[q].why, ZGPU_INDEX_SEEK_TABLE);
+      else { e.info.kind = ZGPU_INDEX_SEEK_TABLE; e.info.nrows = loc[q].nf; e.tab = loc[q].tab; }
+    }
+  }
+  // the chains: the summary pass says which entries can be indexed and how many rows each has
+  std::vector<uint32_t> ch_of;
+  std::vector<Engine::DevEntry> chain;
+  for (uint32_t i = 0; i < n; i++) if (by_chain[i]) { ch_of.push_back(i); chain.push_back(dev[i]); }
+  std::vector<zgi::Entry> sum(chain.size());
+  int st = eng->index_pass(chain.data(), (uint32_t)chain.size(), nullptr, nullptr, sum.data(), nullptr, stats);
+  if (st) return st;
+  for (size_t q = 0; q < ch_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
+    const uint32_t why = zgx::refusal(sum[q]);
+    if (sum[q].chain_end > lens[ch_of[q]]) { eng->last_error = "zgpu_seek_index_create_device: a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
+    if (why) refuse_index(e, ZGPU_E_FRAME_INDEX, why, ZGPU_INDEX_DECLARED);
+    else if (sum[q].nrec > zgt::kMaxFrames) refuse_index(e, ZGPU_E_FRAME_INDEX, ZGPU_SEEKTAB_TOO_LARGE, ZGPU_INDEX_DECLARED);
+    else { e.info.kind = ZGPU_INDEX_DECLARED; e.info.nrows = sum[q].nrec; e.tab = lens[ch_of[q]]; }
+  }
+  // the handle's pairs: every indexed entry's range
+  uint64_t pairs = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    zgpu_seek_index::Ent& e = x->ents[i];
+    if (e.info.status) continue;
+    e.pre = pairs;
+    pairs += (uint64_t)e.info.nrows + 1;
+  }
+  if (pairs > SIZE_MAX / sizeof(zgm::Pair)) return ZGPU_E_NOMEM;
+  if (pairs && (st = x->pairs.reserve((size_t)pairs * sizeof(zgm::Pair)))) return st;
+  stats[kSeekIdxStatDeviceBytes] = pairs * sizeof(zgm::Pair);
+  zgm::Pair* dp = x->pairs.as<zgm::Pair>();
+  hipStream_t s = eng->stream();
+  // table kind: the prefixes move over, and each entry's closing pair comes back (16 bytes: C[nrows], D[nrows])
+  std::vector<zgm::Pair> closing(tab_of.size(), zgm::Pair{0, 0});
+  for (size_t q = 0; q < tab_of.size(); q++) {
+    const zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
+    const zgm::Pair* from = scratch.as<zgm::Pair>() + tpre[q];
+    if (hipMemcpyAsync(dp + e.pre, from, ((size_t)e.info.nrows + 1) * sizeof(zgm::Pair), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(&closing[q], from + e.info.nrows, sizeof(zgm::Pair), hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+    stats[kSeekIdxStatBytesDownloaded] += sizeof(zgm::Pair);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  for (size_t q = 0; q < tab_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
+    if (e.info.status || e.info.kind != ZGPU_INDEX_SEEK_TABLE) continue;
+    e.info.compressed = closing[q].c; e.info.plaintext = closing[q].d;
+  }
+  // declared kind: the rows pass over the entries the summary pass accepted
+  std::vector<zgx::Lane> lanes;
+  std::vector<uint32_t> lane_of;
+  for (size_t q = 0; q < ch_of.size(); q++) {
+    const zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
+    if (e.info.status) continue;
+    lane_of.push_back(ch_of[q]);
+    lanes.push_back(zgx::Lane{chain[q].src, chain[q].len, e.pre, e.info.nrows});
+  }
+  std::vector<zgx::Rows> rows(lanes.size());
+  if ((st = eng->seekidx_rows_pass(lanes.data(), (uint32_t)lanes.size(), dp, rows.data(), stats))) return st;
+  for (size_t q = 0; q < lane_of.size(); q++) {
+    zgpu_seek_index::Ent& e = x->ents[lane_of[q]];
+    // (a source that changed between the passes — the caller's promise broken —, or pairs that do not add up to the entry)
+    if (rows[q].why || rows[q].nrows != e.info.nrows || rows[q].c != e.info.len) {
+      eng->last_error = "zgpu_seek_index_create_device: a source changed while it was indexed";
+      return ZGPU_E_INTERNAL;
+    }
+    e.info.compressed = rows[q].c; e.info.plaintext = rows[q].d;
+  }
+  for (const zgpu_seek_index::Ent& e : x->ents) if (!e.info.status) stats[kSeekIdxStatRows] += e.info.nrows;
+  return ZGPU_OK;
+}
+
+// Both indexed calls up to the records. Every range is looked at on its own, as seek_many looks at it (check_entry_ranges), with what the
+// index alone knows of an entry: one it refused is not refused again — its ranges pass untouched and get its status and why —; srcs != nullptr
+// (the gather call): lens[i] must be the length the entry was indexed at; table_flag: ZGPU_DEVICE_VERIFY_SEEK_TABLE refuses the ranges of
+// declared-kind entries. Then ONE find launch over the handle's pairs.
+int indexed_ranges(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
+                   void* const* dsts, const size_t* caps, bool table_flag, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const uint32_t n = (uint32_t)x->ents.size();
+  out->assign(m, zgk::Seek{});
+  std::vector<uint8_t> is_live;
+  check_entry_ranges(c, srcs, lens, n, ranges, m, dsts, caps, [&](uint32_t i) {
+    const zgpu_seek_index_info& info = x->ents[i].info;
+    if (info.status) return kPass;   // (the record is the entry's status and why: written below, nothing of the entry is looked at)
+    return (srcs && (uint64_t)lens[i] != info.len) || (table_flag && info.kind != ZGPU_INDEX_SEEK_TABLE) ? kRefuse : kCheck;
+  }, refused, &is_live, nullptr);
+  std::vector<zgm::Find> lanes(m);
+  for (uint32_t j = 0; j < m; j++) {
+    const zgpu_seek_index::Ent* e = is_live[j] ? &x->ents[ranges[j].entry] : nullptr;
+    lanes[j] = e ? zgm::Find{ranges[j].begin, ranges[j].len, e->pre, e->tab, e->info.nrows, 0, 0, 0} : zgm::Find{ranges[j].begin, 0, 0, 0, 0, 0, 0, 0};
+  }
+  Engine::ManyStats more;
+  int st = drain(c, c->eng->seekmany_find(lanes.data(), m, x->pairs.as<zgm::Pair>(), out->data(), nullptr, &more));
+  c->ranges_many_stats[kManyStatFindLaunches] = more.find_launches; c->ranges_many_stats[kManyStatFindUs] = more.find_us;
+  if (st) return st;
+  // (every record is held against the length its entry was indexed at before anything is gathered)
+  if ((st = accept_records(c, out, *refused, [&](uint32_t j) { return x->ents[ranges[j].entry].info.len; }, (uint32_t)ZGPU_E_SEEK_TABLE,
+                           "zgpu_frames_seek_indexed_device: a record that leaves its entry")))
+    return st;
+  for (uint32_t j = 0; j < m; j++) {   // the ranges of entries the index refused (their lanes had length 0: records of zeros so far)
+    if ((*refused)[j] || !ranges[j].len) continue;
+    const zgpu_seek_index_info& info = x->ents[ranges[j].entry].info;
+    if (info.status) { zgk::Seek& s = (*out)[j]; s = zgk::Seek{}; s.status = info.status; s.why = info.why; }
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_seek_index_create_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t kind,
+                                             zgpu_seek_index** out) {
+  if (out) *out = nullptr;
+  if (!c || !out || kind > ZGPU_INDEX_AUTO || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
+  zgpu_seek_index* x = new zgpu_seek_index();
+  x->ctx = c;
+  const int st = drain(c, build_index(c, x, device_srcs, lens, n, kind));
+  if (st) { zgpu_seek_index_destroy(x); return st; }   // (nothing is left behind)
+  *out = x;
+  return ZGPU_OK;
+}
+extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
+  if (!x) return;
+  if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
+  x->pairs.release();
+  delete x;
+}
+extern "C" uint32_t zgpu_seek_index_entries(const zgpu_seek_index* x) { return x ? (uint32_t)x->ents.size() : 0; }
+extern "C" int zgpu_seek_index_info_of(const zgpu_seek_index* x, uint32_t i, zgpu_seek_index_info* out) {
+  if (!x || !out || i >= x->ents.size()) return ZGPU_E_BAD_ARG;
+  *out = x->ents[i].info;
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) { return x ? copy_stats(x->stats, out, n) : 0; }
+
+extern "C" int zgpu_frames_seek_indexed_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
+  if (!c || !x || x->ctx != c || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
+  return seek_only(c, m, out, [&](auto* recs, auto* refused) { return indexed_ranges(c, x, nullptr, nullptr, ranges, m, nullptr, nullptr, false, recs, refused); });
+}
+
+extern "C" int zgpu_gather_ranges_indexed_device_src(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                     const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                     const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results)))
+    return ZGPU_E_BAD_ARG;
+  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](const DeviceSink& sink, auto* recs, auto* refused) {
+    return indexed_ranges(c, x, device_srcs, lens, ranges, m, device_dsts, caps, sink.table_flag, recs, refused);
+  });
+}
+
+extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
+  if (!c) return 0;
+  const int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others)
+  return k < (int)kRangeStatCount || !out ? k : k + copy_stats(c->ranges_many_stats, out + k, n - k);
+}

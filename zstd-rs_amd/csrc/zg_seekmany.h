@@ -66,6 +66,63 @@ inline uint32_t chunks_of(uint32_t nf, uint32_t ch) { return nf ? (nf + ch - 1) 
 }  // namespace zgm
 #endif  // ZG_SEEKMANY_TYPES
 
+// ---- the groups of a gather call (host only; zg_ranges.cpp: gather_groups, tests/test_seekmany_cpu.py) ------------------------------------------
+// The ranges of one entry whose rows overlap form a GROUP — the rows [gfirst, glast] its ranges take together, decoded once — and every range
+// of it is a clip of the group's plaintext. The ranges that take rows are sorted by (entry, first row, last row, index); one that begins at or
+// in front of the last row of the group in front of it joins that group. Plain host arithmetic on the records: no HIP call.
+#ifndef ZG_SEEKMANY_GROUPS
+#define ZG_SEEKMANY_GROUPS
+#include <algorithm>
+#include <vector>
+namespace zgm {
+
+struct Group { uint32_t entry, gfirst, glast; uint64_t c_lo, c_hi, d_lo, d_hi; };
+struct Groups {
+  std::vector<Group> groups;
+  std::vector<uint32_t> group_of, clip_of;   // per range (0 where it takes no rows)
+  std::vector<uint32_t> order;               // clip q is range order[q]; group g's clips are [first[g], first[g + 1])
+  std::vector<uint32_t> first;               // groups + 1 slots
+  std::vector<uint64_t> skip;                // per clip: where it begins in its group's plaintext (begin - d_lo)
+};
+// ranges[j] (anything with .entry, .begin, .len) has the record recs[j]: rows [frames_skipped, frames_skipped + frames_taken), bytes
+// [src_lo, src_hi) and plaintext [plain_lo, plain_seen) of its entry. Only a range that takes rows is in a group: one that is not refused,
+// has a length, and whose record has a status of 0 and frames_taken > 0.
+template <class R> Groups group_ranges(const R* ranges, const zgk::Seek* recs, const uint8_t* refused, uint32_t m) {
+  Groups o;
+  for (uint32_t j = 0; j < m; j++)
+    if (!refused[j] && ranges[j].len && !recs[j].status && recs[j].frames_taken) o.order.push_back(j);
+  std::sort(o.order.begin(), o.order.end(), [&](uint32_t a, uint32_t b) {
+    const zgk::Seek& x = recs[a], & y = recs[b];
+    if (ranges[a].entry != ranges[b].entry) return ranges[a].entry < ranges[b].entry;
+    if (x.frames_skipped != y.frames_skipped) return x.frames_skipped < y.frames_skipped;
+    if (x.frames_taken != y.frames_taken) return x.frames_taken < y.frames_taken;
+    return a < b;
+  });
+  o.group_of.assign(m, 0);
+  o.clip_of.assign(m, 0);
+  o.skip.reserve(o.order.size());
+  for (uint32_t q = 0; q < (uint32_t)o.order.size(); q++) {
+    const uint32_t j = o.order[q];
+    const zgk::Seek& s = recs[j];
+    const uint32_t first = s.frames_skipped, last = s.frames_skipped + s.frames_taken - 1;
+    if (o.groups.empty() || o.groups.back().entry != ranges[j].entry || first > o.groups.back().glast) {
+      o.groups.push_back(Group{ranges[j].entry, first, last, s.src_lo, s.src_hi, s.plain_lo, s.plain_seen});
+      o.first.push_back(q);
+    } else if (last > o.groups.back().glast) {
+      Group& g = o.groups.back();
+      g.glast = last; g.c_hi = s.src_hi; g.d_hi = s.plain_seen;
+    }
+    o.group_of[j] = (uint32_t)o.groups.size() - 1;
+    o.clip_of[j] = q;
+    o.skip.push_back(ranges[j].begin - o.groups.back().d_lo);
+  }
+  o.first.push_back((uint32_t)o.order.size());
+  return o;
+}
+
+}  // namespace zgm
+#endif  // ZG_SEEKMANY_GROUPS
+
 #if defined(ZX_DEV) && !defined(ZG_SEEKMANY_WAVE)
 #define ZG_SEEKMANY_WAVE
 namespace zgm {

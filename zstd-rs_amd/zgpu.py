@@ -812,24 +812,32 @@ class Context:
             rg[i] = RangeC(int(ranges[i][0]), int(ranges[i][1]), int(a[0]), int(a[1]))
         return rg
 
+    def _seek_call(self, what, m, *args):
+        """the body of every seek call: zgpu_<what>(context, *args, out) gives one Seek per range, m of them. args: what lies between the
+        context and the records — the sources and lengths with n, or the index handle, then the marshalled ranges, with m where the call
+        counts them on their own"""
+        out = (SeekC * max(m, 1))()
+        self._check(getattr(self.L, "zgpu_" + what)(self.h, *args, out))
+        return [Seek(c) for c in out[:m]]
+
+    def _decode_call(self, what, m, args, dst_ptrs, caps, opts):
+        """the body of every range-decode and gather call: zgpu_<what>(context, *args, destinations, capacities, options, results) gives
+        (results, seeks), m of each. args: as _seek_call takes them"""
+        res = (RangeResultC * max(m, 1))()
+        self._check(getattr(self.L, "zgpu_" + what)(self.h, *args, _ptr_array(dst_ptrs), _size_array(caps), C.byref(opts), res))
+        return _results(res, m), [Seek(res[j].seek) for j in range(m)]
+
     def _frames_seek(self, what, src_ptrs, lens, ranges, anchors):
-        """the body of the two seek calls: zgpu_<what> on the sources and ranges (anchors: None for the seek-table form)"""
+        """the two seek calls with one range per entry (anchors: None for the seek-table form)"""
         n = len(src_ptrs)
         _one_per(what, n, lens, ranges, anchors)
-        out = (SeekC * max(n, 1))()
-        fn = getattr(self.L, "zgpu_" + what)
-        self._check(fn(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors), out))
-        return [Seek(c) for c in out[:n]]
+        return self._seek_call(what, n, _ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors))
 
     def _decode_ranges(self, what, src_ptrs, lens, ranges, anchors, dst_ptrs, caps, opts):
-        """the body of the two range-decode calls: zgpu_<what> (anchors: None for the seek-table form)"""
+        """the two range-decode calls with one range per entry (anchors: None for the seek-table form)"""
         n = len(src_ptrs)
         _one_per(what, n, lens, ranges, anchors, dst_ptrs, caps)
-        res = (RangeResultC * max(n, 1))()
-        fn = getattr(self.L, "zgpu_" + what)
-        self._check(fn(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors), _ptr_array(dst_ptrs), _size_array(caps),
-                       C.byref(opts), res))
-        return _results(res, n), [Seek(res[i].seek) for i in range(n)]
+        return self._decode_call(what, n, (_ptr_array(src_ptrs), _size_array(lens), n, self._ranges(ranges, anchors)), dst_ptrs, caps, opts)
 
     def frames_seek_device(self, src_ptrs, lens, ranges, anchors=None):
         """zgpu_frames_seek_device: which whole frames of entries in DEVICE memory hold plaintext bytes [begin, begin + len) of them, from
@@ -881,9 +889,7 @@ class Context:
         entry is out of range gets E_BAD_ARG in its record, the others are unaffected."""
         n, m = len(src_ptrs), len(ranges)
         _one_per("frames_seek_table_many_device", n, lens)
-        out = (SeekC * max(m, 1))()
-        self._check(self.L.zgpu_frames_seek_table_many_device(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m, out))
-        return [Seek(c) for c in out[:m]]
+        return self._seek_call("frames_seek_table_many_device", m, _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m)
 
     def gather_ranges_seek_table_device_src(self, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
                                             verify_table=False):
@@ -896,11 +902,8 @@ class Context:
         n, m = len(src_ptrs), len(ranges)
         _one_per("gather_ranges_seek_table_device_src", n, lens)
         _one_per("gather_ranges_seek_table_device_src", m, dst_ptrs, caps)
-        res = (RangeResultC * max(m, 1))()
-        self._check(self.L.zgpu_gather_ranges_seek_table_device_src(self.h, _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m,
-                                                                    _ptr_array(dst_ptrs), _size_array(caps),
-                                                                    C.byref(_opts(hash_max, no_hash, verify, verify_table)), res))
-        return _results(res, m), [Seek(res[j].seek) for j in range(m)]
+        return self._decode_call("gather_ranges_seek_table_device_src", m, (_ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m),
+                                 dst_ptrs, caps, _opts(hash_max, no_hash, verify, verify_table))
 
     # the slots zgpu_debug_ranges_stats appends behind _STATS["Context.ranges_stats"] (csrc/zg_capi_int.h: kManyStat*, an enumeration of its own)
     GATHER_STATS = ("groups_decoded", "prefix_launches", "prefix_us", "find_launches", "find_us", "prefix_scratch_bytes")
@@ -942,9 +945,7 @@ class Context:
         in src_lo, src_hi, plain_lo, plain_seen and `nothing` (frames_skipped / frames_taken count rows, skippable frames included). A range
         of an entry the index refused carries that entry's status and why."""
         m = len(ranges)
-        out = (SeekC * max(m, 1))()
-        self._check(self.L.zgpu_frames_seek_indexed_device(self.h, self._index_handle(index, "frames_seek_indexed_device"), self._entry_ranges(ranges), m, out))
-        return [Seek(c) for c in out[:m]]
+        return self._seek_call("frames_seek_indexed_device", m, self._index_handle(index, "frames_seek_indexed_device"), self._entry_ranges(ranges), m)
 
     def gather_ranges_indexed_device_src(self, index, src_ptrs, lens, ranges, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
                                          verify_table=False):
@@ -956,12 +957,9 @@ class Context:
         n, m = len(src_ptrs), len(ranges)
         _one_per("gather_ranges_indexed_device_src", n, lens)
         _one_per("gather_ranges_indexed_device_src", m, dst_ptrs, caps)
-        res = (RangeResultC * max(m, 1))()
-        self._check(self.L.zgpu_gather_ranges_indexed_device_src(self.h, self._index_handle(index, "gather_ranges_indexed_device_src"),
-                                                                 _ptr_array(src_ptrs), _size_array(lens), n, self._entry_ranges(ranges), m,
-                                                                 _ptr_array(dst_ptrs), _size_array(caps),
-                                                                 C.byref(_opts(hash_max, no_hash, verify, verify_table)), res))
-        return _results(res, m), [Seek(res[j].seek) for j in range(m)]
+        return self._decode_call("gather_ranges_indexed_device_src", m,
+                                 (self._index_handle(index, "gather_ranges_indexed_device_src"), _ptr_array(src_ptrs), _size_array(lens), n,
+                                  self._entry_ranges(ranges), m), dst_ptrs, caps, _opts(hash_max, no_hash, verify, verify_table))
 
     def gather_tensor_ranges(self, tensors, ranges, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False, index=None):
         """gather_ranges_seek_table_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding
