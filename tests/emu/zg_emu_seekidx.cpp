@@ -1,11 +1,11 @@
 // zg_emu_seekidx.cpp — TEST-ONLY: runs the SOURCE of a declared-kind seek index (zstd-rs_amd/csrc/zg_seekidx.h: the rows routine; zg_index.h:
 // the summary pass; zg_seekmany.h: the find pass) on the CPU through the SIMT emulator of zg_simt.h, laid out as zgpu_seek_index_create_device
 // and zgpu_frames_seek_indexed_device lay them out: one lane per entry in waves of 64, the host's decision between the passes, the pairs sized
-// from the summaries, one lane per range. tests/test_seekidx_cpu.py builds this file itself (it is not in the Makefile's library), twice: as a
-// shared library whose accessors count every read outside [0, len), every read of a block body, every pair store outside the lane's own range
-// [pre, pre + limit] and every pair load outside the entry's pairs, and — with -DSEEKIDX_MAIN — as a stand-alone AddressSanitizer program in
-// which every entry and the pairs lie in heap blocks of exactly their size. Both hand back every record, and zgk::seek_entry's record for the
-// same range (anchor 0) beside it. Not part of the product.
+// from the summaries, one lane per range. tests/test_seekidx_cpu.py builds this file (tests/lanesuite.py; it is not in the Makefile's library),
+// twice: as a shared library whose accessors count every read outside [0, len), every read of a block body, every pair store outside the
+// lane's own range [pre, pre + limit] and every pair load outside the entry's pairs, and — with -DSEEKIDX_MAIN — as a stand-alone
+// AddressSanitizer program in which every entry and the pairs lie in heap blocks of exactly their size (zg_lane_mem.h). Both hand back every
+// record, and zgk::seek_entry's record for the same range (anchor 0) beside it. Not part of the product.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,36 +16,23 @@
 #include "../../zstd-rs_amd/csrc/zg_seektab.h"
 #include "../../zstd-rs_amd/csrc/zg_seekmany.h"
 #include "../../zstd-rs_amd/csrc/zg_seekidx.h"
+#include "zg_lane_mem.h"
 
 namespace {
-struct Count { uint64_t bad_reads = 0, body_reads = 0, bad_stores = 0, bad_loads = 0, stores = 0; };
-struct Reader {   // the entry as a lane may see it: bytes [0, len), and none that belongs to a block body
-  const uint8_t* p; uint64_t len; const uint8_t* body; Count* c;
-  uint8_t ld1(uint64_t off) const {
-    if (off >= len) { c->bad_reads++; return 0; }
-    if (body && body[off]) c->body_reads++;
-    return p[off];
-  }
+using Reader = lane::Reader<uint8_t>;   // the entry as a lane may see it: bytes [0, len), and none that belongs to a block body
+using Direct = lane::Direct<uint8_t>;
+// the pairs under the names the passes use. A: lane::Array<zgm::Pair> over the pairs lane i may write, [pre, pre + limit], or over the pairs
+// find may read, those of the call (an access outside is counted and dropped), or lane::DirectArray<zgm::Pair>
+template <class A> struct Pairs {
+  A a;
+  void ld(uint64_t i, uint64_t* c, uint64_t* d) const { const zgm::Pair x = a.ld(i); *c = x.c; *d = x.d; }
+  uint64_t ld_d(uint64_t i) const { return a.ld(i).d; }
+  void st(uint64_t i, uint64_t c, uint64_t d) const { a.st(i, zgm::Pair{c, d}); }
 };
-struct Direct { const uint8_t* p; uint8_t ld1(uint64_t off) const { return p[off]; } };
-struct PairStore {   // the pairs lane i may write: [lo, hi]; a store outside is counted and dropped
-  zgm::Pair* p; uint64_t lo, hi; Count* c;
-  void st(uint64_t i, uint64_t a, uint64_t b) const { c->stores++; if (i < lo || i > hi) { c->bad_stores++; return; } p[i].c = a; p[i].d = b; }
-};
-struct PairLoad {    // find reads the pairs of the call only: [0, n)
-  const zgm::Pair* p; uint64_t n; Count* c;
-  bool ok(uint64_t i) const { if (i >= n) { c->bad_loads++; return false; } return true; }
-  void ld(uint64_t i, uint64_t* a, uint64_t* b) const { *a = *b = 0; if (ok(i)) { *a = p[i].c; *b = p[i].d; } }
-  uint64_t ld_d(uint64_t i) const { return ok(i) ? p[i].d : 0; }
-};
-struct DirectPairs {
-  zgm::Pair* p;
-  void ld(uint64_t i, uint64_t* a, uint64_t* b) const { *a = p[i].c; *b = p[i].d; }
-  uint64_t ld_d(uint64_t i) const { return p[i].d; }
-  void st(uint64_t i, uint64_t a, uint64_t b) const { p[i].c = a; p[i].d = b; }
-};
+using CountedPairs = Pairs<lane::Array<zgm::Pair>>;
+using DirectPairs = Pairs<lane::DirectArray<zgm::Pair>>;
 struct NoRecs { void put(uint64_t, const zgi::FrameRec&) const {} };
-struct WalkWriter { zgw::Rec* recs; void put(uint64_t i, const zgw::Rec& x) const { recs[i] = x; } };
+using WalkWriter = lane::DirectArray<zgw::Rec>;
 
 // body[off] != 0: byte off of the entry belongs to a block body (from zgw::walk_entry's records: existing code, not the routine under test)
 std::vector<uint8_t> bodies(const uint8_t* data, uint64_t len) {
@@ -101,7 +88,7 @@ bool launch(const uint64_t* lens, uint32_t n, int64_t cut, const uint64_t* range
   }
   zgm::Pair* pairs = (zgm::Pair*)malloc(total ? (size_t)total * sizeof(zgm::Pair) : 1);   // exactly: a store behind it is an AddressSanitizer report
   if (!pairs) return false;
-  memset(pairs, 0xEE, (size_t)total * sizeof(zgm::Pair));
+  memset(pairs, lane::kFill, (size_t)total * sizeof(zgm::Pair));
   *pairs_out = pairs; *npairs = total;
   // rows pass: zg_k_seekidx_rows, one lane per entry the host accepted
   const uint32_t nl = (uint32_t)live.size();
@@ -148,15 +135,15 @@ bool five_same(const zgk::Seek& a, const zgk::Seek& b) {
 // plain_seen and flag bit 2; UINT32_MAX: no memory.
 extern "C" uint32_t zgemu_seekidx(const uint8_t* const* entries, const uint64_t* lens, uint32_t n, int64_t cut, const uint64_t* ranges, uint32_t m,
                                   void* out, uint64_t* counts, uint64_t* meta, uint64_t* pairs, uint64_t cap, uint64_t* npairs) {
-  Count c;
+  lane::Count rc, sc, lc;   // reads of the entries, pair stores of the rows pass, pair loads of the find pass
   std::vector<std::vector<uint8_t>> body(n);
   for (uint32_t i = 0; i < n; i++) body[i] = bodies(entries[i], lens[i]);
   std::vector<Built> built;
   std::vector<zgk::Seek> recs(m ? m : 1);
   zgm::Pair* block = nullptr;
-  if (!launch(lens, n, cut, ranges, m, [&](uint32_t i) { return Reader{entries[i], lens[i], body[i].data(), &c}; },
-              [&](zgm::Pair* p, uint64_t lo, uint64_t hi) { return PairStore{p, lo, hi, &c}; },
-              [&](zgm::Pair* p, uint64_t np) { return PairLoad{p, np, &c}; }, &built, &block, npairs, recs.data()))
+  if (!launch(lens, n, cut, ranges, m, [&](uint32_t i) { return Reader::over(entries[i], 0, lens[i], &rc, body[i].data()); },
+              [&](zgm::Pair* p, uint64_t lo, uint64_t hi) { return CountedPairs{{p, lo, hi + 1, &sc}}; },
+              [&](zgm::Pair* p, uint64_t np) { return CountedPairs{{p, 0, np, &lc}}; }, &built, &block, npairs, recs.data()))
     return UINT32_MAX;
   uint32_t differ = 0;
   for (uint32_t j = 0; j < m; j++) {
@@ -166,7 +153,7 @@ extern "C" uint32_t zgemu_seekidx(const uint8_t* const* entries, const uint64_t*
     if (!five_same(ref, recs[j])) differ++;
   }
   memcpy(out, recs.data(), 64 * (size_t)m);
-  counts[0] = c.bad_reads; counts[1] = c.body_reads; counts[2] = c.bad_stores; counts[3] = c.bad_loads; counts[4] = c.stores;
+  counts[0] = rc.bad; counts[1] = rc.forbidden; counts[2] = sc.bad; counts[3] = lc.bad; counts[4] = sc.n;
   for (uint32_t i = 0; i < n; i++) {
     const Built& b = built[i];
     uint64_t* o = meta + 8 * (size_t)i;
@@ -182,40 +169,34 @@ extern "C" uint32_t zgemu_seekidx(const uint8_t* const* entries, const uint64_t*
 // the m records, 64 bytes each, then per entry (u64 accepted, u64 nrows). Every entry lies in a heap block of exactly its length, the pairs in
 // one of exactly their size, and both are accessed directly: an access outside either is an AddressSanitizer report.
 int main(int argc, char** argv) {
-  if (argc < 3) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  FILE* g = fopen(argv[2], "wb");
-  if (!f || !g) return 2;
+  lane::CaseFile f(argc > 2 ? argv[1] : nullptr, "rb"), g(argc > 2 ? argv[2] : nullptr, "wb");
   uint64_t launches = 0, runs = 0, hdr[3];
-  for (; fread(hdr, 8, 3, f) == 3; launches++) {
+  for (; f.next(hdr, 24); launches++) {
     const uint32_t n = (uint32_t)hdr[0], m = (uint32_t)hdr[1];
     std::vector<uint64_t> lens(n + 1), rg(3 * (size_t)m + 1);
-    if (n && fread(lens.data(), 8, n, f) != n) return 2;
-    if (m && fread(rg.data(), 24, m, f) != m) return 2;
+    f.read(lens.data(), 8, n);
+    f.read(rg.data(), 24, m);
     std::vector<uint8_t*> e(n + 1, nullptr);
-    for (uint32_t i = 0; i < n; i++) {
-      e[i] = (uint8_t*)malloc(lens[i] ? lens[i] : 1);
-      if (!e[i] || (lens[i] && fread(e[i], 1, lens[i], f) != lens[i])) return 2;
-    }
+    for (uint32_t i = 0; i < n; i++) e[i] = f.block(lens[i]);
     std::vector<Built> built;
     std::vector<zgk::Seek> recs(m ? m : 1);
     zgm::Pair* block = nullptr;
     uint64_t npairs = 0;
     if (!launch(lens.data(), n, (int64_t)hdr[2], rg.data(), m, [&](uint32_t i) { return Direct{e[i]}; },
-                [&](zgm::Pair* p, uint64_t, uint64_t) { return DirectPairs{p}; }, [&](zgm::Pair* p, uint64_t) { return DirectPairs{p}; }, &built,
+                [&](zgm::Pair* p, uint64_t, uint64_t) { return DirectPairs{{p}}; }, [&](zgm::Pair* p, uint64_t) { return DirectPairs{{p}}; }, &built,
                 &block, &npairs, recs.data()))
-      return 2;
-    if (m && fwrite(recs.data(), 64, m, g) != m) return 2;
+      return lane::kExitIO;
+    g.write(recs.data(), 64, m);
     for (uint32_t i = 0; i < n; i++) {
       const uint64_t o[2] = {built[i].ok, built[i].rows.nrows};
-      if (fwrite(o, 8, 2, g) != 2) return 2;
+      g.write(o, 8, 2);
     }
     runs += m;
     free(block);
     for (uint8_t* p : e) free(p);
   }
-  fclose(f);
-  if (fclose(g)) return 2;
+  f.close();
+  g.close();
   printf("seekidx_asan ok: %llu launches, %llu ranges\n", (unsigned long long)launches, (unsigned long long)runs);
   return 0;
 }

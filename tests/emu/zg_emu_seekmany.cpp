@@ -1,11 +1,11 @@
 // zg_emu_seekmany.cpp — TEST-ONLY: runs the SOURCE of the seek-many passes (zstd-rs_amd/csrc/zg_seekmany.h: locate, total, prefix, find) on
 // the CPU through the SIMT emulator of zg_simt.h, laid out as Engine::seekmany_pass lays them out: one lane per entry, one wave per chunk, one
-// lane per range, the scratch sized from the located row count. tests/test_seekmany_cpu.py builds this file itself (it is not in the Makefile's
-// library), twice: as a shared library whose accessors count every access and every access outside the entry's window and outside the
-// scratch, and — with -DSEEKMANY_MAIN — as a stand-alone AddressSanitizer program in which every entry and the scratch lie in heap blocks of
-// exactly their length. Both hand back every record (and the library the prefix sums), and both can run zgt::seektab_entry's wave beside every
-// range and compare the two records (the program does for entries below 8 KiB, in its first round). The library also exports the host-side
-// grouping of the gather calls (zgm::group_ranges), which needs no emulator. Not part of the product.
+// lane per range, the scratch sized from the located row count. tests/test_seekmany_cpu.py builds this file (tests/lanesuite.py; it is not in
+// the Makefile's library), twice: as a shared library whose accessors count every access and every access outside the entry's window and
+// outside the scratch, and — with -DSEEKMANY_MAIN — as a stand-alone AddressSanitizer program in which every entry and the scratch lie in heap
+// blocks of exactly their length (zg_lane_mem.h). Both hand back every record (and the library the prefix sums), and both can run
+// zgt::seektab_entry's wave beside every range and compare the two records (the program does for entries below 8 KiB, in its first round).
+// The library also exports the host-side grouping of the gather calls (zgm::group_ranges), which needs no emulator. Not part of the product.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,41 +15,20 @@
 #include "zg_simt.h"
 #include "../../zstd-rs_amd/csrc/zg_seektab.h"
 #include "../../zstd-rs_amd/csrc/zg_seekmany.h"
+#include "zg_lane_mem.h"
 
 namespace {
-struct Count { uint64_t reads = 0, bad = 0, pairs = 0, bad_pairs = 0; };
-struct Reader {   // the entry as the passes may see it: bytes [lo, len)
-  const uint8_t* p; uint64_t lo, len; Count* c;
-  bool ok(uint64_t off, uint64_t n) const { c->reads++; if (off < lo || off > len || n > len - off) { c->bad++; return false; } return true; }
-  uint32_t ld1(uint64_t off) const { return ok(off, 1) ? p[off] : 0u; }
-  uint32_t ld4(uint64_t off) const { uint32_t v = 0; if (ok(off, 4)) memcpy(&v, p + off, 4); return v; }
-  void ld8(uint64_t off, uint32_t* a, uint32_t* b) const { *a = *b = 0; if (ok(off, 8)) { memcpy(a, p + off, 4); memcpy(b, p + off + 4, 4); } }
+using Reader = lane::Reader<uint32_t>;   // the entry as the passes may see it: bytes [lo, len)
+using Direct = lane::Direct<uint32_t>;
+// the scratch under the names the passes use. A: lane::Array<zgm::Pair> over its n pairs (an access outside is counted and dropped), or
+// lane::DirectArray<zgm::Pair>
+template <class A> struct Pairs {
+  A a;
+  void ld(uint64_t i, uint64_t* c, uint64_t* d) const { const zgm::Pair x = a.ld(i); *c = x.c; *d = x.d; }
+  uint64_t ld_d(uint64_t i) const { return a.ld(i).d; }
+  void st(uint64_t i, uint64_t c, uint64_t d) const { a.st(i, zgm::Pair{c, d}); }
 };
-struct Direct {   // no checks: what the kernel's reader does
-  const uint8_t* p;
-  uint32_t ld1(uint64_t off) const { return p[off]; }
-  uint32_t ld4(uint64_t off) const { uint32_t v; memcpy(&v, p + off, 4); return v; }
-  void ld8(uint64_t off, uint32_t* a, uint32_t* b) const { memcpy(a, p + off, 4); memcpy(b, p + off + 4, 4); }
-};
-struct Pairs {   // the scratch: n pairs; an access outside is counted and dropped
-  zgm::Pair* p; uint64_t n; Count* c;
-  bool ok(uint64_t i) const { c->pairs++; if (i >= n) { c->bad_pairs++; return false; } return true; }
-  void ld(uint64_t i, uint64_t* a, uint64_t* b) const { *a = *b = 0; if (ok(i)) { *a = p[i].c; *b = p[i].d; } }
-  uint64_t ld_d(uint64_t i) const { return ok(i) ? p[i].d : 0; }
-  void st(uint64_t i, uint64_t a, uint64_t b) const { if (ok(i)) { p[i].c = a; p[i].d = b; } }
-};
-struct DirectPairs {
-  zgm::Pair* p;
-  void ld(uint64_t i, uint64_t* a, uint64_t* b) const { *a = p[i].c; *b = p[i].d; }
-  uint64_t ld_d(uint64_t i) const { return p[i].d; }
-  void st(uint64_t i, uint64_t a, uint64_t b) const { p[i].c = a; p[i].d = b; }
-};
-
-bool same(const zgk::Seek& a, const zgk::Seek& b) {
-  return a.src_lo == b.src_lo && a.src_hi == b.src_hi && a.plain_lo == b.plain_lo && a.bound == b.bound && a.plain_seen == b.plain_seen &&
-         a.status == b.status && a.frames_skipped == b.frames_skipped && a.frames_taken == b.frames_taken && a.nblocks == b.nblocks &&
-         a.why == b.why && a.flags == b.flags;
-}
+using DirectPairs = Pairs<lane::DirectArray<zgm::Pair>>;
 
 // One entry, n ranges, the four passes as the engine runs them. MakeR(base) / MakeS(pairs, count): the accessors. out: n records as find's
 // lanes stored them; *loc: what locate stored; scratch: the block the passes used (prefixes, then chunk totals). Returns the number of ranges
@@ -58,7 +37,7 @@ template <uint32_t CH, class R, class MakeS>
 uint32_t passes(const R& r, const uint8_t* entry, uint64_t len, const uint64_t* ranges, uint32_t n, zgk::Seek* out, zgm::Loc* loc,
                 std::vector<zgm::Pair*>* keep, MakeS make_s, uint64_t* npairs, bool compare) {
   alignas(16) static zgm::Loc stored_loc;
-  memset(&stored_loc, 0xEE, sizeof stored_loc);
+  memset(&stored_loc, lane::kFill, sizeof stored_loc);
   memset(loc, 0, sizeof *loc);
   *npairs = 0;
   bool live = false;
@@ -74,7 +53,7 @@ uint32_t passes(const R& r, const uint8_t* entry, uint64_t len, const uint64_t* 
       total_pairs = pre_pairs + nq;
       pairs = (zgm::Pair*)malloc((size_t)total_pairs * sizeof(zgm::Pair));   // exactly: a store behind it is an AddressSanitizer report
       if (!pairs) return UINT32_MAX;
-      memset(pairs, 0xEE, (size_t)total_pairs * sizeof(zgm::Pair));
+      memset(pairs, lane::kFill, (size_t)total_pairs * sizeof(zgm::Pair));
       keep->push_back(pairs);
       const auto s = make_s(pairs, total_pairs);
       for (int pass = 0; pass < 2; pass++)
@@ -104,7 +83,7 @@ uint32_t passes(const R& r, const uint8_t* entry, uint64_t len, const uint64_t* 
     if (!compare) continue;
     zgk::Seek ref;
     simt::run(64, [&]() { const zgk::Seek o = zgt::seektab_entry(Direct{entry}, len, ranges[2 * j], ranges[2 * j + 1]); if (zx_tid() == 0) ref = o; });
-    if (!same(ref, out[j])) differ++;
+    if (!lane::same_seek(ref, out[j])) differ++;
   }
   return differ;
 }
@@ -115,19 +94,19 @@ uint32_t passes(const R& r, const uint8_t* entry, uint64_t len, const uint64_t* 
 // compare != 0: returns how many records differ from zg_k_seektab's wave, else 0 (UINT32_MAX: a chunk size that is not built, or no memory).
 extern "C" uint32_t zgemu_seekmany(const uint8_t* entry, uint64_t len, uint64_t lo, const uint64_t* ranges, uint32_t n, uint32_t chunk, uint32_t compare, void* out,
                                    uint64_t* counts, uint64_t* meta, uint64_t* prefix, uint64_t cap) {
-  Count c;
+  lane::Count rc, pc;
   zgm::Loc loc;
   std::vector<zgm::Pair*> keep;
   std::vector<zgk::Seek> recs(n ? n : 1);
   uint64_t npairs = 0;
-  const Reader r{entry, lo, len, &c};
-  auto make_s = [&](zgm::Pair* p, uint64_t np) { return Pairs{p, np, &c}; };
+  const Reader r = Reader::over(entry, lo, len, &rc);
+  auto make_s = [&](zgm::Pair* p, uint64_t np) { return Pairs<lane::Array<zgm::Pair>>{{p, 0, np, &pc}}; };
   uint32_t differ;
   if (chunk == 128) differ = passes<128>(r, entry, len, ranges, n, recs.data(), &loc, &keep, make_s, &npairs, compare != 0);
   else if (chunk == zgm::kChunkRows) differ = passes<zgm::kChunkRows>(r, entry, len, ranges, n, recs.data(), &loc, &keep, make_s, &npairs, compare != 0);
   else return UINT32_MAX;
   memcpy(out, recs.data(), 64 * (size_t)n);
-  counts[0] = c.reads; counts[1] = c.bad; counts[2] = c.pairs; counts[3] = c.bad_pairs;
+  counts[0] = rc.n; counts[1] = rc.bad; counts[2] = pc.n; counts[3] = pc.bad;
   meta[0] = loc.why; meta[1] = loc.nf; meta[2] = loc.es; meta[3] = npairs;
   for (uint64_t i = 0; i < npairs && i < cap && !keep.empty(); i++) { prefix[2 * i] = keep[0][i].c; prefix[2 * i + 1] = keep[0][i].d; }
   for (zgm::Pair* p : keep) free(p);
@@ -168,35 +147,31 @@ extern "C" uint32_t zgemu_group_ranges(const uint64_t* in, uint32_t m, uint64_t*
 // size (128, then the product's). Every entry lies in a heap block of exactly its length, the scratch in one of exactly its size, and both are
 // accessed directly: an access outside either is an AddressSanitizer report.
 int main(int argc, char** argv) {
-  if (argc < 3) return 2;
-  FILE* g = fopen(argv[2], "wb");
-  if (!g) return 2;
+  lane::CaseFile g(argc > 2 ? argv[2] : nullptr, "wb");
   uint64_t entries = 0, runs = 0;
   for (int round = 0; round < 2; round++) {
-    FILE* f = fopen(argv[1], "rb");
-    if (!f) return 2;
+    lane::CaseFile f(argv[1], "rb");
     uint64_t hdr[2];
-    for (; fread(hdr, 8, 2, f) == 2; entries++) {
+    for (; f.next(hdr, 16); entries++) {
       std::vector<uint64_t> rg(2 * hdr[1] + 1);
-      if (hdr[1] && fread(rg.data(), 16, hdr[1], f) != hdr[1]) return 2;
-      uint8_t* e = (uint8_t*)malloc(hdr[0]);
-      if (hdr[0] && (!e || fread(e, 1, hdr[0], f) != hdr[0])) return 2;
+      f.read(rg.data(), 16, hdr[1]);
+      uint8_t* e = f.block(hdr[0]);
       std::vector<zgk::Seek> recs(hdr[1] ? hdr[1] : 1);
       std::vector<zgm::Pair*> keep;
       zgm::Loc loc;
       uint64_t npairs = 0;
-      auto make_s = [&](zgm::Pair* p, uint64_t) { return DirectPairs{p}; };
+      auto make_s = [&](zgm::Pair* p, uint64_t) { return DirectPairs{{p}}; };
       const uint32_t differ = round == 0 ? passes<128>(Direct{e}, e, hdr[0], rg.data(), (uint32_t)hdr[1], recs.data(), &loc, &keep, make_s, &npairs, hdr[0] < 8192)
                                          : passes<zgm::kChunkRows>(Direct{e}, e, hdr[0], rg.data(), (uint32_t)hdr[1], recs.data(), &loc, &keep, make_s, &npairs, false);
-      if (differ) { fprintf(stderr, "seekmany_asan: %u records differ from zg_k_seektab's\n", differ); return 3; }
-      if (hdr[1] && fwrite(recs.data(), 64, hdr[1], g) != hdr[1]) return 2;
+      if (differ) { fprintf(stderr, "seekmany_asan: %u records differ from zg_k_seektab's\n", differ); return lane::kExitLanes; }
+      g.write(recs.data(), 64, hdr[1]);
       runs += hdr[1];
       for (zgm::Pair* p : keep) free(p);
       free(e);
     }
-    fclose(f);
+    f.close();
   }
-  if (fclose(g)) return 2;
+  g.close();
   printf("seekmany_asan ok: %llu entries, %llu runs\n", (unsigned long long)entries, (unsigned long long)runs);
   return 0;
 }

@@ -2,96 +2,13 @@
 compiled with g++: every destination against a slice copy with guard bytes on both sides, every read inside the chunk's own source range,
 every 16-byte store aligned and inside the chunk's own destination range, every byte written exactly once; the chunk table cut by the
 <= 64 KiB and 16-byte rules and ordered by source and source window; a dictionary frame of the walk gets dict_len, history and carry mask, its first
-unit is not direct, and without a lookup the walk is what it was."""
+unit is not direct, and without a lookup the walk is what it was. tests/emu/zg_lane_dictfill.cpp is the harness, built by tests/lanesuite.py."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-import pytest
-
+import lanesuite
 from golden_io import read_pack
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-HARNESS = r'''
-#include "zg_dictfill.h"
-#include "zg_host_parse.h"
-namespace {
-struct Count { uint64_t bad_reads = 0, bad_writes = 0, unaligned = 0, written = 0; };
-struct Reader {   // the source as the lanes may see it: addresses [lo, hi)
-  uint64_t lo, hi; Count* c;
-  bool ok(uint64_t a, uint64_t n) const { const bool in = a >= lo && a + n <= hi; if (!in) c->bad_reads++; return in; }
-  uint8_t ld1(uint64_t a) const { return ok(a, 1) ? *(const uint8_t*)a : (uint8_t)0; }
-  zgs::V16 ld16(uint64_t a) const { zgs::V16 v{0, 0}; if (ok(a, 16)) memcpy(&v, (const void*)a, 16); return v; }
-};
-struct Writer {   // the destination: addresses [lo, hi); 16-byte stores at multiples of 16 only
-  uint64_t lo, hi; Count* c;
-  bool ok(uint64_t a, uint64_t n) const { const bool in = a >= lo && a + n <= hi; if (!in) c->bad_writes++; return in; }
-  void st1(uint64_t a, uint8_t v) const { if (ok(a, 1)) { *(uint8_t*)a = v; c->written += 1; } }
-  void st16(uint64_t a, const zgs::V16& v) const { if (a & 15) c->unaligned++; if (ok(a, 16)) { memcpy((void*)a, &v, 16); c->written += 16; } }
-};
-struct Dicts { uint32_t id; zg::DictFacts f; };
-const zg::DictFacts* find(const void* user, uint32_t id) { const Dicts* d = (const Dicts*)user; return d->id == id ? &d->f : nullptr; }
-}
-extern "C" uint64_t df_plan(const zgd::Seg* segs, uint32_t n, uint32_t chunk, zgs::Chunk* out, uint64_t cap) {
-  std::vector<zgs::Chunk> v;
-  zgd::plan_fill(segs, n, chunk, &v);
-  for (uint64_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
-  return v.size();
-}
-extern "C" void df_run(const zgd::Seg* segs, const zgs::Chunk* chunks, uint64_t nchunks, uint32_t T, uint64_t* counts) {
-  Count c;
-  uint64_t wrong_total = 0;
-  for (uint64_t i = 0; i < nchunks; i++) {
-    const zgs::Chunk ch = chunks[i];
-    const zgd::Seg sg = segs[ch.seg];
-    const Reader r{sg.src + ch.at, sg.src + ch.at + ch.len, &c};
-    const Writer w{sg.dst + ch.at, sg.dst + ch.at + ch.len, &c};
-    const uint64_t before = c.written;
-    for (uint32_t t = 0; t < T; t++) zgd::fill_chunk(r, w, segs, ch, t, T);
-    if (c.written - before != ch.len) wrong_total++;
-  }
-  counts[0] = c.bad_reads; counts[1] = c.bad_writes; counts[2] = c.unaligned; counts[3] = wrong_total;
-}
-extern "C" void df_image(uint64_t base, uint64_t len, uint64_t* out) {
-  const zgd::DictImage m = zgd::image_at(base, len);
-  out[0] = m.content; out[1] = m.fse; out[2] = m.logs; out[3] = m.huf; out[4] = m.maxbits; out[5] = zgd::image_bytes(len);
-}
-// the walk of src with (id != 0) or without a lookup that knows dictionary `id`. out: [0] walk status, [1] frames, then per frame (up to 8)
-// dict_len, hist[0..2], whether every table of its first block that can be carried is (mask as begin_frame took it: read back from the
-// lineage of a Treeless / Repeat block is not possible here, so the mask is reported as "first block's slots are the frame's carry slots"),
-// the first unit's noseq flags, nunits
-extern "C" void df_walk(const uint8_t* src, uint64_t len, uint32_t id, uint64_t content_len, const uint32_t* hist, uint64_t* out) {
-  zg::BatchBuilder bb;
-  bb.sparse_max = 0;   // (no frame is handed to zg_k_sparse: a first unit with sequences is a direct unit wherever the builder allows one)
-  std::vector<zg::FrameInfo> info;
-  Dicts d{id, zg::DictFacts{content_len, {hist[0], hist[1], hist[2]}}};
-  const zg::DictLookup lk{find, &d};
-  out[0] = (uint64_t)zg::parse_frames(src, len, 1ull << 27, &bb, &info, 0, id ? &lk : nullptr);
-  bb.finish();
-  out[1] = bb.frames.size();
-  out[2] = zg::plaintext_bound(src, len, id ? &lk : nullptr);
-  for (size_t f = 0; f < bb.frames.size() && f < 8; f++) {
-    const ZgFrame& fr = bb.frames[f];
-    uint64_t* o = out + 3 + 8 * f;
-    o[0] = fr.dict_len; o[1] = fr.hist_init[0]; o[2] = fr.hist_init[1]; o[3] = fr.hist_init[2];
-    uint64_t carried = 0;   // bit 0 Huffman, 1 LL, 2 OF, 3 ML: a block of the frame decodes with the frame's carry slot
-    for (uint32_t i = 0; i < fr.nblocks; i++) {
-      const ZgBlock& b = bb.blocks[fr.first_block + i];
-      if (b.btype != ZG_BT_COMPRESSED || b.host_status) continue;
-      if (b.huf_slot == fr.carry_huf_slot) carried |= 1;
-      if (b.nseq && b.ll_slot == (int32_t)fr.carry_slot) carried |= 2;
-      if (b.nseq && b.of_slot == (int32_t)fr.carry_slot) carried |= 4;
-      if (b.nseq && b.ml_slot == (int32_t)fr.carry_slot) carried |= 8;
-    }
-    o[4] = carried;
-    o[5] = fr.nunits ? bb.units[fr.first_unit].noseq : 99;
-    o[6] = fr.nunits;
-    o[7] = info[f].header.has_dict_id ? info[f].header.dict_id : 0;
-  }
-}
-'''
 SENT = 0xA5
 GUARD = 64
 CHUNK = 64 << 10
@@ -105,20 +22,15 @@ class Chunk(C.Structure):
     _fields_ = [("seg", C.c_uint32), ("len", C.c_uint32), ("at", C.c_uint64)]
 
 
-@pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("dictfill")
-    src, so = d / "dictfill_lane.cpp", d / "libdictfill_lane.so"
-    src.write_text(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src),
-                           os.path.join(CSRC, "zg_host_parse.cpp")])
-    L = C.CDLL(str(so))
+def _declare(L):
     L.df_plan.argtypes = [C.POINTER(Seg), C.c_uint32, C.c_uint32, C.POINTER(Chunk), C.c_uint64]
     L.df_plan.restype = C.c_uint64
     L.df_run.argtypes = [C.POINTER(Seg), C.POINTER(Chunk), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
     L.df_image.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     L.df_walk.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    return L
+
+
+lib = lanesuite.built_fixture("zg_lane_dictfill.cpp", "dictfill_lane", extra_sources=lanesuite.HOST_PARSE, declare=_declare)
 
 
 def _run(L, source, segs, threads=256):

@@ -1,61 +1,12 @@
 """zg_k_scatter's chunk plan and lane routine (zstd-rs_amd/csrc/zg_scatter.h), compiled with g++ and run lane by lane: every destination
 against a Python slice copy, guard bytes on both sides intact, every read inside the chunk's own source range, every 16-byte store aligned and
-inside the chunk's own destination range, every byte written exactly once; and zgpu_decode_frames_device's argument check, which needs no GPU."""
+inside the chunk's own destination range, every byte written exactly once; and zgpu_decode_frames_device's argument check, which needs no GPU.
+tests/emu/zg_lane_scatter.cpp is the harness, built by tests/lanesuite.py."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-import pytest
+import lanesuite
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-HARNESS = r'''
-#include "zg_scatter.h"
-namespace {
-struct Count { uint64_t bad_reads = 0, bad_writes = 0, unaligned = 0, written = 0; };
-// the source as the lanes may see it: bytes [lo, hi) of base, nothing else
-struct Reader {
-  const uint8_t* base; uint64_t lo, hi; Count* c;
-  bool ok(uint64_t off, uint64_t n) const { const bool in = off >= lo && off + n <= hi; if (!in) c->bad_reads++; return in; }
-  uint8_t ld1(uint64_t off) const { return ok(off, 1) ? base[off] : (uint8_t)0; }
-  zgs::V16 ld16(uint64_t off) const { zgs::V16 v{0, 0}; if (ok(off, 16)) memcpy(&v, base + off, 16); return v; }
-};
-// the destination: addresses [lo, hi); 16-byte stores at multiples of 16 only
-struct Writer {
-  uint64_t lo, hi; Count* c;
-  bool ok(uint64_t a, uint64_t n) const { const bool in = a >= lo && a + n <= hi; if (!in) c->bad_writes++; return in; }
-  void st1(uint64_t a, uint8_t v) const { if (ok(a, 1)) { *(uint8_t*)a = v; c->written += 1; } }
-  void st16(uint64_t a, const zgs::V16& v) const { if (a & 15) c->unaligned++; if (ok(a, 16)) { memcpy((void*)a, &v, 16); c->written += 16; } }
-};
-}
-extern "C" uint32_t sc_chunk_bytes(uint32_t want) { return zgs::chunk_bytes(want); }
-extern "C" uint32_t sc_default_chunk() { return zgs::kChunkDefault; }
-extern "C" uint32_t sc_threads() { return zgs::kThreads; }
-extern "C" uint64_t sc_plan(const zgs::Seg* segs, uint32_t n, uint32_t chunk, zgs::Chunk* out, uint64_t cap) {
-  std::vector<zgs::Chunk> v;
-  zgs::plan_chunks(segs, n, chunk, &v);
-  for (uint64_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
-  return v.size();
-}
-// what the kernel does with a chunk table, one emulated lane after the other; counts[0..3] = reads outside the chunk's source range, writes
-// outside its destination range, unaligned 16-byte stores, chunks whose lanes did not write exactly len bytes
-extern "C" void sc_run(const uint8_t* src, const zgs::Seg* segs, const zgs::Chunk* chunks, uint64_t nchunks, uint32_t T, uint64_t* counts) {
-  Count c;
-  uint64_t wrong_total = 0;
-  for (uint64_t i = 0; i < nchunks; i++) {
-    const zgs::Chunk ch = chunks[i];
-    const zgs::Seg sg = segs[ch.seg];
-    const uint64_t s = sg.src_off + ch.at, d = sg.dst + ch.at;
-    const Reader r{src, s, s + ch.len, &c};
-    const Writer w{d, d + ch.len, &c};
-    const uint64_t before = c.written;
-    for (uint32_t t = 0; t < T; t++) zgs::copy_chunk(r, w, s, d, ch.len, t, T);
-    if (c.written - before != ch.len) wrong_total++;
-  }
-  counts[0] = c.bad_reads; counts[1] = c.bad_writes; counts[2] = c.unaligned; counts[3] = wrong_total;
-}
-'''
 SENT = 0xA5
 GUARD = 64
 
@@ -68,13 +19,7 @@ class Chunk(C.Structure):
     _fields_ = [("seg", C.c_uint32), ("len", C.c_uint32), ("at", C.c_uint64)]
 
 
-@pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("scatter")
-    src, so = d / "scatter_lane.cpp", d / "libscatter_lane.so"
-    src.write_text(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+def _declare(L):
     L.sc_chunk_bytes.argtypes = [C.c_uint32]
     L.sc_chunk_bytes.restype = C.c_uint32
     L.sc_default_chunk.restype = C.c_uint32
@@ -82,7 +27,9 @@ def lib(tmp_path_factory):
     L.sc_plan.argtypes = [C.POINTER(Seg), C.c_uint32, C.c_uint32, C.POINTER(Chunk), C.c_uint64]
     L.sc_plan.restype = C.c_uint64
     L.sc_run.argtypes = [C.c_void_p, C.POINTER(Seg), C.POINTER(Chunk), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
-    return L
+
+
+lib = lanesuite.built_fixture("zg_lane_scatter.cpp", "scatter_lane", declare=_declare)
 
 
 class Source:

@@ -1,7 +1,7 @@
 """A declared-kind seek index (zstd-rs_amd/csrc/zg_seekidx.h: zg_k_seekidx_rows' lane routine), compiled with g++ over the SIMT emulator
 (tests/emu/zg_simt.h) and run on the CPU as zgpu_seek_index_create_device and zgpu_frames_seek_indexed_device lay the passes out: the summary
 pass (zgi::index_entry<false>), the host's decision, the rows pass, the host's check, the find pass (zgm::seekmany_find).
-tests/emu/zg_emu_seekidx.cpp is the harness; this file builds it itself. Demanded of every launch:
+tests/emu/zg_emu_seekidx.cpp is the harness, built by tests/lanesuite.py. Demanded of every launch:
   - the pairs of every accepted entry equal tests/seekidx.py's model (rows and prefix sums parsed from the bytes in Python);
   - reads outside [0, len) 0, reads of a block body 0, pair stores outside the lane's [pre, pre + limit] 0, pair loads outside the pairs 0;
   - every record equals the model's rule on the rows, all 64 bytes, and zgk::seek_entry's (anchor 0) in src_lo, src_hi, plain_lo, plain_seen
@@ -14,21 +14,18 @@ import ctypes as C
 import os
 import random
 import struct
-import subprocess
 import sys
 
 import pytest
 
+import lanesuite
 import seekidx
 import zgpu
 from seekidx import U64
 from test_seek_cpu import sized_frame
 from test_walk_cpu import MAGIC, block, skippable
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
-sys.path.insert(0, os.path.join(ROOT, "tools"))   # zgdata: the workload generators
+sys.path.insert(0, os.path.join(lanesuite.ROOT, "tools"))   # zgdata: the workload generators
 
 
 def eight_byte_fcs(frame):
@@ -119,19 +116,13 @@ def launches():
     return out
 
 
-@pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    d = tmp_path_factory.mktemp("seekidx")
-    src, so, exe = os.path.join(EMU, "zg_emu_seekidx.cpp"), d / "libzg_emu_seekidx.so", d / "seekidx_asan"
-    flags = ["-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-fno-strict-aliasing", "-I", CSRC]
-    subprocess.check_call(["g++", "-O2", *flags, "-shared", "-fPIC", "-o", str(so), src])
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address", "-static-libasan", "-fno-omit-frame-pointer", "-DSEEKIDX_MAIN", *flags,
-                           "-o", str(exe), src])
-    L = C.CDLL(str(so))
+def _declare(L):
     vp = C.c_void_p
     L.zgemu_seekidx.argtypes = [vp, vp, C.c_uint32, C.c_int64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp]
     L.zgemu_seekidx.restype = C.c_uint32
-    return L, str(exe), d
+
+
+built = lanesuite.built_fixture("zg_emu_seekidx.cpp", "seekidx", "SEEKIDX_MAIN", declare=_declare)
 
 
 @pytest.fixture(scope="module")
@@ -227,9 +218,7 @@ def test_seekidx_under_address_sanitizer_stand_alone(built, cases):
         for _, zs, cut, rg, _, _ in cases:
             f.write(struct.pack("<QQq", len(zs), len(rg), cut) + b"".join(struct.pack("<Q", len(e)) for e in zs) +
                     b"".join(struct.pack("<QQQ", *r) for r in rg) + b"".join(zs))
-    p = subprocess.run([exe, str(src), str(dst)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1800)
-    assert p.returncode == 0, p.stderr.decode()[-4000:]
-    assert b"seekidx_asan ok" in p.stdout and b"AddressSanitizer" not in p.stderr
+    lanesuite.run_stand_alone(exe, [src, dst], b"seekidx_asan ok", timeout=1800)
     recs = open(dst, "rb").read()
     at = 0
     for name, zs, cut, rg, idx, want in cases:

@@ -1,6 +1,6 @@
 """The seek-many passes (zstd-rs_amd/csrc/zg_seekmany.h: locate, total, prefix, find), compiled with g++ over the SIMT emulator
 (tests/emu/zg_simt.h) and run on the CPU as Engine::seekmany_pass lays them out: one lane per entry, one wave per chunk of rows, one lane per
-range, the scratch sized from the located row count. tests/emu/zg_emu_seekmany.cpp is the harness; this file builds it itself. Demanded of
+range, the scratch sized from the located row count. tests/emu/zg_emu_seekmany.cpp is the harness, built by tests/lanesuite.py. Demanded of
 every entry and every range:
   - the record equals tests/seektabs.py's model, all 64 bytes, and the one zgt::seektab_entry's wave gives for the same range;
   - no access of the entry outside [tab, len) (outside the footer, where the table is refused before its frame is located), none at all where
@@ -15,25 +15,22 @@ import ctypes as C
 import os
 import random
 import struct
-import subprocess
 from types import SimpleNamespace as NS
 
 import pytest
 
+import lanesuite
 import seekmany
 import seektabs
 import zgpu
 from seektabs import U64, model
 from test_seektab_cpu import cases as seektab_cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
 SMALL = 128
 
 
 def product_chunk():
-    text = open(os.path.join(CSRC, "zg_seekmany.h")).read()
+    text = open(os.path.join(lanesuite.CSRC, "zg_seekmany.h")).read()
     return int(text.split("constexpr uint32_t kChunkRows = ")[1].split(";")[0])
 
 
@@ -82,21 +79,15 @@ def big_cases():
     return out
 
 
-@pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    d = tmp_path_factory.mktemp("seekmany")
-    src, so, exe = os.path.join(EMU, "zg_emu_seekmany.cpp"), d / "libzg_emu_seekmany.so", d / "seekmany_asan"
-    flags = ["-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-fno-strict-aliasing", "-I", CSRC]
-    subprocess.check_call(["g++", "-O2", *flags, "-shared", "-fPIC", "-o", str(so), src])
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address", "-static-libasan", "-fno-omit-frame-pointer", "-DSEEKMANY_MAIN", *flags,
-                           "-o", str(exe), src])
-    L = C.CDLL(str(so))
+def _declare(L):
     vp = C.c_void_p
     L.zgemu_seekmany.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64]
     L.zgemu_seekmany.restype = C.c_uint32
     L.zgemu_seekmany_chunk_rows.restype = C.c_uint32
     assert L.zgemu_seekmany_chunk_rows() == product_chunk()
-    return L, str(exe), d
+
+
+built = lanesuite.built_fixture("zg_emu_seekmany.cpp", "seekmany", "SEEKMANY_MAIN", declare=_declare)
 
 
 @pytest.fixture(scope="module")
@@ -108,14 +99,12 @@ def expected():
 
 def run_passes(L, e, lo, rg, chunk, compare):
     """the entry at a 16-byte aligned address through the four passes; (records, counts, meta, prefix pairs)"""
-    buf = C.create_string_buffer(len(e) + 32)
-    at = (-C.addressof(buf)) % 16
-    C.memmove(C.addressof(buf) + at, e, len(e))
+    buf, at = lanesuite.aligned_copy(e)
     n = len(rg)
     nf_room = (len(e) // 8) + 2
     ranges, out = (C.c_uint64 * (2 * n))(*[x for r in rg for x in r]), (zgpu.SeekC * n)()
     counts, meta, prefix = (C.c_uint64 * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * (2 * nf_room))()
-    differ = L.zgemu_seekmany(C.addressof(buf) + at, len(e), lo, ranges, n, chunk, 1 if compare else 0, out, counts, meta, prefix, nf_room)
+    differ = L.zgemu_seekmany(at, len(e), lo, ranges, n, chunk, 1 if compare else 0, out, counts, meta, prefix, nf_room)
     assert differ == 0, "%d records differ from zg_k_seektab's wave" % differ
     pairs = [(prefix[2 * i], prefix[2 * i + 1]) for i in range(meta[3])]
     return [zgpu.Seek(out[i]).key() for i in range(n)], list(counts), list(meta), pairs
@@ -185,9 +174,7 @@ def test_seekmany_under_address_sanitizer_stand_alone(built, expected):
     with open(src, "wb") as f:
         for _, e, rg, _, _ in expected:
             f.write(struct.pack("<QQ", len(e), len(rg)) + b"".join(struct.pack("<QQ", *r) for r in rg) + e)
-    p = subprocess.run([exe, str(src), str(dst)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1800)
-    assert p.returncode == 0, p.stderr.decode()[-4000:]
-    assert b"seekmany_asan ok" in p.stdout and b"AddressSanitizer" not in p.stderr
+    lanesuite.run_stand_alone(exe, [src, dst], b"seekmany_asan ok", timeout=1800)
     recs = open(dst, "rb").read()
     at = 0
     for _round in range(2):   # chunks of 128 rows, then the product's

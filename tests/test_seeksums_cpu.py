@@ -1,6 +1,6 @@
 """zg_k_seeksums' wave routine and the host form of its rule (zstd-rs_amd/csrc/zg_seeksums.h), compiled with g++ over the SIMT emulator
 (tests/emu/zg_simt.h) and run on the CPU: 64 fibers, the ballots, shuffles and the prefix sum of the source as it is compiled for gfx950.
-tests/emu/zg_emu_seeksums.cpp is the harness; this file builds it itself. Every case runs over readers that count every access and every
+tests/emu/zg_emu_seeksums.cpp is the harness, built by tests/lanesuite.py. Every case runs over readers that count every access and every
 access outside what the model (tests/seeksums.py) allows. Demanded of every case:
   - the wave's record equals the model's, field for field, and all 64 lanes hold the same record;
   - the host function's record equals it too (except where the model refuses the table frame's header: the host path does not fetch it);
@@ -13,20 +13,16 @@ two rows; a table without checksums; a selection that leaves the table; a slot b
 bytes. The same cases run once more in a stand-alone AddressSanitizer program (its own main, no Python in the process) in which every entry,
 slice and digest array lies in a heap block of exactly its length."""
 import ctypes as C
-import os
 import random
 import struct
-import subprocess
 
 import pytest
 
+import lanesuite
 import seeksums
 import zgpu
 from seeksums import FIELDS, NO_ROW, model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
 TAKEN, FIRST = (0, 1, 2, 63, 64, 65, 128, 129), (0, 1, 63, 64)
 NOT_HASHED = 0xFFFFFFFF
 
@@ -154,22 +150,13 @@ def cases():
     return out
 
 
-def _flags(extra=()):
-    return ["-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-fno-strict-aliasing", "-I", CSRC, *extra]
-
-
-@pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    d = tmp_path_factory.mktemp("seeksums")
-    src, so, exe = os.path.join(EMU, "zg_emu_seeksums.cpp"), d / "libzg_emu_seeksums.so", d / "seeksums_asan"
-    subprocess.check_call(["g++", "-O2", *_flags(), "-shared", "-fPIC", "-o", str(so), src])
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address", "-static-libasan", "-fno-omit-frame-pointer", "-DSEEKSUMS_MAIN", *_flags(),
-                           "-o", str(exe), src])
-    L = C.CDLL(str(so))
+def _declare(L):
     L.zgemu_seeksums.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                  C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.zgemu_seeksums.restype = C.c_uint32
-    return L, str(exe), d
+
+
+built = lanesuite.built_fixture("zg_emu_seeksums.cpp", "seeksums", "SEEKSUMS_MAIN", declare=_declare)
 
 
 @pytest.fixture(scope="module")
@@ -195,17 +182,12 @@ def test_seeksums_equals_the_model_and_stays_inside_its_windows(built, expected)
     L, _, _ = built
     whys, seen = set(), {"differ": 0, "uncovered": 0, "unhashed": 0, "rowless": 0, "nothing": 0}
     for c, rec, win in expected:
-        buf = C.create_string_buffer(len(c.entry) + 32)
-        at = (-C.addressof(buf)) % 16
-        C.memmove(C.addressof(buf) + at, c.entry, len(c.entry))
-        fr = _packed_frames(c.frames)
-        fbuf = C.create_string_buffer(len(fr) + 32)
-        fat = (-C.addressof(fbuf)) % 16
-        C.memmove(C.addressof(fbuf) + fat, fr, len(fr))
+        buf, at = lanesuite.aligned_copy(c.entry)
+        fbuf, fat = lanesuite.aligned_copy(_packed_frames(c.frames))
         dig = (C.c_uint64 * max(len(c.digests), 1))(*c.digests)
         w = (C.c_uint64 * 6)(*[x for lo_hi in win for x in lo_hi] + [0] * (6 - 2 * len(win)))
         out, counts = C.create_string_buffer(64), (C.c_uint64 * 4)()
-        bad = L.zgemu_seeksums(C.addressof(buf) + at, len(c.entry), c.first, c.taken, C.addressof(fbuf) + fat, len(c.frames), c.lo, c.n, dig,
+        bad = L.zgemu_seeksums(at, len(c.entry), c.first, c.taken, fat, len(c.frames), c.lo, c.n, dig,
                                len(c.digests), w, len(win), out, counts)
         assert bad == 0, (c.name, "lanes of a wave disagree")
         got, host = _records(out.raw, 0)
@@ -247,9 +229,7 @@ def test_seeksums_under_address_sanitizer_stand_alone(built, expected):
         for c, _, _ in expected:
             f.write(struct.pack("<QIIII", len(c.entry), c.first, c.taken, c.n, len(c.digests)) + _packed_frames(c.slice()) +
                     b"".join(struct.pack("<Q", x) for x in c.digests) + c.entry)
-    p = subprocess.run([exe, str(src), str(dst)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, p.stderr.decode()[-4000:]
-    assert b"seeksums_asan ok" in p.stdout and b"AddressSanitizer" not in p.stderr
+    lanesuite.run_stand_alone(exe, [src, dst], b"seeksums_asan ok", timeout=900)
     recs = open(dst, "rb").read()
     assert len(recs) == 64 * len(expected)
     for i, (c, rec, _) in enumerate(expected):

@@ -1,6 +1,6 @@
 """zg_k_seektab's wave routine (zstd-rs_amd/csrc/zg_seektab.h), compiled with g++ over the SIMT emulator (tests/emu/zg_simt.h) and run on the
 CPU: 64 fibers, the ballots, shuffles and prefix sums of the source as it is compiled for gfx950. tests/emu/zg_emu_seektab.cpp is the
-harness; this file builds it itself. For every entry and every range the wave runs over a reader that counts every access and every access
+harness, built by tests/lanesuite.py. For every entry and every range the wave runs over a reader that counts every access and every access
 outside the window the model allows, and every field of its record is compared with tests/seektabs.py's model of the rule. Demanded of every
 case:
   - the record equals the model's, field for field, and all 64 lanes hold the same record;
@@ -13,20 +13,16 @@ alignment mod 16; one malformed table per `why` and every single-byte edit of th
 once more in a stand-alone AddressSanitizer program (its own main, no Python in the process) in which every entry lies in a heap block of
 exactly its length, and its records are compared with the model as well."""
 import ctypes as C
-import os
 import random
 import struct
-import subprocess
 
 import pytest
 
+import lanesuite
 import seektabs
 import zgpu
 from seektabs import U64, model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-EMU = os.path.join(ROOT, "tests", "emu")
 NFRAMES = (0, 1, 2, 63, 64, 65, 127, 128, 129, 200)
 
 
@@ -100,18 +96,12 @@ def malformed():
     return out
 
 
-@pytest.fixture(scope="module")
-def built(tmp_path_factory):
-    d = tmp_path_factory.mktemp("seektab")
-    src, so, exe = os.path.join(EMU, "zg_emu_seektab.cpp"), d / "libzg_emu_seektab.so", d / "seektab_asan"
-    flags = ["-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-fno-strict-aliasing", "-I", CSRC]
-    subprocess.check_call(["g++", "-O2", *flags, "-shared", "-fPIC", "-o", str(so), src])
-    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address", "-static-libasan", "-fno-omit-frame-pointer", "-DSEEKTAB_MAIN", *flags,
-                           "-o", str(exe), src])
-    L = C.CDLL(str(so))
+def _declare(L):
     L.zgemu_seektab.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.zgemu_seektab.restype = C.c_uint32
-    return L, str(exe), d
+
+
+built = lanesuite.built_fixture("zg_emu_seektab.cpp", "seektab", "SEEKTAB_MAIN", declare=_declare)
 
 
 @pytest.fixture(scope="module")
@@ -122,12 +112,10 @@ def expected():
 
 def run_waves(L, e, lo, rg):
     """the entry at a 16-byte aligned address, every range through the emulated wave; [(record, reads, reads outside [lo, len))]"""
-    buf = C.create_string_buffer(len(e) + 32)
-    at = (-C.addressof(buf)) % 16
-    C.memmove(C.addressof(buf) + at, e, len(e))
+    buf, at = lanesuite.aligned_copy(e)
     n = len(rg)
     ranges, out, counts = (C.c_uint64 * (2 * n))(*[x for r in rg for x in r]), (zgpu.SeekC * n)(), (C.c_uint64 * (2 * n))()
-    assert L.zgemu_seektab(C.addressof(buf) + at, len(e), lo, ranges, n, out, counts) == 0, "lanes of a wave disagree"
+    assert L.zgemu_seektab(at, len(e), lo, ranges, n, out, counts) == 0, "lanes of a wave disagree"
     return [(zgpu.Seek(out[i]).key(), counts[2 * i], counts[2 * i + 1]) for i in range(n)]
 
 
@@ -181,9 +169,7 @@ def test_seektab_under_address_sanitizer_stand_alone(built, expected):
     with open(src, "wb") as f:
         for _, e, rg, _ in expected:
             f.write(struct.pack("<QQ", len(e), len(rg)) + b"".join(struct.pack("<QQ", *r) for r in rg) + e)
-    p = subprocess.run([exe, str(src), str(dst)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0, p.stderr.decode()[-4000:]
-    assert b"seektab_asan ok" in p.stdout and b"AddressSanitizer" not in p.stderr
+    lanesuite.run_stand_alone(exe, [src, dst], b"seektab_asan ok", timeout=900)
     recs = open(dst, "rb").read()
     at = 0
     for name, e, rg, want in expected:

@@ -1,23 +1,14 @@
-"""The lane routine of zg_k_xxh64 (zstd-rs_amd/csrc/zg_xxh64_dev.h), compiled with g++, against the oracle's XXH64; and zgpu_decode_frames'
+"""The lane routine of zg_k_xxh64 (zstd-rs_amd/csrc/zg_xxh64_dev.h), compiled with g++ (tests/emu/zg_lane_xxh64.cpp,
+built by tests/lanesuite.py), against the oracle's XXH64; and zgpu_decode_frames'
 argument check, which needs no GPU."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-HARNESS = r'''
-#include "zg_xxh64_dev.h"
-extern "C" uint64_t lane_xxh64(const uint8_t* p, uint64_t n, uint64_t seed) { return zgx::xxh64(p, n, seed); }
-'''
+import lanesuite
 
 
 def _lane(tmp_path):
-    src, so = tmp_path / "xxh64_lane.cpp", tmp_path / "libxxh64_lane.so"
-    src.write_text(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L, _ = lanesuite.build(tmp_path, "zg_lane_xxh64.cpp", "xxh64_lane")
     L.lane_xxh64.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.lane_xxh64.restype = C.c_uint64
     return L

@@ -1,24 +1,14 @@
-"""The quad routine of zg_k_xxh64q (zstd-rs_amd/csrc/zg_xxh64_dev.h: xxh64q_acc, xxh64q_finish), compiled with g++, against the oracle's XXH64.
+"""The quad routine of zg_k_xxh64q (zstd-rs_amd/csrc/zg_xxh64_dev.h: xxh64q_acc, xxh64q_finish), compiled with g++ (tests/emu/zg_lane_xxh64_quad.cpp,
+built by tests/lanesuite.py), against the oracle's XXH64.
 
 The harness plays one quad: lane l = 0 .. 3 computes its accumulator over the whole stripes (the lanes exchange nothing before the gather, so
 running them one after the other is what four lanes in lockstep compute), the gather is four plain variables, and lane 0's finish does the
 merge, the tail and the avalanche. The length and offset lists are shared with tests/test_gpu_xxh64_quad.py (quad_cases)."""
 import ctypes as C
-import os
 import random
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "zstd-rs_amd", "csrc")
-HARNESS = r'''
-#include "zg_xxh64_dev.h"
-extern "C" uint64_t quad_xxh64(const uint8_t* p, uint64_t n, uint64_t seed) {
-  uint64_t v[4];
-  for (uint32_t l = 0; l < 4; l++) v[l] = zgx::xxh64q_acc(p, n, seed, l);   // the four lanes of the quad
-  return zgx::xxh64q_finish(p, n, seed, v[0], v[1], v[2], v[3]);            // lane 0, after the gather
-}
-extern "C" uint32_t quad_round() { return zgx::kQuadRound; }
-'''
+import lanesuite
+
 DATA_BYTES = (1 << 20) + 64
 
 
@@ -43,10 +33,7 @@ def quad_cases(R):
 
 
 def _quad(tmp_path):
-    src, so = tmp_path / "xxh64_quad.cpp", tmp_path / "libxxh64_quad.so"
-    src.write_text(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L, _ = lanesuite.build(tmp_path, "zg_lane_xxh64_quad.cpp", "xxh64_quad")
     L.quad_xxh64.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.quad_xxh64.restype = C.c_uint64
     L.quad_round.restype = C.c_uint32
