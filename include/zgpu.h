@@ -569,8 +569,8 @@ int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx*, const void* const* devic
  * Diagnostics: zgpu_seek_index_stats — [0] launches of the build, [1] their microseconds (HIP events), [2] bytes downloaded, [3] device bytes
  * held, [4] rows, [5] input bytes that crossed to the host (always 0). zgpu_debug_ranges_stats after an indexed call: [0] - [2], [14], [15]
  * and [18] are 0 (no locate, no prefix pass), [16] is 1 when any range has nonzero length, [13], [5], [6] count groups and their frames once.
- * Out of scope: updating an index in place, entries with unsized frames (use a seek table), host sources, several GPUs, sharing one handle
- * between contexts. */
+ * Entries whose frames declare no size are indexed by measuring them: zgpu_seek_index_measure_device, below.
+ * Out of scope: updating an index in place, host sources, several GPUs, sharing one handle between contexts. */
 typedef struct zgpu_seek_index zgpu_seek_index;        /* belongs to one zgpu_ctx; destroy it before the context */
 enum { ZGPU_INDEX_SEEK_TABLE = 0, ZGPU_INDEX_DECLARED = 1, ZGPU_INDEX_AUTO = 2 };
 #define ZGPU_INDEX_UNSIZED 32u                         /* zgpu_seek_index_info.why: a zstd frame declares no Frame_Content_Size */
@@ -579,8 +579,8 @@ typedef struct {
   uint64_t compressed;   /* C[nrows] */
   uint64_t plaintext;    /* D[nrows] */
   uint32_t status;       /* 0, ZGPU_E_BAD_ARG (pointer check), ZGPU_E_SEEK_TABLE, ZGPU_E_FRAME_INDEX; != 0: nrows = compressed = plaintext = 0 */
-  uint32_t why;          /* ZGPU_SEEKTAB_* | ZGPU_CHAIN_* (the chain broke) | ZGPU_INDEX_UNSIZED */
-  uint32_t kind;         /* ZGPU_INDEX_SEEK_TABLE or ZGPU_INDEX_DECLARED: what this entry was indexed by */
+  uint32_t why;          /* ZGPU_SEEKTAB_* | ZGPU_CHAIN_* (the chain broke) | ZGPU_INDEX_UNSIZED | ZGPU_INDEX_UNMEASURED | ZGPU_INDEX_DICT */
+  uint32_t kind;         /* ZGPU_INDEX_SEEK_TABLE, ZGPU_INDEX_DECLARED or ZGPU_INDEX_MEASURED: what this entry was indexed by */
   uint32_t nrows;
 } zgpu_seek_index_info;
 int zgpu_seek_index_create_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t kind, zgpu_seek_index** out);
@@ -592,6 +592,62 @@ int zgpu_frames_seek_indexed_device(zgpu_ctx*, const zgpu_seek_index*, const zgp
 int zgpu_gather_ranges_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
                                           const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts /* m */,
                                           const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
+
+/* ---- seek index by measuring: entries whose frames declare no size and that carry no seek table ----------------------------------------------
+ * A shard of frames written by a streaming compressor (ZSTD_compressStream with ZSTD_e_end per record, zstd reading a pipe, a stream writer
+ * that flushes a frame per record, files joined with cat) has no Frame_Content_Size and no seek table: ZGPU_INDEX_DECLARED refuses it with
+ * ZGPU_INDEX_UNSIZED, ZGPU_INDEX_SEEK_TABLE with ZGPU_SEEKTAB_NONE, and every range call decodes everything behind the first frame it takes.
+ * zgpu_seek_index_measure_device indexes such entries by MEASURING them on the device, once: a frame's plaintext length is the sum of its
+ * blocks' lengths — a raw or RLE block: Block_Size; a compressed block without sequences: Regenerated_Size of its literals; a compressed
+ * block with sequences: Regenerated_Size + the sum of its match lengths — and those sums need the FSE tables, the sequence bitstream and the
+ * LL and ML extra bits, but no Huffman stream, no byte of LZ77 execution and no output buffer.
+ * The call returns the same kind of handle under the same rules as zgpu_seek_index_create_device: every entry with lens[i] > 0 passes the
+ * pointer check before any launch; one that fails has ZGPU_E_BAD_ARG in its info and the others are unaffected; the return value reports
+ * engine failures only, nothing is left behind on failure (*out = NULL), the streams are drained on return, an entry of length 0 is a valid
+ * index without rows, and no byte of an entry comes back to the host (frame records and skeleton records do).
+ *  - mode ZGPU_MEASURE_ALL: every entry is measured, whatever it declares or carries. ZGPU_MEASURE_UNSIZED: every entry is first indexed as
+ *    ZGPU_INDEX_AUTO indexes it, and only an entry that AUTO refuses with ZGPU_E_FRAME_INDEX / ZGPU_INDEX_UNSIZED is measured; a malformed
+ *    table or a broken chain stays the error it is. Any other mode: ZGPU_E_BAD_ARG.
+ *  - Rows of a measured entry: the frame records of its header chain, exactly as for the declared kind — c_k the frame's bytes; a skippable
+ *    frame, or a seek table at the end, is a row with d_k = 0 — but d_k of a zstd frame is its MEASURED size. A declared Frame_Content_Size
+ *    is not consulted: a frame that lies about it fails later, per frame, in the gather, as it does today. info.kind =
+ *    ZGPU_INDEX_MEASURED, tab = lens[i] (ZGPU_SEEKTAB_PAST_TABLE cannot arise), info.plaintext = D[nrows]; D saturates at 2^64 - 1.
+ *  - Refusals (ZGPU_E_FRAME_INDEX, kind ZGPU_INDEX_MEASURED, nrows = compressed = plaintext = 0), in this order: the chain does not reach
+ *    the entry's end (why = the ZGPU_CHAIN_* reason); more than 2^27 rows (ZGPU_SEEKTAB_TOO_LARGE); a frame names a dictionary id
+ *    (ZGPU_INDEX_DICT); the measuring of a frame ends in a status (ZGPU_INDEX_UNMEASURED): a header the host's parse refuses, an FSE table
+ *    description, the sequence bitstream, a block whose literal lengths add up to more than its literals (NotEnoughLiterals), a block
+ *    that regenerates 2^31 bytes or more (Unsupported). zgpu_last_error names the first such entry, its frame (counted in zstd frames) and
+ *    zgpu_status_name of the status. An entry that fails never disturbs another, in any order.
+ *  - How: the summary pass and the frame records of zgpu_frames_table_device; runs of whole frames then go through the machinery of the
+ *    device-source calls (zg_k_walk's skeleton, the host's one parse, zg_k_gather) in submits cut at frame boundaries at the input budget of
+ *    the decode submits — a frame is never split, one above the budget is a submit of its own, and no plaintext budget applies: nothing is
+ *    produced —, and every submit runs zg_k_reset, the FSE tables, zg_k_seq, zg_k_seqsize (zg_seqsize.h) and zg_k_scan; the sizes come back
+ *    per frame, the host builds the pairs and uploads them in one copy.
+ * WHAT MEASURING DOES NOT SEE: Huffman tree descriptions and Huffman streams; offsets (too far, zero); content checksums. An entry with
+ * such a defect IS indexed, with the sizes its headers, tables and sequences give. The defect surfaces when the frame is decoded, as a status
+ * of the ranges whose group holds that frame. AN INDEX IS A PROMISE ABOUT SIZES, NOT A VERDICT ON THE BYTES.
+ * Using a measured index: zgpu_frames_seek_indexed_device and zgpu_gather_ranges_indexed_device_src, unchanged — one find launch over the
+ * pairs; a group's promise D[glast + 1] - D[gfirst] is held against the decoded total (ZGPU_E_CONTENT_SIZE_MISMATCH on a stale index); a range
+ * of a measured-kind entry under ZGPU_DEVICE_VERIFY_SEEK_TABLE gets ZGPU_E_BAD_ARG, as a declared-kind entry's does.
+ * zgpu_seek_index_export_seek_table writes entry `entry`'s rows, of whatever kind, as ONE seekable-format skippable frame into HOST memory
+ * (it is meant for a file), so that the entry never needs measuring again:
+ *    0x184D2A5E | Frame_Size = 8 * nrows + 9 | nrows x { c_k u32, d_k u32 } | Number_Of_Frames | descriptor 0 (no checksums) | 0x8F92EAB1
+ * 17 + 8 * nrows bytes; the entry's 16 * (nrows + 1) bytes of pairs are downloaded, nothing else. For a declared- or measured-kind entry,
+ * the entry's bytes followed by the exported frame are an entry whose ZGPU_INDEX_SEEK_TABLE index has the same nrows, C and D.
+ * ZGPU_E_BAD_ARG: a null handle or `written`, entry out of range, an entry whose info has a status, host_dst == NULL with cap > 0.
+ * ZGPU_E_TARGET_TOO_SMALL with *written = the size needed: cap too small (host_dst == NULL with cap == 0 asks for the size).
+ * ZGPU_E_SEEK_TABLE: some c_k or d_k exceeds 0xFFFFFFFF — the format cannot say it —, and nothing is written.
+ * Diagnostics: zgpu_seek_index_stats appends [6] measuring submits, [7] their phase-1 microseconds (HIP events), [8] zstd frames measured;
+ * [0] - [2] include the measuring call's lane passes and gathers, [5] stays 0 (records are not input bytes). A caller that asks for 6
+ * gets what it always got.
+ * Out of scope: frames that name a dictionary id, checksums in the exported table, updating an index in place, host sources, several
+ * GPUs, cutting one frame's measuring over submits, ZGPU_INDEX_AUTO falling through to measuring (it would change an existing answer). */
+enum { ZGPU_INDEX_MEASURED = 3 };        /* zgpu_seek_index_info.kind only; not accepted by zgpu_seek_index_create_device */
+#define ZGPU_INDEX_UNMEASURED 33u        /* info.why: a frame of the entry could not be measured (its headers or its sequence stage fail) */
+#define ZGPU_INDEX_DICT 34u              /* info.why: a frame of the entry names a dictionary id (out of scope, above) */
+enum { ZGPU_MEASURE_ALL = 0, ZGPU_MEASURE_UNSIZED = 1 };
+int zgpu_seek_index_measure_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t mode, zgpu_seek_index** out);
+int zgpu_seek_index_export_seek_table(const zgpu_seek_index*, uint32_t entry, uint8_t* host_dst, size_t cap, size_t* written);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

@@ -61,7 +61,8 @@ struct zgpu_ctx {
 // A seek index (include/zgpu.h: zgpu_seek_index): the pairs { C[k], D[k] } of every indexed entry in device memory, and per entry where they
 // lie and what the selection needs besides. No source pointer: offsets only.
 enum { kSeekIdxStatLaunches = 0, kSeekIdxStatKernelUs, kSeekIdxStatBytesDownloaded, kSeekIdxStatDeviceBytes, kSeekIdxStatRows, kSeekIdxStatInputBytesToHost,
-       kSeekIdxStatCount };
+       // zgpu_seek_index_measure_device: measuring submits (Batch::measure), their phase-1 microseconds (HIP events), zstd frames measured
+       kSeekIdxStatMeasureSubmits, kSeekIdxStatMeasureUs, kSeekIdxStatFramesMeasured, kSeekIdxStatCount };
 static_assert(kSeekIdxStatLaunches == zg::kPassLaunches && kSeekIdxStatKernelUs == zg::kPassUs && kSeekIdxStatBytesDownloaded == zg::kPassBytes,
               "the array handed to the passes of the build");
 struct zgpu_seek_index {

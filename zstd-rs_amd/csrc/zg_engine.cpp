@@ -113,6 +113,7 @@ Tuning Tuning::from_env() {
   num("ZGPU_SWEEP_HEAD_LDS", &t.sweep.head_lds, false);
   num("ZGPU_SWEEP_HEAD_NB", &t.sweep.head_nbatch, true);
   { const char* e = getenv("ZGPU_FRAMES_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.frames_submit_bytes = (uint64_t)atoll(e); }
+  { const char* e = getenv("ZGPU_MEASURE_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.measure_submit_bytes = (uint64_t)atoll(e); }
   num("ZGPU_SCATTER_CHUNK", &t.scatter_chunk, true);
   { const char* e = getenv("ZGPU_HASH_DEVICE_MAX"); if (e && atoll(e) >= 0) { t.hash_device_max_set = true; t.hash_device_max = (uint64_t)atoll(e); } }
 #endif
@@ -839,6 +840,40 @@ int Batch::run() {
   if (st2) return st2;
   ZG_HIP(hipGetLastError());
   ran = true;
+  return ZG_OK;
+}
+
+// run()'s phase 1 without the literals chain, with zg_k_seqsize where run() has zg_k_seqpost, and with nothing behind the scan: the sizes
+// of the frames and the statuses the sequence stages find, in frame_out. (zg_k_merge is what folds the Huffman chain's verdicts and the
+// host's sequences-header verdict into the block statuses; the former do not exist here, and the latter is FrameInfo::host_status of the
+// frame, which the caller looks at anyway.) No frame is placed (zg_k_scanf): nothing is produced.
+int Batch::measure(uint64_t* phase1_us) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  hipStream_t s = eng->stream_;
+  ZgBatchDev& d = dev;
+  if (phase1_us) *phase1_us = 0;
+  frame_out.assign(d.nframes, ZgFrameOut{});
+  total_out = 0; ran = false; synced = true;
+  if (wait_upload) { ZG_HIP(hipStreamWaitEvent(s, sc->ev_up, 0)); wait_upload = false; }
+  if (d.nframes == 0 || d.nblocks == 0 || fs) {   // (no block: nothing to launch, as in run(); a continued frame is not measured)
+    ZG_HIP(hipStreamSynchronize(s));
+    return fs ? ZG_BAD_ARG : ZG_OK;
+  }
+  hipEvent_t* ev = sc->ev;
+  d.dst_cap_pre = 0;
+  d.flags &= ~ZG_FLAG_LIT_DIRECT;
+  ZG_HIP(hipEventRecord(ev[0], s));
+  zg_launch_reset(d, s);
+  zg_launch_tables(d, s, 1);
+  zg_launch_seq(d, s, bb.seq_packed);
+  zg_launch_seqsize(d, s);
+  { uint32_t mb = 0; for (const ZgFrame& fr : bb.frames) mb = fr.nblocks > mb ? fr.nblocks : mb; zg_launch_scan_sizes(d, s, mb); }
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev[1], s));
+  ZG_HIP(hipMemcpyAsync(frame_out.data(), d.frame_out, (size_t)d.nframes * sizeof(ZgFrameOut), hipMemcpyDeviceToHost, s));
+  ZG_HIP(hipStreamSynchronize(s));
+  float m = 0;
+  if (phase1_us && hipEventElapsedTime(&m, ev[0], ev[1]) == hipSuccess) *phase1_us = (uint64_t)(m * 1000.0f + 0.5f);
   return ZG_OK;
 }
 

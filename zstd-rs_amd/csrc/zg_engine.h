@@ -108,6 +108,7 @@ struct Tuning {
   int seq_packed = -1;             // ZGPU_SEQ_PACKED: zg_k_seq's table entries — -1 (default): packed (16 bits, three workgroups per CU) when the submit has more
                                    // blocks with sequences than one round holds, else unpacked; 0 / 1: never / always
   ZgSweepTuning sweep;             // ZGPU_SWEEP_MODE / _NB / _GROUP / _HEAD_LDS
+  uint64_t measure_submit_bytes = 0; // ZGPU_MEASURE_SUBMIT_BYTES: input per measuring submit of zgpu_seek_index_measure_device (0: the input budget of the decode submits; tests force several)
   uint64_t frames_submit_bytes = 0;  // ZGPU_FRAMES_SUBMIT_BYTES: plaintext (and input) per submit of zgpu_decode_frames (0: the library's constant; tests force several submits)
   uint32_t scatter_chunk = 0;        // ZGPU_SCATTER_CHUNK: bytes per chunk of zg_k_scatter's plan (0: zgs::kChunkDefault; measurement of the chunk size)
   bool hash_device_max_set = false;  // ZGPU_HASH_DEVICE_MAX: longest frame zgpu_decode_frames hashes on the device (measurement of the threshold)
@@ -155,6 +156,12 @@ class Batch {
   // stages and the scan run first; the host reads the exact output size of every frame, sizes the output and the flatten
   // scratch to it, and then enqueues the LZ77 stages. Returns when the second phase is enqueued.
   int run();
+  // In place of run() + sync(), for a caller that wants the frames' SIZES and nothing else (zgpu_seek_index_measure_device): zg_k_reset, the
+  // FSE tables, zg_k_seq, zg_k_seqsize (zg_seqsize.h) where run() has zg_k_seqpost, zg_k_scan, and frame_out comes back — out_size and
+  // status of every frame, as size_output() reads them. Nothing of the Huffman chain runs, no output and no flatten scratch is reserved, no
+  // LZ77 stage follows: what those stages would find (a Huffman description or stream, an offset, a checksum) is not found. The stream is
+  // drained on return. *phase1_us, if asked for: the kernels' time between two HIP events. A measured batch is not run afterwards.
+  int measure(uint64_t* phase1_us = nullptr);
   // streaming submits: after sync(), fold this run into the frame's carried state (tables, history, produced bytes)
   int commit(FrameState* fs);
   uint32_t carry_mask_in = 0;            // streaming runs: the tables that existed when the run was parsed

@@ -55,8 +55,7 @@ using namespace zgf;
 
 namespace {
 
-// plaintext per submit: bounds the device output (+ 4x its size of flatten scratch) and the pinned staging of one submit
-constexpr uint64_t kFramesSubmitBytes = 512ull << 20;
+// (kFramesSubmitBytes, plaintext and input per submit: zg_frames_int.h)
 // Where a submit's frames are hashed (LABNOTES.md "decode_frames", measured on MI355X): on the device one lane runs XXH64 at ~225 MB/s (a lone
 // 4 MiB frame: 18.6 ms), all lanes together at ~1 TB/s (65,536 x 128 KiB: 8.6 ms); a host core at >= 10 GB/s, and the host copies every byte
 // to the caller anyway, on up to kHostThreads threads. A submit's frames go to the device only when the estimate of the kernel —

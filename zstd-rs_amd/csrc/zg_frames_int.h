@@ -8,6 +8,10 @@
 
 namespace zgf {
 
+// plaintext per submit of the decode calls: bounds the device output (+ 4x its size of flatten scratch) and the pinned staging of one submit;
+// their input is bounded by the same number, and so is the input of a measuring submit (zg_ranges.cpp), which produces no plaintext
+constexpr uint64_t kFramesSubmitBytes = 512ull << 20;
+
 // destinations in device memory of the caller (zgpu_decode_frames_device and every call built on it)
 struct DeviceSink {
   zgpu_device_entry_result* res = nullptr;

@@ -35,9 +35,11 @@ void zg_launch_tables(const ZgBatchDev& d, hipStream_t s, int part);   // part 0
 void zg_launch_huf(const ZgBatchDev& d, hipStream_t s);
 void zg_launch_seq(const ZgBatchDev& d, hipStream_t s, bool packed);   // packed: 16-bit table entries, three workgroups per CU (submits of more blocks than one round holds)
 void zg_launch_seqpost(const ZgBatchDev& d, hipStream_t s);
+void zg_launch_seqsize(const ZgBatchDev& d, hipStream_t s);   // in zg_launch_seqpost's place where a submit is only measured (zg_seqsize.h): the blocks' sums, no records
 void zg_launch_merge(const ZgBatchDev& d, hipStream_t s);
 void zg_launch_litfix(const ZgBatchDev& d, hipStream_t s);   // ZG_FLAG_LIT_DIRECT: literal verdicts found after the scan -> block and frame statuses
 void zg_launch_scan(const ZgBatchDev& d, hipStream_t s, uint32_t max_frame_blocks);   // max_frame_blocks: of the submit's frames (picks the workgroup size)
+void zg_launch_scan_sizes(const ZgBatchDev& d, hipStream_t s, uint32_t max_frame_blocks);   // zg_k_scan without zg_k_scanf: a submit that is only measured places no frame (Batch::measure)
 void zg_launch_lit(const ZgBatchDev& d, hipStream_t s);
 void zg_launch_flat(const ZgBatchDev& d, hipStream_t s, hipStream_t s2, hipEvent_t* ev, int flat4);   // s2, ev[2]: the direct units beside the pointer-mode ones
 void zg_launch_sparse(const ZgBatchDev& d, hipStream_t s);   // the matches of frames marked sparse, in order (after zg_launch_flat)

@@ -7,6 +7,8 @@
 //     zg_k_seq      decoder + mover wave per 16 blocks, four lanes per block
 //                                              the three FSE state chains of a block -> the states of every sequence (8 B)
 //     zg_k_seqpost  one workgroup per block    symbols, extra bits, values, positions, offset history (scans) -> ZgSeq[] (12 B)
+//     zg_k_seqsize  one workgroup per block    in zg_k_seqpost's place where a submit is only MEASURED (Batch::measure): the sums of the literal and
+//                                              match lengths, nothing else (zg_seqsize.h); then zg_k_scan, and no other kernel of this list
 //   literals chain (low-priority stream, beside zg_k_seq)
 //     zg_k_tables   one wave per block         Huffman tree descriptions -> Huffman arena
 //     zg_k_huf      one wave per stream        Huffman literal streams, self-synchronising -> literals arena
@@ -129,6 +131,7 @@ ZX_DEV uint32_t zx_ld32(ZxBuf b, uint32_t off) { return __builtin_amdgcn_raw_buf
 ZX_DEV ZxU2 zx_ld64(ZxBuf b, uint32_t off) { const zg_v2u v = __builtin_amdgcn_raw_buffer_load_b64(b, off, 0, 0); ZxU2 r; r.x = v.x; r.y = v.y; return r; }
 ZX_DEV ZxU3 zx_ld96(ZxBuf b, uint32_t off) { const zg_v3u v = __builtin_amdgcn_raw_buffer_load_b96(b, off, 0, 0); ZxU3 r; r.x = v.x; r.y = v.y; r.z = v.z; return r; }
 ZX_DEV uint32_t zx_ld8(ZxBuf b, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b8(b, off, 0, 0); }
+ZX_DEV ZxU4 zx_ld128(ZxBuf b, uint32_t off) { const zg_v4u v = __builtin_amdgcn_raw_buffer_load_b128(b, off, 0, 0); ZxU4 r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; return r; }   // off: dword-aligned
 ZX_DEV void zx_add_lds(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }   // ds_add_u32
 ZX_DEV void zx_st8(ZxBuf b, uint32_t off, uint32_t v) { __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, b, off, 0, 0); }
 ZX_DEV void zx_st32(ZxBuf b, uint32_t off, uint32_t v) { __builtin_amdgcn_raw_buffer_store_b32(v, b, off, 0, 0); }
@@ -1192,6 +1195,17 @@ __global__ void __launch_bounds__(ZG_SP_T, 4) zg_k_seqpost(ZgBatchDev d) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// zg_k_seqsize: zg_k_seqpost's place in a submit that is only MEASURED (Batch::measure): Σ ll and Σ ml of every block with sequences, from
+// the states zg_k_seq recorded and the LL and ML extra-bit fields — the body is zg_seqsize.h (zx_* primitives: the same source runs under
+// the CPU emulator). One workgroup per block.
+// ------------------------------------------------------------------------------------------------------------
+#include "zg_seqsize.h"
+__global__ void __launch_bounds__(ZG_SZ_T) zg_k_seqsize(ZgBatchDev d) {
+  __shared__ ZgSeqSizeLds s_l;
+  zg_seqsize_block(d, d.seq_blocks[blockIdx.x], s_l);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // zg_k_scan: per frame — output position of every block and the offset history at every block start.
 // The history recurrence (sequence_execution.rs:59-118; never reset between blocks, scratch.rs:22) is a
 // composition of per-block maps on three symbolic slots, so it is scanned like a prefix sum.
@@ -2071,6 +2085,15 @@ void zg_launch_litfix(const ZgBatchDev& d, hipStream_t s) {
 }
 void zg_launch_seqpost(const ZgBatchDev& d, hipStream_t s) {
   if (d.nseq_blocks) hipLaunchKernelGGL(zg_k_seqpost, dim3(d.nseq_blocks), dim3(ZG_SP_T), 0, s, d);
+}
+void zg_launch_seqsize(const ZgBatchDev& d, hipStream_t s) {
+  if (d.nseq_blocks) hipLaunchKernelGGL(zg_k_seqsize, dim3(d.nseq_blocks), dim3(ZG_SZ_T), 0, s, d);
+}
+// zg_k_scan alone, for a submit that is only measured (Batch::measure): no frame is placed, so no zg_k_scanf. The same choice of form as below.
+void zg_launch_scan_sizes(const ZgBatchDev& d, hipStream_t s, uint32_t max_frame_blocks) {
+  if (max_frame_blocks <= 64u) hipLaunchKernelGGL((zg_k_scan<64, 1>), dim3(d.nframes), dim3(64), 0, s, d);
+  else if (max_frame_blocks <= 1024u) hipLaunchKernelGGL((zg_k_scan<1024, 1>), dim3(d.nframes), dim3(1024), 0, s, d);
+  else hipLaunchKernelGGL((zg_k_scan<1024, 8>), dim3(d.nframes), dim3(1024), 0, s, d);
 }
 void zg_launch_scan(const ZgBatchDev& d, hipStream_t s, uint32_t max_frame_blocks) {
   if (max_frame_blocks <= 64u) hipLaunchKernelGGL((zg_k_scan<64, 1>), dim3(d.nframes), dim3(64), 0, s, d);

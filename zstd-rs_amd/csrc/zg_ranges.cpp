@@ -8,9 +8,12 @@
 // every range of it is a clip of the group's span with its own destination. zgpu_gather_ranges_indexed_device_src is the same call behind
 // another selection: a zgpu_seek_index keeps the prefix sums of its entries' rows in device memory — built from their seek tables, or from
 // their header chains where every frame declares its size (zg_seekidx.h) —, indexed_ranges finds every range's rows in them with one launch,
-// and gather_groups is shared.
+// and gather_groups is shared. zgpu_seek_index_measure_device builds the same handle for entries whose frames declare nothing: measure_entries
+// cuts their frame records into runs, runs them through the device-source machinery and Batch::measure (zg_seqsize.h), and the sizes that
+// come back become the pairs; zgpu_seek_index_export_seek_table writes an entry's pairs out as a seek table (zg_seektab.h).
 #include <stddef.h>
 #include <string.h>
+#include <string>
 #include <vector>
 #include "zg_frames_int.h"
 #include "zg_seeksums.h"
@@ -248,6 +251,8 @@ extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void*
 
 // ---- seek index handles (include/zgpu.h: zgpu_seek_index; zg_seekidx.h) -------------------------------------------------------------------------
 static_assert(sizeof(zgpu_seek_index_info) == 40 && ZGPU_INDEX_UNSIZED == zgx::kUnsized && ZGPU_E_FRAME_INDEX == 74, "include/zgpu.h");
+static_assert(ZGPU_INDEX_MEASURED == 3 && ZGPU_INDEX_UNMEASURED == 33u && ZGPU_INDEX_DICT == 34u && ZGPU_MEASURE_ALL == 0 && ZGPU_MEASURE_UNSIZED == 1,
+              "include/zgpu.h");
 namespace {
 // an entry the index refuses: nothing of it is held
 void refuse_index(zgpu_seek_index::Ent& e, uint32_t status, uint32_t why, uint32_t kind) {
@@ -256,10 +261,127 @@ void refuse_index(zgpu_seek_index::Ent& e, uint32_t status, uint32_t why, uint32
   e.pre = 0; e.tab = 0;
 }
 
+// ---- measuring (zgpu_seek_index_measure_device) ------------------------------------------------------------------------------------------------
+// What measuring found of one entry: its nrows + 1 pairs, or the first zstd frame of it whose measuring ended in a status.
+struct Measured { std::vector<zgm::Pair> pairs; uint32_t status = 0, frame = 0; };
+constexpr int kNoMeasure = -1;   // build_index: zgpu_seek_index_create_device
+
+// The entries ent[0 .. ne) — whole chains without a dictionary frame, sum[q] their summaries — measured: the frame records of the table call
+// give every row's bytes (zg_k_index<true>); runs of whole frames become the entries of the device-source machinery (zg_k_walk's skeleton,
+// the host's one parse, zg_k_gather), cut at frame boundaries into submits of at most S input bytes — a frame is never split, one above S
+// is a submit of its own —, and each submit is measured (Batch::measure) where a decode call runs it. d_k = the frame's out_size as
+// zg_k_scan left it. No byte of an entry comes back: records and skeletons do.
+int measure_entries(zgpu_ctx* c, const std::vector<Engine::DevEntry>& ent, const std::vector<zgi::Entry>& sum, std::vector<Measured>* out, uint64_t* stats) {
+  zg::Engine* eng = c->eng;
+  const uint32_t ne = (uint32_t)ent.size();
+  out->assign(ne, Measured{});
+  if (!ne) return ZGPU_OK;
+  const Tuning& tn = eng->tuning();
+  const uint64_t S = tn.measure_submit_bytes ? tn.measure_submit_bytes : tn.frames_submit_bytes ? tn.frames_submit_bytes : kFramesSubmitBytes;
+  const char* const changed = "zgpu_seek_index_measure_device: a source changed while it was measured";
+  std::vector<uint64_t> first((size_t)ne + 1);
+  const uint64_t total = zgi::frame_ranges(sum.data(), ne, first.data());
+  std::vector<zgi::FrameRec> recs(total);
+  std::vector<zgi::Entry> again(ne);
+  int st;
+  if (total && (st = eng->index_pass(ent.data(), ne, first.data(), sum.data(), again.data(), recs.data(), stats))) return st;
+  // the runs: consecutive frame records of one entry, up to S bytes, each with a zstd frame in it
+  struct Run { uint32_t q; uint64_t k0, k1; };
+  std::vector<Run> runs;
+  std::vector<Engine::DevEntry> rdev;
+  for (uint32_t q = 0; q < ne; q++) {
+    if (total && !zgi::same_entry(again[q], sum[q])) { eng->last_error = changed; return ZGPU_E_INTERNAL; }
+    uint64_t at = 0, k0 = first[q];
+    bool any = false;
+    auto close = [&](uint64_t k1) {
+      if (any) { runs.push_back(Run{q, k0, k1}); rdev.push_back(Engine::DevEntry{ent[q].src + recs[k0].begin, recs[k1 - 1].end - recs[k0].begin}); }
+      k0 = k1; any = false;
+    };
+    for (uint64_t k = first[q]; k < first[q + 1]; k++) {
+      const zgi::FrameRec& r = recs[k];
+      if (r.begin != at || r.end < r.begin || r.end > ent[q].len) { eng->last_error = changed; return ZGPU_E_INTERNAL; }
+      at = r.end;
+      if (k > k0 && r.end - recs[k0].begin > S) close(k);
+      any = any || !(r.flags & zgi::kSkippable);
+    }
+    close(first[q + 1]);
+    if (at != ent[q].len) { eng->last_error = changed; return ZGPU_E_INTERNAL; }
+  }
+  // every run's skeleton: two launches for the whole call
+  Engine::Skeleton sk;
+  if ((st = eng->walk_entries(rdev.data(), (uint32_t)rdev.size(), &sk, stats))) return st;
+  // d_k of every record (0: a skippable frame), submit by submit
+  std::vector<uint64_t> dk(total, 0);
+  std::vector<uint32_t> zframes(ne, 0);   // zstd frames of the entry seen so far
+  for (size_t r0 = 0; r0 < runs.size();) {
+    std::vector<uint32_t> idx;
+    std::vector<uint64_t> off;
+    uint64_t in_bytes = 0;
+    size_t r1 = r0;
+    for (; r1 < runs.size() && (r1 == r0 || in_bytes + rdev[r1].len <= S); r1++) { idx.push_back((uint32_t)r1); off.push_back(in_bytes); in_bytes += rdev[r1].len; }
+    Batch* b = nullptr;
+    std::vector<int> walk;
+    std::vector<uint32_t> ff;
+    if ((st = eng->prepare_entries_device(rdev.data(), sk, idx.data(), off.data(), (uint32_t)idx.size(), (size_t)in_bytes, &b, &walk, &ff, nullptr))) return st;
+    struct Del { Batch* b; ~Del() { delete b; } } del{b};
+    stats[kSeekIdxStatLaunches] += b->gather_launched ? 1u : 0u; stats[kSeekIdxStatKernelUs] += b->gather_us;
+    uint64_t us = 0;
+    if ((st = b->measure(&us))) return st;
+    stats[kSeekIdxStatMeasureSubmits]++; stats[kSeekIdxStatMeasureUs] += us;
+    if (b->frame_out.size() != b->info.size()) return ZGPU_E_INTERNAL;
+    for (size_t j = 0; j < idx.size(); j++) {
+      const Run& run = runs[idx[j]];
+      Measured& m = (*out)[run.q];
+      uint32_t f = ff[j];
+      for (uint64_t k = run.k0; k < run.k1; k++) {
+        const zgi::FrameRec& r = recs[k];
+        if (r.flags & zgi::kSkippable) continue;
+        const uint32_t zf = zframes[run.q]++;
+        uint32_t fst;
+        if (f < ff[j + 1]) {
+          const FrameInfo& fi = b->info[f];
+          fst = fi.host_status ? (uint32_t)fi.host_status : b->frame_out[f].status;
+          if (!fi.host_status && (fi.src_begin != off[j] + (r.begin - recs[run.k0].begin) || fi.src_end - fi.src_begin != r.end - r.begin)) {
+            eng->last_error = changed;
+            return ZGPU_E_INTERNAL;
+          }
+          dk[k] = b->frame_out[f].out_size;
+          f++;
+        } else {   // the host's walk of the run ended in front of this frame: at its header
+          if (!walk[j]) { eng->last_error = changed; return ZGPU_E_INTERNAL; }
+          fst = (uint32_t)walk[j];
+        }
+        if (fst && !m.status) { m.status = fst; m.frame = zf; }
+        if (!fst) stats[kSeekIdxStatFramesMeasured]++;
+        if (fst) break;   // (what lies behind a frame the walk stopped in is not in the submit)
+      }
+    }
+    r0 = r1;
+  }
+  for (uint32_t q = 0; q < ne; q++) {
+    Measured& m = (*out)[q];
+    if (m.status) continue;
+    const uint64_t nrows = first[q + 1] - first[q];
+    m.pairs.resize((size_t)nrows + 1);
+    uint64_t d = 0;
+    for (uint64_t k = 0; k < nrows; k++) {
+      m.pairs[k] = zgm::Pair{recs[first[q] + k].begin, d};
+      const uint64_t add = dk[first[q] + k];
+      d = add > UINT64_MAX - d ? UINT64_MAX : d + add;
+    }
+    m.pairs[nrows] = zgm::Pair{ent[q].len, d};
+  }
+  return ZGPU_OK;
+}
+
 // The build. The table pass works in a scratch of its own (its chunk totals lie behind the prefixes); the handle's buffer is sized exactly —
 // 16 * (nrows + 1) bytes per indexed entry —, gets the table entries' pairs by one device copy each, and the declared entries' pairs straight
-// from zg_k_seekidx_rows.
-int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, uint32_t kind) {
+// from zg_k_seekidx_rows. measure (zgpu_seek_index_measure_device): ZGPU_MEASURE_ALL — no table and no declared size is looked at, every entry
+// is measured —, or ZGPU_MEASURE_UNSIZED with kind = ZGPU_INDEX_AUTO — an entry is measured where AUTO answers ZGPU_INDEX_UNSIZED. The
+// measured entries' pairs are built on the host (measure_entries), lie behind the others' and reach the handle in one copy.
+int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, uint32_t kind, int measure) {
+  const bool all = measure == (int)ZGPU_MEASURE_ALL, unsized = measure == (int)ZGPU_MEASURE_UNSIZED;
+  const std::string who = measure == kNoMeasure ? "zgpu_seek_index_create_device" : "zgpu_seek_index_measure_device";   // (the call last_error names)
   zg::Engine* eng = c->eng;
   if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   std::vector<Engine::DevEntry> dev;
@@ -269,8 +391,8 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
   std::vector<uint8_t> by_chain(n, 0);   // entries the chain is asked about
   for (uint32_t i = 0; i < n; i++) {
     x->ents[i].info.len = lens[i];
-    if (refused[i]) refuse_index(x->ents[i], ZGPU_E_BAD_ARG, 0, kind == ZGPU_INDEX_DECLARED ? ZGPU_INDEX_DECLARED : ZGPU_INDEX_SEEK_TABLE);
-    else by_chain[i] = kind == ZGPU_INDEX_DECLARED;
+    if (refused[i]) refuse_index(x->ents[i], ZGPU_E_BAD_ARG, 0, all ? ZGPU_INDEX_MEASURED : kind == ZGPU_INDEX_DECLARED ? ZGPU_INDEX_DECLARED : ZGPU_INDEX_SEEK_TABLE);
+    else by_chain[i] = kind == ZGPU_INDEX_DECLARED || all;
   }
   uint64_t* stats = x->stats;
   // the tables
@@ -279,7 +401,7 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
   std::vector<uint64_t> tpre;
   std::vector<uint32_t> tab_of;   // the entries the table pass was asked about
   struct Free { zg::DevBuf& b; ~Free() { b.release(); } } free_scratch{scratch};
-  if (kind != ZGPU_INDEX_DECLARED) {
+  if (kind != ZGPU_INDEX_DECLARED && !all) {
     std::vector<Engine::DevEntry> live;
     for (uint32_t i = 0; i < n; i++) if (!refused[i]) { tab_of.push_back(i); live.push_back(dev[i]); }
     loc.resize(live.size());
@@ -303,21 +425,47 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
   std::vector<zgi::Entry> sum(chain.size());
   int st = eng->index_pass(chain.data(), (uint32_t)chain.size(), nullptr, nullptr, sum.data(), nullptr, stats);
   if (st) return st;
+  std::vector<uint32_t> meas_of;   // the entries that are measured, and (chain / sum index) where their summaries lie
+  std::vector<size_t> meas_q;
   for (size_t q = 0; q < ch_of.size(); q++) {
     zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
     const uint32_t why = zgx::refusal(sum[q]);
-    if (sum[q].chain_end > lens[ch_of[q]]) { eng->last_error = "zgpu_seek_index_create_device: a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
+    if (sum[q].chain_end > lens[ch_of[q]]) { eng->last_error = who + ": a summary that leaves its entry"; return ZGPU_E_INTERNAL; }   // (never)
+    if (all || (unsized && why == zgx::kUnsized)) {   // (kUnsized: the chain itself is whole)
+      const uint32_t mw = sum[q].why ? sum[q].why : sum[q].nrec > zgt::kMaxFrames ? (uint32_t)ZGPU_SEEKTAB_TOO_LARGE : (sum[q].flags & zgi::kAnyDict) ? ZGPU_INDEX_DICT : 0u;
+      if (mw) refuse_index(e, ZGPU_E_FRAME_INDEX, mw, ZGPU_INDEX_MEASURED);
+      else { e.info.kind = ZGPU_INDEX_MEASURED; e.info.nrows = sum[q].nrec; e.tab = lens[ch_of[q]]; meas_of.push_back(ch_of[q]); meas_q.push_back(q); }
+      continue;
+    }
     if (why) refuse_index(e, ZGPU_E_FRAME_INDEX, why, ZGPU_INDEX_DECLARED);
     else if (sum[q].nrec > zgt::kMaxFrames) refuse_index(e, ZGPU_E_FRAME_INDEX, ZGPU_SEEKTAB_TOO_LARGE, ZGPU_INDEX_DECLARED);
     else { e.info.kind = ZGPU_INDEX_DECLARED; e.info.nrows = sum[q].nrec; e.tab = lens[ch_of[q]]; }
   }
-  // the handle's pairs: every indexed entry's range
-  uint64_t pairs = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    zgpu_seek_index::Ent& e = x->ents[i];
-    if (e.info.status) continue;
-    e.pre = pairs;
-    pairs += (uint64_t)e.info.nrows + 1;
+  // the measured entries: an entry with a frame whose measuring ended in a status is refused, and the first of them is named
+  std::vector<Measured> meas;
+  {
+    std::vector<Engine::DevEntry> ment(meas_of.size());
+    std::vector<zgi::Entry> msum(meas_of.size());
+    for (size_t t = 0; t < meas_of.size(); t++) { ment[t] = chain[meas_q[t]]; msum[t] = sum[meas_q[t]]; }
+    if ((st = measure_entries(c, ment, msum, &meas, stats))) return st;
+    bool named = false;
+    for (size_t t = 0; t < meas_of.size(); t++) {
+      if (!meas[t].status) continue;
+      refuse_index(x->ents[meas_of[t]], ZGPU_E_FRAME_INDEX, ZGPU_INDEX_UNMEASURED, ZGPU_INDEX_MEASURED);
+      if (!named) eng->last_error = "zgpu_seek_index_measure_device: entry " + std::to_string(meas_of[t]) + ", frame " + std::to_string(meas[t].frame) + ": " + zgpu_status_name((int)meas[t].status);
+      named = true;
+    }
+  }
+  // the handle's pairs: every indexed entry's range, the measured entries' behind the others'
+  uint64_t pairs = 0, meas_pre = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass) meas_pre = pairs;
+    for (uint32_t i = 0; i < n; i++) {
+      zgpu_seek_index::Ent& e = x->ents[i];
+      if (e.info.status || (e.info.kind == ZGPU_INDEX_MEASURED) != (pass == 1)) continue;
+      e.pre = pairs;
+      pairs += (uint64_t)e.info.nrows + 1;
+    }
   }
   if (pairs > SIZE_MAX / sizeof(zgm::Pair)) return ZGPU_E_NOMEM;
   if (pairs && (st = x->pairs.reserve((size_t)pairs * sizeof(zgm::Pair)))) return st;
@@ -334,6 +482,16 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
         hipMemcpyAsync(&closing[q], from + e.info.nrows, sizeof(zgm::Pair), hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
     stats[kSeekIdxStatBytesDownloaded] += sizeof(zgm::Pair);
   }
+  // measured kind: the pairs the host built, in one copy
+  std::vector<zgm::Pair> mpairs;
+  for (size_t t = 0; t < meas_of.size(); t++) {
+    zgpu_seek_index::Ent& e = x->ents[meas_of[t]];
+    if (e.info.status) continue;
+    if (meas[t].pairs.size() != (size_t)e.info.nrows + 1 || e.pre != meas_pre + mpairs.size()) return ZGPU_E_INTERNAL;   // (never)
+    mpairs.insert(mpairs.end(), meas[t].pairs.begin(), meas[t].pairs.end());
+    e.info.compressed = meas[t].pairs.back().c; e.info.plaintext = meas[t].pairs.back().d;
+  }
+  if (!mpairs.empty() && hipMemcpyAsync(dp + meas_pre, mpairs.data(), mpairs.size() * sizeof(zgm::Pair), hipMemcpyHostToDevice, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   for (size_t q = 0; q < tab_of.size(); q++) {
     zgpu_seek_index::Ent& e = x->ents[tab_of[q]];
@@ -345,7 +503,7 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
   std::vector<uint32_t> lane_of;
   for (size_t q = 0; q < ch_of.size(); q++) {
     const zgpu_seek_index::Ent& e = x->ents[ch_of[q]];
-    if (e.info.status) continue;
+    if (e.info.status || e.info.kind != ZGPU_INDEX_DECLARED) continue;
     lane_of.push_back(ch_of[q]);
     lanes.push_back(zgx::Lane{chain[q].src, chain[q].len, e.pre, e.info.nrows});
   }
@@ -355,7 +513,7 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
     zgpu_seek_index::Ent& e = x->ents[lane_of[q]];
     // (a source that changed between the passes — the caller's promise broken —, or pairs that do not add up to the entry)
     if (rows[q].why || rows[q].nrows != e.info.nrows || rows[q].c != e.info.len) {
-      eng->last_error = "zgpu_seek_index_create_device: a source changed while it was indexed";
+      eng->last_error = who + ": a source changed while it was indexed";
       return ZGPU_E_INTERNAL;
     }
     e.info.compressed = rows[q].c; e.info.plaintext = rows[q].d;
@@ -407,9 +565,35 @@ extern "C" int zgpu_seek_index_create_device(zgpu_ctx* c, const void* const* dev
   if (!c || !out || kind > ZGPU_INDEX_AUTO || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
   zgpu_seek_index* x = new zgpu_seek_index();
   x->ctx = c;
-  const int st = drain(c, build_index(c, x, device_srcs, lens, n, kind));
+  const int st = drain(c, build_index(c, x, device_srcs, lens, n, kind, kNoMeasure));
   if (st) { zgpu_seek_index_destroy(x); return st; }   // (nothing is left behind)
   *out = x;
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_measure_device(zgpu_ctx* c, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t mode,
+                                              zgpu_seek_index** out) {
+  if (out) *out = nullptr;
+  if (!c || !out || mode > ZGPU_MEASURE_UNSIZED || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
+  zgpu_seek_index* x = new zgpu_seek_index();
+  x->ctx = c;
+  const int st = drain(c, build_index(c, x, device_srcs, lens, n, ZGPU_INDEX_AUTO, (int)mode));
+  if (st) { zgpu_seek_index_destroy(x); return st; }   // (nothing is left behind)
+  *out = x;
+  return ZGPU_OK;
+}
+// The entry's 16 * (nrows + 1) bytes of pairs come down, and zg_seektab.h's serialiser writes them out: one definition of the layout.
+extern "C" int zgpu_seek_index_export_seek_table(const zgpu_seek_index* x, uint32_t entry, uint8_t* host_dst, size_t cap, size_t* written) {
+  if (written) *written = 0;
+  if (!x || !written || entry >= x->ents.size() || x->ents[entry].info.status || (!host_dst && cap)) return ZGPU_E_BAD_ARG;
+  const zgpu_seek_index::Ent& e = x->ents[entry];
+  const uint64_t need = zgt::seek_table_bytes(e.info.nrows);
+  if (need > cap) { *written = (size_t)need; return ZGPU_E_TARGET_TOO_SMALL; }
+  if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  std::vector<zgm::Pair> pairs((size_t)e.info.nrows + 1);
+  if (hipMemcpy(pairs.data(), x->pairs.as<zgm::Pair>() + e.pre, pairs.size() * sizeof(zgm::Pair), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  static_assert(sizeof(zgm::Pair) == 16, "pairs as words");
+  if (zgt::write_seek_table((const uint64_t*)pairs.data(), e.info.nrows, host_dst)) return ZGPU_E_SEEK_TABLE;
+  *written = (size_t)need;
   return ZGPU_OK;
 }
 extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {

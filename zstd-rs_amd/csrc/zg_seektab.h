@@ -62,6 +62,30 @@ constexpr uint32_t kSkipMagic = 0x184D2A5Eu, kSeekMagic = 0x8F92EAB1u, kMaxFrame
 struct alignas(16) Lane { uint64_t src, len, begin, rlen; };   // src: the entry's address, len its bytes
 static_assert(sizeof(Lane) == 32, "seek table lane");
 
+// The other direction (zgpu_seek_index_export_seek_table): nrows rows WRITTEN as one seek table frame without checksums, from their
+// exclusive prefix sums cd[2 * k] = C[k], cd[2 * k + 1] = D[k], k = 0 .. nrows (a zgm::Pair array seen as words) —
+//   kSkipMagic | Frame_Size = 8 * nrows + 9 | nrows x { c_k u32, d_k u32 } | Number_Of_Frames | descriptor 0 | kSeekMagic
+// seek_table_bytes(nrows) = 17 + 8 * nrows bytes, all little-endian, byte by byte: dst may have any alignment. A row the format cannot say
+// (c_k or d_k above 0xFFFFFFFF; sums that decrease) is kSeekTable, and then NOTHING is written: the rows are looked at before the first
+// store. Plain C++: g++ compiles it for tests/test_seektab_write_cpu.py.
+static inline uint64_t seek_table_bytes(uint64_t nrows) { return kFraming + 8u * nrows; }
+static inline uint32_t write_seek_table(const uint64_t* cd, uint32_t nrows, uint8_t* dst) {
+  if (nrows > kMaxFrames) return kSeekTable;
+  for (uint32_t k = 0; k < nrows; k++) {
+    if (cd[2 * k + 2] < cd[2 * k] || cd[2 * k + 3] < cd[2 * k + 1]) return kSeekTable;
+    if (cd[2 * k + 2] - cd[2 * k] > 0xFFFFFFFFull || cd[2 * k + 3] - cd[2 * k + 1] > 0xFFFFFFFFull) return kSeekTable;
+  }
+  auto le32 = [](uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); };
+  le32(dst, kSkipMagic);
+  le32(dst + 4, 8u * nrows + 9u);
+  uint8_t* p = dst + 8;
+  for (uint32_t k = 0; k < nrows; k++, p += 8) { le32(p, (uint32_t)(cd[2 * k + 2] - cd[2 * k])); le32(p + 4, (uint32_t)(cd[2 * k + 3] - cd[2 * k + 1])); }
+  le32(p, nrows);
+  p[4] = 0;
+  le32(p + 5, kSeekMagic);
+  return 0;
+}
+
 }  // namespace zgt
 #endif  // ZG_SEEKTAB_TYPES
 

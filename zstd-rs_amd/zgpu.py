@@ -33,6 +33,10 @@ E_FRAME_INDEX = 74             # a SeekIndex entry, and the ranges that name it:
 INDEX_SEEK_TABLE, INDEX_DECLARED, INDEX_AUTO = 0, 1, 2   # zgpu_seek_index_create_device's kind
 INDEX_UNSIZED = 32             # SeekIndexInfo.why: a zstd frame declares no Frame_Content_Size
 _INDEX_KINDS = {"seek_table": INDEX_SEEK_TABLE, "declared": INDEX_DECLARED, "auto": INDEX_AUTO}
+INDEX_MEASURED = 3             # SeekIndexInfo.kind only (Context.seek_index_measured): the entry's frames were measured on the device
+INDEX_UNMEASURED = 33          # SeekIndexInfo.why: a frame of the entry could not be measured (its headers or its sequence stage fail)
+INDEX_DICT = 34                # SeekIndexInfo.why: a frame of the entry names a dictionary id
+MEASURE_ALL, MEASURE_UNSIZED = 0, 1   # zgpu_seek_index_measure_device's mode
 E_UNSUPPORTED = 80
 E_HIP = 92
 E_BAD_ARG = 93
@@ -55,7 +59,8 @@ _STATS = {
                               "plaintext_decoded", "bytes_written",
                               "compare_launches", "compare_us", "compare_bytes_downloaded", "frames_compared", "entries_failed_table")),
     "SeekIndex.stats": ("zgpu_seek_index_stats", C.c_uint64,
-                        ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host")),
+                        ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host",
+                         "measure_submits", "measure_us", "frames_measured")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
                        ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
     "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
@@ -201,8 +206,8 @@ class SeekIndexInfoC(C.Structure):
 
 class SeekIndexInfo:
     """One entry of a SeekIndex (zgpu_seek_index_info): len, the entry's bytes when it was indexed; compressed = C[nrows], plaintext = D[nrows];
-    status 0, E_BAD_ARG, E_SEEK_TABLE or E_FRAME_INDEX with why (SEEKTAB_*, a CHAIN_* reason, INDEX_UNSIZED); kind INDEX_SEEK_TABLE or
-    INDEX_DECLARED: what the entry was indexed by; nrows, its rows (frames, skippable ones included)."""
+    status 0, E_BAD_ARG, E_SEEK_TABLE or E_FRAME_INDEX with why (SEEKTAB_*, a CHAIN_* reason, INDEX_UNSIZED, INDEX_UNMEASURED, INDEX_DICT); kind
+    INDEX_SEEK_TABLE, INDEX_DECLARED or INDEX_MEASURED: what the entry was indexed by; nrows, its rows (frames, skippable ones included)."""
     __slots__ = FIELDS = ("len", "compressed", "plaintext", "status", "why", "kind", "nrows")
 
     def __init__(self, c):
@@ -321,6 +326,7 @@ NO_READ_AHEAD = 1
 EXPORTS = [
     "zgpu_seek_index_create_device", "zgpu_seek_index_destroy", "zgpu_seek_index_entries", "zgpu_seek_index_info_of", "zgpu_seek_index_stats",
     "zgpu_frames_seek_indexed_device", "zgpu_gather_ranges_indexed_device_src",
+    "zgpu_seek_index_measure_device", "zgpu_seek_index_export_seek_table",
     "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
@@ -411,6 +417,8 @@ def _declare(L):
     L.zgpu_gather_ranges_seek_table_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
                                                            P(RangeResultC)]
     L.zgpu_seek_index_create_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, C.c_uint32, P(vp)]
+    L.zgpu_seek_index_measure_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, C.c_uint32, P(vp)]
+    L.zgpu_seek_index_export_seek_table.argtypes = [vp, C.c_uint32, C.c_char_p, sz, P(sz)]
     L.zgpu_seek_index_destroy.argtypes = [vp]
     L.zgpu_seek_index_destroy.restype = None
     L.zgpu_seek_index_entries.argtypes = [vp]
@@ -656,6 +664,10 @@ class Context:
         """the one error path of the calls below: a status other than 0 raises with the context's last error (or the fixed text `what`)"""
         if st:
             raise ZgpuError(st, self.L.zgpu_last_error(self.h).decode() if what is None else what)
+
+    def last_error(self):
+        """zgpu_last_error: the text the engine left last (seek_index_measured names there the first frame it could not measure)"""
+        return self.L.zgpu_last_error(self.h).decode()
 
     def _stats(self, getter, slots=None):
         return _read_stats(self.L, "Context." + getter, self.h, slots=slots)
@@ -934,6 +946,26 @@ class Context:
         self._tensor_check(tensors, "seek_index_tensors")
         return self.seek_index([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors], kind)
 
+    def seek_index_measured(self, src_ptrs, lens, only_unsized=False):
+        """zgpu_seek_index_measure_device: a SeekIndex over entries in DEVICE memory whose frames declare no size and that carry no seek table
+        (what a streaming compressor writes) — every frame's plaintext length is MEASURED on the device, once: block sizes, literal sizes and
+        the sums of match lengths, without a Huffman stream, an LZ77 byte or an output buffer. only_unsized: every entry is indexed as
+        seek_index(kind="auto") indexes it, and only those it refuses as INDEX_UNSIZED are measured; else every entry is measured. An entry
+        that cannot be measured has E_FRAME_INDEX in index.infos[i] (why: a CHAIN_* reason, SEEKTAB_TOO_LARGE, INDEX_DICT, INDEX_UNMEASURED —
+        last_error names the frame). Measuring does not see Huffman, offset or checksum defects: those surface when the frame is decoded.
+        The index serves frames_seek_indexed_device and gather_ranges_indexed_device_src like any other; export_seek_table writes it out."""
+        n = len(src_ptrs)
+        _one_per("seek_index_measured", n, lens)
+        h = C.c_void_p()
+        self._check(self.L.zgpu_seek_index_measure_device(self.h, _ptr_array(src_ptrs), _size_array(lens), n,
+                                                          MEASURE_UNSIZED if only_unsized else MEASURE_ALL, C.byref(h)))
+        return SeekIndex(self, h)
+
+    def seek_index_measured_tensors(self, tensors, only_unsized=False):
+        """seek_index_measured on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding shard i."""
+        self._tensor_check(tensors, "seek_index_measured_tensors")
+        return self.seek_index_measured([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors], only_unsized)
+
     def _index_handle(self, index, what):
         if not isinstance(index, SeekIndex) or not index.h:
             raise ValueError("%s: an open SeekIndex" % what)
@@ -1119,8 +1151,23 @@ class SeekIndex:
 
     def stats(self):
         """the build (zgpu_seek_index_stats): launches, kernel_us (HIP events), bytes_downloaded, device_bytes held, rows, input_bytes_to_host
-        (always 0). Gather calls on the index do not change it: the index is never rebuilt."""
+        (always 0); of a measured index also measure_submits, measure_us (their phase-1 time, HIP events) and frames_measured. Gather calls on
+        the index do not change it: the index is never rebuilt."""
         return _read_stats(self.L, "SeekIndex.stats", self.h)
+
+    def export_seek_table(self, entry):
+        """zgpu_seek_index_export_seek_table: entry `entry`'s rows as one seek table frame of zstd's seekable format (no checksums), as bytes —
+        what seek_table_frame(csizes, dsizes) builds for those rows. Appended behind the entry's bytes it makes the entry seekable: a file
+        written that way never needs measuring again. A size query, then the call; the entry's pairs are all that is downloaded."""
+        if not self.h:
+            raise ValueError("export_seek_table: an open SeekIndex")
+        need = C.c_size_t(0)
+        st = self.L.zgpu_seek_index_export_seek_table(self.h, entry, None, 0, C.byref(need))
+        if st != E_TARGET_TOO_SMALL:
+            self.ctx._check(st if st else E_BAD_ARG, "zgpu_seek_index_export_seek_table")
+        buf = C.create_string_buffer(need.value)
+        self.ctx._check(self.L.zgpu_seek_index_export_seek_table(self.h, entry, buf, need.value, C.byref(need)), "zgpu_seek_index_export_seek_table")
+        return buf.raw[:need.value]
 
     def close(self):
         if getattr(self, "h", None):
