@@ -561,7 +561,8 @@ int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx*, const void* const* devic
  * held against the group's total, declared sizes per frame; fate sharing within a group; ZGPU_E_TARGET_TOO_SMALL per range; the rank order
  * of verdicts; dictionary frames; ZGPU_DEVICE_VERIFY; no byte of a failed range's destination written, none at or behind dst + written; the
  * streams synchronised on return. ZGPU_DEVICE_VERIFY_SEEK_TABLE works for ranges of table-kind entries (the rows are read from the entry at
- * verify time); a range of a declared-kind entry under that flag gets ZGPU_E_BAD_ARG in its result: there is no table to enforce.
+ * verify time); a range of a declared-kind entry under that flag gets ZGPU_E_BAD_ARG in its result: there is no table to enforce
+ * (unless the handle holds the entry's sums: seek index checksums, below).
  * RANDOM ACCESS here means: a call costs one find launch plus the decode of the frames its ranges touch; nothing in front of them is read.
  * THE INDEX IS THE CALLER'S PROMISE that the entry's bytes have not changed since it was built. A stale index is a status, never a fault:
  * every record is held against lens[i] on the host (src_lo <= src_hi <= lens[i]) before anything is gathered, the bytes then go through the
@@ -628,7 +629,8 @@ int zgpu_gather_ranges_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, con
  * of the ranges whose group holds that frame. AN INDEX IS A PROMISE ABOUT SIZES, NOT A VERDICT ON THE BYTES.
  * Using a measured index: zgpu_frames_seek_indexed_device and zgpu_gather_ranges_indexed_device_src, unchanged — one find launch over the
  * pairs; a group's promise D[glast + 1] - D[gfirst] is held against the decoded total (ZGPU_E_CONTENT_SIZE_MISMATCH on a stale index); a range
- * of a measured-kind entry under ZGPU_DEVICE_VERIFY_SEEK_TABLE gets ZGPU_E_BAD_ARG, as a declared-kind entry's does.
+ * of a measured-kind entry under ZGPU_DEVICE_VERIFY_SEEK_TABLE gets ZGPU_E_BAD_ARG, as a declared-kind entry's does — until the handle holds the
+ * entry's sums (zgpu_seek_index_hash_device, below, which also sees what measuring does not).
  * zgpu_seek_index_export_seek_table writes entry `entry`'s rows, of whatever kind, as ONE seekable-format skippable frame into HOST memory
  * (it is meant for a file), so that the entry never needs measuring again:
  *    0x184D2A5E | Frame_Size = 8 * nrows + 9 | nrows x { c_k u32, d_k u32 } | Number_Of_Frames | descriptor 0 (no checksums) | 0x8F92EAB1
@@ -640,7 +642,7 @@ int zgpu_gather_ranges_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, con
  * Diagnostics: zgpu_seek_index_stats appends [6] measuring submits, [7] their phase-1 microseconds (HIP events), [8] zstd frames measured;
  * [0] - [2] include the measuring call's lane passes and gathers, [5] stays 0 (records are not input bytes). A caller that asks for 6
  * gets what it always got.
- * Out of scope: frames that name a dictionary id, checksums in the exported table, updating an index in place, host sources, several
+ * Out of scope: frames that name a dictionary id, updating an index in place, host sources, several
  * GPUs, cutting one frame's measuring over submits, ZGPU_INDEX_AUTO falling through to measuring (it would change an existing answer). */
 enum { ZGPU_INDEX_MEASURED = 3 };        /* zgpu_seek_index_info.kind only; not accepted by zgpu_seek_index_create_device */
 #define ZGPU_INDEX_UNMEASURED 33u        /* info.why: a frame of the entry could not be measured (its headers or its sequence stage fail) */
@@ -648,6 +650,69 @@ enum { ZGPU_INDEX_MEASURED = 3 };        /* zgpu_seek_index_info.kind only; not 
 enum { ZGPU_MEASURE_ALL = 0, ZGPU_MEASURE_UNSIZED = 1 };
 int zgpu_seek_index_measure_device(zgpu_ctx*, const void* const* device_srcs, const size_t* lens, uint32_t n, uint32_t mode, zgpu_seek_index** out);
 int zgpu_seek_index_export_seek_table(const zgpu_seek_index*, uint32_t entry, uint8_t* host_dst, size_t cap, size_t* written);
+
+/* ---- seek index checksums: hash a shard once, enforce on every gather ---------------------------------------------------------------------------
+ * A handle may hold, beside its pairs, ONE uint32_t PER ROW in device memory: the low 32 bits of XXH64 (seed 0) of that row's plaintext; a
+ * skippable row holds 0 and is never looked at. The array — 4 bytes per row of every indexed entry — is allocated when the first entry of the
+ * handle gets sums; a handle that never gets any holds what it always held. Every entry has a state: 0 none, 1 hashed
+ * (zgpu_seek_index_hash_device), 2 set by the caller (zgpu_seek_index_set_sums). zgpu_seek_index_info is unchanged; the state is read with
+ * zgpu_seek_index_sums_of.
+ * zgpu_seek_index_hash_device decodes every zstd frame of every chosen entry ONCE, hashes its plaintext on the device and keeps the sums in
+ * the handle. No plaintext is delivered: there is no destination. THIS PASS SEES WHAT MEASURING DOES NOT SEE — Huffman tree descriptions and
+ * Huffman streams, offsets, content checksums: every frame goes through the whole decode, and a frame that carries a Content_Checksum is
+ * held against it. An entry that passes is known good, not merely measured.
+ *  - n must be the handle's entry count and the handle this context's (else ZGPU_E_BAD_ARG). which_or_null[i] == 0 leaves entry i untouched;
+ *    NULL chooses every entry. An entry the index refused is skipped: its sums record carries the index's status. A chosen entry must pass
+ *    the pointer check of the device-source calls and have lens[i] == info.len, else its record is ZGPU_E_BAD_ARG; the others are unaffected.
+ *  - Runs. The entry's pairs come down (16 bytes a row) and its rows are cut into runs of consecutive rows: a run closes in front of a zstd
+ *    row (d_k > 0) when it already holds one and its plaintext, with that row, would exceed run_bytes (0: 64 MiB); skippable rows join the
+ *    run in progress; a single frame above the limit is a run of its own. Each run is one selection [C[k0], C[k1]) of the machinery of the
+ *    gather calls, decoded under the promise D[k1] - D[k0] — a stale index is ZGPU_E_CONTENT_SIZE_MISMATCH — with every decoded zstd frame
+ *    hashed on the device, whatever its length; a frame whose own Content_Checksum disagrees fails its run with ZGPU_E_CHECKSUM_MISMATCH.
+ *    Dictionary frames and entries that go alone are served as in the gather calls. A frame is mapped to its row by the rule of
+ *    ZGPU_DEVICE_VERIFY_SEEK_TABLE: it begins at C[k] - C[k0] and is C[k + 1] - C[k] bytes long; a decoded zstd frame that coincides with
+ *    no row is ZGPU_E_CONTENT_SIZE_MISMATCH. The sums reach the handle in one copy per stretch of chosen entries (NULL: one copy).
+ *  - ALL OR NOTHING PER ENTRY: if any run of an entry ends in a status the entry keeps NO sums — earlier ones are dropped, state 0 —, its
+ *    record carries that status and [row_lo, row_hi), the rows of the first failing run in row order, and zgpu_last_error names the entry,
+ *    the run and zgpu_status_name. A failing entry does not disturb another. The return value reports engine failures only; on such a
+ *    failure no entry's state has changed. The streams are drained on return. Hashing an entry again replaces its sums.
+ * zgpu_seek_index_set_sums uploads nrows sums the caller kept (its own metadata, a checksummed table): the caller's promise, as an anchor is.
+ * zgpu_seek_index_read_sums downloads an entry's sums (*nrows = info.nrows; cap_rows below that: ZGPU_E_TARGET_TOO_SMALL, nothing written).
+ * ZGPU_E_BAD_ARG: a null argument, entry out of range, an entry the index refused, nrows != info.nrows, reading an entry without sums.
+ * Enforcing: under ZGPU_DEVICE_VERIFY_SEEK_TABLE, zgpu_gather_ranges_indexed_device_src applies one rule — AN ENTRY WHOSE HANDLE HOLDS SUMS IS
+ * VOUCHED FOR BY THE HANDLE; ANY OTHER ENTRY IS TREATED AS BEFORE (a table-kind entry reads its table; a declared- or measured-kind entry
+ * gets ZGPU_E_BAD_ARG). The rule of the flag carries over word for word with sums[k] in the Checksum's place, R_k = C[k] - C[gfirst] and
+ * c_k = C[k + 1] - C[k] from the pairs: every decoded zstd frame of such a group is hashed (hash_max_bytes == 0: no limit), the comparison
+ * runs on the device (zg_k_idxsums, zg_idxsums.h: one wave per group, one launch per submit behind the hash kernel, no byte of the entry
+ * read, 32 bytes per group back; a submit that holds groups of both routes launches both compare kernels), the verdict
+ * ZGPU_E_SEEK_CHECKSUM_MISMATCH ranks last, falls on every range of the group, and no byte of a failed range's destination is written.
+ * checksums / checksum_mismatches / checksums_unverified of a failed range and zgpu_debug_ranges_stats [8] - [12] mean what they mean for a
+ * table. Groups decoded alone get the same verdict on the host from rows [gfirst, glast] of pairs and sums. With the flag a changed byte
+ * inside a frame — which changes no size, and which a gather without the flag delivers with status 0: the index is a promise about sizes —
+ * fails the group.
+ * zgpu_seek_index_export_seek_table_ex: flags == 0 is zgpu_seek_index_export_seek_table; ZGPU_EXPORT_CHECKSUMS writes
+ *    0x184D2A5E | Frame_Size = 12 * nrows + 9 | nrows x { c_k u32, d_k u32, sums[k] u32 } | Number_Of_Frames | descriptor 0x80 | 0x8F92EAB1
+ * 17 + 12 * nrows bytes, for an entry that has sums (else, or with unknown flag bits, ZGPU_E_BAD_ARG); the size query,
+ * ZGPU_E_TARGET_TOO_SMALL and ZGPU_E_SEEK_TABLE as above. The entry's bytes followed by that frame are an entry whose ZGPU_INDEX_SEEK_TABLE
+ * index has the same rows and which passes ZGPU_DEVICE_VERIFY_SEEK_TABLE by its table.
+ * Diagnostics: zgpu_seek_index_stats appends [9] decode submits of the hash passes, [10] their hash kernels' microseconds (HIP events), [11]
+ * zstd frames hashed, [12] bytes of sums held (0 until an entry gets sums; [3] is unchanged), [13] runs cut. A caller that asks for 9 gets
+ * what it always got.
+ * Out of scope: sums for single rows of an entry, updating in place, host sources, several GPUs. */
+typedef struct {
+  uint32_t status;       /* of the last zgpu_seek_index_hash_device that chose the entry (0; the index's status; ZGPU_E_BAD_ARG; the failing run's) */
+  uint32_t state;        /* 0 none, 1 hashed, 2 set by the caller */
+  uint32_t row_lo, row_hi;   /* status != 0 from a run: its rows */
+  uint64_t frames;       /* zstd frames hashed (state 1) */
+  uint64_t bytes;        /* plaintext bytes hashed (state 1) */
+} zgpu_seek_index_sums;
+#define ZGPU_EXPORT_CHECKSUMS 1u
+int zgpu_seek_index_hash_device(zgpu_ctx*, zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                const uint8_t* which_or_null, uint64_t run_bytes);
+int zgpu_seek_index_set_sums(zgpu_seek_index*, uint32_t entry, const uint32_t* sums, uint32_t nrows);
+int zgpu_seek_index_read_sums(const zgpu_seek_index*, uint32_t entry, uint32_t* dst, uint32_t cap_rows, uint32_t* nrows);
+int zgpu_seek_index_sums_of(const zgpu_seek_index*, uint32_t i, zgpu_seek_index_sums* out);
+int zgpu_seek_index_export_seek_table_ex(const zgpu_seek_index*, uint32_t entry, uint32_t flags, uint8_t* host_dst, size_t cap, size_t* written);
 
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of

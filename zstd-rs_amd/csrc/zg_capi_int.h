@@ -63,14 +63,24 @@ struct zgpu_ctx {
 enum { kSeekIdxStatLaunches = 0, kSeekIdxStatKernelUs, kSeekIdxStatBytesDownloaded, kSeekIdxStatDeviceBytes, kSeekIdxStatRows, kSeekIdxStatInputBytesToHost,
        // zgpu_seek_index_measure_device: measuring submits (Batch::measure), their phase-1 microseconds (HIP events), zstd frames measured
        kSeekIdxStatMeasureSubmits, kSeekIdxStatMeasureUs, kSeekIdxStatFramesMeasured, kSeekIdxStatCount };
+// what zgpu_seek_index_stats appends behind the slots above (out[9] ...): zgpu_seek_index_hash_device, summed over its calls — decode submits, the
+// hash kernels' microseconds (HIP events), zstd frames hashed —; the bytes of sums the handle holds now (0 until an entry gets sums); the
+// runs the passes cut
+enum { kSumStatHashSubmits = 0, kSumStatHashUs, kSumStatFramesHashed, kSumStatSumsBytes, kSumStatHashRuns, kSumStatCount };
 static_assert(kSeekIdxStatLaunches == zg::kPassLaunches && kSeekIdxStatKernelUs == zg::kPassUs && kSeekIdxStatBytesDownloaded == zg::kPassBytes,
               "the array handed to the passes of the build");
 struct zgpu_seek_index {
   zgpu_ctx* ctx = nullptr;
   zg::DevBuf pairs;                      // 16 * (nrows + 1) bytes per indexed entry, back to back
-  struct Ent { zgpu_seek_index_info info; uint64_t pre, tab; };   // pre: the index of the entry's pair 0; tab: where its table frame begins (declared kind: len)
+  uint64_t npairs = 0;                   // pairs of all indexed entries
+  // pre: the index of the entry's pair 0; tab: where its table frame begins (declared kind: len); spre: the index of its sum 0; sums: what
+  // zgpu_seek_index_sums_of answers (state 0: the handle vouches for nothing of it)
+  struct Ent { zgpu_seek_index_info info; uint64_t pre, tab, spre; zgpu_seek_index_sums sums; };
   std::vector<Ent> ents;
+  zg::DevBuf sums;                       // 4 bytes per row of every indexed entry, in the pairs' order; allocated when the first entry gets sums
+  uint64_t nsums = 0;                    // rows of all indexed entries
   uint64_t stats[kSeekIdxStatCount] = {};
+  uint64_t sums_stats[kSumStatCount] = {};
 };
 
 namespace zg { class StreamCore; }

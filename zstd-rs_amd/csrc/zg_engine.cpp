@@ -179,6 +179,8 @@ Batch::~Batch() {
   for (hipEvent_t e : ev_hash_) if (e) (void)hipEventDestroy(e);
   if (d_seeksums_.p && eng) { (void)hipSetDevice(eng->device_); d_seeksums_.release(); }
   for (hipEvent_t e : ev_seeksums_) if (e) (void)hipEventDestroy(e);
+  if (d_idxsums_.p && eng) { (void)hipSetDevice(eng->device_); d_idxsums_.release(); }
+  for (hipEvent_t e : ev_idxsums_) if (e) (void)hipEventDestroy(e);
   for (DevBuf& x : d_fill_) if (x.p && eng) { (void)hipSetDevice(eng->device_); x.release(); }
   for (hipEvent_t e : ev_fill_) if (e) (void)hipEventDestroy(e);
   if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
@@ -1362,6 +1364,50 @@ int Batch::seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
   *bytes = (uint64_t)seeksums_n_ * sizeof(zgv::Sums);
   ZG_HIP(hipMemcpy(out, (uint8_t*)d_seeksums_.p + seeksums_out_, (size_t)*bytes, hipMemcpyDeviceToHost));
   seeksums_n_ = 0;
+  return ZG_OK;
+}
+int Batch::idxsums_launch(const zgh::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, const void* pairs, uint64_t npairs,
+                          const uint32_t* sums, uint64_t nsums) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  idxsums_n_ = 0;
+  if (!n) return ZG_OK;
+  if (!synced || !pairs || (!sums && nsums)) return ZG_BAD_ARG;
+  for (uint32_t i = 0; i < n; i++) {   // a wave reads pairs [first, first + taken] and sums [first, first + taken) of its entry, its own slice, the digests it names (zg_idxsums.h)
+    const zgh::Lane& l = lanes[i];
+    if (l.frame_lo > nframes || l.frame_n > nframes - l.frame_lo) return ZG_INTERNAL;
+    if (l.pair0 > npairs || (uint64_t)l.nrows + 1 > npairs - l.pair0 || l.sum0 > nsums || l.nrows > nsums - l.sum0) return ZG_INTERNAL;
+  }
+  for (uint32_t q = 0; q < nframes; q++)
+    if (frames[q].slot != zgv::kNotHashed && frames[q].slot >= hash_n_) return ZG_INTERNAL;
+  const size_t lb = (size_t)n * sizeof(zgh::Lane), fb = (size_t)nframes * sizeof(zgv::Frame), ob = (size_t)n * sizeof(zgv::Sums);
+  int st = d_idxsums_.reserve(lb + fb + ob);
+  if (st) return st;
+  for (hipEvent_t& e : ev_idxsums_) if (!e) ZG_HIP(hipEventCreate(&e));
+  hipStream_t up = eng->stream2_, s = eng->stream_;   // (as seeksums_launch: the tables on the idle second stream, the kernel behind the hash kernel)
+  ZG_HIP(hipMemcpyAsync(d_idxsums_.p, lanes, lb, hipMemcpyHostToDevice, up));
+  if (fb) ZG_HIP(hipMemcpyAsync((uint8_t*)d_idxsums_.p + lb, frames, fb, hipMemcpyHostToDevice, up));
+  ZG_HIP(hipStreamSynchronize(up));   // (the tables are pageable)
+  const uint64_t* dig = hash_n_ ? (const uint64_t*)((uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange)) : nullptr;
+  ZG_HIP(hipEventRecord(ev_idxsums_[0], s));
+  zg_launch_idxsums(d_idxsums_.as<zgh::Lane>(), n, pairs, sums, (const zgv::Frame*)((uint8_t*)d_idxsums_.p + lb), dig, hash_n_,
+                    (zgv::Sums*)((uint8_t*)d_idxsums_.p + lb + fb), s);
+  ZG_HIP(hipGetLastError());
+  ZG_HIP(hipEventRecord(ev_idxsums_[1], s));
+  idxsums_n_ = n;
+  idxsums_out_ = lb + fb;
+  return ZG_OK;
+}
+int Batch::idxsums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
+  *kernel_us = 0; *bytes = 0;
+  if (!idxsums_n_) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  ZG_HIP(hipStreamSynchronize(eng->stream_));
+  float ms = 0;
+  ZG_HIP(hipEventElapsedTime(&ms, ev_idxsums_[0], ev_idxsums_[1]));
+  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  *bytes = (uint64_t)idxsums_n_ * sizeof(zgv::Sums);
+  ZG_HIP(hipMemcpy(out, (uint8_t*)d_idxsums_.p + idxsums_out_, (size_t)*bytes, hipMemcpyDeviceToHost));
+  idxsums_n_ = 0;
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

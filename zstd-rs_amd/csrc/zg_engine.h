@@ -199,6 +199,12 @@ class Batch {
   // waits and writes record i of lanes[i]; *kernel_us = the kernel's time between two HIP events, *bytes = what came back
   int seeksums_launch(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes);
   int seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
+  // the same position for zg_k_idxsums (zg_idxsums.h): the rows come from a seek index handle's arrays — pairs[0 .. npairs) of 16 bytes,
+  // sums[0 .. nsums), device memory the handle owns — and no byte of an entry is read. A lane whose rows leave those arrays, a slice or a slot
+  // that leaves its array is refused (ZGPU_E_INTERNAL) before anything is launched. A submit may launch both compare kernels
+  int idxsums_launch(const zgh::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, const void* pairs, uint64_t npairs,
+                     const uint32_t* sums, uint64_t nsums);
+  int idxsums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -231,6 +237,10 @@ class Batch {
   hipEvent_t ev_seeksums_[2] = {nullptr, nullptr};
   uint32_t seeksums_n_ = 0;
   size_t seeksums_out_ = 0;              //   where the records begin
+  DevBuf d_idxsums_;                     // idxsums_launch: the same three
+  hipEvent_t ev_idxsums_[2] = {nullptr, nullptr};
+  uint32_t idxsums_n_ = 0;
+  size_t idxsums_out_ = 0;
   std::vector<zgd::DictImage> frame_dicts_;   // set_frame_dicts
   DevBuf d_fill_[2];                          // dictfill_launch: the segments, then the chunk table (0: tables, 1: contents)
   hipEvent_t ev_fill_[4] = {nullptr, nullptr, nullptr, nullptr};

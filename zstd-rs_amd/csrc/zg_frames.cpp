@@ -48,6 +48,7 @@
 #include "zg_frames_int.h"
 #include "zg_scatter.h"
 #include "zg_seeksums.h"
+#include "zg_idxsums.h"
 #include "zg_xxh64_dev.h"
 
 using namespace zg;
@@ -67,7 +68,8 @@ constexpr unsigned kHostThreads = 16;
 // ZGPU_DEVICE_VERIFY_SEEK_TABLE hashes the few mid-sized frames a range takes and waits for them: up to this many frames a submit of such a call
 // is hashed by zg_k_xxh64q (four lanes per frame). From tools/dev/hash_ranges.py on an MI355X (LABNOTES.md "xxh64q"): the quad kernel is 5.1 x
 // (8 x 128 KiB) to 10.3 x (4096 x 128 KiB) the one-lane kernel on ranges of this kind; 4096 is the largest count of mid-sized ranges measured.
-// No other call hashes differently: ZG_XXH64Q_MAX_RANGES (zg_kernels.h) stays 0.
+// zgpu_seek_index_hash_device (DeviceSink::hash_every) hashes whole frames and waits for them in the same way and takes the same rule. No other
+// call hashes differently: ZG_XXH64Q_MAX_RANGES (zg_kernels.h) stays 0.
 constexpr uint32_t kTableQuadMaxRanges = 4096;
 
 unsigned host_threads() {
@@ -178,7 +180,7 @@ struct Call {
       cl.written = cl.small ? 0 : w;
       if (!cl.small) { sum += w; any = true; }
     }
-    *too_small = !any;
+    *too_small = !any && ranges->first[i] != ranges->first[i + 1];   // (an empty span — zgpu_seek_index_hash_device — wants no byte: never too small)
     return sum;
   }
   zgpu_entry_result& result(uint32_t i) const { return sink ? sink->res[i].r : res[i]; }
@@ -294,7 +296,8 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[kDictStatFramesShared] += b->bb.frames[f].dict_len ? 1u : 0u;
     r.written = fits;
     r.nframes = ff[j + 1] - ff[j];
-    const bool table_all = k.sink && k.sink->table_all && k.sink->table(i);   // (the seek table's checksums: every frame, with or without a Content_Checksum)
+    // (the seek table's checksums, a handle's sums, the hash pass: every frame, with or without a Content_Checksum)
+    const bool table_all = k.sink && ((k.sink->table_all && k.sink->compared(i)) || k.sink->hash_every);
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (fo[f].out_size <= k.hash_max() || (k.sink && k.sink->hash_all && b->info[f].has_checksum) || table_all) u.cand.push_back(f);   // (candidates)
       const uint64_t e = fo[f].out_base + fo[f].out_size;
@@ -321,6 +324,7 @@ bool table_verdict(zgpu_device_entry_result& d, const zgv::Sums& s, uint32_t nfr
   range_stats[kRangeStatEntriesFailedTable]++;
   return true;
 }
+const char* const kHandleChanged = "zgpu_gather_ranges_indexed_device_src: rows or digests that leave the arrays of the checksum compare";
 const char* const kTableChanged = "zgpu_decode_ranges_seek_table_device_src: a seek table changed between the seek and the checksum compare";
 
 // What both sinks do about hashing: the frames of u.cand, as the sink left that list, are hashed by the device — launch() enqueues the kernel
@@ -397,7 +401,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   if (sink.no_hash) u.cand.clear();
   SubmitHash h;
   int st;
-  if ((st = h.launch(u, sink.table_flag ? kTableQuadMaxRanges : 0u))) return st;
+  if ((st = h.launch(u, sink.table_flag || sink.hash_every ? kTableQuadMaxRanges : 0u))) return st;   // (the hash pass waits for whole frames as well)
   uint64_t bytes = 0;
   auto scatter = [&]() -> int {   // the frames of every entry that stands at status 0, in one launch
     std::vector<zgs::Seg> segs;
@@ -441,28 +445,41 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     return b->scatter_launch(segs.data(), (uint32_t)segs.size(), k.c->eng->tuning().scatter_chunk);
   };
   // ZGPU_DEVICE_VERIFY_SEEK_TABLE: one zg_k_seeksums launch for the submit's entries that stand at status 0, behind the hash kernel on its stream
-  std::vector<uint32_t> tv;   // their j
+  // The entries whose handle holds sums go to zg_k_idxsums (zg_idxsums.h) in the same position: a submit that holds both kinds launches both
+  std::vector<uint32_t> tv, hv;   // their j: by the table, by the handle
   if (sink.table_flag) {
     std::vector<zgv::Lane> lanes;
-    std::vector<zgv::Frame> list;
+    std::vector<zgh::Lane> hlanes;
+    std::vector<zgv::Frame> list, hlist;
     std::vector<uint32_t> slot(fo.size(), zgv::kNotHashed);
     for (size_t q = 0; q < u.cand.size(); q++) slot[u.cand[q]] = (uint32_t)q;
     for (uint32_t j = 0; j < n; j++) {
       const zgpu_entry_result& r = dres[idx[j]].r;
-      if (r.status || r.nframes == 0 || !sink.table(idx[j])) continue;
-      const DeviceSink::TableEntry& e = sink.table_verify[idx[j]];
-      const uint32_t lo = (uint32_t)list.size();
+      if (r.status || r.nframes == 0 || !sink.compared(idx[j])) continue;
+      const bool by_handle = sink.by_handle(idx[j]);
+      std::vector<zgv::Frame>& to = by_handle ? hlist : list;
+      const uint32_t lo = (uint32_t)to.size();
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
         const FrameInfo& fi = b->info[f];
         if (fi.src_begin < u.off[j] || fi.src_end < fi.src_begin) return ZGPU_E_INTERNAL;   // (never)
         if (fi.src_end - fi.src_begin > 0xFFFFFFFFull) continue;   // (no row can hold its length: it coincides with none)
-        list.push_back(zgv::Frame{fi.src_begin - u.off[j], (uint32_t)(fi.src_end - fi.src_begin), slot[f]});
+        to.push_back(zgv::Frame{fi.src_begin - u.off[j], (uint32_t)(fi.src_end - fi.src_begin), slot[f]});
       }
-      lanes.push_back(zgv::Lane{e.src, e.len, e.first, e.taken, lo, (uint32_t)list.size() - lo});
-      tv.push_back(j);
+      if (by_handle) {
+        const DeviceSink::HandleEntry& e = sink.handle_verify[idx[j]];
+        hlanes.push_back(zgh::Lane{e.pair0, e.sum0, e.nrows, e.first, e.taken, lo, (uint32_t)to.size() - lo, {0, 0, 0}});
+        hv.push_back(j);
+      } else {
+        const DeviceSink::TableEntry& e = sink.table_verify[idx[j]];
+        lanes.push_back(zgv::Lane{e.src, e.len, e.first, e.taken, lo, (uint32_t)to.size() - lo});
+        tv.push_back(j);
+      }
     }
-    if (list.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
+    if (list.size() > 0xFFFFFFFFull || hlist.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
     if ((st = b->seeksums_launch(lanes.data(), (uint32_t)lanes.size(), list.data(), (uint32_t)list.size()))) return st;
+    if (!hlanes.empty() && (st = b->idxsums_launch(hlanes.data(), (uint32_t)hlanes.size(), hlist.data(), (uint32_t)hlist.size(), sink.handle->pairs,
+                                                   sink.handle->npairs, sink.handle->sums, sink.handle->nsums)))
+      return st;
   }
   const bool gated = sink.verify || sink.table_flag;   // the scatter waits for the verdicts
   if (!gated && (st = scatter())) return st;
@@ -475,6 +492,14 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     if ((st = b->seeksums_wait(sums.data(), &us, &back))) return st;
     uint64_t* rs = k.ranges->stats;
     rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
+  }
+  if (!hv.empty()) {   // (the same slots count both compare kernels)
+    uint64_t us = 0, back = 0;
+    sums.resize(tv.size() + hv.size());
+    if ((st = b->idxsums_wait(sums.data() + tv.size(), &us, &back))) return st;
+    uint64_t* rs = k.ranges->stats;
+    rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
+    tv.insert(tv.end(), hv.begin(), hv.end());   // (the verdicts below: one list, the table's records first)
   }
   auto count_frame = [&](uint32_t f) { sink.stats[h.on_dev[f] ? kDevStatFramesHashed : kDevStatFramesNotHashed]++; };
   if (sink.verify) {
@@ -498,7 +523,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   // the table's verdict ranks last: only what still stands is looked at
   for (size_t t = 0; t < tv.size(); t++) {
     const uint32_t j = tv[t];
-    if (sums[t].why) { k.c->eng->last_error = kTableChanged; return ZGPU_E_INTERNAL; }
+    if (sums[t].why) { k.c->eng->last_error = sink.by_handle(idx[j]) ? kHandleChanged : kTableChanged; return ZGPU_E_INTERNAL; }
     if (dres[idx[j]].r.status) continue;
     if (table_verdict(dres[idx[j]], sums[t], ff[j + 1] - ff[j], k.ranges->stats))
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
@@ -512,6 +537,11 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     zgpu_device_entry_result& d = dres[idx[j]];
     zgpu_entry_result& r = d.r;
     if (r.status || r.nframes == 0) continue;
+    if (sink.collect)
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+        if (!h.on_dev[f] || b->info[f].src_begin < u.off[j]) return ZGPU_E_INTERNAL;   // (never: hash_every)
+        (*sink.collect)[idx[j]].push_back(DeviceSink::Digest{b->info[f].src_begin - u.off[j], b->info[f].src_end - b->info[f].src_begin, h.digest[f]});
+      }
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       const FrameInfo& fi = b->info[f];
       const uint32_t calc = (uint32_t)h.digest[f];
@@ -601,7 +631,7 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   bool summed = false;
   uint32_t size_lies = 0;
   std::vector<ZgFrameSum> frames;   // (ZGPU_DEVICE_VERIFY_SEEK_TABLE) where every decoded frame lies in the selection, and its digest
-  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies, sink.table(i) ? &frames : nullptr);
+  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies, sink.compared(i) || sink.collect ? &frames : nullptr);
   zgpu_device_entry_result& d = sink.res[i];
   d.checksums_unverified = 0;
   d.first_hashed = 0;
@@ -659,6 +689,40 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
     if (rec.why) { k.c->eng->last_error = kTableChanged; free(tmp); return ZGPU_E_INTERNAL; }
     const uint32_t nframes = d.r.nframes;
     if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
+  }
+  // the same flag by the handle (zg_idxsums.h: sums_pairs): C of rows [first, first + taken] and their sums come down from the handle's arrays
+  if (ok && !d.r.status && d.r.nframes && sink.by_handle(i)) {
+    const DeviceSink::HandleEntry& e = sink.handle_verify[i];
+    const DeviceSink::Handle& hd = *sink.handle;
+    zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
+    if (summed) {
+      if (e.pair0 > hd.npairs || (uint64_t)e.nrows + 1 > hd.npairs - e.pair0 || e.sum0 > hd.nsums || e.nrows > hd.nsums - e.sum0 || (uint64_t)e.first + e.taken > e.nrows)
+        rec.why = zgv::kRows;
+      else {
+        std::vector<uint64_t> pairs, cs;
+        std::vector<uint32_t> rs;
+        try { pairs.resize(2 * ((size_t)e.taken + 1)); cs.resize((size_t)e.taken + 1); rs.resize(e.taken); } catch (...) { free(tmp); return ZGPU_E_NOMEM; }
+        if (hipMemcpy(pairs.data(), (const uint8_t*)hd.pairs + 16 * (e.pair0 + e.first), pairs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(rs.data(), hd.sums + e.sum0 + e.first, rs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
+        for (size_t q = 0; q < cs.size(); q++) cs[q] = pairs[2 * q];
+        std::vector<zgv::Frame> list;
+        std::vector<uint64_t> dig;
+        for (const ZgFrameSum& f : frames) {
+          if (f.end - f.begin > 0xFFFFFFFFull) continue;
+          const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
+          list.push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig.size() : zgv::kNotHashed});
+          if (hashed) dig.push_back(f.calc);
+        }
+        rec = zgh::sums_pairs(cs.data(), rs.data(), e.nrows, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
+      }
+    }
+    if (rec.why) { k.c->eng->last_error = kHandleChanged; free(tmp); return ZGPU_E_INTERNAL; }
+    const uint32_t nframes = d.r.nframes;
+    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
+  }
+  if (sink.collect && ok && !d.r.status) {
+    if (!summed) { k.c->eng->last_error = "zgpu_seek_index_hash_device: an entry decoded alone that could not be hashed frame by frame"; free(tmp); return ZGPU_E_INTERNAL; }   // (never seen)
+    for (const ZgFrameSum& f : frames) (*sink.collect)[i].push_back(DeviceSink::Digest{f.begin, f.end - f.begin, f.calc});
   }
   // ranges: only the clipped bytes are uploaded, every clip of the span that has room to its own destination
   if (clip && ok && !d.r.status) {
@@ -854,6 +918,8 @@ int zgf::decode_selections(zgpu_ctx* c, DeviceSink& sink, const void* const* dev
   Ranges rg{clip, first, std::vector<uint64_t>(n), promise, c->ranges_stats};
   sink.res = dres;
   if (sink.table_flag) sink.table_verify.resize(n);
+  if (sink.table_flag && sink.handle) sink.handle_verify.assign(n, DeviceSink::HandleEntry{0, 0, 0, 0, 0});
+  if (sink.collect) sink.collect->assign(n, std::vector<DeviceSink::Digest>());
   for (uint32_t i = 0; i < n; i++) {
     const Selection& s = sel[i];
     srcs[i] = (const uint8_t*)device_srcs[s.entry] + s.lo;
@@ -862,6 +928,11 @@ int zgf::decode_selections(zgpu_ctx* c, DeviceSink& sink, const void* const* dev
     src.refused[i] = s.refused;
     rg.declared[i] = s.declared;
     if (sink.table_flag) sink.table_verify[i] = DeviceSink::TableEntry{(uint64_t)(uintptr_t)device_srcs[s.entry], (uint64_t)lens[s.entry], s.first_row, s.rows};
+    if (sink.table_flag && sink.handle && sink.handle->on[s.entry]) {   // the handle vouches for this entry: not its table, should it have one
+      sink.handle_verify[i] = sink.handle->ent[s.entry];
+      sink.handle_verify[i].first = s.first_row; sink.handle_verify[i].taken = s.rows;
+      sink.table_verify[i].taken = 0;
+    }
   }
   Call k(c, srcs.data(), sub.data(), no_dsts.data(), no_caps.data());
   k.sink = &sink;

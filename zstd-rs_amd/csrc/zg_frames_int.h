@@ -25,7 +25,23 @@ struct DeviceSink {
   std::vector<TableEntry> table_verify;
   bool table_flag = false, table_all = false;
   bool table(uint32_t i) const { return !table_verify.empty() && table_verify[i].taken != 0; }
-  uint64_t* stats = nullptr;      // zgpu_ctx::frames_device_stats (kDevStat*)
+  // The same flag on an entry whose seek index handle holds sums (zg_idxsums.h): the handle vouches, not a table. handle: set by the indexed
+  // gather call before decode_selections — the handle's two arrays and, per WHOLE entry, where its rows lie in them (on: the handle holds its
+  // sums); handle_verify: per sub-entry, filled by decode_selections — a sub-entry goes one route or the other (handle_verify[i].taken != 0
+  // leaves table_verify[i].taken == 0)
+  struct HandleEntry { uint64_t pair0, sum0; uint32_t nrows, first, taken; };
+  struct Handle { const void* pairs = nullptr; uint64_t npairs = 0; const uint32_t* sums = nullptr; uint64_t nsums = 0; std::vector<HandleEntry> ent; std::vector<uint8_t> on; };
+  const Handle* handle = nullptr;
+  std::vector<HandleEntry> handle_verify;
+  bool by_handle(uint32_t i) const { return !handle_verify.empty() && handle_verify[i].taken != 0; }
+  bool compared(uint32_t i) const { return table(i) || by_handle(i); }   // the flag looks at this sub-entry, by either route
+  // zgpu_seek_index_hash_device: every decoded zstd frame is hashed, with or without a Content_Checksum, whatever its length; and the collector —
+  // per sub-entry that stands at status 0 behind every verdict, its decoded zstd frames in source order: where the frame begins in the
+  // selection, its compressed length, its digest (of an entry decoded alone the low 32 bits only: the host's hash keeps no more)
+  bool hash_every = false;
+  struct Digest { uint64_t begin, clen, digest; };
+  std::vector<std::vector<Digest>>* collect = nullptr;
+  uint64_t* stats = nullptr;     // zgpu_ctx::frames_device_stats (kDevStat*)
   uint64_t alone_written = 0;     // bytes the entries decoded alone brought to their destinations
 };
 // The device sink of a call, from its options. ZGPU_DEVICE_NO_HASH with ZGPU_DEVICE_VERIFY (hash nothing, verify everything) is refused: *st.

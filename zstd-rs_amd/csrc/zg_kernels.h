@@ -10,6 +10,7 @@
 #include "zg_seek.h"
 #include "zg_seektab.h"
 #include "zg_seeksums.h"
+#include "zg_idxsums.h"
 #include "zg_seekmany.h"
 #include "zg_seekidx.h"
 
@@ -85,6 +86,10 @@ void zg_launch_seektab(const zgt::Lane* lanes, uint32_t n, zgk::Seek* out, hipSt
 // zg_k_seeksums (zg_seeksums.h): one wave per entry compares the Checksum fields of the entry's seek table with the digests the hash kernel wrote
 // (digests[0 .. ndig), device memory) for the entry's slice of frames; one 64-thread workgroup per entry, out[i] = entry i's 32-byte record
 void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, const uint64_t* digests, uint32_t ndig, zgv::Sums* out, hipStream_t s);
+// zg_k_idxsums (zg_idxsums.h): one wave per group compares the sums a seek index handle holds (pairs, sums: the handle's arrays in device memory)
+// with the same digests for the group's slice of frames; one 64-thread workgroup per group, out[i] = group i's 32-byte record
+void zg_launch_idxsums(const zgh::Lane* lanes, uint32_t n, const void* pairs, const uint32_t* sums, const zgv::Frame* frames, const uint64_t* digests,
+                       uint32_t ndig, zgv::Sums* out, hipStream_t s);
 // zg_seekmany.h: the seek tables of a few entries scanned once, many ranges answered from the prefix sums. locate: one lane per entry, out[i] =
 // what entry i's table frame is. prefix: two launches over the nw chunks of work — zg_k_seekmany_total, then zg_k_seekmany_prefix — that fill
 // pairs[], the scratch the host laid out. find: one lane per range, out[j] = range j's record

@@ -1924,6 +1924,35 @@ void zg_launch_seeksums(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* fr
   hipLaunchKernelGGL(zg_k_seeksums, dim3(n), dim3(zgv::kThreads), 0, s, lanes, n, frames, digests, ndig, out);
 }
 
+// Does a seek index handle vouch for the frames decoded of a group of its rows (ZGPU_DEVICE_VERIFY_SEEK_TABLE on an entry whose handle holds
+// sums)? One WAVE per group of a submit, behind the hash kernel on the same stream: the handle's pairs and sums against the digests that
+// kernel left in device memory (zg_idxsums.h has the rule's source, the access bounds and the ISA notes). No byte of an entry is read. The host
+// checked every lane's rows against the handle's arrays and every slice and slot against the arrays it uploaded (Batch::idxsums_launch);
+// lane 0 writes the group's 32-byte record only.
+#include "zg_idxsums.h"
+struct ZgIdxRows {
+  uint64_t pairs, sums;   // the addresses of the entry's pair 0 and sum 0
+  __device__ __forceinline__ uint64_t c(uint64_t k) const { return *(const __attribute__((address_space(1))) uint64_t*)(pairs + 16 * k); }
+  __device__ __forceinline__ uint32_t sum(uint64_t k) const { return *(const __attribute__((address_space(1))) uint32_t*)(sums + 4 * k); }
+};
+__global__ void __launch_bounds__(zgh::kThreads) zg_k_idxsums(const zgh::Lane* lanes, uint32_t n, uint64_t pairs, uint64_t sums, const zgv::Frame* frames,
+                                                              const uint64_t* digests, uint32_t ndig, zgv::Sums* out) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const zgh::Lane l = lanes[i];
+  const ZgSumsList list{(const __attribute__((address_space(1))) zgv::Frame*)(uintptr_t)(frames + l.frame_lo),
+                        (const __attribute__((address_space(1))) uint64_t*)(uintptr_t)digests};
+  const ZgIdxRows rows{pairs + 16 * l.pair0, sums + 4 * l.sum0};
+  const zgv::Sums o = zgh::idxsums_group(rows, list, l.nrows, l.first, l.taken, l.frame_n, ndig);
+  if (threadIdx.x == 0) zgv::seeksums_store(&out[i], o);
+}
+void zg_launch_idxsums(const zgh::Lane* lanes, uint32_t n, const void* pairs, const uint32_t* sums, const zgv::Frame* frames, const uint64_t* digests,
+                       uint32_t ndig, zgv::Sums* out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_idxsums, dim3(n), dim3(zgh::kThreads), 0, s, lanes, n, (uint64_t)(uintptr_t)pairs, (uint64_t)(uintptr_t)sums, frames, digests,
+                     ndig, out);
+}
+
 // Many ranges over few seekable entries (zg_seekmany.h has the passes, the scratch layout, the access bounds and the ISA notes): the tables are
 // scanned once into prefix sums, every range is a binary search. The host checked every [src, src + len) against the runtime's allocations,
 // sized the scratch from the located row counts and handed every wave and lane its indices into it.

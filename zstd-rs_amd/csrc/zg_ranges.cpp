@@ -12,11 +12,13 @@
 // cuts their frame records into runs, runs them through the device-source machinery and Batch::measure (zg_seqsize.h), and the sizes that
 // come back become the pairs; zgpu_seek_index_export_seek_table writes an entry's pairs out as a seek table (zg_seektab.h).
 #include <stddef.h>
+#include <algorithm>
 #include <string.h>
 #include <string>
 #include <vector>
 #include "zg_frames_int.h"
 #include "zg_seeksums.h"
+#include "zg_idxsums.h"
 
 using namespace zg;
 using namespace zgf;
@@ -244,7 +246,7 @@ extern "C" int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx* c, const void*
                                                         const zgpu_entry_range* ranges, uint32_t m, void* const* device_dsts, const size_t* caps,
                                                         const zgpu_device_opts* opts, zgpu_range_result* results) {
   if (!c || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results))) return ZGPU_E_BAD_ARG;
-  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](const DeviceSink&, auto* recs, auto* refused) {
+  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](DeviceSink&, auto* recs, auto* refused) {
     return seek_many(c, device_srcs, lens, n, ranges, m, device_dsts, caps, recs, refused);
   });
 }
@@ -465,10 +467,13 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
       if (e.info.status || (e.info.kind == ZGPU_INDEX_MEASURED) != (pass == 1)) continue;
       e.pre = pairs;
       pairs += (uint64_t)e.info.nrows + 1;
+      e.spre = x->nsums;   // (where its sums will lie, should it get any)
+      x->nsums += e.info.nrows;
     }
   }
   if (pairs > SIZE_MAX / sizeof(zgm::Pair)) return ZGPU_E_NOMEM;
   if (pairs && (st = x->pairs.reserve((size_t)pairs * sizeof(zgm::Pair)))) return st;
+  x->npairs = pairs;
   stats[kSeekIdxStatDeviceBytes] = pairs * sizeof(zgm::Pair);
   zgm::Pair* dp = x->pairs.as<zgm::Pair>();
   hipStream_t s = eng->stream();
@@ -525,7 +530,7 @@ int build_index(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const 
 // Both indexed calls up to the records. Every range is looked at on its own, as seek_many looks at it (check_entry_ranges), with what the
 // index alone knows of an entry: one it refused is not refused again — its ranges pass untouched and get its status and why —; srcs != nullptr
 // (the gather call): lens[i] must be the length the entry was indexed at; table_flag: ZGPU_DEVICE_VERIFY_SEEK_TABLE refuses the ranges of
-// declared-kind entries. Then ONE find launch over the handle's pairs.
+// declared- and measured-kind entries whose handle holds no sums. Then ONE find launch over the handle's pairs.
 int indexed_ranges(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* srcs, const size_t* lens, const zgpu_entry_range* ranges, uint32_t m,
                    void* const* dsts, const size_t* caps, bool table_flag, std::vector<zgk::Seek>* out, std::vector<uint8_t>* refused) {
   if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
@@ -535,7 +540,8 @@ int indexed_ranges(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* src
   check_entry_ranges(c, srcs, lens, n, ranges, m, dsts, caps, [&](uint32_t i) {
     const zgpu_seek_index_info& info = x->ents[i].info;
     if (info.status) return kPass;   // (the record is the entry's status and why: written below, nothing of the entry is looked at)
-    return (srcs && (uint64_t)lens[i] != info.len) || (table_flag && info.kind != ZGPU_INDEX_SEEK_TABLE) ? kRefuse : kCheck;
+    // (the flag: an entry whose handle holds sums is vouched for by the handle, whatever its kind; else only a table can be enforced)
+    return (srcs && (uint64_t)lens[i] != info.len) || (table_flag && info.kind != ZGPU_INDEX_SEEK_TABLE && !x->ents[i].sums.state) ? kRefuse : kCheck;
   }, refused, &is_live, nullptr);
   std::vector<zgm::Find> lanes(m);
   for (uint32_t j = 0; j < m; j++) {
@@ -582,24 +588,205 @@ extern "C" int zgpu_seek_index_measure_device(zgpu_ctx* c, const void* const* de
   return ZGPU_OK;
 }
 // The entry's 16 * (nrows + 1) bytes of pairs come down, and zg_seektab.h's serialiser writes them out: one definition of the layout.
+// ZGPU_EXPORT_CHECKSUMS: the entry's sums come down too (4 bytes a row) and the sibling serialiser writes rows of 12 bytes.
 extern "C" int zgpu_seek_index_export_seek_table(const zgpu_seek_index* x, uint32_t entry, uint8_t* host_dst, size_t cap, size_t* written) {
+  return zgpu_seek_index_export_seek_table_ex(x, entry, 0, host_dst, cap, written);
+}
+extern "C" int zgpu_seek_index_export_seek_table_ex(const zgpu_seek_index* x, uint32_t entry, uint32_t flags, uint8_t* host_dst, size_t cap, size_t* written) {
   if (written) *written = 0;
-  if (!x || !written || entry >= x->ents.size() || x->ents[entry].info.status || (!host_dst && cap)) return ZGPU_E_BAD_ARG;
+  if (!x || !written || entry >= x->ents.size() || x->ents[entry].info.status || (!host_dst && cap) || (flags & ~ZGPU_EXPORT_CHECKSUMS)) return ZGPU_E_BAD_ARG;
   const zgpu_seek_index::Ent& e = x->ents[entry];
-  const uint64_t need = zgt::seek_table_bytes(e.info.nrows);
+  const bool with_sums = (flags & ZGPU_EXPORT_CHECKSUMS) != 0;
+  if (with_sums && !e.sums.state) return ZGPU_E_BAD_ARG;
+  const uint64_t need = with_sums ? zgt::seek_table_sums_bytes(e.info.nrows) : zgt::seek_table_bytes(e.info.nrows);
   if (need > cap) { *written = (size_t)need; return ZGPU_E_TARGET_TOO_SMALL; }
   if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   std::vector<zgm::Pair> pairs((size_t)e.info.nrows + 1);
   if (hipMemcpy(pairs.data(), x->pairs.as<zgm::Pair>() + e.pre, pairs.size() * sizeof(zgm::Pair), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
   static_assert(sizeof(zgm::Pair) == 16, "pairs as words");
-  if (zgt::write_seek_table((const uint64_t*)pairs.data(), e.info.nrows, host_dst)) return ZGPU_E_SEEK_TABLE;
+  std::vector<uint32_t> sums(with_sums ? e.info.nrows : 0);
+  if (!sums.empty() && hipMemcpy(sums.data(), x->sums.as<uint32_t>() + e.spre, sums.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  if (with_sums ? zgt::write_seek_table_sums((const uint64_t*)pairs.data(), sums.data(), e.info.nrows, host_dst)
+                : zgt::write_seek_table((const uint64_t*)pairs.data(), e.info.nrows, host_dst))
+    return ZGPU_E_SEEK_TABLE;
   *written = (size_t)need;
+  return ZGPU_OK;
+}
+// ---- sums in the handle (include/zgpu.h: seek index checksums; zg_idxsums.h) ---------------------------------------------------------------------
+static_assert(sizeof(zgpu_seek_index_sums) == 32 && offsetof(zgpu_seek_index_sums, frames) == 16 && ZGPU_EXPORT_CHECKSUMS == 1u, "include/zgpu.h");
+namespace {
+constexpr uint64_t kHashRunBytes = 64ull << 20;   // run_bytes == 0
+
+// the handle's array of sums, allocated (zeros: what a skippable row holds) when the first entry gets sums
+int ensure_sums(zgpu_seek_index* x) {
+  if (x->sums.p) return ZGPU_OK;
+  if (x->nsums > SIZE_MAX / 4) return ZGPU_E_NOMEM;
+  const size_t bytes = (size_t)(x->nsums ? x->nsums : 1) * 4;
+  const int st = x->sums.reserve(bytes);
+  if (st) return st;
+  if (hipMemset(x->sums.p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); x->sums.release(); return ZGPU_E_HIP; }
+  x->sums_stats[kSumStatSumsBytes] = x->nsums * 4;
+  return ZGPU_OK;
+}
+
+// The pass. Nothing of the handle changes before every run of every chosen entry has its verdict: an engine failure leaves it as it was.
+int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, const uint8_t* which, uint64_t run_bytes) {
+  zg::Engine* eng = c->eng;
+  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const uint64_t limit = run_bytes ? run_bytes : kHashRunBytes;
+  auto chosen = [&](uint32_t i) { return !which || which[i]; };
+  std::vector<Engine::DevEntry> dev;
+  std::vector<uint8_t> refused;
+  check_entries(c, srcs, lens, nullptr, nullptr, n, [&](uint32_t i) {
+    const zgpu_seek_index_info& info = x->ents[i].info;
+    return !chosen(i) || info.status ? kPass : (uint64_t)lens[i] != info.len ? kRefuse : kCheck;
+  }, &dev, &refused);
+  // the runs of every entry that is hashed: rows [k0, k1) of entry i, one selection each with an empty span of clips
+  struct Run { uint32_t i, k0, k1; };
+  std::vector<Run> runs;
+  std::vector<Selection> sel;
+  std::vector<std::vector<zgm::Pair>> pairs(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const zgpu_seek_index::Ent& e = x->ents[i];
+    if (!chosen(i) || e.info.status || refused[i]) continue;
+    std::vector<zgm::Pair>& p = pairs[i];
+    try { p.resize((size_t)e.info.nrows + 1); } catch (...) { return ZGPU_E_NOMEM; }
+    if (hipMemcpy(p.data(), x->pairs.as<zgm::Pair>() + e.pre, p.size() * sizeof(zgm::Pair), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+    uint32_t k0 = 0;
+    bool any = false;   // the run in progress holds a zstd row
+    auto close = [&](uint32_t k1) {
+      if (k1 > k0) {
+        runs.push_back(Run{i, k0, k1});
+        // (a handle whose pairs do not describe the entry — never: build_index accepted them — is held against the entry's length like any record)
+        const bool bad = p[k0].c > p[k1].c || p[k1].c > e.info.len || p[k0].d > p[k1].d;
+        sel.push_back(Selection{i, bad ? 0 : p[k0].c, bad ? 0 : p[k1].c, bad ? UINT64_MAX : p[k1].d - p[k0].d, k0, k1 - k0, (uint8_t)(bad ? 1 : 0)});
+      }
+      k0 = k1; any = false;
+    };
+    for (uint32_t k = 0; k < e.info.nrows; k++) {
+      const bool zstd = p[k + 1].d > p[k].d;
+      if (zstd && any && p[k + 1].d - p[k0].d > limit) close(k);
+      any = any || zstd;
+    }
+    close(e.info.nrows);
+  }
+  // decoded as the gather calls decode their groups; the sink hashes every frame and hands the digests back
+  zgpu_device_opts opts{0, ZGPU_DEVICE_VERIFY, 0};
+  int st;
+  DeviceSink sink = device_sink(c, &opts, nullptr, &st, false);
+  if (st) return st;
+  sink.hash_every = true;
+  std::vector<std::vector<DeviceSink::Digest>> got;
+  sink.collect = &got;
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  std::vector<Clip> no_clips;
+  std::vector<uint32_t> first(sel.size() + 1, 0);
+  std::vector<zgpu_device_entry_result> dres(sel.size());
+  if (!sel.empty() && (st = decode_selections(c, sink, srcs, lens, sel, no_clips, first, true, nullptr, dres.data()))) return st;
+  // every run's frames to rows; the first failing run of an entry, in row order, is its verdict
+  std::vector<std::vector<uint32_t>> sums(n);
+  std::vector<zgpu_seek_index_sums> rec(n, zgpu_seek_index_sums{0, 0, 0, 0, 0, 0});
+  for (uint32_t i = 0; i < n; i++) if (!pairs[i].empty()) sums[i].assign(x->ents[i].info.nrows, 0);
+  std::string named;
+  for (size_t r = 0; r < runs.size(); r++) {
+    const Run& run = runs[r];
+    zgpu_seek_index_sums& o = rec[run.i];
+    if (o.status) continue;
+    const std::vector<zgm::Pair>& p = pairs[run.i];
+    uint32_t status = (uint32_t)dres[r].r.status;
+    size_t q = 0;
+    for (uint32_t k = run.k0; k < run.k1 && !status; k++) {
+      if (q == got[r].size()) break;
+      const DeviceSink::Digest& f = got[r][q];
+      if (f.begin != p[k].c - p[run.k0].c || f.clen != p[k + 1].c - p[k].c) continue;   // (a skippable row: no frame coincides with it)
+      sums[run.i][k] = (uint32_t)f.digest;
+      q++;
+    }
+    if (!status && q != got[r].size()) status = ZGPU_E_CONTENT_SIZE_MISMATCH;   // (a decoded frame that coincides with no row)
+    if (status) {
+      o = zgpu_seek_index_sums{status, 0, run.k0, run.k1, 0, 0};
+      if (named.empty())
+        named = "zgpu_seek_index_hash_device: entry " + std::to_string(run.i) + ", run of rows [" + std::to_string(run.k0) + ", " + std::to_string(run.k1) + "): " +
+                zgpu_status_name((int)status);
+      continue;
+    }
+    o.frames += got[r].size(); o.bytes += p[run.k1].d - p[run.k0].d;
+  }
+  // the handle: one copy per stretch of chosen entries whose sums lie back to back
+  if ((st = ensure_sums(x))) return st;
+  std::vector<uint32_t> stage;
+  uint64_t at = 0;      // the index of stage[0] in the handle's array
+  hipStream_t s = eng->stream();
+  std::vector<std::vector<uint32_t>> keep;   // (the staging of the stretches sent so far: alive until the stream is drained)
+  auto flush = [&]() -> int {
+    if (stage.empty()) return ZGPU_OK;
+    keep.push_back(std::move(stage));
+    stage.clear();
+    if (hipMemcpyAsync(x->sums.as<uint32_t>() + at, keep.back().data(), keep.back().size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+    return ZGPU_OK;
+  };
+  std::vector<uint32_t> order;
+  for (uint32_t i = 0; i < n; i++) if (!pairs[i].empty()) order.push_back(i);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return x->ents[a].spre < x->ents[b].spre; });
+  for (uint32_t i : order) {
+    const zgpu_seek_index::Ent& e = x->ents[i];
+    if (!stage.empty() && at + stage.size() != e.spre && (st = flush())) return st;
+    if (stage.empty()) at = e.spre;
+    if (rec[i].status) sums[i].assign(e.info.nrows, 0);   // (dropped)
+    stage.insert(stage.end(), sums[i].begin(), sums[i].end());
+  }
+  if ((st = flush())) return st;
+  if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  for (uint32_t i = 0; i < n; i++) {
+    zgpu_seek_index::Ent& e = x->ents[i];
+    if (!chosen(i)) continue;
+    if (e.info.status) { e.sums = zgpu_seek_index_sums{e.info.status, 0, 0, 0, 0, 0}; continue; }
+    if (refused[i]) { e.sums.status = ZGPU_E_BAD_ARG; continue; }   // (nothing of it was looked at: what it holds stays)
+    e.sums = rec[i];
+    if (!rec[i].status) { e.sums.state = 1; x->sums_stats[kSumStatFramesHashed] += rec[i].frames; }
+  }
+  x->sums_stats[kSumStatHashSubmits] += c->frames_submits; x->sums_stats[kSumStatHashUs] += c->frames_device_stats[kDevStatHashUs];
+  x->sums_stats[kSumStatHashRuns] += runs.size();
+  if (!named.empty()) eng->last_error = named;
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_seek_index_hash_device(zgpu_ctx* c, zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                           const uint8_t* which_or_null, uint64_t run_bytes) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens))) return ZGPU_E_BAD_ARG;
+  return drain(c, hash_entries(c, x, device_srcs, lens, n, which_or_null, run_bytes));
+}
+extern "C" int zgpu_seek_index_set_sums(zgpu_seek_index* x, uint32_t entry, const uint32_t* sums, uint32_t nrows) {
+  if (!x || entry >= x->ents.size() || x->ents[entry].info.status || nrows != x->ents[entry].info.nrows || (nrows && !sums)) return ZGPU_E_BAD_ARG;
+  if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  int st = ensure_sums(x);
+  if (st) return st;
+  zgpu_seek_index::Ent& e = x->ents[entry];
+  if (nrows && hipMemcpy(x->sums.as<uint32_t>() + e.spre, sums, (size_t)nrows * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  e.sums = zgpu_seek_index_sums{0, 2, 0, 0, 0, 0};
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_read_sums(const zgpu_seek_index* x, uint32_t entry, uint32_t* dst, uint32_t cap_rows, uint32_t* nrows) {
+  if (nrows) *nrows = 0;
+  if (!x || !nrows || entry >= x->ents.size() || x->ents[entry].info.status || !x->ents[entry].sums.state || (!dst && cap_rows)) return ZGPU_E_BAD_ARG;
+  const zgpu_seek_index::Ent& e = x->ents[entry];
+  *nrows = e.info.nrows;
+  if (cap_rows < e.info.nrows) return ZGPU_E_TARGET_TOO_SMALL;
+  if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  if (e.info.nrows && hipMemcpy(dst, x->sums.as<uint32_t>() + e.spre, (size_t)e.info.nrows * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_sums_of(const zgpu_seek_index* x, uint32_t i, zgpu_seek_index_sums* out) {
+  if (!x || !out || i >= x->ents.size()) return ZGPU_E_BAD_ARG;
+  *out = x->ents[i].sums;
   return ZGPU_OK;
 }
 extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
   if (!x) return;
   if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
   x->pairs.release();
+  x->sums.release();
   delete x;
 }
 extern "C" uint32_t zgpu_seek_index_entries(const zgpu_seek_index* x) { return x ? (uint32_t)x->ents.size() : 0; }
@@ -608,7 +795,11 @@ extern "C" int zgpu_seek_index_info_of(const zgpu_seek_index* x, uint32_t i, zgp
   *out = x->ents[i].info;
   return ZGPU_OK;
 }
-extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) { return x ? copy_stats(x->stats, out, n) : 0; }
+extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) {
+  if (!x) return 0;
+  const int k = copy_stats(x->stats, out, n);   // (the slots of the sums lie behind the others)
+  return k < (int)kSeekIdxStatCount || !out ? k : k + copy_stats(x->sums_stats, out + k, n - k);
+}
 
 extern "C" int zgpu_frames_seek_indexed_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
   if (!c || !x || x->ctx != c || (m && (!ranges || !out))) return ZGPU_E_BAD_ARG;
@@ -620,7 +811,20 @@ extern "C" int zgpu_gather_ranges_indexed_device_src(zgpu_ctx* c, const zgpu_see
                                                      const zgpu_device_opts* opts, zgpu_range_result* results) {
   if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && (!ranges || !device_dsts || !caps || !results)))
     return ZGPU_E_BAD_ARG;
-  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](const DeviceSink& sink, auto* recs, auto* refused) {
+  // ZGPU_DEVICE_VERIFY_SEEK_TABLE: the entries whose handle holds sums go the handle's route (zg_idxsums.h), the others their table's
+  DeviceSink::Handle hs;
+  return gather_groups(c, device_srcs, lens, ranges, m, device_dsts, caps, opts, results, [&](DeviceSink& sink, auto* recs, auto* refused) {
+    if (sink.table_flag && x->sums.p) {
+      hs.pairs = x->pairs.p; hs.npairs = x->npairs;
+      hs.sums = x->sums.as<uint32_t>(); hs.nsums = x->nsums;
+      hs.ent.resize(n); hs.on.assign(n, 0);
+      for (uint32_t i = 0; i < n; i++) {
+        const zgpu_seek_index::Ent& e = x->ents[i];
+        hs.ent[i] = DeviceSink::HandleEntry{e.pre, e.spre, e.info.nrows, 0, 0};
+        hs.on[i] = !e.info.status && e.sums.state != 0;
+      }
+      sink.handle = &hs;
+    }
     return indexed_ranges(c, x, device_srcs, lens, ranges, m, device_dsts, caps, sink.table_flag, recs, refused);
   });
 }

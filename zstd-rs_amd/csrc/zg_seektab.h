@@ -85,6 +85,27 @@ static inline uint32_t write_seek_table(const uint64_t* cd, uint32_t nrows, uint
   le32(p + 5, kSeekMagic);
   return 0;
 }
+// The same frame with the Checksum fields (zgpu_seek_index_export_seek_table_ex, ZGPU_EXPORT_CHECKSUMS): rows of 12 bytes — c_k, d_k, sums[k] —,
+// Frame_Size = 12 * nrows + 9, descriptor 0x80; seek_table_sums_bytes(nrows) = 17 + 12 * nrows bytes. The same refusals, nothing written.
+static inline uint64_t seek_table_sums_bytes(uint64_t nrows) { return kFraming + 12u * nrows; }
+static inline uint32_t write_seek_table_sums(const uint64_t* cd, const uint32_t* sums, uint32_t nrows, uint8_t* dst) {
+  if (nrows > kMaxFrames) return kSeekTable;
+  for (uint32_t k = 0; k < nrows; k++) {
+    if (cd[2 * k + 2] < cd[2 * k] || cd[2 * k + 3] < cd[2 * k + 1]) return kSeekTable;
+    if (cd[2 * k + 2] - cd[2 * k] > 0xFFFFFFFFull || cd[2 * k + 3] - cd[2 * k + 1] > 0xFFFFFFFFull) return kSeekTable;
+  }
+  auto le32 = [](uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); };
+  le32(dst, kSkipMagic);
+  le32(dst + 4, 12u * nrows + 9u);
+  uint8_t* p = dst + 8;
+  for (uint32_t k = 0; k < nrows; k++, p += 12) {
+    le32(p, (uint32_t)(cd[2 * k + 2] - cd[2 * k])); le32(p + 4, (uint32_t)(cd[2 * k + 3] - cd[2 * k + 1])); le32(p + 8, sums[k]);
+  }
+  le32(p, nrows);
+  p[4] = 0x80;
+  le32(p + 5, kSeekMagic);
+  return 0;
+}
 
 }  // namespace zgt
 #endif  // ZG_SEEKTAB_TYPES

@@ -61,6 +61,11 @@ _STATS = {
     "SeekIndex.stats": ("zgpu_seek_index_stats", C.c_uint64,
                         ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host",
                          "measure_submits", "measure_us", "frames_measured")),
+    # the same getter asked for the slots zgpu_seek_index_hash_device appends (csrc/zg_capi_int.h: kSeekIdxStatHash*)
+    "SeekIndex.sums_stats": ("zgpu_seek_index_stats", C.c_uint64,
+                             ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host",
+                              "measure_submits", "measure_us", "frames_measured",
+                              "hash_submits", "hash_us", "frames_hashed", "sums_bytes", "hash_runs")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
                        ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
     "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
@@ -219,6 +224,31 @@ class SeekIndexInfo:
             self.status, self.why, self.kind, self.nrows, self.len, self.compressed, self.plaintext)
 
 
+class SeekIndexSumsC(C.Structure):
+    """zgpu_seek_index_sums (include/zgpu.h)"""
+    _fields_ = [("status", C.c_uint32), ("state", C.c_uint32), ("row_lo", C.c_uint32), ("row_hi", C.c_uint32), ("frames", C.c_uint64),
+                ("bytes", C.c_uint64)]
+
+
+SUMS_NONE, SUMS_HASHED, SUMS_SET = 0, 1, 2   # SeekIndexSums.state
+EXPORT_CHECKSUMS = 1                         # zgpu_seek_index_export_seek_table_ex's flags
+
+
+class SeekIndexSums:
+    """What a SeekIndex knows of one entry's sums (zgpu_seek_index_sums): state SUMS_NONE, SUMS_HASHED or SUMS_SET; status of the last
+    SeekIndex.hash that chose the entry (0, the index's status, E_BAD_ARG, or the failing run's with its rows [row_lo, row_hi)); frames and
+    bytes: the zstd frames and plaintext bytes hashed."""
+    __slots__ = FIELDS = ("status", "state", "row_lo", "row_hi", "frames", "bytes")
+
+    def __init__(self, c):
+        for k in self.FIELDS:
+            setattr(self, k, int(getattr(c, k)))
+
+    def __repr__(self):
+        return "SeekIndexSums(status=%d, state=%d, rows=[%d, %d), frames=%d, bytes=%d)" % (
+            self.status, self.state, self.row_lo, self.row_hi, self.frames, self.bytes)
+
+
 class Seek:
     """One entry of Context.frames_seek_device (zgpu_seek): the whole frames [src_lo, src_hi) of the entry that hold the range, the plaintext
     offset plain_lo of the first of them, bound = plaintext_bound of those bytes. flags: open_ended (an unsized frame was taken: everything
@@ -327,6 +357,8 @@ EXPORTS = [
     "zgpu_seek_index_create_device", "zgpu_seek_index_destroy", "zgpu_seek_index_entries", "zgpu_seek_index_info_of", "zgpu_seek_index_stats",
     "zgpu_frames_seek_indexed_device", "zgpu_gather_ranges_indexed_device_src",
     "zgpu_seek_index_measure_device", "zgpu_seek_index_export_seek_table",
+    "zgpu_seek_index_hash_device", "zgpu_seek_index_set_sums", "zgpu_seek_index_read_sums", "zgpu_seek_index_sums_of",
+    "zgpu_seek_index_export_seek_table_ex",
     "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
@@ -419,6 +451,11 @@ def _declare(L):
     L.zgpu_seek_index_create_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, C.c_uint32, P(vp)]
     L.zgpu_seek_index_measure_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, C.c_uint32, P(vp)]
     L.zgpu_seek_index_export_seek_table.argtypes = [vp, C.c_uint32, C.c_char_p, sz, P(sz)]
+    L.zgpu_seek_index_export_seek_table_ex.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, sz, P(sz)]
+    L.zgpu_seek_index_hash_device.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, C.c_char_p, C.c_uint64]
+    L.zgpu_seek_index_set_sums.argtypes = [vp, C.c_uint32, P(C.c_uint32), C.c_uint32]
+    L.zgpu_seek_index_read_sums.argtypes = [vp, C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_uint32)]
+    L.zgpu_seek_index_sums_of.argtypes = [vp, C.c_uint32, P(SeekIndexSumsC)]
     L.zgpu_seek_index_destroy.argtypes = [vp]
     L.zgpu_seek_index_destroy.restype = None
     L.zgpu_seek_index_entries.argtypes = [vp]
@@ -952,7 +989,8 @@ class Context:
         the sums of match lengths, without a Huffman stream, an LZ77 byte or an output buffer. only_unsized: every entry is indexed as
         seek_index(kind="auto") indexes it, and only those it refuses as INDEX_UNSIZED are measured; else every entry is measured. An entry
         that cannot be measured has E_FRAME_INDEX in index.infos[i] (why: a CHAIN_* reason, SEEKTAB_TOO_LARGE, INDEX_DICT, INDEX_UNMEASURED —
-        last_error names the frame). Measuring does not see Huffman, offset or checksum defects: those surface when the frame is decoded.
+        last_error names the frame). Measuring does not see Huffman, offset or checksum defects: those surface when the frame is decoded —
+        in a gather, or once for the whole shard in SeekIndex.hash.
         The index serves frames_seek_indexed_device and gather_ranges_indexed_device_src like any other; export_seek_table writes it out."""
         n = len(src_ptrs)
         _one_per("seek_index_measured", n, lens)
@@ -984,8 +1022,9 @@ class Context:
         """zgpu_gather_ranges_indexed_device_src: gather_ranges_seek_table_device_src with the selection taken from a SeekIndex — one find
         launch plus the decode, no locate and no prefix pass. src_ptrs / lens name the index's entries (all of them; an entry's length must
         be the one it was indexed at, its address may differ). Everything behind the selection is that call: groups decoded once, fate
-        sharing, E_TARGET_TOO_SMALL per range, the options. verify_table serves table-kind entries; a range of a declared-kind entry gets
-        E_BAD_ARG under it. A stale index ends in a status per range, never in a fault. Returns (results, seeks), one of each per range."""
+        sharing, E_TARGET_TOO_SMALL per range, the options. verify_table: an entry whose index holds sums (SeekIndex.hash / set_sums) is
+        vouched for by the index, of whatever kind; else a table-kind entry reads its table and a range of a declared- or measured-kind
+        entry gets E_BAD_ARG. A stale index ends in a status per range, never in a fault. Returns (results, seeks), one of each per range."""
         n, m = len(src_ptrs), len(ranges)
         _one_per("gather_ranges_indexed_device_src", n, lens)
         _one_per("gather_ranges_indexed_device_src", m, dst_ptrs, caps)
@@ -1149,24 +1188,76 @@ class SeekIndex:
         self.device_bytes = self.stats()["device_bytes"]
         ctx._indexes.append(self)
 
-    def stats(self):
+    def stats(self, sums=False):
         """the build (zgpu_seek_index_stats): launches, kernel_us (HIP events), bytes_downloaded, device_bytes held, rows, input_bytes_to_host
         (always 0); of a measured index also measure_submits, measure_us (their phase-1 time, HIP events) and frames_measured. Gather calls on
-        the index do not change it: the index is never rebuilt."""
-        return _read_stats(self.L, "SeekIndex.stats", self.h)
+        the index do not change it: the index is never rebuilt. sums=True: what hash appends as well — hash_submits, hash_us (the hash
+        kernels' time), frames_hashed, sums_bytes (held now), hash_runs."""
+        return _read_stats(self.L, "SeekIndex.sums_stats" if sums else "SeekIndex.stats", self.h)
 
-    def export_seek_table(self, entry):
-        """zgpu_seek_index_export_seek_table: entry `entry`'s rows as one seek table frame of zstd's seekable format (no checksums), as bytes —
-        what seek_table_frame(csizes, dsizes) builds for those rows. Appended behind the entry's bytes it makes the entry seekable: a file
-        written that way never needs measuring again. A size query, then the call; the entry's pairs are all that is downloaded."""
+    def _open(self, what):
         if not self.h:
-            raise ValueError("export_seek_table: an open SeekIndex")
+            raise ValueError("%s: an open SeekIndex" % what)
+
+    def hash(self, src_ptrs, lens, which=None, run_bytes=0):
+        """zgpu_seek_index_hash_device: every zstd frame of every chosen entry decoded once, its plaintext hashed on the device, the sums —
+        the low 32 bits of XXH64 per row — kept in the index; nothing is delivered. src_ptrs / lens name the index's entries (all of them).
+        which: one truth value per entry (None: all). run_bytes: plaintext per run of rows (0: 64 MiB). This sees what measuring does not:
+        Huffman descriptions and streams, offsets, content checksums. An entry with a failing run keeps no sums; sums_infos says which and
+        why, ctx.last_error names the first. Returns sums_infos."""
+        self._open("hash")
+        n = len(src_ptrs)
+        _one_per("hash", n, lens, which)
+        w = None if which is None else bytes(1 if x else 0 for x in which)
+        self.ctx._check(self.L.zgpu_seek_index_hash_device(self.ctx.h, self.h, _ptr_array(src_ptrs), _size_array(lens), n, w, int(run_bytes)),
+                        "zgpu_seek_index_hash_device")
+        return self.sums_infos
+
+    def hash_tensors(self, tensors, which=None, run_bytes=0):
+        """hash on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on the index's device holding shard i."""
+        self._open("hash_tensors")
+        self.ctx._tensor_check(tensors, "hash_tensors")
+        return self.hash([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors], which, run_bytes)
+
+    def sums(self, entry):
+        """zgpu_seek_index_read_sums: entry `entry`'s sums, one int per row (0 for a skippable row); E_BAD_ARG for an entry without sums"""
+        self._open("sums")
+        n = C.c_uint32(0)
+        rows = self.infos[entry].nrows if 0 <= entry < len(self.infos) else 0
+        a = (C.c_uint32 * max(rows, 1))()
+        self.ctx._check(self.L.zgpu_seek_index_read_sums(self.h, entry, a, rows, C.byref(n)), "zgpu_seek_index_read_sums")
+        return list(a[:n.value])
+
+    def set_sums(self, entry, sums):
+        """zgpu_seek_index_set_sums: the caller's own sums for entry `entry`, one per row — a promise, as an anchor is"""
+        self._open("set_sums")
+        a = (C.c_uint32 * max(len(sums), 1))(*[int(x) & 0xFFFFFFFF for x in sums])
+        self.ctx._check(self.L.zgpu_seek_index_set_sums(self.h, entry, a, len(sums)), "zgpu_seek_index_set_sums")
+
+    @property
+    def sums_infos(self):
+        """one SeekIndexSums per entry (zgpu_seek_index_sums_of), as it stands now"""
+        self._open("sums_infos")
+        rec, out = SeekIndexSumsC(), []
+        for i in range(len(self.infos)):
+            self.ctx._check(self.L.zgpu_seek_index_sums_of(self.h, i, C.byref(rec)), "zgpu_seek_index_sums_of")
+            out.append(SeekIndexSums(rec))
+        return out
+
+    def export_seek_table(self, entry, checksums=False):
+        """zgpu_seek_index_export_seek_table_ex: entry `entry`'s rows as one seek table frame of zstd's seekable format, as bytes — what
+        seek_table_frame(csizes, dsizes) builds for those rows, or, checksums=True, seek_table_frame(csizes, dsizes, self.sums(entry)) (the
+        entry must have sums). Appended behind the entry's bytes it makes the entry seekable: a file written that way never needs measuring
+        again, and with checksums it passes verify_table by its table. A size query, then the call."""
+        self._open("export_seek_table")
+        flags = EXPORT_CHECKSUMS if checksums else 0
         need = C.c_size_t(0)
-        st = self.L.zgpu_seek_index_export_seek_table(self.h, entry, None, 0, C.byref(need))
+        st = self.L.zgpu_seek_index_export_seek_table_ex(self.h, entry, flags, None, 0, C.byref(need))
         if st != E_TARGET_TOO_SMALL:
-            self.ctx._check(st if st else E_BAD_ARG, "zgpu_seek_index_export_seek_table")
+            self.ctx._check(st if st else E_BAD_ARG, "zgpu_seek_index_export_seek_table_ex")
         buf = C.create_string_buffer(need.value)
-        self.ctx._check(self.L.zgpu_seek_index_export_seek_table(self.h, entry, buf, need.value, C.byref(need)), "zgpu_seek_index_export_seek_table")
+        self.ctx._check(self.L.zgpu_seek_index_export_seek_table_ex(self.h, entry, flags, buf, need.value, C.byref(need)),
+                        "zgpu_seek_index_export_seek_table_ex")
         return buf.raw[:need.value]
 
     def close(self):
