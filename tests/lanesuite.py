@@ -38,15 +38,21 @@ def run_stand_alone(exe, args, marker, timeout):
 
 def built_fixture(source, name, main_define=None, extra_sources=(), declare=None):
     """a module-scoped fixture: build() into a temporary directory of its own, then declare(L) for the suite's argtypes. Its value is the
-    library where the harness has no program, else (library, program path, directory)."""
+    library where the harness has no program, else (library, program path, directory). A suite that borrows another suite's fixture gets
+    what that suite built: one build per harness and session."""
     @pytest.fixture(scope="module")
     def built(tmp_path_factory):
-        d = tmp_path_factory.mktemp(name)
-        L, exe = build(d, source, name, main_define, extra_sources)
-        if declare:
-            declare(L)
-        return (L, exe, d) if main_define else L
+        if name not in _BUILT:
+            d = tmp_path_factory.mktemp(name)
+            L, exe = build(d, source, name, main_define, extra_sources)
+            if declare:
+                declare(L)
+            _BUILT[name] = (L, exe, d) if main_define else L
+        return _BUILT[name]
     return built
+
+
+_BUILT = {}
 
 
 def exact_buffer(data):

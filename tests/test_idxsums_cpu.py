@@ -12,7 +12,9 @@ Cases: taken in {1, 63, 64, 65, 128, 129} x first in {0, 1, 63, 64} (skippable r
 unhashed frames, decoy frames of other groups around the slice); a differing sum in lane 0, in lane 63 and in the second step; a frame
 whose begin matches and whose length does not; a frame between two rows; a frame left out of the list; a slot at the digest count; a group
 that leaves the entry; nothing taken. The same cases run once more in a stand-alone AddressSanitizer program (its own main, no Python in
-the process) in which the pairs and sums the wave may read, the slice and the digests each lie in a heap block of exactly their length."""
+the process) in which the pairs and sums the wave may read, the slice and the digests each lie in a heap block of exactly their length.
+One rule behind both routes: every case of test_seeksums_cpu's list whose table is accepted and carries checksums runs through this routine
+as well, its rows turned into pairs and sums, and both records must equal the table route's."""
 import ctypes as C
 import random
 import struct
@@ -21,6 +23,7 @@ import pytest
 
 import idxsums
 import lanesuite
+import test_seeksums_cpu as table_suite
 from idxsums import FIELDS, NO_ROW, model
 
 TAKEN, FIRST = (1, 63, 64, 65, 128, 129), (0, 1, 63, 64)
@@ -154,6 +157,9 @@ def _declare(L):
 built = lanesuite.built_fixture("zg_emu_idxsums.cpp", "idxsums", "IDXSUMS_MAIN", declare=_declare)
 
 
+table_built = table_suite.built   # the table route's harness (lanesuite builds a harness once per session)
+
+
 @pytest.fixture(scope="module")
 def expected():
     """[(case, record, pair window, sum window)]: the model, computed once"""
@@ -198,6 +204,43 @@ def test_idxsums_equals_the_model_and_stays_inside_its_windows(built, expected):
         seen["nothing"] += pw is None
     assert whys == {0, idxsums.WHY_ROWS, idxsums.WHY_LIST}, whys
     assert seen["differ"] >= 5 and seen["uncovered"] >= 2 and seen["unhashed"] > 10 and seen["rowless"] > 10 and seen["nothing"] >= 7, seen
+
+
+def test_both_routes_apply_one_rule(built, table_built):
+    """The rule is written once (zgv::sums_step / zgv::Tally for the waves, zgv::sums_host for the hosts). Every case of the table suite whose
+    table the wave accepts (no why of zg_seektab.h's) and that carries checksums: the rows become a handle's pairs (C[k] = the running sum of
+    c) and sums, and the handle route's wave and host function give the table route's record for the same frames and digests, all eight
+    fields — a selection that leaves the rows (kRows) and a slot behind the digests (kList) included."""
+    L, T = built[0], table_built[0]
+    ran, whys = 0, set()
+    for c in table_suite.cases():
+        e, n = c.entry, len(c.entry)
+        buf, at = lanesuite.aligned_copy(e)
+        fbuf, fat = lanesuite.aligned_copy(_packed_frames(c.frames))
+        dig = (C.c_uint64 * max(len(c.digests), 1))(*c.digests)
+        out, counts = C.create_string_buffer(64), (C.c_uint64 * 5)()
+        open_win = (C.c_uint64 * 6)(0, n, 0, 0, 0, 0)
+        assert T.zgemu_seeksums(at, n, c.first, c.taken, fat, len(c.frames), c.lo, c.n, dig, len(c.digests), open_win, 1, out, counts) == 0
+        table = struct.unpack_from("<8I", out.raw, 0)
+        if table[5] in (16, 17, 18, 19) or table[6]:   # a table the wave refuses; one without checksums
+            continue
+        nf, es = struct.unpack_from("<I", e, n - 9)[0], 12
+        assert e[n - 5] & 0x80 and n >= nf * es + 17
+        rows = [struct.unpack_from("<III", e, n - 9 - (nf - k) * es) for k in range(nf)]
+        cs = [0]
+        for r in rows:
+            cs.append(cs[-1] + r[0])
+        pbuf, pat = lanesuite.aligned_copy(b"".join(struct.pack("<QQ", x, 0) for x in cs))
+        sbuf, sat = lanesuite.aligned_copy(struct.pack("<%dI" % max(nf, 1), *([r[2] for r in rows] or [0])))
+        win = (C.c_uint64 * 4)(0, nf + 1, 0, nf)
+        assert L.zgemu_idxsums(pat, sat, 0, 0, nf, c.first, c.taken, fat, c.lo, c.n, dig, len(c.digests), win, out, counts) == 0
+        wave, host = struct.unpack_from("<8I", out.raw, 0), struct.unpack_from("<8I", out.raw, 32)
+        assert wave == table and host == table, (c.name, dict(zip(FIELDS, wave)), dict(zip(FIELDS, host)), dict(zip(FIELDS, table)))
+        ran += 1
+        whys.add(table[5])
+    # (the 32 taken x first cases, 16 alignments, 5 + 2 + 1 differing / uncovered / unhashed, the selection that leaves the table, the bad slot
+    # and the empty slice: 59; the edits of the 17 framing bytes that leave the table acceptable come on top)
+    assert ran >= 59 and whys == {0, idxsums.WHY_ROWS, idxsums.WHY_LIST}, (ran, whys)
 
 
 def test_idxsums_pinned_example():

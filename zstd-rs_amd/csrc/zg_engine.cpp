@@ -37,6 +37,35 @@ void DevBuf::release() {
   cap = 0;
 }
 
+int SidePass::reserve(size_t bytes) {
+  const int st = buf.reserve(bytes);
+  if (st) return st;
+  for (hipEvent_t& e : ev) if (!e && hipEventCreate(&e) != hipSuccess) return ZG_HIP_ERROR;
+  return 0;
+}
+hipError_t SidePass::upload(const void* a, size_t ab, const void* b, size_t bb, hipStream_t s) const {
+  const hipError_t e = hipMemcpyAsync(buf.p, a, ab, hipMemcpyHostToDevice, s);
+  return e != hipSuccess || !bb ? e : hipMemcpyAsync(at<uint8_t>(ab), b, bb, hipMemcpyHostToDevice, s);
+}
+hipError_t SidePass::end(hipStream_t s) const {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : hipEventRecord(ev[1], s);
+}
+// the time between two recorded events in microseconds, rounded; *us is left alone on an error
+static hipError_t us_between(hipEvent_t a, hipEvent_t b, uint64_t* us) {
+  float ms = 0;
+  const hipError_t e = hipEventElapsedTime(&ms, a, b);
+  if (e == hipSuccess) *us = (uint64_t)(ms * 1000.0f + 0.5f);
+  return e;
+}
+hipError_t SidePass::elapsed_us(uint64_t* us) const { return us_between(ev[0], ev[1], us); }
+void SidePass::release(int device) {
+  if (buf.p && device >= 0) (void)hipSetDevice(device);
+  buf.release();
+  for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  n = 0;
+}
+
 int Scratch::init_events() {
   if (have_events) return 0;
   for (auto& e : ev)
@@ -173,18 +202,7 @@ Batch::~Batch() {
     (void)hipStreamSynchronize(eng->stream5_);                      // (the second half of a download)
     eng->recycle(sc);
   }
-  if (d_hash_.p && eng) { (void)hipSetDevice(eng->device_); d_hash_.release(); }
-  if (d_scatter_.p && eng) { (void)hipSetDevice(eng->device_); d_scatter_.release(); }
-  for (hipEvent_t e : ev_scatter_) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ev_hash_) if (e) (void)hipEventDestroy(e);
-  if (d_seeksums_.p && eng) { (void)hipSetDevice(eng->device_); d_seeksums_.release(); }
-  for (hipEvent_t e : ev_seeksums_) if (e) (void)hipEventDestroy(e);
-  if (d_idxsums_.p && eng) { (void)hipSetDevice(eng->device_); d_idxsums_.release(); }
-  for (hipEvent_t e : ev_idxsums_) if (e) (void)hipEventDestroy(e);
-  for (DevBuf& x : d_fill_) if (x.p && eng) { (void)hipSetDevice(eng->device_); x.release(); }
-  for (hipEvent_t e : ev_fill_) if (e) (void)hipEventDestroy(e);
-  if (d_gather_.p && eng) { (void)hipSetDevice(eng->device_); d_gather_.release(); }
-  for (hipEvent_t e : ev_gather_) if (e) (void)hipEventDestroy(e);
+  for (SidePass& p : side_) p.release(eng ? eng->device_ : -1);   // (no engine: nothing was ever reserved)
 }
 
 void FrameState::reset() {
@@ -347,13 +365,10 @@ int Engine::prepare_entries(const uint8_t* src, size_t len, const uint64_t* off,
 }
 
 // device memory and events of the lane passes of one call
-struct Engine::LaneTmp {
-  DevBuf lanes, out, extra;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~LaneTmp() {
-    lanes.release(); out.release(); extra.release();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
+struct Engine::LaneTmp : SidePass {
+  DevBuf& lanes = buf;   // (the pass's own buffer holds the lanes)
+  DevBuf out, extra;
+  ~LaneTmp() { release(); out.release(); extra.release(); }
 };
 
 template <class Launch>
@@ -362,20 +377,18 @@ int Engine::lane_pass(LaneTmp& t, const void* lanes, size_t lane_bytes, Down out
   ZG_HIP(hipSetDevice(device_));
   hipStream_t s = stream_;
   int st;
-  if ((st = t.lanes.reserve(lane_bytes)) || (st = t.out.reserve(out.bytes)) || (extra.host && (st = t.extra.reserve(extra.bytes)))) return st;
-  for (hipEvent_t& x : t.ev) if (!x) ZG_HIP(hipEventCreate(&x));
-  ZG_HIP(hipMemcpyAsync(t.lanes.p, lanes, lane_bytes, hipMemcpyHostToDevice, s));
+  if ((st = t.reserve(lane_bytes)) || (st = t.out.reserve(out.bytes)) || (extra.host && (st = t.extra.reserve(extra.bytes)))) return st;
+  ZG_HIP(t.upload(lanes, lane_bytes, nullptr, 0, s));
   ZG_HIP(hipStreamSynchronize(s));   // (pageable)
-  ZG_HIP(hipEventRecord(t.ev[0], s));
+  ZG_HIP(t.begin(s));
   launch(t, s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(t.ev[1], s));
+  ZG_HIP(t.end(s));
   ZG_HIP(hipMemcpyAsync(out.host, t.out.p, out.bytes, hipMemcpyDeviceToHost, s));
   if (extra.bytes) ZG_HIP(hipMemcpyAsync(extra.host, t.extra.p, extra.bytes, hipMemcpyDeviceToHost, s));
   ZG_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
-  stats[kPassLaunches] += 1; stats[kPassUs] += (uint64_t)(ms * 1000.0f + 0.5f); stats[kPassBytes] += out.bytes + extra.bytes;
+  uint64_t us = 0;
+  ZG_HIP(t.elapsed_us(&us));
+  stats[kPassLaunches] += 1; stats[kPassUs] += us; stats[kPassBytes] += out.bytes + extra.bytes;
   return ZG_OK;
 }
 
@@ -481,18 +494,17 @@ int Engine::seekmany_prefixes(const DevEntry* e, uint32_t ne, zgm::Loc* loc, uin
   const size_t bytes = (size_t)(pairs + chunks) * sizeof(zgm::Pair), wbytes = work.size() * sizeof(zgm::Work);
   ZG_HIP(hipSetDevice(device_));
   int st;
-  if ((st = scratch->reserve(bytes)) || (st = tp.lanes.reserve(wbytes))) return st;
-  for (hipEvent_t& x : tp.ev) if (!x) ZG_HIP(hipEventCreate(&x));
-  ZG_HIP(hipMemcpyAsync(tp.lanes.p, work.data(), wbytes, hipMemcpyHostToDevice, stream_));
+  // (lane_pass's steps without its download: nothing of the prefixes comes back, and nothing is added to stats[])
+  if ((st = scratch->reserve(bytes)) || (st = tp.reserve(wbytes))) return st;
+  ZG_HIP(tp.upload(work.data(), wbytes, nullptr, 0, stream_));
   ZG_HIP(hipStreamSynchronize(stream_));   // (pageable)
-  ZG_HIP(hipEventRecord(tp.ev[0], stream_));
+  ZG_HIP(tp.begin(stream_));
   zg_launch_seekmany_prefix(tp.lanes.as<zgm::Work>(), (uint32_t)work.size(), scratch->as<zgm::Pair>(), stream_);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(tp.ev[1], stream_));
+  ZG_HIP(tp.end(stream_));
   ZG_HIP(hipStreamSynchronize(stream_));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, tp.ev[0], tp.ev[1]));
-  more->prefix_launches += 2; more->prefix_us += (uint64_t)(ms * 1000.0f + 0.5f); more->scratch_bytes += (uint64_t)pairs * sizeof(zgm::Pair);
+  uint64_t us = 0;
+  ZG_HIP(tp.elapsed_us(&us));
+  more->prefix_launches += 2; more->prefix_us += us; more->scratch_bytes += (uint64_t)pairs * sizeof(zgm::Pair);
   *npairs = pairs;
   return ZG_OK;
 }
@@ -666,14 +678,12 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
     if (b->gather_chunks_.size() > 0xFFFFFFFFull) { delete b; return ZG_INTERNAL; }
     if (!b->gather_chunks_.empty()) {
       const size_t sb = b->gather_segs_.size() * sizeof(zgs::Seg), cb = b->gather_chunks_.size() * sizeof(zgs::Chunk);
-      if ((st = b->d_gather_.reserve(sb + cb))) { delete b; return st; }
-      bool ok = true;
-      for (hipEvent_t& e : b->ev_gather_) ok = ok && (e || hipEventCreate(&e) == hipSuccess);
-      ok = ok && hipMemcpyAsync(b->d_gather_.p, b->gather_segs_.data(), sb, hipMemcpyHostToDevice, us) == hipSuccess;
-      ok = ok && hipMemcpyAsync((uint8_t*)b->d_gather_.p + sb, b->gather_chunks_.data(), cb, hipMemcpyHostToDevice, us) == hipSuccess;
-      ok = ok && hipEventRecord(b->ev_gather_[0], us) == hipSuccess;
-      if (ok) zg_launch_gather(b->d_gather_.as<zgs::Seg>(), (const zgs::Chunk*)((uint8_t*)b->d_gather_.p + sb), (uint32_t)b->gather_chunks_.size(), us);
-      ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(b->ev_gather_[1], us) == hipSuccess;
+      SidePass& p = b->side_[Batch::kSideGather];
+      if ((st = p.reserve(sb + cb))) { delete b; return st; }
+      // (no wait behind the upload: the tables travel from the batch's own vectors, which outlive the copies)
+      bool ok = p.upload(b->gather_segs_.data(), sb, b->gather_chunks_.data(), cb, us) == hipSuccess && p.begin(us) == hipSuccess;
+      if (ok) zg_launch_gather(p.at<zgs::Seg>(0), p.at<zgs::Chunk>(sb), (uint32_t)b->gather_chunks_.size(), us);
+      ok = ok && p.end(us) == hipSuccess;
       if (!ok) { delete b; return ZG_HIP_ERROR; }
       b->gather_launched = true;
     }
@@ -736,11 +746,7 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
     if (hipEventRecord(sc->ev_up, us) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
     b->wait_upload = true;
   } else if (hipStreamSynchronize(stream_) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
-  if (b->gather_launched && !side) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, b->ev_gather_[0], b->ev_gather_[1]) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
-    b->gather_us = (uint64_t)(ms * 1000.0f + 0.5f);
-  }
+  if (b->gather_launched && !side && b->side_[Batch::kSideGather].elapsed_us(&b->gather_us) != hipSuccess) { delete b; return ZG_HIP_ERROR; }
   *out = b;
   return ZG_OK;
 }
@@ -772,7 +778,7 @@ int Batch::run() {
   // (not for a declared total of 0: the device's "sized in advance" marker is a capacity > 0, and a submit that declares nothing but produces
   //  one byte kept its promise by that marker while the host's capacity said 0 — zgpu_batch_read refused the byte, tools/dev/soak_batch.py)
   // (nor a shared submit with dictionary frames: the host places their contents once it knows where the scan put the frames)
-  dictfill_launches = 0; dictfill_bytes = 0; dictfill_us = 0; fill_mask_ = 0;
+  dictfill_launches = 0; dictfill_bytes = 0; dictfill_us = 0; side_[kSideFill0].n = side_[kSideFill1].n = 0;
   if (!fs && all_declared && declared_total && !eng->no_presize_ && declared_total <= bb.out_bound && !bb.ramped && frame_dicts_.empty()) {
     // (the scratch first: it is four times the output. When either reserve fails nothing of the attempt stays allocated — the sizes taken
     //  from the scan may well fit where the declared ones did not: ADVICE r5)
@@ -874,8 +880,7 @@ int Batch::measure(uint64_t* phase1_us) {
   ZG_HIP(hipEventRecord(ev[1], s));
   ZG_HIP(hipMemcpyAsync(frame_out.data(), d.frame_out, (size_t)d.nframes * sizeof(ZgFrameOut), hipMemcpyDeviceToHost, s));
   ZG_HIP(hipStreamSynchronize(s));
-  float m = 0;
-  if (phase1_us && hipEventElapsedTime(&m, ev[0], ev[1]) == hipSuccess) *phase1_us = (uint64_t)(m * 1000.0f + 0.5f);
+  if (phase1_us) (void)us_between(ev[0], ev[1], phase1_us);
   return ZG_OK;
 }
 
@@ -921,19 +926,16 @@ int Batch::dictfill_launch(int part) {
   zgd::plan_fill(segs.data(), (uint32_t)segs.size(), 0, &ch);
   if (ch.empty() || ch.size() > 0xFFFFFFFFull) return ch.empty() ? ZG_OK : ZG_INTERNAL;
   const size_t sb = segs.size() * sizeof(zgd::Seg), cb = ch.size() * sizeof(zgs::Chunk);
-  DevBuf& t = d_fill_[part];
+  SidePass& t = side_[kSideFill0 + part];
   int st = t.reserve(sb + cb);
   if (st) return st;
-  for (int k = 0; k < 2; k++) if (!ev_fill_[2 * part + k]) ZG_HIP(hipEventCreate(&ev_fill_[2 * part + k]));
   hipStream_t s = eng->stream_;
-  ZG_HIP(hipMemcpyAsync(t.p, segs.data(), sb, hipMemcpyHostToDevice, s));
-  ZG_HIP(hipMemcpyAsync((uint8_t*)t.p + sb, ch.data(), cb, hipMemcpyHostToDevice, s));
+  ZG_HIP(t.upload(segs.data(), sb, ch.data(), cb, s));
   ZG_HIP(hipStreamSynchronize(s));   // (the tables are pageable and go out of scope; the stream is idle here: the uploads, or the scan, were waited for)
-  ZG_HIP(hipEventRecord(ev_fill_[2 * part], s));
-  zg_launch_dictfill(t.as<zgd::Seg>(), (const zgs::Chunk*)((uint8_t*)t.p + sb), (uint32_t)ch.size(), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(ev_fill_[2 * part + 1], s));
-  fill_mask_ |= 1u << part;
+  ZG_HIP(t.begin(s));
+  zg_launch_dictfill(t.at<zgd::Seg>(0), t.at<zgs::Chunk>(sb), (uint32_t)ch.size(), s);
+  ZG_HIP(t.end(s));
+  t.n = 1;
   dictfill_launches++;
   for (const zgd::Seg& x : segs) dictfill_bytes += x.len;
   return ZG_OK;
@@ -1178,8 +1180,10 @@ int Batch::sync() {
   }
   float m = 0;
   dictfill_us = 0;
-  for (int k = 0; k < 2; k++)
-    if (((fill_mask_ >> k) & 1u) && hipEventElapsedTime(&m, ev_fill_[2 * k], ev_fill_[2 * k + 1]) == hipSuccess) dictfill_us += (uint64_t)(m * 1000.0f + 0.5f);
+  for (int k = 0; k < 2; k++) {
+    uint64_t us = 0;
+    if (side_[kSideFill0 + k].n && side_[kSideFill0 + k].elapsed_us(&us) == hipSuccess) dictfill_us += us;
+  }
   if (hipEventElapsedTime(&m, sc->ev_huf[0], sc->ev_huf[1]) == hipSuccess) ms[ZG_T_HUF] = m;   // beside seq + seqpost, not in line ...
   if (dev.flags & ZG_FLAG_LIT_DIRECT) ms[ZG_T_LIT] = ms[ZG_T_LIT] > ms[ZG_T_HUF] ? ms[ZG_T_LIT] - ms[ZG_T_HUF] : 0.f;   // ... or, after the scan, in front of zg_k_lit
   if (hipEventElapsedTime(&m, ev[0], ev[ZG_T_TOTAL]) == hipSuccess) ms[ZG_T_TOTAL] = m;
@@ -1246,7 +1250,8 @@ int Batch::read_output(uint64_t off, uint8_t* dst, uint64_t n) {
 }
 int Batch::hash_launch(const uint32_t* frames, uint32_t n, uint32_t quad_max_ranges) {
   ZG_HIP(hipSetDevice(eng->device_));
-  hash_n_ = 0;
+  SidePass& p = side_[kSideHash];
+  p.n = 0;
   if (!n) return ZG_OK;
   if (!synced) return ZG_BAD_ARG;
   // longest first: the 64 lanes of a wave get ranges of similar length (a wave lasts as long as its longest lane), and the longest waves start first
@@ -1259,36 +1264,33 @@ int Batch::hash_launch(const uint32_t* frames, uint32_t n, uint32_t quad_max_ran
   }
   std::stable_sort(r.begin(), r.end(), [](const ZgHashRange& a, const ZgHashRange& b) { return a.len > b.len; });
   const size_t rb = (size_t)n * sizeof(ZgHashRange);
-  int st = d_hash_.reserve(rb + (size_t)n * 8);
+  int st = p.reserve(rb + (size_t)n * 8);
   if (st) return st;
   hipStream_t s = eng->stream_;
-  ZG_HIP(hipMemcpyAsync(d_hash_.p, r.data(), rb, hipMemcpyHostToDevice, s));
+  ZG_HIP(p.upload(r.data(), rb, nullptr, 0, s));
   ZG_HIP(hipStreamSynchronize(s));   // (r is pageable and goes out of scope)
-  for (hipEvent_t& e : ev_hash_) if (!e) ZG_HIP(hipEventCreate(&e));
-  ZG_HIP(hipEventRecord(ev_hash_[0], s));
-  zg_launch_xxh64_with(dev.dst, d_hash_.as<ZgHashRange>(), (uint64_t*)((uint8_t*)d_hash_.p + rb), n, s, n <= quad_max_ranges ? 4 : 0);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(ev_hash_[1], s));
-  hash_n_ = n;
+  ZG_HIP(p.begin(s));
+  zg_launch_xxh64_with(dev.dst, p.at<ZgHashRange>(0), p.at<uint64_t>(rb), n, s, n <= quad_max_ranges ? 4 : 0);
+  ZG_HIP(p.end(s));
+  p.n = n;
+  p.back = rb;
   return ZG_OK;
 }
 int Batch::hash_wait(uint64_t* out, uint64_t* kernel_us) {
+  SidePass& p = side_[kSideHash];
   if (kernel_us) *kernel_us = 0;
-  if (!hash_n_) return ZG_OK;
+  if (!p.n) return ZG_OK;
   ZG_HIP(hipSetDevice(eng->device_));
   ZG_HIP(hipStreamSynchronize(eng->stream_));
-  if (kernel_us) {
-    float ms = 0;
-    ZG_HIP(hipEventElapsedTime(&ms, ev_hash_[0], ev_hash_[1]));
-    *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
-  }
-  ZG_HIP(hipMemcpy(out, (uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange), (size_t)hash_n_ * 8, hipMemcpyDeviceToHost));
-  hash_n_ = 0;
+  if (kernel_us) ZG_HIP(p.elapsed_us(kernel_us));
+  ZG_HIP(hipMemcpy(out, p.at<uint8_t>(p.back), (size_t)p.n * 8, hipMemcpyDeviceToHost));
+  p.n = 0;
   return ZG_OK;
 }
 int Batch::scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk) {
   ZG_HIP(hipSetDevice(eng->device_));
-  scatter_on_ = false;
+  SidePass& p = side_[kSideScatter];
+  p.n = 0;
   if (!n) return ZG_OK;
   if (!synced) return ZG_BAD_ARG;
   for (uint32_t i = 0; i < n; i++)   // reads stay inside the output: the lanes read [src_off, src_off + len) and nothing else (zg_scatter.h)
@@ -1298,116 +1300,82 @@ int Batch::scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk) {
   if (ch.empty()) return ZG_OK;
   if (ch.size() > 0xFFFFFFFFull) return ZG_INTERNAL;
   const size_t sb = (size_t)n * sizeof(zgs::Seg), cb = ch.size() * sizeof(zgs::Chunk);
-  int st = d_scatter_.reserve(sb + cb);
+  int st = p.reserve(sb + cb);
   if (st) return st;
-  for (hipEvent_t& e : ev_scatter_) if (!e) ZG_HIP(hipEventCreate(&e));
   hipStream_t s = eng->stream2_;
-  ZG_HIP(hipMemcpyAsync(d_scatter_.p, segs, sb, hipMemcpyHostToDevice, s));
-  ZG_HIP(hipMemcpyAsync((uint8_t*)d_scatter_.p + sb, ch.data(), cb, hipMemcpyHostToDevice, s));
+  ZG_HIP(p.upload(segs, sb, ch.data(), cb, s));
   ZG_HIP(hipStreamSynchronize(s));   // (the tables are pageable, and ch goes out of scope)
-  ZG_HIP(hipEventRecord(ev_scatter_[0], s));
-  zg_launch_scatter(dev.dst, d_scatter_.as<zgs::Seg>(), (const zgs::Chunk*)((uint8_t*)d_scatter_.p + sb), (uint32_t)ch.size(), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(ev_scatter_[1], s));
-  scatter_on_ = true;
+  ZG_HIP(p.begin(s));
+  zg_launch_scatter(dev.dst, p.at<zgs::Seg>(0), p.at<zgs::Chunk>(sb), (uint32_t)ch.size(), s);
+  ZG_HIP(p.end(s));
+  p.n = 1;
   return ZG_OK;
 }
 int Batch::scatter_wait(uint64_t* kernel_us, bool* launched) {
+  SidePass& p = side_[kSideScatter];
   *kernel_us = 0;
-  *launched = scatter_on_;
-  if (!scatter_on_) return ZG_OK;
+  *launched = p.n != 0;
+  if (!p.n) return ZG_OK;
   ZG_HIP(hipSetDevice(eng->device_));
-  scatter_on_ = false;
+  p.n = 0;
   ZG_HIP(hipStreamSynchronize(eng->stream2_));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, ev_scatter_[0], ev_scatter_[1]));
-  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
+  ZG_HIP(p.elapsed_us(kernel_us));
+  return ZG_OK;
+}
+// What the two compare launches share. L: the route's Lane (frame_lo, frame_n: its slice). p's buffer holds lanes | frames | records; the
+// tables travel on the second stream (idle: the scatter waits for the verdicts) and launch(lanes, frames, digests, records, stream) goes
+// behind the hash kernel on the first, which is not waited for.
+template <class L, class Launch>
+int Batch::compare_launch(SidePass& p, const L* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, Launch launch) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  p.n = 0;
+  if (!n) return ZG_OK;
+  if (!synced) return ZG_BAD_ARG;
+  const SidePass& h = side_[kSideHash];
+  for (uint32_t i = 0; i < n; i++)   // a wave reads its own slice of the list and the digests that slice names (zg_seeksums.h)
+    if (lanes[i].frame_lo > nframes || lanes[i].frame_n > nframes - lanes[i].frame_lo) return ZG_INTERNAL;
+  for (uint32_t q = 0; q < nframes; q++)
+    if (frames[q].slot != zgv::kNotHashed && frames[q].slot >= h.n) return ZG_INTERNAL;
+  const size_t lb = (size_t)n * sizeof(L), fb = (size_t)nframes * sizeof(zgv::Frame), ob = (size_t)n * sizeof(zgv::Sums);
+  int st = p.reserve(lb + fb + ob);
+  if (st) return st;
+  hipStream_t up = eng->stream2_, s = eng->stream_;
+  ZG_HIP(p.upload(lanes, lb, frames, fb, up));
+  ZG_HIP(hipStreamSynchronize(up));   // (the tables are pageable)
+  ZG_HIP(p.begin(s));
+  launch(p.at<L>(0), p.at<zgv::Frame>(lb), h.n ? h.at<uint64_t>(h.back) : nullptr, p.at<zgv::Sums>(lb + fb), s);
+  ZG_HIP(p.end(s));
+  p.n = n;
+  p.back = lb + fb;
   return ZG_OK;
 }
 int Batch::seeksums_launch(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes) {
-  ZG_HIP(hipSetDevice(eng->device_));
-  seeksums_n_ = 0;
-  if (!n) return ZG_OK;
-  if (!synced) return ZG_BAD_ARG;
-  for (uint32_t i = 0; i < n; i++)   // a wave reads its own slice of the list and the digests that slice names, and nothing else (zg_seeksums.h)
-    if (lanes[i].frame_lo > nframes || lanes[i].frame_n > nframes - lanes[i].frame_lo) return ZG_INTERNAL;
-  for (uint32_t q = 0; q < nframes; q++)
-    if (frames[q].slot != zgv::kNotHashed && frames[q].slot >= hash_n_) return ZG_INTERNAL;
-  const size_t lb = (size_t)n * sizeof(zgv::Lane), fb = (size_t)nframes * sizeof(zgv::Frame), ob = (size_t)n * sizeof(zgv::Sums);
-  int st = d_seeksums_.reserve(lb + fb + ob);
-  if (st) return st;
-  for (hipEvent_t& e : ev_seeksums_) if (!e) ZG_HIP(hipEventCreate(&e));
-  // the tables travel on the second stream (idle: the scatter waits for the verdicts) and the kernel goes behind the hash kernel on the first,
-  // which is not waited for
-  hipStream_t up = eng->stream2_, s = eng->stream_;
-  ZG_HIP(hipMemcpyAsync(d_seeksums_.p, lanes, lb, hipMemcpyHostToDevice, up));
-  if (fb) ZG_HIP(hipMemcpyAsync((uint8_t*)d_seeksums_.p + lb, frames, fb, hipMemcpyHostToDevice, up));
-  ZG_HIP(hipStreamSynchronize(up));   // (the tables are pageable)
-  const uint64_t* dig = hash_n_ ? (const uint64_t*)((uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange)) : nullptr;
-  ZG_HIP(hipEventRecord(ev_seeksums_[0], s));
-  zg_launch_seeksums(d_seeksums_.as<zgv::Lane>(), n, (const zgv::Frame*)((uint8_t*)d_seeksums_.p + lb), dig, hash_n_,
-                     (zgv::Sums*)((uint8_t*)d_seeksums_.p + lb + fb), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(ev_seeksums_[1], s));
-  seeksums_n_ = n;
-  seeksums_out_ = lb + fb;
-  return ZG_OK;
-}
-int Batch::seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
-  *kernel_us = 0; *bytes = 0;
-  if (!seeksums_n_) return ZG_OK;
-  ZG_HIP(hipSetDevice(eng->device_));
-  ZG_HIP(hipStreamSynchronize(eng->stream_));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, ev_seeksums_[0], ev_seeksums_[1]));
-  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
-  *bytes = (uint64_t)seeksums_n_ * sizeof(zgv::Sums);
-  ZG_HIP(hipMemcpy(out, (uint8_t*)d_seeksums_.p + seeksums_out_, (size_t)*bytes, hipMemcpyDeviceToHost));
-  seeksums_n_ = 0;
-  return ZG_OK;
+  return compare_launch(side_[kSideTable], lanes, n, frames, nframes, [&](const zgv::Lane* l, const zgv::Frame* f, const uint64_t* dig, zgv::Sums* out, hipStream_t s) {
+    zg_launch_seeksums(l, n, f, dig, side_[kSideHash].n, out, s);
+  });
 }
 int Batch::idxsums_launch(const zgh::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, const void* pairs, uint64_t npairs,
                           const uint32_t* sums, uint64_t nsums) {
-  ZG_HIP(hipSetDevice(eng->device_));
-  idxsums_n_ = 0;
-  if (!n) return ZG_OK;
-  if (!synced || !pairs || (!sums && nsums)) return ZG_BAD_ARG;
-  for (uint32_t i = 0; i < n; i++) {   // a wave reads pairs [first, first + taken] and sums [first, first + taken) of its entry, its own slice, the digests it names (zg_idxsums.h)
+  side_[kSideHandle].n = 0;
+  if (n && (!synced || !pairs || (!sums && nsums))) return ZG_BAD_ARG;
+  for (uint32_t i = 0; i < n; i++) {   // a wave reads pairs [first, first + taken] and sums [first, first + taken) of its entry (zg_idxsums.h)
     const zgh::Lane& l = lanes[i];
-    if (l.frame_lo > nframes || l.frame_n > nframes - l.frame_lo) return ZG_INTERNAL;
     if (l.pair0 > npairs || (uint64_t)l.nrows + 1 > npairs - l.pair0 || l.sum0 > nsums || l.nrows > nsums - l.sum0) return ZG_INTERNAL;
   }
-  for (uint32_t q = 0; q < nframes; q++)
-    if (frames[q].slot != zgv::kNotHashed && frames[q].slot >= hash_n_) return ZG_INTERNAL;
-  const size_t lb = (size_t)n * sizeof(zgh::Lane), fb = (size_t)nframes * sizeof(zgv::Frame), ob = (size_t)n * sizeof(zgv::Sums);
-  int st = d_idxsums_.reserve(lb + fb + ob);
-  if (st) return st;
-  for (hipEvent_t& e : ev_idxsums_) if (!e) ZG_HIP(hipEventCreate(&e));
-  hipStream_t up = eng->stream2_, s = eng->stream_;   // (as seeksums_launch: the tables on the idle second stream, the kernel behind the hash kernel)
-  ZG_HIP(hipMemcpyAsync(d_idxsums_.p, lanes, lb, hipMemcpyHostToDevice, up));
-  if (fb) ZG_HIP(hipMemcpyAsync((uint8_t*)d_idxsums_.p + lb, frames, fb, hipMemcpyHostToDevice, up));
-  ZG_HIP(hipStreamSynchronize(up));   // (the tables are pageable)
-  const uint64_t* dig = hash_n_ ? (const uint64_t*)((uint8_t*)d_hash_.p + (size_t)hash_n_ * sizeof(ZgHashRange)) : nullptr;
-  ZG_HIP(hipEventRecord(ev_idxsums_[0], s));
-  zg_launch_idxsums(d_idxsums_.as<zgh::Lane>(), n, pairs, sums, (const zgv::Frame*)((uint8_t*)d_idxsums_.p + lb), dig, hash_n_,
-                    (zgv::Sums*)((uint8_t*)d_idxsums_.p + lb + fb), s);
-  ZG_HIP(hipGetLastError());
-  ZG_HIP(hipEventRecord(ev_idxsums_[1], s));
-  idxsums_n_ = n;
-  idxsums_out_ = lb + fb;
-  return ZG_OK;
+  return compare_launch(side_[kSideHandle], lanes, n, frames, nframes, [&](const zgh::Lane* l, const zgv::Frame* f, const uint64_t* dig, zgv::Sums* out, hipStream_t s) {
+    zg_launch_idxsums(l, n, pairs, sums, f, dig, side_[kSideHash].n, out, s);
+  });
 }
-int Batch::idxsums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
+int Batch::compare_wait(bool by_handle, zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes) {
+  SidePass& p = side_[by_handle ? kSideHandle : kSideTable];
   *kernel_us = 0; *bytes = 0;
-  if (!idxsums_n_) return ZG_OK;
+  if (!p.n) return ZG_OK;
   ZG_HIP(hipSetDevice(eng->device_));
   ZG_HIP(hipStreamSynchronize(eng->stream_));
-  float ms = 0;
-  ZG_HIP(hipEventElapsedTime(&ms, ev_idxsums_[0], ev_idxsums_[1]));
-  *kernel_us = (uint64_t)(ms * 1000.0f + 0.5f);
-  *bytes = (uint64_t)idxsums_n_ * sizeof(zgv::Sums);
-  ZG_HIP(hipMemcpy(out, (uint8_t*)d_idxsums_.p + idxsums_out_, (size_t)*bytes, hipMemcpyDeviceToHost));
-  idxsums_n_ = 0;
+  ZG_HIP(p.elapsed_us(kernel_us));
+  *bytes = (uint64_t)p.n * sizeof(zgv::Sums);
+  ZG_HIP(hipMemcpy(out, p.at<uint8_t>(p.back), (size_t)*bytes, hipMemcpyDeviceToHost));
+  p.n = 0;
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

@@ -26,6 +26,23 @@ struct DevBuf {
   template <typename T> T* as() const { return (T*)p; }
 };
 
+// One timed pass beside or behind the decode: what Batch's side passes (below) and the engine's lane passes each need — ONE device buffer for the
+// pass's tables and what it leaves, two events created with the first reserve, and n: what the pass in flight was launched over (0: none).
+// Which stream a site uploads and launches on, where it waits and what it counts stay the site's: this holds only what every site repeated.
+struct SidePass {
+  DevBuf buf;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  uint32_t n = 0;
+  size_t back = 0;                             // where what the kernel leaves begins in buf
+  int reserve(size_t bytes);                   // the buffer and the events
+  hipError_t upload(const void* a, size_t ab, const void* b, size_t bb, hipStream_t s) const;   // a to the front of buf, b (bb != 0) behind it
+  hipError_t begin(hipStream_t s) const { return hipEventRecord(ev[0], s); }
+  hipError_t end(hipStream_t s) const;         // the launch's hipGetLastError, then the second event
+  hipError_t elapsed_us(uint64_t* us) const;   // the time between the two events, rounded to microseconds
+  void release(int device = -1);               // device >= 0: made current in front of the free (a Batch may die on any thread)
+  template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
+};
+
 // What one frame carries from one submit of its blocks to the next (the reference's DecoderScratch, scratch.rs:15-27):
 // the decode window (a dictionary's content sits in front of it), the offset history, and the Huffman / FSE tables a
 // later Treeless / Repeat block may decode with. The device holds [front pad][dictionary content][the last `have` bytes of
@@ -179,32 +196,32 @@ class Batch {
   int read_output(uint64_t off, uint8_t* dst, uint64_t n);   // D2H
   int read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s);
   const uint8_t* device_output() const { return dev.dst; }
-  // after sync(): XXH64 (seed 0) of the output bytes of frames[0 .. n) as sync() left them ([out_base, out_base + out_size): a failed frame's
-  // good blocks), one lane or one quad of lanes per frame (zg_k_xxh64 / zg_k_xxh64q: zg_launch_xxh64 chooses), enqueued on the engine's first
-  // stream; hash_wait() waits and writes digest i of frames[i]; *kernel_us, if asked for: the kernel's time between two HIP events
-  // quad_max_ranges: up to this many frames the launch is zg_k_xxh64q's whatever zg_launch_xxh64 would choose (0: its choice; the calls that
-  // carry ZGPU_DEVICE_VERIFY_SEEK_TABLE hash few mid-sized frames per range, LABNOTES.md "xxh64q")
+  // The side passes of a finished submit (after sync()). Each is a launch / wait pair over a SidePass of its own: launch checks what the kernel
+  // will read against the arrays it uploads (a range, segment, slice or slot that leaves them: ZGPU_E_INTERNAL, nothing launched), uploads its
+  // tables, and enqueues ONE kernel between two HIP events; wait waits for the kernel's stream and gives *kernel_us, the time between the
+  // events, and what the kernel left. No launch (n == 0, no bytes): wait gives zeros. What differs:
+  //  - hash: XXH64 (seed 0) of the output bytes of frames[0 .. n) as sync() left them ([out_base, out_base + out_size): a failed frame's good
+  //    blocks), one lane or one quad of lanes per frame (zg_k_xxh64 / zg_k_xxh64q: zg_launch_xxh64 chooses), on the first stream; digest i is
+  //    frames[i]'s. quad_max_ranges: up to this many frames the launch is zg_k_xxh64q's whatever zg_launch_xxh64 would choose (0: its choice;
+  //    the calls that carry ZGPU_DEVICE_VERIFY_SEEK_TABLE hash few mid-sized frames per range, LABNOTES.md "xxh64q").
+  //  - scatter: zg_k_scatter (zg_scatter.h) copies segs[0 .. n) of the output to their destinations — device memory of the CALLER, which it
+  //    has checked (zgpu_decode_frames_device) — on the second stream, beside the hash kernel. chunk: bytes per chunk of the plan (0:
+  //    zgs::kChunkDefault). *launched: whether there was a kernel.
+  //  - the two compares, between hash_launch and hash_wait: zg_k_seeksums (zg_seeksums.h) compares the Checksum fields of the seek tables of
+  //    lanes[0 .. n) — whole entries in device memory of the CALLER, which it has checked — with the digests the hash kernel writes, for
+  //    frames[0 .. nframes) (a lane's slice; Frame::slot: the index of the frame in hash_launch's list); zg_k_idxsums (zg_idxsums.h) takes the
+  //    rows from a seek index handle's arrays instead — pairs[0 .. npairs) of 16 bytes, sums[0 .. nsums), device memory the handle owns, against
+  //    which every lane's rows are checked as well — and reads no byte of an entry. Tables on the second stream, the kernel on the first behind
+  //    the hash kernel: no wait in between. A submit may launch both; compare_wait(by_handle) writes record i of that route's lanes[i], *bytes
+  //    = what came back.
   int hash_launch(const uint32_t* frames, uint32_t n, uint32_t quad_max_ranges = 0);
   int hash_wait(uint64_t* out, uint64_t* kernel_us = nullptr);
-  // after sync(): zg_k_scatter (zg_scatter.h) copies segs[0 .. n) of the output to their destinations — device memory of the CALLER, which it
-  // has checked (zgpu_decode_frames_device) — in one launch on the engine's second stream, beside hash_launch's kernel on the first. Segments
-  // that leave the output are refused (ZGPU_E_INTERNAL) before anything is launched. chunk: bytes per chunk of the plan (0: zgs::kChunkDefault).
-  // scatter_wait() waits for the kernel; *kernel_us = its time between two HIP events, *launched = whether there was one (no bytes: none)
   int scatter_launch(const zgs::Seg* segs, uint32_t n, uint32_t chunk);
   int scatter_wait(uint64_t* kernel_us, bool* launched);
-  // between hash_launch and hash_wait: zg_k_seeksums (zg_seeksums.h) compares the Checksum fields of the seek tables of lanes[0 .. n) — whole
-  // entries in device memory of the CALLER, which it has checked — with the digests hash_launch's kernel writes, for frames[0 .. nframes) (a
-  // lane's slice; Frame::slot: the index of the frame in hash_launch's list). One launch on the engine's first stream, behind the hash kernel:
-  // no wait in between. A slice or a slot that leaves its array is refused (ZGPU_E_INTERNAL) before anything is launched. seeksums_wait()
-  // waits and writes record i of lanes[i]; *kernel_us = the kernel's time between two HIP events, *bytes = what came back
   int seeksums_launch(const zgv::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes);
-  int seeksums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
-  // the same position for zg_k_idxsums (zg_idxsums.h): the rows come from a seek index handle's arrays — pairs[0 .. npairs) of 16 bytes,
-  // sums[0 .. nsums), device memory the handle owns — and no byte of an entry is read. A lane whose rows leave those arrays, a slice or a slot
-  // that leaves its array is refused (ZGPU_E_INTERNAL) before anything is launched. A submit may launch both compare kernels
   int idxsums_launch(const zgh::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, const void* pairs, uint64_t npairs,
                      const uint32_t* sums, uint64_t nsums);
-  int idxsums_wait(zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
+  int compare_wait(bool by_handle, zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -227,29 +244,16 @@ class Batch {
   bool ran = false;
   uint32_t epoch_ = 0;                   // runs of this batch so far (the flatten's per-unit flags carry it)
   FrameState* fs = nullptr;              // streaming submit: the frame state this run reads from / writes into
-  DevBuf d_hash_;                        // hash_launch: the ranges, then the digests
-  uint32_t hash_n_ = 0;
-  hipEvent_t ev_hash_[2] = {nullptr, nullptr};
-  DevBuf d_scatter_;                     // scatter_launch: the segments, then the chunk table
-  hipEvent_t ev_scatter_[2] = {nullptr, nullptr};
-  bool scatter_on_ = false;
-  DevBuf d_seeksums_;                    // seeksums_launch: the lanes, the frame list, then the records
-  hipEvent_t ev_seeksums_[2] = {nullptr, nullptr};
-  uint32_t seeksums_n_ = 0;
-  size_t seeksums_out_ = 0;              //   where the records begin
-  DevBuf d_idxsums_;                     // idxsums_launch: the same three
-  hipEvent_t ev_idxsums_[2] = {nullptr, nullptr};
-  uint32_t idxsums_n_ = 0;
-  size_t idxsums_out_ = 0;
+  // The side passes, one SidePass each (a new one: a name here, its launch and wait; ~Batch releases them all). What the buffers hold — hash: the
+  // ranges, then the digests; scatter, the two dictfill parts (0: tables, 1: contents) and the gather: the segments, then the chunk table;
+  // the compares: the lanes, the frame list, then the records.
+  enum { kSideHash, kSideScatter, kSideTable, kSideHandle, kSideFill0, kSideFill1, kSideGather, kSideCount };
+  SidePass side_[kSideCount];
+  template <class L, class Launch> int compare_launch(SidePass& p, const L* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, Launch launch);
   std::vector<zgd::DictImage> frame_dicts_;   // set_frame_dicts
-  DevBuf d_fill_[2];                          // dictfill_launch: the segments, then the chunk table (0: tables, 1: contents)
-  hipEvent_t ev_fill_[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint32_t fill_mask_ = 0;                    //   which of the two ran
   int dictfill_launch(int part);
   std::vector<zgs::Seg> gather_segs_;    // Engine::upload with a gather: the entries' segments and their chunks (the tables travel from here)
   std::vector<zgs::Chunk> gather_chunks_;
-  DevBuf d_gather_;
-  hipEvent_t ev_gather_[2] = {nullptr, nullptr};
 };
 
 class Engine {
@@ -346,8 +350,9 @@ class Engine {
   Scratch* acquire();
   void recycle(Scratch* s);
   int fail(hipError_t e, const char* what);
-  // One lane pass on the first stream: t's buffers reserved (they and its two events are reused by a second pass of the same call), lane_bytes
-  // of lanes uploaded and the stream synchronised (the lane array is pageable), event, launch(t, stream), hipGetLastError, event, out — and
+  // One lane pass on the first stream: t's buffers reserved (they and its two events are reused by a second pass of the same call; LaneTmp is a
+  // SidePass with the two download buffers), lane_bytes of lanes uploaded and the stream synchronised (the lane array is pageable), event,
+  // launch(t, stream), hipGetLastError, event, out — and
   // extra, the second array of an emit pass, if it has a host side — downloaded, the stream synchronised, the three kPass* slots of stats added to.
   struct LaneTmp;
   struct Down { void* host = nullptr; size_t bytes = 0; };   // bytes of a device array (LaneTmp::out / extra) that come back to host

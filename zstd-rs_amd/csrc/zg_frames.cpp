@@ -446,18 +446,18 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   };
   // ZGPU_DEVICE_VERIFY_SEEK_TABLE: one zg_k_seeksums launch for the submit's entries that stand at status 0, behind the hash kernel on its stream
   // The entries whose handle holds sums go to zg_k_idxsums (zg_idxsums.h) in the same position: a submit that holds both kinds launches both
-  std::vector<uint32_t> tv, hv;   // their j: by the table, by the handle
+  std::vector<uint32_t> who[2];   // their j, by route: 0 by the table, 1 by the handle
   if (sink.table_flag) {
     std::vector<zgv::Lane> lanes;
     std::vector<zgh::Lane> hlanes;
-    std::vector<zgv::Frame> list, hlist;
+    std::vector<zgv::Frame> list[2];
     std::vector<uint32_t> slot(fo.size(), zgv::kNotHashed);
     for (size_t q = 0; q < u.cand.size(); q++) slot[u.cand[q]] = (uint32_t)q;
     for (uint32_t j = 0; j < n; j++) {
       const zgpu_entry_result& r = dres[idx[j]].r;
       if (r.status || r.nframes == 0 || !sink.compared(idx[j])) continue;
       const bool by_handle = sink.by_handle(idx[j]);
-      std::vector<zgv::Frame>& to = by_handle ? hlist : list;
+      std::vector<zgv::Frame>& to = list[by_handle];
       const uint32_t lo = (uint32_t)to.size();
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
         const FrameInfo& fi = b->info[f];
@@ -468,16 +468,15 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       if (by_handle) {
         const DeviceSink::HandleEntry& e = sink.handle_verify[idx[j]];
         hlanes.push_back(zgh::Lane{e.pair0, e.sum0, e.nrows, e.first, e.taken, lo, (uint32_t)to.size() - lo, {0, 0, 0}});
-        hv.push_back(j);
       } else {
         const DeviceSink::TableEntry& e = sink.table_verify[idx[j]];
         lanes.push_back(zgv::Lane{e.src, e.len, e.first, e.taken, lo, (uint32_t)to.size() - lo});
-        tv.push_back(j);
       }
+      who[by_handle].push_back(j);
     }
-    if (list.size() > 0xFFFFFFFFull || hlist.size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
-    if ((st = b->seeksums_launch(lanes.data(), (uint32_t)lanes.size(), list.data(), (uint32_t)list.size()))) return st;
-    if (!hlanes.empty() && (st = b->idxsums_launch(hlanes.data(), (uint32_t)hlanes.size(), hlist.data(), (uint32_t)hlist.size(), sink.handle->pairs,
+    if (list[0].size() > 0xFFFFFFFFull || list[1].size() > 0xFFFFFFFFull) return ZGPU_E_INTERNAL;
+    if ((st = b->seeksums_launch(lanes.data(), (uint32_t)lanes.size(), list[0].data(), (uint32_t)list[0].size()))) return st;
+    if (!hlanes.empty() && (st = b->idxsums_launch(hlanes.data(), (uint32_t)hlanes.size(), list[1].data(), (uint32_t)list[1].size(), sink.handle->pairs,
                                                    sink.handle->npairs, sink.handle->sums, sink.handle->nsums)))
       return st;
   }
@@ -486,20 +485,13 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   uint64_t hash_us = 0;
   if ((st = h.wait(u, &hash_us))) return st;
   sink.stats[kDevStatHashUs] += hash_us;
-  std::vector<zgv::Sums> sums(tv.size());
-  if (!tv.empty()) {
+  std::vector<zgv::Sums> sums(who[0].size() + who[1].size());   // the table's records, then the handle's
+  for (int route = 0; route < 2; route++) {   // (the same slots count both compare kernels)
+    if (who[route].empty()) continue;
     uint64_t us = 0, back = 0;
-    if ((st = b->seeksums_wait(sums.data(), &us, &back))) return st;
+    if ((st = b->compare_wait(route != 0, sums.data() + (route ? who[0].size() : 0), &us, &back))) return st;
     uint64_t* rs = k.ranges->stats;
     rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
-  }
-  if (!hv.empty()) {   // (the same slots count both compare kernels)
-    uint64_t us = 0, back = 0;
-    sums.resize(tv.size() + hv.size());
-    if ((st = b->idxsums_wait(sums.data() + tv.size(), &us, &back))) return st;
-    uint64_t* rs = k.ranges->stats;
-    rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
-    tv.insert(tv.end(), hv.begin(), hv.end());   // (the verdicts below: one list, the table's records first)
   }
   auto count_frame = [&](uint32_t f) { sink.stats[h.on_dev[f] ? kDevStatFramesHashed : kDevStatFramesNotHashed]++; };
   if (sink.verify) {
@@ -521,13 +513,15 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     }
   }
   // the table's verdict ranks last: only what still stands is looked at
-  for (size_t t = 0; t < tv.size(); t++) {
-    const uint32_t j = tv[t];
-    if (sums[t].why) { k.c->eng->last_error = sink.by_handle(idx[j]) ? kHandleChanged : kTableChanged; return ZGPU_E_INTERNAL; }
-    if (dres[idx[j]].r.status) continue;
-    if (table_verdict(dres[idx[j]], sums[t], ff[j + 1] - ff[j], k.ranges->stats))
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
-  }
+  const zgv::Sums* rec = sums.data();
+  for (int route = 0; route < 2; route++)
+    for (const uint32_t j : who[route]) {
+      const zgv::Sums& s = *rec++;
+      if (s.why) { k.c->eng->last_error = route ? kHandleChanged : kTableChanged; return ZGPU_E_INTERNAL; }
+      if (dres[idx[j]].r.status) continue;
+      if (table_verdict(dres[idx[j]], s, ff[j + 1] - ff[j], k.ranges->stats))
+        for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
+    }
   if (gated && (st = scatter())) return st;
   uint64_t us = 0;
   bool launched = false;
@@ -611,6 +605,17 @@ int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, 
   return ZGPU_OK;
 }
 
+// ZGPU_DEVICE_VERIFY_SEEK_TABLE on an entry decoded alone: its frame list and digests (zg_seeksums.h) from the frames the host hashed. A frame
+// of 2^32 bytes or more is left out, as in a submit; one longer than a nonzero hash_max_bytes is listed unhashed.
+void alone_frames(const DeviceSink& sink, const std::vector<ZgFrameSum>& frames, std::vector<zgv::Frame>* list, std::vector<uint64_t>* dig) {
+  for (const ZgFrameSum& f : frames) {
+    if (f.end - f.begin > 0xFFFFFFFFull) continue;
+    const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
+    list->push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig->size() : zgv::kNotHashed});
+    if (hashed) dig->push_back(f.calc);
+  }
+}
+
 // the device sink's form of decode_alone: into a host buffer (no larger than the entry can need), then one H2D to the caller's memory. The host
 // hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
 int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
@@ -661,6 +666,16 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   // ZGPU_DEVICE_VERIFY_SEEK_TABLE, last: zg_seeksums.h's rule over rows the host holds — the footer and rows [first, first + taken) come down (the
   // entry crossed to the host anyway), the host hashed every frame (a frame longer than a nonzero hash_max_bytes passes uncompared, as in a
   // submit). Should the frame-by-frame pass have failed (never seen), nothing is known of the frames and nothing vouches for them.
+  std::vector<zgv::Frame> list;   // the frame list and digests of either route, as a submit would build them
+  std::vector<uint64_t> dig;
+  if (ok && !d.r.status && d.r.nframes && sink.compared(i)) alone_frames(sink, frames, &list, &dig);
+  // what both routes end with: a why is the call's error, else the verdict (0, or the status the call ends with; tmp is freed then)
+  auto verdict = [&](const zgv::Sums& rec, const char* changed) -> int {
+    if (rec.why) { k.c->eng->last_error = changed; free(tmp); return ZGPU_E_INTERNAL; }
+    const uint32_t nframes = d.r.nframes;
+    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
+    return ZGPU_OK;
+  };
   if (ok && !d.r.status && d.r.nframes && sink.table(i)) {
     const DeviceSink::TableEntry& e = sink.table_verify[i];
     zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
@@ -675,20 +690,10 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
         try { rows.resize((size_t)e.taken * es); } catch (...) { free(tmp); return ZGPU_E_NOMEM; }
         if (hipMemcpy(rows.data(), (const uint8_t*)(uintptr_t)e.src + rows_off, rows.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
         k.src->stats[kSrcStatInputBytesToHost] += 9 + rows.size();
-        std::vector<zgv::Frame> list;
-        std::vector<uint64_t> dig;
-        for (const ZgFrameSum& f : frames) {
-          if (f.end - f.begin > 0xFFFFFFFFull) continue;
-          const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
-          list.push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig.size() : zgv::kNotHashed});
-          if (hashed) dig.push_back(f.calc);
-        }
         rec = zgv::sums_rows(rows.data(), es, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
       }
     } else if (summed) rec.why = zgt::kNone;
-    if (rec.why) { k.c->eng->last_error = kTableChanged; free(tmp); return ZGPU_E_INTERNAL; }
-    const uint32_t nframes = d.r.nframes;
-    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
+    if ((st = verdict(rec, kTableChanged))) return st;
   }
   // the same flag by the handle (zg_idxsums.h: sums_pairs): C of rows [first, first + taken] and their sums come down from the handle's arrays
   if (ok && !d.r.status && d.r.nframes && sink.by_handle(i)) {
@@ -705,20 +710,10 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
         if (hipMemcpy(pairs.data(), (const uint8_t*)hd.pairs + 16 * (e.pair0 + e.first), pairs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(rs.data(), hd.sums + e.sum0 + e.first, rs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
         for (size_t q = 0; q < cs.size(); q++) cs[q] = pairs[2 * q];
-        std::vector<zgv::Frame> list;
-        std::vector<uint64_t> dig;
-        for (const ZgFrameSum& f : frames) {
-          if (f.end - f.begin > 0xFFFFFFFFull) continue;
-          const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
-          list.push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig.size() : zgv::kNotHashed});
-          if (hashed) dig.push_back(f.calc);
-        }
         rec = zgh::sums_pairs(cs.data(), rs.data(), e.nrows, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
       }
     }
-    if (rec.why) { k.c->eng->last_error = kHandleChanged; free(tmp); return ZGPU_E_INTERNAL; }
-    const uint32_t nframes = d.r.nframes;
-    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
+    if ((st = verdict(rec, kHandleChanged))) return st;
   }
   if (sink.collect && ok && !d.r.status) {
     if (!summed) { k.c->eng->last_error = "zgpu_seek_index_hash_device: an entry decoded alone that could not be hashed frame by frame"; free(tmp); return ZGPU_E_INTERNAL; }   // (never seen)

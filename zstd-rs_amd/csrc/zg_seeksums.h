@@ -5,7 +5,8 @@
 // hash kernel. Written against the zx_* primitives like zg_seektab.h (whose format description, scan64 and lane64 it uses) behind two reader
 // accessors: tests/test_seeksums_cpu.py runs this source with readers that count every access outside the windows below and compares every
 // field with a model in Python (tests/seeksums.py). sums_rows / locate_rows are the same rule in plain C++ over rows the host holds: the
-// entries that are decoded alone (decode_alone_device) cross to the host anyway.
+// entries that are decoded alone (decode_alone_device) cross to the host anyway. The rule itself is written twice, once for the wave
+// (sums_step, Tally) and once for the host (sums_host): this routine and zg_idxsums.h's differ in where a row's R_k, c_k and sum come from.
 //
 // THE RULE (quoted in include/zgpu.h and DESIGN.md 4.7c). An entry whose selection is table rows [first, first + taken), R_k = C_k - C_first:
 //   - a decoded zstd frame COINCIDES with row k if it begins at selection offset R_k and is c_k bytes long;
@@ -27,10 +28,9 @@
 // a `why` — the host makes it ZGPU_E_INTERNAL with a last_error —, never a stray access. Any why: every other field of the record is 0.
 // The scan, 64 rows a step from `first`: lane l loads row first + base + l — three dwords (c, d, Checksum) at a byte address, two where the table
 // has no checksums — with the next step's loads issued in front of this step's scan; ONE 64-bit inclusive prefix sum of c on a wave-uniform
-// carry gives R_k = sum - c_k; the lane binary-searches its entry's slice for a frame that begins at R_k (loads of `begin` only), and at a
-// hit loads the frame, checks the length, loads the digest's low dword and compares. Three ballots and population counts accumulate
-// coinciding, compared and differing frames (coinciding - compared: the unhashed ones); a find-first-set of the first step that differs
-// gives first_bad, the table row (kNoRow: none). Two rows never coincide with one frame: rows that share an R_k all have c = 0 but the last.
+// carry gives R_k = sum - c_k; sums_step (the row's search and compare) and Tally (the wave's counts) below say the rest: coinciding,
+// compared and differing frames (coinciding - compared: the unhashed ones) and first_bad, the first table row that differs (kNoRow: none).
+// Two rows never coincide with one frame: rows that share an R_k all have c = 0 but the last.
 // The record, 32 bytes, leaves lane 0 as two 16-byte stores: rows (= taken), coinciding, compared, differing, first_bad, why, flags
 // (kNoChecksums), 0.
 //
@@ -94,27 +94,41 @@ inline uint32_t locate_rows(const uint8_t footer[9], uint64_t len, uint32_t firs
   *rows_off = len - size + 8 + (uint64_t)first * *es;
   return 0;
 }
-// rows: taken rows of es bytes; fr[0 .. nfr): the entry's frames; dig[0 .. ndig): their digests by slot
-inline Sums sums_rows(const uint8_t* rows, uint32_t es, uint32_t first, uint32_t taken, const Frame* fr, uint32_t nfr, const uint64_t* dig, uint32_t ndig) {
-  Sums o{taken, 0, 0, 0, kNoRow, 0, es == 12 ? 0u : kNoChecksums, 0};
-  uint64_t at = 0;
-  uint32_t q = 0;   // (begins increase with the rows' offsets: one pass over both)
+// THE RULE over rows the host holds, once (sums_rows below and zg_idxsums.h's sums_pairs hand it their rows): row(k, &at, &len, &sum) gives
+// R_k, c_k and the Checksum of row k, asked for k = 0 .. taken - 1 in that order; sums: the rows carry checksums; fr[0 .. nfr): the entry's
+// frames; dig[0 .. ndig): their digests by slot. Every row searches on its own, as the wave's lanes do: the pairs of a stale handle need not
+// increase. (Over a table's rows a merge would find the same frame: begin is strictly increasing inside a slice.)
+template <class Row> Sums sums_host(Row row, bool sums, uint32_t first, uint32_t taken, const Frame* fr, uint32_t nfr, const uint64_t* dig, uint32_t ndig) {
+  Sums o{taken, 0, 0, 0, kNoRow, 0, sums ? 0u : kNoChecksums, 0};
   for (uint32_t k = 0; k < taken; k++) {
-    uint32_t c, sum = 0;
-    memcpy(&c, rows + (size_t)k * es, 4);
-    if (es == 12) memcpy(&sum, rows + (size_t)k * es + 8, 4);
-    while (q < nfr && fr[q].begin < at) q++;
-    if (q < nfr && fr[q].begin == at && fr[q].clen == c) {
-      o.coinciding++;
-      if (es == 12 && fr[q].slot != kNotHashed) {
-        if (fr[q].slot >= ndig) return Sums{0, 0, 0, 0, 0, kList, 0, 0};
-        o.compared++;
-        if ((uint32_t)dig[fr[q].slot] != sum) { o.differing++; if (o.first_bad == kNoRow) o.first_bad = first + k; }
-      }
+    uint64_t at, len;
+    uint32_t sum;
+    row(k, &at, &len, &sum);
+    uint32_t lo = 0, hi = nfr;   // the first frame that begins at or behind R_k
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (fr[mid].begin < at) lo = mid + 1; else hi = mid;
     }
-    at += c;
+    if (lo == nfr || fr[lo].begin != at || fr[lo].clen != len) continue;
+    o.coinciding++;
+    if (!sums || fr[lo].slot == kNotHashed) continue;
+    if (fr[lo].slot >= ndig) return Sums{0, 0, 0, 0, 0, kList, 0, 0};
+    o.compared++;
+    if ((uint32_t)dig[fr[lo].slot] != sum) { o.differing++; if (o.first_bad == kNoRow) o.first_bad = first + k; }
   }
   return o;
+}
+// rows: taken rows of es bytes
+inline Sums sums_rows(const uint8_t* rows, uint32_t es, uint32_t first, uint32_t taken, const Frame* fr, uint32_t nfr, const uint64_t* dig, uint32_t ndig) {
+  uint64_t r = 0;   // R_k: the compressed sizes in front of row k
+  return sums_host([&](uint32_t k, uint64_t* at, uint64_t* len, uint32_t* sum) {
+    uint32_t c;
+    memcpy(&c, rows + (size_t)k * es, 4);
+    *sum = 0;
+    if (es == 12) memcpy(sum, rows + (size_t)k * es + 8, 4);
+    *at = r; *len = c;
+    r += c;
+  }, es == 12, first, taken, fr, nfr, dig, ndig);
 }
 
 }  // namespace zgv
@@ -124,13 +138,60 @@ inline Sums sums_rows(const uint8_t* rows, uint32_t es, uint32_t first, uint32_t
 #define ZG_SEEKSUMS_WAVE
 namespace zgv {
 
-// What the wave of one entry does; every lane calls it and every lane gets the record. R reads the entry (ld1 / ld4 / ld8 / ld12 at an offset
-// counted from the entry's first byte, any alignment; ld8 and ld12 give c, d (and the Checksum) of a row). F reads the entry's slice of the
-// frame list and the digests: begin(i), frame(i, &begin, &clen, &slot) for i < nfr, digest(slot) = the low 32 bits, for slot < ndig.
-template <class R, class F> ZX_DEV Sums seeksums_entry(const R& r, const F& f, uint64_t len, uint32_t first, uint32_t taken, uint32_t nfr, uint32_t ndig) {
-  const uint32_t lane = zx_tid() & 63u;
+// ---- what does not depend on where the rows come from (zg_idxsums.h's wave uses the same two) ------------------------------------------------
+// The step of one row: this lane holds row k = (R_k, c_k, sum_k) — in: it lies inside the selection; sums: the rows carry checksums. The lane
+// binary-searches its slice for the first frame that begins at or behind R_k, and at a hit loads the frame, checks the length (a c_k above
+// 0xFFFFFFFF matches no frame), loads the digest's low dword and compares. F: begin(i), frame(i, &begin, &clen, &slot) for i < nfr,
+// digest(slot) = the low 32 bits, for slot < ndig.
+// What comes out, four predicates (separate bools: a struct of them is packed into one VGPR, the bools stay lane masks in SGPRs): hit — a
+// frame coincides with the row; cmp — it was hashed and is compared; diff — it differs; oob — its slot lies at or behind the digest count.
+template <class F> ZX_DEV void sums_step(const F& f, uint64_t rk, uint64_t c, uint32_t s, bool in, bool sums, uint32_t nfr, uint32_t ndig,
+                                         bool& hit, bool& cmp, bool& diff, bool& oob) {
+  hit = cmp = diff = oob = false;
+  if (in && nfr) {
+    uint32_t lo = 0, hi = nfr;
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (f.begin(mid) < rk) lo = mid + 1; else hi = mid;
+    }
+    if (lo < nfr) {
+      uint64_t fb;
+      uint32_t fc, slot;
+      f.frame(lo, &fb, &fc, &slot);
+      hit = fb == rk && (uint64_t)fc == c;
+      if (hit && sums && slot != kNotHashed) {
+        oob = slot >= ndig;
+        cmp = !oob;
+        if (cmp) diff = f.digest(slot) != s;
+      }
+    }
+  }
+}
+// The tally of a wave: tally_add takes every lane's four predicates of the 64 rows from row0 (= first + base) — three ballots and population counts, a
+// find-first-set of the first step that differs —, tally_record writes them into an all-zero record: kList alone if a slot left the digests.
+struct Tally { uint32_t coinciding = 0, compared = 0, differing = 0, first_bad = kNoRow; bool bad_list = false; };
+ZX_DEV void tally_add(Tally& a, bool hit, bool cmp, bool diff, bool oob, uint32_t row0) {
+  const unsigned long long mh = zx_ballot(hit), mc = zx_ballot(cmp), md = zx_ballot(diff);
+  a.coinciding += (uint32_t)__builtin_popcountll(mh); a.compared += (uint32_t)__builtin_popcountll(mc); a.differing += (uint32_t)__builtin_popcountll(md);
+  if (md && a.first_bad == kNoRow) a.first_bad = row0 + (uint32_t)__builtin_ctzll(md);
+  if (zx_ballot(oob)) a.bad_list = true;
+}
+ZX_DEV Sums sums_zero() {
   Sums o;
   o.rows = o.coinciding = o.compared = o.differing = o.first_bad = o.why = o.flags = o.pad = 0;
+  return o;
+}
+ZX_DEV void tally_record(const Tally& a, uint32_t taken, uint32_t flags, Sums& o) {
+  if (a.bad_list) o.why = kList;
+  else { o.rows = taken; o.coinciding = a.coinciding; o.compared = a.compared; o.differing = a.differing; o.first_bad = a.first_bad; o.flags = flags; }
+}
+
+// What the wave of one entry does; every lane calls it and every lane gets the record. R reads the entry (ld1 / ld4 / ld8 / ld12 at an offset
+// counted from the entry's first byte, any alignment; ld8 and ld12 give c, d (and the Checksum) of a row). F reads the entry's slice of the
+// frame list and the digests (sums_step).
+template <class R, class F> ZX_DEV Sums seeksums_entry(const R& r, const F& f, uint64_t len, uint32_t first, uint32_t taken, uint32_t nfr, uint32_t ndig) {
+  const uint32_t lane = zx_tid() & 63u;
+  Sums o = sums_zero();
   if (!taken) return o;
   uint32_t why = 0, nf = 0, es = 8;
   uint64_t tab = 0;
@@ -150,12 +211,13 @@ template <class R, class F> ZX_DEV Sums seeksums_entry(const R& r, const F& f, u
       else if ((uint64_t)first + taken > nf) why = kRows;
     }
   }
+  o.why = why;
   if (!why) {
     const bool sums = es == 12;
     const uint64_t ent = tab + 8 + (uint64_t)first * es;
     uint64_t carry = 0;                        // the compressed sizes in front of this step
-    uint32_t c = 0, d = 0, s = 0, coinciding = 0, compared = 0, differing = 0, first_bad = kNoRow;
-    bool bad_list = false;
+    uint32_t c = 0, d = 0, s = 0;
+    Tally t;
     if (lane < taken) { if (sums) r.ld12(ent + (uint64_t)lane * es, &c, &d, &s); else r.ld8(ent + (uint64_t)lane * es, &c, &d); }
     for (uint32_t base = 0; base < taken; base += 64) {
       uint32_t nc = 0, nd = 0, ns = 0;
@@ -164,41 +226,16 @@ template <class R, class F> ZX_DEV Sums seeksums_entry(const R& r, const F& f, u
         if (sums) r.ld12(at, &nc, &nd, &ns); else r.ld8(at, &nc, &nd);
       }
       // (a lane behind the selection holds c = 0: lane 63 always holds the sum up to the end of the step)
-      const uint64_t ce = carry + zgt::scan64(c, lane), rk = ce - c;
-      bool hit = false, cmp = false, diff = false, oob = false;
-      if (base + lane < taken && nfr) {
-        uint32_t lo = 0, hi = nfr;             // the first frame that begins at or behind R_k
-        while (lo < hi) {
-          const uint32_t mid = lo + ((hi - lo) >> 1);
-          if (f.begin(mid) < rk) lo = mid + 1; else hi = mid;
-        }
-        if (lo < nfr) {
-          uint64_t fb;
-          uint32_t fc, slot;
-          f.frame(lo, &fb, &fc, &slot);
-          hit = fb == rk && fc == c;
-          if (hit && sums && slot != kNotHashed) {
-            oob = slot >= ndig;
-            cmp = !oob;
-            if (cmp) diff = f.digest(slot) != s;
-          }
-        }
-      }
-      const unsigned long long mh = zx_ballot(hit), mc = zx_ballot(cmp), md = zx_ballot(diff);
-      coinciding += (uint32_t)__builtin_popcountll(mh); compared += (uint32_t)__builtin_popcountll(mc); differing += (uint32_t)__builtin_popcountll(md);
-      if (md && first_bad == kNoRow) first_bad = first + base + (uint32_t)__builtin_ctzll(md);
-      if (zx_ballot(oob)) bad_list = true;
+      const uint64_t ce = carry + zgt::scan64(c, lane);
+      bool hit, cmp, diff, oob;
+      sums_step(f, ce - c, c, s, base + lane < taken, sums, nfr, ndig, hit, cmp, diff, oob);
+      tally_add(t, hit, cmp, diff, oob, first + base);
       carry = zgt::lane64(ce, 63);
       c = nc; d = nd; s = ns;
     }
     (void)d;
-    if (bad_list) why = kList;
-    else {
-      o.rows = taken; o.coinciding = coinciding; o.compared = compared; o.differing = differing; o.first_bad = first_bad;
-      o.flags = sums ? 0u : kNoChecksums;
-    }
+    tally_record(t, taken, sums ? 0u : kNoChecksums, o);
   }
-  o.why = why;
   return o;
 }
 
