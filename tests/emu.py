@@ -23,6 +23,7 @@ def lib():
         L.zgemu_decode2.restype = C.c_void_p
         L.zgemu_decode2.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_int]
         L.zgemu_free.argtypes = [C.c_void_p]
+        L.zgemu_set_fill.argtypes = [C.c_int]          # (tests/emu/zg_emu_fill.h: process-wide; whoever sets it puts it back)
         L.zgemu_parse_status.argtypes = [C.c_void_p]
         L.zgemu_num_frames.argtypes = [C.c_void_p]
         L.zgemu_num_blocks.argtypes = [C.c_void_p]
@@ -129,10 +130,10 @@ class Plan:
             L.zgemu_free(h)
 
 
-def decode_all_verdict(m, max_window=128 << 20):
+def decode_all_verdict(m, max_window=128 << 20, batch=None):
     """zgpu_decode_all's verdict rule on the CPU harness: the first failing frame in stream order (zg_k_exact's verdict where it has
     one), else the error of the host walk — what lies in front of the point where the walk stops is decoded first (zg_capi.cpp)"""
-    e = EmuBatch(m, max_window=max_window)
+    e = batch or EmuBatch(m, max_window=max_window)       # (batch: m decoded already)
     if e.nframes == 0 or e.nblocks == 0:
         return e.parse_status
     ex = e.exact(drain_rule=1)

@@ -246,7 +246,7 @@ static void k_scan(EmuBatch& e) {  // serial statement of zg_k_scan / zg_k_scanf
     e.fout[f] = fo;
     base += pos;
   }
-  e.dst.assign(base + 64, 0);
+  e.dst.assign(base + 64, emufill::byte(0));
 }
 
 static void k_exec(EmuBatch& e) {  // zg_k_lit + zg_k_lz, serial
@@ -303,21 +303,24 @@ void* zgemu_decode3(const uint8_t* src, size_t len, uint64_t max_window, int use
   e->parse_status = walk(e->src, len, max_window, &e->bb);
   e->bb.finish();
   const uint32_t nb = (uint32_t)e->bb.blocks.size(), nf = (uint32_t)e->bb.frames.size();
-  e->aux.resize(nb + 1); e->slot_log.assign((size_t)e->bb.nslots() * 4, 0);
-  e->fse.assign((size_t)e->bb.nslots() * ZG_FSE_SLOT_U32, 0xDEADBEEF);
-  e->huf.assign((size_t)(e->bb.nhuf_slots + 1) * ZG_HUF_SLOT_U16, 0xFFFF);
+  e->aux.resize(nb + 1); emufill::records(e->aux); e->slot_log.assign((size_t)e->bb.nslots() * 4, 0);
+  e->fse.assign((size_t)e->bb.nslots() * ZG_FSE_SLOT_U32, emufill::word(0xDEADBEEF));
+  e->huf.assign((size_t)(e->bb.nhuf_slots + 1) * ZG_HUF_SLOT_U16, emufill::half(0xFFFF));
   e->hufmax.assign(e->bb.nhuf_slots + 1, 0);
   e->status.assign(nb + 1, 0);
   e->fse_status.assign(nb + 1, 0);
-  e->lit.assign(e->bb.lit_bytes + 64, 0xEE);
+  e->lit.assign(e->bb.lit_bytes + 64, emufill::byte(0xEE));
   e->seq.resize(e->bb.seq_count + 1);
   e->seqout.resize(nb + 1); e->pos.resize(nb + 1); e->fout.resize(nf + 1);
+  emufill::records(e->seq); emufill::records(e->seqout); emufill::records(e->pos); emufill::records(e->fout);
   k_tables(*e); k_huf(*e); k_seq(*e); k_scan(*e); k_exec(*e);
   return e;
 }
 void* zgemu_decode2(const uint8_t* src, size_t len, uint64_t max_window, int use_fast) { return zgemu_decode3(src, len, max_window, use_fast, 0, 0); }
 void* zgemu_decode(const uint8_t* src, size_t len, uint64_t max_window) { return zgemu_decode2(src, len, max_window, 1); }
 void zgemu_free(void* h) { delete (EmuBatch*)h; }
+// what memory no stage has written holds from now on: a byte, or < 0 for every site's own value (zg_emu_fill.h); returns what it was
+int zgemu_set_fill(int v) { const int was = emufill::g_fill; emufill::set(v); return was; }
 int zgemu_parse_status(void* h) { return ((EmuBatch*)h)->parse_status; }
 uint32_t zgemu_num_frames(void* h) { return (uint32_t)((EmuBatch*)h)->bb.frames.size(); }
 uint32_t zgemu_num_blocks(void* h) { return (uint32_t)((EmuBatch*)h)->bb.blocks.size(); }

@@ -1,9 +1,10 @@
 // zg_emu_batch.h — TEST-ONLY: the state of one submit in the CPU harness (zg_emu.cpp fills it stage by stage, in the
-// order of the HIP pipeline; zg_emu_flat.cpp runs the flatten kernel's source on it).
+// order of the HIP pipeline; zg_emu_flat.cpp runs the flatten kernel's source on it). What no stage has written holds the fill of zg_emu_fill.h.
 #pragma once
 #include <stdint.h>
 #include <vector>
 #include "zg_emu_serial.h"
+#include "zg_emu_fill.h"
 #include "../../zstd-rs_amd/csrc/zg_host_parse.h"
 
 struct EmuBatch {

@@ -22,6 +22,7 @@ int zgemu_exact(void* h, uint32_t drain_rule, uint64_t dict_len, uint64_t prior_
   const zg::BatchBuilder& bb = e->bb;
   const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size();
   std::vector<ZgSeq> seqs(e->seq.size() + 2);
+  emufill::records(seqs);
   for (size_t i = 0; i < e->seq.size(); i++) {
     const EmuSeq& q = e->seq[i];
     seqs[i].of = q.of; seqs[i].w1 = ZG_SEQ_W1(q.mdst, q.ml); seqs[i].w2 = ZG_SEQ_W2(q.lit_start, q.ml);

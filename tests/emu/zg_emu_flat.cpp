@@ -35,7 +35,7 @@ extern "C" {
 // with a nonzero scratch word copies from that many bytes back): direct units through zg_flat4_unit, pointer-mode units through
 // zg_flat1_unit (zg_flat1.h). shape as for zgemu_flat4.
 //   dst_out   [total output bytes] the plaintext after the sweep
-//   og_out    [total output bytes] the flatten scratch (effective offsets; untouched words: 0xEEEEEEEE)
+//   og_out    [total output bytes] the flatten scratch (effective offsets; untouched words: 0xEEEEEEEE, or the fill of zg_emu_fill.h)
 //   unit_mode [units] 0 pointer, 1 no sequences, 2 direct; may be null
 // Frames marked sparse (no scratch): zg_flat1_unit places their literal runs, zg_sparse_frame (zg_inorder.h, the body of zg_k_sparse) copies their matches in order.
 int zgemu_flatten(void* h, int shape, uint8_t* dst_out, uint32_t* og_out, uint32_t* unit_mode) {
@@ -44,15 +44,17 @@ int zgemu_flatten(void* h, int shape, uint8_t* dst_out, uint32_t* og_out, uint32
   const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size(), nu = (uint32_t)bb.units.size();
   uint64_t total = 0;
   for (uint32_t f = 0; f < nf; f++) total = e->fout[f].out_base + e->fout[f].out_size > total ? e->fout[f].out_base + e->fout[f].out_size : total;
-  std::vector<uint8_t> dst(256 + total + 64, 0xAA), lit(64 + e->lit.size() + 64, 0);
-  std::vector<uint32_t> og(total + 64, 0xEEEEEEEEu);
+  std::vector<uint8_t> dst(256 + total + 64, emufill::byte(0xAA)), lit(64 + e->lit.size() + 64, emufill::byte(0));
+  std::vector<uint32_t> og(total + 64, emufill::word(0xEEEEEEEEu));
   memcpy(lit.data() + 64, e->lit.data(), e->lit.size());
   std::vector<ZgSeq> seqs(e->seq.size() + 2);
+  emufill::records(seqs);
   for (size_t i = 0; i < e->seq.size(); i++) {
     const EmuSeq& q = e->seq[i];
     seqs[i].of = q.of; seqs[i].w1 = ZG_SEQ_W1(q.mdst, q.ml); seqs[i].w2 = ZG_SEQ_W2(q.lit_start, q.ml);
   }
   std::vector<ZgUnitInfo> uinfo(nu + 1);
+  emufill::records(uinfo);
   std::vector<ZgFrameOut> fout(e->fout.begin(), e->fout.begin() + nf);
   for (ZgFrameOut& fo : fout) { fo.fast = 1; fo.err_packed = 0xFFFFFFFFu; fo.og_base = fo.out_base; }
   uint32_t totals[4] = {0, 0, 0, 0};
@@ -130,14 +132,16 @@ int zgemu_flat4(void* h, int shape, uint8_t* dst_out, uint32_t* unit_mode) {
   uint64_t total = 0;
   for (uint32_t f = 0; f < nf; f++) total = e->fout[f].out_base + e->fout[f].out_size > total ? e->fout[f].out_base + e->fout[f].out_size : total;
   // device-side buffers as the engine lays them out: front pads in front of the output and the literals
-  std::vector<uint8_t> dst(256 + total + 64, 0xAA), lit(64 + e->lit.size() + 64, 0);
+  std::vector<uint8_t> dst(256 + total + 64, emufill::byte(0xAA)), lit(64 + e->lit.size() + 64, emufill::byte(0));
   memcpy(lit.data() + 64, e->lit.data(), e->lit.size());
   std::vector<ZgSeq> seqs(e->seq.size() + 2);
+  emufill::records(seqs);
   for (size_t i = 0; i < e->seq.size(); i++) {
     const EmuSeq& q = e->seq[i];
     seqs[i].of = q.of; seqs[i].w1 = ZG_SEQ_W1(q.mdst, q.ml); seqs[i].w2 = ZG_SEQ_W2(q.lit_start, q.ml);
   }
   std::vector<ZgUnitInfo> uinfo(nu + 1);
+  emufill::records(uinfo);
   std::vector<ZgFrameOut> fout(e->fout.begin(), e->fout.begin() + nf);
   for (ZgFrameOut& fo : fout) { fo.fast = 1; fo.err_packed = 0xFFFFFFFFu; fo.og_base = fo.out_base; }
   uint32_t totals[4] = {0, 0, 0, 0};

@@ -19,7 +19,7 @@ uint64_t zgemu_block_out_base(void* h, uint32_t b) { EmuBatch* e = (EmuBatch*)h;
 
 // h: an EmuBatch after zgemu_decode* (e->lit: the serial model's literals, e->dst: its plaintext, e->status: its verdicts).
 //   lit_out     [bb.lit_bytes] the arena zg_k_huf's source fills
-//   dst_out     [total output] only with direct != 0: what it wrote straight into the output (0xAA elsewhere)
+//   dst_out     [total output] only with direct != 0: what it wrote straight into the output (0xAA, or the fill of zg_emu_fill.h, elsewhere)
 //   lit_status  [blocks] rank << 8 | status, as the kernel leaves it (zg_k_merge strips the rank)
 //   lit_counts  [4 * blocks]
 // Blocks whose tables or headers the earlier stages rejected are skipped like on the GPU (tab_status).
@@ -29,8 +29,8 @@ int zgemu_huf(void* h, int direct, uint8_t* lit_out, uint8_t* dst_out, uint32_t*
   const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size();
   uint64_t total = 0;
   for (uint32_t f = 0; f < nf; f++) total = e->fout[f].out_base + e->fout[f].out_size > total ? e->fout[f].out_base + e->fout[f].out_size : total;
-  std::vector<uint8_t> dst(256 + total + 64, 0xAA), lit(64 + bb.lit_bytes + 128, 0x55);
-  std::vector<uint32_t> tab_status(nb + 1, 0), lstat(nb + 1, 0), lcnt(4 * (size_t)nb + 4, 0);
+  std::vector<uint8_t> dst(256 + total + 64, emufill::byte(0xAA)), lit(64 + bb.lit_bytes + 128, emufill::byte(0x55));
+  std::vector<uint32_t> tab_status(nb + 1, 0), lstat(nb + 1, 0), lcnt(4 * (size_t)nb + 4, emufill::word(0));   // (lit_counts: no reset on the GPU either)
   // what zg_k_tables leaves: a tree description that failed keeps its block out of zg_k_huf. The harness folds every stage's
   // verdict into one word per block; statuses of the table stage are the HUF_TABLE / FSE ones, found before any stream is read
   for (uint32_t b = 0; b < nb; b++) {

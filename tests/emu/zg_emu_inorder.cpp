@@ -25,10 +25,11 @@ struct Dev {
     const zg::BatchBuilder& bb = e->bb;
     const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size();
     for (uint32_t f = 0; f < nf; f++) total = e->fout[f].out_base + e->fout[f].out_size > total ? e->fout[f].out_base + e->fout[f].out_size : total;
-    dst.assign(256 + total + room_behind + 64, 0xAA);
-    lit.assign(64 + e->lit.size() + 64, 0);
+    dst.assign(256 + total + room_behind + 64, emufill::byte(0xAA));
+    lit.assign(64 + e->lit.size() + 64, emufill::byte(0));
     memcpy(lit.data() + 64, e->lit.data(), e->lit.size());
     seqs.resize(e->seq.size() + 2);
+    emufill::records(seqs);
     for (size_t i = 0; i < e->seq.size(); i++) {
       const EmuSeq& q = e->seq[i];
       seqs[i].of = q.of; seqs[i].w1 = ZG_SEQ_W1(q.mdst, q.ml); seqs[i].w2 = ZG_SEQ_W2(q.lit_start, q.ml);

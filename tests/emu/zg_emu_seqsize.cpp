@@ -14,6 +14,7 @@
 #include "../../zstd-rs_amd/csrc/zg_types.h"
 #include "zg_simt.h"
 #include "zg_emu_serial.h"
+#include "zg_emu_fill.h"
 #include "../../zstd-rs_amd/csrc/zg_host_parse.h"
 
 // ---- the primitives zg_simt.h does not have ------------------------------------------------------------------------------------------------
@@ -116,7 +117,7 @@ struct SzBlock { uint32_t frame, block, nseq, regen, front_status, status, sum_l
 // number of blocks with sequences (at most cap are written), or -(status) if the host's walk refuses the input; counts: the reader's four.
 extern "C" int32_t sz_run(const uint8_t* src, uint64_t len, uint32_t shift, uint32_t cap, SzBlock* out, uint64_t* counts) {
   BatchBuilder bb;
-  std::vector<uint8_t> store(len + 64 + 16 + 64 + 16, 0x5A);   // (the padding holds no zeros: a dword served from it would change a sum)
+  std::vector<uint8_t> store(len + 64 + 16 + 64 + 16, emufill::byte(0x5A));   // (the padding holds no zeros: a dword served from it would change a sum)
   uint8_t* base = store.data() + ((16 - ((uintptr_t)store.data() & 15u)) & 15u) + 64 + (shift & 3u);
   memcpy(base, src, len);
   const int wst = walk(base, len, &bb);
@@ -124,12 +125,12 @@ extern "C" int32_t sz_run(const uint8_t* src, uint64_t len, uint32_t shift, uint
   bb.finish();
   const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size();
   const uint32_t nslots = nb + 1 + nf;
-  std::vector<uint32_t> fse((size_t)nslots * ZG_FSE_SLOT_U32, 0), status(nb + 4, 0), raw(bb.seq_count + 8, 0);
+  std::vector<uint32_t> fse((size_t)nslots * ZG_FSE_SLOT_U32, emufill::word(0)), status(nb + 4, 0), raw(bb.seq_count + 8, emufill::word(0));
   std::vector<uint8_t> slot_log((size_t)nslots * 4, 0);
   std::vector<ZgBlockAux> aux(nb + 1);
   std::vector<ZgBlockSeqOut> seqout(nb + 1);
-  memset(aux.data(), 0, aux.size() * sizeof(ZgBlockAux));
-  memset(seqout.data(), 0, seqout.size() * sizeof(ZgBlockSeqOut));
+  memset(aux.data(), emufill::byte(0), aux.size() * sizeof(ZgBlockAux));         // (every field the kernel reads is written below: seq_bits_off for every block, log[] where a table is built)
+  memset(seqout.data(), emufill::byte(0), seqout.size() * sizeof(ZgBlockSeqOut));   // (pad: written below for every block that runs)
   int16_t probs[256]; uint16_t counter[256];
   {   // the predefined tables (zg_k_ftab; tests/emu/zg_emu.cpp: k_tables)
     uint32_t* slot = fse.data() + (size_t)nb * ZG_FSE_SLOT_U32;
@@ -204,7 +205,7 @@ extern "C" int32_t sz_run(const uint8_t* src, uint64_t len, uint32_t shift, uint
     // the dwords that hold the bitstream: what zg_k_seqpost's load may touch of the input (its third dword may lie behind them, in the engine's padding)
     g_lo = (uintptr_t)bs & ~(uintptr_t)3;
     g_hi = ((uintptr_t)bs + nbytes + 3) & ~(uintptr_t)3;
-    memset(&lds, 0xEE, sizeof lds);
+    memset(&lds, emufill::byte(0xEE), sizeof lds);
     simt::run(ZG_SZ_T, [&]() { zg_seqsize_block(d, b, lds); });
     if ((uint32_t)n < cap) {
       SzBlock& o = out[n];
@@ -220,3 +221,4 @@ extern "C" int32_t sz_run(const uint8_t* src, uint64_t len, uint32_t shift, uint
   return n;
 }
 extern "C" uint32_t sz_per_thread(void) { return ZG_SZ_S; }
+extern "C" int sz_set_fill(int v) { const int was = emufill::g_fill; emufill::set(v); return was; }   // (zg_emu_fill.h)

@@ -111,6 +111,51 @@ def dev_context(monkeypatch, env):
         c.close()
 
 
+POISONS = (0x00, 0xA5, 0xFF)
+
+
+@contextlib.contextmanager
+def poisoned_context(monkeypatch, poison, env=None):
+    """a fresh context of the development build under ZGPU_POISON=poison (and the switches of env): every byte of device memory the
+    design does not define when a submit starts holds that value (zstd-rs_amd/csrc/zg_engine.h: Poison). A context of its own per
+    poison: the fill covers a buffer's whole capacity, which an earlier submit of the same context may have grown"""
+    with dev_context(monkeypatch, dict(env or {}, ZGPU_POISON=str(poison))) as c:
+        assert c.tuning()["poison"] == poison
+        yield c
+
+
+def oracle_verdict(z):
+    """(status, failing block, bytes of the good blocks) of the frame at the start of z, from the oracle block by block: nothing is
+    drained, so what its decode buffer holds after the last call that succeeded is the good blocks' bytes. A valid frame: (0, its
+    number of blocks, its plaintext)"""
+    d = oracle.FrameDecoder()
+    d.set_max_window_size(1 << 31)
+    st, pos, _, _ = d.init(z)
+    assert st == 0
+    good = 0
+    while True:
+        st, used, fin = d.decode_blocks(z[pos:], oracle.STRAT_UPTO_BLOCKS, 1)
+        if st:
+            return st, d.blocks_decoded(), d.held()[:good]
+        pos += used
+        good = len(d.held())
+        if fin:
+            return 0, d.blocks_decoded(), d.held()
+
+
+def frame_alone(c, z):
+    """the frame at the start of z as a submit of its own: (status, failing block, out_size, bytes) as sync() leaves them, and behind
+    them the status of the host's walk (not 0: the host found the error, and a submit ends with such a frame)"""
+    b = c.prepare(z)
+    try:
+        b.run()
+        b.sync()
+        fi = b.frame_info(0)
+        return fi.status, fi.bad_block, fi.out_size, (b.read(fi.out_base, fi.out_size) if fi.out_size else b""), b.parse_status
+    finally:
+        b.close()
+
+
 def submit(c, frames, oblocks=None, extra=(), lit_direct=None):
     """frames in one submit, `extra` (more valid frames) behind them: parse_status, nframes, bad_status, total_out, every frame's
     out_size and bytes (from one read of the whole output and from b.frame_bytes); with oblocks (name -> the oracle's records, or a
@@ -300,11 +345,13 @@ def lockstep(c, name, z, k=1, header=None, decoder=None, oracle_decoder=oracle.F
 
 def check_on_harness(name, z, plain, status, oblocks=blockcheck.oracle_blocks):
     """one frame through the CPU harness: an invalid one (plain None) gets status[name] from decode_all_verdict; a valid one decodes to
-    its plaintext, agrees block by block with the oracle's records oblocks(z), and zg_k_exact's source (drain rule 1) accepts it"""
+    its plaintext, agrees block by block with the oracle's records oblocks(z), and zg_k_exact's source (drain rule 1) accepts it.
+    Returns the emu.EmuBatch it decoded (tests/test_poison_cpu.py compares what it left under another fill)"""
     import emu
     if plain is None:
-        assert emu.decode_all_verdict(z) == status[name], name
-        return
+        e = emu.EmuBatch(z, max_window=1 << 31)
+        assert emu.decode_all_verdict(z, batch=e) == status[name], name
+        return e
     e = emu.EmuBatch(z, max_window=1 << 31)
     assert e.parse_status == 0 and e.nframes == 1, name
     out, st = e.frame_bytes(0)
@@ -314,3 +361,4 @@ def check_on_harness(name, z, plain, status, oblocks=blockcheck.oracle_blocks):
     blockcheck.check_frame(e, 0, ob, name)
     ex = e.exact(drain_rule=1)
     assert ex[0][0] == 0, (name, ex)
+    return e

@@ -210,7 +210,9 @@ def test_two_dictionaries_and_an_unregistered_id(corpus):
 
 
 # 6 ---------------------------------------------------------------------------------------------------------------------------------
-def test_hand_built_edges_of_the_reach(ctx, corpus):
+def reach_cases(corpus):
+    """(names of the hand-built frames, [(pieces, cap)], wants): the dictframes cases at the edges of the reach and the corpus frames whose
+    first block's tables can only come from the dictionary (tests/test_gpu_poison.py runs them under other memory histories)"""
     raw, frames, sizes = corpus
     did = int.from_bytes(raw[4:8], "little")
     # the content's length, from the oracle: the longest reach from the frame's first byte that still decodes
@@ -240,7 +242,11 @@ def test_hand_built_edges_of_the_reach(ctx, corpus):
     assert treeless and repeat
     items = [([z], 1 << 12) for z in built.values()]
     items += [([frames[k]], sizes[k]) for k in treeless[:4] + repeat[:4]]
-    wants = [Want(p, cap, [raw]) for p, cap in items]
+    return list(built), items, [Want(p, cap, [raw]) for p, cap in items]
+
+
+def test_hand_built_edges_of_the_reach(ctx, corpus):
+    built, items, wants = reach_cases(corpus)
     by_name = dict(zip(built, wants))
     # (repeat code 3 with a literal length of 0 is history[0] - 1: with this dictionary's history the oracle answers 0 or ZeroOffset — it decides)
     assert all(by_name[n].status == 0 for n in built if not n.startswith("one_byte_in_front") and n != "repeat_code_3"), {n: w.status for n, w in by_name.items()}

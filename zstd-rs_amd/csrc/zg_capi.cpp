@@ -238,8 +238,16 @@ int zgpu_debug_calibrate(zgpu_ctx* c, uint64_t bytes) {
 int zgpu_debug_tuning(const zgpu_ctx* c, uint32_t* out, int n) {
   if (!c || !out || n <= 0) return 0;
   const Tuning& t = c->eng->tuning();
-  const uint32_t v[8] = {t.dev_build ? 1u : 0u, t.unit_blocks, (uint32_t)t.seq_packed, (uint32_t)t.flat4, t.ramp_percent, t.sweep_w, (uint32_t)t.flat_shape, t.force_inorder ? 1u : 0u};
-  const int k = n < 8 ? n : 8;
+  // ... and ZGPU_POISON (0xFFFFFFFF: not set), the bytes filled since the last submit was prepared and the capacity of that submit's Scratch, each as low and high word
+  const uint64_t pb = zg::Poison::bytes();
+#ifdef ZG_DEV_SWITCHES
+  const uint64_t sc = zg::Poison::scratch_cap;
+#else
+  const uint64_t sc = 0;
+#endif
+  const uint32_t v[13] = {t.dev_build ? 1u : 0u, t.unit_blocks, (uint32_t)t.seq_packed, (uint32_t)t.flat4, t.ramp_percent, t.sweep_w, (uint32_t)t.flat_shape, t.force_inorder ? 1u : 0u,
+                          (uint32_t)t.poison, (uint32_t)pb, (uint32_t)(pb >> 32), (uint32_t)sc, (uint32_t)(sc >> 32)};
+  const int k = n < 13 ? n : 13;
   for (int i = 0; i < k; i++) out[i] = v[i];
   return k;
 }

@@ -12,6 +12,24 @@ namespace zg {
     if (e_ != hipSuccess) return eng->fail(e_, #call); \
   } while (0)
 
+#ifdef ZG_DEV_SWITCHES
+static int g_poison = -1;
+static uint64_t g_poisoned = 0;          // (submits are prepared by one thread at a time per process in the tests that read it: a diagnostic)
+uint64_t Poison::scratch_cap = 0;
+int Poison::value() { return g_poison; }
+void Poison::set(int v) { g_poison = v; }
+void Poison::fill(void* p, size_t n, hipStream_t s) {
+  if (g_poison < 0 || !p || !n) return;
+  if (hipMemsetAsync(p, g_poison, n, s) == hipSuccess) g_poisoned += n;
+}
+void Poison::fill_now(void* p, size_t n) {
+  if (g_poison < 0 || !p || !n) return;
+  if (hipMemset(p, g_poison, n) == hipSuccess && hipDeviceSynchronize() == hipSuccess) g_poisoned += n;
+}
+void Poison::begin_submit() { g_poisoned = 0; }
+uint64_t Poison::bytes() { return g_poisoned; }
+#endif
+
 int DevBuf::reserve(size_t n, bool keep, hipStream_t s) {
   if (n <= cap && p) return 0;
   size_t ncap = n < 256 ? 256 : n;
@@ -40,6 +58,7 @@ void DevBuf::release() {
 int SidePass::reserve(size_t bytes) {
   const int st = buf.reserve(bytes);
   if (st) return st;
+  Poison::fill_now(buf.p, buf.cap);   // (every site uploads and launches behind its reserve, and has waited for the pass in front)
   for (hipEvent_t& e : ev) if (!e && hipEventCreate(&e) != hipSuccess) return ZG_HIP_ERROR;
   return 0;
 }
@@ -86,11 +105,14 @@ void Scratch::release_but_output() {
   DevBuf* all[] = {&d_src, &d_aux, &d_fparsed, &d_slot_log, &d_fse, &d_huf, &d_hufmax, &d_lit, &d_seq, &d_og, &d_raw};
   for (DevBuf* b : all) b->release();
 }
-void Scratch::release() {
+template <class F> void Scratch::each_buf(F f) {
   DevBuf* all[] = {&d_src, &d_blocks, &d_frames, &d_aux, &d_fparsed, &d_slot_log, &d_fse, &d_huf, &d_hufmax, &d_status, &d_lit, &d_seq, &d_seqout, &d_pos,
                    &d_frameout, &d_dst, &d_seqblocks, &d_hufitems, &d_hufgroups, &d_totals, &d_og, &d_units, &d_unitinfo, &d_stepunits, &d_swdesc,
                    &d_dbg, &d_raw, &d_unitlist};
-  for (DevBuf* b : all) b->release();
+  for (DevBuf* b : all) f(*b);
+}
+void Scratch::release() {
+  each_buf([](DevBuf& b) { b.release(); });
   for (auto& e : ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
   for (auto& e : ev_huf)
@@ -144,6 +166,7 @@ Tuning Tuning::from_env() {
   { const char* e = getenv("ZGPU_FRAMES_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.frames_submit_bytes = (uint64_t)atoll(e); }
   { const char* e = getenv("ZGPU_MEASURE_SUBMIT_BYTES"); if (e && atoll(e) > 0) t.measure_submit_bytes = (uint64_t)atoll(e); }
   num("ZGPU_SCATTER_CHUNK", &t.scatter_chunk, true);
+  { const char* e = getenv("ZGPU_POISON"); if (e && e[0] && atoi(e) >= 0 && atoi(e) <= 255) t.poison = atoi(e); }
   { const char* e = getenv("ZGPU_HASH_DEVICE_MAX"); if (e && atoll(e) >= 0) { t.hash_device_max_set = true; t.hash_device_max = (uint64_t)atoll(e); } }
 #endif
   return t;
@@ -161,6 +184,9 @@ int Engine::create(int device, Engine** out) {
     e->tn_ = Tuning::from_env();                        // the only place the engine looks at the environment
     e->flat_shape_ = e->tn_.flat_shape;
     e->no_presize_ = e->tn_.no_presize;
+#ifdef ZG_DEV_SWITCHES
+    Poison::set(e->tn_.poison);
+#endif
   }
   // two streams: the sequences chain is the critical one (its kernels last as long as one block's serial chain), so its
   // workgroups are dispatched first; the literals chain fills what is left
@@ -225,6 +251,7 @@ int FrameState::make_room(uint64_t extra, uint64_t keep, hipStream_t s) {
     if (keep && have - keep >= keep) e = hipMemcpyAsync(dst, src, keep, hipMemcpyDeviceToDevice, s);   // the ranges do not overlap
     else if (keep) {
       if (d_tmp.reserve(keep)) return ZG_NOMEM;
+      Poison::fill(d_tmp.p, d_tmp.cap, s);
       e = hipMemcpyAsync(d_tmp.p, src, keep, hipMemcpyDeviceToDevice, s);
       if (e == hipSuccess) e = hipMemcpyAsync(dst, d_tmp.p, keep, hipMemcpyDeviceToDevice, s);
     }
@@ -243,6 +270,7 @@ int FrameState::make_room(uint64_t extra, uint64_t keep, hipStream_t s) {
     if (keep && have - keep >= keep) e = hipMemcpyAsync(dst, src, keep, hipMemcpyDeviceToDevice, s);
     else if (keep) {
       if (d_tmp.reserve(keep)) return ZG_NOMEM;
+      Poison::fill(d_tmp.p, d_tmp.cap, s);
       e = hipMemcpyAsync(d_tmp.p, src, keep, hipMemcpyDeviceToDevice, s);
       if (e == hipSuccess) e = hipMemcpyAsync(dst, d_tmp.p, keep, hipMemcpyDeviceToDevice, s);
     }
@@ -378,6 +406,8 @@ int Engine::lane_pass(LaneTmp& t, const void* lanes, size_t lane_bytes, Down out
   hipStream_t s = stream_;
   int st;
   if ((st = t.reserve(lane_bytes)) || (st = t.out.reserve(out.bytes)) || (extra.host && (st = t.extra.reserve(extra.bytes)))) return st;
+  Poison::fill_now(t.out.p, t.out.cap);
+  if (extra.host) Poison::fill_now(t.extra.p, t.extra.cap);
   ZG_HIP(t.upload(lanes, lane_bytes, nullptr, 0, s));
   ZG_HIP(hipStreamSynchronize(s));   // (pageable)
   ZG_HIP(t.begin(s));
@@ -496,6 +526,7 @@ int Engine::seekmany_prefixes(const DevEntry* e, uint32_t ne, zgm::Loc* loc, uin
   int st;
   // (lane_pass's steps without its download: nothing of the prefixes comes back, and nothing is added to stats[])
   if ((st = scratch->reserve(bytes)) || (st = tp.reserve(wbytes))) return st;
+  Poison::fill_now(scratch->p, scratch->cap);
   ZG_HIP(tp.upload(work.data(), wbytes, nullptr, 0, stream_));
   ZG_HIP(hipStreamSynchronize(stream_));   // (pageable)
   ZG_HIP(tp.begin(stream_));
@@ -653,10 +684,12 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
   b->bb.finish();
   BatchBuilder& bb = b->bb;
   Scratch* sc = b->sc = acquire();
+  Poison::begin_submit();
   const uint32_t nb = (uint32_t)bb.blocks.size(), nf = (uint32_t)bb.frames.size();
   auto up = [&](DevBuf& d, const void* h, size_t bytes) -> int {
     int st = d.reserve(bytes ? bytes : 16);
     if (st) return st;
+    Poison::fill(d.p, d.cap, us);                                  // (the whole capacity, in front of the upload)
     if (bytes && hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, us) != hipSuccess) return ZG_HIP_ERROR;
     return 0;
   };
@@ -664,6 +697,7 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
   // compressed bytes, padded so that 8-byte bit-window loads near the end stay inside the allocation
   // ... and 64 bytes in front for the 16-byte windows of the sequence decoder
   if ((st = sc->d_src.reserve(len + 128))) { delete b; return st; }
+  Poison::fill(sc->d_src.p, sc->d_src.cap, us);                    // (in front of the two zero pads and the bytes)
   (void)hipMemsetAsync(sc->d_src.p, 0, 64, us);
   if (g) {
     // the bytes are on the device already: one launch copies every entry to its place behind the front pad (zg_k_gather: the lanes read
@@ -708,6 +742,20 @@ int Engine::upload(Batch* b, const uint8_t* src, size_t len, Batch** out, bool s
       (st = sc->d_unitinfo.reserve(bb.units.size() * sizeof(ZgUnitInfo) + 16)) || (st = sc->d_dbg.reserve(8192)) || (st = sc->init_events())) {
     delete b;
     return st;
+  }
+  if (Poison::value() >= 0) {
+    // the arenas only kernels write (run() enqueues them behind this), and what the Scratch still holds of an earlier submit's output and
+    // flatten scratch; the uploaded tables were filled in front of their uploads
+    DevBuf* up_bufs[] = {&sc->d_src, &sc->d_blocks, &sc->d_frames, &sc->d_seqblocks, &sc->d_hufitems, &sc->d_hufgroups, &sc->d_units, &sc->d_stepunits, &sc->d_unitlist};
+    sc->each_buf([&](DevBuf& x) {
+      bool uploaded = false;
+      for (DevBuf* u : up_bufs) uploaded = uploaded || u == &x;
+      if (!uploaded) Poison::fill(x.p, x.cap, us);
+    });
+#ifdef ZG_DEV_SWITCHES
+    Poison::scratch_cap = 0;
+    sc->each_buf([&](DevBuf& x) { Poison::scratch_cap += x.p ? x.cap : 0; });
+#endif
   }
   // the output and the flatten scratch are sized in run(), when the exact output size of every frame is known
   ZgBatchDev& d = b->dev;
@@ -783,6 +831,7 @@ int Batch::run() {
     // (the scratch first: it is four times the output. When either reserve fails nothing of the attempt stays allocated — the sizes taken
     //  from the scan may well fit where the declared ones did not: ADVICE r5)
     if (sc->d_og.reserve(declared_total * 4 + 64) == 0 && sc->d_dst.reserve(kOutFront + declared_total + 64) == 0) {
+      Poison::fill(sc->d_og.p, sc->d_og.cap, s); Poison::fill(sc->d_dst.p, sc->d_dst.cap, s);   // (a reserve may have given new memory)
       d.dst = sc->d_dst.as<uint8_t>() + kOutFront; d.dst_cap = declared_total;
       d.og = sc->d_og.as<uint32_t>(); d.og_words = og_words = declared_total;
       d.dst_cap_pre = declared_total;                        // (0 means "not sized in advance")
@@ -799,6 +848,11 @@ int Batch::run() {
     ZG_HIP(hipMemcpyAsync((void*)d.frames, bb.frames.data(), sizeof(ZgFrame), hipMemcpyHostToDevice, s));
   }
   zg_launch_reset(d, s);   // status words, slot logs, totals, d.dbg: one kernel (in front of the carried tables and dictionary fills, which write into what it clears)
+  if (fs && Poison::value() >= 0) {   // the carried tables that do not exist
+    const uint32_t offs[3] = {ZG_FSE_LL_OFF, ZG_FSE_OF_OFF, ZG_FSE_ML_OFF}, nent[3] = {512, 256, 512};
+    for (int k = 0; k < 3; k++) if (!(fs->carry_mask & (2u << k))) Poison::fill(fs->d_fse.as<uint32_t>() + offs[k], nent[k] * 4, s);
+    if (!(fs->carry_mask & 1u)) Poison::fill(fs->d_huf.p, ZG_HUF_SLOT_U16 * 2, s);
+  }
   if (fs && fs->carry_mask) {   // tables carried into this run: the frame's carry slots of the two arenas
     const ZgFrame& fr = bb.frames[0];
     ZG_HIP(hipMemcpyAsync(d.fse_arena + (size_t)fr.carry_slot * ZG_FSE_SLOT_U32, fs->d_fse.p, ZG_FSE_SLOT_U32 * 4, hipMemcpyDeviceToDevice, s));
@@ -968,14 +1022,18 @@ int Batch::size_output() {
     ZG_HIP(hipMemcpyAsync((void*)d.frames, bb.frames.data(), sizeof(ZgFrame), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(&d.frame_out[0].out_base, &fr.out_base_fixed, 8, hipMemcpyHostToDevice, s));
     frame_out[0].out_base = fr.out_base_fixed;
+    Poison::fill(fs->d_out.p, kOutFront, s);                                                   // the front pad, and what lies behind [dictionary][have]
+    Poison::fill(fs->out_ptr() + fs->base + fs->have, fs->d_out.cap - kOutFront - fs->base - fs->have, s);
     d.dst = fs->out_ptr(); d.dst_cap = fs->base + fs->have + add;
     og_words = add;
   } else {
     if ((st = sc->d_dst.reserve(kOutFront + total_out + 64))) return st;
+    Poison::fill(sc->d_dst.p, sc->d_dst.cap, s);
     d.dst = sc->d_dst.as<uint8_t>() + kOutFront; d.dst_cap = total_out;
     og_words = total_out;
   }
   if (any_fast && (st = sc->d_og.reserve(og_words * 4 + 64))) return st;
+  Poison::fill(sc->d_og.p, sc->d_og.cap, s);
   d.og = sc->d_og.as<uint32_t>();
   d.og_words = og_words;
   return ZG_OK;

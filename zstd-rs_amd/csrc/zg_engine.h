@@ -17,6 +17,32 @@ namespace zg {
 // byte i of the dword that starts i bytes before it, so up to 3 bytes in front of the first output byte are touched.
 constexpr size_t kOutFront = 256;
 
+// ZGPU_POISON=<0..255> (development build only; Tuning::poison): every byte of device memory whose content the design does not define when a
+// submit starts is filled with the value, in stream order in front of the first upload or kernel of the submit that touches the buffer —
+// every DevBuf of the submit's Scratch over its whole cap (d_src's zero pads are issued behind the fill), the output with its front pad and
+// what lies behind it, a frame's window outside [dictionary][have], the staging buffer, the carried table slots carry_mask says do not
+// exist, a SidePass's buffer and the lane passes' buffers when they are reserved. Uploaded input, carried state, a seek index handle's pairs
+// and sums, registered dictionaries and the caller's own memory are never touched. The value is the process's (the engine created last
+// read it: a streaming decoder's worker engine fills with the same byte as the context's); bytes(): filled since the last submit was
+// prepared (Engine::upload). Without ZG_DEV_SWITCHES every member is an empty inline function: the product contains none of this.
+struct Poison {
+#ifdef ZG_DEV_SWITCHES
+  static int value();                                        // -1: off
+  static void set(int v);
+  static void fill(void* p, size_t n, hipStream_t s);        // in stream order on s
+  static void fill_now(void* p, size_t n);                   // returns when the bytes are there (a buffer no stream has seen yet)
+  static void begin_submit();
+  static uint64_t bytes();
+  static uint64_t scratch_cap;                               // the sum of the capacities of the last prepared submit's Scratch, as filled
+#else
+  static int value() { return -1; }
+  static void fill(void*, size_t, hipStream_t) {}
+  static void fill_now(void*, size_t) {}
+  static void begin_submit() {}
+  static uint64_t bytes() { return 0; }
+#endif
+};
+
 // growable device buffer; a buffer that is grown again grows by at least half of its size (amortised reuse)
 struct DevBuf {
   void* p = nullptr;
@@ -89,6 +115,7 @@ struct Scratch {
   hipEvent_t ev_sw[80] = {};                      // split sweep: heads on the second stream (zg_launch_sweep)
   hipEvent_t ev_flat[2] = {};                     // the direct units' flatten on the second stream beside the pointer-mode units' (zg_launch_flat)
   bool have_events = false;
+  template <class F> void each_buf(F f);          // every DevBuf above
   int init_events();
   void release();
   void release_but_output();
@@ -130,6 +157,7 @@ struct Tuning {
   uint32_t scatter_chunk = 0;        // ZGPU_SCATTER_CHUNK: bytes per chunk of zg_k_scatter's plan (0: zgs::kChunkDefault; measurement of the chunk size)
   bool hash_device_max_set = false;  // ZGPU_HASH_DEVICE_MAX: longest frame zgpu_decode_frames hashes on the device (measurement of the threshold)
   uint64_t hash_device_max = 0;
+  int poison = -1;                   // ZGPU_POISON=<0..255>: what memory no submit has defined holds (struct Poison above); -1: left as it is
   static Tuning from_env();
 };
 

@@ -67,7 +67,8 @@ _STATS = {
                               "measure_submits", "measure_us", "frames_measured",
                               "hash_submits", "hash_us", "frames_hashed", "sums_bytes", "hash_runs")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
-                       ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder")),
+                       ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder",
+                        "poison", "poisoned_lo", "poisoned_hi", "scratch_cap_lo", "scratch_cap_hi")),
     "Pool.plan_stats": ("zgpu_pool_plan_stats", C.c_uint64,
                         ("units", "direct_units", "noseq_units", "pointer_units", "sweep_steps", "pointer_bytes", "direct_bytes")),
     "CStreamingDecoder.stats": ("zgpu_streaming_stats", C.c_uint64,
@@ -647,9 +648,12 @@ class Context:
     def tuning(self):
         """the switches this context's engine took when it was created (zgpu_debug_tuning): all defaults in the product library"""
         d = _read_stats(self.L, "Context.tuning", self.h)
-        for k in ("seq_packed", "flat4"):
+        for k in ("seq_packed", "flat4", "poison"):
             if d.get(k, 0) >= 1 << 31:
                 d[k] -= 1 << 32
+        # ZGPU_POISON (-1: not set), the bytes filled for the last prepared submit and the capacity of its scratch buffers (development build)
+        for k in ("poisoned", "scratch_cap"):
+            d[k + "_bytes"] = d.pop(k + "_lo", 0) | d.pop(k + "_hi", 0) << 32
         return d
 
     def set_max_window_size(self, n):
