@@ -108,7 +108,11 @@ typedef struct zgpu_ctx zgpu_ctx;         /* one per (GPU, HIP stream); not thre
 typedef struct zgpu_batch zgpu_batch;     /* one submit: a run of whole frames, parsed and resident on the device */
 typedef struct zgpu_decoder zgpu_decoder; /* mirror of ruzstd's FrameDecoder for one frame at a time */
 
-/* ---- context ------------------------------------------------------------------------------------------- */
+/* ---- context -------------------------------------------------------------------------------------------
+ * Threads. Distinct contexts, and everything made from them, may be used from distinct threads at once. One context together with its
+ * decoders, streams, batches and seek indexes is one thread's at a time: no two calls on any of them may overlap, and the library takes no
+ * lock for them. Between calls these objects may change threads, and they may be destroyed on any thread. What the process shares — the
+ * caches behind the streams — is locked inside the library; zgpu_release_caches must be called only while no stream is in a call. */
 int zgpu_ctx_create(int device_id, zgpu_ctx** out);                 /* ~ FrameDecoder::new  frame_decoder.rs:158 */
 void zgpu_ctx_destroy(zgpu_ctx*);
 void zgpu_set_max_window_size(zgpu_ctx*, uint64_t max_window_size); /* frame_decoder.rs:175 (clamped to the format maximum) */
@@ -572,7 +576,7 @@ int zgpu_gather_ranges_seek_table_device_src(zgpu_ctx*, const void* const* devic
  * and [18] are 0 (no locate, no prefix pass), [16] is 1 when any range has nonzero length, [13], [5], [6] count groups and their frames once.
  * Entries whose frames declare no size are indexed by measuring them: zgpu_seek_index_measure_device, below.
  * Out of scope: updating an index in place, host sources, several GPUs, sharing one handle between contexts. */
-typedef struct zgpu_seek_index zgpu_seek_index;        /* belongs to one zgpu_ctx; destroy it before the context */
+typedef struct zgpu_seek_index zgpu_seek_index;        /* belongs to one zgpu_ctx; destroy it before the context; its context's thread rule (context section) */
 enum { ZGPU_INDEX_SEEK_TABLE = 0, ZGPU_INDEX_DECLARED = 1, ZGPU_INDEX_AUTO = 2 };
 #define ZGPU_INDEX_UNSIZED 32u                         /* zgpu_seek_index_info.why: a zstd frame declares no Frame_Content_Size */
 typedef struct {
@@ -717,7 +721,7 @@ int zgpu_seek_index_export_seek_table_ex(const zgpu_seek_index*, uint32_t entry,
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of
  * FrameDecoder::decode_all (frame_decoder.rs:541-577), which decodes the frames of a buffer one after the other. */
-typedef struct zgpu_pool zgpu_pool;
+typedef struct zgpu_pool zgpu_pool;                   /* one thread's at a time, like a context; distinct pools may run on distinct threads at once */
 int zgpu_pool_create(int n_gpus /* <= 0: all visible */, zgpu_pool** out);
 int zgpu_pool_create_on(const int* devices, int n, zgpu_pool** out);   /* explicit device ids (e.g. {LOCAL_RANK} in a one-process-per-GPU job) */
 void zgpu_pool_destroy(zgpu_pool*);
@@ -924,7 +928,7 @@ uint64_t zgpu_frame_blocks_decoded(const zgpu_frame*);   /* frame_decoder.rs:297
  * thread's side cannot be set up — the engine refuses (no device memory for the larger window) or there is no pinned memory for the ring or a
  * staging buffer — the stream goes on decoding on the caller's thread. Host memory that cannot be got inside a read() (ZGPU_E_NOMEM
  * from the library's own buffers) ends the stream in the same way. */
-typedef struct zgpu_streaming zgpu_streaming;
+typedef struct zgpu_streaming zgpu_streaming;         /* its context's thread rule (context section): one thread at a time, any thread between calls */
 typedef size_t (*zgpu_read_fn)(void* user, uint8_t* dst, size_t n);   /* io::Read::read of the source: 0 = end of input */
 typedef struct {
   uint64_t read_ahead_bytes;   /* plaintext that may be decoded ahead of the reader = size of the pinned host ring. 0: default (512 MiB, and
@@ -959,7 +963,7 @@ int zgpu_streaming_read(zgpu_streaming*, uint8_t* dst, size_t cap, size_t* n);
 int zgpu_streaming_copy(zgpu_streaming*, size_t buf_size, zgpu_write_fn write, void* user, uint64_t* total);
 /* A stream that used a worker thread leaves its engine (streams, device buffers sized to its runs; at most two per device) and its pinned ring /
  * staging memory (at most 3 GiB) to the next stream of the process: allocating them is what a short-lived stream would otherwise spend its time on.
- * This returns all of that to the runtime (no stream may be in a call meanwhile). */
+ * This returns all of that to the runtime. It must be called only while no stream of the process, on any thread, is in a call. */
 void zgpu_release_caches(void);
 /* diagnostics: out[0] mode now (0 runs on the caller's thread, 1 worker thread + ring, 2 block by block), [1] runs decoded ahead and
  * taken, [2] runs decoded ahead and dropped, [3] host bytes held (buffer + ring); [4..11] microseconds — worker thread: waiting for a run

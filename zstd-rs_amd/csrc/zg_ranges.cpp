@@ -617,14 +617,16 @@ static_assert(sizeof(zgpu_seek_index_sums) == 32 && offsetof(zgpu_seek_index_sum
 namespace {
 constexpr uint64_t kHashRunBytes = 64ull << 20;   // run_bytes == 0
 
-// the handle's array of sums, allocated (zeros: what a skippable row holds) when the first entry gets sums
-int ensure_sums(zgpu_seek_index* x) {
+// the handle's array of sums, allocated (zeros: what a skippable row holds) when the first entry gets sums. The zeros go out on the stream
+// that the caller writes the sums on next, so that they are in front of them by stream order (the engine's streams do not wait for the
+// null stream); s == nullptr: the null stream, for a caller whose next write is a null-stream hipMemcpy.
+int ensure_sums(zgpu_seek_index* x, hipStream_t s) {
   if (x->sums.p) return ZGPU_OK;
   if (x->nsums > SIZE_MAX / 4) return ZGPU_E_NOMEM;
   const size_t bytes = (size_t)(x->nsums ? x->nsums : 1) * 4;
   const int st = x->sums.reserve(bytes);
   if (st) return st;
-  if (hipMemset(x->sums.p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); x->sums.release(); return ZGPU_E_HIP; }
+  if ((s ? hipMemsetAsync(x->sums.p, 0, bytes, s) : hipMemset(x->sums.p, 0, bytes)) != hipSuccess) { (void)hipGetLastError(); x->sums.release(); return ZGPU_E_HIP; }
   x->sums_stats[kSumStatSumsBytes] = x->nsums * 4;
   return ZGPU_OK;
 }
@@ -713,10 +715,10 @@ int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const
     o.frames += got[r].size(); o.bytes += p[run.k1].d - p[run.k0].d;
   }
   // the handle: one copy per stretch of chosen entries whose sums lie back to back
-  if ((st = ensure_sums(x))) return st;
+  hipStream_t s = eng->stream();
+  if ((st = ensure_sums(x, s))) return st;
   std::vector<uint32_t> stage;
   uint64_t at = 0;      // the index of stage[0] in the handle's array
-  hipStream_t s = eng->stream();
   std::vector<std::vector<uint32_t>> keep;   // (the staging of the stretches sent so far: alive until the stream is drained)
   auto flush = [&]() -> int {
     if (stage.empty()) return ZGPU_OK;
@@ -760,7 +762,7 @@ extern "C" int zgpu_seek_index_hash_device(zgpu_ctx* c, zgpu_seek_index* x, cons
 extern "C" int zgpu_seek_index_set_sums(zgpu_seek_index* x, uint32_t entry, const uint32_t* sums, uint32_t nrows) {
   if (!x || entry >= x->ents.size() || x->ents[entry].info.status || nrows != x->ents[entry].info.nrows || (nrows && !sums)) return ZGPU_E_BAD_ARG;
   if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  int st = ensure_sums(x);
+  int st = ensure_sums(x, nullptr);
   if (st) return st;
   zgpu_seek_index::Ent& e = x->ents[entry];
   if (nrows && hipMemcpy(x->sums.as<uint32_t>() + e.spre, sums, (size_t)nrows * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }

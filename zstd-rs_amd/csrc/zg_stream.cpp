@@ -7,6 +7,7 @@
 #include <mutex>
 #include <new>
 #include <vector>
+#include "zg_caches.h"
 #include "zg_capi_int.h"
 #include "zg_stream.h"
 
@@ -14,80 +15,17 @@ using namespace zg;
 
 namespace {
 
-// Pinned host memory is expensive to get (the pages are faulted in and locked: ~0.1 s per few hundred MiB) and a stream needs a ring and
-// staging buffers of that size: blocks are kept for the next stream of the process (bounded), not returned to the runtime.
-struct PinnedCache {
-  struct Blk { void* p; size_t n; };
-  std::mutex mu;
-  std::vector<Blk> free_;
-  size_t held = 0;
-  static constexpr size_t kMaxHeld = 3ull << 30;
-  void* get(size_t n) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      size_t best = free_.size();
-      for (size_t i = 0; i < free_.size(); i++)
-        if (free_[i].n >= n && free_[i].n <= n + n / 4 + (1u << 20) && (best == free_.size() || free_[i].n < free_[best].n)) best = i;
-      if (best != free_.size()) {
-        void* p = free_[best].p;
-        held -= free_[best].n;
-        sizes_.push_back(Blk{p, free_[best].n});
-        free_.erase(free_.begin() + best);
-        return p;
-      }
-    }
+// the process-wide caches of zg_caches.h, over the runtime's pinned memory and the engine
+struct HipHostMem {
+  void* alloc(size_t n) {
     void* p = nullptr;
     if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    std::lock_guard<std::mutex> lk(mu);
-    sizes_.push_back(Blk{p, n});
     return p;
   }
-  void put(void* p) {
-    size_t n = 0;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (size_t i = 0; i < sizes_.size(); i++)
-        if (sizes_[i].p == p) { n = sizes_[i].n; sizes_.erase(sizes_.begin() + i); break; }
-      if (n && held + n <= kMaxHeld) { free_.push_back(Blk{p, n}); held += n; return; }
-    }
-    (void)hipHostFree(p);
-  }
-  void trim() {
-    std::lock_guard<std::mutex> lk(mu);
-    for (const Blk& b : free_) (void)hipHostFree(b.p);
-    free_.clear(); held = 0;
-  }
-  std::vector<Blk> sizes_;   // blocks handed out (their real sizes)
+  void free(void* p) { (void)hipHostFree(p); }
 };
-PinnedCache g_pinned;
-
-// Engines of streaming decoders that are not in use. A stream whose worker thread decodes ahead has an engine of its own (streams, scratch
-// buffers sized to its runs); the next stream on the same device takes it over instead of allocating all of that again. Process-wide (a
-// stream may outlive the context it was made from), at most two per device.
-struct IdleEngines {
-  std::mutex mu;
-  std::vector<Engine*> v;
-  Engine* take(int device) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (size_t i = 0; i < v.size(); i++) if (v[i]->device() == device) { Engine* e = v[i]; v.erase(v.begin() + i); return e; }
-    return nullptr;
-  }
-  void give(Engine* e) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      size_t same = 0;
-      for (Engine* x : v) same += x->device() == e->device();
-      if (same < 2) { v.push_back(e); return; }
-    }
-    delete e;
-  }
-  void trim() {
-    std::vector<Engine*> all;
-    { std::lock_guard<std::mutex> lk(mu); all.swap(v); }
-    for (Engine* e : all) delete e;
-  }
-};
-IdleEngines g_idle_engines;
+PinnedCache<HipHostMem> g_pinned;
+IdleEngines<Engine> g_idle_engines;
 
 class GpuStreamBackend : public StreamBackend {
  public:
