@@ -369,6 +369,7 @@ int zgpu_debug_frames_index_stats(const zgpu_ctx*, uint64_t* out, int n);
  *    a decode error, a walk error and BAD_ARG, in front of TARGET_TOO_SMALL and of the checksum verdict of ZGPU_DEVICE_VERIFY. The check is
  *    per frame, and the order is one — decode and walk, size, TARGET_TOO_SMALL, checksum — for every entry: with or without dictionary
  *    frames, in a shared submit or decoded alone (an entry's status does not depend on zgpu_set_frames_shared_dicts).
+ *    (In the library that order is written once: zstd-rs_amd/csrc/zg_entry.h, for the entries of a submit and for those decoded alone.)
  *  - results[i].d is zgpu_decode_frames_device_src's result for the selection, except: written is the CLIPPED count — the bytes of
  *    [begin - plain_lo, begin - plain_lo + len) that the taken frames' concatenation has — and ZGPU_E_TARGET_TOO_SMALL is decided by that
  *    count against caps[i], not by the decoded size; nframes counts the frames decoded. The destination holds exactly those bytes.

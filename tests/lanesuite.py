@@ -1,5 +1,5 @@
 """What the CPU suites of the lane and wave routines share (test_walk_cpu, test_index_cpu, test_seek_cpu, test_seektab_cpu, test_seeksums_cpu,
-test_seekmany_cpu, test_seekidx_cpu, test_scatter_cpu, test_dictfill_cpu, test_xxh64_cpu, test_xxh64_quad_cpu): the build of a harness under
+test_seekmany_cpu, test_seekidx_cpu, test_scatter_cpu, test_dictfill_cpu, test_xxh64_cpu, test_xxh64_quad_cpu, test_entry_verdict_cpu): the build of a harness under
 tests/emu/ (every one runs a routine of zstd-rs_amd/csrc over the accessors of tests/emu/zg_lane_mem.h) as a shared library and, where it has
 a main, as a stand-alone AddressSanitizer program; the run of such a program; the fixture each suite's `built` is made of; two ctypes helpers.
 The sanitizer's runtime is linked statically into a program with its own main: nothing is loaded into the interpreter."""

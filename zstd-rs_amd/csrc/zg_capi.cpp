@@ -861,22 +861,19 @@ int zgpu_decoder_collect_to_writer(zgpu_decoder* d, zgpu_write_fn write, void* u
 
 }  // extern "C"
 
-int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums) {
+int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, std::vector<zge::Frame>* frames) {
   // FrameDecoder::decode_all (frame_decoder.rs:541-577) frame by frame
   zgpu_decoder* d = nullptr;
   int st = zgpu_decoder_create(c, &d);
   if (st) return st;
-  // (sums: the content checksums of the frames decoded, as zgpu_decode_frames reports them — the decoder hashes what is drained)
+  // (frames: what zgpu_decode_frames reports of the frames decoded — the decoder hashes what is drained)
   auto note = [&](uint64_t yielded, size_t begin, size_t end) {
-    if (!sums) return;
-    if (d->fh.has_fcs() && d->fh.frame_content_size != yielded) sums->size_lies++;
+    if (!frames) return;
     uint32_t v = 0;
     const bool has = zgpu_decoder_checksum_from_data(d, &v) != 0;
-    const uint32_t calc = zgpu_decoder_calculated_checksum(d);
-    if (sums->nframes == 0) { sums->first_data = has ? v : 0u; sums->first_calc = calc; }
-    sums->nframes++;
-    sums->frames.push_back(ZgFrameSum{begin, end, yielded, calc});
-    if (has) { sums->checksums++; if (v != calc) sums->mismatches++; }
+    const uint64_t before = frames->empty() ? 0 : frames->back().end;
+    frames->push_back(zge::Frame{begin, end - begin, yielded, before + yielded, d->fh.frame_content_size, zgpu_decoder_calculated_checksum(d),
+                                 has ? v : 0u, (uint32_t)frames->size(), d->fh.has_fcs(), has, true});
   };
   d->drain_rule = ZG_DRAIN_DECODE_ALL;   // one decode_blocks(All) per frame stands for the reference's rounds of UptoBytes(1 MiB) + read(): same verdicts
   size_t p = 0, total = 0;

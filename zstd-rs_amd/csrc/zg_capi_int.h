@@ -7,6 +7,7 @@
 #include "../../include/zgpu.h"
 #include "zg_engine.h"
 #include "zg_xxh64.h"
+#include "zg_entry.h"
 
 struct ZgDict {   // Dictionary (decoding/dictionary.rs:12-37), tables in the engine's packed formats
   uint32_t id = 0;
@@ -123,13 +124,10 @@ uint64_t zg_stream_host_bytes(const zg::StreamCore* c);
 int zg_stream_error(const zg::StreamCore* c);                          // the engine error that ended the stream (0: none)
 size_t zg_stream_take(zg::StreamCore* c, uint8_t* dst, size_t n);   // n <= can_collect: bytes that are buffered already
 
-// (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); sums, if given, collects the
-// content checksums of the frames it decoded (zgpu_decode_frames)
-// size_lies: frames that declare a Frame_Content_Size and yielded another number of bytes
-// frames: every decoded frame's bytes [begin, end) of src, what it yielded and the low 32 bits of the XXH64 of that
-struct ZgFrameSum { uint64_t begin, end, yielded; uint32_t calc; };
-struct ZgFrameSums { uint32_t nframes = 0, checksums = 0, mismatches = 0, first_data = 0, first_calc = 0, size_lies = 0; std::vector<ZgFrameSum> frames; };
-int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, ZgFrameSums* sums);
+// (zg_capi.cpp) FrameDecoder::decode_all frame by frame through the FrameDecoder mirror (the path of dictionary frames); frames, if given, collects
+// the facts of every frame it decoded (zg_entry.h): bytes [begin, begin + clen) of src, what it yielded, what it declares, its Content_Checksum
+// and the low 32 bits of the XXH64 of what it yielded — the decoder hashes what is drained: every frame is hashed, its slot is its index
+int zg_decode_all_per_frame(zgpu_ctx* c, const uint8_t* src, size_t len, uint8_t* dst, size_t cap, size_t* written, std::vector<zge::Frame>* frames);
 // (zg_stream.cpp) the process-wide cache of pinned host blocks the streams use; nullptr if none can be had
 void* zg_pinned_get(size_t n);
 void zg_pinned_put(void* p);

@@ -35,12 +35,18 @@
 // decode_entries ask for a part by its pointer — `if (k.sink)`, `if (k.src)`, `if (k.ranges)` — never by which field happens to be set.
 // Around them: reset_stats zeroes the statistics a call family owns (kOwns*), device_ptr_ok is the one question asked of a pointer and
 // check_entries / check_entry_ranges the two loops that ask it in front of the engine's lane passes, drain the two-stream wait every call
-// ends with, SubmitHash the hashing both sinks start before they copy. Every statistics slot is written under its name (zg_capi_int.h, kPass*).
+// ends with, hash_launch / hash_wait the hashing both sinks start before they copy. Every statistics slot is written under its name (zg_capi_int.h,
+// kPass*).
+// What an entry's result is. decode_submit and decode_alone PRODUCE facts (zg_entry.h: zge::Frame, zge::Entry) — from frame_out, info and the walk,
+// or from the FrameDecoder mirror's frame-by-frame pass — and everything that turns facts into a result is written once, there: the order of
+// verdicts (ladder), the two checksum verdicts (verify_fails, table_fails), the frame list of the seek-table compare (compare_list), the checksum fields (fill) and the
+// pieces a clip takes of the frames (clip_pieces). The sinks and decode_alone_device keep what is theirs: launches, waits, downloads, uploads.
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <new>
 #include <thread>
 #include <utility>
@@ -166,22 +172,20 @@ struct Call {
       : c(ctx), srcs(s), lens(l), dsts(d), caps(cp), lookup{shared_find, ctx}, shared(ctx->frames_shared_dicts && !ctx->dicts.empty()) {}
   const DictLookup* dicts() const { return shared ? &lookup : nullptr; }
   uint64_t hash_max() const { return sink ? sink->hash_max : host_hash_max; }
-  // What of `bytes` decoded bytes of entry i its destinations get, and *too_small: none of them has room. Ranges: every clip of the entry's
-  // span is measured by its own count against its own capacity (Clip::written, Clip::small); a clip that is too small gets nothing and
-  // does not disturb the others, and the entry as a whole is too small only if every clip is.
-  uint64_t fit(uint32_t i, uint64_t bytes, bool* too_small) const {
-    if (!ranges) { *too_small = bytes > caps[i]; return bytes; }
-    uint64_t sum = 0;
-    bool any = false;
-    for (uint32_t q = ranges->first[i]; q < ranges->first[i + 1]; q++) {
-      Clip& cl = ranges->clip[q];
-      const uint64_t rest = bytes > cl.skip ? bytes - cl.skip : 0, w = rest < cl.len ? rest : cl.len;
-      cl.small = w > cl.cap;
-      cl.written = cl.small ? 0 : w;
-      if (!cl.small) { sum += w; any = true; }
-    }
-    *too_small = !any && ranges->first[i] != ranges->first[i + 1];   // (an empty span — zgpu_seek_index_hash_device — wants no byte: never too small)
-    return sum;
+  // what entry i's bytes are measured against (zg_entry.h: ladder): its capacity, or — ranges — its span of clips and what its frames declare
+  zge::Mode mode(uint32_t i) const {
+    zge::Mode m;
+    m.cap = caps[i];
+    if (!ranges) return m;
+    m.ranges = true; m.promise = ranges->promise; m.declared = ranges->declared[i];
+    m.clip = ranges->clip.data() + ranges->first[i]; m.nclips = ranges->first[i + 1] - ranges->first[i];
+    return m;
+  }
+  // entry i's clips — without ranges the whole entry is one (*whole: room for it, `written` what the ladder said) — and how many
+  const zge::Clip* clips(uint32_t i, uint64_t written, zge::Clip* whole, uint32_t* n) const {
+    *whole = zge::Clip{0, UINT64_MAX, dsts[i], caps[i], written, false};
+    *n = ranges ? ranges->first[i + 1] - ranges->first[i] : 1;
+    return ranges ? ranges->clip.data() + ranges->first[i] : whole;
   }
   zgpu_entry_result& result(uint32_t i) const { return sink ? sink->res[i].r : res[i]; }
 };
@@ -218,6 +222,8 @@ struct Submit {
   std::vector<int> walk;
   std::vector<uint32_t> ff;       // entry j's frames are [ff[j], ff[j + 1])
   std::vector<uint64_t> off;      // entry j lies at off[j] of the submit's input (FrameInfo::src_begin / src_end are counted from its begin)
+  std::vector<zge::Frame> fr;     // the facts (zg_entry.h), flat: every frame of the submit, hashed / slot / digest filled in by hash_launch / hash_wait ...
+  std::vector<zge::Entry> ent;    // ... and entry j, a view of fr[ff[j] .. ff[j + 1])
   std::vector<uint32_t> cand;     // frames of successful entries short enough to be hashed on the device
   uint64_t down = 0;              // output bytes the successful entries reach up to
   ~Submit() { delete b; }
@@ -263,88 +269,67 @@ int decode_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   uint64_t* ds = k.c->frames_dict_stats;
   ds[kDictStatFillLaunches] += b->dictfill_launches; ds[kDictStatBytesReplicated] += b->dictfill_bytes; ds[kDictStatFillUs] += b->dictfill_us;
 
-  // verdicts (zgpu_decode_all, zg_capi.cpp, on the entry's own frames)
+  // the facts: every frame's from its FrameInfo and ZgFrameOut, every entry's from its walk and its frames in stream order
+  u.fr.resize(fo.size());
+  u.ent.assign(n, zge::Entry{});
+  for (uint32_t j = 0; j < n; j++) {
+    zge::Entry& e = u.ent[j];
+    e.walk = walk[j]; e.dict = has_dict[j] != 0;
+    e.nframes = ff[j + 1] - ff[j]; e.fr = u.fr.data() + ff[j];
+    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
+      const FrameInfo& fi = b->info[f];
+      if (!e.decode && fo[f].status) e.decode = (int)fo[f].status;
+      e.total += fo[f].out_size;
+      if (!e.decode && !fi.host_status) e.sound = e.total;
+      u.fr[f] = zge::Frame{fi.src_begin - off[j], fi.src_end - fi.src_begin, fo[f].out_size, e.total, fi.header.frame_content_size, 0, fi.checksum,
+                           zgv::kNotHashed, fi.header.has_fcs(), fi.has_checksum, false};
+    }
+  }
+  // verdicts (zgpu_decode_all, zg_capi.cpp, on the entry's own frames): zg_entry.h's ladder
   for (uint32_t j = 0; j < n; j++) {
     const uint32_t i = idx[j];
+    const zge::Entry& e = u.ent[j];
     zgpu_entry_result& r = k.result(i);
     // zgpu_decode_all's frame-by-frame path (the switch off, or an id the lookup did not resolve)
     if (walk[j] == ZGPU_E_DICT_NOT_PROVIDED && !k.c->dicts.empty()) { k.again.push_back({i, true}); ds[kDictStatEntriesAlone] += k.shared ? 1u : 0u; continue; }
-    int dev = 0;
-    uint64_t bytes = 0;
-    bool small = false;   // (has_dict) the entry's output up to a frame in front of the first failing one does not fit
-    bool lied = false;    // (ranges) a frame that declares a size decoded to another length: the coordinates of the range mean nothing
-    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      if (!dev && fo[f].status) dev = (int)fo[f].status;
-      bytes += fo[f].out_size;
-      if (has_dict[j] && !k.ranges && !dev && !b->info[f].host_status && bytes > k.caps[i]) small = true;
-      if (k.ranges && b->info[f].header.has_fcs() && b->info[f].header.frame_content_size != fo[f].out_size) lied = true;
-    }
-    if (k.ranges && k.ranges->promise && bytes != k.ranges->declared[i]) lied = true;  // (the selection yields another length than its seek table says)
-    if (dev == ZGPU_E_UNSUPPORTED || dev == ZGPU_E_INTERNAL) { k.again.push_back({i, has_dict[j] != 0}); ds[kDictStatEntriesAlone] += has_dict[j]; continue; }
-    if (k.ranges) { k.ranges->stats[kRangeStatFramesDecoded] += ff[j + 1] - ff[j]; k.ranges->stats[kRangeStatPlaintextDecoded] += bytes; }   // (work done, failed entries too; an entry that goes alone is counted there)
-    // An entry with a dictionary frame is what zgpu_decode_all decodes frame by frame (zg_decode_all_per_frame: every frame is read out before the
-    // next one is looked at), so a frame that does not fit ends it with TargetTooSmall BEFORE a later frame's error or the walk's; without one,
-    // zgpu_decode_all's one submit reports a device error first, then the walk's, then TargetTooSmall.
-    // (ranges have ONE order, with or without dictionary frames, in a submit or alone: the decode and walk verdicts, ContentSizeMismatch,
-    // TargetTooSmall by the clipped count — taken in coordinates that the declared sizes define —, then the checksum verdict)
-    // (ranges with several clips: TargetTooSmall is each clip's own verdict, and the entry's only where no clip has room)
-    bool too_small = false;
-    const uint64_t fits = k.fit(i, bytes, &too_small);
-    if (has_dict[j] && !k.ranges) r.status = small ? ZGPU_E_TARGET_TOO_SMALL : dev ? dev : walk[j] ? walk[j] : ZGPU_OK;
-    else r.status = dev ? dev : walk[j] ? walk[j] : lied ? ZGPU_E_CONTENT_SIZE_MISMATCH : too_small ? ZGPU_E_TARGET_TOO_SMALL : ZGPU_OK;
+    if (e.decode == ZGPU_E_UNSUPPORTED || e.decode == ZGPU_E_INTERNAL) { k.again.push_back({i, e.dict}); ds[kDictStatEntriesAlone] += e.dict; continue; }
+    if (k.ranges) { k.ranges->stats[kRangeStatFramesDecoded] += e.nframes; k.ranges->stats[kRangeStatPlaintextDecoded] += e.total; }   // (work done, failed entries too; an entry that goes alone is counted there)
+    const zge::Verdict v = zge::ladder(e, k.mode(i));
+    r.status = v.status;
     if (r.status) continue;
     if (has_dict[j]) for (uint32_t f = ff[j]; f < ff[j + 1]; f++) ds[kDictStatFramesShared] += b->bb.frames[f].dict_len ? 1u : 0u;
-    r.written = fits;
-    r.nframes = ff[j + 1] - ff[j];
+    r.written = v.written;
+    r.nframes = e.nframes;
     // (the seek table's checksums, a handle's sums, the hash pass: every frame, with or without a Content_Checksum)
     const bool table_all = k.sink && ((k.sink->table_all && k.sink->compared(i)) || k.sink->hash_every);
     for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
       if (fo[f].out_size <= k.hash_max() || (k.sink && k.sink->hash_all && b->info[f].has_checksum) || table_all) u.cand.push_back(f);   // (candidates)
-      const uint64_t e = fo[f].out_base + fo[f].out_size;
-      if (e > u.down) u.down = e;
+      const uint64_t upto = fo[f].out_base + fo[f].out_size;
+      if (upto > u.down) u.down = upto;
     }
   }
   return ZGPU_OK;
 }
 
-// A device-sink entry fails with `status`: written = nframes = 0 like any failed entry (sums / bad: the two counts of the checksum verdict,
-// which say why). The arguments are taken by value: they may be d's own fields.
-void fail_entry(zgpu_device_entry_result& d, int status, uint32_t sums = 0, uint32_t bad = 0, uint32_t unverified = 0) {
-  memset(&d, 0, sizeof d);
-  d.r.status = status;
-  d.r.checksums = sums; d.r.checksum_mismatches = bad;
-  d.checksums_unverified = unverified;
-}
-// The verdict of ZGPU_DEVICE_VERIFY_SEEK_TABLE on an entry of nframes decoded zstd frames that stands at status 0, from its record (zg_seeksums.h:
-// vouched). A failed entry reports the frames compared, those that differ and the decoded frames not compared. Returns whether it failed.
-bool table_verdict(zgpu_device_entry_result& d, const zgv::Sums& s, uint32_t nframes, uint64_t* range_stats) {
-  range_stats[kRangeStatFramesCompared] += s.compared;
-  if (zgv::vouched(s, nframes)) return false;
-  fail_entry(d, ZGPU_E_SEEK_CHECKSUM_MISMATCH, s.compared, s.differing, nframes - s.compared);
-  range_stats[kRangeStatEntriesFailedTable]++;
-  return true;
-}
+using zge::fail_entry;
 const char* const kHandleChanged = "zgpu_gather_ranges_indexed_device_src: rows or digests that leave the arrays of the checksum compare";
 const char* const kTableChanged = "zgpu_decode_ranges_seek_table_device_src: a seek table changed between the seek and the checksum compare";
 
-// What both sinks do about hashing: the frames of u.cand, as the sink left that list, are hashed by the device — launch() enqueues the kernel
-// on the first stream, and the sink does its copying beside it; wait() collects the digests (*kernel_us, if asked for: the kernel's time).
-struct SubmitHash {
-  std::vector<uint8_t> on_dev;    // per frame of the submit: hashed on the device
-  std::vector<uint64_t> digest;   // per frame: its XXH64 (on_dev frames after wait(); the host sink fills in the others)
-  int launch(const Submit& u, uint32_t quad_max_ranges = 0) {
-    on_dev.assign(u.b->frame_out.size(), 0);
-    for (uint32_t f : u.cand) on_dev[f] = 1;
-    return u.b->hash_launch(u.cand.data(), (uint32_t)u.cand.size(), quad_max_ranges);
-  }
-  int wait(const Submit& u, uint64_t* kernel_us = nullptr) {
-    digest.assign(u.b->frame_out.size(), 0);
-    std::vector<uint64_t> dh(u.cand.size());
-    const int st = u.b->hash_wait(dh.data(), kernel_us);
-    for (size_t q = 0; q < u.cand.size() && !st; q++) digest[u.cand[q]] = dh[q];
-    return st;
-  }
-};
+void count_frames(DeviceSink& sink, const zge::Hashed& h) { sink.stats[kDevStatFramesHashed] += h.hashed; sink.stats[kDevStatFramesNotHashed] += h.not_hashed; }
+
+// What both sinks do about hashing: the frames of u.cand, as the sink left that list, are hashed by the device — hash_launch enqueues the kernel
+// on the first stream, and the sink does its copying beside it; hash_wait collects the digests into the facts (*kernel_us, if asked for: the
+// kernel's time). A frame's slot is its place in u.cand: where its digest lies in device memory for the compare kernels.
+int hash_launch(Submit& u, uint32_t quad_max_ranges = 0) {
+  for (size_t q = 0; q < u.cand.size(); q++) { u.fr[u.cand[q]].hashed = true; u.fr[u.cand[q]].slot = (uint32_t)q; }
+  return u.b->hash_launch(u.cand.data(), (uint32_t)u.cand.size(), quad_max_ranges);
+}
+int hash_wait(Submit& u, uint64_t* kernel_us = nullptr) {
+  std::vector<uint64_t> dh(u.cand.size());
+  const int st = u.b->hash_wait(dh.data(), kernel_us);
+  for (size_t q = 0; q < u.cand.size() && !st; q++) u.fr[u.cand[q]].digest = dh[q];
+  return st;
+}
 
 // the host sink: the plaintext comes back, goes to the callers' buffers on the host threads, and the frames the device did not hash are hashed there
 int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
@@ -355,11 +340,10 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   const uint64_t down = u.down;                // output bytes the host needs (of entries that succeed)
   int st;
   if (!k.hash_forced && !hash_on_device(u.cand, fo)) u.cand.clear();   // (what stays is hashed on the device)
-  SubmitHash h;
   // the device hashes its frames while the output comes back
-  if ((st = h.launch(u))) return st;
+  if ((st = hash_launch(u))) return st;
   Staging out;
-  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down)) || (st = h.wait(u))) return st;
+  if ((st = out.get(down)) || (st = b->read_output(0, out.p, down)) || (st = hash_wait(u))) return st;
   // bytes to the callers' buffers; the long frames hashed here, from those bytes
   parallel_for(n, down, 4u << 20, [&](uint32_t j) {
     zgpu_entry_result& r = k.res[idx[j]];
@@ -370,18 +354,13 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       const uint8_t* s = out.p + fo[f].out_base;
       if (fo[f].out_size) memcpy(d + at, s, fo[f].out_size);
       at += fo[f].out_size;
-      if (!h.on_dev[f]) h.digest[f] = zgx::xxh64(s, fo[f].out_size, 0);
+      if (!u.fr[f].hashed) { u.fr[f].digest = zgx::xxh64(s, fo[f].out_size, 0); u.fr[f].hashed = true; }
     }
   });
   for (uint32_t j = 0; j < n; j++) {
     zgpu_entry_result& r = k.res[idx[j]];
     if (r.status || r.nframes == 0) continue;
-    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      const FrameInfo& fi = b->info[f];
-      const uint32_t calc = (uint32_t)h.digest[f];
-      if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = calc; }
-      if (fi.has_checksum) { r.checksums++; if (fi.checksum != calc) r.checksum_mismatches++; }
-    }
+    zge::fill(u.ent[j], false, &r, nullptr, nullptr);
   }
   return ZGPU_OK;
 }
@@ -399,43 +378,27 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   DeviceSink& sink = *k.sink;
   zgpu_device_entry_result* const dres = sink.res;
   if (sink.no_hash) u.cand.clear();
-  SubmitHash h;
   int st;
-  if ((st = h.launch(u, sink.table_flag || sink.hash_every ? kTableQuadMaxRanges : 0u))) return st;   // (the hash pass waits for whole frames as well)
+  if ((st = hash_launch(u, sink.table_flag || sink.hash_every ? kTableQuadMaxRanges : 0u))) return st;   // (the hash pass waits for whole frames as well)
   uint64_t bytes = 0;
   auto scatter = [&]() -> int {   // the frames of every entry that stands at status 0, in one launch
     std::vector<zgs::Seg> segs;
     for (uint32_t j = 0; j < n; j++) {
-      const zgpu_entry_result& r = dres[idx[j]].r;
+      const uint32_t i = idx[j];
+      const zgpu_entry_result& r = dres[i].r;
       if (r.status || r.nframes == 0) continue;   // (failed, or waiting on the again-list: nothing of it is written here)
-      // (ranges: a frame's segment is clipped to [lo, hi) of the concatenation of the entry's frames; a clipped frame is just a shorter segment.
-      // Every clip of the entry's span that has room takes its own segments to its own destination: the frames are in the output once)
-      const uint32_t q0 = k.ranges ? k.ranges->first[idx[j]] : 0, q1 = k.ranges ? k.ranges->first[idx[j] + 1] : 1;
+      // (ranges: every clip of the entry's span that has room takes its own pieces to its own destination — a clipped frame is just a shorter
+      // segment, and the frames are in the output once; no ranges: the whole entry is one clip)
+      zge::Clip whole;
+      uint32_t nclips;
+      const zge::Clip* cl = k.clips(i, r.written, &whole, &nclips);
       uint64_t total = 0;
-      std::vector<uint64_t> ends;   // (several clips) where every frame ends in the concatenation: a clip starts at the frame a search finds
-      if (q1 - q0 > 1) {
-        uint64_t cat = 0;
-        for (uint32_t f = ff[j]; f < ff[j + 1]; f++) { cat += fo[f].out_size; ends.push_back(cat); }
-      }
-      for (uint32_t q = q0; q < q1; q++) {
-        const Clip* cl = k.ranges ? &k.ranges->clip[q] : nullptr;
-        if (cl && cl->small) continue;
-        const uint64_t lo = cl ? cl->skip : 0, hi = cl && cl->len < UINT64_MAX - lo ? lo + cl->len : UINT64_MAX;
-        const uint64_t dst = (uint64_t)(uintptr_t)(cl ? cl->dst : k.dsts[idx[j]]), cap = cl ? cl->cap : k.caps[idx[j]];
-        uint32_t f0 = ff[j];
-        uint64_t cat = 0, at = 0;
-        if (!ends.empty()) {   // the first frame that ends behind lo
-          f0 = ff[j] + (uint32_t)(std::upper_bound(ends.begin(), ends.end(), lo) - ends.begin());
-          cat = f0 > ff[j] ? ends[f0 - ff[j] - 1] : 0;
-        }
-        for (uint32_t f = f0; f < ff[j + 1] && cat < hi; f++) {
-          const uint64_t a = cat, e = cat + fo[f].out_size, s = a > lo ? a : lo, t = e < hi ? e : hi;
-          cat = e;
-          if (s >= t) continue;
-          segs.push_back(zgs::Seg{fo[f].out_base + (s - a), dst + at, t - s});
-          at += t - s;
-        }
-        if ((cl && at != cl->written) || at > cap) return ZGPU_E_INTERNAL;   // (never: the verdict above counted the same frames)
+      for (uint32_t q = 0; q < nclips; q++) {
+        const uint64_t dst = (uint64_t)(uintptr_t)cl[q].dst;
+        const uint64_t at = zge::clip_pieces(u.ent[j].fr, u.ent[j].nframes, cl[q], [&](const zge::Piece& p) {
+          segs.push_back(zgs::Seg{fo[ff[j] + p.frame].out_base + p.in_frame, dst + p.at, p.len});
+        });
+        if (at != cl[q].written || at > cl[q].cap) return ZGPU_E_INTERNAL;   // (never: the verdict counted the same frames)
         total += at;
       }
       if (total != r.written) return ZGPU_E_INTERNAL;   // (never)
@@ -451,20 +414,15 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     std::vector<zgv::Lane> lanes;
     std::vector<zgh::Lane> hlanes;
     std::vector<zgv::Frame> list[2];
-    std::vector<uint32_t> slot(fo.size(), zgv::kNotHashed);
-    for (size_t q = 0; q < u.cand.size(); q++) slot[u.cand[q]] = (uint32_t)q;
     for (uint32_t j = 0; j < n; j++) {
       const zgpu_entry_result& r = dres[idx[j]].r;
       if (r.status || r.nframes == 0 || !sink.compared(idx[j])) continue;
       const bool by_handle = sink.by_handle(idx[j]);
       std::vector<zgv::Frame>& to = list[by_handle];
       const uint32_t lo = (uint32_t)to.size();
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-        const FrameInfo& fi = b->info[f];
-        if (fi.src_begin < u.off[j] || fi.src_end < fi.src_begin) return ZGPU_E_INTERNAL;   // (never)
-        if (fi.src_end - fi.src_begin > 0xFFFFFFFFull) continue;   // (no row can hold its length: it coincides with none)
-        to.push_back(zgv::Frame{fi.src_begin - u.off[j], (uint32_t)(fi.src_end - fi.src_begin), slot[f]});
-      }
+      for (uint32_t f = ff[j]; f < ff[j + 1]; f++)
+        if (b->info[f].src_begin < u.off[j] || b->info[f].src_end < b->info[f].src_begin) return ZGPU_E_INTERNAL;   // (never)
+      zge::compare_list(u.ent[j], [](const zge::Frame&) { return true; }, &to);   // (a submit's hashed frames are its candidates: every digest may be used)
       if (by_handle) {
         const DeviceSink::HandleEntry& e = sink.handle_verify[idx[j]];
         hlanes.push_back(zgh::Lane{e.pair0, e.sum0, e.nrows, e.first, e.taken, lo, (uint32_t)to.size() - lo, {0, 0, 0}});
@@ -483,7 +441,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   const bool gated = sink.verify || sink.table_flag;   // the scatter waits for the verdicts
   if (!gated && (st = scatter())) return st;
   uint64_t hash_us = 0;
-  if ((st = h.wait(u, &hash_us))) return st;
+  if ((st = hash_wait(u, &hash_us))) return st;
   sink.stats[kDevStatHashUs] += hash_us;
   std::vector<zgv::Sums> sums(who[0].size() + who[1].size());   // the table's records, then the handle's
   for (int route = 0; route < 2; route++) {   // (the same slots count both compare kernels)
@@ -493,24 +451,14 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
     uint64_t* rs = k.ranges->stats;
     rs[kRangeStatCompareLaunches]++; rs[kRangeStatCompareUs] += us; rs[kRangeStatCompareBytesDownloaded] += back;
   }
-  auto count_frame = [&](uint32_t f) { sink.stats[h.on_dev[f] ? kDevStatFramesHashed : kDevStatFramesNotHashed]++; };
-  if (sink.verify) {
-    // the verdict of verification ranks behind every other one: only entries that stand at status 0 are looked at
-    for (uint32_t j = 0; j < n; j++) {
-      zgpu_entry_result& r = dres[idx[j]].r;
-      if (r.status || r.nframes == 0) continue;
-      uint32_t sums = 0, bad = 0;
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-        const FrameInfo& fi = b->info[f];
-        if (!fi.has_checksum) continue;
-        sums++;
-        if (h.on_dev[f] && fi.checksum != (uint32_t)h.digest[f]) bad++;
-      }
-      if (!bad) continue;
-      for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
-      fail_entry(dres[idx[j]], ZGPU_E_CHECKSUM_MISMATCH, sums, bad);
-      sink.stats[kDevStatEntriesFailedVerify]++;
-    }
+  // the verdict of verification ranks behind every other one: only entries that stand at status 0 are looked at. (An entry that fails here
+  // or below counts its frames, hashed or not, at that moment: the fill at the end no longer sees it.)
+  for (uint32_t j = 0; j < n && sink.verify; j++) {
+    const zgpu_entry_result& r = dres[idx[j]].r;
+    if (r.status || r.nframes == 0) continue;
+    if (!zge::verify_fails(dres[idx[j]], u.ent[j])) continue;
+    count_frames(sink, zge::hashed_frames(u.ent[j], false));
+    sink.stats[kDevStatEntriesFailedVerify]++;
   }
   // the table's verdict ranks last: only what still stands is looked at
   const zgv::Sums* rec = sums.data();
@@ -519,8 +467,10 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       const zgv::Sums& s = *rec++;
       if (s.why) { k.c->eng->last_error = route ? kHandleChanged : kTableChanged; return ZGPU_E_INTERNAL; }
       if (dres[idx[j]].r.status) continue;
-      if (table_verdict(dres[idx[j]], s, ff[j + 1] - ff[j], k.ranges->stats))
-        for (uint32_t f = ff[j]; f < ff[j + 1]; f++) count_frame(f);
+      k.ranges->stats[kRangeStatFramesCompared] += s.compared;
+      if (!zge::table_fails(dres[idx[j]], s, u.ent[j].nframes)) continue;
+      count_frames(sink, zge::hashed_frames(u.ent[j], false));
+      k.ranges->stats[kRangeStatEntriesFailedTable]++;
     }
   if (gated && (st = scatter())) return st;
   uint64_t us = 0;
@@ -529,23 +479,13 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   sink.stats[kDevStatScatterLaunches] += launched ? 1u : 0u; sink.stats[kDevStatBytesScattered] += bytes; sink.stats[kDevStatScatterUs] += us;
   for (uint32_t j = 0; j < n; j++) {
     zgpu_device_entry_result& d = dres[idx[j]];
-    zgpu_entry_result& r = d.r;
-    if (r.status || r.nframes == 0) continue;
+    if (d.r.status || d.r.nframes == 0) continue;
     if (sink.collect)
       for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-        if (!h.on_dev[f] || b->info[f].src_begin < u.off[j]) return ZGPU_E_INTERNAL;   // (never: hash_every)
-        (*sink.collect)[idx[j]].push_back(DeviceSink::Digest{b->info[f].src_begin - u.off[j], b->info[f].src_end - b->info[f].src_begin, h.digest[f]});
+        if (!u.fr[f].hashed || b->info[f].src_begin < u.off[j]) return ZGPU_E_INTERNAL;   // (never: hash_every)
+        (*sink.collect)[idx[j]].push_back(DeviceSink::Digest{u.fr[f].begin, u.fr[f].clen, u.fr[f].digest});
       }
-    for (uint32_t f = ff[j]; f < ff[j + 1]; f++) {
-      const FrameInfo& fi = b->info[f];
-      const uint32_t calc = (uint32_t)h.digest[f];
-      count_frame(f);
-      if (f == ff[j]) { r.checksum_from_data = fi.has_checksum ? fi.checksum : 0u; r.calculated_checksum = h.on_dev[f] ? calc : 0u; d.first_hashed = h.on_dev[f]; }
-      if (!fi.has_checksum) continue;
-      r.checksums++;
-      if (!h.on_dev[f]) d.checksums_unverified++;
-      else if (fi.checksum != calc) r.checksum_mismatches++;
-    }
+    count_frames(sink, zge::fill(u.ent[j], sink.no_hash, &d.r, &d.checksums_unverified, &d.first_hashed));
   }
   return ZGPU_OK;
 }
@@ -558,69 +498,70 @@ int run_submit(Call& k, const uint32_t* idx, uint32_t n) {
   return k.sink ? sink_device(k, idx, n, u) : sink_host(k, idx, n, u);
 }
 
-// an entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
-// which also hashes what it hands out)
-int decode_alone(Call& k, uint32_t i, bool dict_walk, uint8_t* dst, size_t cap, bool* summed = nullptr, const uint8_t* host_src = nullptr,
-                 uint32_t* size_lies = nullptr, std::vector<ZgFrameSum>* frames = nullptr) {
-  const uint8_t* src = host_src ? host_src : k.srcs[i];   // (device sources: the entry's bytes downloaded by decode_alone_device)
-  zgpu_entry_result& r = k.result(i);
-  memset(&r, 0, sizeof r);
-  ZgFrameSums sums;
+// host memory of an entry that is decoded alone (not zeroed: it may be as large as the entry's plaintext)
+using HostBuf = std::unique_ptr<uint8_t, decltype(&free)>;
+inline HostBuf host_buf(size_t n) { return HostBuf((uint8_t*)malloc(n ? n : 1), &free); }
+
+// An entry the submit did not serve: zgpu_decode_all on it alone (its dictionary frames go frame by frame through the FrameDecoder mirror,
+// which also hashes what it hands out). What comes back is the facts of the entry (zg_entry.h), as a submit produces them for its entries,
+// for the same ladder and the same fill — call: the status the CALL ends with (NOMEM, HIP), then nothing else means anything.
+// The differences of this producer, each a property of the facts: the decoder's status is the decode verdict and carries the walk's and, without
+// ranges, zgpu_decode_all's own order (dict stays false); every frame is hashed, by the host; the digests hold 32 bits.
+struct Alone { int call = ZGPU_OK; zge::Entry e; std::vector<zge::Frame> fr; };
+Alone decode_alone(Call& k, uint32_t i, bool dict_walk, const uint8_t* src, uint8_t* dst, size_t cap) {
+  Alone a;
   size_t w = 0;
   int st;
-  bool sums_ok = true;
   if (dict_walk) {
     // (what zgpu_decode_all does with this entry: its walk meets a dictionary frame, and dictionaries are registered)
-    st = zg_decode_all_per_frame(k.c, src, k.lens[i], dst, cap, &w, &sums);
+    st = zg_decode_all_per_frame(k.c, src, k.lens[i], dst, cap, &w, &a.fr);
   } else {
     st = zgpu_decode_all(k.c, src, k.lens[i], dst, cap, &w);
     if (!st) {
-      // (Unsupported / Internal in a larger submit, but not alone — never seen; the status stays zgpu_decode_all's.) The checksums come from a
-      // second, frame-by-frame pass into a buffer of its own; should that pass fail or disagree, the entry reports none rather than a wrong one.
+      // (Unsupported / Internal in a larger submit, but not alone — never seen; the status stays zgpu_decode_all's.) The frames come from a
+      // second, frame-by-frame pass into a buffer of its own; should that pass fail or disagree, the frames are not known: they are counted
+      // from their headers and the entry reports no checksum rather than a wrong one.
       size_t w2 = 0;
-      uint8_t* tmp = (uint8_t*)malloc(w ? w : 1);
-      if (!tmp) return ZGPU_E_NOMEM;
-      const int s2 = zg_decode_all_per_frame(k.c, src, k.lens[i], tmp, w, &w2, &sums);
-      sums_ok = s2 == ZGPU_OK && w2 == w && (w == 0 || memcmp(tmp, dst, w) == 0);
-      free(tmp);
-      if (s2 == ZGPU_E_NOMEM || s2 == ZGPU_E_HIP) return s2;
+      const HostBuf tmp = host_buf(w);
+      if (!tmp) { a.call = ZGPU_E_NOMEM; return a; }
+      const int s2 = zg_decode_all_per_frame(k.c, src, k.lens[i], tmp.get(), w, &w2, &a.fr);
+      a.e.known = s2 == ZGPU_OK && w2 == w && (w == 0 || memcmp(tmp.get(), dst, w) == 0);
+      if (s2 == ZGPU_E_NOMEM || s2 == ZGPU_E_HIP) { a.call = s2; return a; }
     }
   }
-  if (st == ZGPU_E_NOMEM || st == ZGPU_E_HIP) return st;
-  r.status = st;
-  if (st) return ZGPU_OK;
-  if (summed) *summed = sums_ok;
-  if (size_lies) *size_lies = sums.size_lies;
-  if (frames && sums_ok) frames->swap(sums.frames);
-  if (!sums_ok) {   // the frames are counted from their headers; no checksum is reported
+  if (st == ZGPU_E_NOMEM || st == ZGPU_E_HIP) { a.call = st; return a; }
+  a.e.decode = st;
+  if (st || !a.e.known) a.fr.clear();
+  if (st) return a;
+  a.e.total = w;
+  a.e.nframes = (uint32_t)a.fr.size();
+  if (!a.e.known) {
     std::vector<FrameSpan> sp;
     (void)split_frames(src, k.lens[i], &sp);
-    r.written = w;
-    for (const FrameSpan& x : sp) r.nframes += x.skippable ? 0u : 1u;
-    return ZGPU_OK;
+    for (const FrameSpan& x : sp) a.e.nframes += x.skippable ? 0u : 1u;
   }
-  r.written = w;
-  r.nframes = sums.nframes; r.checksums = sums.checksums; r.checksum_mismatches = sums.mismatches;
-  r.checksum_from_data = sums.first_data; r.calculated_checksum = sums.first_calc;
+  a.e.fr = a.fr.data();
+  return a;
+}
+
+// the host sink's entry of the again-list
+int decode_alone_host(Call& k, uint32_t i, bool dict_walk) {
+  const Alone a = decode_alone(k, i, dict_walk, k.srcs[i], k.dsts[i], k.caps[i]);
+  if (a.call) return a.call;
+  zgpu_entry_result& r = k.res[i];
+  memset(&r, 0, sizeof r);
+  r.status = zge::ladder(a.e, k.mode(i)).status;
+  if (r.status) return ZGPU_OK;
+  r.written = a.e.total; r.nframes = a.e.nframes;   // (no ranges: everything that was decoded)
+  zge::fill(a.e, false, &r, nullptr, nullptr);
   return ZGPU_OK;
 }
 
-// ZGPU_DEVICE_VERIFY_SEEK_TABLE on an entry decoded alone: its frame list and digests (zg_seeksums.h) from the frames the host hashed. A frame
-// of 2^32 bytes or more is left out, as in a submit; one longer than a nonzero hash_max_bytes is listed unhashed.
-void alone_frames(const DeviceSink& sink, const std::vector<ZgFrameSum>& frames, std::vector<zgv::Frame>* list, std::vector<uint64_t>* dig) {
-  for (const ZgFrameSum& f : frames) {
-    if (f.end - f.begin > 0xFFFFFFFFull) continue;
-    const bool hashed = sink.table_all || f.yielded <= sink.hash_max;
-    list->push_back(zgv::Frame{f.begin, (uint32_t)(f.end - f.begin), hashed ? (uint32_t)dig->size() : zgv::kNotHashed});
-    if (hashed) dig->push_back(f.calc);
-  }
-}
-
-// the device sink's form of decode_alone: into a host buffer (no larger than the entry can need), then one H2D to the caller's memory. The host
-// hashed what it decoded, whatever its length; with hashing off the entry reports its checksums as unverified like every other one.
+// The device sink's form: into a host buffer (no larger than the entry can need), then the entry's pieces H2D to the caller's memory — the
+// same ladder, verdicts and fill as a submit's entries get (zg_entry.h). What is this path's own: the D2H of a device source, the host buffer,
+// the download of footer, rows, pairs and sums for the host's form of the table compare, and the uploads.
 int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   DeviceSink& sink = *k.sink;
-  const bool clip = k.ranges != nullptr;   // (the entry's span of clips: Call::fit, and the uploads below)
   std::vector<uint8_t> down;   // device sources: the entry comes to the host with one D2H (rare; correct first)
   if (k.src) {
     try { down.resize(k.lens[i] ? k.lens[i] : 1); } catch (...) { return ZGPU_E_NOMEM; }
@@ -629,115 +570,103 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
   }
   const uint8_t* src = k.src ? down.data() : k.srcs[i];
   const uint64_t bound = plaintext_bound(src, k.lens[i]);
-  // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i]. Ranges: the whole selection is decoded, and clipped below)
-  const size_t cap = clip ? (size_t)bound : k.caps[i] < bound ? k.caps[i] : (size_t)bound;
-  uint8_t* tmp = (uint8_t*)malloc(cap ? cap : 1);
+  // (beyond the bound nothing can be written: TargetTooSmall is decided as with caps[i]. Ranges: the whole selection is decoded, and clipped
+  // below — the buffer holds the selection's bound, every frame's declared size or what its block headers allow where that is less, so only a
+  // frame that yields more than it declares can overflow it: Entry::bound_buffer)
+  const size_t cap = k.ranges ? (size_t)bound : k.caps[i] < bound ? k.caps[i] : (size_t)bound;
+  const HostBuf tmp = host_buf(cap);
   if (!tmp) return ZGPU_E_NOMEM;
-  bool summed = false;
-  uint32_t size_lies = 0;
-  std::vector<ZgFrameSum> frames;   // (ZGPU_DEVICE_VERIFY_SEEK_TABLE) where every decoded frame lies in the selection, and its digest
-  int st = decode_alone(k, i, dict_walk, tmp, cap, &summed, src, &size_lies, sink.compared(i) || sink.collect ? &frames : nullptr);
+  Alone a = decode_alone(k, i, dict_walk, src, tmp.get(), cap);
+  a.e.bound_buffer = k.ranges != nullptr;
+  const zge::Entry& e = a.e;
   zgpu_device_entry_result& d = sink.res[i];
-  d.checksums_unverified = 0;
-  d.first_hashed = 0;
-  const bool ok = !st;   // (the call itself goes on; below, `ok && !d.r.status` is an entry that still stands)
-  if (k.ranges && ok && !d.r.status) { k.ranges->stats[kRangeStatFramesDecoded] += d.r.nframes; k.ranges->stats[kRangeStatPlaintextDecoded] += d.r.written; }
-  // ranges, in the order of a submit's verdicts (decode_submit): the size check, TargetTooSmall by the clipped count, then the checksums.
-  // The size check is per frame, from the frame-by-frame pass; should that pass have failed (never seen), the frames are measured together.
-  // The buffer holds the selection's bound: every frame's declared size, or what its block headers allow where that is less. Only a frame
-  // that yields more than it declares can overflow it.
-  if (clip && ok && d.r.status == ZGPU_E_TARGET_TOO_SMALL) fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
-  if (clip && ok && !d.r.status &&
-      ((summed ? size_lies != 0 : k.ranges->declared[i] != UINT64_MAX && d.r.written != k.ranges->declared[i]) ||
-       (k.ranges->promise && d.r.written != k.ranges->declared[i])))
-    fail_entry(d, ZGPU_E_CONTENT_SIZE_MISMATCH);
-  uint64_t fits = 0;   // (ranges) what the clips that have room get together
-  if (clip && ok && !d.r.status) {
-    bool too_small = false;
-    fits = k.fit(i, d.r.written, &too_small);
-    if (too_small) fail_entry(d, ZGPU_E_TARGET_TOO_SMALL);
-  }
-  // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its one H2D
-  if (ok && !d.r.status && sink.verify && summed && !sink.no_hash && d.r.checksum_mismatches) {
-    sink.stats[kDevStatFramesHashed] += d.r.nframes;
-    fail_entry(d, ZGPU_E_CHECKSUM_MISMATCH, d.r.checksums, d.r.checksum_mismatches);
-    sink.stats[kDevStatEntriesFailedVerify]++;
-  }
-  // ZGPU_DEVICE_VERIFY_SEEK_TABLE, last: zg_seeksums.h's rule over rows the host holds — the footer and rows [first, first + taken) come down (the
-  // entry crossed to the host anyway), the host hashed every frame (a frame longer than a nonzero hash_max_bytes passes uncompared, as in a
-  // submit). Should the frame-by-frame pass have failed (never seen), nothing is known of the frames and nothing vouches for them.
-  std::vector<zgv::Frame> list;   // the frame list and digests of either route, as a submit would build them
-  std::vector<uint64_t> dig;
-  if (ok && !d.r.status && d.r.nframes && sink.compared(i)) alone_frames(sink, frames, &list, &dig);
-  // what both routes end with: a why is the call's error, else the verdict (0, or the status the call ends with; tmp is freed then)
-  auto verdict = [&](const zgv::Sums& rec, const char* changed) -> int {
-    if (rec.why) { k.c->eng->last_error = changed; free(tmp); return ZGPU_E_INTERNAL; }
-    const uint32_t nframes = d.r.nframes;
-    if (table_verdict(d, rec, nframes, k.ranges->stats)) sink.stats[kDevStatFramesHashed] += nframes;
-    return ZGPU_OK;
-  };
-  if (ok && !d.r.status && d.r.nframes && sink.table(i)) {
-    const DeviceSink::TableEntry& e = sink.table_verify[i];
-    zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
-    if (summed && e.len >= zgt::kFraming) {
-      uint8_t footer[9];
-      uint32_t es = 8;
-      uint64_t rows_off = 0;
-      if (hipMemcpy(footer, (const uint8_t*)(uintptr_t)e.src + (e.len - 9), 9, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
-      rec.why = zgv::locate_rows(footer, e.len, e.first, e.taken, &es, &rows_off);
-      std::vector<uint8_t> rows;
-      if (!rec.why) {
-        try { rows.resize((size_t)e.taken * es); } catch (...) { free(tmp); return ZGPU_E_NOMEM; }
-        if (hipMemcpy(rows.data(), (const uint8_t*)(uintptr_t)e.src + rows_off, rows.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
-        k.src->stats[kSrcStatInputBytesToHost] += 9 + rows.size();
-        rec = zgv::sums_rows(rows.data(), es, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
-      }
-    } else if (summed) rec.why = zgt::kNone;
-    if ((st = verdict(rec, kTableChanged))) return st;
-  }
-  // the same flag by the handle (zg_idxsums.h: sums_pairs): C of rows [first, first + taken] and their sums come down from the handle's arrays
-  if (ok && !d.r.status && d.r.nframes && sink.by_handle(i)) {
-    const DeviceSink::HandleEntry& e = sink.handle_verify[i];
-    const DeviceSink::Handle& hd = *sink.handle;
-    zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
-    if (summed) {
-      if (e.pair0 > hd.npairs || (uint64_t)e.nrows + 1 > hd.npairs - e.pair0 || e.sum0 > hd.nsums || e.nrows > hd.nsums - e.sum0 || (uint64_t)e.first + e.taken > e.nrows)
-        rec.why = zgv::kRows;
-      else {
-        std::vector<uint64_t> pairs, cs;
-        std::vector<uint32_t> rs;
-        try { pairs.resize(2 * ((size_t)e.taken + 1)); cs.resize((size_t)e.taken + 1); rs.resize(e.taken); } catch (...) { free(tmp); return ZGPU_E_NOMEM; }
-        if (hipMemcpy(pairs.data(), (const uint8_t*)hd.pairs + 16 * (e.pair0 + e.first), pairs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(rs.data(), hd.sums + e.sum0 + e.first, rs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); free(tmp); return ZGPU_E_HIP; }
-        for (size_t q = 0; q < cs.size(); q++) cs[q] = pairs[2 * q];
-        rec = zgh::sums_pairs(cs.data(), rs.data(), e.nrows, e.first, e.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
-      }
+  int st = a.call;
+  if (!st) {
+    // (work done, counted here and not in the submit. A difference between the producers that is kept as it was found: an entry whose DECODE
+    // fails alone is not counted — the decoder says nothing of its frames —, one that fails to decode in a submit is. LABNOTES.md "entry facts")
+    if (k.ranges && !e.decode) { k.ranges->stats[kRangeStatFramesDecoded] += e.nframes; k.ranges->stats[kRangeStatPlaintextDecoded] += e.total; }
+    const zge::Verdict v = zge::ladder(e, k.mode(i));
+    fail_entry(d, v.status);   // (or status 0, for now with nothing written)
+    // ZGPU_DEVICE_VERIFY: the host hashed every frame of the entry as it decoded it; a mismatch fails the entry before its uploads
+    if (!d.r.status && sink.verify && zge::verify_fails(d, e)) { sink.stats[kDevStatFramesHashed] += e.nframes; sink.stats[kDevStatEntriesFailedVerify]++; }
+    // ZGPU_DEVICE_VERIFY_SEEK_TABLE, last: zg_seeksums.h's rule over rows the host holds — the footer and rows [first, first + taken) come down (the
+    // entry crossed to the host anyway). The host hashed every frame, but a frame longer than a nonzero hash_max_bytes passes uncompared, as in
+    // a submit. Should the frames not be known (never seen), the list is empty and nothing vouches for them.
+    std::vector<zgv::Frame> list;   // the frame list and digests of either route, as a submit would build them
+    std::vector<uint64_t> dig;
+    const bool compared = !d.r.status && e.nframes && sink.compared(i);
+    if (compared) {
+      zge::compare_list(e, [&](const zge::Frame& f) { return sink.table_all || f.yielded <= sink.hash_max; }, &list);
+      for (const zge::Frame& f : a.fr) dig.push_back(f.digest);
     }
-    if ((st = verdict(rec, kHandleChanged))) return st;
-  }
-  if (sink.collect && ok && !d.r.status) {
-    if (!summed) { k.c->eng->last_error = "zgpu_seek_index_hash_device: an entry decoded alone that could not be hashed frame by frame"; free(tmp); return ZGPU_E_INTERNAL; }   // (never seen)
-    for (const ZgFrameSum& f : frames) (*sink.collect)[i].push_back(DeviceSink::Digest{f.begin, f.end - f.begin, f.calc});
-  }
-  // ranges: only the clipped bytes are uploaded, every clip of the span that has room to its own destination
-  if (clip && ok && !d.r.status) {
-    const uint64_t decoded = d.r.written;
-    d.r.written = fits;
-    for (uint32_t q = k.ranges->first[i]; q < k.ranges->first[i + 1] && !st; q++) {
-      const Clip& cl = k.ranges->clip[q];
-      const size_t from = (size_t)(cl.skip < decoded ? cl.skip : decoded);
-      if (!cl.small && cl.written && hipMemcpy(cl.dst, tmp + from, cl.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    // what both routes end with: a why is the call's error, else the verdict (a failed entry counts its frames as hashed: the host hashed them)
+    auto verdict = [&](const zgv::Sums& rec, const char* changed) -> int {
+      if (rec.why) { k.c->eng->last_error = changed; return ZGPU_E_INTERNAL; }
+      k.ranges->stats[kRangeStatFramesCompared] += rec.compared;
+      if (zge::table_fails(d, rec, e.nframes)) { sink.stats[kDevStatFramesHashed] += e.nframes; k.ranges->stats[kRangeStatEntriesFailedTable]++; }
+      return ZGPU_OK;
+    };
+    if (compared && sink.table(i)) {
+      const DeviceSink::TableEntry& t = sink.table_verify[i];
+      zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
+      if (e.known && t.len >= zgt::kFraming) {
+        uint8_t footer[9];
+        uint32_t es = 8;
+        uint64_t rows_off = 0;
+        if (hipMemcpy(footer, (const uint8_t*)(uintptr_t)t.src + (t.len - 9), 9, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+        rec.why = zgv::locate_rows(footer, t.len, t.first, t.taken, &es, &rows_off);
+        std::vector<uint8_t> rows;
+        if (!rec.why) {
+          try { rows.resize((size_t)t.taken * es); } catch (...) { return ZGPU_E_NOMEM; }
+          if (hipMemcpy(rows.data(), (const uint8_t*)(uintptr_t)t.src + rows_off, rows.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+          k.src->stats[kSrcStatInputBytesToHost] += 9 + rows.size();
+          rec = zgv::sums_rows(rows.data(), es, t.first, t.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
+        }
+      } else if (e.known) rec.why = zgt::kNone;
+      if ((st = verdict(rec, kTableChanged))) return st;
+    }
+    // the same flag by the handle (zg_idxsums.h: sums_pairs): C of rows [first, first + taken] and their sums come down from the handle's arrays
+    if (compared && sink.by_handle(i)) {
+      const DeviceSink::HandleEntry& t = sink.handle_verify[i];
+      const DeviceSink::Handle& hd = *sink.handle;
+      zgv::Sums rec{0, 0, 0, 0, zgv::kNoRow, 0, 0, 0};
+      if (e.known) {
+        if (t.pair0 > hd.npairs || (uint64_t)t.nrows + 1 > hd.npairs - t.pair0 || t.sum0 > hd.nsums || t.nrows > hd.nsums - t.sum0 || (uint64_t)t.first + t.taken > t.nrows)
+          rec.why = zgv::kRows;
+        else {
+          std::vector<uint64_t> pairs, cs;
+          std::vector<uint32_t> rs;
+          try { pairs.resize(2 * ((size_t)t.taken + 1)); cs.resize((size_t)t.taken + 1); rs.resize(t.taken); } catch (...) { return ZGPU_E_NOMEM; }
+          if (hipMemcpy(pairs.data(), (const uint8_t*)hd.pairs + 16 * (t.pair0 + t.first), pairs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(rs.data(), hd.sums + t.sum0 + t.first, rs.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+          for (size_t q = 0; q < cs.size(); q++) cs[q] = pairs[2 * q];
+          rec = zgh::sums_pairs(cs.data(), rs.data(), t.nrows, t.first, t.taken, list.data(), (uint32_t)list.size(), dig.data(), (uint32_t)dig.size());
+        }
+      }
+      if ((st = verdict(rec, kHandleChanged))) return st;
+    }
+    if (sink.collect && !d.r.status) {
+      if (!e.known) { k.c->eng->last_error = "zgpu_seek_index_hash_device: an entry decoded alone that could not be hashed frame by frame"; return ZGPU_E_INTERNAL; }   // (never seen)
+      for (const zge::Frame& f : a.fr) (*sink.collect)[i].push_back(DeviceSink::Digest{f.begin, f.clen, f.digest});
+    }
+    if (!d.r.status) {
+      // The uploads. The host buffer holds the frames back to back: as far as the pieces go it is ONE frame of e.total bytes (which is also all
+      // that is known of an entry whose frames are not), so every clip that has room is one H2D; no ranges: the whole entry is one clip.
+      zge::Frame buf{};
+      buf.yielded = buf.end = e.total;
+      zge::Clip whole;
+      uint32_t nclips;
+      const zge::Clip* cl = k.clips(i, v.written, &whole, &nclips);
+      for (uint32_t q = 0; q < nclips; q++)
+        zge::clip_pieces(&buf, 1, cl[q], [&](const zge::Piece& p) {
+          if (!st && hipMemcpy(cl[q].dst + p.at, tmp.get() + p.cat, p.len, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+        });
+      d.r.written = v.written; d.r.nframes = e.nframes;
+      sink.alone_written += d.r.written;
+      // (hashing off: the entry reports its checksums as unverified like every other one, though the host hashed them)
+      count_frames(sink, zge::fill(e, sink.no_hash, &d.r, &d.checksums_unverified, &d.first_hashed));
     }
   }
-  if (ok && !d.r.status) {
-    if (!clip && d.r.written && hipMemcpy(k.dsts[i], tmp, d.r.written, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
-    sink.alone_written += d.r.written;
-    const bool hashed = summed && !sink.no_hash && d.r.nframes;
-    if (sink.no_hash) { d.checksums_unverified = d.r.checksums; d.r.checksum_mismatches = 0; d.r.calculated_checksum = 0; }
-    d.first_hashed = hashed ? 1u : 0u;
-    sink.stats[hashed ? kDevStatFramesHashed : kDevStatFramesNotHashed] += d.r.nframes;
-  }
-  free(tmp);
   sink.stats[kDevStatEntriesAlone]++;
   return st;
 }
@@ -789,7 +718,7 @@ int decode_entries(Call& k, uint32_t n) {
   }
   for (size_t q = 0; q < k.again.size() && !st; q++) {
     const uint32_t i = k.again[q].first;
-    st = k.sink ? decode_alone_device(k, i, k.again[q].second) : decode_alone(k, i, k.again[q].second, k.dsts[i], k.caps[i]);
+    st = k.sink ? decode_alone_device(k, i, k.again[q].second) : decode_alone_host(k, i, k.again[q].second);
   }
   return st;
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include <vector>
 #include "zg_capi_int.h"
+#include "zg_entry.h"
 
 namespace zgf {
 
@@ -56,9 +57,8 @@ struct Selection {
   uint32_t first_row, rows;       // DeviceSink::TableEntry::first / taken (rows == 0: not looked at)
   uint8_t refused;                // 0, 1 (its source or destination failed the pointer check), or the status itself (ZGPU_E_SEEK_TABLE)
 };
-// Of the concatenation of a sub-entry's decoded frames only [skip, skip + len) goes to dst. small / written: the clip's own verdict and count
-// once the sub-entry's frames are measured; they mean something only where the sub-entry stands at status 0.
-struct Clip { uint64_t skip, len; uint8_t* dst; uint64_t cap; uint64_t written; bool small; };
+// Of the concatenation of a sub-entry's decoded frames only [skip, skip + len) goes to dst (zg_entry.h, with the verdicts that fill it in).
+using zge::Clip;
 // The selections decoded, each a sub-entry with a SPAN of clips, clip[first[i] .. first[i + 1]), and one result in dres. promise: `declared`
 // is a seek table's promise, which always holds — a selection that yields another length fails with ContentSizeMismatch. want_bound, if
 // given: the plaintext bound every selection of nonzero length must walk to (not compared while shared dictionaries put gaps into the walk's).
