@@ -719,6 +719,79 @@ int zgpu_seek_index_read_sums(const zgpu_seek_index*, uint32_t entry, uint32_t* 
 int zgpu_seek_index_sums_of(const zgpu_seek_index*, uint32_t i, zgpu_seek_index_sums* out);
 int zgpu_seek_index_export_seek_table_ex(const zgpu_seek_index*, uint32_t entry, uint32_t flags, uint8_t* host_dst, size_t cap, size_t* written);
 
+/* ---- record index: gather delimited records of indexed shards by number -----------------------------------------------------------------------
+ * Every call above speaks in plaintext BYTE offsets. A shard of text (one document per line) is asked for by record NUMBER. A handle may hold,
+ * beside its pairs and sums, the RECORD OFFSETS of an entry in device memory, and two calls take record numbers in front of the indexed gather.
+ * Definitions, for an indexed entry with plaintext P of length L = info.plaintext and a delimiter byte d (0 .. 255):
+ *  - a record is a maximal run of bytes ending in d; the delimiter belongs to the record it ends;
+ *  - if L > 0 and P[L - 1] != d, the bytes behind the last delimiter are one more record, the OPEN TAIL;
+ *  - R is the number of records (L == 0: R == 0); the entry's offsets are O[0 .. R], 64 bits each: O[0] = 0, O[r] the position just behind
+ *    the r-th delimiter, O[R] = L; O is strictly increasing; record r is plaintext [O[r], O[r + 1]);
+ *  - records ignore frame and row boundaries: a record may straddle frames, runs and submits; skippable rows contribute nothing.
+ * A RECORD INDEX, LIKE THE PAIRS, IS A PROMISE ABOUT BYTES, NOT A VERDICT: offsets that no longer describe the shard (a stale index, a wrong
+ * zgpu_seek_index_set_records) deliver the wrong bytes with status 0. Only the handle's sums under ZGPU_DEVICE_VERIFY_SEEK_TABLE catch a shard
+ * that changed.
+ * zgpu_seek_index_records_device decodes every zstd frame of every chosen entry ONCE, as zgpu_seek_index_hash_device does, finds every byte
+ * equal to `delimiter` on the device and keeps the offsets in the handle; nothing is delivered. The argument rules are that call's: n must be
+ * the handle's entry count and the handle this context's (else ZGPU_E_BAD_ARG); which_or_null chooses entries; an entry the index refused is
+ * skipped and its record carries the index's status; a chosen entry whose pointer check fails or whose lens[i] != info.len gets
+ * ZGPU_E_BAD_ARG in its record and keeps what it held; delimiter > 255 is ZGPU_E_BAD_ARG for the whole call. Runs are cut by the same rule
+ * (run_bytes, 0: 64 MiB) and each run is one selection decoded under its promise D[k1] - D[k0] (a stale index: ZGPU_E_CONTENT_SIZE_MISMATCH);
+ * dictionary frames and entries that go alone are served as in the gather calls (an entry decoded alone is searched on the host, by the same
+ * definition). No frame is hashed. ALL OR NOTHING PER ENTRY: if any run ends in a status the entry keeps no offsets (state 0), its record
+ * names the first failing run's rows and zgpu_last_error names entry, run and status; a failing entry does not disturb another. The return
+ * value reports engine failures only, and such a failure leaves the whole handle as it was. The streams are drained on return. Running the
+ * pass on an entry again, with the same or another delimiter, replaces its offsets.
+ * On the device, per submit, behind the submit's verdicts (zg_records.h): zg_k_recs_count — one wave per chunk of 4096 plaintext bytes of
+ * one decoded frame, 16-byte loads, the ragged head and tail byte by byte, a population count per chunk —, zg_k_recs_scan — the exclusive
+ * prefix of the counts, the submit's total and the frames' totals, which come back to the host (8 + 8 bytes per frame: the one round trip
+ * per submit) and size the submit's staging —, zg_k_recs_emit — the same chunks, a wave-level prefix of the lanes' counts, every offset stored
+ * once, already in the entry's coordinates. The staging buffers live until every run has its verdict; then the handle's array — 8 bytes per
+ * offset, R + 1 per entry — is allocated anew and filled by device-to-device copies in row order, O[0] = 0 in front and O[R] = L appended
+ * for an open tail. PEAK EXTRA DEVICE MEMORY IS TWICE THE FINAL ARRAY, beside the array a repeated pass replaces.
+ * zgpu_seek_index_read_records downloads O[first .. min(first + cap, R + 1)) of an entry into host memory, *n = how many (host_dst == NULL
+ * with cap == 0 asks for R + 1 in *n). zgpu_seek_index_set_records uploads offsets the caller kept (a sidecar file): offsets[0] == 0, strictly
+ * increasing, offsets[nrecords] == info.plaintext (so nrecords == 0 needs info.plaintext == 0), the delimiter in the low bits of `delimiter`
+ * and ZGPU_RECORDS_OPEN_TAIL in its top bit if the last record ends in no delimiter (the call cannot see the bytes; what
+ * zgpu_seek_index_records_of reports as flags bit 0 is that bit) — else ZGPU_E_BAD_ARG, and nothing changes. State 2 is the caller's promise.
+ * ZGPU_E_BAD_ARG: a null argument, an entry out of range, an entry the index refused, reading an entry without records.
+ * zgpu_seek_index_record_ranges_device turns m record ranges into byte ranges with ONE zg_k_recs_find launch, one lane per range; nothing of
+ * any entry is read. [first, first + count) is clipped to [0, R) as byte ranges clip to the plaintext (the sum saturates): first >= R or
+ * count == 0 gives { begin = O[min(first, R)], len = 0 }; else begin = O[first], len = O[last + 1] - O[first], and with ZGPU_RECORDS_STRIP
+ * len is one less unless the last record taken is the open tail. status[j], decided on the host before the launch, in this order: entry out
+ * of range or unknown flag bits: ZGPU_E_BAD_ARG; the index's own status for a refused entry; ZGPU_E_BAD_ARG for an entry without records.
+ * A range with a status has out[j] = { 0, 0, entry, 0 }; a failing range never disturbs another.
+ * zgpu_gather_records_indexed_device_src is that lookup followed by zgpu_gather_ranges_indexed_device_src on the byte ranges: the same
+ * groups, verdict order, per-range destinations and options (ZGPU_E_TARGET_TOO_SMALL is the range's own; ZGPU_DEVICE_VERIFY and
+ * ZGPU_DEVICE_VERIFY_SEEK_TABLE by the handle's sums; no byte of a failed range's destination is written). A range whose lookup failed
+ * carries that status in results[j].d.r.status and the gather skips it. The cost over the byte gather: one launch and 24 * m bytes back.
+ * Diagnostics: zgpu_seek_index_stats appends [14] decode submits of the record passes, [15] the microseconds of count + scan + emit (HIP
+ * events), [16] chunks scanned, [17] records held, [18] bytes of offsets held, [19] bytes that came back from the side pass. A caller that
+ * asks for 14 gets what it always got. zgpu_debug_ranges_stats appends [19] record find launches, [20] their microseconds, [21] bytes back.
+ * Out of scope: host sources, several GPUs, multi-byte delimiters, length-prefixed records, hashing and record finding in one decode, offsets
+ * narrower than 64 bits, the lookup fused into the gather's find kernel, updating in place. */
+typedef struct {
+  uint32_t status;      /* of the last zgpu_seek_index_records_device that chose the entry (0; the index's status; ZGPU_E_BAD_ARG; the failing run's) */
+  uint32_t state;       /* 0 none, 1 found by the pass, 2 set by the caller */
+  uint32_t delimiter;
+  uint32_t flags;       /* bit 0: open tail */
+  uint64_t nrecords;
+  uint32_t row_lo, row_hi;   /* status != 0 from a run: its rows */
+} zgpu_seek_index_records;
+typedef struct { uint64_t first, count; uint32_t entry, flags; } zgpu_record_range;   /* records [first, first + count) of entry `entry` */
+#define ZGPU_RECORDS_STRIP 1u   /* zgpu_record_range.flags: drop the final delimiter of the last record taken (an open tail has none) */
+#define ZGPU_RECORDS_OPEN_TAIL 0x80000000u   /* zgpu_seek_index_set_records' delimiter word: the last record ends in no delimiter */
+int zgpu_seek_index_records_device(zgpu_ctx*, zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                   const uint8_t* which_or_null, uint32_t delimiter, uint64_t run_bytes);
+int zgpu_seek_index_records_of(const zgpu_seek_index*, uint32_t i, zgpu_seek_index_records* out);
+int zgpu_seek_index_read_records(const zgpu_seek_index*, uint32_t entry, uint64_t first, uint64_t* host_dst, uint64_t cap, uint64_t* n);
+int zgpu_seek_index_set_records(zgpu_seek_index*, uint32_t entry, const uint64_t* offsets /* nrecords + 1 */, uint64_t nrecords, uint32_t delimiter);
+int zgpu_seek_index_record_ranges_device(zgpu_ctx*, const zgpu_seek_index*, const zgpu_record_range* recs, uint32_t m,
+                                         zgpu_entry_range* out /* m */, uint32_t* status /* m */);
+int zgpu_gather_records_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                           const zgpu_record_range* recs, uint32_t m, void* const* device_dsts /* m */,
+                                           const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
+
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of
  * FrameDecoder::decode_all (frame_decoder.rs:541-577), which decodes the frames of a buffer one after the other. */

@@ -36,6 +36,9 @@ enum { kRangeStatSeekLaunches = 0, kRangeStatSeekUs, kRangeStatSeekBytesDownload
 // what zgpu_debug_ranges_stats appends behind the slots above (out[13] ...): the calls that take many ranges per entry (zg_seekmany.h)
 enum { kManyStatGroupsDecoded = 0, kManyStatPrefixLaunches, kManyStatPrefixUs, kManyStatFindLaunches, kManyStatFindUs, kManyStatPrefixScratchBytes,
        kManyStatCount };
+// and behind those (out[19] ...): the lookup of the calls that take record numbers (zg_records.h) — zg_k_recs_find launches, their microseconds
+// (HIP events), the bytes they brought back (24 per range)
+enum { kRecFindStatLaunches = 0, kRecFindStatUs, kRecFindStatBytesDownloaded, kRecFindStatCount };
 static_assert(kSrcStatWalkLaunches == zg::kPassLaunches && kSrcStatWalkUs == zg::kPassUs && kSrcStatSkeletonBytes == zg::kPassBytes &&
               kIndexStatLaunches == zg::kPassLaunches && kIndexStatKernelUs == zg::kPassUs && kIndexStatBytesDownloaded == zg::kPassBytes &&
               kRangeStatSeekLaunches == zg::kPassLaunches && kRangeStatSeekUs == zg::kPassUs && kRangeStatSeekBytesDownloaded == zg::kPassBytes,
@@ -55,6 +58,7 @@ struct zgpu_ctx {
   uint64_t frames_index_stats[kIndexStatCount] = {};      // zgpu_frames_index_device / zgpu_frames_table_device (zgpu_debug_frames_index_stats)
   uint64_t ranges_stats[kRangeStatCount] = {};            // the seek and decode_ranges calls (zgpu_debug_ranges_stats)
   uint64_t ranges_many_stats[kManyStatCount] = {};        //   the slots behind them (zgpu_frames_seek_table_many_device, zgpu_gather_ranges_seek_table_device_src)
+  uint64_t ranges_rec_stats[kRecFindStatCount] = {};      //   and behind those (zgpu_seek_index_record_ranges_device, zgpu_gather_records_indexed_device_src)
   uint64_t hash_ranges_us = 0;                           // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
@@ -68,6 +72,10 @@ enum { kSeekIdxStatLaunches = 0, kSeekIdxStatKernelUs, kSeekIdxStatBytesDownload
 // hash kernels' microseconds (HIP events), zstd frames hashed —; the bytes of sums the handle holds now (0 until an entry gets sums); the
 // runs the passes cut
 enum { kSumStatHashSubmits = 0, kSumStatHashUs, kSumStatFramesHashed, kSumStatSumsBytes, kSumStatHashRuns, kSumStatCount };
+// and behind those (out[14] ...): zgpu_seek_index_records_device, summed over its calls — decode submits, the microseconds of zg_k_recs_count,
+// _scan and _emit (HIP events), chunks scanned, bytes the side pass brought back (totals, open-tail probes) —; what the handle holds now:
+// records, bytes of offsets
+enum { kRecStatSubmits = 0, kRecStatUs, kRecStatChunks, kRecStatRecordsHeld, kRecStatOffsetBytes, kRecStatBytesDownloaded, kRecStatCount };
 static_assert(kSeekIdxStatLaunches == zg::kPassLaunches && kSeekIdxStatKernelUs == zg::kPassUs && kSeekIdxStatBytesDownloaded == zg::kPassBytes,
               "the array handed to the passes of the build");
 struct zgpu_seek_index {
@@ -76,12 +84,16 @@ struct zgpu_seek_index {
   uint64_t npairs = 0;                   // pairs of all indexed entries
   // pre: the index of the entry's pair 0; tab: where its table frame begins (declared kind: len); spre: the index of its sum 0; sums: what
   // zgpu_seek_index_sums_of answers (state 0: the handle vouches for nothing of it)
-  struct Ent { zgpu_seek_index_info info; uint64_t pre, tab, spre; zgpu_seek_index_sums sums; };
+  // rpre: the index of the entry's O[0] in recs (recs.state != 0); recs: what zgpu_seek_index_records_of answers
+  struct Ent { zgpu_seek_index_info info; uint64_t pre, tab, spre; zgpu_seek_index_sums sums; uint64_t rpre = 0; zgpu_seek_index_records recs = {}; };
   std::vector<Ent> ents;
   zg::DevBuf sums;                       // 4 bytes per row of every indexed entry, in the pairs' order; allocated when the first entry gets sums
   uint64_t nsums = 0;                    // rows of all indexed entries
   uint64_t stats[kSeekIdxStatCount] = {};
   uint64_t sums_stats[kSumStatCount] = {};
+  zg::DevBuf recs;                       // the record offsets (zg_records.h): 8 * (nrecords + 1) bytes per entry that has records, in entry order
+  uint64_t nrec_slots = 0;               // offsets of all such entries
+  uint64_t rec_stats[kRecStatCount] = {};
 };
 
 namespace zg { class StreamCore; }

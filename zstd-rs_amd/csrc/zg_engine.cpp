@@ -581,6 +581,13 @@ int Engine::seekidx_rows_pass(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pai
                    [&](LaneTmp& d, hipStream_t s) { zg_launch_seekidx_rows(d.lanes.as<zgx::Lane>(), n, pairs, d.out.as<zgx::Rows>(), s); });
 }
 
+int Engine::records_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, uint64_t* stats) {
+  if (!m) return ZG_OK;
+  LaneTmp t;
+  return lane_pass(t, lanes, (size_t)m * sizeof(zgr::Find), Down{out, (size_t)m * sizeof(zgr::Found)}, Down{}, stats,
+                   [&](LaneTmp& d, hipStream_t s) { zg_launch_recs_find(d.lanes.as<zgr::Find>(), m, recs, d.out.as<zgr::Found>(), s); });
+}
+
 int Engine::hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats) {
   if (!n) return ZG_OK;
   LaneTmp t;
@@ -1434,6 +1441,75 @@ int Batch::compare_wait(bool by_handle, zgv::Sums* out, uint64_t* kernel_us, uin
   *bytes = (uint64_t)p.n * sizeof(zgv::Sums);
   ZG_HIP(hipMemcpy(out, p.at<uint8_t>(p.back), (size_t)*bytes, hipMemcpyDeviceToHost));
   p.n = 0;
+  return ZG_OK;
+}
+// The records pass (zg_records.h). p's buffer holds chunks | fstart | counts | prefixes | totals; everything runs on the first stream.
+int Batch::records_launch(const zgr::Chunk* chunks, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes, uint32_t d) {
+  ZG_HIP(hipSetDevice(eng->device_));
+  SidePass& p = side_[kSideRecords];
+  p.n = 0;
+  rec_.emitted = false;
+  if (!nchunks) return ZG_OK;
+  if (!synced || d > 255u) return ZG_BAD_ARG;
+  if ((uintptr_t)dev.dst % 16) return ZG_INTERNAL;   // (never: the output lies kOutFront bytes into an allocation)
+  for (uint32_t i = 0; i < nchunks; i++) {   // a wave reads [out_off, out_off + len) and nothing else
+    const zgr::Chunk& c = chunks[i];
+    if (!c.len || c.len > zgr::kChunk || c.out_off > dev.dst_cap || c.len > dev.dst_cap - c.out_off || c.frame >= nframes) return ZG_INTERNAL;
+  }
+  for (uint32_t f = 0; f < nframes; f++) if (fstart[f] > fstart[f + 1] || fstart[f + 1] > nchunks) return ZG_INTERNAL;
+  const size_t cb = (size_t)nchunks * sizeof(zgr::Chunk), fb = ((size_t)nframes + 1) * 4;
+  rec_.counts = (cb + fb + 7) & ~(size_t)7;
+  rec_.prefix = (rec_.counts + (size_t)nchunks * 4 + 7) & ~(size_t)7;
+  rec_.totals = rec_.prefix + (size_t)nchunks * 8;
+  rec_.nframes = nframes; rec_.d = d;
+  int st = p.reserve(rec_.totals + ((size_t)nframes + 1) * 8);
+  if (st) return st;
+  hipStream_t s = eng->stream_;
+  ZG_HIP(p.upload(chunks, cb, fstart, fb, s));
+  ZG_HIP(hipStreamSynchronize(s));   // (the tables are pageable)
+  ZG_HIP(p.begin(s));
+  zg_launch_recs_count(dev.dst, p.at<zgr::Chunk>(0), nchunks, d, p.at<uint32_t>(rec_.counts), s);
+  zg_launch_recs_scan(p.at<uint32_t>(rec_.counts), nchunks, p.at<uint32_t>(cb), nframes, p.at<uint64_t>(rec_.prefix), p.at<uint64_t>(rec_.totals), s);
+  ZG_HIP(p.end(s));
+  p.n = nchunks;
+  return ZG_OK;
+}
+int Batch::records_sizes(uint64_t* total, uint64_t* ftot, uint64_t* kernel_us, uint64_t* bytes) {
+  SidePass& p = side_[kSideRecords];
+  *total = 0; *kernel_us = 0; *bytes = 0;
+  if (!p.n) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  ZG_HIP(hipStreamSynchronize(eng->stream_));
+  ZG_HIP(p.elapsed_us(kernel_us));
+  std::vector<uint64_t> t((size_t)rec_.nframes + 1);
+  *bytes = t.size() * 8;
+  ZG_HIP(hipMemcpy(t.data(), p.at<uint8_t>(rec_.totals), (size_t)*bytes, hipMemcpyDeviceToHost));
+  *total = t[0];
+  uint64_t sum = 0;
+  for (uint32_t f = 0; f < rec_.nframes; f++) { ftot[f] = t[1 + f]; sum += t[1 + f]; }
+  return sum == t[0] ? ZG_OK : ZG_INTERNAL;   // (never: the frames' chunks are all the chunks)
+}
+int Batch::records_emit(uint64_t* staging, uint64_t total) {
+  SidePass& p = side_[kSideRecords];
+  if (!p.n || !total) return ZG_OK;
+  if (!staging) return ZG_BAD_ARG;
+  ZG_HIP(hipSetDevice(eng->device_));
+  hipStream_t s = eng->stream_;
+  ZG_HIP(p.begin(s));
+  zg_launch_recs_emit(dev.dst, p.at<zgr::Chunk>(0), p.n, rec_.d, p.at<uint64_t>(rec_.prefix), staging, total, s);
+  ZG_HIP(p.end(s));
+  rec_.emitted = true;
+  return ZG_OK;
+}
+int Batch::records_wait(uint64_t* kernel_us) {
+  SidePass& p = side_[kSideRecords];
+  *kernel_us = 0;
+  const bool emitted = p.n && rec_.emitted;
+  p.n = 0;
+  if (!emitted) return ZG_OK;
+  ZG_HIP(hipSetDevice(eng->device_));
+  ZG_HIP(hipStreamSynchronize(eng->stream_));
+  ZG_HIP(p.elapsed_us(kernel_us));
   return ZG_OK;
 }
 int Batch::read_output_async(uint64_t off, uint8_t* dst, uint64_t n, hipStream_t s) {

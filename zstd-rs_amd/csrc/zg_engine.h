@@ -250,6 +250,16 @@ class Batch {
   int idxsums_launch(const zgh::Lane* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, const void* pairs, uint64_t npairs,
                      const uint32_t* sums, uint64_t nsums);
   int compare_wait(bool by_handle, zgv::Sums* out, uint64_t* kernel_us, uint64_t* bytes);
+  //  - records (zg_records.h), THREE kernels and one round trip in between, all on the first stream: records_launch uploads the chunk table
+  //    (every chunk checked against the output) and the frames' first chunks fstart[0 .. nframes] and enqueues zg_k_recs_count and
+  //    zg_k_recs_scan; records_sizes waits and brings back *total, the bytes equal to d in all chunks, and ftot[f], those of the chunks
+  //    [fstart[f], fstart[f + 1]) (8 + 8 * nframes bytes); records_emit enqueues zg_k_recs_emit, which stores `total` 64-bit offsets in
+  //    chunk order into staging — device memory of the caller with room for them —; records_wait waits for it. *kernel_us: count + scan, and
+  //    the emit. No launch (no chunk): zeros.
+  int records_launch(const zgr::Chunk* chunks, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes, uint32_t d);
+  int records_sizes(uint64_t* total, uint64_t* ftot, uint64_t* kernel_us, uint64_t* bytes);
+  int records_emit(uint64_t* staging, uint64_t total);
+  int records_wait(uint64_t* kernel_us);
   // after sync(): free everything but the plaintext (a finished submit that waits to be read: zgpu_pool_decode_all)
   void release_scratch();
   // intermediates, for parity tests
@@ -274,9 +284,10 @@ class Batch {
   FrameState* fs = nullptr;              // streaming submit: the frame state this run reads from / writes into
   // The side passes, one SidePass each (a new one: a name here, its launch and wait; ~Batch releases them all). What the buffers hold — hash: the
   // ranges, then the digests; scatter, the two dictfill parts (0: tables, 1: contents) and the gather: the segments, then the chunk table;
-  // the compares: the lanes, the frame list, then the records.
-  enum { kSideHash, kSideScatter, kSideTable, kSideHandle, kSideFill0, kSideFill1, kSideGather, kSideCount };
+  // the compares: the lanes, the frame list, then the records; records: the chunk table, fstart, then counts, prefixes and totals.
+  enum { kSideHash, kSideScatter, kSideTable, kSideHandle, kSideFill0, kSideFill1, kSideGather, kSideRecords, kSideCount };
   SidePass side_[kSideCount];
+  struct { uint32_t nframes = 0, d = 0; size_t counts = 0, prefix = 0, totals = 0; bool emitted = false; } rec_;   // the records pass in flight: where its arrays lie
   template <class L, class Launch> int compare_launch(SidePass& p, const L* lanes, uint32_t n, const zgv::Frame* frames, uint32_t nframes, Launch launch);
   std::vector<zgd::DictImage> frame_dicts_;   // set_frame_dicts
   int dictfill_launch(int part);
@@ -340,6 +351,10 @@ class Engine {
   // seekidx_rows_pass — the same pairs from the header chain of entries that declare their sizes (zg_seekidx.h): zg_k_seekidx_rows, one lane
   // per entry, stores into pairs[lanes[i].pre .. + lanes[i].limit] (device memory of the caller); out[i] = what lane i found.
   int seekidx_rows_pass(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, uint64_t* stats);
+  // records_find — m record ranges looked up in a seek index handle's record offsets (zg_records.h): zg_k_recs_find, one lane per range, ONE
+  // launch; recs: the handle's array (device memory the handle owns; the caller checked every lane's rpre + nrec against it), out[j] = lane
+  // j's 24-byte answer.
+  int records_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, uint64_t* stats);
   // hash_ranges_pass — XXH64 of ranges[0 .. n) of base (device memory the caller has checked) by the hash kernel `kernel` chooses
   // (zg_launch_xxh64_with); digests[i] is ranges[i]'s (zgpu_debug_hash_ranges).
   int hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats);

@@ -365,6 +365,56 @@ int sink_host(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
   return ZGPU_OK;
 }
 
+// DeviceSink::records: the submit's entries that stand at status 0 behind every verdict have their decoded frames cut into chunks — each
+// frame's [out_base, out_base + out_size), the ranges the hash launch takes: the dictionary gap in front of a frame is in no chunk — and the
+// three kernels of zg_records.h find the delimiters: count and scan, the one round trip that sizes the submit's staging, emit. What stays is
+// the staging buffer and, per sub-entry, where its offsets lie in it.
+int records_submit(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
+  DeviceSink& sink = *k.sink;
+  DeviceSink::Records& rc = *sink.records;
+  Batch* b = u.b;
+  const std::vector<ZgFrameOut>& fo = b->frame_out;
+  std::vector<zgr::Chunk> chunks;
+  std::vector<uint32_t> fstart, owner;   // per listed frame: its first chunk, the j it belongs to
+  for (uint32_t j = 0; j < n; j++) {
+    const zgpu_entry_result& r = sink.res[idx[j]].r;
+    if (r.status || r.nframes == 0) continue;
+    uint64_t at = rc.base[idx[j]];
+    for (uint32_t f = u.ff[j]; f < u.ff[j + 1]; f++) {
+      fstart.push_back((uint32_t)chunks.size());
+      zgr::cut_chunks(fo[f].out_base, fo[f].out_size, at, (uint32_t)owner.size(), &chunks);
+      owner.push_back(j);
+      at += fo[f].out_size;
+      if (chunks.size() > 0x7FFFFFFFull) return ZGPU_E_INTERNAL;   // (never: a submit's plaintext is bounded)
+    }
+  }
+  fstart.push_back((uint32_t)chunks.size());
+  if (chunks.empty()) return ZGPU_OK;
+  const uint32_t nf = (uint32_t)owner.size();
+  int st;
+  if ((st = b->records_launch(chunks.data(), (uint32_t)chunks.size(), fstart.data(), nf, rc.delimiter))) return st;
+  std::vector<uint64_t> ftot(nf, 0);
+  uint64_t total = 0, us = 0, back = 0;
+  if ((st = b->records_sizes(&total, ftot.data(), &us, &back))) return st;
+  rc.us += us; rc.bytes_back += back; rc.chunks += chunks.size();
+  if (total > SIZE_MAX / 8) return ZGPU_E_NOMEM;
+  if (total) {
+    rc.staging.push_back(zg::DevBuf());
+    if ((st = rc.staging.back().reserve((size_t)total * 8))) return st;
+    if ((st = b->records_emit(rc.staging.back().as<uint64_t>(), total))) return st;
+  }
+  uint64_t at = 0;
+  for (uint32_t q = 0; q < nf; q++) {   // (a sub-entry's frames follow each other in the list, and so do their offsets in the staging)
+    DeviceSink::Records::Run& run = rc.run[idx[owner[q]]];
+    if (!run.n) { run.buf = total ? (int32_t)rc.staging.size() - 1 : -1; run.at = at; }
+    run.n += ftot[q];
+    at += ftot[q];
+  }
+  if ((st = b->records_wait(&us))) return st;   // (the output goes with the submit: the emit must have read it)
+  rc.us += us;
+  return ZGPU_OK;
+}
+
 // the device sink: the plaintext stays on the device; one zg_k_scatter launch copies the frames of every successful entry to its destination
 // (an entry's frames back to back) while the hash kernel (zg_launch_xxh64) hashes the candidates beside it; frames that are not hashed are
 // counted, not verified. With ZGPU_DEVICE_VERIFY the order is hash launch, hash wait, verdicts, and only then the scatter of the entries that
@@ -487,7 +537,7 @@ int sink_device(Call& k, const uint32_t* idx, uint32_t n, Submit& u) {
       }
     count_frames(sink, zge::fill(u.ent[j], sink.no_hash, &d.r, &d.checksums_unverified, &d.first_hashed));
   }
-  return ZGPU_OK;
+  return sink.records ? records_submit(k, idx, n, u) : ZGPU_OK;
 }
 
 // one submit: the entries idx[0 .. n)
@@ -649,6 +699,11 @@ int decode_alone_device(Call& k, uint32_t i, bool dict_walk) {
       if (!e.known) { k.c->eng->last_error = "zgpu_seek_index_hash_device: an entry decoded alone that could not be hashed frame by frame"; return ZGPU_E_INTERNAL; }   // (never seen)
       for (const zge::Frame& f : a.fr) (*sink.collect)[i].push_back(DeviceSink::Digest{f.begin, f.clen, f.digest});
     }
+    if (sink.records && !d.r.status) {   // the record offsets of an entry decoded alone: the same definition over the host buffer (zg_records.h)
+      DeviceSink::Records& rc = *sink.records;
+      try { zgr::records_host(tmp.get(), e.total, rc.delimiter, rc.base[i], &rc.host[i]); } catch (...) { return ZGPU_E_NOMEM; }
+      rc.run[i] = DeviceSink::Records::Run{-1, 0, (uint64_t)rc.host[i].size()};
+    }
     if (!d.r.status) {
       // The uploads. The host buffer holds the frames back to back: as far as the pieces go it is ONE frame of e.total bytes (which is also all
       // that is known of an entry whose frames are not), so every clip that has room is one H2D; no ranges: the whole entry is one clip.
@@ -758,7 +813,7 @@ void zgf::reset_stats(zgpu_ctx* c, unsigned owned) {
   if (owned & kOwnsDevice) zero(c->frames_device_stats);
   if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
   if (owned & kOwnsIndex) zero(c->frames_index_stats);
-  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); }
+  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); zero(c->ranges_rec_stats); }
 }
 
 int zgf::drain(zgpu_ctx* c, int st) {
@@ -844,6 +899,11 @@ int zgf::decode_selections(zgpu_ctx* c, DeviceSink& sink, const void* const* dev
   if (sink.table_flag) sink.table_verify.resize(n);
   if (sink.table_flag && sink.handle) sink.handle_verify.assign(n, DeviceSink::HandleEntry{0, 0, 0, 0, 0});
   if (sink.collect) sink.collect->assign(n, std::vector<DeviceSink::Digest>());
+  if (sink.records) {
+    if (sink.records->base.size() != n) return ZGPU_E_INTERNAL;   // (never: the caller says where every selection begins)
+    sink.records->run.assign(n, DeviceSink::Records::Run());
+    sink.records->host.assign(n, std::vector<uint64_t>());
+  }
   for (uint32_t i = 0; i < n; i++) {
     const Selection& s = sel[i];
     srcs[i] = (const uint8_t*)device_srcs[s.entry] + s.lo;

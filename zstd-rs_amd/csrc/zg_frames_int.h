@@ -42,6 +42,21 @@ struct DeviceSink {
   bool hash_every = false;
   struct Digest { uint64_t begin, clen, digest; };
   std::vector<std::vector<Digest>>* collect = nullptr;
+  // zgpu_seek_index_records_device (zg_records.h): behind a submit's verdicts the bytes equal to `delimiter` in the decoded frames of every
+  // sub-entry that stands at status 0 are found on the device (Batch::records_launch .. records_wait), and the offsets stay in a staging
+  // buffer per submit. base[i], set by the caller: the entry coordinate of sub-entry i's first plaintext byte. run[i]: where sub-entry i's
+  // n offsets lie — staging[buf] from slot `at`, or, of an entry decoded alone, host[i] (buf < 0; zgr::records_host over the host buffer).
+  struct Records {
+    uint32_t delimiter = 0;
+    std::vector<uint64_t> base;
+    struct Run { int32_t buf = -1; uint64_t at = 0, n = 0; };
+    std::vector<Run> run;
+    std::vector<std::vector<uint64_t>> host;
+    std::vector<zg::DevBuf> staging;
+    uint64_t us = 0, chunks = 0, bytes_back = 0;   // count + scan + emit microseconds (HIP events), chunks scanned, bytes the side pass brought back
+    ~Records() { for (zg::DevBuf& b : staging) b.release(); }
+  };
+  Records* records = nullptr;
   uint64_t* stats = nullptr;     // zgpu_ctx::frames_device_stats (kDevStat*)
   uint64_t alone_written = 0;     // bytes the entries decoded alone brought to their destinations
 };

@@ -13,6 +13,7 @@
 #include "zg_idxsums.h"
 #include "zg_seekmany.h"
 #include "zg_seekidx.h"
+#include "zg_records.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -99,3 +100,12 @@ void zg_launch_seekmany_find(const zgm::Find* lanes, uint32_t m, const zgm::Pair
 // zg_k_seekidx_rows (zg_seekidx.h): one lane per entry follows the entry's header chain and stores the exclusive prefixes of its frame records
 // into pairs[lanes[i].pre .. + lanes[i].limit]: the pairs zg_k_seekmany_find reads; out[i] = what lane i found
 void zg_launch_seekidx_rows(const zgx::Lane* lanes, uint32_t n, zgm::Pair* pairs, zgx::Rows* out, hipStream_t s);
+// zg_records.h: the record index's side pass over a synced submit's output `out` (one wave per chunk) and its lookup. count: counts[i] = the
+// bytes of chunk i equal to d. scan (one workgroup): prefix[i] = the exclusive prefix of the counts, totals[0] = their sum, totals[1 + f] = the
+// sum over the chunks [fstart[f], fstart[f + 1]) of frame f. emit: the value base + p + 1 of every such byte, in order, to
+// staging[prefix[chunk] ...), never at or behind staging[total]. find: one lane per record range over the handle's offsets recs, out[j] = its answer
+void zg_launch_recs_count(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, uint32_t* counts, hipStream_t s);
+void zg_launch_recs_scan(const uint32_t* counts, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes, uint64_t* prefix, uint64_t* totals, hipStream_t s);
+void zg_launch_recs_emit(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, const uint64_t* prefix, uint64_t* staging, uint64_t total,
+                         hipStream_t s);
+void zg_launch_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, hipStream_t s);

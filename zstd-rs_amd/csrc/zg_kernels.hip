@@ -2223,3 +2223,75 @@ void zg_launch_exact(const ZgBatchDev& d, hipStream_t s, uint32_t drain_rule) {
 void zg_launch_lz(const ZgBatchDev& d, hipStream_t s) {
   hipLaunchKernelGGL(zg_k_lz, dim3(d.nframes), dim3(ZG_LZ_T), 0, s, d);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// the record index: behind everything else, so that no other kernel moves in the code object
+// ------------------------------------------------------------------------------------------------------------
+// The record index (zg_records.h has the definitions, the chunk table, what every wave reads and writes, and the ISA notes). count, scan and
+// emit are one side pass over a synced submit's output: the host cut the chunk table from the decoded frames' [out_base, out_base + out_size)
+// and checked every chunk against the output's capacity (Batch::records_launch). find is the lookup in front of a gather by record number:
+// the handle's offsets are read, no byte of any entry.
+#include "zg_records.h"
+struct ZgRecRead {   // the submit's output, which begins at a multiple of 16
+  uint64_t base;
+  __device__ __forceinline__ uint32_t ld1(uint64_t off) const { return *(const __attribute__((address_space(1))) uint8_t*)(base + off); }
+  __device__ __forceinline__ ZxU4 ld16(uint64_t off) const { return zx_gld128((const void*)(uintptr_t)(base + off)); }
+};
+struct ZgRecU64 {    // an array of 64-bit words in global memory
+  uint64_t base;
+  __device__ __forceinline__ uint64_t ld(uint64_t i) const { return *(const __attribute__((address_space(1))) uint64_t*)(base + 8 * i); }
+  __device__ __forceinline__ void st(uint64_t i, uint64_t v) const { *(__attribute__((address_space(1))) uint64_t*)(base + 8 * i) = v; }
+};
+struct ZgRecU32 {
+  uint64_t base;
+  __device__ __forceinline__ uint32_t ld(uint64_t i) const { return *(const __attribute__((address_space(1))) uint32_t*)(base + 4 * i); }
+};
+struct ZgRecTotals {   // totals[0]: the submit's total; totals[1 + f]: frame f's
+  uint64_t base;
+  __device__ __forceinline__ void total(uint64_t v) const { *(__attribute__((address_space(1))) uint64_t*)base = v; }
+  __device__ __forceinline__ void ftot(uint32_t f, uint64_t v) const { *(__attribute__((address_space(1))) uint64_t*)(base + 8 + 8ull * f) = v; }
+};
+__global__ void __launch_bounds__(zgr::kThreads) zg_k_recs_count(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, uint32_t* counts) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const zgr::Chunk c = chunks[i];
+  const uint32_t v = zgr::recs_count_chunk(ZgRecRead{(uint64_t)(uintptr_t)out}, c.out_off, c.len, d);
+  if (threadIdx.x == 0) counts[i] = v;
+}
+__global__ void __launch_bounds__(zgr::kScanThreads) zg_k_recs_scan(const uint32_t* counts, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes,
+                                                                    uint64_t* prefix, uint64_t* totals) {
+  __shared__ uint64_t lds[zgr::kScanThreads / 64];
+  zgr::recs_scan(ZgRecU32{(uint64_t)(uintptr_t)counts}, ZgRecU32{(uint64_t)(uintptr_t)fstart}, ZgRecU64{(uint64_t)(uintptr_t)prefix},
+                 ZgRecTotals{(uint64_t)(uintptr_t)totals}, nchunks, nframes, lds);
+}
+__global__ void __launch_bounds__(zgr::kThreads) zg_k_recs_emit(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, const uint64_t* prefix,
+                                                                uint64_t* staging, uint64_t total) {
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const zgr::Chunk c = chunks[i];
+  zgr::recs_emit_chunk(ZgRecRead{(uint64_t)(uintptr_t)out}, ZgRecU64{(uint64_t)(uintptr_t)staging}, c.out_off, c.len, c.base, d, prefix[i], total);
+}
+__global__ void __launch_bounds__(zgr::kThreads) zg_k_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out) {
+  const uint32_t j = blockIdx.x * zgr::kThreads + threadIdx.x;
+  if (j >= m) return;
+  const zgr::Find f = lanes[j];
+  const zgr::Found o = zgr::recs_find(ZgRecU64{(uint64_t)(uintptr_t)recs}, f);
+  const ZgRecU64 w{(uint64_t)(uintptr_t)&out[j]};
+  w.st(0, o.begin); w.st(1, o.len); w.st(2, (uint64_t)o.entry | ((uint64_t)o.status << 32));
+}
+void zg_launch_recs_count(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, uint32_t* counts, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_recs_count, dim3(n), dim3(zgr::kThreads), 0, s, out, chunks, n, d, counts);
+}
+void zg_launch_recs_scan(const uint32_t* counts, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes, uint64_t* prefix, uint64_t* totals, hipStream_t s) {
+  hipLaunchKernelGGL(zg_k_recs_scan, dim3(1), dim3(zgr::kScanThreads), 0, s, counts, nchunks, fstart, nframes, prefix, totals);
+}
+void zg_launch_recs_emit(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, const uint64_t* prefix, uint64_t* staging, uint64_t total,
+                         hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(zg_k_recs_emit, dim3(n), dim3(zgr::kThreads), 0, s, out, chunks, n, d, prefix, staging, total);
+}
+void zg_launch_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, hipStream_t s) {
+  if (!m) return;
+  hipLaunchKernelGGL(zg_k_recs_find, dim3((m + zgr::kThreads - 1) / zgr::kThreads), dim3(zgr::kThreads), 0, s, lanes, m, recs, out);
+}

@@ -19,6 +19,7 @@
 #include "zg_frames_int.h"
 #include "zg_seeksums.h"
 #include "zg_idxsums.h"
+#include "zg_records.h"
 
 using namespace zg;
 using namespace zgf;
@@ -631,27 +632,37 @@ int ensure_sums(zgpu_seek_index* x, hipStream_t s) {
   return ZGPU_OK;
 }
 
-// The pass. Nothing of the handle changes before every run of every chosen entry has its verdict: an engine failure leaves it as it was.
-int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, const uint8_t* which, uint64_t run_bytes) {
-  zg::Engine* eng = c->eng;
-  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
-  const uint64_t limit = run_bytes ? run_bytes : kHashRunBytes;
-  auto chosen = [&](uint32_t i) { return !which || which[i]; };
-  std::vector<Engine::DevEntry> dev;
+// What the passes over a handle's entries share (zgpu_seek_index_hash_device, zgpu_seek_index_records_device): the argument rules — which
+// chooses; an entry the index refused is passed over; a chosen entry must pass the pointer check at the length it was indexed at (refused[i]) —,
+// the entry's pairs brought down, and its rows cut into runs: rows [k0, k1) of entry i, one selection each with an empty span of clips,
+// decoded under the promise D[k1] - D[k0]. A run closes in front of a zstd row when it already holds one and its plaintext, with that row,
+// would exceed run_bytes (0: 64 MiB); skippable rows join the run in progress.
+struct Run { uint32_t i, k0, k1; };
+struct RunPlan {
+  const uint8_t* which = nullptr;
   std::vector<uint8_t> refused;
-  check_entries(c, srcs, lens, nullptr, nullptr, n, [&](uint32_t i) {
-    const zgpu_seek_index_info& info = x->ents[i].info;
-    return !chosen(i) || info.status ? kPass : (uint64_t)lens[i] != info.len ? kRefuse : kCheck;
-  }, &dev, &refused);
-  // the runs of every entry that is hashed: rows [k0, k1) of entry i, one selection each with an empty span of clips
-  struct Run { uint32_t i, k0, k1; };
   std::vector<Run> runs;
   std::vector<Selection> sel;
-  std::vector<std::vector<zgm::Pair>> pairs(n);
+  std::vector<std::vector<zgm::Pair>> pairs;   // of the entries that have runs (empty: not chosen, refused by the index or by the check)
+  bool chosen(uint32_t i) const { return !which || which[i]; }
+};
+int cut_runs(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, const uint8_t* which, uint64_t run_bytes,
+             RunPlan* rp) {
+  const uint64_t limit = run_bytes ? run_bytes : kHashRunBytes;
+  rp->which = which;
+  std::vector<Engine::DevEntry> dev;
+  std::vector<uint8_t>& refused = rp->refused;
+  check_entries(c, srcs, lens, nullptr, nullptr, n, [&](uint32_t i) {
+    const zgpu_seek_index_info& info = x->ents[i].info;
+    return !rp->chosen(i) || info.status ? kPass : (uint64_t)lens[i] != info.len ? kRefuse : kCheck;
+  }, &dev, &refused);
+  std::vector<Run>& runs = rp->runs;
+  std::vector<Selection>& sel = rp->sel;
+  rp->pairs.assign(n, std::vector<zgm::Pair>());
   for (uint32_t i = 0; i < n; i++) {
     const zgpu_seek_index::Ent& e = x->ents[i];
-    if (!chosen(i) || e.info.status || refused[i]) continue;
-    std::vector<zgm::Pair>& p = pairs[i];
+    if (!rp->chosen(i) || e.info.status || refused[i]) continue;
+    std::vector<zgm::Pair>& p = rp->pairs[i];
     try { p.resize((size_t)e.info.nrows + 1); } catch (...) { return ZGPU_E_NOMEM; }
     if (hipMemcpy(p.data(), x->pairs.as<zgm::Pair>() + e.pre, p.size() * sizeof(zgm::Pair), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
     uint32_t k0 = 0;
@@ -672,19 +683,42 @@ int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const
     }
     close(e.info.nrows);
   }
+  return ZGPU_OK;
+}
+// the runs decoded as the gather calls decode their groups, whatever the sink does beside: dres[r] is run r's result
+int decode_runs(zgpu_ctx* c, DeviceSink& sink, const void* const* srcs, const size_t* lens, const RunPlan& rp, std::vector<zgpu_device_entry_result>* dres) {
+  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  std::vector<Clip> no_clips;
+  std::vector<uint32_t> first(rp.sel.size() + 1, 0);
+  dres->assign(rp.sel.size(), zgpu_device_entry_result{});
+  return rp.sel.empty() ? ZGPU_OK : decode_selections(c, sink, srcs, lens, rp.sel, no_clips, first, true, nullptr, dres->data());
+}
+// what zgpu_last_error says of the first failing run of a pass
+std::string run_failure(const char* call, const Run& run, uint32_t status) {
+  return std::string(call) + ": entry " + std::to_string(run.i) + ", run of rows [" + std::to_string(run.k0) + ", " + std::to_string(run.k1) + "): " +
+         zgpu_status_name((int)status);
+}
+
+// The pass. Nothing of the handle changes before every run of every chosen entry has its verdict: an engine failure leaves it as it was.
+int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, const uint8_t* which, uint64_t run_bytes) {
+  zg::Engine* eng = c->eng;
+  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  RunPlan rp;
+  int st = cut_runs(c, x, srcs, lens, n, which, run_bytes, &rp);
+  if (st) return st;
+  auto chosen = [&](uint32_t i) { return rp.chosen(i); };
+  const std::vector<uint8_t>& refused = rp.refused;
+  const std::vector<Run>& runs = rp.runs;
+  const std::vector<std::vector<zgm::Pair>>& pairs = rp.pairs;
   // decoded as the gather calls decode their groups; the sink hashes every frame and hands the digests back
   zgpu_device_opts opts{0, ZGPU_DEVICE_VERIFY, 0};
-  int st;
   DeviceSink sink = device_sink(c, &opts, nullptr, &st, false);
   if (st) return st;
   sink.hash_every = true;
   std::vector<std::vector<DeviceSink::Digest>> got;
   sink.collect = &got;
-  reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
-  std::vector<Clip> no_clips;
-  std::vector<uint32_t> first(sel.size() + 1, 0);
-  std::vector<zgpu_device_entry_result> dres(sel.size());
-  if (!sel.empty() && (st = decode_selections(c, sink, srcs, lens, sel, no_clips, first, true, nullptr, dres.data()))) return st;
+  std::vector<zgpu_device_entry_result> dres;
+  if ((st = decode_runs(c, sink, srcs, lens, rp, &dres))) return st;
   // every run's frames to rows; the first failing run of an entry, in row order, is its verdict
   std::vector<std::vector<uint32_t>> sums(n);
   std::vector<zgpu_seek_index_sums> rec(n, zgpu_seek_index_sums{0, 0, 0, 0, 0, 0});
@@ -707,9 +741,7 @@ int hash_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const
     if (!status && q != got[r].size()) status = ZGPU_E_CONTENT_SIZE_MISMATCH;   // (a decoded frame that coincides with no row)
     if (status) {
       o = zgpu_seek_index_sums{status, 0, run.k0, run.k1, 0, 0};
-      if (named.empty())
-        named = "zgpu_seek_index_hash_device: entry " + std::to_string(run.i) + ", run of rows [" + std::to_string(run.k0) + ", " + std::to_string(run.k1) + "): " +
-                zgpu_status_name((int)status);
+      if (named.empty()) named = run_failure("zgpu_seek_index_hash_device", run, status);
       continue;
     }
     o.frames += got[r].size(); o.bytes += p[run.k1].d - p[run.k0].d;
@@ -784,11 +816,265 @@ extern "C" int zgpu_seek_index_sums_of(const zgpu_seek_index* x, uint32_t i, zgp
   *out = x->ents[i].sums;
   return ZGPU_OK;
 }
+// ---- record offsets in the handle (include/zgpu.h: record index; zg_records.h) ---------------------------------------------------------------------
+static_assert(sizeof(zgpu_seek_index_records) == 32 && offsetof(zgpu_seek_index_records, nrecords) == 16 && offsetof(zgpu_seek_index_records, row_lo) == 24 &&
+              sizeof(zgpu_record_range) == 24 && offsetof(zgpu_record_range, entry) == 16 && ZGPU_RECORDS_STRIP == zgr::kStrip, "include/zgpu.h");
+namespace {
+// One stretch of an entry's offsets on its way into the handle's array: n 64-bit words at p, device or host memory.
+struct Piece { const uint64_t* p; uint64_t n; bool host; };
+// The handle's array laid out anew: entry i gets the pieces news[i] and the record rec[i] if fresh[i]; any other entry keeps what it holds
+// (state 0: nothing). A new array is allocated, filled in entry order — device-to-device copies but for what the host holds — on the engine's
+// first stream, which is drained before the old array goes; on a failure the handle is as it was. The host pieces must outlive the call.
+int relay_records(zgpu_seek_index* x, const std::vector<uint8_t>& fresh, const std::vector<std::vector<Piece>>& news, const std::vector<zgpu_seek_index_records>& rec) {
+  const uint32_t n = (uint32_t)x->ents.size();
+  std::vector<uint64_t> rpre(n, 0);
+  uint64_t slots = 0, held = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const zgpu_seek_index_records& r = fresh[i] ? rec[i] : x->ents[i].recs;
+    if (!r.state) continue;
+    rpre[i] = slots;
+    slots += r.nrecords + 1;
+    held += r.nrecords;
+  }
+  if (slots > SIZE_MAX / 8) return ZGPU_E_NOMEM;
+  zg::DevBuf nb;
+  int st = nb.reserve((size_t)(slots ? slots : 1) * 8);
+  if (st) return st;
+  hipStream_t s = x->ctx->eng->stream();
+  bool ok = true;
+  for (uint32_t i = 0; i < n && ok; i++) {
+    uint64_t* to = nb.as<uint64_t>() + rpre[i];
+    if (!fresh[i]) {
+      const zgpu_seek_index::Ent& e = x->ents[i];
+      if (e.recs.state) ok = hipMemcpyAsync(to, x->recs.as<uint64_t>() + e.rpre, (size_t)(e.recs.nrecords + 1) * 8, hipMemcpyDeviceToDevice, s) == hipSuccess;
+      continue;
+    }
+    if (!rec[i].state) continue;
+    uint64_t at = 0;
+    for (const Piece& pc : news[i]) {
+      if (!pc.n) continue;
+      if (at + pc.n > rec[i].nrecords + 1) { nb.release(); return ZGPU_E_INTERNAL; }   // (never)
+      ok = ok && hipMemcpyAsync(to + at, pc.p, (size_t)pc.n * 8, pc.host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s) == hipSuccess;
+      at += pc.n;
+    }
+    if (at != rec[i].nrecords + 1) { (void)hipStreamSynchronize(s); nb.release(); return ZGPU_E_INTERNAL; }   // (never)
+  }
+  if (!ok || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(s); nb.release(); return ZGPU_E_HIP; }
+  x->recs.release();
+  x->recs = nb;
+  x->nrec_slots = slots;
+  for (uint32_t i = 0; i < n; i++) x->ents[i].rpre = rpre[i];
+  x->rec_stats[kRecStatRecordsHeld] = held; x->rec_stats[kRecStatOffsetBytes] = slots * 8;
+  return ZGPU_OK;
+}
+
+// The pass: hash_entries' runs behind another sink. Nothing of the handle changes before every run of every chosen entry has its verdict.
+int records_entries(zgpu_ctx* c, zgpu_seek_index* x, const void* const* srcs, const size_t* lens, uint32_t n, const uint8_t* which, uint32_t delimiter,
+                    uint64_t run_bytes) {
+  zg::Engine* eng = c->eng;
+  if (hipSetDevice(eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  RunPlan rp;
+  int st = cut_runs(c, x, srcs, lens, n, which, run_bytes, &rp);
+  if (st) return st;
+  const std::vector<Run>& runs = rp.runs;
+  // decoded as the gather calls decode their groups; no frame is hashed, and the sink finds the delimiters of what stands at status 0
+  zgpu_device_opts opts{0, ZGPU_DEVICE_NO_HASH, 0};
+  DeviceSink sink = device_sink(c, &opts, nullptr, &st, false);
+  if (st) return st;
+  DeviceSink::Records rc;
+  rc.delimiter = delimiter;
+  for (const Run& run : runs) rc.base.push_back(rp.pairs[run.i][run.k0].d);
+  sink.records = &rc;
+  std::vector<zgpu_device_entry_result> dres;
+  if ((st = decode_runs(c, sink, srcs, lens, rp, &dres))) return st;
+  // the first failing run of an entry, in row order, is its verdict; else its runs' offsets follow each other in row order
+  std::vector<zgpu_seek_index_records> rec(n, zgpu_seek_index_records{0, 0, delimiter, 0, 0, 0, 0});
+  std::vector<std::vector<Piece>> news(n);
+  std::vector<uint8_t> fresh(n, 0);
+  std::vector<uint64_t> consts;   // O[0] and O[R] = L of every entry: host words the copies read until the stream is drained
+  consts.reserve(2 * (size_t)n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (rp.pairs[i].empty()) continue;
+    fresh[i] = 1;
+    consts.push_back(0);
+    news[i].push_back(Piece{&consts.back(), 1, true});
+  }
+  std::string named;
+  uint64_t back = 0;
+  for (size_t r = 0; r < runs.size(); r++) {
+    const Run& run = runs[r];
+    zgpu_seek_index_records& o = rec[run.i];
+    if (o.status) continue;
+    const uint32_t status = (uint32_t)dres[r].r.status;
+    if (status) {
+      o = zgpu_seek_index_records{status, 0, delimiter, 0, 0, run.k0, run.k1};
+      if (named.empty()) named = run_failure("zgpu_seek_index_records_device", run, status);
+      continue;
+    }
+    const DeviceSink::Records::Run& found = rc.run[r];
+    if (!found.n) continue;
+    if (found.buf < 0) news[run.i].push_back(Piece{rc.host[r].data(), found.n, true});
+    else news[run.i].push_back(Piece{rc.staging[(size_t)found.buf].as<uint64_t>() + found.at, found.n, false});
+    o.nrecords += found.n;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    if (!fresh[i] || rec[i].status) continue;
+    zgpu_seek_index_records& o = rec[i];
+    const uint64_t L = x->ents[i].info.plaintext;
+    uint64_t last = 0;   // the last offset found (O[0] where there is none)
+    if (o.nrecords) {
+      const Piece& pc = news[i].back();
+      if (pc.host) last = pc.p[pc.n - 1];
+      else {
+        if (hipMemcpy(&last, pc.p + (pc.n - 1), 8, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+        back += 8;
+      }
+    }
+    if (last > L) { eng->last_error = "zgpu_seek_index_records_device: an offset behind the entry's plaintext"; return ZGPU_E_INTERNAL; }   // (never: the runs kept their promise)
+    if (last != L) {   // the open tail: O[R] = L
+      consts.push_back(L);
+      news[i].push_back(Piece{&consts.back(), 1, true});
+      o.nrecords++;
+      o.flags = 1;
+    }
+    o.state = 1;
+  }
+  if ((st = relay_records(x, fresh, news, rec))) return st;
+  for (uint32_t i = 0; i < n; i++) {
+    zgpu_seek_index::Ent& e = x->ents[i];
+    if (!rp.chosen(i)) continue;
+    if (e.info.status) { e.recs = zgpu_seek_index_records{e.info.status, 0, delimiter, 0, 0, 0, 0}; continue; }
+    if (rp.refused[i]) { e.recs.status = ZGPU_E_BAD_ARG; continue; }   // (nothing of it was looked at: what it holds stays)
+    e.recs = rec[i];
+    if (rec[i].status) e.recs.nrecords = 0;
+  }
+  x->rec_stats[kRecStatSubmits] += c->frames_submits; x->rec_stats[kRecStatUs] += rc.us; x->rec_stats[kRecStatChunks] += rc.chunks;
+  x->rec_stats[kRecStatBytesDownloaded] += rc.bytes_back + back;
+  if (!named.empty()) eng->last_error = named;
+  return ZGPU_OK;
+}
+
+// Both record calls up to the answers: every range's status decided on the host, then ONE zg_k_recs_find launch over the handle's offsets.
+int lookup_records(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_record_range* recs, uint32_t m, std::vector<zgr::Found>* out, uint64_t* stats) {
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const uint32_t n = (uint32_t)x->ents.size();
+  std::vector<zgr::Find> lanes(m);
+  for (uint32_t j = 0; j < m; j++) {
+    const zgpu_record_range& g = recs[j];
+    zgr::Find f{g.first, g.count, 0, 0, g.flags, 0, g.entry, 0};
+    if (g.entry >= n || (g.flags & ~ZGPU_RECORDS_STRIP)) f.status = ZGPU_E_BAD_ARG;
+    else {
+      const zgpu_seek_index::Ent& e = x->ents[g.entry];
+      if (e.info.status) f.status = e.info.status;
+      else if (!e.recs.state) f.status = ZGPU_E_BAD_ARG;
+      else {
+        if (!x->recs.p || e.rpre > x->nrec_slots || e.recs.nrecords + 1 > x->nrec_slots - e.rpre) {   // (never: relay_records laid them out)
+          c->eng->last_error = "zgpu_seek_index_record_ranges_device: an entry's offsets leave the handle's array";
+          return ZGPU_E_INTERNAL;
+        }
+        f.rpre = e.rpre; f.nrec = e.recs.nrecords;
+        f.flags = (g.flags & zgr::kStrip) | ((e.recs.flags & 1u) ? zgr::kOpenTail : 0u);
+      }
+    }
+    lanes[j] = f;
+  }
+  out->assign(m, zgr::Found{0, 0, 0, 0});
+  uint64_t pass[3] = {0, 0, 0};
+  const int st = drain(c, c->eng->records_find(lanes.data(), m, x->recs.as<uint64_t>(), out->data(), pass));
+  stats[kRecFindStatLaunches] = pass[kPassLaunches]; stats[kRecFindStatUs] = pass[kPassUs]; stats[kRecFindStatBytesDownloaded] = pass[kPassBytes];
+  if (st) return st;
+  for (uint32_t j = 0; j < m; j++) {   // (every answer is held against its entry's plaintext before anything is gathered)
+    const zgr::Found& f = (*out)[j];
+    if (f.status != lanes[j].status || f.entry != lanes[j].entry ||
+        (!f.status && (f.begin > x->ents[f.entry].info.plaintext || f.len > x->ents[f.entry].info.plaintext - f.begin))) {
+      c->eng->last_error = "zgpu_seek_index_record_ranges_device: an answer that leaves its entry";
+      return ZGPU_E_INTERNAL;
+    }
+  }
+  return ZGPU_OK;
+}
+}  // namespace
+
+extern "C" int zgpu_seek_index_records_device(zgpu_ctx* c, zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                              const uint8_t* which_or_null, uint32_t delimiter, uint64_t run_bytes) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || delimiter > 255u) return ZGPU_E_BAD_ARG;
+  return drain(c, records_entries(c, x, device_srcs, lens, n, which_or_null, delimiter, run_bytes));
+}
+extern "C" int zgpu_seek_index_records_of(const zgpu_seek_index* x, uint32_t i, zgpu_seek_index_records* out) {
+  if (!x || !out || i >= x->ents.size()) return ZGPU_E_BAD_ARG;
+  *out = x->ents[i].recs;
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_read_records(const zgpu_seek_index* x, uint32_t entry, uint64_t first, uint64_t* host_dst, uint64_t cap, uint64_t* n) {
+  if (n) *n = 0;
+  if (!x || !n || entry >= x->ents.size() || x->ents[entry].info.status || !x->ents[entry].recs.state || (!host_dst && cap)) return ZGPU_E_BAD_ARG;
+  const zgpu_seek_index::Ent& e = x->ents[entry];
+  const uint64_t have = e.recs.nrecords + 1;
+  if (!host_dst) { *n = have; return ZGPU_OK; }
+  const uint64_t take = first >= have ? 0 : cap < have - first ? cap : have - first;
+  if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  if (take && hipMemcpy(host_dst, x->recs.as<uint64_t>() + e.rpre + first, (size_t)take * 8, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  *n = take;
+  return ZGPU_OK;
+}
+extern "C" int zgpu_seek_index_set_records(zgpu_seek_index* x, uint32_t entry, const uint64_t* offsets, uint64_t nrecords, uint32_t delimiter) {
+  const uint32_t d = delimiter & ~ZGPU_RECORDS_OPEN_TAIL;
+  const bool open = (delimiter & ZGPU_RECORDS_OPEN_TAIL) != 0;
+  if (!x || entry >= x->ents.size() || x->ents[entry].info.status || !offsets || d > 255u || nrecords == UINT64_MAX || (open && !nrecords)) return ZGPU_E_BAD_ARG;
+  if (offsets[0] != 0 || offsets[nrecords] != x->ents[entry].info.plaintext) return ZGPU_E_BAD_ARG;
+  for (uint64_t r = 0; r < nrecords; r++) if (offsets[r] >= offsets[r + 1]) return ZGPU_E_BAD_ARG;
+  if (!x->ctx || hipSetDevice(x->ctx->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const uint32_t n = (uint32_t)x->ents.size();
+  std::vector<uint8_t> fresh(n, 0);
+  std::vector<std::vector<Piece>> news(n);
+  std::vector<zgpu_seek_index_records> rec(n, zgpu_seek_index_records{0, 0, 0, 0, 0, 0, 0});
+  fresh[entry] = 1;
+  news[entry].push_back(Piece{offsets, nrecords + 1, true});
+  rec[entry] = zgpu_seek_index_records{0, 2, d, open ? 1u : 0u, nrecords, 0, 0};
+  const int st = relay_records(x, fresh, news, rec);
+  if (!st) x->ents[entry].recs = rec[entry];
+  return st;
+}
+extern "C" int zgpu_seek_index_record_ranges_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_record_range* recs, uint32_t m,
+                                                    zgpu_entry_range* out, uint32_t* status) {
+  if (!c || !x || x->ctx != c || (m && (!recs || !out || !status))) return ZGPU_E_BAD_ARG;
+  reset_stats(c, kOwnsRanges);
+  std::vector<zgr::Found> found;
+  const int st = lookup_records(c, x, recs, m, &found, c->ranges_rec_stats);
+  for (uint32_t j = 0; j < m; j++) {
+    const bool ok = !st && !found[j].status;
+    out[j] = zgpu_entry_range{ok ? found[j].begin : 0, ok ? found[j].len : 0, recs[j].entry, 0};
+    status[j] = st ? 0u : found[j].status;
+  }
+  return st;
+}
+// The lookup, then the indexed gather on the byte ranges: a range whose lookup failed travels as a range of length 0 — the gather passes it
+// untouched — and gets the lookup's status afterwards.
+extern "C" int zgpu_gather_records_indexed_device_src(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                      const zgpu_record_range* recs, uint32_t m, void* const* device_dsts, const size_t* caps,
+                                                      const zgpu_device_opts* opts, zgpu_range_result* results) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && (!recs || !device_dsts || !caps || !results)))
+    return ZGPU_E_BAD_ARG;
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgr::Found> found;
+  uint64_t find_stats[kRecFindStatCount] = {};
+  int st = lookup_records(c, x, recs, m, &found, find_stats);
+  if (st) return st;
+  std::vector<zgpu_entry_range> ranges(m);
+  for (uint32_t j = 0; j < m; j++)
+    ranges[j] = found[j].status ? zgpu_entry_range{0, 0, 0, 0} : zgpu_entry_range{found[j].begin, found[j].len, found[j].entry, 0};
+  st = zgpu_gather_ranges_indexed_device_src(c, x, device_srcs, lens, n, ranges.data(), m, device_dsts, caps, opts, results);
+  for (uint32_t j = 0; j < m && !st; j++)
+    if (found[j].status) { memset(&results[j], 0, sizeof results[j]); results[j].d.r.status = (int)found[j].status; }
+  memcpy(c->ranges_rec_stats, find_stats, sizeof find_stats);
+  return st;
+}
 extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
   if (!x) return;
   if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
   x->pairs.release();
   x->sums.release();
+  x->recs.release();
   delete x;
 }
 extern "C" uint32_t zgpu_seek_index_entries(const zgpu_seek_index* x) { return x ? (uint32_t)x->ents.size() : 0; }
@@ -799,8 +1085,10 @@ extern "C" int zgpu_seek_index_info_of(const zgpu_seek_index* x, uint32_t i, zgp
 }
 extern "C" int zgpu_seek_index_stats(const zgpu_seek_index* x, uint64_t* out, int n) {
   if (!x) return 0;
-  const int k = copy_stats(x->stats, out, n);   // (the slots of the sums lie behind the others)
-  return k < (int)kSeekIdxStatCount || !out ? k : k + copy_stats(x->sums_stats, out + k, n - k);
+  int k = copy_stats(x->stats, out, n);   // (the slots of the sums lie behind the others, those of the records behind them)
+  if (k < (int)kSeekIdxStatCount || !out) return k;
+  k += copy_stats(x->sums_stats, out + k, n - k);
+  return k < (int)(kSeekIdxStatCount + kSumStatCount) ? k : k + copy_stats(x->rec_stats, out + k, n - k);
 }
 
 extern "C" int zgpu_frames_seek_indexed_device(zgpu_ctx* c, const zgpu_seek_index* x, const zgpu_entry_range* ranges, uint32_t m, zgpu_seek* out) {
@@ -833,6 +1121,8 @@ extern "C" int zgpu_gather_ranges_indexed_device_src(zgpu_ctx* c, const zgpu_see
 
 extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) {
   if (!c) return 0;
-  const int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others)
-  return k < (int)kRangeStatCount || !out ? k : k + copy_stats(c->ranges_many_stats, out + k, n - k);
+  int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others, the record lookup's behind them)
+  if (k < (int)kRangeStatCount || !out) return k;
+  k += copy_stats(c->ranges_many_stats, out + k, n - k);
+  return k < (int)(kRangeStatCount + kManyStatCount) ? k : k + copy_stats(c->ranges_rec_stats, out + k, n - k);
 }

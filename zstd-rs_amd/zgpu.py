@@ -66,6 +66,13 @@ _STATS = {
                              ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host",
                               "measure_submits", "measure_us", "frames_measured",
                               "hash_submits", "hash_us", "frames_hashed", "sums_bytes", "hash_runs")),
+    # the same getter asked for the slots zgpu_seek_index_records_device appends behind those (csrc/zg_capi_int.h: kRecStat*)
+    "SeekIndex.records_stats": ("zgpu_seek_index_stats", C.c_uint64,
+                                ("launches", "kernel_us", "bytes_downloaded", "device_bytes", "rows", "input_bytes_to_host",
+                                 "measure_submits", "measure_us", "frames_measured",
+                                 "hash_submits", "hash_us", "frames_hashed", "sums_bytes", "hash_runs",
+                                 "records_submits", "records_us", "records_chunks", "records_held", "records_offset_bytes",
+                                 "records_bytes_downloaded")),
     "Context.tuning": ("zgpu_debug_tuning", C.c_uint32,
                        ("dev_build", "unit_blocks", "seq_packed", "flat4", "ramp_percent", "sweep_w", "flat_shape", "force_inorder",
                         "poison", "poisoned_lo", "poisoned_hi", "scratch_cap_lo", "scratch_cap_hi")),
@@ -250,6 +257,41 @@ class SeekIndexSums:
             self.status, self.state, self.row_lo, self.row_hi, self.frames, self.bytes)
 
 
+class SeekIndexRecordsC(C.Structure):
+    """zgpu_seek_index_records (include/zgpu.h)"""
+    _fields_ = [("status", C.c_uint32), ("state", C.c_uint32), ("delimiter", C.c_uint32), ("flags", C.c_uint32), ("nrecords", C.c_uint64),
+                ("row_lo", C.c_uint32), ("row_hi", C.c_uint32)]
+
+
+class RecordRangeC(C.Structure):
+    """zgpu_record_range (include/zgpu.h)"""
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("entry", C.c_uint32), ("flags", C.c_uint32)]
+
+
+RECORDS_NONE, RECORDS_FOUND, RECORDS_SET = 0, 1, 2   # SeekIndexRecords.state
+RECORDS_STRIP = 1                                    # zgpu_record_range.flags
+RECORDS_OPEN_TAIL = 0x80000000                       # zgpu_seek_index_set_records' delimiter word
+
+
+class SeekIndexRecords:
+    """What a SeekIndex knows of one entry's record offsets (zgpu_seek_index_records): state RECORDS_NONE, RECORDS_FOUND or RECORDS_SET;
+    status of the last SeekIndex.records that chose the entry (0, the index's status, E_BAD_ARG, or the failing run's with its rows
+    [row_lo, row_hi)); delimiter; flags bit 0 (open_tail): the last record ends in no delimiter; nrecords."""
+    __slots__ = FIELDS = ("status", "state", "delimiter", "flags", "nrecords", "row_lo", "row_hi")
+
+    def __init__(self, c):
+        for k in self.FIELDS:
+            setattr(self, k, int(getattr(c, k)))
+
+    @property
+    def open_tail(self):
+        return bool(self.flags & 1)
+
+    def __repr__(self):
+        return "SeekIndexRecords(status=%d, state=%d, delimiter=%d, flags=%d, nrecords=%d, rows=[%d, %d))" % (
+            self.status, self.state, self.delimiter, self.flags, self.nrecords, self.row_lo, self.row_hi)
+
+
 class Seek:
     """One entry of Context.frames_seek_device (zgpu_seek): the whole frames [src_lo, src_hi) of the entry that hold the range, the plaintext
     offset plain_lo of the first of them, bound = plaintext_bound of those bytes. flags: open_ended (an unsized frame was taken: everything
@@ -360,6 +402,8 @@ EXPORTS = [
     "zgpu_seek_index_measure_device", "zgpu_seek_index_export_seek_table",
     "zgpu_seek_index_hash_device", "zgpu_seek_index_set_sums", "zgpu_seek_index_read_sums", "zgpu_seek_index_sums_of",
     "zgpu_seek_index_export_seek_table_ex",
+    "zgpu_seek_index_records_device", "zgpu_seek_index_records_of", "zgpu_seek_index_read_records", "zgpu_seek_index_set_records",
+    "zgpu_seek_index_record_ranges_device", "zgpu_gather_records_indexed_device_src",
     "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
@@ -457,6 +501,13 @@ def _declare(L):
     L.zgpu_seek_index_set_sums.argtypes = [vp, C.c_uint32, P(C.c_uint32), C.c_uint32]
     L.zgpu_seek_index_read_sums.argtypes = [vp, C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_uint32)]
     L.zgpu_seek_index_sums_of.argtypes = [vp, C.c_uint32, P(SeekIndexSumsC)]
+    L.zgpu_seek_index_records_device.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint64]
+    L.zgpu_seek_index_records_of.argtypes = [vp, C.c_uint32, P(SeekIndexRecordsC)]
+    L.zgpu_seek_index_read_records.argtypes = [vp, C.c_uint32, C.c_uint64, P(C.c_uint64), C.c_uint64, P(C.c_uint64)]
+    L.zgpu_seek_index_set_records.argtypes = [vp, C.c_uint32, P(C.c_uint64), C.c_uint64, C.c_uint32]
+    L.zgpu_seek_index_record_ranges_device.argtypes = [vp, vp, P(RecordRangeC), C.c_uint32, P(EntryRangeC), P(C.c_uint32)]
+    L.zgpu_gather_records_indexed_device_src.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, P(RecordRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
+                                                         P(RangeResultC)]
     L.zgpu_seek_index_destroy.argtypes = [vp]
     L.zgpu_seek_index_destroy.restype = None
     L.zgpu_seek_index_entries.argtypes = [vp]
@@ -1036,6 +1087,76 @@ class Context:
                                  (self._index_handle(index, "gather_ranges_indexed_device_src"), _ptr_array(src_ptrs), _size_array(lens), n,
                                   self._entry_ranges(ranges), m), dst_ptrs, caps, _opts(hash_max, no_hash, verify, verify_table))
 
+    @staticmethod
+    def _record_ranges(recs):
+        """zgpu_record_range[max(m, 1)] of m triples (entry, first, count); a fourth element, if given, is the record's flags (RECORDS_STRIP)"""
+        m = len(recs)
+        rg = (RecordRangeC * max(m, 1))()
+        for j, r in enumerate(recs):
+            rg[j] = RecordRangeC(int(r[1]), int(r[2]), int(r[0]), int(r[3]) if len(r) > 3 else 0)
+        return rg
+
+    def record_ranges(self, index, recs):
+        """zgpu_seek_index_record_ranges_device: recs[j] = (entry, first, count[, flags]) — records [first, first + count) of entry `entry`
+        of a SeekIndex that holds its record offsets (SeekIndex.records / set_records) — as plaintext byte ranges, by ONE find launch over
+        the index's offsets; nothing of any entry is read. The records are clipped to those the entry has; flags RECORDS_STRIP drops the
+        final delimiter of the last record taken. Returns (ranges, statuses): ranges[j] = (entry, begin, len), what
+        gather_ranges_indexed_device_src takes; statuses[j] E_BAD_ARG for an entry out of range, unknown flags or an entry without records,
+        the index's status for an entry it refused."""
+        m = len(recs)
+        out, status = (EntryRangeC * max(m, 1))(), (C.c_uint32 * max(m, 1))()
+        self._check(self.L.zgpu_seek_index_record_ranges_device(self.h, self._index_handle(index, "record_ranges"), self._record_ranges(recs), m, out,
+                                                                status), "zgpu_seek_index_record_ranges_device")
+        return [(int(o.entry), int(o.begin), int(o.len)) for o in out[:m]], list(status[:m])
+
+    def gather_records_indexed_device_src(self, index, src_ptrs, lens, recs, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False,
+                                          verify_table=False):
+        """zgpu_gather_records_indexed_device_src: gather_ranges_indexed_device_src by record NUMBER — recs[j] = (entry, first, count[, flags])
+        as record_ranges takes them, record range j to dst_ptrs[j] (caps[j] bytes of device memory). The lookup is one launch and 24 bytes
+        per range; everything behind it is that call: groups decoded once, fate sharing, E_TARGET_TOO_SMALL per range, the options. A range
+        whose lookup failed carries that status and nothing of it is gathered. Returns (results, seeks), one of each per range."""
+        n, m = len(src_ptrs), len(recs)
+        _one_per("gather_records_indexed_device_src", n, lens)
+        _one_per("gather_records_indexed_device_src", m, dst_ptrs, caps)
+        return self._decode_call("gather_records_indexed_device_src", m,
+                                 (self._index_handle(index, "gather_records_indexed_device_src"), _ptr_array(src_ptrs), _size_array(lens), n,
+                                  self._record_ranges(recs), m), dst_ptrs, caps, _opts(hash_max, no_hash, verify, verify_table))
+
+    # the slots zgpu_debug_ranges_stats appends behind GATHER_STATS (csrc/zg_capi_int.h: kRecFindStat*)
+    RECORD_STATS = ("record_find_launches", "record_find_us", "record_find_bytes_downloaded")
+
+    def gather_records_stats(self):
+        """gather_ranges_stats of the last call plus the slots of the record lookup (out[19] ...): record_find_launches, record_find_us (HIP
+        events), record_find_bytes_downloaded (24 per range)."""
+        keys = _STATS["Context.ranges_stats"][2] + self.GATHER_STATS + self.RECORD_STATS
+        a = (C.c_uint64 * len(keys))()
+        k = self.L.zgpu_debug_ranges_stats(self.h, a, len(keys))
+        return dict(zip(keys[:k], a[:k]))
+
+    def gather_tensor_records(self, tensors, recs, index, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False):
+        """gather_records_indexed_device_src on torch tensors, the sibling of gather_tensor_ranges(index=...): tensors[i] is a contiguous
+        torch.uint8 tensor on this context's device holding shard i, recs[j] = (entry, first, count[, flags]) the records wanted of shard
+        `entry`, index a SeekIndex over these shards that holds their record offsets. record_ranges sizes the destinations — the lookup
+        knows every range's length —, and the bytes go to ONE new torch.uint8 tensor. Returns (tensors, results, seeks) or, packed=True,
+        (buffer, offsets, results, seeks), as gather_tensor_ranges does."""
+        self._tensor_check(tensors, "gather_tensor_records")
+        ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
+        ranges, _ = self.record_ranges(index, recs)
+        caps = [r[2] for r in ranges]
+        if packed:
+            offs = [0]
+            for cp in caps:
+                offs.append(offs[-1] + cp)
+            buf, _, base = self._slot_tensor([offs[-1]])
+            dsts = [base[0] + o for o in offs[:-1]]
+        else:
+            buf, offs, dsts = self._slot_tensor(caps)
+        res, seeks = self.gather_records_indexed_device_src(index, ptrs, lens, recs, dsts, caps, hash_max=hash_max, no_hash=no_hash, verify=verify,
+                                                            verify_table=verify_table)
+        if packed:
+            return buf[:offs[-1]], offs, res, seeks
+        return self._views(buf, offs, res), res, seeks
+
     def gather_tensor_ranges(self, tensors, ranges, hash_max=0, no_hash=False, verify=False, verify_table=False, packed=False, index=None):
         """gather_ranges_seek_table_device_src on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding
         seekable shard i, ranges[j] = (entry, begin, len) the record wanted of shard `entry`. A frames_seek_table_many_device call of its own
@@ -1246,6 +1367,67 @@ class SeekIndex:
         for i in range(len(self.infos)):
             self.ctx._check(self.L.zgpu_seek_index_sums_of(self.h, i, C.byref(rec)), "zgpu_seek_index_sums_of")
             out.append(SeekIndexSums(rec))
+        return out
+
+    def records_stats(self):
+        """stats(sums=True) plus what records appends (zgpu_seek_index_stats [14] ...): records_submits, records_us (count + scan + emit, HIP
+        events), records_chunks, records_held and records_offset_bytes (held now), records_bytes_downloaded"""
+        self._open("records_stats")
+        return _read_stats(self.L, "SeekIndex.records_stats", self.h)
+
+    def records(self, src_ptrs, lens, delimiter=b"\n", which=None, run_bytes=0):
+        """zgpu_seek_index_records_device: every zstd frame of every chosen entry decoded once, every byte equal to `delimiter` (one byte, or
+        an int 0 .. 255) found on the device, and where each record begins kept in the index; nothing is delivered. src_ptrs / lens name the
+        index's entries (all of them). which: one truth value per entry (None: all). run_bytes: plaintext per run of rows (0: 64 MiB). An
+        entry with a failing run keeps no offsets; records_infos says which and why, ctx.last_error names the first. A record index is a
+        promise about bytes, not a verdict: a stale one delivers the wrong bytes with status 0. Returns records_infos."""
+        self._open("records")
+        n = len(src_ptrs)
+        _one_per("records", n, lens, which)
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) and len(delimiter) == 1 else delimiter
+        if not isinstance(d, int) or d < 0:
+            raise ValueError("records: a delimiter of one byte")
+        w = None if which is None else bytes(1 if x else 0 for x in which)
+        self.ctx._check(self.L.zgpu_seek_index_records_device(self.ctx.h, self.h, _ptr_array(src_ptrs), _size_array(lens), n, w, d, int(run_bytes)),
+                        "zgpu_seek_index_records_device")
+        return self.records_infos()
+
+    def records_tensors(self, tensors, delimiter=b"\n", which=None, run_bytes=0):
+        """records on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on the index's device holding shard i."""
+        self._open("records_tensors")
+        self.ctx._tensor_check(tensors, "records_tensors")
+        return self.records([t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors], delimiter, which, run_bytes)
+
+    def record_offsets(self, entry, first=0, count=None):
+        """zgpu_seek_index_read_records: O[first .. first + count) of entry `entry` (count None: to the end, O[R] = the entry's plaintext
+        length included), as a list of ints; E_BAD_ARG for an entry without records. A size query, then the call."""
+        self._open("record_offsets")
+        n = C.c_uint64(0)
+        self.ctx._check(self.L.zgpu_seek_index_read_records(self.h, entry, 0, None, 0, C.byref(n)), "zgpu_seek_index_read_records")
+        cap = max(n.value - first, 0) if count is None else min(int(count), max(n.value - first, 0))
+        a = (C.c_uint64 * max(cap, 1))()
+        self.ctx._check(self.L.zgpu_seek_index_read_records(self.h, entry, int(first), a, cap, C.byref(n)), "zgpu_seek_index_read_records")
+        return list(a[:n.value])
+
+    def set_records(self, entry, offsets, delimiter=b"\n", open_tail=False):
+        """zgpu_seek_index_set_records: the caller's own offsets for entry `entry` — O[0] = 0, strictly increasing, O[-1] = the entry's
+        plaintext length, len(offsets) - 1 records; open_tail: the last record ends in no delimiter (the call cannot see the bytes) — a
+        promise, as an anchor is"""
+        self._open("set_records")
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) and len(delimiter) == 1 else delimiter
+        if not isinstance(d, int) or d < 0 or not len(offsets):
+            raise ValueError("set_records: a delimiter of one byte and at least O[0]")
+        a = (C.c_uint64 * len(offsets))(*[int(x) for x in offsets])
+        self.ctx._check(self.L.zgpu_seek_index_set_records(self.h, entry, a, len(offsets) - 1, d | (RECORDS_OPEN_TAIL if open_tail else 0)),
+                        "zgpu_seek_index_set_records")
+
+    def records_infos(self):
+        """one SeekIndexRecords per entry (zgpu_seek_index_records_of), as it stands now"""
+        self._open("records_infos")
+        rec, out = SeekIndexRecordsC(), []
+        for i in range(len(self.infos)):
+            self.ctx._check(self.L.zgpu_seek_index_records_of(self.h, i, C.byref(rec)), "zgpu_seek_index_records_of")
+            out.append(SeekIndexRecords(rec))
         return out
 
     def export_seek_table(self, entry, checksums=False):
