@@ -1,6 +1,6 @@
 // zg_emu_records.cpp — TEST-ONLY: runs the SOURCE of the record index's kernels (zstd-rs_amd/csrc/zg_records.h: zg_k_recs_count, zg_k_recs_scan,
 // zg_k_recs_emit, zg_k_recs_find) on the CPU through the SIMT emulator of zg_simt.h, and the host forms (zgr::records_host, zgr::cut_chunks,
-// zgr::find_host) beside them. tests/test_records_cpu.py builds this file (tests/lanesuite.py; it is not in the Makefile's library), twice: as
+// zgr::find_host) beside them. tests/test_records_cpu.py and tests/test_recshapes_cpu.py build this file (tests/lanesuite.py; it is not in the Makefile's library), twice: as
 // a shared library whose accessors count every access outside what a wave may touch — a count or emit wave its own chunk's bytes and, the
 // emit wave, its own chunk's slots of the staging; the scan workgroup the counts, the frame starts, the prefixes and the totals; a find lane
 // its own entry's offsets —, and — with -DRECORDS_MAIN — as a stand-alone AddressSanitizer program in which every chunk's bytes end at the
@@ -108,20 +108,54 @@ extern "C" uint32_t zgemu_records(const uint8_t* buf, const void* chunks_, uint3
   return agree ? 0u : 1u;
 }
 
-// m <= 64 find lanes over the handle's offsets o; a lane may read [win[2j], win[2j + 1]) of them. out: the lanes' answers, host: zgr::find_host's
-// (24 bytes each); counters: [0] reads, [1] reads outside the lane's window.
+// m find lanes over the handle's offsets o, in the workgroups zg_launch_recs_find launches: ceil(m / kThreads) of kThreads, lane j = workgroup *
+// kThreads + thread, a thread with j >= m does nothing. A lane may read [win[2j], win[2j + 1]) of the offsets. out: the lanes' answers (every
+// byte kFill where no lane stored), host: zgr::find_host's (24 bytes each); counters: [0] reads, [1] reads outside the lane's window.
 extern "C" void zgemu_records_find(const uint64_t* o, const void* lanes_, uint32_t m, const uint64_t* win, void* out, void* host, uint64_t* counters) {
   const zgr::Find* lanes = (const zgr::Find*)lanes_;
   lane::Count c;
-  static zgr::Found got[64];
-  simt::run(m, [&]() {
-    const uint32_t j = zx_tid();
-    const Words<lane::Array<const uint64_t>> w{{o, win[2 * j], win[2 * j + 1], &c}};
-    got[j] = zgr::recs_find(w, lanes[j]);
-  });
-  memcpy(out, got, (size_t)m * sizeof(zgr::Found));
+  std::vector<zgr::Found> got(m);
+  memset((void*)got.data(), lane::kFill, (size_t)m * sizeof(zgr::Found));
+  for (uint32_t g = 0; g < (m + zgr::kThreads - 1) / zgr::kThreads; g++)
+    simt::run(zgr::kThreads, [&]() {
+      const uint32_t j = g * zgr::kThreads + zx_tid();
+      if (j >= m) return;
+      const Words<lane::Array<const uint64_t>> w{{o, win[2 * j], win[2 * j + 1], &c}};
+      got[j] = zgr::recs_find(w, lanes[j]);
+    });
+  memcpy(out, got.data(), (size_t)m * sizeof(zgr::Found));
   for (uint32_t j = 0; j < m; j++) { const zgr::Found h = zgr::find_host(o, lanes[j]); memcpy((uint8_t*)host + 24 * j, &h, 24); }
   counters[0] = c.n; counters[1] = c.bad;
+}
+
+// zg_k_recs_scan alone: counts (nchunks) and fstart (nframes + 1) in, prefix (nchunks) and totals (1 + nframes) out — no plaintext, so a large
+// nchunks costs nothing. Every array lies between guard bands and is seen through a counted accessor of its own; counters: [0] accesses outside
+// an array, [1] prefix stores kept, [2] stores of the total, [3] stores of a frame's total, [4] guard bands damaged.
+namespace {
+template <class A> struct SplitTotals {   // the total and the frames' totals counted apart: [0] and [1 + f] of one array
+  A tot, fr;
+  void total(uint64_t v) const { tot.st(0, v); }
+  void ftot(uint32_t f, uint64_t v) const { fr.st(1ull + f, v); }
+};
+}  // namespace
+extern "C" void zgemu_records_scan(const uint32_t* counts, uint32_t nchunks, const uint32_t* fstart, uint32_t nframes, uint64_t* prefix, uint64_t* totals,
+                                   uint64_t* counters) {
+  lane::Count cc, cf, cp, ct, cq;
+  lane::Guarded<uint32_t> gcounts(nchunks), gfstart((uint64_t)nframes + 1);
+  lane::Guarded<uint64_t> gprefix(nchunks), gtotals(1ull + nframes);
+  memcpy(gcounts.mid(), counts, (size_t)nchunks * 4);
+  memcpy(gfstart.mid(), fstart, ((size_t)nframes + 1) * 4);
+  {
+    const Counts<lane::Array<const uint32_t>> c{{gcounts.mid(), 0, nchunks, &cc}};
+    const Counts<lane::Array<const uint32_t>> f{{gfstart.mid(), 0, (uint64_t)nframes + 1, &cf}};
+    const Words<lane::Array<uint64_t>> p{{gprefix.mid(), 0, nchunks, &cp}};
+    const SplitTotals<lane::Array<uint64_t>> t{{gtotals.mid(), 0, 1, &ct}, {gtotals.mid(), 1, 1ull + nframes, &cq}};
+    scan_group(c, f, p, t, nchunks, nframes);
+  }
+  memcpy(prefix, gprefix.mid(), (size_t)nchunks * 8);
+  memcpy(totals, gtotals.mid(), (size_t)(1 + nframes) * 8);
+  counters[0] = cc.bad + cf.bad + cp.bad + ct.bad + cq.bad; counters[1] = cp.kept; counters[2] = ct.kept; counters[3] = cq.kept;
+  counters[4] = (gcounts.intact() && gfstart.intact() && gprefix.intact() && gtotals.intact()) ? 0 : 1;
 }
 
 // zgr::records_host over p[0 .. n): the offsets to out (cap slots); returns how many there are
@@ -143,8 +177,9 @@ extern "C" uint64_t zgemu_records_cut(uint64_t out_off, uint64_t size, uint64_t 
 #ifdef RECORDS_MAIN
 // argv[1]: per case [u32 kind] and
 //   kind 0 (the three kernels): [u32 nchunks][u32 nframes][u32 d][u64 cap] [nchunks x 24 bytes][(nframes + 1) x u32] and per chunk its len bytes;
-//   kind 1 (find): [u32 m][u32 pad][u32 pad][u64 nwords] [m x 48 bytes][nwords x u64].
-// argv[2]: kind 0 — counts, prefixes, totals, staging as they were left; kind 1 — m answers of 24 bytes. A chunk's bytes end at the end of a
+//   kind 1 (find): [u32 m][u32 pad][u32 pad][u64 nwords] [m x 48 bytes][nwords x u64];
+//   kind 2 (the scan alone): [u32 nchunks][u32 nframes][u32 pad][u64 pad] [nchunks x u32 counts][(nframes + 1) x u32].
+// argv[2]: kind 0 — counts, prefixes, totals, staging as they were left; kind 1 — m answers of 24 bytes; kind 2 — prefixes, totals. A chunk's bytes end at the end of a
 // heap block that begins at a multiple of 16 out_off % 16 bytes in front of them; every other array lies in a block of exactly its length and
 // is accessed directly: an access outside one is an AddressSanitizer report.
 int main(int argc, char** argv) {
@@ -165,6 +200,18 @@ int main(int argc, char** argv) {
         g.write(&r, 24, 1);
       }
       free(o); free(lanes);
+      continue;
+    }
+    if (kind == 2) {
+      const uint32_t nchunks = h[0], nframes = h[1];
+      uint32_t* counts = (uint32_t*)f.block((uint64_t)nchunks * 4);
+      uint32_t* fstart = (uint32_t*)f.block(((uint64_t)nframes + 1) * 4);
+      uint64_t* prefix = (uint64_t*)malloc((size_t)nchunks * 8);
+      uint64_t* totals = (uint64_t*)malloc((size_t)(1 + nframes) * 8);
+      scan_group(Counts<lane::DirectArray<const uint32_t>>{{counts}}, Counts<lane::DirectArray<const uint32_t>>{{fstart}},
+                 Words<lane::DirectArray<uint64_t>>{{prefix}}, Totals<lane::DirectArray<uint64_t>>{{totals}}, nchunks, nframes);
+      g.write(prefix, 8, nchunks); g.write(totals, 8, 1 + (size_t)nframes);
+      free(totals); free(prefix); free(fstart); free(counts);
       continue;
     }
     const uint32_t nchunks = h[0], nframes = h[1], d = h[2];

@@ -1,5 +1,5 @@
 """The model of the record index (include/zgpu.h: "record index"; zstd-rs_amd/csrc/zg_records.h), for the CPU suite of its kernels
-(test_records_cpu) and the GPU suite of its calls (test_gpu_seek_index_records). Nothing here comes from the code under test: a record
+(test_records_cpu, test_recshapes_cpu) and the GPU suites of its calls (test_gpu_seek_index_records, test_gpu_recshapes). Nothing here comes from the code under test: a record
 offset is numpy.flatnonzero(plain == d) + 1, with O[0] = 0 in front and, for an open tail, O[R] = L behind."""
 import numpy as np
 
@@ -56,3 +56,14 @@ def expected(buf, frames, d):
         ftot.append(len(found))
         staging += found
     return counts, prefix, [at] + ftot, staging
+
+
+def scan(counts, fstart):
+    """what zg_k_recs_scan leaves for the chunks' counts and the frames' first chunks fstart[0 .. nframes]: (prefixes, total, frame totals),
+    in plain Python integers — prefix[i] = counts[0] + ... + counts[i - 1], P(nchunks) = the total, a frame's total P(fstart[f + 1]) - P(fstart[f])"""
+    prefix, at = [], 0
+    for c in counts:
+        prefix.append(at)
+        at += int(c)
+    P = prefix + [at]
+    return prefix, at, [P[fstart[f + 1]] - P[fstart[f]] for f in range(len(fstart) - 1)]

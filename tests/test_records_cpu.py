@@ -35,6 +35,8 @@ def _declare(L):
     L.zgemu_records.restype = C.c_uint32
     L.zgemu_records_find.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
     L.zgemu_records_find.restype = None
+    L.zgemu_records_scan.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]   # (tests/test_recshapes_cpu.py: the scan alone)
+    L.zgemu_records_scan.restype = None
     L.zgemu_records_host.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.c_uint64]
     L.zgemu_records_host.restype = C.c_uint64
     L.zgemu_records_cut.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64]
