@@ -792,6 +792,61 @@ int zgpu_gather_records_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, co
                                            const zgpu_record_range* recs, uint32_t m, void* const* device_dsts /* m */,
                                            const size_t* caps /* m */, const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */);
 
+/* ---- record batches: gather records into one padded or packed tensor ---------------------------------------------------------------------------
+ * zgpu_gather_records_indexed_device_src delivers m separate destinations, which the caller sizes with a lookup of its own. A training step
+ * consumes ONE tensor: PADDED — uint8[m, width], every row a record followed by the pad byte, plus lengths[m] — or PACKED — the records back to
+ * back plus offsets[m + 1] (the cu_seqlens form). zgpu_gather_records_batch_indexed_device_src writes either, layered on the calls above:
+ * 1. LOOKUP. The record lookup exactly as in zgpu_seek_index_record_ranges_device: one zg_k_recs_find launch, 24 bytes per range,
+ *    ZGPU_RECORDS_STRIP and the status rules. len_j: the range's byte length, 0 where the lookup gave a status or the range is empty.
+ *    host_record_bytes[j] = len_j (HOST memory), before any truncation.
+ * 2. LAYOUT, on the host from the lookup alone, before anything is decoded (zg_records.h: plan_rows). want_j = len_j, or min(len_j, width)
+ *    under ZGPU_BATCH_TRUNCATE with width > 0; rows_truncated counts the rows that were cut. Padded: at_j = j * width, slot_j = width,
+ *    total = m * width. Packed: at_j = want_0 + ... + want_{j-1}, slot_j = want_j, total = at_m. Every sum and product is checked: a layout
+ *    that does not fit in 64 bits is ZGPU_E_BAD_ARG.
+ * 3. ARGUMENTS. ZGPU_E_BAD_ARG for the whole call, with nothing written: a null batch, results or info; a handle of another context; n other
+ *    than the handle's entry count; an unknown layout, unknown flag bits, reserved != 0; pad_byte > 255; padded with width == 0; packed with
+ *    width != 0 and no ZGPU_BATCH_TRUNCATE; device_lengths or device_offsets not 8-byte aligned; device_lengths (m slots), device_offsets
+ *    (m + 1 slots) or, when 0 < total <= cap, [device_dst, device_dst + total) not device memory of the context's device inside one
+ *    allocation (the check of the other device-sink calls); options the gather refuses. All of these are found before anything is launched,
+ *    but for a packed batch's device_dst and a packed sum that overflows, which need the lookup (it reads the handle and writes nothing of
+ *    the caller's). A wrong pointer is a status, never a GPU fault.
+ * 4. THE BATCH DOES NOT FIT (total > cap): info->total holds the need, every range whose lookup succeeded gets ZGPU_E_TARGET_TOO_SMALL (the
+ *    others keep the lookup's status), nothing behind the lookup is launched, NOTHING IN DEVICE MEMORY IS WRITTEN, the two arrays included,
+ *    and the call returns ZGPU_OK. cap == 0 with device_dst == NULL is therefore the size query.
+ * 5. GATHER. Else the byte ranges (entry, begin_j, want_j) go through zgpu_gather_ranges_indexed_device_src with destination
+ *    device_dst + at_j and capacity slot_j: groups, fate sharing, verdict order, the three option flags, entries decoded alone and results[j]
+ *    are that call's, field for field. A truncated range asks for fewer bytes, so the frames behind the cut are neither selected nor
+ *    decoded. Without ZGPU_BATCH_TRUNCATE a padded row with len_j > width is that call's own ZGPU_E_TARGET_TOO_SMALL for that row alone. A
+ *    range whose lookup failed keeps the lookup's status, as in zgpu_gather_records_indexed_device_src.
+ * 6. FINISH, behind the gather's verdicts. final_j = results[j].d.r.written if the row's status is 0, else 0. ONE zg_k_fill launch
+ *    (zg_scatter.h: a ragged fill of m regions, one wave per chunk, plain vector stores) writes pad_byte into [at_j + final_j, at_j + slot_j)
+ *    of every row: a failed row is all pad in both layouts, and in the packed layout its slot keeps its place. device_lengths[j] = final_j,
+ *    device_offsets[j] = at_j, device_offsets[m] = total, by host-to-device copies on the engine's stream. The streams are drained on return.
+ *    ON ZGPU_OK WITH total <= cap EVERY BYTE OF [device_dst, device_dst + total) IS EITHER A RECORD'S BYTE OR THE PAD BYTE: no result depends
+ *    on memory the call never wrote. No byte at or behind device_dst + total is written, and none outside the arrays' m and m + 1 slots.
+ *    info: total, bytes_filled (pad bytes written), rows_ok, rows_failed (rows with a status), rows_truncated.
+ * 7. m == 0: total = 0, device_offsets[0] = 0 if the array is given, no launch.
+ * The call adds no status code. Diagnostics: zgpu_debug_ranges_stats appends [22] fill launches, [23] their microseconds (HIP events), [24]
+ * bytes filled, [25] bytes uploaded into the two arrays. A caller that asks for 22 gets what it always got.
+ * Out of scope: the fill fused into the scatter's chunks, record numbers that live in device memory, host sources, several GPUs, element
+ * types other than bytes. */
+#define ZGPU_BATCH_PADDED   0u
+#define ZGPU_BATCH_PACKED   1u
+#define ZGPU_BATCH_TRUNCATE 1u          /* zgpu_record_batch.flags */
+typedef struct {
+  void*     device_dst;  uint64_t cap;  /* the batch: ONE piece of device memory, any alignment */
+  uint64_t* device_lengths;             /* m values, or NULL */
+  uint64_t* device_offsets;             /* m + 1 values, or NULL */
+  uint64_t* host_record_bytes;          /* m values in HOST memory, or NULL: each range's length before any truncation */
+  uint64_t  width;                      /* padded: bytes per row, > 0; packed: 0, or with TRUNCATE the most bytes taken of one range */
+  uint32_t  layout, flags, pad_byte, reserved;
+} zgpu_record_batch;
+typedef struct { uint64_t total, bytes_filled; uint32_t rows_ok, rows_failed, rows_truncated, pad; } zgpu_record_batch_info;
+int zgpu_gather_records_batch_indexed_device_src(zgpu_ctx*, const zgpu_seek_index*, const void* const* device_srcs, const size_t* lens, uint32_t n,
+                                                 const zgpu_record_range* recs, uint32_t m, const zgpu_record_batch* batch,
+                                                 const zgpu_device_opts* opts_or_null, zgpu_range_result* results /* m */,
+                                                 zgpu_record_batch_info* info);
+
 /* ---- the same over several GPUs: frames are independent, a host-side work queue shards them (no collective) -------
  * One worker thread + one engine (HIP streams, device buffers) per GPU inside the library. Replaces the frame loop of
  * FrameDecoder::decode_all (frame_decoder.rs:541-577), which decodes the frames of a buffer one after the other. */

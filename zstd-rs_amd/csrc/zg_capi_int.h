@@ -39,6 +39,11 @@ enum { kManyStatGroupsDecoded = 0, kManyStatPrefixLaunches, kManyStatPrefixUs, k
 // and behind those (out[19] ...): the lookup of the calls that take record numbers (zg_records.h) — zg_k_recs_find launches, their microseconds
 // (HIP events), the bytes they brought back (24 per range)
 enum { kRecFindStatLaunches = 0, kRecFindStatUs, kRecFindStatBytesDownloaded, kRecFindStatCount };
+// and behind those (out[22] ...): the finish of a record batch (zg_scatter.h: zg_k_fill) — fill launches, their microseconds (HIP events), bytes
+// filled, bytes uploaded into the batch's two arrays
+enum { kBatchStatFillLaunches = 0, kBatchStatFillUs, kBatchStatBytesFilled, kBatchStatBytesUploaded, kBatchStatCount };
+static_assert(kBatchStatFillLaunches == zg::kPassLaunches && kBatchStatFillUs == zg::kPassUs && kBatchStatBytesFilled == zg::kPassBytes,
+              "the array handed to Engine::fill_pass");
 static_assert(kSrcStatWalkLaunches == zg::kPassLaunches && kSrcStatWalkUs == zg::kPassUs && kSrcStatSkeletonBytes == zg::kPassBytes &&
               kIndexStatLaunches == zg::kPassLaunches && kIndexStatKernelUs == zg::kPassUs && kIndexStatBytesDownloaded == zg::kPassBytes &&
               kRangeStatSeekLaunches == zg::kPassLaunches && kRangeStatSeekUs == zg::kPassUs && kRangeStatSeekBytesDownloaded == zg::kPassBytes,
@@ -59,7 +64,8 @@ struct zgpu_ctx {
   uint64_t ranges_stats[kRangeStatCount] = {};            // the seek and decode_ranges calls (zgpu_debug_ranges_stats)
   uint64_t ranges_many_stats[kManyStatCount] = {};        //   the slots behind them (zgpu_frames_seek_table_many_device, zgpu_gather_ranges_seek_table_device_src)
   uint64_t ranges_rec_stats[kRecFindStatCount] = {};      //   and behind those (zgpu_seek_index_record_ranges_device, zgpu_gather_records_indexed_device_src)
-  uint64_t hash_ranges_us = 0;                           // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
+  uint64_t ranges_batch_stats[kBatchStatCount] = {};      //   and behind those (zgpu_gather_records_batch_indexed_device_src)
+  uint64_t hash_ranges_us = 0;                          // kernel time of the last zgpu_debug_hash_ranges call (HIP events)
   std::string err;
 };
 

@@ -588,6 +588,31 @@ int Engine::records_find(const zgr::Find* lanes, uint32_t m, const uint64_t* rec
                    [&](LaneTmp& d, hipStream_t s) { zg_launch_recs_find(d.lanes.as<zgr::Find>(), m, recs, d.out.as<zgr::Found>(), s); });
 }
 
+int Engine::fill_pass(const zgs::Seg* regions, uint32_t n, uint32_t byte, uint64_t* stats) {
+  Engine* eng = this;
+  std::vector<zgs::Chunk> ch;
+  zgs::plan_chunks(regions, n, zgs::kFillChunk, &ch);
+  if (ch.empty()) return ZG_OK;
+  if (ch.size() > 0xFFFFFFFFull) return ZG_INTERNAL;
+  uint64_t bytes = 0;
+  for (const zgs::Chunk& c : ch) bytes += c.len;
+  ZG_HIP(hipSetDevice(device_));
+  LaneTmp t;   // (lanes: the regions, the chunk table behind them; nothing comes back)
+  const size_t sb = (size_t)n * sizeof(zgs::Seg), cb = ch.size() * sizeof(zgs::Chunk);
+  const int st = t.reserve(sb + cb);
+  if (st) return st;
+  ZG_HIP(t.upload(regions, sb, ch.data(), cb, stream_));
+  ZG_HIP(hipStreamSynchronize(stream_));   // (pageable)
+  ZG_HIP(t.begin(stream_));
+  zg_launch_fill(t.at<zgs::Seg>(0), t.at<zgs::Chunk>(sb), (uint32_t)ch.size(), byte, stream_);
+  ZG_HIP(t.end(stream_));
+  ZG_HIP(hipStreamSynchronize(stream_));
+  uint64_t us = 0;
+  ZG_HIP(t.elapsed_us(&us));
+  stats[kPassLaunches] += 1; stats[kPassUs] += us; stats[kPassBytes] += bytes;
+  return ZG_OK;
+}
+
 int Engine::hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats) {
   if (!n) return ZG_OK;
   LaneTmp t;

@@ -355,6 +355,10 @@ class Engine {
   // launch; recs: the handle's array (device memory the handle owns; the caller checked every lane's rpre + nrec against it), out[j] = lane
   // j's 24-byte answer.
   int records_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, uint64_t* stats);
+  // fill_pass — `byte` into the n regions (zgs::Seg, src_off unused) of device memory the CALLER checked, region by region, against the one
+  // piece they lie in (zg_scatter.h: zg_k_fill): the regions and their chunk table go up, ONE launch between two HIP events, the stream is
+  // drained. stats[kPassBytes] counts the bytes FILLED (nothing comes back). Regions of length 0 only: no pass at all.
+  int fill_pass(const zgs::Seg* regions, uint32_t n, uint32_t byte, uint64_t* stats);
   // hash_ranges_pass — XXH64 of ranges[0 .. n) of base (device memory the caller has checked) by the hash kernel `kernel` chooses
   // (zg_launch_xxh64_with); digests[i] is ranges[i]'s (zgpu_debug_hash_ranges).
   int hash_ranges_pass(const uint8_t* base, const ZgHashRange* ranges, uint32_t n, int kernel, uint64_t* digests, uint64_t* stats);

@@ -813,7 +813,7 @@ void zgf::reset_stats(zgpu_ctx* c, unsigned owned) {
   if (owned & kOwnsDevice) zero(c->frames_device_stats);
   if (owned & kOwnsSrc) zero(c->frames_device_src_stats);
   if (owned & kOwnsIndex) zero(c->frames_index_stats);
-  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); zero(c->ranges_rec_stats); }
+  if (owned & kOwnsRanges) { zero(c->ranges_stats); zero(c->ranges_many_stats); zero(c->ranges_rec_stats); zero(c->ranges_batch_stats); }
 }
 
 int zgf::drain(zgpu_ctx* c, int st) {

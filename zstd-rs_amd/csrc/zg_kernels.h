@@ -109,3 +109,5 @@ void zg_launch_recs_scan(const uint32_t* counts, uint32_t nchunks, const uint32_
 void zg_launch_recs_emit(const uint8_t* out, const zgr::Chunk* chunks, uint32_t n, uint32_t d, const uint64_t* prefix, uint64_t* staging, uint64_t total,
                          hipStream_t s);
 void zg_launch_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, hipStream_t s);
+// zg_k_fill (zg_scatter.h): `byte` into the chunks of the regions segs[] (src_off unused), one wave per chunk
+void zg_launch_fill(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, uint32_t byte, hipStream_t s);

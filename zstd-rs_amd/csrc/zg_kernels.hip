@@ -2295,3 +2295,17 @@ void zg_launch_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* rec
   if (!m) return;
   hipLaunchKernelGGL(zg_k_recs_find, dim3((m + zgr::kThreads - 1) / zgr::kThreads), dim3(zgr::kThreads), 0, s, lanes, m, recs, out);
 }
+
+// The ragged fill behind a record batch (zg_scatter.h: zg_k_fill — the plan, the lane routine, the shape and why): one wave per chunk of the
+// host's plan, grid-stride over the chunk table. Behind the record kernels, for the reason they are behind everything else. The host checked
+// every region against the batch and the batch against the runtime's allocation table before the launch (zg_ranges.cpp).
+__global__ void __launch_bounds__(zgs::kFillThreads) zg_k_fill(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, uint32_t byte) {
+  const ZgScatterWrite w{};
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const zgs::Chunk ch = chunks[c];
+    zgs::fill_chunk(w, segs[ch.seg].dst + ch.at, ch.len, (uint8_t)byte, threadIdx.x, zgs::kFillThreads);
+  }
+}
+void zg_launch_fill(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, uint32_t byte, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(zg_k_fill, dim3(nchunks < zgs::kFillMaxGroups ? nchunks : zgs::kFillMaxGroups), dim3(zgs::kFillThreads), 0, s, segs, chunks, nchunks, byte);
+}

@@ -11,6 +11,8 @@
 // and gather_groups is shared. zgpu_seek_index_measure_device builds the same handle for entries whose frames declare nothing: measure_entries
 // cuts their frame records into runs, runs them through the device-source machinery and Batch::measure (zg_seqsize.h), and the sizes that
 // come back become the pairs; zgpu_seek_index_export_seek_table writes an entry's pairs out as a seek table (zg_seektab.h).
+// The calls that take record NUMBERS (zg_records.h) are a lookup in front of the indexed gather; zgpu_gather_records_batch_indexed_device_src
+// lays that gather's destinations out in ONE piece of device memory (plan_rows) and pads what it left unwritten (zg_scatter.h: zg_k_fill).
 #include <stddef.h>
 #include <algorithm>
 #include <string.h>
@@ -1069,6 +1071,106 @@ extern "C" int zgpu_gather_records_indexed_device_src(zgpu_ctx* c, const zgpu_se
   memcpy(c->ranges_rec_stats, find_stats, sizeof find_stats);
   return st;
 }
+// ---- record batches (include/zgpu.h: record batches; zg_records.h: plan_rows; zg_scatter.h: zg_k_fill) ---------------------------------------------
+static_assert(sizeof(zgpu_record_batch) == 64 && offsetof(zgpu_record_batch, width) == 40 && offsetof(zgpu_record_batch, layout) == 48 &&
+              sizeof(zgpu_record_batch_info) == 32 && offsetof(zgpu_record_batch_info, rows_ok) == 16 && ZGPU_BATCH_PADDED == zgr::kBatchPadded &&
+              ZGPU_BATCH_PACKED == zgr::kBatchPacked, "include/zgpu.h");
+// The lookup, the layout (plan_rows), the indexed gather on the byte ranges with every destination a piece of the ONE batch, then the finish:
+// one zg_k_fill launch over what the gather left unwritten of every row's slot, and the two arrays from what the host holds.
+extern "C" int zgpu_gather_records_batch_indexed_device_src(zgpu_ctx* c, const zgpu_seek_index* x, const void* const* device_srcs, const size_t* lens,
+                                                            uint32_t n, const zgpu_record_range* recs, uint32_t m, const zgpu_record_batch* batch,
+                                                            const zgpu_device_opts* opts, zgpu_range_result* results, zgpu_record_batch_info* info) {
+  if (!c || !x || x->ctx != c || n != x->ents.size() || (n && (!device_srcs || !lens)) || (m && !recs) || !batch || !results || !info) return ZGPU_E_BAD_ARG;
+  const zgpu_record_batch& b = *batch;
+  const bool padded = b.layout == ZGPU_BATCH_PADDED, truncate = (b.flags & ZGPU_BATCH_TRUNCATE) != 0;
+  if (b.layout > ZGPU_BATCH_PACKED || (b.flags & ~ZGPU_BATCH_TRUNCATE) || b.reserved || b.pad_byte > 255u || (padded && !b.width) ||
+      (!padded && b.width && !truncate) || ((uintptr_t)b.device_lengths & 7) || ((uintptr_t)b.device_offsets & 7))
+    return ZGPU_E_BAD_ARG;
+  int st;
+  (void)device_sink(c, opts, nullptr, &st, true);   // (the options the gather would refuse, refused before anything is launched)
+  if (st) return st;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  uint8_t* const dst = (uint8_t*)b.device_dst;
+  const int device = c->eng->device();
+  std::vector<DevRange> known;
+  if ((b.device_lengths && m && !check_device_range(device, b.device_lengths, (size_t)m * 8, known)) ||
+      (b.device_offsets && !check_device_range(device, b.device_offsets, ((size_t)m + 1) * 8, known)))
+    return ZGPU_E_BAD_ARG;
+  // (padded: the total is known without the lookup, and a batch that is no device memory is refused before the lookup's launch; packed: behind
+  // it — the lookup reads the handle's offsets and writes nothing of the caller's)
+  const auto dst_ok = [&](uint64_t total) { return !total || total > b.cap || (total <= SIZE_MAX && check_device_range(device, dst, (size_t)total, known)); };
+  if (padded && (m > UINT64_MAX / b.width || !dst_ok((uint64_t)m * b.width))) return ZGPU_E_BAD_ARG;
+  for (uint32_t j = 0; j < m; j++) memset(&results[j], 0, sizeof results[j]);
+  std::vector<zgr::Found> found;
+  uint64_t find_stats[kRecFindStatCount] = {}, batch_stats[kBatchStatCount] = {};
+  if ((st = lookup_records(c, x, recs, m, &found, find_stats))) return st;
+  std::vector<uint64_t> len(m);
+  for (uint32_t j = 0; j < m; j++) len[j] = found[j].status ? 0 : found[j].len;
+  std::vector<zgr::Row> rows(m);
+  uint64_t total = 0;
+  uint32_t cut = 0;
+  if (!zgr::plan_rows(len.data(), m, b.layout, truncate, b.width, rows.data(), &total, &cut) || !dst_ok(total)) return ZGPU_E_BAD_ARG;
+  if (b.host_record_bytes) for (uint32_t j = 0; j < m; j++) b.host_record_bytes[j] = len[j];
+  *info = zgpu_record_batch_info{total, 0, 0, 0, cut, 0};
+  const auto own_stats = [&]() {   // (the gather zeroed the arrays of its family: this call's lookup and finish go back in)
+    memcpy(c->ranges_rec_stats, find_stats, sizeof find_stats);
+    memcpy(c->ranges_batch_stats, batch_stats, sizeof batch_stats);
+  };
+  hipStream_t s = c->eng->stream();
+  std::vector<uint64_t> lengths(m, 0), offsets((size_t)m + 1, 0);   // (host words the copies read until the stream is drained)
+  if (total > b.cap) {   // the batch does not fit: the need in info->total, nothing behind the lookup is launched, no device memory is written
+    reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+    for (uint32_t j = 0; j < m; j++) {
+      results[j].d.r.status = found[j].status ? (int)found[j].status : ZGPU_E_TARGET_TOO_SMALL;
+      info->rows_failed++;
+    }
+    own_stats();
+    return ZGPU_OK;
+  }
+  if (m) {
+    std::vector<zgpu_entry_range> ranges(m);
+    std::vector<void*> dsts(m);
+    std::vector<size_t> caps(m);
+    for (uint32_t j = 0; j < m; j++) {
+      ranges[j] = found[j].status ? zgpu_entry_range{0, 0, 0, 0} : zgpu_entry_range{found[j].begin, rows[j].want, found[j].entry, 0};
+      dsts[j] = dst + rows[j].at;
+      caps[j] = (size_t)rows[j].slot;
+    }
+    if ((st = zgpu_gather_ranges_indexed_device_src(c, x, device_srcs, lens, n, ranges.data(), m, dsts.data(), caps.data(), opts, results))) return st;
+    // the finish: what of every slot the gather did not write
+    std::vector<zgs::Seg> regions(m);
+    for (uint32_t j = 0; j < m; j++) {
+      if (found[j].status) { memset(&results[j], 0, sizeof results[j]); results[j].d.r.status = (int)found[j].status; }
+      const zgpu_entry_result& r = results[j].d.r;
+      const uint64_t fin = r.status ? 0 : r.written;
+      // (every region is held against the batch before the launch, as the scatter's caller holds its segments against the output)
+      if (fin > rows[j].slot || rows[j].at > total || rows[j].slot > total - rows[j].at) {
+        c->eng->last_error = "zgpu_gather_records_batch_indexed_device_src: a row that leaves the batch";
+        return ZGPU_E_INTERNAL;
+      }
+      regions[j] = zgs::Seg{0, (uint64_t)(uintptr_t)dst + rows[j].at + fin, rows[j].slot - fin};
+      lengths[j] = fin;
+      offsets[j] = rows[j].at;
+      info->bytes_filled += rows[j].slot - fin;
+      if (r.status) info->rows_failed++; else info->rows_ok++;
+    }
+    st = c->eng->fill_pass(regions.data(), m, b.pad_byte, batch_stats);
+  } else {
+    reset_stats(c, kOwnsDecode | kOwnsDevice | kOwnsSrc | kOwnsRanges);
+  }
+  offsets[m] = total;
+  if (!st && b.device_lengths && m) {
+    if (hipMemcpyAsync(b.device_lengths, lengths.data(), (size_t)m * 8, hipMemcpyHostToDevice, s) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    else batch_stats[kBatchStatBytesUploaded] += (uint64_t)m * 8;
+  }
+  if (!st && b.device_offsets) {
+    if (hipMemcpyAsync(b.device_offsets, offsets.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) { (void)hipGetLastError(); st = ZGPU_E_HIP; }
+    else batch_stats[kBatchStatBytesUploaded] += ((uint64_t)m + 1) * 8;
+  }
+  st = drain(c, st);
+  own_stats();
+  return st;
+}
 extern "C" void zgpu_seek_index_destroy(zgpu_seek_index* x) {
   if (!x) return;
   if (x->pairs.p && x->ctx && hipSetDevice(x->ctx->eng->device()) != hipSuccess) (void)hipGetLastError();
@@ -1124,5 +1226,7 @@ extern "C" int zgpu_debug_ranges_stats(const zgpu_ctx* c, uint64_t* out, int n) 
   int k = copy_stats(c->ranges_stats, out, n);   // (the slots of the calls with many ranges per entry lie behind the others, the record lookup's behind them)
   if (k < (int)kRangeStatCount || !out) return k;
   k += copy_stats(c->ranges_many_stats, out + k, n - k);
-  return k < (int)(kRangeStatCount + kManyStatCount) ? k : k + copy_stats(c->ranges_rec_stats, out + k, n - k);
+  if (k < (int)(kRangeStatCount + kManyStatCount)) return k;
+  k += copy_stats(c->ranges_rec_stats, out + k, n - k);   // (and the finish of a record batch behind the lookup)
+  return k < (int)(kRangeStatCount + kManyStatCount + kRecFindStatCount) ? k : k + copy_stats(c->ranges_batch_stats, out + k, n - k);
 }

@@ -122,6 +122,29 @@ inline Found find_host(const uint64_t* o, const Find& f) {
   return Found{begin, len, f.entry, 0};
 }
 
+// The layout of a record batch (include/zgpu.h: "record batches"), decided on the host from the lookup's lengths alone, before anything is
+// decoded. len[j]: range j's byte length (0 where the lookup gave a status). want = len, or min(len, width) under truncate with width > 0.
+// Padded: at = j * width, slot = width, total = m * width. Packed: at = the sum of the wants in front, slot = want, total = the sum of all.
+// False — and nothing of *rows is to be used — if a product or a sum does not fit in 64 bits.
+constexpr uint32_t kBatchPadded = 0, kBatchPacked = 1;
+struct Row { uint64_t at, slot, want; };
+inline bool plan_rows(const uint64_t* len, uint32_t m, uint32_t layout, bool truncate, uint64_t width, Row* rows, uint64_t* total, uint32_t* truncated) {
+  *total = 0; *truncated = 0;
+  const bool cut = truncate && width > 0;
+  if (layout == kBatchPadded && width && m > UINT64_MAX / width) return false;
+  uint64_t at = 0;
+  for (uint32_t j = 0; j < m; j++) {
+    const uint64_t want = cut && len[j] > width ? width : len[j];
+    if (want != len[j]) (*truncated)++;
+    const uint64_t slot = layout == kBatchPadded ? width : want;
+    if (slot > UINT64_MAX - at) return false;
+    rows[j] = Row{at, slot, want};
+    at += slot;
+  }
+  *total = at;
+  return true;
+}
+
 }  // namespace zgr
 #endif  // ZG_RECORDS_TYPES
 

@@ -17,6 +17,22 @@
 // each; head and tail are global_load_ubyte / global_store_byte; 38 VGPRs, no scratch, no LDS. (The writer stores through address space 1:
 // through a generic pointer made from the table's integer the stores are flat_store_dwordx4.) Measured: 512 MiB in 187 us, 0.51 x the time
 // of the 16 B/lane calibration copy on the same bytes; 16 / 64 / 256 KiB chunks measure the same (LABNOTES.md "decode_frames_device").
+//
+// zg_k_fill — the store half of the same problem: m byte regions of any length and alignment in ONE piece of the caller's device memory set to
+// one byte (zgpu_gather_records_batch_indexed_device_src: the pad behind every row of a record batch). A region is a Seg whose src_off is
+// unused; plan_chunks cuts the regions with kFillChunk, so inner chunk boundaries lie on 16-byte boundaries of the destination, only a
+// region's first chunk has head bytes and only its last one tail bytes. fill_chunk is copy_chunk without the loads: head bytes up to the
+// 16-byte boundary (one st1 per lane), st16 of the replicated byte at multiples of 16 — four in flight per lane —, tail bytes. Plain vector
+// stores, no nontemporal ones (above), no atomics; the kernel reads its two tables and nothing else.
+// Shape: ONE WAVE per chunk (kFillThreads = 64, a workgroup is a wave), grid-stride over the chunk table, at most kFillMaxGroups workgroups;
+// kFillChunk = 4096 bytes is four passes of 64 lanes x 16 bytes. Why: a pad region is a fraction of a row — hundreds of bytes to a few KiB —,
+// so a chunk rarely has more than 64 16-byte stores to hand out and three of a 256-thread workgroup's four waves would compute a head, a
+// body count and a tail only to store nothing; with a wave per chunk the CUs hold four times as many chunks in flight. UNMEASURED as a
+// comparison of shapes: LABNOTES.md "records_batch" has what was measured of this one. The host checks every region against
+// [device_dst, device_dst + total) before the launch (zg_ranges.cpp).
+// gfx950 ISA of zg_k_fill (hipcc -O3 --save-temps, the code object's metadata and the .s): 18 VGPRs, 32 SGPRs, no scratch (private segment 0),
+// no spill, no LDS. Per chunk 1 global_load_dwordx4 (the 16-byte Chunk) and 1 global_load_dwordx2 (the region's dst); the head and the tail
+// are 1 global_store_byte each, the body loop 4 global_store_dwordx4 per iteration and its remainder loop 1. No flat_*, no atomic.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -35,7 +51,11 @@ constexpr uint32_t kMaxGroups = 2048;        // workgroups of a launch (8 per CU
 constexpr uint32_t kChunkDefault = 64u << 10;   // bytes per chunk: 16 passes of 256 lanes x 16 bytes (LABNOTES.md "decode_frames_device")
 constexpr uint32_t kChunkMin = 4096;
 
-struct Seg { uint64_t src_off, dst, len; };       // dst: the destination's address
+constexpr uint32_t kFillThreads = 64;        // zg_k_fill: one wave takes a chunk
+constexpr uint32_t kFillMaxGroups = 2048;    // zg_k_fill: workgroups (waves) of a launch
+constexpr uint32_t kFillChunk = 4096;        // zg_k_fill: bytes per chunk, four passes of 64 lanes x 16 bytes
+
+struct Seg { uint64_t src_off, dst, len; };       // dst: the destination's address (zg_k_fill: src_off is unused)
 struct Chunk { uint32_t seg, len; uint64_t at; };   // bytes [at, at + len) of segment seg
 struct alignas(16) V16 { uint64_t a, b; };
 
@@ -81,6 +101,26 @@ template <class R, class W> ZG_SC_FN void copy_chunk(const R& r, const W& w, uin
   for (; k < nbody; k += T) w.st16(d0 + 16ull * k, r.ld16(s0 + 16ull * k));
   const uint32_t done = head + (nbody << 4);   // (the tail is shorter than 16 bytes)
   if (t < len - done) w.st1(dst + done + t, r.ld1(src + done + t));
+}
+
+// What lane t of T does for the chunk [dst, dst + len) of a fill: W as above, `byte` into every byte. No byte is read.
+template <class W> ZG_SC_FN void fill_chunk(const W& w, uint64_t dst, uint32_t len, uint8_t byte, uint32_t t, uint32_t T) {
+  uint32_t head = (uint32_t)((16 - (dst & 15)) & 15);
+  if (head > len) head = len;
+  if (t < head) w.st1(dst + t, byte);
+  const uint32_t nbody = (len - head) >> 4;
+  const uint64_t d0 = dst + head, r = 0x0101010101010101ull * byte;
+  const V16 v{r, r};
+  uint32_t k = t;
+  for (; k + 3 * T < nbody; k += 4 * T) {   // four stores in flight per lane
+    w.st16(d0 + 16ull * k, v);
+    w.st16(d0 + 16ull * (k + T), v);
+    w.st16(d0 + 16ull * (k + 2 * T), v);
+    w.st16(d0 + 16ull * (k + 3 * T), v);
+  }
+  for (; k < nbody; k += T) w.st16(d0 + 16ull * k, v);
+  const uint32_t done = head + (nbody << 4);   // (the tail is shorter than 16 bytes)
+  if (t < len - done) w.st1(dst + done + t, byte);
 }
 
 }  // namespace zgs

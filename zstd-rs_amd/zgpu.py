@@ -268,6 +268,35 @@ class RecordRangeC(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("entry", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RecordBatchC(C.Structure):
+    """zgpu_record_batch (include/zgpu.h)"""
+    _fields_ = [("device_dst", C.c_void_p), ("cap", C.c_uint64), ("device_lengths", C.c_void_p), ("device_offsets", C.c_void_p),
+                ("host_record_bytes", C.POINTER(C.c_uint64)), ("width", C.c_uint64), ("layout", C.c_uint32), ("flags", C.c_uint32),
+                ("pad_byte", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RecordBatchInfoC(C.Structure):
+    """zgpu_record_batch_info (include/zgpu.h)"""
+    _fields_ = [("total", C.c_uint64), ("bytes_filled", C.c_uint64), ("rows_ok", C.c_uint32), ("rows_failed", C.c_uint32),
+                ("rows_truncated", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class RecordBatchInfo:
+    """What Context.gather_records_batch says of the batch it wrote (zgpu_record_batch_info): total — the bytes the layout needs —,
+    bytes_filled — pad bytes written —, rows_ok, rows_failed (rows with a status), rows_truncated."""
+    __slots__ = FIELDS = ("total", "bytes_filled", "rows_ok", "rows_failed", "rows_truncated")
+
+    def __init__(self, c):
+        for k in self.FIELDS:
+            setattr(self, k, int(getattr(c, k)))
+
+    def __repr__(self):
+        return "RecordBatchInfo(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k in self.FIELDS)
+
+
+BATCH_PADDED, BATCH_PACKED = 0, 1                    # zgpu_record_batch.layout
+BATCH_TRUNCATE = 1                                   # zgpu_record_batch.flags
+_BATCH_LAYOUTS = {"padded": BATCH_PADDED, "packed": BATCH_PACKED}
 RECORDS_NONE, RECORDS_FOUND, RECORDS_SET = 0, 1, 2   # SeekIndexRecords.state
 RECORDS_STRIP = 1                                    # zgpu_record_range.flags
 RECORDS_OPEN_TAIL = 0x80000000                       # zgpu_seek_index_set_records' delimiter word
@@ -403,7 +432,7 @@ EXPORTS = [
     "zgpu_seek_index_hash_device", "zgpu_seek_index_set_sums", "zgpu_seek_index_read_sums", "zgpu_seek_index_sums_of",
     "zgpu_seek_index_export_seek_table_ex",
     "zgpu_seek_index_records_device", "zgpu_seek_index_records_of", "zgpu_seek_index_read_records", "zgpu_seek_index_set_records",
-    "zgpu_seek_index_record_ranges_device", "zgpu_gather_records_indexed_device_src",
+    "zgpu_seek_index_record_ranges_device", "zgpu_gather_records_indexed_device_src", "zgpu_gather_records_batch_indexed_device_src",
     "zgpu_frames_seek_table_many_device", "zgpu_gather_ranges_seek_table_device_src",
     "zgpu_frames_seek_table_device", "zgpu_decode_ranges_seek_table_device_src",
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
@@ -508,6 +537,8 @@ def _declare(L):
     L.zgpu_seek_index_record_ranges_device.argtypes = [vp, vp, P(RecordRangeC), C.c_uint32, P(EntryRangeC), P(C.c_uint32)]
     L.zgpu_gather_records_indexed_device_src.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, P(RecordRangeC), C.c_uint32, P(vp), P(sz), P(DeviceOptsC),
                                                          P(RangeResultC)]
+    L.zgpu_gather_records_batch_indexed_device_src.argtypes = [vp, vp, P(vp), P(sz), C.c_uint32, P(RecordRangeC), C.c_uint32, P(RecordBatchC),
+                                                               P(DeviceOptsC), P(RangeResultC), P(RecordBatchInfoC)]
     L.zgpu_seek_index_destroy.argtypes = [vp]
     L.zgpu_seek_index_destroy.restype = None
     L.zgpu_seek_index_entries.argtypes = [vp]
@@ -924,11 +955,13 @@ class Context:
         self._check(getattr(self.L, "zgpu_" + what)(self.h, *args, out))
         return [Seek(c) for c in out[:m]]
 
-    def _decode_call(self, what, m, args, dst_ptrs, caps, opts):
+    def _decode_call(self, what, m, args, dst_ptrs, caps, opts, batch=None, tail=()):
         """the body of every range-decode and gather call: zgpu_<what>(context, *args, destinations, capacities, options, results) gives
-        (results, seeks), m of each. args: as _seek_call takes them"""
+        (results, seeks), m of each. args: as _seek_call takes them. batch: the call's ONE destination, a RecordBatchC, in place of the m
+        destinations and capacities; tail: what the call takes behind the results"""
         res = (RangeResultC * max(m, 1))()
-        self._check(getattr(self.L, "zgpu_" + what)(self.h, *args, _ptr_array(dst_ptrs), _size_array(caps), C.byref(opts), res))
+        dest = (_ptr_array(dst_ptrs), _size_array(caps)) if batch is None else (C.byref(batch),)
+        self._check(getattr(self.L, "zgpu_" + what)(self.h, *args, *dest, C.byref(opts), res, *tail))
         return _results(res, m), [Seek(res[j].seek) for j in range(m)]
 
     def _frames_seek(self, what, src_ptrs, lens, ranges, anchors):
@@ -1125,10 +1158,65 @@ class Context:
     # the slots zgpu_debug_ranges_stats appends behind GATHER_STATS (csrc/zg_capi_int.h: kRecFindStat*)
     RECORD_STATS = ("record_find_launches", "record_find_us", "record_find_bytes_downloaded")
 
+    # and behind RECORD_STATS (csrc/zg_capi_int.h: kBatchStat*)
+    BATCH_STATS = ("batch_fill_launches", "batch_fill_us", "batch_bytes_filled", "batch_bytes_uploaded")
+
+    def gather_records_batch(self, index, src_ptrs, lens, recs, dst_ptr, cap, layout="padded", width=0, pad=0, truncate=False, lengths_ptr=0,
+                             offsets_ptr=0, hash_max=0, no_hash=False, verify=False, verify_table=False):
+        """zgpu_gather_records_batch_indexed_device_src: gather_records_indexed_device_src into ONE piece of device memory, dst_ptr of cap
+        bytes. layout "padded": row j is the width bytes at dst_ptr + j * width, its record followed by the byte `pad`; "packed": the
+        records back to back (width: 0, or with truncate the most bytes taken of one record). truncate: a record longer than width is cut to
+        width — the frames behind the cut are not decoded — where it otherwise gets E_TARGET_TOO_SMALL (padded). lengths_ptr / offsets_ptr
+        (device memory, 8-byte aligned, or 0): m lengths — 0 for a row with a status, which is all pad — and m + 1 offsets. A batch that
+        needs more than cap bytes writes nothing: every row gets E_TARGET_TOO_SMALL and info.total is the need (cap=0, dst_ptr=0: the
+        size query). Returns (results, seeks, info, record_bytes): a RecordBatchInfo and every range's byte length before truncation."""
+        n, m = len(src_ptrs), len(recs)
+        _one_per("gather_records_batch", n, lens)
+        rb, info = (C.c_uint64 * max(m, 1))(), RecordBatchInfoC()
+        batch = RecordBatchC(dst_ptr or None, int(cap), lengths_ptr or None, offsets_ptr or None, rb, int(width), _BATCH_LAYOUTS[layout],
+                             BATCH_TRUNCATE if truncate else 0, int(pad), 0)
+        res, seeks = self._decode_call("gather_records_batch_indexed_device_src", m,
+                                       (self._index_handle(index, "gather_records_batch"), _ptr_array(src_ptrs), _size_array(lens), n,
+                                        self._record_ranges(recs), m), None, None, _opts(hash_max, no_hash, verify, verify_table),
+                                       batch=batch, tail=(C.byref(info),))
+        return res, seeks, RecordBatchInfo(info), list(rb[:m])
+
+    def gather_records_batch_tensors(self, index, tensors, recs, width=None, pad=0, truncate=False, hash_max=0, no_hash=False, verify=False,
+                                     verify_table=False):
+        """gather_records_batch on torch tensors: tensors[i] is a contiguous torch.uint8 tensor on this context's device holding shard i,
+        index a SeekIndex over these shards that holds their record offsets — index once, then ONE call per step. width given: the padded
+        batch, (uint8[m, width], int64 lengths[m], results). width None: the packed batch, (uint8[total], int64 offsets[m + 1], int64
+        lengths[m], results) — one call with cap = 0 asks for the size, a second one writes. A row with a status is all `pad` and has
+        length 0. torch is imported here, not by `import zgpu`."""
+        import torch
+        self._tensor_check(tensors, "gather_records_batch_tensors")
+        ptrs, lens = [t.data_ptr() if t.numel() else 0 for t in tensors], [t.numel() for t in tensors]
+        m, dev = len(recs), torch.device("cuda", self.device)
+        opts = dict(pad=pad, truncate=truncate, hash_max=hash_max, no_hash=no_hash, verify=verify, verify_table=verify_table)
+        if width is None:
+            if truncate:
+                raise ValueError("gather_records_batch_tensors: truncate needs a width")
+            total = self.gather_records_batch(index, ptrs, lens, recs, 0, 0, layout="packed", **opts)[2].total
+            layout, shape = "packed", (total,)
+        else:
+            total, layout, shape = m * int(width), "padded", (m, int(width))
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        lengths, offsets = torch.empty(max(m, 1), dtype=torch.int64, device=dev), torch.empty(m + 1, dtype=torch.int64, device=dev)
+        self._torch_sync()   # (the caching allocator may hand out memory that is still in use on torch's stream)
+        res, _, info, _ = self.gather_records_batch(index, ptrs, lens, recs, buf.data_ptr() if total else 0, total, layout=layout,
+                                                    width=width or 0, lengths_ptr=lengths.data_ptr() if m else 0,
+                                                    offsets_ptr=offsets.data_ptr(), **opts)
+        if info.total != total:
+            raise RuntimeError("gather_records_batch_tensors: the index changed between the size query and the gather")
+        if width is None:
+            return buf[:total], offsets, lengths[:m], res
+        return buf[:total].view(shape), lengths[:m], res
+
     def gather_records_stats(self):
         """gather_ranges_stats of the last call plus the slots of the record lookup (out[19] ...): record_find_launches, record_find_us (HIP
-        events), record_find_bytes_downloaded (24 per range)."""
-        keys = _STATS["Context.ranges_stats"][2] + self.GATHER_STATS + self.RECORD_STATS
+        events), record_find_bytes_downloaded (24 per range); and of a record batch's finish (out[22] ...): batch_fill_launches,
+        batch_fill_us (HIP events), batch_bytes_filled, batch_bytes_uploaded (into the lengths and offsets arrays)."""
+        keys = _STATS["Context.ranges_stats"][2] + self.GATHER_STATS + self.RECORD_STATS + self.BATCH_STATS
         a = (C.c_uint64 * len(keys))()
         k = self.L.zgpu_debug_ranges_stats(self.h, a, len(keys))
         return dict(zip(keys[:k], a[:k]))
