@@ -233,6 +233,15 @@ int zgpu_debug_frames_device_stats(const zgpu_ctx*, uint64_t* out, int n);
 int zgpu_debug_hash_ranges(zgpu_ctx*, const void* device_base, const uint64_t* offs, const uint64_t* lens, uint32_t n, int kernel,
                            uint64_t* digests);
 uint64_t zgpu_debug_hash_ranges_us(const zgpu_ctx*);
+/* tests: ONE of the primitives the kernel bodies are written against (zstd-rs_amd/csrc/zg_zxprobe.h names them: op, the operand words in[8 t ..]
+ * of thread t, the result words out[4 t ..]) on one workgroup of `threads` threads, so that the CPU emulator the suites run those bodies on can be
+ * held against the hardware. out[] goes up as the caller filled it and comes back with the words the threads wrote; arena_in goes up as the
+ * kernel's memory arena and comes back whole in arena_out. The buffer resource is [res_off, res_off + res_bytes) of the arena, or with flags = 1
+ * (res_off = res_bytes = 0) a resource of 0 bytes over a null base. Refused with ZGPU_E_BAD_ARG before any HIP call: threads other than 64 or
+ * 256; an arena below 512 bytes, above 1 MiB or no multiple of 16; a resource with less than 256 bytes of arena on either side; a buffer offset
+ * at or above 0x80000040; an index of a global store, load or atomic outside the arena or misaligned for its width; an LDS word >= 64. */
+int zgpu_debug_zx_probe(zgpu_ctx*, uint32_t op, uint32_t threads, uint32_t flags, uint32_t res_off, uint32_t res_bytes, const uint32_t* in,
+                        uint32_t* out, const uint8_t* arena_in, uint8_t* arena_out, uint32_t arena_bytes);
 
 /* ---- the same, with the compressed input in device memory too ------------------------------------------------------------------
  * For callers whose compressed bytes are in HBM already (a GPUDirect / RDMA read, a torch tensor loaded from a sharded checkpoint, the output of

@@ -17,24 +17,6 @@
 #include "zg_emu_fill.h"
 #include "../../zstd-rs_amd/csrc/zg_host_parse.h"
 
-// ---- the primitives zg_simt.h does not have ------------------------------------------------------------------------------------------------
-// inclusive sum over the wave, lane order (zg_kernels.hip: six DPP steps); every lane of the wave calls it
-static inline uint32_t zx_scan_incl_add(uint32_t v) {
-  simt::Machine* m = simt::M();
-  const uint32_t me = m->cur, w0 = me & ~63u;
-  m->slot[me] = v;
-  simt::yield(simt::WAVE_WAIT);
-  uint32_t r = 0;
-  for (uint32_t l = w0; l <= me; l++) r += (uint32_t)m->slot[l];
-  simt::yield(simt::WAVE_WAIT);
-  return r;
-}
-static inline ZxU4 zx_ld128(const ZxBuf& b, uint32_t off) {
-  ZX_ALIGNED(off, 4);
-  ZxU4 r;
-  r.x = zx__dw(b, off); r.y = zx__dw(b, (uint64_t)off + 4); r.z = zx__dw(b, (uint64_t)off + 8); r.w = zx__dw(b, (uint64_t)off + 12);
-  return r;
-}
 // the bitstream reader: counts[0] loads, [1] dwords served from outside [g_lo, g_hi), [2] dwords asked for that the resource refused (they
 // read as 0: the second or third dword of a load near the stream's end), [3] those of them that were the FIRST dword of their load — the
 // dword that holds bit q_ll, which lies inside the stream for every sequence zg_k_seq recorded

@@ -961,6 +961,30 @@ extern "C" int zgpu_debug_hash_ranges(zgpu_ctx* c, const void* device_base, cons
 }
 extern "C" uint64_t zgpu_debug_hash_ranges_us(const zgpu_ctx* c) { return c ? c->hash_ranges_us : 0; }
 
+// ---- one zx_* primitive on one workgroup (zg_zxprobe.h; tests/test_gpu_zxprobe.py) ----------------------------------------------------------
+// Everything an operand could lead outside the three allocations with is refused by zxp::args_ok before the first HIP call. Then: allocate,
+// upload, ONE launch on the context's stream, synchronise, download the results and the whole arena, free.
+extern "C" int zgpu_debug_zx_probe(zgpu_ctx* c, uint32_t op, uint32_t threads, uint32_t flags, uint32_t res_off, uint32_t res_bytes, const uint32_t* in,
+                                   uint32_t* out, const uint8_t* arena_in, uint8_t* arena_out, uint32_t arena_bytes) {
+  if (!c || !in || !out || !arena_in || !arena_out || !zxp::args_ok(op, threads, flags, res_off, res_bytes, in, arena_bytes)) return ZGPU_E_BAD_ARG;
+  if (hipSetDevice(c->eng->device()) != hipSuccess) { (void)hipGetLastError(); return ZGPU_E_HIP; }
+  const size_t in_bytes = (size_t)threads * zxp::kIn * 4, out_bytes = (size_t)threads * zxp::kOut * 4;
+  void *d_in = nullptr, *d_out = nullptr, *d_arena = nullptr;
+  hipStream_t s = c->eng->stream();
+  bool ok = hipMalloc(&d_in, in_bytes) == hipSuccess && hipMalloc(&d_out, out_bytes) == hipSuccess && hipMalloc(&d_arena, arena_bytes) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+       hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+       hipMemcpyAsync(d_arena, arena_in, arena_bytes, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  if (ok) {
+    zg_launch_zxprobe(op, threads, flags, (const uint32_t*)d_in, (uint32_t*)d_out, (uint8_t*)d_arena, res_off, res_bytes, s);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  }
+  ok = ok && hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(arena_out, d_arena, arena_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); c->eng->last_error = "zgpu_debug_zx_probe: a HIP call failed"; }
+  (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_arena);
+  return ok ? ZGPU_OK : ZGPU_E_HIP;
+}
+
 // ---- what device-resident entries hold, from their headers alone (zg_index.h) --------------------------------------------------------------
 // The stop reasons of the chain are public under the values the lanes use.
 static_assert(ZGPU_CHAIN_END == zgw::kEnd && ZGPU_CHAIN_SHORT_HEADER == zgw::kShortHeader && ZGPU_CHAIN_BAD_MAGIC == zgw::kBadMagic &&

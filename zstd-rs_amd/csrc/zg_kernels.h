@@ -14,6 +14,7 @@
 #include "zg_seekmany.h"
 #include "zg_seekidx.h"
 #include "zg_records.h"
+#include "zg_zxprobe.h"
 
 // one launch of zg_k_sweep
 // zg_k_sweep: threads per workgroup, groups of 4 output bytes a thread has in flight; a workgroup takes ZG_SW_BATCH bytes of a unit.
@@ -111,3 +112,6 @@ void zg_launch_recs_emit(const uint8_t* out, const zgr::Chunk* chunks, uint32_t 
 void zg_launch_recs_find(const zgr::Find* lanes, uint32_t m, const uint64_t* recs, zgr::Found* out, hipStream_t s);
 // zg_k_fill (zg_scatter.h): `byte` into the chunks of the regions segs[] (src_off unused), one wave per chunk
 void zg_launch_fill(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, uint32_t byte, hipStream_t s);
+// zg_k_zxprobe (zg_zxprobe.h): ONE zx_* primitive on one workgroup of `threads` (64 or 256) threads; in, out, arena: device memory whose
+// every operand-named index the caller checked with zxp::args_ok
+void zg_launch_zxprobe(uint32_t op, uint32_t threads, uint32_t flags, const uint32_t* in, uint32_t* out, uint8_t* arena, uint32_t res_off, uint32_t res_bytes, hipStream_t s);

@@ -2309,3 +2309,14 @@ __global__ void __launch_bounds__(zgs::kFillThreads) zg_k_fill(const zgs::Seg* s
 void zg_launch_fill(const zgs::Seg* segs, const zgs::Chunk* chunks, uint32_t nchunks, uint32_t byte, hipStream_t s) {
   if (nchunks) hipLaunchKernelGGL(zg_k_fill, dim3(nchunks < zgs::kFillMaxGroups ? nchunks : zgs::kFillMaxGroups), dim3(zgs::kFillThreads), 0, s, segs, chunks, nchunks, byte);
 }
+
+// The zx_* primitives above, one per launch (zg_zxprobe.h: what a launch does, and the argument rules the host checks in front of it): ONE
+// workgroup of 64 or 256 threads, results by plain vector stores. Behind everything else: it is no part of any submit (zgpu_debug_zx_probe).
+#include "zg_zxprobe.h"
+__global__ void __launch_bounds__(256) zg_k_zxprobe(uint32_t op, uint32_t flags, const uint32_t* in, uint32_t* out, uint8_t* arena, uint32_t res_off, uint32_t res_bytes) {
+  __shared__ zxp::Lds s_l;
+  zxp::probe(op, flags, in, out, arena, res_off, res_bytes, s_l);
+}
+void zg_launch_zxprobe(uint32_t op, uint32_t threads, uint32_t flags, const uint32_t* in, uint32_t* out, uint8_t* arena, uint32_t res_off, uint32_t res_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(zg_k_zxprobe, dim3(1), dim3(threads), 0, s, op, flags, in, out, arena, res_off, res_bytes);
+}

@@ -438,7 +438,7 @@ EXPORTS = [
     "zgpu_frames_seek_device", "zgpu_decode_ranges_device_src", "zgpu_debug_ranges_stats",
     "zgpu_frames_index_device", "zgpu_frames_table_device", "zgpu_debug_frames_index_stats",
     "zgpu_decode_frames_device_src", "zgpu_debug_frames_device_src_stats",
-    "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats", "zgpu_debug_hash_ranges", "zgpu_debug_hash_ranges_us",
+    "zgpu_decode_frames_device", "zgpu_debug_frames_device_stats", "zgpu_debug_hash_ranges", "zgpu_debug_hash_ranges_us", "zgpu_debug_zx_probe",
     "zgpu_set_frames_shared_dicts", "zgpu_frames_shared_dicts", "zgpu_debug_frames_dict_stats",
     "zgpu_decode_frames", "zgpu_batch_checksums", "zgpu_plaintext_bound", "zgpu_debug_frames_submits",
     "zgpu_ctx_create", "zgpu_ctx_destroy", "zgpu_set_max_window_size", "zgpu_max_window_size", "zgpu_last_error", "zgpu_status_name",
@@ -509,6 +509,7 @@ def _declare(L):
     L.zgpu_debug_hash_ranges.argtypes = [vp, vp, P(C.c_uint64), P(C.c_uint64), C.c_uint32, C.c_int, P(C.c_uint64)]
     L.zgpu_debug_hash_ranges_us.argtypes = [vp]
     L.zgpu_debug_hash_ranges_us.restype = C.c_uint64
+    L.zgpu_debug_zx_probe.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32), vp, vp, C.c_uint32]
     L.zgpu_decode_frames_device_src.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(vp), P(sz), P(DeviceOptsC), P(DeviceEntryResultC)]
     L.zgpu_debug_frames_device_src_stats.argtypes = [vp, P(C.c_uint64), C.c_int]
     L.zgpu_frames_index_device.argtypes = [vp, P(vp), P(sz), C.c_uint32, P(EntryIndexC)]
@@ -885,6 +886,15 @@ class Context:
 
     def hash_ranges_us(self):
         return int(self.L.zgpu_debug_hash_ranges_us(self.h))
+
+    def zx_probe(self, op, threads, flags, res_off, res_bytes, in_words, out_words, arena):
+        """zgpu_debug_zx_probe: one zx_* primitive (zg_zxprobe.h) on one workgroup. in_words: 8 per thread, out_words: 4 per thread as they go up,
+        arena: bytes. Returns (the result words, the arena afterwards, the operand words as the call left them)."""
+        a, o = (C.c_uint32 * len(in_words))(*in_words), (C.c_uint32 * len(out_words))(*out_words)
+        src, dst = C.create_string_buffer(bytes(arena), len(arena)), C.create_string_buffer(len(arena))
+        self._check(self.L.zgpu_debug_zx_probe(self.h, op, threads, flags, res_off, res_bytes, a, o, src, dst, len(arena)), "zgpu_debug_zx_probe")
+        assert src.raw == bytes(arena)
+        return list(o), dst.raw, list(a)
 
     def decode_frames_device_src(self, src_ptrs, lens, dst_ptrs, caps, hash_max=0, no_hash=False, verify=False):
         """zgpu_decode_frames_device_src: decode_frames_device with the compressed input in DEVICE memory too. src_ptrs[i] is the address of
